@@ -2,7 +2,7 @@
 """Headline benchmark: clips/s of the full AV hot path (static CNN + LSTM + audio model + fusion) on synthetic
 clips of 16 x 224x224 frames + 2 s @ 16 kHz (BASELINE.json metric), one process per GPU.
 
-    python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,8 +10,14 @@ A step = one pass of the hot path over one batch of `--clips` clips per GPU (wea
 config 5 at 8 GPUs; the static CNN runs in passes of up to 1024 frames).  Inputs are resident in HBM before
 the timed region.  Rank 0 prints ONE JSON line.  The headline `value` is measured in a parity-green arithmetic mode
 (--mode x3, default: f16 MFMA on fp16 hi/lo operand pairs with f32 accumulation, f32-grade: probabilities within 1e-4 of
-the CPU oracle at every head sharpness tested; --mode fp32: exact f32 MFMA); the other modes are measured next to it under
-"modes", each with ITS measured max |dprob| (plain bf16 does not meet the 1e-4 gate and is never the headline).
+the CPU oracle at every head sharpness tested; --mode fp32: exact f32 MFMA).
+
+A plain run sets up, warms up, times exactly `--steps` steps and prints the line (`ms_per_step` = one timed step); with
+`--dump-outputs DIR` it also writes what the last timed step returned (dump_outputs).  `--full` adds everything else, each
+after the timed region: the serial evented pass behind `roofline`, the other arithmetic modes under "modes" (each with ITS
+measured max |dprob|; plain bf16 does not meet the 1e-4 gate and is never the headline), the multi-rank check, BASELINE
+configs 2 and 3, per-call latency, `configs.run_inference`, the measured ceilings of the GPU, the CPU baseline and the oracle
+parity.  The --no-* switches below leave out single legs of a --full run.
 """
 from __future__ import annotations
 
@@ -64,6 +70,7 @@ KERNEL = {"fp32": "all MFMA launches of a step: conv_gemm_kernel<0,0,*>",
                 "stem_pool_u8_kernel, conv_gemm_skinny_kernel<*> (launches of few positions: the LSTM steps) -- see roofline.per_family"}
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.2-6.3 TB/s measured for a streaming copy)
 FAMILY_BOUND = {"bneck_kernel": "hbm"}  # every other family is priced against the MFMA peak
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
 
 
 def log(msg):
@@ -146,7 +153,13 @@ def parse():
     ap.add_argument("--one-lane", action="store_true", help="A/B: avcer_set_static_lanes(1) -- every static-CNN call on one stream")
     ap.add_argument("--no-events", action="store_true", help="skip the separate evented pass (the roofline object is then empty)")
     ap.add_argument("--no-run-inference", action="store_true", help="skip configs.run_inference (one 30 s video through run.py)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run every measurement and check beyond the headline (roofline pass, "
+                                                         "other modes, configs, CPU baseline, parity, ceilings, multi-rank check)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the arrays the last timed step returned to DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def make_inputs(n_clips, rank, device):
@@ -174,7 +187,7 @@ def timed(pipe, frames, wav, n_total, steps, warmup, device, profile):
     WITHOUT any per-launch instrumentation.  When `profile` is set, a second pass of the same `steps` steps follows, outside
     the timed region, strictly serial (one stream) and with a HIP-event pair around every MFMA-kernel launch: the roofline
     figure comes from that pass, so the measurement does not sit inside the thing measured and co-running kernels of the
-    overlapped audio branch cannot inflate per-launch durations."""
+    overlapped audio branch cannot inflate per-launch durations.  Also returns what the last timed step returned (`last`)."""
     for _ in range(warmup):
         one_step(pipe, frames, wav, n_total)
     torch.cuda.synchronize(device)
@@ -183,7 +196,7 @@ def timed(pipe, frames, wav, n_total, steps, warmup, device, profile):
     torch.cuda.synchronize(device)
     t0 = time.perf_counter()
     for _ in range(steps):
-        one_step(pipe, frames, wav, n_total)
+        last = one_step(pipe, frames, wav, n_total)
     torch.cuda.synchronize(device)
     own = time.perf_counter() - t0  # this rank's K steps, before it waits for the others
     if dist.is_initialized():
@@ -222,7 +235,26 @@ def timed(pipe, frames, wav, n_total, steps, warmup, device, profile):
         kern_ms, launches = sum(v[0] for v in fams.values()), sum(v[1] for v in fams.values())
         pipe.engine.profile_enable(False)
         pipe.overlap_branches = overlap
-    return dt, kern_ms, launches, serial_dt, per_rank, fams
+    return dt, kern_ms, launches, serial_dt, per_rank, fams, last
+
+
+def dump_outputs(path, prob, am, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the arrays one_step returns to its caller, from the last timed step -- the compound probabilities
+    [4, clips, 16, 7] (float64, as the library computes them) and the compound argmax [4, clips, 16] (as float32) -- one
+    DIR/<name>.npy each.  The inputs and weights are pure functions of their seeds, so two builds run with the same arguments
+    can be compared array for array.  Above `limit` bytes in all, a fixed seeded sample of clips is written instead, with
+    their indices as clip_index.npy.  Returns the names written."""
+    arrays = {"compound_prob": prob.cpu().numpy().astype(np.float64), "compound_argmax": am.cpu().numpy().astype(np.float32)}
+    n = arrays["compound_prob"].shape[1]
+    per_clip = sum(a.nbytes for a in arrays.values()) // n + 8
+    if per_clip * n > limit - 4096:  # 4 KiB: the .npy headers
+        keep = np.sort(np.random.default_rng(0).choice(n, (limit - 4096) // per_clip, replace=False))
+        arrays = {k: a[:, keep] for k, a in arrays.items()}
+        arrays["clip_index"] = keep.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
 
 
 def verify_ranks(pipe, frames, wav, n_total, clips, world, rank, device, check=8):
@@ -650,7 +682,7 @@ def main():
     from avcer_amd.pipeline import AVPipeline
 
     modes = {"fp32": MODE_FP32, "bf16": MODE_BF16, "x3": MODE_F16X3}
-    pk, pk_src = peaks()
+    pk, pk_src = peaks() if args.full else (None, None)
     torch.set_num_threads(min(usable_cores(), 16))
     log(f"rank {rank}/{world}: building pipeline (synthetic weights, seed 42)")
     pipe = AVPipeline(device=local_rank, seed=42, mode=modes[args.mode])
@@ -668,8 +700,13 @@ def main():
     def measure(name, steps, warmup):
         set_mode(name)
         log(f"timing {name}: {warmup} warm-up + {steps} steps of {args.clips} clips/GPU")
-        dt, kern_ms, launches, serial_dt, per_rank, fams = timed(pipe, frames, wav, n_total, steps, warmup, device,
-                                                                   profile=not args.no_events)
+        dt, kern_ms, launches, serial_dt, per_rank, fams, last = timed(pipe, frames, wav, n_total, steps, warmup, device,
+                                                                         profile=args.full and not args.no_events)
+        res = {"clips_per_s": n_total * steps / dt, "ms_per_step": dt / steps * 1e3, "per_rank_s": per_rank, "last": last,
+               "roofline": None}
+        log(f"{name}: {res['clips_per_s']:.1f} clips/s, {res['ms_per_step']:.1f} ms/step")
+        if not args.full:
+            return res
         per_family = None
         if fams:
             # each family against the roof that bounds it: the fused chains of ResNet stages 1-2 move 2.5-5 KB per position
@@ -692,40 +729,42 @@ def main():
         flops_gemm = GFLOP_CLIP_GEMM * 1e9 * args.clips * steps  # algorithmic FLOPs this rank pushed through the MFMA kernels
         ach = flops_gemm / (kern_ms * 1e-3) / 1e12 if kern_ms else None
         traffic, traffic_src, stamp = pmc_traffic(name, args.clips)
-        res = {
-            "clips_per_s": n_total * steps / dt,
-            "ms_per_step": dt / steps * 1e3,
-            "per_rank_s": per_rank,
-            "roofline": {
-                "bound": "mfma", "kernel": KERNEL[name], "achieved": ach, "peak": pk[name], "unit": "TFLOP/s",
-                "frac": ach / pk[name] if ach else None, "peak_source": pk_src,
-                "traffic": traffic, "traffic_unit": "HBM bytes per launch",
-                "traffic_source": traffic_src, "traffic_stamp": stamp,
-                "mfma_products_per_algorithmic_product": MFMA_PASSES[name],
-                "frac_of_peak_executed": ach * MFMA_PASSES[name] / pk[name] if ach else None,
-                "launches_per_step": launches / steps if steps else 0,
-                "avg_launch_us": kern_ms * 1e3 / launches if launches else None,
-                "alg_gflop_per_launch": flops_gemm / launches / 1e9 if launches else None,
-                "kernel_time_share": kern_ms * 1e-3 / serial_dt if serial_dt else None,
-                "measured_in": f"a separate serial pass of the same {steps} steps (one stream, a HIP-event pair around every "
-                               "MFMA-kernel launch) run right after the timed region; the timed region itself carries no "
-                               "events" + ("" if args.no_overlap else " and runs the audio branch on a second HIP stream"),
-                "serial_evented_ms_per_step": serial_dt / steps * 1e3 if serial_dt else None,
-                "per_family": per_family,
-                "per_family_note": "same evented pass; compulsory_gb_per_s = every operand read once + every output written once "
-                                   "(4 bytes per sp32 element) / event time; frac of a family = achieved / peak of ITS bound",
-            },
+        res["roofline"] = {
+            "bound": "mfma", "kernel": KERNEL[name], "achieved": ach, "peak": pk[name], "unit": "TFLOP/s",
+            "frac": ach / pk[name] if ach else None, "peak_source": pk_src,
+            "traffic": traffic, "traffic_unit": "HBM bytes per launch",
+            "traffic_source": traffic_src, "traffic_stamp": stamp,
+            "mfma_products_per_algorithmic_product": MFMA_PASSES[name],
+            "frac_of_peak_executed": ach * MFMA_PASSES[name] / pk[name] if ach else None,
+            "launches_per_step": launches / steps if steps else 0,
+            "avg_launch_us": kern_ms * 1e3 / launches if launches else None,
+            "alg_gflop_per_launch": flops_gemm / launches / 1e9 if launches else None,
+            "kernel_time_share": kern_ms * 1e-3 / serial_dt if serial_dt else None,
+            "measured_in": f"a separate serial pass of the same {steps} steps (one stream, a HIP-event pair around every "
+                           "MFMA-kernel launch) run right after the timed region; the timed region itself carries no "
+                           "events" + ("" if args.no_overlap else " and runs the audio branch on a second HIP stream"),
+            "serial_evented_ms_per_step": serial_dt / steps * 1e3 if serial_dt else None,
+            "per_family": per_family,
+            "per_family_note": "same evented pass; compulsory_gb_per_s = every operand read once + every output written once "
+                               "(4 bytes per sp32 element) / event time; frac of a family = achieved / peak of ITS bound",
         }
-        log(f"{name}: {res['clips_per_s']:.1f} clips/s, {res['ms_per_step']:.1f} ms/step")
         return res
 
     head = measure(args.mode, args.steps, args.warmup)
-    rank_check = verify_ranks(pipe, frames, wav, n_total, args.clips, world, rank, device) if world > 1 else None
-    others = {} if args.no_secondary else {m: measure(m, args.steps, args.warmup) for m in modes if m != args.mode}
+    last = head.pop("last")
+    if args.dump_outputs and rank == 0:  # after the all-gather every rank holds the same outputs
+        names = dump_outputs(args.dump_outputs, *last)
+        log(f"wrote {', '.join(n + '.npy' for n in names)} to {args.dump_outputs}")
+    del last
+    full = args.full
+    rank_check = verify_ranks(pipe, frames, wav, n_total, args.clips, world, rank, device) if full and world > 1 else None
+    others = {} if args.no_secondary or not full else {m: measure(m, args.steps, args.warmup) for m in modes if m != args.mode}
+    for res in others.values():
+        del res["last"]
 
     if rank == 0:
-        cfgs = None if args.no_configs else config_benches(pipe, modes, pk, device)
-        do_cpu = not args.no_cpu
+        cfgs = None if args.no_configs or not full else config_benches(pipe, modes, pk, device)
+        do_cpu = full and not args.no_cpu
         gpu_by_mode = {}
         if do_cpu:  # GPU outputs of every measured mode on the parity clips (the first clips of the CPU sample)
             pf, pw = cpu_sample(args.cpu_clips)
@@ -737,16 +776,17 @@ def main():
         base, par = cpu_baseline(args.cpu_clips, gpu_by_mode, args.parity_clips, timed=world == 1) if do_cpu else (None, {})
         dprob, same = par.get(args.mode, (None, None))
         props = torch.cuda.get_device_properties(device)
-        try:
-            meas_mfma, meas_copy = pipe.engine.measure_ceilings()
-        except Exception as exc:  # a diagnostic: never lose the bench line over it
-            log(f"measure_ceilings failed: {exc}")
-            meas_mfma = meas_copy = None
+        meas_mfma = meas_copy = None
+        if full:
+            try:
+                meas_mfma, meas_copy = pipe.engine.measure_ceilings()
+            except Exception as exc:  # a diagnostic: never lose the bench line over it
+                log(f"measure_ceilings failed: {exc}")
         out = {
             "metric": "clips/sec (224x224x16f + 2s@16kHz), full AV path: static CNN + LSTM + wav2vec2 audio model + fusion",
             "value": head["clips_per_s"], "unit": "clips/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": DTYPE[args.mode], "data": "synthetic",
+            "dtype": DTYPE[args.mode], "data": "synthetic", "full": full,
             "config": {"workload": "full AV clips (BASELINE configs[3]/[4]): 16 u8 224x224 RGB face tiles + 32000 f32 "
                                    "samples per clip, synthetic weights (ResNet-50 + LSTM + wav2vec2-large-robust-12 "
                                    "ExprModelV3)", "clips_per_gpu": args.clips, "global_clips": n_total,

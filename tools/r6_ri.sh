@@ -5,7 +5,7 @@ O=gpurun_out/${1:-r6e}
 mkdir -p "$O"
 timeout -k 10 300 python3 -m pytest tests/test_gpu_face.py tests/test_gpu_retina.py tests/test_gpu_run.py tests/test_gpu_dropin.py -q -x > "$O/pytest.txt" 2>&1; tail -3 "$O/pytest.txt"
 timeout -k 10 200 python3 tools/face_run.py 3 fam 2>&1 | grep -v amdgpu.ids | tee "$O/face_families.txt"
-timeout -k 10 400 python3 bench.py --steps 3 --warmup 2 --no-secondary --no-cpu > "$O/bench_ri.json" 2> "$O/bench_ri.err"
+timeout -k 10 400 python3 bench.py --full --steps 3 --warmup 2 --no-secondary --no-cpu > "$O/bench_ri.json" 2> "$O/bench_ri.err"
 python3 - "$O/bench_ri.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
