@@ -32,7 +32,7 @@ class ConvDesc(C.Structure):
     ]
 
 
-ABI_VERSION = 4          # include/avcer_hip.h AVCER_ABI_VERSION: struct layouts, argument lists and buffer sizes below
+ABI_VERSION = 5          # include/avcer_hip.h AVCER_ABI_VERSION: struct layouts, argument lists and buffer sizes below
 SPLIT_TRAILER = 256      # include/avcer_hip.h AVCER_SPLIT_TRAILER: bytes behind a split weight matrix (its scale)
 
 # name -> (restype, argtypes); exactly the symbols include/avcer_hip.h declares
@@ -75,6 +75,12 @@ SIGNATURES = {
                                     C.c_void_p, C.POINTER(C.c_int64)]),
     "avcer_lsap": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "avcer_crop_tiles": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                   C.c_void_p, c_stream]),
+    "avcer_static_forward_cam": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, c_stream]),
+    "avcer_crop_resize_linear": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                           C.c_int, C.c_void_p, c_stream]),
+    "avcer_cam_render": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double,
                                    C.c_void_p, c_stream]),
     "avcer_fuse": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                              C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_stream]),

@@ -1,0 +1,160 @@
+// Grad-CAM overlays (get_prob_video.py:137-155, data/utils.py:92-112, visualization/visualize.py:218-253): the face crop
+// resized as cv2 resizes u8 images, and the heat map rendered and blended onto it.  The maps themselves come out of the static
+// CNN (avcer_static_forward_cam, kernels.hip cam_grad_kernel / cam_map_kernel).
+//
+// Both kernels restate host statements pixel for pixel (avcer_amd/heatmaps.py holds the numpy form the tests compare with), so
+// products and sums are rounded one by one, as the x86-64 code they restate does: no FMA contraction in this file.
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// One axis of cv2's INTER_LINEAR table (resize.cpp, resizeGeneric_ set-up): the source position of destination index d at
+// scale s = src / dst with half-pixel centres, clamped at both borders (weight 0 on the outer tap).
+struct LinTap {
+    int i0, i1;
+    float f;  // weight of i1
+};
+__device__ __forceinline__ LinTap lin_tap(int d, double scale, int ssize) {
+    float fx = (float)((d + 0.5) * scale - 0.5);
+    int sx = (int)floorf(fx);
+    fx -= (float)sx;
+    if (sx < 0) { sx = 0; fx = 0.f; }
+    if (sx >= ssize - 1) { sx = ssize - 1; fx = 0.f; }
+    return {sx, min(sx + 1, ssize - 1), fx};
+}
+
+// cv2.resize(crop, (out_w, out_h)) with INTER_LINEAR on u8: 11-bit fixed-point weights (saturate_cast<short>(w * 2048), round to
+// nearest even), an exact integer horizontal pass, and the vertical pass as OpenCV's SIMD rows compute it on x86-64
+// (VResizeLinearVec_32s8u: (((S0 >> 4) * b0) >> 16) + (((S1 >> 4) * b1) >> 16), + 2, >> 2).  A rect of the output's size is
+// copied.  One thread per output pixel; a rect that is empty or leaves its frame yields zeros.
+__global__ void crop_resize_linear_kernel(const uint8_t* __restrict__ frames, int T, int H, int W, const int32_t* __restrict__ rects,
+                                          int n, int swap_rb, int oh, int ow, uint8_t* __restrict__ out) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)n * oh * ow) return;
+    const int x = idx % ow, y = (idx / ow) % oh;
+    const long t = idx / ((long)ow * oh);
+    const int32_t* r = rects + 5 * t;
+    const int f = r[0], x0 = r[1], y0 = r[2], cw = r[3] - r[1], ch = r[4] - r[2];
+    uint8_t* o = out + idx * 3;
+    const bool ok = f >= 0 && f < T && x0 >= 0 && y0 >= 0 && cw > 0 && ch > 0 && x0 + cw <= W && y0 + ch <= H;
+    if (!ok) {
+        o[0] = o[1] = o[2] = 0;
+        return;
+    }
+    const uint8_t* img = frames + (long)f * H * W * 3;
+    int v[3];
+    if (cw == ow && ch == oh) {
+        const uint8_t* s = img + ((long)(y0 + y) * W + x0 + x) * 3;
+        v[0] = s[0]; v[1] = s[1]; v[2] = s[2];
+    } else {
+        const LinTap tx = lin_tap(x, (double)1.0 / ((double)ow / cw), cw);
+        const LinTap ty = lin_tap(y, (double)1.0 / ((double)oh / ch), ch);
+        const int a0 = __float2int_rn((1.f - tx.f) * 2048.f), a1 = __float2int_rn(tx.f * 2048.f);
+        const int b0 = __float2int_rn((1.f - ty.f) * 2048.f), b1 = __float2int_rn(ty.f * 2048.f);
+        const uint8_t* r0 = img + ((long)(y0 + ty.i0) * W + x0) * 3;
+        const uint8_t* r1 = img + ((long)(y0 + ty.i1) * W + x0) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int s0 = r0[tx.i0 * 3 + c] * a0 + r0[tx.i1 * 3 + c] * a1;
+            const int s1 = r1[tx.i0 * 3 + c] * a0 + r1[tx.i1 * 3 + c] * a1;
+            const int q = ((((s0 >> 4) * b0) >> 16) + (((s1 >> 4) * b1) >> 16) + 2) >> 2;
+            v[c] = min(max(q, 0), 255);
+        }
+    }
+    o[0] = (uint8_t)(swap_rb ? v[2] : v[0]);
+    o[1] = (uint8_t)v[1];
+    o[2] = (uint8_t)(swap_rb ? v[0] : v[2]);
+}
+
+// One overlay of 224 x 224 per block (256 threads).  Map m = cam[rows[i], cls[i]] (7 x 7): max(m, 0) / max (0 / 0 = NaN when no
+// value is positive), cv2's INTER_LINEAR on f32 to 224 x 224 (scale 1/32: horizontal pass, then vertical, each a * w0 + b * w1),
+// u8(255 * mask) by truncation (NaN -> 0, numpy's cast on x86-64), the colour table, then
+//   cam = (1 - image_weight) * lut / 255 + image_weight * base / 255,  out = u8(255 * cam / max(cam))
+// all in f32, one rounding per operation.
+__device__ __forceinline__ float cam_pixel(const float* m, const uint8_t* __restrict__ lut, const uint8_t* __restrict__ base, int y,
+                                           int x, int c, float wh, float wi) {
+    const LinTap tx = lin_tap(x, 7.0 / 224.0, 7), ty = lin_tap(y, 7.0 / 224.0, 7);
+    const float a0 = 1.f - tx.f, a1 = tx.f, b0 = 1.f - ty.f, b1 = ty.f;
+    const float h0 = m[ty.i0 * 7 + tx.i0] * a0 + m[ty.i0 * 7 + tx.i1] * a1;
+    const float h1 = m[ty.i1 * 7 + tx.i0] * a0 + m[ty.i1 * 7 + tx.i1] * a1;
+    const float mv = h0 * b0 + h1 * b1;
+    const float s = 255.f * mv;
+    const int q = s != s ? 0 : min(max((int)s, 0), 255);
+    const float heat = (float)lut[q * 3 + c] / 255.f;
+    const float img = (float)base[((long)y * 224 + x) * 3 + c] / 255.f;
+    return wh * heat + wi * img;
+}
+
+__global__ void __launch_bounds__(256) cam_render_kernel(const float* __restrict__ cam, const int32_t* __restrict__ rows,
+                                                         const int32_t* __restrict__ cls, const uint8_t* __restrict__ base,
+                                                         const uint8_t* __restrict__ lut, float wh, float wi,
+                                                         uint8_t* __restrict__ out) {
+    __shared__ float m[49];
+    __shared__ float red[256];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const float* src = cam + (long)rows[i] * 343 + min(max(cls[i], 0), 6) * 49;
+    if (tid < 49) m[tid] = fmaxf(src[tid], 0.f);
+    __syncthreads();
+    if (tid == 0) {
+        float mx = m[0];
+        for (int p = 1; p < 49; ++p) mx = fmaxf(mx, m[p]);
+        red[0] = mx;
+    }
+    __syncthreads();
+    const float mx = red[0];
+    __syncthreads();
+    if (tid < 49) m[tid] = m[tid] / mx;
+    __syncthreads();
+    const uint8_t* b = base + (long)i * 224 * 224 * 3;
+    float cmax = 0.f;
+    for (int e = tid; e < 224 * 224 * 3; e += 256) {
+        const int c = e % 3, x = (e / 3) % 224, y = e / (3 * 224);
+        cmax = fmaxf(cmax, cam_pixel(m, lut, b, y, x, c, wh, wi));
+    }
+    red[tid] = cmax;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] = fmaxf(red[tid], red[tid + o]);
+        __syncthreads();
+    }
+    const float top = red[0];
+    uint8_t* dst = out + (long)i * 224 * 224 * 3;
+    for (int e = tid; e < 224 * 224 * 3; e += 256) {
+        const int c = e % 3, x = (e / 3) % 224, y = e / (3 * 224);
+        const float v = cam_pixel(m, lut, b, y, x, c, wh, wi) / top;
+        dst[e] = (uint8_t)(int)(255.f * v);
+    }
+}
+
+}  // namespace
+
+extern "C" int avcer_crop_resize_linear(avcer_ctx* ctx, const uint8_t* frames, int n_frames, int h, int w, const int32_t* rects, int n,
+                                        int swap_rb, int out_h, int out_w, uint8_t* out, avcer_stream_t stream) {
+    if (!ctx) return AVCER_EINVAL;
+    if (!frames || !rects || !out || n_frames <= 0 || h <= 0 || w <= 0 || n <= 0 || out_h <= 0 || out_w <= 0 ||
+        (long)n * out_h * out_w >= (1L << 31))
+        return set_err(ctx, AVCER_EINVAL, "crop_resize_linear: bad arguments");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    crop_resize_linear_kernel<<<cdiv((long)n * out_h * out_w, 256), 256, 0, st>>>(frames, n_frames, h, w, rects, n, swap_rb ? 1 : 0,
+                                                                                  out_h, out_w, out);
+    HIP_TRY(ctx, hipGetLastError());
+    return AVCER_OK;
+}
+
+extern "C" int avcer_cam_render(avcer_ctx* ctx, const float* cam, const int32_t* rows, const int32_t* cls, const uint8_t* base_rgb,
+                                int n, const uint8_t* lut_bgr, double image_weight, uint8_t* out_bgr, avcer_stream_t stream) {
+    if (!ctx) return AVCER_EINVAL;
+    if (!cam || !rows || !cls || !base_rgb || !lut_bgr || !out_bgr || n <= 0 || !(image_weight >= 0.0 && image_weight <= 1.0))
+        return set_err(ctx, AVCER_EINVAL, "cam_render: bad arguments");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the weights as numpy applies them to f32 arrays: the Python floats (1 - image_weight) and image_weight rounded to f32
+    const float wh = (float)(1.0 - image_weight), wi = (float)image_weight;
+    cam_render_kernel<<<n, 256, 0, (hipStream_t)stream>>>(cam, rows, cls, base_rgb, lut_bgr, wh, wi, out_bgr);
+    HIP_TRY(ctx, hipGetLastError());
+    return AVCER_OK;
+}

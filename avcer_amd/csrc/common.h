@@ -144,6 +144,10 @@ int measure_ceilings(avcer_ctx* ctx, double* mfma_bf16_tflops, double* hbm_copy_
 int k_preprocess(avcer_ctx*, const uint8_t* frames, int n, int in_h, int in_w, void* out, int kind, hipStream_t);
 int k_maxpool3s2(avcer_ctx*, const void* x, void* y, int n, int h, int w, int c, int oh, int ow, int bf16, hipStream_t);
 int k_avgpool_hw(avcer_ctx*, const void* x, float* y, void* y_sp32, int n, int hw, int c, int kind, hipStream_t);
+// Grad-CAM of layer 4 for all 7 classes (kernels.hip): x = layer 4's output [n,7,7,2048] in storage `kind`, probs [n,7],
+// h = fc1's pre-ReLU output [n,512], w1 = fc1.w [512,2048], w2 = fc2.w [7,512], g = scratch f32 [n,7,2048] -> cam f32 [n,7,49]
+int k_cam_maps(avcer_ctx*, const void* x, const float* probs, const float* h, const float* w1, const float* w2, float* g,
+               float* cam, int n, int kind, hipStream_t);
 int k_small_linear(avcer_ctx*, const float* x, const float* w, const float* b, float* logits, float* probs, int m,
                    int k, int n, int relu_in, hipStream_t);
 int k_lstm_cell(avcer_ctx*, const float* xproj, int64_t xproj_ld, const float* hproj, float* c, float* h_out, void* h_sp,

@@ -740,6 +740,93 @@ __global__ void avgpool_kernel(const T* __restrict__ x, float* __restrict__ y, s
     if (ysp) st8<sp32_t>(ysp, b * c + cc, s, ovf);
 }
 
+// Grad-CAM of layer 4 (get_prob_video.py:137-149, data/utils.py:92-100) in closed form.  Above layer 4 the network is
+// avgpool -> fc1 -> ReLU -> fc2 -> softmax, so d p_k / d A[c,y,x] is the same at all 49 positions:
+//   s = p_k (e_k - p),  u = 1[h > 0] * (W2^T s),  g_k = (1/49) W1^T u            (cam_grad_kernel, all 7 classes)
+//   cam[k,y,x] = mean_c g_k[c] * A[c,y,x]                                         (cam_map_kernel)
+// f32 arithmetic in every mode.  cam_grad_kernel: one block per CAM_FR frames x 256 channels, u of those frames' 7 classes in
+// 64-row chunks in LDS; each output row is its own sum in the same order whatever the batch, so a frame's map does not depend on
+// the frames around it.
+constexpr int CAM_FR = 2;  // 14 rows per block: 4 blocks per CU at 256 frames (8 frames per block left one wave per SIMD)
+constexpr int CAM_ROWS = CAM_FR * 7;
+constexpr int CAM_KC = 64;
+__global__ void __launch_bounds__(256) cam_grad_kernel(const float* __restrict__ probs, const float* __restrict__ h,
+                                                       const float* __restrict__ w1, const float* __restrict__ w2,
+                                                       float* __restrict__ g, int n) {
+    __shared__ float s[CAM_ROWS][8];
+    __shared__ float u[CAM_KC][CAM_ROWS];
+    const int tid = threadIdx.x;
+    const int f0 = blockIdx.x * CAM_FR;
+    const int c = blockIdx.y * 256 + tid;
+    for (int e = tid; e < CAM_ROWS * 7; e += 256) {
+        const int r = e / 7, j = e % 7, f = f0 + r / 7, k = r % 7;
+        float v = 0.f;
+        if (f < n) {
+            const float pk = probs[(long)f * 7 + k], pj = probs[(long)f * 7 + j];
+            v = pj * ((j == k ? 1.f : 0.f) - pk);   // softmax backward of e_k
+        }
+        s[r][j] = v;
+    }
+    float acc[CAM_ROWS];
+#pragma unroll
+    for (int r = 0; r < CAM_ROWS; ++r) acc[r] = 0.f;
+    for (int i0 = 0; i0 < 512; i0 += CAM_KC) {
+        __syncthreads();
+        for (int e = tid; e < CAM_KC * CAM_ROWS; e += 256) {
+            const int r = e / CAM_KC, i = i0 + e % CAM_KC, f = f0 + r / 7;
+            float v = 0.f;
+            if (f < n && h[(long)f * 512 + i] > 0.f) {
+#pragma unroll
+                for (int j = 0; j < 7; ++j) v += w2[j * 512 + i] * s[r][j];
+            }
+            u[e % CAM_KC][r] = v;
+        }
+        __syncthreads();
+        for (int i = 0; i < CAM_KC; ++i) {
+            const float w = w1[(long)(i0 + i) * 2048 + c];
+#pragma unroll
+            for (int r = 0; r < CAM_ROWS; ++r) acc[r] += u[i][r] * w;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < CAM_ROWS; ++r)
+        if (f0 + r / 7 < n) g[((long)f0 * 7 + r) * 2048 + c] = acc[r] / 49.f;
+}
+
+// cam[f,k,p] = (1/2048) sum_c g[f,k,c] * A[f,p,c] over layer 4's NHWC map in its own storage (f32 / bf16 / sp32 pairs, as
+// avgpool_kernel reads it).  One block per frame, lane l of wave w holds g of the 8 channels 512 w + 8 l for all 7 classes; per
+// position the 64 lanes reduce by butterfly, the 4 waves in a fixed order through LDS.
+template <typename T>
+__global__ void __launch_bounds__(256) cam_map_kernel(const T* __restrict__ x, const float* __restrict__ g, float* __restrict__ cam) {
+    __shared__ float part[4][7][49];
+    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int cc = wv * 512 + lane * 8;
+    float gk[7][8];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) ld8<float>(g, ((long)f * 7 + k) * 2048 + cc, gk[k]);
+    for (int p0 = 0; p0 < 49; p0 += 7) {  // seven positions requested before any is used (49 dependent round trips otherwise)
+        float a[7][8];
+#pragma unroll
+        for (int q = 0; q < 7; ++q) ld8<T>(x, ((long)f * 49 + p0 + q) * 2048 + cc, a[q]);
+#pragma unroll
+        for (int q = 0; q < 7; ++q)
+#pragma unroll
+            for (int k = 0; k < 7; ++k) {
+                float v = 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v += gk[k][j] * a[q][j];
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+                if (lane == 0) part[wv][k][p0 + q] = v;
+            }
+    }
+    __syncthreads();
+    for (int e = tid; e < 7 * 49; e += 256) {
+        const int k = e / 49, p = e % 49;
+        cam[(long)f * 343 + e] = (((part[0][k][p] + part[1][k][p]) + part[2][k][p]) + part[3][k][p]) / 2048.f;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ tiny heads
 // out[m, j] = sum_k f(x[m,k]) * w[j,k] + b[j], n <= 16 outputs; optional ReLU on the input, optional softmax.
 // video.py:131-132 (relu1 -> fc2) + get_prob_video.py:107-109 (softmax dim=1); LSTM fc (video.py:184);
@@ -1573,6 +1660,17 @@ int k_avgpool_hw(avcer_ctx* ctx, const void* x, float* y, void* y_sp32, int n, i
     else if (kind == 2) avgpool_kernel<sp32_t><<<grid, 64, 0, st>>>((const sp32_t*)x, y, ysp, n, hw, c, ctx->ovf);
     else avgpool_kernel<float><<<grid, 64, 0, st>>>((const float*)x, y, ysp, n, hw, c, ctx->ovf);
     CHECK_LAUNCH(ctx, "avgpool");
+    return AVCER_OK;
+}
+
+int k_cam_maps(avcer_ctx* ctx, const void* x, const float* probs, const float* h, const float* w1, const float* w2, float* g,
+               float* cam, int n, int kind, hipStream_t st) {
+    cam_grad_kernel<<<dim3(cdiv(n, CAM_FR), 2048 / 256), 256, 0, st>>>(probs, h, w1, w2, g, n);
+    CHECK_LAUNCH(ctx, "cam_grad");
+    if (kind == 1) cam_map_kernel<bf16_t><<<n, 256, 0, st>>>((const bf16_t*)x, g, cam);
+    else if (kind == 2) cam_map_kernel<sp32_t><<<n, 256, 0, st>>>((const sp32_t*)x, g, cam);
+    else cam_map_kernel<float><<<n, 256, 0, st>>>((const float*)x, g, cam);
+    CHECK_LAUNCH(ctx, "cam_map");
     return AVCER_OK;
 }
 

@@ -155,6 +155,18 @@ class Engine:
                                                   _ptr(feats), self._stream()))
         return logits, probs, feats
 
+    def static_forward_cam(self, frames_u8, mode: int = MODE_DEFAULT):
+        """`static_forward` plus the Grad-CAM maps of layer 4 for all 7 classes: (logits, probs, feats, cam [N,7,7,7]); cam is the
+        raw map mean_c g_k[c] * A[c,y,x] before ReLU and normalisation (include/avcer_hip.h avcer_static_forward_cam)."""
+        x = self._dev(frames_u8, torch.uint8)
+        if x.dim() != 4 or x.shape[-1] != 3:
+            raise ValueError(f"frames must be [N,H,W,3] uint8, got {tuple(x.shape)}")
+        n, h, w = int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
+        logits, probs, feats, cam = self._new(n, 7), self._new(n, 7), self._new(n, 512), self._new(n, 7, 7, 7)
+        self._check(self.lib.avcer_static_forward_cam(self.ctx, _ptr(x), n, h, w, mode, _ptr(logits), _ptr(probs), _ptr(feats),
+                                                      _ptr(cam), self._stream()))
+        return logits, probs, feats, cam
+
     def static_forward_nchw(self, x, mode: int = MODE_DEFAULT):
         x = self._dev(x, torch.float32)
         if x.dim() != 4 or tuple(x.shape[1:]) != (3, 224, 224):
@@ -314,6 +326,45 @@ class Engine:
         self._check(self.lib.avcer_crop_tiles(self.ctx, _ptr(x), int(x.shape[0]), int(x.shape[1]), int(x.shape[2]),
                                               _ptr(r), n, 1 if bgr else 0, _ptr(tiles), self._stream()))
         return tiles
+
+    def crop_resize_linear(self, frames_u8, rects, swap_rb: bool = False, out_h: int = 224, out_w: int = 224):
+        """frames u8 [T,H,W,3] + rects i32 [n,5] (frame, x0, y0, x1, y1) -> u8 [n,out_h,out_w,3]: cv2.resize of each crop with
+        INTER_LINEAR, first and last channel swapped when `swap_rb`."""
+        x = self._dev(frames_u8, torch.uint8)
+        r = self._dev(rects, torch.int32)
+        if x.dim() != 4 or x.shape[-1] != 3 or r.dim() != 2 or r.shape[1] != 5:
+            raise ValueError("crop_resize_linear: frames [T,H,W,3] uint8, rects [n,5] int32")
+        n = int(r.shape[0])
+        out = self._new(n, out_h, out_w, 3, dtype=torch.uint8)
+        if n:
+            self._check(self.lib.avcer_crop_resize_linear(self.ctx, _ptr(x), int(x.shape[0]), int(x.shape[1]), int(x.shape[2]),
+                                                          _ptr(r), n, 1 if swap_rb else 0, int(out_h), int(out_w), _ptr(out),
+                                                          self._stream()))
+        return out
+
+    def cam_render(self, cam, rows, cls, base_rgb, lut_bgr, image_weight: float = 0.8):
+        """Grad-CAM overlays: cam f32 [M,7,7,7] (static_forward_cam), rows [n] (map rows, checked here), cls [n] (classes 0..6),
+        base_rgb u8 [n,224,224,3], lut_bgr u8 [256,3] -> u8 [n,224,224,3] BGR as show_cam_on_image returns it."""
+        cam = self._dev(cam, torch.float32)
+        rows_h = np.asarray(rows.cpu() if torch.is_tensor(rows) else rows, dtype=np.int64).reshape(-1)
+        if cam.dim() != 4 or tuple(cam.shape[1:]) != (7, 7, 7):
+            raise ValueError(f"cam must be [M,7,7,7] float32, got {tuple(cam.shape)}")
+        if len(rows_h) and (rows_h.min() < 0 or rows_h.max() >= cam.shape[0]):
+            raise ValueError("cam_render: a row outside the maps")
+        r = self._dev(rows_h.astype(np.int32), torch.int32)
+        c = self._dev(cls, torch.int32).reshape(-1)
+        b = self._dev(base_rgb, torch.uint8)
+        lut = self._dev(lut_bgr, torch.uint8)
+        n = len(rows_h)
+        if c.numel() != n or tuple(b.shape) != (n, 224, 224, 3) or tuple(lut.shape) != (256, 3):
+            raise ValueError("cam_render: cls [n], base_rgb [n,224,224,3] uint8, lut_bgr [256,3] uint8")
+        if not 0.0 <= float(image_weight) <= 1.0:
+            raise ValueError(f"image_weight should be in the range [0, 1], got {image_weight}")
+        out = self._new(n, 224, 224, 3, dtype=torch.uint8)
+        if n:
+            self._check(self.lib.avcer_cam_render(self.ctx, _ptr(cam), _ptr(r), _ptr(c), _ptr(b), n, _ptr(lut), float(image_weight),
+                                                  _ptr(out), self._stream()))
+        return out
 
     def fuse(self, stat, dyn_logits, aud_mean, n_aud: int, weights_1=None, weights_2=(1, 1, 1),
              ce_weights_type: bool = False, ce_mask: bool = True):

@@ -3,7 +3,8 @@ first track, audio model over sliding windows, compound-expression fusion.
 
 What the reference does through files -- cv2.VideoCapture frames, JPEG crops under `<save>/<video>/00/`, an ffmpeg
 wav at 16 kHz, CSV tables when `flag_save_prob` -- is replaced by arrays: decoded BGR frames `[T,H,W,3]` u8 and a mono
-waveform at 16 kHz go in; per-frame predictions come out.  Plotting and Grad-CAM heat maps are not part of this build.
+waveform at 16 kHz go in; per-frame predictions come out.  Grad-CAM heat maps (`flag_heatmaps`) come back as arrays and are
+written as JPEG files when a results path is given.  Plotting is not part of this build.
 """
 from __future__ import annotations
 
@@ -25,14 +26,25 @@ from .video_pipeline import visual_forward
 def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections: Optional[Sequence[np.ndarray]] = None,
                   path_save_results: str = "", name_video: str = "video", flag_save_prob: bool = False,
                   weights_prob_model=None, weights_model=(1, 1, 1), ce_weights_type: bool = True, ce_mask: bool = False,
-                  sr: int = 16000, window: float = 4, step: float = 0.5, padding: str = "mean", mode: int = MODE_DEFAULT):
+                  sr: int = 16000, window: float = 4, step: float = 0.5, padding: str = "mean", mode: int = MODE_DEFAULT,
+                  flag_heatmaps: bool = False, model_heatmaps: str = "static"):
     """engine: an `Engine` with the static, dynamic and audio weights loaded.  frames_bgr u8 [T,H,W,3] as cv2 decodes
     them; wav float32 [L] mono at `sr`; fps as `int(cv2.CAP_PROP_FPS)` gives it (get_face_images.py:23).
     `detector`: a `face_tiles.RetinaFacePredictor` (threshold 0.8 in the reference); or pass per-frame `detections`.
     Defaults follow `run_inference`'s signature (Rule 2 weights on, Rule 1 mask off; `run.py --help` flips them).
     Returns a dict: av / vs / vd / a predictions (int32 [T], compound class per frame), `compound_prob` f64 [4,T,7],
     `static_probs`, `dynamic_logits` [T,7], `audio_rows` / `audio_frames` (the audio table), `records` (face files),
-    `real_time_factor` (elapsed / video duration, the figure run.py:307 prints)."""
+    `real_time_factor` (elapsed / video duration, the figure run.py:307 prints).
+    `flag_heatmaps` (run.py:231-239, get_prob_video.py:135-155): `out["heatmaps"]` = (frame_idx int32 [m], overlays u8
+    [m,224,224,3] BGR), one Grad-CAM overlay per frame of track 00 that starts an LSTM evaluation, of the static softmax of the
+    class the static or the dynamic model (`model_heatmaps`) chose; the base image is the crop cut from the frames on the device
+    and resized with cv2's INTER_LINEAR.  Written as `<path_save_results>/<name_video>/heatmaps_<model>/NNNNNN.jpg` when
+    `path_save_results` is given.  A `model_heatmaps` other than "static" / "dynamic" raises ValueError before any work (the
+    reference dies with UnboundLocalError at its first heat-map frame)."""
+    if flag_heatmaps:
+        from . import heatmaps as hm
+
+        hm.check_model(model_heatmaps)
     start_time = time.time()                                                # run.py:200
     frames = frames_bgr if torch.is_tensor(frames_bgr) else torch.from_numpy(np.ascontiguousarray(frames_bgr))
     total_frames = int(frames.shape[0])
@@ -68,14 +80,28 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
                 host["records"] = records
                 host["clip"] = track_clip(records, tiles, 0, total_frames)
             clip, present = host["clip"]
-            static_probs, dynamic_logits = visual_forward(engine, clip, present, fps, m)             # get_prob_video.py:67-204
+            maps = None
+            if flag_heatmaps:
+                static_probs, dynamic_logits, cam, fidx, rows, cls = hm.visual_forward_cam(engine, clip, present, fps, m, model_heatmaps)
+                if len(rows):
+                    recs = host["records"]
+                    r00 = recs[recs[:, 1] == 0]
+                    at = {int(f): k for k, f in enumerate(r00[:, 0])}
+                    pick = r00[[at[int(f)] for f in fidx]]
+                    rects = torch.from_numpy(pick[:, [0, 2, 3, 4, 5]].astype(np.int32))
+                    base = engine.crop_resize_linear(frames, rects, swap_rb=True)
+                    maps = (fidx, engine.cam_render(cam, rows, cls, base, hm.JET_BGR, hm.IMAGE_WEIGHT))
+                else:
+                    maps = (fidx, torch.zeros((0, 224, 224, 3), dtype=torch.uint8, device=dev))
+            else:
+                static_probs, dynamic_logits = visual_forward(engine, clip, present, fps, m)         # get_prob_video.py:67-204
             # (3) fusion last, behind both branches; nothing has been copied to the host yet
             main.wait_stream(side)
             joined = True
             win_logits.record_stream(main)
             prob, am = fuse(engine, static_probs, dynamic_logits, win_logits, lo, hi, weights_prob_model, weights_model,
                             ce_weights_type, ce_mask)                                                # run.py:25-189
-            return static_probs, dynamic_logits, win_logits, lo, hi, prob, am
+            return static_probs, dynamic_logits, win_logits, lo, hi, prob, am, maps
         finally:
             # the reference's failure paths (no face track, a detector error) unwind from here: the audio branch already queued
             # on `side` is joined all the same, so that no launch of this video outlives the call (its workspace and the
@@ -85,7 +111,7 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
 
     # MODE_F16X3: one read of the range-contract counter behind the last launch; a video during which an activation left fp16's
     # range is run again in MODE_FP32 (engine.guarded)
-    static_probs, dynamic_logits, win_logits, lo, hi, prob, am = engine.guarded(mode, gpu_work)
+    static_probs, dynamic_logits, win_logits, lo, hi, prob, am, maps = engine.guarded(mode, gpu_work)
     records = host["records"]
     rows, aud_frames = replicate_per_frame(win_logits.cpu().numpy(), lo, hi)
     if flag_save_prob:
@@ -95,6 +121,10 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
     out = {name.lower(): am[i] for i, name in enumerate(MODEL_ORDER)}
     out.update(compound_prob=prob.cpu().numpy(), static_probs=static_probs.cpu().numpy(),
                dynamic_logits=dynamic_logits.cpu().numpy(), audio_rows=rows, audio_frames=aud_frames, records=records)
+    if maps is not None:
+        out["heatmaps"] = (maps[0].astype(np.int32), maps[1].cpu().numpy())
+        if path_save_results:
+            hm.write_heatmaps(hm.heatmap_dir(path_save_results, name_video, model_heatmaps), maps[0], maps[1])
     # "Real-time factor for compound expression prediction" as run.py:304-307 prints it: elapsed / video duration (the
     # device -> host copies above have synchronised the stream, so the clock covers all the work); None where the
     # container reported no frame rate

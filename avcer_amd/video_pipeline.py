@@ -150,14 +150,61 @@ def read_face_dir(path_images: str, total_frames: int, track: str = "00"):
     return frames, present
 
 
+def read_face_crops(path_images: str, frame_idx, track: str = "00"):
+    """The original-size crops `<path_images>/<track>/NNNNNN.jpg` of the frames `frame_idx`, decoded to RGB (PIL), packed into
+    one canvas u8 [m, max h, max w, 3] with rects i32 [m,5] = (i, 0, 0, w, h): the input of Engine.crop_resize_linear.  The
+    heat-map base image is cv2.resize of this crop (get_prob_video.py:99-100, data/utils.py:105), not the NEAREST tile."""
+    from PIL import Image
+
+    crops = []
+    for i in np.asarray(frame_idx).reshape(-1):
+        with Image.open(os.path.join(path_images, track, str(int(i)).zfill(6) + ".jpg")) as img:
+            crops.append(np.asarray(img.convert("RGB")))
+    hmax = max([c.shape[0] for c in crops], default=1)
+    wmax = max([c.shape[1] for c in crops], default=1)
+    canvas = np.zeros((max(len(crops), 1), hmax, wmax, 3), dtype=np.uint8)
+    rects = np.zeros((len(crops), 5), dtype=np.int32)
+    for i, c in enumerate(crops):
+        canvas[i, :c.shape[0], :c.shape[1]] = c
+        rects[i] = (i, 0, 0, c.shape[1], c.shape[0])
+    return canvas, rects
+
+
 def preprocess_video_and_predict(engine: Engine, path_images: str = "", save_path: str = "", fps: float = 30, total_frames: int = 0,
-                                 flag_save_prob: bool = False, mode: int = MODE_DEFAULT):
+                                 flag_save_prob: bool = False, mode: int = MODE_DEFAULT, flag_heatmaps: bool = False,
+                                 model_heatmaps: str = "static"):
     """`get_prob_video.preprocess_video_and_predict` (get_prob_video.py:67-204) with the reference's argument meaning, on the HIP
     path: the face-crop directory of one video in, the two per-frame tables out -- (dynamic logits, static probabilities), float32
     [total_frames, 7] in DICT_EMO_VIDEO column order -- and `dynamic__<video>.csv` / `static__<video>.csv` under `save_path` when
-    `flag_save_prob` (the reference's files, io_formats.write_visual_csvs).  Heat maps (`flag_heatmaps`) need a backward pass and
-    are not part of this build."""
+    `flag_save_prob` (the reference's files, io_formats.write_visual_csvs).
+    `flag_heatmaps`: one Grad-CAM overlay per frame that starts an LSTM evaluation, written as
+    `<save_path>/<video>/heatmaps_<model_heatmaps>/NNNNNN.jpg` (avcer_amd/heatmaps.py); the tables are the same as without it.
+    The visual call then runs through `engine.guarded`, maps included.  `model_heatmaps` other than "static" / "dynamic" raises
+    ValueError before any work (the reference dies with UnboundLocalError at its first heat-map frame)."""
     from . import io_formats
+
+    if flag_heatmaps:
+        from . import heatmaps as hm
+
+        hm.check_model(model_heatmaps)
+        frames, present = read_face_dir(path_images, total_frames)
+        frame_idx = hm.heatmap_plan(present, fps)[0]
+        canvas, rects = read_face_crops(path_images, frame_idx)
+
+        def call(m):
+            stat, dyn, cam, fidx, rows, cls = hm.visual_forward_cam(engine, torch.from_numpy(frames), present, fps, m, model_heatmaps)
+            imgs = None
+            if len(rows):
+                base = engine.crop_resize_linear(torch.from_numpy(canvas), rects, swap_rb=False)
+                imgs = engine.cam_render(cam, rows, cls, base, hm.JET_BGR, hm.IMAGE_WEIGHT)
+            return stat, dyn, imgs
+
+        stat, dyn, imgs = engine.guarded(mode, call)
+        if imgs is not None:
+            hm.write_heatmaps(hm.heatmap_dir(save_path, os.path.basename(path_images), model_heatmaps), frame_idx, imgs)
+        if flag_save_prob:
+            io_formats.write_visual_csvs(stat, dyn, save_path, os.path.basename(path_images))
+        return dyn.cpu().numpy(), stat.cpu().numpy()
 
     frames, present = read_face_dir(path_images, total_frames)
     stat, dyn = visual_forward(engine, torch.from_numpy(frames), present, fps, mode)

@@ -67,8 +67,9 @@ enum {
  *      split weight buffers carry a trailer and AVCER_MODE_BF16X3 became AVCER_MODE_F16X3 (round 4).
  *   3: avcer_x3_overflow_count, avcer_profile_read_families; avcer_bneck_chain gained w2_frags (round 5).
  *   4: avcer_source_hash, avcer_set_static_back_batch, avcer_set_static_lanes, avcer_set_static_lane_range, avcer_face_decode_batch, avcer_track_faces,
- *      avcer_lsap, avcer_profile_read_launches (round 6). */
-#define AVCER_ABI_VERSION 4
+ *      avcer_lsap, avcer_profile_read_launches (round 6).
+ *   5: avcer_static_forward_cam, avcer_crop_resize_linear, avcer_cam_render (Grad-CAM heat maps). */
+#define AVCER_ABI_VERSION 5
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
  * avcer_amd/build.py (source_hash()).  The Python binding refuses a library whose hash differs from the tree's, and bench.py
@@ -218,6 +219,27 @@ int avcer_face_decode_batch(avcer_ctx* ctx, const float* loc, const float* conf,
                             avcer_stream_t stream);
 int avcer_crop_tiles(avcer_ctx* ctx, const uint8_t* frames, int n_frames, int h, int w, const int32_t* rects, int n,
                      int swap_rb, uint8_t* tiles, avcer_stream_t stream);
+
+/* Grad-CAM heat maps of the static CNN (get_prob_video.py:101-155 with flag_heatmaps, data/utils.py:92-112,
+ * visualization/visualize.py:218-253).
+ *   avcer_static_forward_cam: avcer_static_forward (same arguments, same logits / probs / feats bit for bit; probs required,
+ *     logits and feats may be NULL) plus cam f32 [n,7,7,7]: for every frame and class k the raw map
+ *     cam[f,k,y,x] = mean_c g_k[c] * A[c,y,x] over layer 4's output A, where g_k = d p_k / d A is constant over the 7 x 7
+ *     positions (s = p_k (e_k - p), u = 1[h > 0] W2^T s, g_k = W1^T u / 49), before ReLU and normalisation.  f32 arithmetic in
+ *     every mode; a frame's map does not depend on the frames around it.
+ *   avcer_crop_resize_linear: cv2.resize(frames[f][y0:y1, x0:x1], (out_w, out_h)) with INTER_LINEAR on u8 (11-bit fixed-point
+ *     weights); rects i32 [n,5] = frame, x0, y0, x1, y1 as avcer_crop_tiles takes them; swap_rb swaps the first and last channel.
+ *     A rect of the output's size is copied.  A rect that is empty or leaves its frame yields zeros.  out u8 [n,out_h,out_w,3].
+ *   avcer_cam_render: overlay i of n from cam[rows[i], cls[i]] (rows index the [.,7,7,7] maps and must be in range, cls in
+ *     0..6): max(m, 0) / max (NaN -> 0 when nothing is positive), f32 bilinear to 224 x 224, u8 truncation, lut_bgr u8 [256,3],
+ *     blend (1 - image_weight) * lut / 255 + image_weight * base_rgb / 255 with base_rgb u8 [n,224,224,3], / max, u8 ->
+ *     out_bgr u8 [n,224,224,3].  Every operation rounded once in f32, as the numpy statement computes it. */
+int avcer_static_forward_cam(avcer_ctx* ctx, const uint8_t* frames, int n, int in_h, int in_w, int mode, float* logits, float* probs,
+                             float* feats, float* cam, avcer_stream_t stream);
+int avcer_crop_resize_linear(avcer_ctx* ctx, const uint8_t* frames, int n_frames, int h, int w, const int32_t* rects, int n,
+                             int swap_rb, int out_h, int out_w, uint8_t* out, avcer_stream_t stream);
+int avcer_cam_render(avcer_ctx* ctx, const float* cam, const int32_t* rows, const int32_t* cls, const uint8_t* base_rgb, int n,
+                     const uint8_t* lut_bgr, double image_weight, uint8_t* out_bgr, avcer_stream_t stream);
 
 /* The face tracker between detector and tiles, for a whole video in ONE call -- HOST code and HOST pointers (the tracker is
  * sequential in time and sees a handful of boxes per frame; the reference runs it on the host too):
