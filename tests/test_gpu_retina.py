@@ -64,7 +64,7 @@ def test_batch_and_rgb_against_oracle(engine_face, sd_retina):
 @pytest.mark.parametrize("h,w,n", [(150, 214, 3), (70, 33, 2), (75, 101, 2), (360, 640, 2)])
 def test_x3_fused_body_against_oracle_and_fp32_mode(engine_face, sd_retina, h, w, n):
     """The x3 mode runs the body's stride-1 bottlenecks on the fused chain / tail kernels of the recognition CNN (api.hip
-    face_forward_impl): odd extents (38 x 54 and 19 x 27 positions per frame in stages 1-2), a frame narrower than one tile row, and
+    run_bneck_stage): odd extents (38 x 54 and 19 x 27 positions per frame in stages 1-2), a frame narrower than one tile row, and
     the bench's 640 x 360 -- against the oracle where it finishes in seconds, against the exact-f32 mode of the library otherwise."""
     frames = synth.video_frames(41, n, h, w)
     loc, conf, lm = (t.cpu().numpy() for t in engine_face.face_forward(frames, MODE_F16X3))
@@ -108,7 +108,7 @@ def test_batch_equals_frame_by_frame(engine_face, sd_retina):
 
 @pytest.mark.parametrize("mode", [MODE_F16X3, MODE_FP32])
 def test_two_lane_detector_batches_are_bit_identical(engine_face, mode):
-    """Batches of at least 16 frames run as two lanes (api.hip face_forward_impl: the halves on two streams, equal passes inside a
+    """Batches of at least 16 frames run as two lanes (api.hip run_two_lanes: the halves on two streams, equal passes inside a
     lane); 21 frames of 96 x 128 split 11 + 10.  Same bits as on one lane, and the outputs are complete on the caller's stream."""
     frames = synth.video_frames(21, 21, 96, 128)
     try:
