@@ -1,6 +1,7 @@
 """ORACLE (test infrastructure, never shipped on the product path).
 
-CPU fp32 restatement of AVCER's audio hot path.  The wav2vec2 arithmetic lives in a third-party
+CPU restatement of AVCER's audio hot path: functional torch, float32 as the reference runs it, float64 when the state dict
+and the input are double (state_dict64 / expr_model_v3_forward64: the high-precision side of tests/test_gpu_audio_stages.py).  The wav2vec2 arithmetic lives in a third-party
 dependency that is NOT under /root/reference: transformers==4.36.2 (src/requirements.txt:46),
 classes Wav2Vec2Model / Wav2Vec2FeatureExtractor, configured as
 audeering/wav2vec2-large-robust-12-ft-emotion-msp-dim (src/get_prob_audio_8_cl.py:53-57).  Its
@@ -102,11 +103,15 @@ def feature_extractor(sd, x, taps=None):
         p = f"wav2vec2.feature_extractor.conv_layers.{i}"
         h = F.conv1d(h, sd[p + ".conv.weight"], sd[p + ".conv.bias"], stride=s)
         h = h.transpose(-2, -1)
+        if taps is not None:
+            taps[f"out:fe{i}.w"] = h  # the conv output in front of the LN, time-major (the library fuses layer 0: no such tap there)
         h = F.layer_norm(h, (h.shape[-1],), sd[p + ".layer_norm.weight"], sd[p + ".layer_norm.bias"], LN_EPS)
         h = h.transpose(-2, -1)
         h = F.gelu(h)
-        if taps is not None and i == 0:
-            taps["conv0"] = h
+        if taps is not None:
+            taps[f"ln:fe{i}.ln"] = h.transpose(-2, -1)  # LN + GELU output, time-major: the library's "conv0" (i = 0) .. "extract" (6)
+            if i == 0:
+                taps["conv0"] = h
     return h.transpose(1, 2)
 
 
@@ -135,22 +140,35 @@ def encoder(sd, h, taps=None):
         p = f"{w}layers.{i}"
         res = h
         x = F.layer_norm(h, (HIDDEN,), sd[p + ".layer_norm.weight"], sd[p + ".layer_norm.bias"], LN_EPS)
-        q = F.linear(x, sd[p + ".attention.q_proj.weight"], sd[p + ".attention.q_proj.bias"]) * d ** -0.5
+        q = F.linear(x, sd[p + ".attention.q_proj.weight"], sd[p + ".attention.q_proj.bias"])
         k = F.linear(x, sd[p + ".attention.k_proj.weight"], sd[p + ".attention.k_proj.bias"])
         v = F.linear(x, sd[p + ".attention.v_proj.weight"], sd[p + ".attention.v_proj.bias"])
+        if taps is not None:
+            taps[f"ln:enc{i}.ln1"] = x
+            # Wav2Vec2Attention scales q by d^-0.5 right after the projection; the library scales inside its attention kernel,
+            # so its qkv tensor holds the UNSCALED projection: that is what this tap holds (q | k | v along the last axis)
+            taps[f"out:enc{i}.qkv.w"] = torch.cat([q, k, v], dim=-1)
+        q = q * d ** -0.5
         q = q.view(b, s, HEADS, d).transpose(1, 2)
         k = k.view(b, s, HEADS, d).transpose(1, 2)
         v = v.view(b, s, HEADS, d).transpose(1, 2)
         a = F.softmax(torch.matmul(q, k.transpose(-2, -1)), dim=-1)
         o = torch.matmul(a, v).transpose(1, 2).reshape(b, s, HIDDEN)
+        if taps is not None:
+            taps[f"att:enc{i}"] = o
         o = F.linear(o, sd[p + ".attention.out_proj.weight"], sd[p + ".attention.out_proj.bias"])
         h = res + o
         x = F.layer_norm(h, (HIDDEN,), sd[p + ".final_layer_norm.weight"], sd[p + ".final_layer_norm.bias"], LN_EPS)
+        if taps is not None:
+            taps[f"out:enc{i}.o.w"] = h  # the out-projection with its residual: the stream between the two halves of the layer
+            taps[f"ln:enc{i}.ln2"] = x
         x = F.gelu(F.linear(x, sd[p + ".feed_forward.intermediate_dense.weight"],
                             sd[p + ".feed_forward.intermediate_dense.bias"]))
+        if taps is not None:
+            taps[f"out:enc{i}.ff1.w"] = x
         x = F.linear(x, sd[p + ".feed_forward.output_dense.weight"], sd[p + ".feed_forward.output_dense.bias"])
         h = h + x
-        if taps is not None and i in (0, 5, 11):
+        if taps is not None:
             taps[f"layer{i}"] = h
     return F.layer_norm(h, (HIDDEN,), sd[w + "layer_norm.weight"], sd[w + "layer_norm.bias"], LN_EPS)
 
@@ -164,7 +182,9 @@ def wav2vec2_forward(sd, x, taps=None):
     f = F.layer_norm(f, (f.shape[-1],), sd[p + "layer_norm.weight"], sd[p + "layer_norm.bias"], LN_EPS)
     h = F.linear(f, sd[p + "projection.weight"], sd[p + "projection.bias"])
     if taps is not None:
+        taps["ln:fp.ln"] = f
         taps["proj"] = h
+        taps["pos_in"] = h  # the library's operand-typed copy of proj that the positional conv reads
     h = encoder(sd, h, taps)
     if taps is not None:
         taps["w2v"] = h
@@ -172,7 +192,7 @@ def wav2vec2_forward(sd, x, taps=None):
 
 
 # ----------------------------------------------------------------------------- first-party head
-def transformer_layer(sd, tl: str, x, num_heads: int):
+def transformer_layer(sd, tl: str, x, num_heads: int, taps=None):
     """architectures/attention_layers.py:249-267 with key=value=query=x: the same PE is added to each
     (all three become x+PE, which is also the residual); bias-free Q/K/V/O (:91-96); softmax(QK^T/sqrt(d))V
     (:10-38); LN(res+attn) (:60-77); Linear->ReLU->Linear (:41-57; feed_forward.layer_norm is never applied);
@@ -185,16 +205,27 @@ def transformer_layer(sd, tl: str, x, num_heads: int):
     v = F.linear(xp, sd[tl + ".self_attention.values_w.weight"]).view(b, s, num_heads, d).transpose(1, 2)
     a = F.softmax(torch.matmul(q, k.transpose(-2, -1)) / math.sqrt(d), dim=-1)
     o = torch.matmul(a, v).transpose(1, 2).contiguous().view(b, s, e)
+    if taps is not None:
+        taps[f"pe:{tl}"] = xp
+        taps[f"out:{tl}.qkv.w"] = torch.cat([t.transpose(1, 2).reshape(b, s, e) for t in (q, k, v)], dim=-1)
+        taps[f"att:{tl}"] = o
     o = F.linear(o, sd[tl + ".self_attention.ff_layer_after_concat.weight"])
     p = tl + ".add_norm_after_attention.layer_norm"
     y = F.layer_norm(o + xp, (e,), sd[p + ".weight"], sd[p + ".bias"], LN_EPS)
-    f = F.linear(F.relu(F.linear(y, sd[tl + ".feed_forward.layer_1.weight"], sd[tl + ".feed_forward.layer_1.bias"])),
-                 sd[tl + ".feed_forward.layer_2.weight"], sd[tl + ".feed_forward.layer_2.bias"])
+    f1 = F.relu(F.linear(y, sd[tl + ".feed_forward.layer_1.weight"], sd[tl + ".feed_forward.layer_1.bias"]))
+    f = F.linear(f1, sd[tl + ".feed_forward.layer_2.weight"], sd[tl + ".feed_forward.layer_2.bias"])
     p = tl + ".add_norm_after_ff.layer_norm"
-    return F.layer_norm(f + y, (e,), sd[p + ".weight"], sd[p + ".bias"], LN_EPS)
+    out = F.layer_norm(f + y, (e,), sd[p + ".weight"], sd[p + ".bias"], LN_EPS)
+    if taps is not None:
+        taps[f"out:{tl}.o.w"] = o + xp  # both sums carry their residual, as the library's contractions write them
+        taps[f"ln:{tl}.ln1"] = y
+        taps[f"out:{tl}.ff1.w"] = f1
+        taps[f"out:{tl}.ff2.w"] = f + y
+        taps[f"ln:{tl}.ln2"] = out
+    return out
 
 
-def head(sd, x):
+def head(sd, x, taps=None):
     """architectures/audio_8_cl.py:146-159,185-190: permute, Conv1d k5 s3 dil2, BN, MaxPool(5), ReLU, Conv1d k3, BN,
     global avg, ReLU, squeeze, Linear -> raw logits.  Returns [B,C] ((C,) when B == 1, as `.squeeze()` does)."""
     t = "time_downsample"
@@ -202,25 +233,58 @@ def head(sd, x):
     h = F.conv1d(h, sd[t + ".0.weight"], sd[t + ".0.bias"], stride=3, dilation=2)
     h = F.batch_norm(h, sd[t + ".1.running_mean"], sd[t + ".1.running_var"], sd[t + ".1.weight"], sd[t + ".1.bias"],
                      False, 0.0, BN_EPS)
+    if taps is not None:
+        taps["td0"] = h.transpose(1, 2)  # head taps time-major [B, L, 1024], as the library holds them
     h = F.relu(F.max_pool1d(h, 5))
+    if taps is not None:
+        taps["mp"] = h.transpose(1, 2)
     h = F.conv1d(h, sd[t + ".4.weight"], sd[t + ".4.bias"])
     h = F.batch_norm(h, sd[t + ".5.running_mean"], sd[t + ".5.running_var"], sd[t + ".5.weight"], sd[t + ".5.bias"],
                      False, 0.0, BN_EPS)
+    if taps is not None:
+        taps["td4"] = h.transpose(1, 2)
     h = F.relu(F.adaptive_avg_pool1d(h, 1))
+    if taps is not None:
+        taps["pooled"] = h[:, :, 0]
     h = h.squeeze()
-    return F.linear(h, sd["feature_downsample.weight"], sd["feature_downsample.bias"])
+    h = F.linear(h, sd["feature_downsample.weight"], sd["feature_downsample.bias"])
+    if taps is not None:
+        taps["logits"] = h
+    return h
 
 
 def expr_model_v3_forward(sd, x, taps=None):
     """architectures/audio_8_cl.py:179-190."""
     h = wav2vec2_forward(sd, x, taps)
-    h = transformer_layer(sd, "tl1", h, 32)
+    h = transformer_layer(sd, "tl1", h, 32, taps)
     if taps is not None:
         taps["tl1"] = h
-    h = transformer_layer(sd, "tl2", h, 16)
+    h = transformer_layer(sd, "tl2", h, 16, taps)
     if taps is not None:
         taps["tl2"] = h
-    return head(sd, h)
+    return head(sd, h, taps)
+
+
+# ----------------------------------------------------------------------------- float64 side
+def state_dict64(sd):
+    """The state dict with every floating tensor in float64 (integer buffers such as num_batches_tracked as they are)."""
+    return {k: (v.double() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in sd.items()}
+
+
+def normalize64(x) -> torch.Tensor:
+    """`normalize` evaluated in float64 on the float32 samples: the same formula, population variance, eps 1e-7."""
+    x = torch.as_tensor(np.asarray(x, dtype=np.float32)).double()
+    return (x - x.mean(-1, keepdim=True)) / torch.sqrt(x.var(-1, unbiased=False, keepdim=True) + 1e-7)
+
+
+def expr_model_v3_forward64(sd64, wav, taps=None, norm: bool = True):
+    """The whole model in float64 from the float32 waveform [B,T] (sd64 = state_dict64(sd)): normalisation unless norm is False,
+    then expr_model_v3_forward.  taps additionally gets "norm", the model's input."""
+    with torch.no_grad():
+        x = normalize64(wav) if norm else torch.as_tensor(np.asarray(wav, dtype=np.float32)).double()
+        if taps is not None:
+            taps["norm"] = x
+        return expr_model_v3_forward(sd64, x, taps)
 
 
 def audio_forward(sd, wav: torch.Tensor, sr: int, fps: float, window: float = 4, step: float = 0.5,

@@ -631,8 +631,28 @@ def test_x3_overflow_is_nan_not_a_wrong_number(engine):
 
 
 # ---- attention kernel on its own (avcer_attention)
-@pytest.mark.parametrize("s,heads,d", [(99, 16, 64), (199, 4, 64), (99, 8, 32), (37, 2, 64)])
-def test_attention_f32_and_x3_against_float64(engine, s, heads, d):
+def _peak_last_key(qkv, e, heads, d):
+    """Every query's score against the LAST key exceeds its score against any other by more than 100 (dimension 0 of each head:
+    q = 16, the last key 64 or 45.25 (d = 32), every other key 0, so 128 after the scale): softmax weights of exactly 0 in float32
+    everywhere but one key of the last key tile."""
+    n, s, _ = qkv.shape
+    q, k = qkv[..., :e].view(n, s, heads, d), qkv[..., e:2 * e].view(n, s, heads, d)
+    q[..., 0] = 16.0
+    k[..., 0] = 0.0
+    k[:, s - 1] = 0.0
+    k[:, s - 1, :, 0] = 8.0 * d ** 0.5
+
+
+# s = 1 (127 padded keys), 16 / 17 (one key tile exactly full, one key in the second), 128 / 129 (the last size of the 8-key-tile
+# MFMA form with every tile full, the first of the 16-tile form), 255 / 256 (no padded key at all)
+_ATT_CASES = [(99, 16, 64, False), (199, 4, 64, False), (99, 8, 32, False), (37, 2, 64, False),
+              (1, 4, 64, False), (16, 4, 64, False), (17, 4, 64, False), (128, 4, 64, False), (129, 4, 64, False),
+              (255, 4, 64, False), (256, 4, 64, False), (128, 8, 32, False), (129, 8, 32, False), (256, 8, 32, False),
+              (129, 4, 64, True), (256, 8, 32, True)]
+
+
+@pytest.mark.parametrize("s,heads,d,peak", _ATT_CASES, ids=[f"{s}-{h}-{d}" + ("-peak" if p else "") for s, h, d, p in _ATT_CASES])
+def test_attention_f32_and_x3_against_float64(engine, s, heads, d, peak):
     """softmax(Q K^T * scale) V per head (attention_layers.py:80-144; transformers Wav2Vec2Attention): the f32 VALU kernel
     and the x3 MFMA kernel (fp16 hi/lo pairs, sp32 output) against float64.  Both must be f32-grade -- the x3 form read
     6.8e-6 rms here until round 4: hipcc folded the final multiply into the f16 conversion separately for the hi store and
@@ -641,9 +661,15 @@ def test_attention_f32_and_x3_against_float64(engine, s, heads, d):
     n, e = 3, heads * d
     qkv = torch.randn(n, s, 3 * e, generator=g)
     qkv[..., :e] *= 2.0                                              # scores up to ~ +-10
+    if peak:
+        _peak_last_key(qkv, e, heads, d)
     scale = 1.0 / d ** 0.5
     q, k, v = (qkv[..., i * e:(i + 1) * e].double().view(n, s, heads, d).transpose(1, 2) for i in range(3))
-    ref = (torch.softmax(q @ k.transpose(-1, -2) * scale, -1) @ v).transpose(1, 2).reshape(n, s, e)
+    scores = q @ k.transpose(-1, -2) * scale
+    if peak:
+        top = scores.topk(2, -1).values
+        assert (scores.argmax(-1) == s - 1).all() and (top[..., 0] - top[..., 1]).min() > 100
+    ref = (torch.softmax(scores, -1) @ v).transpose(1, 2).reshape(n, s, e)
     dev = engine.device
     qd = qkv.to(dev)
     o32 = torch.full((n, s, e), float("nan"), device=dev)
@@ -657,6 +683,37 @@ def test_attention_f32_and_x3_against_float64(engine, s, heads, d):
         rel, worst = (err.pow(2).mean().sqrt() / rms).item(), err.abs().max().item()
         print(f"attention s={s} heads={heads} d={d} {name}: rel rms {rel:.2e}, max|err| {worst:.2e}")
         assert rel < 1e-6 and worst < 4e-6, (name, rel, worst)
+
+
+@pytest.mark.parametrize("s", [99, 128, 129, 256])
+def test_attention_bf16_against_float64(engine, s):
+    """The bf16 instantiation (in_kind = out_kind = 1: bf16 q, k, v on the MFMA, bf16 output) against float64 of the bf16-rounded
+    inputs.  The bound is what the storage allows: what rounding q, k and v to bf16 moves the float64 result by (max over the
+    tensor; the kernel's own bf16 roundings of the softmax weights in front of P V are of that size), plus one bf16 ulp of the
+    output (2^-7 of max|ref|)."""
+    heads, d, n = 16, 64, 3
+    e = heads * d
+    g = torch.Generator().manual_seed(1000 + s)
+    qkv = torch.randn(n, s, 3 * e, generator=g)
+    qkv[..., :e] *= 2.0
+    scale = 1.0 / d ** 0.5
+
+    def f64(x):
+        q, k, v = (x[..., i * e:(i + 1) * e].double().view(n, s, heads, d).transpose(1, 2) for i in range(3))
+        return (torch.softmax(q @ k.transpose(-1, -2) * scale, -1) @ v).transpose(1, 2).reshape(n, s, e)
+
+    qb = qkv.to(torch.bfloat16)
+    ref, exact = f64(qb), f64(qkv)
+    out = torch.full((n, s, e), float("nan"), dtype=torch.bfloat16, device=engine.device)
+    engine.attention(qb.to(engine.device), out, n, s, heads, d, scale, 1, 1)
+    torch.cuda.synchronize()
+    got = out.cpu().double()
+    assert torch.isfinite(got).all()
+    worst = (got - ref).abs().max().item()
+    bound = (ref - exact).abs().max().item() + 2.0 ** -7 * ref.abs().max().item()
+    rel = ((got - ref).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt()).item()
+    print(f"attention bf16 s={s}: max|err| {worst:.2e} (bound {bound:.2e}), rel rms {rel:.2e}")
+    assert worst < bound, (s, worst, bound)
 
 
 def test_attention_argument_errors(engine):

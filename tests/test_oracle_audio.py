@@ -85,3 +85,27 @@ def test_seven_class_variant_matches_reference(golden):
         lg = oa.expr_model_v3_forward(sd, torch.from_numpy(x))
     assert tuple(lg.shape) == (2, 7)
     assert np.abs(lg.numpy() - golden("audio_model7")["logits"]).max() < 2e-5
+
+
+def test_float64_and_float32_runs_agree_on_every_tap(golden, sd_audio):
+    """The extended oracle run in float32 (as the reference runs) and in float64 (state_dict64, the reference side of
+    tests/test_gpu_audio_stages.py) agree on every tap to 2e-6 of max|ref|: about twice the float32 run's own rounding error,
+    which is 2.8e-7 (conv0) to 9.0e-7 (w2v) on the stage taps.  A figure of the oracle alone, not of the library.  The float32 run
+    still reproduces the golden logits."""
+    wav = synth.waveforms(5678, 2, 32000)
+    t32, t64 = {}, {}
+    with torch.no_grad():
+        lg = oa.expr_model_v3_forward(sd_audio, torch.from_numpy(oa.normalize(wav)), t32)
+    lg64 = oa.expr_model_v3_forward64(oa.state_dict64(sd_audio), wav, t64)
+    assert lg64.dtype == torch.float64 and np.abs(lg.numpy() - golden("audio_model")["t32000_logits"]).max() < 2e-5
+    assert set(t64) == set(t32) | {"norm"}
+    # every launch of the library has its tensor: 7 + 7 extractor, 7 per encoder layer, 9 per TransformerLayer, the head
+    assert len(t64) == 1 + 1 + 14 + 5 + 7 * 12 + 1 + 2 * 9 + 5, sorted(t64)
+    worst = {}
+    for k, ref in t64.items():
+        got = torch.from_numpy(oa.normalize(wav)) if k == "norm" else t32[k]
+        assert got.shape == ref.shape and got.dtype == torch.float32 and ref.dtype == torch.float64, k
+        worst[k] = ((got.double() - ref).abs().max() / ref.abs().max()).item()
+    top = max(worst, key=worst.get)
+    print(f"float32 against float64 oracle: worst tap {top} {worst[top]:.2e}")
+    assert worst[top] < 2e-6, {k: v for k, v in worst.items() if v >= 2e-6}
