@@ -42,6 +42,7 @@ class Engine:
         self.ctx = ctx
         self.audio_classes = 0
         self.x3_fallbacks = 0  # calls `guarded` had to repeat in MODE_FP32 (the x3 range contract was broken)
+        self._resample_cache = {}  # (orig_freq, new_freq) -> (plan, taps [span, n] and first [n] on the device): Engine.resample
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -243,6 +244,50 @@ class Engine:
         out = self._new(n, window)
         self._check(self.lib.avcer_audio_chunks(self.ctx, _ptr(wav), _ptr(starts), _ptr(ends), n, int(window),
                                                 PAD_MODES[padding], _ptr(out), self._stream()))
+        return out
+
+    def resample(self, src, orig_freq: int, new_freq: int):
+        """Source audio at `orig_freq` -> mono float32 [n_out] at `new_freq` on the device, n_out = ceil(L * new / orig) -- what
+        data/utils.py:50-57 makes of a WAV file (int16 / 32768, channel mean, torchaudio's Resample), in one launch
+        (include/avcer_hip.h avcer_resample).  src: int16 [L] or [L, C] (interleaved frames, as they lie in the file) or float32
+        [L] or [C, L] (as torchaudio.load returns them), C <= 8; anything else raises ValueError, as do rates the kernel does
+        not cover (audio_pipeline.resample_plan).  Equal rates: conversion and downmix alone (float32 mono comes back as it is).
+        The tap table of a rate pair is built once per engine and stays on the device.  No host synchronisation."""
+        from .audio_pipeline import resample_out_len, resample_plan
+
+        if not isinstance(src, torch.Tensor):
+            src = torch.as_tensor(np.asarray(src))
+        if src.dtype == torch.int16 and src.dim() in (1, 2):
+            kind, length, ch = 0, int(src.shape[0]), int(src.shape[1]) if src.dim() == 2 else 1
+        elif src.dtype == torch.float32 and src.dim() in (1, 2):
+            kind, length, ch = 1, int(src.shape[-1]), int(src.shape[0]) if src.dim() == 2 else 1
+        else:
+            raise ValueError(f"resample: source must be int16 [L] / [L, C] or float32 [L] / [C, L], got {src.dtype} {tuple(src.shape)}")
+        if not 1 <= ch <= 8:
+            raise ValueError(f"resample: {ch} channels (1..8)")
+        if length > 2 ** 31 - 1:
+            raise ValueError(f"resample: {length} samples per channel (the kernel takes 2^31 - 1)")
+        if orig_freq == new_freq:
+            resample_plan(orig_freq, new_freq)  # validates the rate
+            if kind == 1 and ch == 1:
+                return self._dev(src, torch.float32).reshape(-1)
+            taps = first = None
+            o = n = 1
+            span = width = 0
+        else:
+            cache = self._resample_cache
+            key = (int(orig_freq), int(new_freq))
+            if key not in cache:
+                plan = resample_plan(*key)
+                cache[key] = (plan, self._dev(np.ascontiguousarray(plan.taps.T), torch.float32), self._dev(plan.first.copy(), torch.int32))
+            plan, taps, first = cache[key]
+            o, n, span, width = plan.o, plan.n, plan.span, plan.width
+        n_out = resample_out_len(length, o, n)
+        x = self._dev(src, src.dtype)
+        out = self._new(n_out)
+        if length:
+            self._check(self.lib.avcer_resample(self.ctx, _ptr(x), kind, length, ch, _ptr(taps), _ptr(first), o, n, span, width,
+                                                _ptr(out), n_out, self._stream()))
         return out
 
     def audio_frame_mean(self, win_logits, frame_lo, frame_hi, n_frames: int):

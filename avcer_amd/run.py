@@ -3,8 +3,9 @@ first track, audio model over sliding windows, compound-expression fusion.
 
 What the reference does through files -- cv2.VideoCapture frames, JPEG crops under `<save>/<video>/00/`, an ffmpeg
 wav at 16 kHz, CSV tables when `flag_save_prob` -- is replaced by arrays: decoded BGR frames `[T,H,W,3]` u8 and a mono
-waveform at 16 kHz go in; per-frame predictions come out.  Grad-CAM heat maps (`flag_heatmaps`) come back as arrays and are
-written as JPEG files when a results path is given.  Plotting is not part of this build.
+waveform at 16 kHz -- or the source audio as it lies in the WAV file, with its rate (`wav_sr`) -- go in; per-frame predictions
+come out.  Grad-CAM heat maps (`flag_heatmaps`) come back as arrays and are written as JPEG files when a results path is given.
+Plotting is not part of this build.
 """
 from __future__ import annotations
 
@@ -16,7 +17,7 @@ import numpy as np
 import torch
 
 from . import io_formats
-from .audio_pipeline import audio_forward, replicate_per_frame
+from .audio_pipeline import audio_forward, replicate_per_frame, resample_plan
 from .engine import MODE_DEFAULT
 from .face_tiles import VideoTiler, track_clip
 from .fusion import MODEL_ORDER, fuse
@@ -27,9 +28,13 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
                   path_save_results: str = "", name_video: str = "video", flag_save_prob: bool = False,
                   weights_prob_model=None, weights_model=(1, 1, 1), ce_weights_type: bool = True, ce_mask: bool = False,
                   sr: int = 16000, window: float = 4, step: float = 0.5, padding: str = "mean", mode: int = MODE_DEFAULT,
-                  flag_heatmaps: bool = False, model_heatmaps: str = "static"):
+                  flag_heatmaps: bool = False, model_heatmaps: str = "static", wav_sr: Optional[int] = None):
     """engine: an `Engine` with the static, dynamic and audio weights loaded.  frames_bgr u8 [T,H,W,3] as cv2 decodes
     them; wav float32 [L] mono at `sr`; fps as `int(cv2.CAP_PROP_FPS)` gives it (get_face_images.py:23).
+    `wav_sr`: `wav` is source audio at that rate instead -- int16 [L] / [L, C] as the frames lie in the WAV file ffmpeg writes
+    (44.1 kHz stereo, data/utils.py:46) or float32 [L] / [C, L] -- and is converted, downmixed and resampled to `sr` on the device,
+    on the audio stream in front of the chunker (data/utils.py:50-57, Engine.resample).  A rate pair the kernel does not cover
+    raises ValueError before any work.
     `detector`: a `face_tiles.RetinaFacePredictor` (threshold 0.8 in the reference); or pass per-frame `detections`.
     Defaults follow `run_inference`'s signature (Rule 2 weights on, Rule 1 mask off; `run.py --help` flips them).
     Returns a dict: av / vs / vd / a predictions (int32 [T], compound class per frame), `compound_prob` f64 [4,T,7],
@@ -53,7 +58,11 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
     duration = total_frames / fps if (fps and fps > 0 and total_frames > 0) else None
     if detections is None and detector is None:
         raise ValueError("give a detector or the per-frame detections")
-    wav_t = wav if torch.is_tensor(wav) else torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32))
+    if wav_sr is None:
+        wav_t = wav if torch.is_tensor(wav) else torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32))
+    else:
+        resample_plan(wav_sr, sr)
+        wav_t = wav if torch.is_tensor(wav) else torch.from_numpy(np.ascontiguousarray(wav))
     dev = engine.device
     wav_t = wav_t.to(dev)
     main = torch.cuda.current_stream(dev)
@@ -70,7 +79,7 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
         joined = False
         try:
             with torch.cuda.stream(side):
-                win_logits, lo, hi = audio_forward(engine, wav_t, sr, fps, window, step, padding, m)  # get_prob_audio_8_cl.py:68-138
+                win_logits, lo, hi = audio_forward(engine, wav_t, sr, fps, window, step, padding, m, wav_sr=wav_sr)  # get_prob_audio_8_cl.py:68-138
             # (2) faces -> tracks -> tiles (get_face_images.py:38-63), then the visual models on track 00
             if "clip" not in host:
                 dets = detections if detections is not None else detector.batch(frames, rgb=False)  # get_face_images.py:49

@@ -68,8 +68,9 @@ enum {
  *   3: avcer_x3_overflow_count, avcer_profile_read_families; avcer_bneck_chain gained w2_frags (round 5).
  *   4: avcer_source_hash, avcer_set_static_back_batch, avcer_set_static_lanes, avcer_set_static_lane_range, avcer_face_decode_batch, avcer_track_faces,
  *      avcer_lsap, avcer_profile_read_launches (round 6).
- *   5: avcer_static_forward_cam, avcer_crop_resize_linear, avcer_cam_render (Grad-CAM heat maps). */
-#define AVCER_ABI_VERSION 5
+ *   5: avcer_static_forward_cam, avcer_crop_resize_linear, avcer_cam_render (Grad-CAM heat maps).
+ *   6: avcer_resample (source audio -> mono at the model's rate). */
+#define AVCER_ABI_VERSION 6
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
  * avcer_amd/build.py (source_hash()).  The Python binding refuses a library whose hash differs from the tree's, and bench.py
@@ -166,6 +167,39 @@ int avcer_audio_num_classes(const avcer_ctx* ctx);
  * and the kernel itself writes NaN for such a row instead of indexing with i % 0). */
 int avcer_audio_chunks(avcer_ctx* ctx, const float* wav, const int32_t* starts, const int32_t* ends, int n,
                        int window, int mode, float* out, avcer_stream_t stream);
+
+/* Source audio -> mono float32 at the model's rate: sample conversion, downmix and resampling in one launch.
+ *   ref: data/utils.py:50-57 (torchaudio.load -> float32 [C, L] = int16 / 32768; wav.mean(dim=0) when C > 1;
+ *        torchaudio.transforms.Resample(orig_freq, new_freq) with its defaults)
+ *        torchaudio==2.1.2 functional/functional.py _get_sinc_resample_kernel, _apply_sinc_resample_kernel (third party, BSD-2:
+ *        resampling_method "sinc_interp_hann", lowpass_filter_width 6, rolloff 0.99)
+ * With g = gcd(orig, new), o = orig / g, n = new / g:  base = min(o, n) * 0.99,  width = ceil(6 * o / base),
+ *   k[p][j] = cos(t * pi / 12)^2 * sinc(pi * t) * base / o,  t = clamp((-p / n + (j - width) / o) * base, -6, 6),
+ *   p in [0, n), j in [0, 2 * width + o),  sinc(0) = 1,  stored as float32;
+ *   y[q * n + p] = sum_j k[p][j] * x[q * o + j - width],  x = 0 outside [0, len);  n_out = ceil(n * len / o).
+ * The clamp makes the window zero outside |t| < 6: per phase only `span` consecutive taps from index first[p] on can be
+ * non-zero, and the kernel works on that compact table (leaving out a zero tap changes no bit of the sum):
+ *   taps  f32 [span][n] (device), TAP-MAJOR: taps[j * n + p] = k[p][first[p] + j];   first i32 [n] (device),
+ *   0 <= first[p] and first[p] + span <= 2 * width + o for every p (the kernel clamps its staging index to both ends, so a
+ *   table that breaks this yields wrong numbers, never a read outside its buffer).  avcer_amd.audio_pipeline.resample_plan builds the table on the host with
+ *   torchaudio's own operations and dtypes.  Each output is accumulated in f64 (f32 products are exact there) and rounded
+ *   to f32 once at the end: one f32 rounding away from the exact sum, at most as far from it as the reference's f32 conv1d.
+ * src: AVCER_PCM_S16_INTERLEAVED = int16 [len][channels] as the frames lie in a WAV file, converted as s / 32768;
+ *      AVCER_PCM_F32_PLANAR = f32 [channels][len] (or [len] with channels = 1).  channels > 1: the f32 sum over the channels
+ *      in channel order divided by their number (exact for <= 2 channels); 1 <= channels <= AVCER_RESAMPLE_MAX_CHANNELS.
+ * taps == NULL (then first == NULL, o = n = 1): equal rates, conversion and downmix alone, n_out = len (utils.py:54).
+ * Limits (AVCER_EINVAL beyond them, there is no other path): o <= AVCER_RESAMPLE_MAX_O, n <= AVCER_RESAMPLE_MAX_N,
+ * span <= AVCER_RESAMPLE_MAX_SPAN, len <= AVCER_RESAMPLE_MAX_LEN.  They cover every pair of the common rates 8000, 11025, 16000,
+ * 22050, 32000, 44100, 48000, 96000 into 16000 (the largest: n = 640 at 11025, o = 441 at 44100, span 73 at 96000).
+ * out f32 [n_out]; n_out is checked against the rule above.  len = 0: nothing is launched.  No host synchronisation. */
+enum { AVCER_PCM_S16_INTERLEAVED = 0, AVCER_PCM_F32_PLANAR = 1 };
+#define AVCER_RESAMPLE_MAX_O 2048
+#define AVCER_RESAMPLE_MAX_N 1024
+#define AVCER_RESAMPLE_MAX_SPAN 128
+#define AVCER_RESAMPLE_MAX_CHANNELS 8
+#define AVCER_RESAMPLE_MAX_LEN 2147483647LL
+int avcer_resample(avcer_ctx* ctx, const void* src, int src_kind, int64_t len, int channels, const float* taps,
+                   const int32_t* first, int o, int n, int span, int width, float* out, int64_t n_out, avcer_stream_t stream);
 
 /* Per-frame mean of window logits.
  *   ref: get_prob_audio_8_cl.py:94-101 (logits replicated for frames [lo,hi) of each window),
