@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/avcer_hip.h"
+#include "arena.h"
 
 typedef uint16_t bf16_t;  // raw bfloat16 bits
 
@@ -19,6 +20,18 @@ struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
 };
+
+// the context's workspace slots (ws_reserve): one per pipeline, the second lanes of the two ResNets and two utilities
+enum { WS_STATIC = 0, WS_DYNAMIC = 1, WS_AUDIO = 2, WS_FACE = 3, WS_NMS = 4, WS_CEILINGS = 5, WS_STATIC_LANE1 = 6, WS_FACE_LANE1 = 7,
+       WS_COUNT = 8 };
+
+// how an activation tensor is stored (the `kind` / `act` arguments of the k_* launchers, Net::gemm's akind / okind)
+enum { KIND_F32 = 0, KIND_BF16 = 1, KIND_SP32 = 2 };
+struct Storage { int kind; size_t es; };  // es: bytes per element
+// activation storage of a forward pass in `mode`: f32 / bf16 / sp32 pairs
+inline Storage mode_storage(int mode) {
+    return mode == AVCER_MODE_BF16 ? Storage{KIND_BF16, 2} : Storage{mode == AVCER_MODE_F16X3 ? KIND_SP32 : KIND_F32, 4};
+}
 
 // One packed tensor of a weight blob, resident on the device in f32 and (lazily) in bf16.
 struct Tensor {
@@ -49,8 +62,8 @@ struct avcer_ctx {
     hipStream_t lane_stream = nullptr;  // the second lane's stream, created on first use, and its fork / join events
     hipEvent_t lane_ev[2] = {nullptr, nullptr};
     int block_slots = 512;    // 2 x hipDeviceProp_t::multiProcessorCount: what grid_rounds() divides a grid by
-    // grow-only workspace arenas (activations), one per pipeline
-    DevBuf ws[8];
+    // grow-only workspace arenas (activations), one per WS_* slot
+    DevBuf ws[WS_COUNT];
     // device counter of the x3 mode's range contract: += 1 per thread that split a finite |x| >= 65520 into an fp16 pair
     // (split_dev.h sp_commit); read and reset by avcer_x3_overflow_count
     unsigned* ovf = nullptr;
@@ -142,7 +155,7 @@ int measure_ceilings(avcer_ctx* ctx, double* mfma_bf16_tflops, double* hbm_copy_
 // ---- kernels.hip (element-wise / reduction kernels; T selects f32 (0) or bf16 (1) activations)
 // kind: 0 = f32 [n,230,230,4], 1 = bf16, 3 = planar fp16 hi / lo (two [n,230,230,4] planes, the stem_pool input)
 int k_preprocess(avcer_ctx*, const uint8_t* frames, int n, int in_h, int in_w, void* out, int kind, hipStream_t);
-int k_maxpool3s2(avcer_ctx*, const void* x, void* y, int n, int h, int w, int c, int oh, int ow, int bf16, hipStream_t);
+int k_maxpool3s2(avcer_ctx*, const void* x, void* y, int n, int h, int w, int c, int oh, int ow, int kind, hipStream_t);
 int k_avgpool_hw(avcer_ctx*, const void* x, float* y, void* y_sp32, int n, int hw, int c, int kind, hipStream_t);
 // Grad-CAM of layer 4 for all 7 classes (kernels.hip): x = layer 4's output [n,7,7,2048] in storage `kind`, probs [n,7],
 // h = fc1's pre-ReLU output [n,512], w1 = fc1.w [512,2048], w2 = fc2.w [7,512], g = scratch f32 [n,7,2048] -> cam f32 [n,7,49]
@@ -154,7 +167,7 @@ int k_lstm_cell(avcer_ctx*, const float* xproj, int64_t xproj_ld, const float* h
                 int64_t h_ld, int n, int hid, int first, hipStream_t);
 int k_wav_normalize(avcer_ctx*, const float* x, float* y, int n, int t, hipStream_t);
 int k_conv0_ln_gelu(avcer_ctx*, const float* x, const float* w, const float* b, const float* g, const float* beta,
-                    void* y, int n, int t_in, int t_out, int bf16, hipStream_t);
+                    void* y, int n, int t_in, int t_out, int kind, hipStream_t);
 int k_layernorm(avcer_ctx*, const void* x, const void* res, const float* g, const float* b, void* yf, void* yb,
                 int64_t rows, int c, float eps, int act, int in_kind, int yb_kind, hipStream_t);
 int k_add_pe(avcer_ctx*, const float* x, const float* pe, float* yf, void* yb, int n, int s, int c, int yb_kind, hipStream_t);

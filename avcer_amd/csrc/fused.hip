@@ -1411,7 +1411,7 @@ int measure_ceilings(avcer_ctx* ctx, double* mfma_bf16_tflops, double* hbm_copy_
     HIP_TRY(ctx, hipEventCreate(&e1));
     void* buf = nullptr;
     const size_t bytes = (size_t)1 << 30;  // 1 GiB source + 1 GiB destination: far beyond the 256 MiB memory-side cache
-    TRY(ws_reserve(ctx, 5, 2 * bytes, &buf));
+    TRY(ws_reserve(ctx, WS_CEILINGS, 2 * bytes, &buf));
     float ms = 0.f;
     const int blocks = 256 * 2, iters = 20000;
     mfma_rate_kernel<<<blocks, 256, 0, st>>>((float*)buf, 2000);  // warm-up (clock ramp)
