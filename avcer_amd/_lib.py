@@ -32,7 +32,7 @@ class ConvDesc(C.Structure):
     ]
 
 
-ABI_VERSION = 6          # include/avcer_hip.h AVCER_ABI_VERSION: struct layouts, argument lists and buffer sizes below
+ABI_VERSION = 7          # include/avcer_hip.h AVCER_ABI_VERSION: struct layouts, argument lists and buffer sizes below
 SPLIT_TRAILER = 256      # include/avcer_hip.h AVCER_SPLIT_TRAILER: bytes behind a split weight matrix (its scale)
 
 # name -> (restype, argtypes); exactly the symbols include/avcer_hip.h declares
@@ -63,6 +63,8 @@ SIGNATURES = {
                                      c_stream]),
     "avcer_resample": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                  C.c_int, C.c_void_p, C.c_int64, c_stream]),
+    "avcer_weight_search_counts": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                             C.c_void_p, C.c_void_p, c_stream]),
     "avcer_audio_frame_mean": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                          C.c_void_p, C.c_void_p, c_stream]),
     "avcer_load_face": (C.c_int, [c_ctx, C.c_void_p, C.c_size_t]),

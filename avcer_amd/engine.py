@@ -290,6 +290,31 @@ class Engine:
                                                 _ptr(out), n_out, self._stream()))
         return out
 
+    def weight_search_counts(self, preds, labels, weights):
+        """Per-candidate argmax counts of the fusion weight search in one launch (include/avcer_hip.h
+        avcer_weight_search_counts; data/utils.py:151-154, :176, :200).  preds [M, N, C] probability tables, labels [N],
+        weights [W, M, C]; returns (tp, pred), int32 [W, C] on the device: how often candidate k's weighted sum picks class j
+        and is right / picks class j.  Inputs are converted to float64 / int32 first -- numpy promotes a float32 table times a
+        float64 weight the same way, so float32 tables give the reference's bits.  Shapes outside 1 <= M <= 4, 2 <= C <= 8,
+        1 <= N < 2^31, 1 <= W <= 2^24 raise ValueError.  No host synchronisation."""
+        p = self._dev(preds, torch.float64)
+        wt = self._dev(weights, torch.float64)
+        lab = self._dev(labels, torch.int32)
+        if p.dim() != 3 or wt.dim() != 3 or lab.dim() != 1:
+            raise ValueError(f"weight search: preds [M, N, C], labels [N], weights [W, M, C] expected, got {tuple(p.shape)}, "
+                             f"{tuple(lab.shape)}, {tuple(wt.shape)}")
+        m, n, c = (int(s) for s in p.shape)
+        w = int(wt.shape[0])
+        if tuple(wt.shape[1:]) != (m, c) or int(lab.shape[0]) != n:
+            raise ValueError(f"weight search: preds {tuple(p.shape)}, labels {tuple(lab.shape)} and weights {tuple(wt.shape)} disagree")
+        if not (1 <= m <= 4 and 2 <= c <= 8 and 1 <= n <= 2 ** 31 - 1 and 1 <= w <= 2 ** 24):
+            raise ValueError(f"weight search: {m} models (1..4), {c} classes (2..8), {n} frames (1..2^31-1), {w} candidates (1..2^24)")
+        tp = self._new(w, c, dtype=torch.int32)
+        pred = self._new(w, c, dtype=torch.int32)
+        self._check(self.lib.avcer_weight_search_counts(self.ctx, _ptr(p), _ptr(lab), n, m, c, _ptr(wt), w, _ptr(tp), _ptr(pred),
+                                                        self._stream()))
+        return tp, pred
+
     def audio_frame_mean(self, win_logits, frame_lo, frame_hi, n_frames: int):
         x = self._dev(win_logits, torch.float32)
         lo, hi = self._dev(frame_lo, torch.int32), self._dev(frame_hi, torch.int32)

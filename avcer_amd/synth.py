@@ -286,3 +286,23 @@ def to_torch(sd):
     import torch
 
     return OrderedDict((k, torch.from_numpy(np.ascontiguousarray(v))) for k, v in sd.items())
+
+
+# --------------------------------------------------------------------------- fusion weight search
+def fusion_tables(seed: int, n_frames: int, n_models: int, n_classes: int = 7, label_classes: int | None = None, agree: float = 0.55):
+    """Validation tables for the fusion weight search: labels int64 [n_frames] uniform over range(label_classes) (default
+    n_classes; one more puts a class into the labels that no model predicts) and float32 probability tables
+    [n_models, n_frames, n_classes], rows summing to 1 within float32 rounding.  Each model favours the frame's label on a
+    fraction `agree` of the frames and is skewed noise elsewhere, so that candidates differ in a few frames and ties between
+    their metrics are common at small n_frames.  Every step is elementwise float32: the same bits on every machine."""
+    lc = n_classes if label_classes is None else label_classes
+    labels = (raw_u64(seed, "ws_labels", n_frames) % _U64(lc)).astype(np.int64)
+    u = uniform01(seed, "ws_probs", n_models * n_frames * n_classes).reshape(n_models, n_frames, n_classes)
+    e = u * u
+    right = uniform01(seed, "ws_agree", n_models * n_frames).reshape(n_models, n_frames) < np.float32(agree)
+    onehot = labels[None, :, None] == np.arange(n_classes)[None, None, :]
+    e = e + (right[:, :, None] & onehot).astype(np.float32)
+    s = e[..., 0].copy()
+    for c in range(1, n_classes):
+        s = s + e[..., c]
+    return labels, (e / s[..., None]).astype(np.float32)

@@ -69,8 +69,9 @@ enum {
  *   4: avcer_source_hash, avcer_set_static_back_batch, avcer_set_static_lanes, avcer_set_static_lane_range, avcer_face_decode_batch, avcer_track_faces,
  *      avcer_lsap, avcer_profile_read_launches (round 6).
  *   5: avcer_static_forward_cam, avcer_crop_resize_linear, avcer_cam_render (Grad-CAM heat maps).
- *   6: avcer_resample (source audio -> mono at the model's rate). */
-#define AVCER_ABI_VERSION 6
+ *   6: avcer_resample (source audio -> mono at the model's rate).
+ *   7: avcer_weight_search_counts (fusion weight search: per-candidate argmax counts). */
+#define AVCER_ABI_VERSION 7
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
  * avcer_amd/build.py (source_hash()).  The Python binding refuses a library whose hash differs from the tree's, and bench.py
@@ -200,6 +201,31 @@ enum { AVCER_PCM_S16_INTERLEAVED = 0, AVCER_PCM_F32_PLANAR = 1 };
 #define AVCER_RESAMPLE_MAX_LEN 2147483647LL
 int avcer_resample(avcer_ctx* ctx, const void* src, int src_kind, int64_t len, int channels, const float* taps,
                    const int32_t* first, int o, int n, int span, int width, float* out, int64_t n_out, avcer_stream_t stream);
+
+/* Fusion weight search: for each of `w` candidate weight sets, how often the weighted sum of `m` probability tables picks each
+ * class, and how often that pick is the label.  The reference's objective (get_metrics_for_fusion: precision, F1 and recall of
+ * classes 1..6 from sklearn's classification_report) is a function of these integers and the labels' own histogram, which
+ * avcer_amd/weight_search.py evaluates on the host: no tolerance is involved anywhere.
+ *   ref: data/utils.py:151-154 (get_weights_prob_model: predictions[0] * weights[k, 0], then += predictions[i] * weights[k, i],
+ *        np.argmax(axis=-1)), :176 (get_weights_v_model) and :200 (get_weights_av_model: the same sum with one scalar weight per
+ *        model), :115-122 (get_metrics_for_fusion); driven from get_pred_video.py:346-390 and get_pred_av.py:339-405
+ * preds f64 [m][n][c], labels i32 [n], weights f64 [w][m][c] (a grid candidate repeats its scalar over the classes), all on the
+ * device.  Per frame i and candidate k, in f64 with numpy's operation order:
+ *   f[j] = preds[0][i][j] * weights[k][0][j];   f[j] = f[j] + preds[q][i][j] * weights[k][q][j]  for q = 1 .. m-1
+ * where every product and every sum rounds on its own (no FMA contraction: a fused sum moves near-ties to another class);
+ *   a = the first index of the maximum of f, a NaN counting as the maximum (np.argmax: the first NaN wins);
+ *   pred[k][a] += 1;   tp[k][a] += 1 if labels[i] == a.   A label outside [0, c) matches no class and counts in no tp.
+ * tp, pred i32 [w][c]: zeroed by the call itself in stream order, then accumulated with integer atomics, so a result does not
+ * depend on the order of the blocks and two calls give the same bits.  Candidates are independent: any split of `w` into
+ * several calls gives the same rows.
+ * Limits (AVCER_EINVAL beyond them): 1 <= m <= AVCER_SEARCH_MAX_MODELS, 2 <= c <= AVCER_SEARCH_MAX_CLASSES,
+ * 1 <= n <= AVCER_SEARCH_MAX_FRAMES, 1 <= w <= AVCER_SEARCH_MAX_CANDIDATES.  No host synchronisation. */
+#define AVCER_SEARCH_MAX_MODELS 4
+#define AVCER_SEARCH_MAX_CLASSES 8
+#define AVCER_SEARCH_MAX_FRAMES 2147483647LL
+#define AVCER_SEARCH_MAX_CANDIDATES 16777216
+int avcer_weight_search_counts(avcer_ctx* ctx, const double* preds, const int32_t* labels, int64_t n, int m, int c,
+                               const double* weights, int w, int32_t* tp, int32_t* pred, avcer_stream_t stream);
 
 /* Per-frame mean of window logits.
  *   ref: get_prob_audio_8_cl.py:94-101 (logits replicated for frames [lo,hi) of each window),
