@@ -32,7 +32,7 @@ class ConvDesc(C.Structure):
     ]
 
 
-ABI_VERSION = 7          # include/avcer_hip.h AVCER_ABI_VERSION: struct layouts, argument lists and buffer sizes below
+ABI_VERSION = 8          # include/avcer_hip.h AVCER_ABI_VERSION: struct layouts, argument lists and buffer sizes below
 SPLIT_TRAILER = 256      # include/avcer_hip.h AVCER_SPLIT_TRAILER: bytes behind a split weight matrix (its scale)
 
 # name -> (restype, argtypes); exactly the symbols include/avcer_hip.h declares
@@ -59,6 +59,11 @@ SIGNATURES = {
     "avcer_dynamic_forward_mode": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_void_p, c_stream]),
     "avcer_audio_forward": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, c_stream]),
     "avcer_audio_num_classes": (C.c_int, [c_ctx]),
+    "avcer_audio_head_kind": (C.c_int, [c_ctx]),
+    "avcer_audio_forward_features": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                               c_stream]),
+    "avcer_gru_layer": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                  c_stream]),
     "avcer_audio_chunks": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                      c_stream]),
     "avcer_resample": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,

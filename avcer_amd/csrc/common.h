@@ -23,7 +23,7 @@ struct DevBuf {
 
 // the context's workspace slots (ws_reserve): one per pipeline, the second lanes of the two ResNets and two utilities
 enum { WS_STATIC = 0, WS_DYNAMIC = 1, WS_AUDIO = 2, WS_FACE = 3, WS_NMS = 4, WS_CEILINGS = 5, WS_STATIC_LANE1 = 6, WS_FACE_LANE1 = 7,
-       WS_COUNT = 8 };
+       WS_GRU = 8, WS_COUNT = 9 };
 
 // how an activation tensor is stored (the `kind` / `act` arguments of the k_* launchers, Net::gemm's akind / okind)
 enum { KIND_F32 = 0, KIND_BF16 = 1, KIND_SP32 = 2 };
@@ -55,6 +55,7 @@ struct avcer_ctx {
     char err[512] = {0};
     Model stat, dyn, aud, face;
     int aud_classes = 0;
+    int aud_head = 0;         // head of the loaded audio model (avcer_audio_head_kind): 0 none, 1 GRU (ExprModelV1), 3 transformer (V2 / V3)
     int static_batch = 1024;  // frames per internal pass of the static CNN (4 GiB buffer-descriptor limit at f32)
     int static_back = 0;      // frames per back pass of the static CNN (0: two front passes; avcer_set_static_back_batch)
     int static_lanes = 2;     // calls of lane_min .. lane_max frames as two half-batches on two streams (avcer_set_static_lanes)
@@ -111,7 +112,7 @@ int launch_conv_gemm(avcer_ctx* ctx, const avcer_conv_desc& d, int dtype, const 
                      const void* x2 = nullptr);
 
 // kernel families of the MFMA launches (avcer_profile_read_families; include/avcer_hip.h AVCER_FAM_*)
-enum { FAM_GEMM = 0, FAM_GEMM_WD = 1, FAM_CHAIN = 2, FAM_TAIL = 3, FAM_STEM = 4, FAM_SKINNY = 5, FAM_COUNT = 6 };
+enum { FAM_GEMM = 0, FAM_GEMM_WD = 1, FAM_CHAIN = 2, FAM_TAIL = 3, FAM_STEM = 4, FAM_SKINNY = 5, FAM_GRU = 6, FAM_COUNT = 7 };
 // `flops` / `bytes`: algorithmic work and compulsory HBM traffic of the launch (operands read once + outputs written once)
 int prof_begin(avcer_ctx* ctx, hipStream_t st, hipEvent_t* ev0, hipEvent_t* ev1, int family, double flops, double bytes, long M = 0,
                long N = 0, long K = 0);
@@ -149,6 +150,13 @@ int launch_bneck(avcer_ctx* ctx, int planes, int nb, int h, int w, const void* t
 // conv3 + residual + ReLU of a planes-256 bottleneck and conv1 of the next block in one launch (t2 = conv2 output [M][256])
 int launch_bneck_tail(avcer_ctx* ctx, int planes, long M, const void* t2, const void* x, void* out, void* t1n, const void* w3,
                       const float* b3, const void* w1n, const float* b1n, hipStream_t st);
+
+// ---- gru.hip
+// The recurrence of one GRU layer (hidden size 256) over S steps in one launch: xp [n, S, 768] f32 (input projections + b_ih,
+// gates r, z, n), w = W_hh [768][256] as f32 (x3 = 0) or as the fragment-order split copy (x3 = 1), bhh [768] ->
+// h_seq [n, S, 256] f32 and, x3 only, h_sp: the same as sp32 pairs (or null)
+int launch_gru_layer(avcer_ctx* ctx, const float* xp, const void* w, int x3, const float* bhh, int n, int S, float* h_seq, void* h_sp,
+                     hipStream_t st);
 
 int measure_ceilings(avcer_ctx* ctx, double* mfma_bf16_tflops, double* hbm_copy_tbs, hipStream_t st);
 

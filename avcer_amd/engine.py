@@ -116,6 +116,11 @@ class Engine:
         self._load(self.lib.avcer_load_audio, packing.pack_audio(state_dict))
         self.audio_classes = self.lib.avcer_audio_num_classes(self.ctx)
 
+    @property
+    def audio_head_kind(self) -> int:
+        """Head of the loaded audio model: 0 none, 1 the GRU of ExprModelV1, 3 the TransformerLayers of ExprModelV2 / V3."""
+        return int(self.lib.avcer_audio_head_kind(self.ctx))
+
     def load_face(self, state_dict):
         self._load(self.lib.avcer_load_face, packing.pack_face(state_dict))
 
@@ -205,13 +210,29 @@ class Engine:
                                                         self._stream()))
         return out
 
-    def audio_forward(self, wav, normalize: bool = True, mode: int = MODE_DEFAULT):
+    def audio_forward(self, wav, normalize: bool = True, mode: int = MODE_DEFAULT, return_features: bool = False):
+        """wav [N,T] -> logits [N,C]; return_features: (logits, the pooled head activations [N, 256 (ExprModelV1) or 1024])."""
         x = self._dev(wav, torch.float32)
         if x.dim() != 2:
             raise ValueError(f"wav must be [N,T], got {tuple(x.shape)}")
         out = self._new(x.shape[0], self.audio_classes)
-        self._check(self.lib.avcer_audio_forward(self.ctx, _ptr(x), int(x.shape[0]), int(x.shape[1]), int(normalize),
-                                                 mode, _ptr(out), self._stream()))
+        if not return_features:
+            self._check(self.lib.avcer_audio_forward(self.ctx, _ptr(x), int(x.shape[0]), int(x.shape[1]), int(normalize),
+                                                     mode, _ptr(out), self._stream()))
+            return out
+        feats = self._new(x.shape[0], 256 if self.audio_head_kind == 1 else 1024)
+        self._check(self.lib.avcer_audio_forward_features(self.ctx, _ptr(x), int(x.shape[0]), int(x.shape[1]), int(normalize),
+                                                          mode, _ptr(out), _ptr(feats), self._stream()))
+        return out, feats
+
+    def gru_layer(self, xp, w_hh, b_hh, mode: int = MODE_DEFAULT):
+        """One GRU layer's recurrence (avcer_gru_layer): xp [N,S,768] = x W_ih^T + b_ih, w_hh [768,256], b_hh [768] -> h [N,S,256]."""
+        xp, w_hh, b_hh = self._dev(xp, torch.float32), self._dev(w_hh, torch.float32), self._dev(b_hh, torch.float32)
+        if xp.dim() != 3 or xp.shape[2] != 768 or tuple(w_hh.shape) != (768, 256) or tuple(b_hh.shape) != (768,):
+            raise ValueError("gru_layer: xp [N,S,768], w_hh [768,256], b_hh [768]")
+        out = self._new(xp.shape[0], xp.shape[1], 256)
+        self._check(self.lib.avcer_gru_layer(self.ctx, _ptr(xp), _ptr(w_hh), _ptr(b_hh), int(xp.shape[0]), int(xp.shape[1]), 256,
+                                             int(mode), _ptr(out), self._stream()))
         return out
 
     def audio_chunks(self, wav, starts, ends, window: int, padding: str = "mean"):
@@ -469,7 +490,7 @@ class Engine:
         return ms.value, n.value
 
     FAMILIES = ("conv_gemm_kernel", "conv_gemm_wd_kernel", "bneck_kernel", "bneck_tail2_kernel", "stem_pool_kernel",
-                "conv_gemm_skinny_kernel")  # AVCER_FAM_*
+                "conv_gemm_skinny_kernel", "gru_layer_kernel")  # AVCER_FAM_*
 
     def profile_read_families(self):
         """Per kernel family since profile_enable / the last read: {name: (event ms, launches, algorithmic FLOPs, compulsory

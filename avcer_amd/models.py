@@ -76,7 +76,9 @@ class DynamicModel:
 
 
 class AudioModel:
-    """Drop-in for `audio_model` (architectures/audio_8_cl.py ExprModelV3 / audio_7_cl.py ExprModelV2, eval mode).
+    """Drop-in for `audio_model`: every head the reference builds on the wav2vec2 trunk, in eval mode -- ExprModelV3 (8 classes,
+    architectures/audio_8_cl.py:131-190), ExprModelV2 (the 7-class twin, audio_7_cl.py) and ExprModelV1 (the two-layer GRU head,
+    audio_8_cl.py:18-72 / audio_7_cl.py:18-72); which one is decided by the state dict's keys (packing.pack_audio).
     Input is the already normalised window, exactly what the reference passes (get_prob_audio_8_cl.py:87-92)."""
 
     def __init__(self, engine: Engine, state_dict, mode: int = MODE_DEFAULT):
@@ -99,3 +101,12 @@ class AudioModel:
         return out.squeeze(0) if out.shape[0] == 1 else out  # `x.squeeze()` at audio_8_cl.py:188
 
     forward = __call__
+
+    def get_features(self, x: torch.Tensor, normalize: bool = False):
+        """(logits, features) as the reference's get_features (audio/models/audio_expr_models.py:180-191): features = the pooled
+        head activations, `.squeeze()`d like the logits ([N,256] for ExprModelV1, [N,1024] otherwise; 1-D for one window)."""
+        if x.dim() == 1:
+            x = x[None]
+        out, feats = self.engine.guarded(
+            self.mode, lambda m: self.engine.audio_forward(x, normalize=normalize, mode=m, return_features=True))
+        return (out.squeeze(0), feats.squeeze(0)) if out.shape[0] == 1 else (out, feats)

@@ -225,7 +225,8 @@ def pos_conv_weight(sd) -> np.ndarray:
 
 
 def pack_audio(sd) -> "OrderedDict[str, np.ndarray]":
-    """ExprModelV3 / ExprModelV2 state_dict (architectures/audio_8_cl.py:131-190, audio_7_cl.py), bare or inside the
+    """ExprModelV3 / ExprModelV2 state_dict (architectures/audio_8_cl.py:131-190, audio_7_cl.py) or the GRU-head ExprModelV1's
+    (audio_8_cl.py:18-72, audio_7_cl.py:18-72: recognised by its gru.weight_ih_l0 key, the others by tl1.*), bare or inside the
     trainer's {"model_state_dict": ...} checkpoint; the positional-conv weight norm in any of its three spellings
     (torch >= 2.1 parametrizations.weight.original0/1, torch 2.0-style weight_g / weight_v as the published checkpoint was
     written under torch 2.1.2 + transformers 4.36.2, or an already materialised .weight)."""
@@ -257,6 +258,18 @@ def pack_audio(sd) -> "OrderedDict[str, np.ndarray]":
         out[f"enc{l}.ff1.w"], out[f"enc{l}.ff1.b"] = _f32(sd[f + "intermediate_dense.weight"]), _f32(sd[f + "intermediate_dense.bias"])
         out[f"enc{l}.ff2.w"], out[f"enc{l}.ff2.b"] = _f32(sd[f + "output_dense.weight"]), _f32(sd[f + "output_dense.bias"])
     out["enc.ln.g"], out["enc.ln.b"] = _f32(sd[w2 + "encoder.layer_norm.weight"]), _f32(sd[w2 + "encoder.layer_norm.bias"])
+    gru, tl = "gru.weight_ih_l0" in sd, any(k.startswith("tl1.") for k in sd)
+    if gru == tl:
+        raise KeyError("pack_audio: the state dict holds " + ("both a GRU head (gru.*) and a transformer head (tl1.*)" if gru else
+                       "neither a GRU head (gru.weight_ih_l0: ExprModelV1) nor a transformer head (tl1.*: ExprModelV2 / V3)"))
+    if gru:
+        # nn.GRU(1024, 256, num_layers=2), gate order r, z, n.  bias_ih rides on the input projection; bias_hh stays separate:
+        # its n part sits inside the r product (torch.nn.GRU), so the two cannot be merged as the LSTM's are
+        for l in (0, 1):
+            out[f"gru{l + 1}.wih.w"], out[f"gru{l + 1}.wih.b"] = _f32(sd[f"gru.weight_ih_l{l}"]), _f32(sd[f"gru.bias_ih_l{l}"])
+            out[f"gru{l + 1}.whh.w"], out[f"gru{l + 1}.whh.b"] = _f32(sd[f"gru.weight_hh_l{l}"]), _f32(sd[f"gru.bias_hh_l{l}"])
+        _pack_audio_head(sd, out)
+        return out
     pe = _f32(sd["tl1.positional_encoding.pe"]).reshape(-1, 1024)
     out["pe"] = np.ascontiguousarray(pe[:PE_ROWS])
     for l in (1, 2):
@@ -272,12 +285,17 @@ def pack_audio(sd) -> "OrderedDict[str, np.ndarray]":
         out[f"tl{l}.ln2.g"] = _f32(sd[t + "add_norm_after_ff.layer_norm.weight"])
         out[f"tl{l}.ln2.b"] = _f32(sd[t + "add_norm_after_ff.layer_norm.bias"])
         # tl{l}.feed_forward.layer_norm.* exists in the state_dict but is never applied (attention_layers.py:46,50-57)
+    _pack_audio_head(sd, out)
+    return out
+
+
+def _pack_audio_head(sd, out) -> None:
+    """time_downsample (BN folded into scale / bias) and feature_downsample, at the head's own width (1024, or 256 behind the GRU)"""
     out["td0.w"] = _conv1d_w(sd["time_downsample.0.weight"])
     out["td0.s"], out["td0.b"] = _bn_fold(sd, "time_downsample.1", AUDIO_BN_EPS, sd["time_downsample.0.bias"])
     out["td4.w"] = _conv1d_w(sd["time_downsample.4.weight"])
     out["td4.s"], out["td4.b"] = _bn_fold(sd, "time_downsample.5", AUDIO_BN_EPS, sd["time_downsample.4.bias"])
     out["fd.w"], out["fd.b"] = _f32(sd["feature_downsample.weight"]), _f32(sd["feature_downsample.bias"])
-    return out
 
 
 def to_blob(tensors: "OrderedDict[str, np.ndarray]") -> bytes:

@@ -233,6 +233,23 @@ def audio_state_dict(seed: int = 42, num_classes: int = 8) -> "OrderedDict[str, 
     """Keys of architectures/audio_8_cl.py:131-190 ExprModelV3(config).state_dict() with the
     audeering/wav2vec2-large-robust-12-ft-emotion-msp-dim config."""
     sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    _wav2vec2(sd, seed)
+    pe = positional_encoding()
+    for tl in ("tl1", "tl2"):
+        for name in ("query_w", "keys_w", "values_w", "ff_layer_after_concat"):
+            _linear(sd, seed, f"{tl}.self_attention.{name}", 1024, 1024, bias=False, gain=2.0)
+        _linear(sd, seed, f"{tl}.feed_forward.layer_1", 1024, 1024, gain=2.0)
+        _linear(sd, seed, f"{tl}.feed_forward.layer_2", 1024, 1024)
+        _ln(sd, seed, f"{tl}.feed_forward.layer_norm", 1024)  # present in the state_dict, never applied
+        _ln(sd, seed, f"{tl}.add_norm_after_attention.layer_norm", 1024)
+        _ln(sd, seed, f"{tl}.add_norm_after_ff.layer_norm", 1024)
+        sd[f"{tl}.positional_encoding.pe"] = pe
+    _time_downsample(sd, seed, 1024, num_classes)
+    return sd
+
+
+def _wav2vec2(sd, seed: int) -> None:
+    """The wav2vec2.* keys (every value a function of seed and key name alone: the same trunk for every head)."""
     w = "wav2vec2."
     sd[w + "masked_spec_embed"] = uniform(seed, w + "masked_spec_embed", (W2V_HIDDEN,), 0.0, 1.0)
     cin = 1
@@ -259,26 +276,38 @@ def audio_state_dict(seed: int = 42, num_classes: int = 8) -> "OrderedDict[str, 
         _linear(sd, seed, p + ".feed_forward.intermediate_dense", W2V_FFN, W2V_HIDDEN, gain=2.0)
         _linear(sd, seed, p + ".feed_forward.output_dense", W2V_HIDDEN, W2V_FFN)
         _ln(sd, seed, p + ".final_layer_norm", W2V_HIDDEN)
-    pe = positional_encoding()
-    for tl in ("tl1", "tl2"):
-        for name in ("query_w", "keys_w", "values_w", "ff_layer_after_concat"):
-            _linear(sd, seed, f"{tl}.self_attention.{name}", 1024, 1024, bias=False, gain=2.0)
-        _linear(sd, seed, f"{tl}.feed_forward.layer_1", 1024, 1024, gain=2.0)
-        _linear(sd, seed, f"{tl}.feed_forward.layer_2", 1024, 1024)
-        _ln(sd, seed, f"{tl}.feed_forward.layer_norm", 1024)  # present in the state_dict, never applied
-        _ln(sd, seed, f"{tl}.add_norm_after_attention.layer_norm", 1024)
-        _ln(sd, seed, f"{tl}.add_norm_after_ff.layer_norm", 1024)
-        sd[f"{tl}.positional_encoding.pe"] = pe
+
+
+def _time_downsample(sd, seed: int, c: int, num_classes: int) -> None:
+    """time_downsample (conv, BN, conv, BN) and feature_downsample at head width c"""
     td = "time_downsample"
-    sd[td + ".0.weight"] = centered(seed, td + ".0.weight", (1024, 1024, 5), math.sqrt(2.0 / (1024 * 5)))
-    sd[td + ".0.bias"] = uniform(seed, td + ".0.bias", (1024,), -0.05, 0.05)
-    _bn(sd, seed, td + ".1", 1024)
-    sd[td + ".4.weight"] = centered(seed, td + ".4.weight", (1024, 1024, 3), math.sqrt(2.0 / (1024 * 3)))
-    sd[td + ".4.bias"] = uniform(seed, td + ".4.bias", (1024,), -0.05, 0.05)
-    _bn(sd, seed, td + ".5", 1024)
+    sd[td + ".0.weight"] = centered(seed, td + ".0.weight", (c, c, 5), math.sqrt(2.0 / (c * 5)))
+    sd[td + ".0.bias"] = uniform(seed, td + ".0.bias", (c,), -0.05, 0.05)
+    _bn(sd, seed, td + ".1", c)
+    sd[td + ".4.weight"] = centered(seed, td + ".4.weight", (c, c, 3), math.sqrt(2.0 / (c * 3)))
+    sd[td + ".4.bias"] = uniform(seed, td + ".4.bias", (c,), -0.05, 0.05)
+    _bn(sd, seed, td + ".5", c)
     sd["feature_downsample.weight"] = centered(
-        seed, "feature_downsample.weight", (num_classes, 1024), math.sqrt(16.0 / 1024))
+        seed, "feature_downsample.weight", (num_classes, c), math.sqrt(16.0 / c))
     sd["feature_downsample.bias"] = uniform(seed, "feature_downsample.bias", (num_classes,), -0.2, 0.2)
+
+
+GRU_HIDDEN = 256
+
+
+def audio_v1_state_dict(seed: int = 42, num_classes: int = 8) -> "OrderedDict[str, np.ndarray]":
+    """Keys of architectures/audio_8_cl.py:18-72 ExprModelV1(config).state_dict() (audio_7_cl.py:18-72 with num_classes=7):
+    the same wav2vec2 trunk as audio_state_dict -- bit for bit at the same seed --, nn.GRU(1024, 256, num_layers=2) and the conv head
+    at width 256.  GRU weights and biases are uniform in +-1/sqrt(256), torch's own initialisation scale, so that the gates
+    neither saturate nor vanish and the recurrent term carries its share of the output."""
+    sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    _wav2vec2(sd, seed)
+    k = 1.0 / math.sqrt(GRU_HIDDEN)
+    for l, cin in enumerate((W2V_HIDDEN, GRU_HIDDEN)):
+        for name, shape in ((f"weight_ih_l{l}", (3 * GRU_HIDDEN, cin)), (f"weight_hh_l{l}", (3 * GRU_HIDDEN, GRU_HIDDEN)),
+                            (f"bias_ih_l{l}", (3 * GRU_HIDDEN,)), (f"bias_hh_l{l}", (3 * GRU_HIDDEN,))):
+            sd["gru." + name] = uniform(seed, "gru." + name, shape, -k, k)
+    _time_downsample(sd, seed, GRU_HIDDEN, num_classes)
     return sd
 
 

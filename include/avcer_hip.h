@@ -70,8 +70,9 @@ enum {
  *      avcer_lsap, avcer_profile_read_launches (round 6).
  *   5: avcer_static_forward_cam, avcer_crop_resize_linear, avcer_cam_render (Grad-CAM heat maps).
  *   6: avcer_resample (source audio -> mono at the model's rate).
- *   7: avcer_weight_search_counts (fusion weight search: per-candidate argmax counts). */
-#define AVCER_ABI_VERSION 7
+ *   7: avcer_weight_search_counts (fusion weight search: per-candidate argmax counts).
+ *   8: avcer_audio_head_kind, avcer_audio_forward_features, avcer_gru_layer, AVCER_FAM_GRU (the GRU-head audio model ExprModelV1). */
+#define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
  * avcer_amd/build.py (source_hash()).  The Python binding refuses a library whose hash differs from the tree's, and bench.py
@@ -159,6 +160,17 @@ int avcer_dynamic_forward_mode(avcer_ctx* ctx, const float* windows, int n, int 
 int avcer_audio_forward(avcer_ctx* ctx, const float* wav, int n, int t, int normalize, int mode,
                         float* logits, avcer_stream_t stream);
 int avcer_audio_num_classes(const avcer_ctx* ctx);
+/* Which head the loaded audio weights hold, recognised by avcer_load_audio from the blob's tensor names: 0 = no audio model
+ * loaded, 1 = the two-layer GRU of ExprModelV1 (gru1.whh.w present), 3 = the two TransformerLayers of ExprModelV2 / V3
+ * (tl1.qkv.w present).  A blob with neither or both is refused with AVCER_EINVAL.  avcer_audio_forward runs whichever is loaded.
+ *   ref: architectures/audio_8_cl.py:18-72 (ExprModelV1), :75-128 (V2), :131-190 (V3); audio_7_cl.py likewise */
+int avcer_audio_head_kind(const avcer_ctx* ctx);
+/* avcer_audio_forward that also copies out the pooled head activations (after AdaptiveAvgPool1d(1) + ReLU, before the last
+ * Linear): features f32 [n, 256] for ExprModelV1, [n, 1024] for V2 / V3; may be NULL (then this IS avcer_audio_forward).
+ *   ref: the second value of the reference's get_features, audio/models/audio_expr_models.py:180-191,
+ *        audio_expr_models_7_cl.py:63,130,205; consumed at net_trainer.py:512 */
+int avcer_audio_forward_features(avcer_ctx* ctx, const float* wav, int n, int t, int normalize, int mode,
+                                 float* logits, float* features, avcer_stream_t stream);
 
 /* Window slicing + padding of one waveform.
  *   ref: get_prob_audio_8_cl.py:78-86, data/utils.py:63-71 (pad_wav, "repeat"), :74-89 (pad_wav_zeros, "mean"/"constant")
@@ -453,6 +465,14 @@ int avcer_weight_frags(avcer_ctx* ctx, const void* rows, void* out, int n, int k
  * the fused q / k / v projection); out [n, s, heads * head_dim].  head_dim 64 or 32, s <= 256.  Storage kinds: 0 = f32,
  * 1 = bf16, 2 = sp32.  (in 0, out 0): exact f32 arithmetic on the VALU; (in 1, out 1): bf16 operands on the MFMA;
  * (in 0, out 2): what AVCER_MODE_F16X3 runs -- f32 in, sp32 out (see the kernel for its arithmetic). */
+/* The recurrence of one torch.nn.GRU layer on caller tensors (device pointers, f32), ONE launch with the time loop inside
+ * (csrc/gru.hip): xp [n, s, 3h] = x W_ih^T + b_ih for all steps (gate order r, z, n), w_hh [3h, h], b_hh [3h] ->
+ * h_seq [n, s, h], h_0 = 0.  h must be 256 (AVCER_EINVAL otherwise).  AVCER_MODE_F16X3 runs the recurrent contraction on the
+ * split-fp16 MFMA (w_hh is split and put into fragment order inside the call), the other two modes on the f32 MFMA.
+ *   ref: architectures/audio_8_cl.py:26,64 (nn.GRU(1024, 256, num_layers=2, batch_first=True)) */
+int avcer_gru_layer(avcer_ctx* ctx, const float* xp, const float* w_hh, const float* b_hh, int n, int s, int h, int mode,
+                    float* h_seq, avcer_stream_t stream);
+
 int avcer_attention(avcer_ctx* ctx, const void* qkv, void* out, int n, int s, int heads, int head_dim, float scale,
                     int in_kind, int out_kind, avcer_stream_t stream);
 
@@ -482,7 +502,8 @@ enum {
     AVCER_FAM_TAIL = 3,    /* bneck_tail2_kernel: conv3 + residual + next conv1 of stage 3 */
     AVCER_FAM_STEM = 4,    /* stem_pool(_u8)_kernel */
     AVCER_FAM_SKINNY = 5,  /* conv_gemm_skinny_kernel: one wave per tile, registers only (dtype 9 / 10; launches of few positions) */
-    AVCER_FAM_COUNT = 6
+    AVCER_FAM_GRU = 6,     /* gru_layer_kernel: a GRU layer's whole recurrence, one block per 16 windows (ExprModelV1's head) */
+    AVCER_FAM_COUNT = 7
 };
 int avcer_profile_read_families(avcer_ctx* ctx, int n_fam, double* ms, int64_t* launches, double* flops, double* bytes);
 /* ... and launch by launch, in launch order (tools/wd_traffic.py matches this list with the dispatches of a rocprofv3 --pmc pass of
