@@ -93,6 +93,8 @@ SIGNATURES = {
                                    C.c_void_p, c_stream]),
     "avcer_fuse": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                              C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_stream]),
+    "avcer_fuse_videos": (C.c_int, [c_ctx] + [C.c_void_p] * 8 + [C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_int, C.c_int] + [C.c_void_p] * 4 + [c_stream]),
     "avcer_conv_gemm": (C.c_int, [c_ctx, C.POINTER(ConvDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, c_stream]),
     "avcer_split_weights": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_size_t, c_stream]),

@@ -189,6 +189,10 @@ int k_frame_mean(avcer_ctx*, const float* win_logits, const int32_t* lo, const i
 int k_fuse(avcer_ctx*, const float* stat, const float* dyn, const float* aud, int n, int n_aud, int aud_c,
            const double* w /*[21] device-side by value*/, int has_w1, int cwt, int cmask, double* comp_prob,
            int32_t* comp_argmax, hipStream_t);
+int k_fuse_videos(avcer_ctx*, const float* stat, const float* dyn, const float* win, const int32_t* lo, const int32_t* hi,
+                  const int32_t* frame_off, const int32_t* win_off, const int32_t* n_aud, int n_videos, int n, int n_win, int c,
+                  const double* w, int has_w1, int cwt, int cmask, float* aud_mean, int32_t* count, double* comp_prob,
+                  int32_t* comp_argmax, hipStream_t);
 int k_pack_nchw(avcer_ctx*, const float* x, int n, void* out, int kind, hipStream_t);
 int k_gather_windows(avcer_ctx*, const float* feats, const int32_t* idx, int nwin, float* out, hipStream_t);
 int k_audio_chunks(avcer_ctx*, const float* wav, const int32_t* starts, const int32_t* ends, int n, int window, int mode,

@@ -1549,20 +1549,16 @@ __device__ __forceinline__ void softmax7(const float* in, float* out) {
 
 // run.py:85-165 + data/utils.py:222-241.  One thread per frame; float32 tables promoted to float64 at the
 // weight multiply exactly like numpy does for `float32 ndarray * python list`.
-__global__ void fuse_kernel(const float* __restrict__ stat, const float* __restrict__ dyn, const float* __restrict__ aud,
-                            int n, int n_aud, int aud_c, FuseParams fp, double* __restrict__ comp_prob,
-                            int32_t* __restrict__ comp_argmax) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= n) return;
+// Frame f of n: `al` is its audio row (mean window logits, audio order).  Shared by fuse_kernel and fuse_videos_kernel.
+__device__ __forceinline__ void fuse_frame(const float* __restrict__ stat, const float* __restrict__ dyn, const float* al, int f,
+                                           int n, const FuseParams& fp, double* __restrict__ comp_prob,
+                                           int32_t* __restrict__ comp_argmax) {
     const int order[7] = {0, 6, 5, 4, 1, 2, 3};  // video column -> audio order (get_prob_video.py:56-64, run.py:56-65)
     const int p1[7] = {3, 4, 5, 2, 1, 3, 1}, p2[7] = {6, 6, 6, 6, 6, 5, 5};  // run.py:66-74
-    float s[7], dl[7], d[7], al[7], a[7];
+    float s[7], dl[7], d[7], a[7];
 #pragma unroll
     for (int k = 0; k < 7; ++k) { s[k] = stat[(long)f * 7 + order[k]]; dl[k] = dyn[(long)f * 7 + order[k]]; }
     softmax7(dl, d);
-    const int fa = f < n_aud ? f : n_aud - 1;  // run.py:99-103 tail padding with the last audio row
-#pragma unroll
-    for (int k = 0; k < 7; ++k) al[k] = aud[(long)fa * aud_c + k];
     softmax7(al, a);
     if (fp.has_w1) {
         // float32 table * python list -> float64 (run.py:108-111)
@@ -1616,6 +1612,73 @@ __global__ void fuse_kernel(const float* __restrict__ stat, const float* __restr
             }
             comp_argmax[(long)m * n + f] = bi;
         }
+    }
+}
+
+__global__ void fuse_kernel(const float* __restrict__ stat, const float* __restrict__ dyn, const float* __restrict__ aud,
+                            int n, int n_aud, int aud_c, FuseParams fp, double* __restrict__ comp_prob,
+                            int32_t* __restrict__ comp_argmax) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n) return;
+    float al[7];
+    const int fa = f < n_aud ? f : n_aud - 1;  // run.py:99-103 tail padding with the last audio row
+#pragma unroll
+    for (int k = 0; k < 7; ++k) al[k] = aud[(long)fa * aud_c + k];
+    fuse_frame(stat, dyn, al, f, n, fp, comp_prob, comp_argmax);
+}
+
+// frame_mean_kernel's row of ONE frame f (the video's own numbering) over the video's windows [wb, we): the same additions
+// in the same (index) order, one rounding.  lo and hi do not decrease within a video (chunk_spans), which bounds the walk: it
+// starts at the first window whose span ends behind f and stops at the first that starts behind f.
+__device__ __forceinline__ int video_frame_mean(const float* __restrict__ win, const int32_t* __restrict__ lo,
+                                                const int32_t* __restrict__ hi, int wb, int we, int c, int f, float* row) {
+    int a = wb, b = we;
+    while (a < b) {
+        const int mid = a + ((b - a) >> 1);
+        if (hi[mid] > f) b = mid; else a = mid + 1;
+    }
+    double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    int cnt = 0;
+    for (int w = a; w < we && lo[w] <= f; ++w)
+        if (f < hi[w]) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (j < c) s[j] += (double)win[(long)w * c + j];
+            ++cnt;
+        }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) row[j] = cnt ? (float)(s[j] / cnt) : 0.f;
+    return cnt;
+}
+
+// frame_mean_kernel + fuse_kernel over a concatenation of videos in one launch.  One thread per frame: it finds its video by
+// binary search in frame_off, computes the audio row it fuses with from that video's windows alone (a frame behind the
+// covered prefix recomputes the row of frame n_aud[v] - 1 itself, run.py:99-103) and runs fuse_frame.
+__global__ void fuse_videos_kernel(const float* __restrict__ stat, const float* __restrict__ dyn, const float* __restrict__ win,
+                                   const int32_t* __restrict__ lo, const int32_t* __restrict__ hi,
+                                   const int32_t* __restrict__ frame_off, const int32_t* __restrict__ win_off,
+                                   const int32_t* __restrict__ n_aud, int n_videos, int n, int n_win, int c, FuseParams fp,
+                                   float* __restrict__ aud_mean, int32_t* __restrict__ count, double* __restrict__ comp_prob,
+                                   int32_t* __restrict__ comp_argmax) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n) return;
+    int a = 0, b = n_videos - 1;  // the video v with frame_off[v] <= f < frame_off[v + 1] (videos without frames are passed over)
+    while (a < b) {
+        const int mid = (a + b) >> 1;
+        if (frame_off[mid + 1] > f) b = mid; else a = mid + 1;
+    }
+    const int v = a, fl = f - frame_off[v];
+    // the offsets come from device memory: whatever they hold, no window outside [0, n_win) is read
+    const int wb = max(win_off[v], 0), we = min(win_off[v + 1], n_win);
+    const int na = n_aud[v];
+    float row[8];
+    int cnt = video_frame_mean(win, lo, hi, wb, we, c, fl < na ? fl : na - 1, row);
+    fuse_frame(stat, dyn, row, f, n, fp, comp_prob, comp_argmax);
+    if (aud_mean || count) {
+        if (fl >= na) cnt = video_frame_mean(win, lo, hi, wb, we, c, fl, row);  // what the frame's own group holds: nothing
+        if (aud_mean)
+            for (int j = 0; j < c; ++j) aud_mean[(long)f * c + j] = row[j];
+        if (count) count[f] = cnt;
     }
 }
 
@@ -1826,8 +1889,7 @@ int k_frame_mean(avcer_ctx* ctx, const float* win_logits, const int32_t* lo, con
     return AVCER_OK;
 }
 
-int k_fuse(avcer_ctx* ctx, const float* stat, const float* dyn, const float* aud, int n, int n_aud, int aud_c,
-           const double* w, int has_w1, int cwt, int cmask, double* comp_prob, int32_t* comp_argmax, hipStream_t st) {
+static FuseParams fuse_params(const double* w, int has_w1, int cwt, int cmask) {
     FuseParams fp;
     for (int i = 0; i < 21; ++i) fp.w[i] = w ? w[i] : 1.0;
     // data/utils.py:228-236 with dict_weights of run.py:116-123 (Rule 2) or 1,1
@@ -1845,8 +1907,25 @@ int k_fuse(avcer_ctx* ctx, const float* stat, const float* dyn, const float* aud
     }
     fp.has_w1 = has_w1;
     fp.cmask = cmask;
+    return fp;
+}
+
+int k_fuse(avcer_ctx* ctx, const float* stat, const float* dyn, const float* aud, int n, int n_aud, int aud_c,
+           const double* w, int has_w1, int cwt, int cmask, double* comp_prob, int32_t* comp_argmax, hipStream_t st) {
+    const FuseParams fp = fuse_params(w, has_w1, cwt, cmask);
     fuse_kernel<<<cdiv(n, 64), 64, 0, st>>>(stat, dyn, aud, n, n_aud, aud_c, fp, comp_prob, comp_argmax);
     CHECK_LAUNCH(ctx, "fuse");
+    return AVCER_OK;
+}
+
+int k_fuse_videos(avcer_ctx* ctx, const float* stat, const float* dyn, const float* win, const int32_t* lo, const int32_t* hi,
+                  const int32_t* frame_off, const int32_t* win_off, const int32_t* n_aud, int n_videos, int n, int n_win, int c,
+                  const double* w, int has_w1, int cwt, int cmask, float* aud_mean, int32_t* count, double* comp_prob,
+                  int32_t* comp_argmax, hipStream_t st) {
+    const FuseParams fp = fuse_params(w, has_w1, cwt, cmask);
+    fuse_videos_kernel<<<cdiv(n, 64), 64, 0, st>>>(stat, dyn, win, lo, hi, frame_off, win_off, n_aud, n_videos, n, n_win, c, fp,
+                                                   aud_mean, count, comp_prob, comp_argmax);
+    CHECK_LAUNCH(ctx, "fuse_videos");
     return AVCER_OK;
 }
 

@@ -1,0 +1,362 @@
+"""A set of videos of unequal length and frame rate, run as packed passes: the batch drivers of the reference
+(get_prob_video.py:207-361, get_prob_audio_8_cl.py `__main__`, run.py:192-268 in a folder loop) without one chain of launches per video.
+
+`run.run_inference` pays, per video, its own launches, host-to-device copies and range-contract read, and a 3 s video fills none
+of them.  The kernels do not depend on what surrounds a frame or a window in its batch (tests/test_gpu_visual.py, tests/test_gpu_audio.py: one frame / window against its row in a batch),
+so frames and windows of different videos share passes here and every video still gets the bits `run_inference` gives it:
+
+  stage 0, per video   detector (or given detections) -> tracker -> the tiles of track 00       (resolutions differ)
+  visual, packed       present tiles of consecutive videos -> static CNN in passes of <= max_frames_per_pass frames; a pass may
+                       end inside a video.  Tiles are dropped behind their pass; the feature and probability tables stay.
+  LSTM, ragged         `plan_clip` per video with its own fps, one index table for the set, gather + LSTM in passes
+  audio, side stream   every waveform (resampled per video where `wav_sr` is set) into ONE device buffer, `chunk_spans` per
+                       video shifted by the video's base, chunker + model in passes of <= max_windows_per_pass windows
+  fusion               ONE `Engine.fuse_videos` launch for the set
+"""
+from __future__ import annotations
+
+import time
+from dataclasses import dataclass
+from typing import Callable, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import dist as adist
+from . import io_formats
+from .audio_pipeline import chunk_spans, replicate_per_frame, resample_out_len, resample_plan
+from .engine import MODE_DEFAULT, MODE_F16X3, MODE_FP32
+from .fusion import MODEL_ORDER, covered_frames
+from .video_pipeline import plan_clip
+
+
+@dataclass
+class VideoJob:
+    """One video of a set.  The metadata (what a container's header gives) is all that planning and sharding read; `load()` is
+    called once, when the video's turn comes, and returns (frames_bgr u8 [n_frames, height, width, 3], wav) as `run_inference`
+    takes them: wav float32 [n_samples] mono at the call's `sr`, or, with `wav_sr`, the source audio at that rate with
+    n_samples frames per channel.  `detections`: per-frame detection arrays instead of the call's detector."""
+    name: str
+    n_frames: int
+    height: int
+    width: int
+    fps: float
+    n_samples: int
+    wav_sr: Optional[int] = None
+    load: Optional[Callable] = None
+    detections: Optional[Sequence[np.ndarray]] = None
+
+
+class DatasetResults(list):
+    """The per-video dicts in job order; `real_time_factor` = elapsed time of the call / summed duration of the videos that
+    ran (None where no video reported a frame rate), `passes` = the sizes of the packed passes of the last attempt."""
+    real_time_factor = None
+    passes = None
+
+
+def ragged_plan(presents, fpss):
+    """`plan_clip` over a set of videos with their own frame rates: (static_src [N], dyn_src [N], windows [n_win,10], n_feat),
+    row numbers counted through the set; -1 = the zero row, as in ClipPlan."""
+    s_src, d_src, win, fb, wb = [], [], [], 0, 0
+    for present, fps in zip(presents, fpss):
+        p = plan_clip(present, fps, fb, wb)
+        fb += int(np.asarray(present, dtype=bool).sum())
+        wb += len(p.windows)
+        s_src += p.static_src
+        d_src += p.dyn_src
+        win += p.windows
+    return (np.asarray(s_src, dtype=np.int64), np.asarray(d_src, dtype=np.int64),
+            np.asarray(win, dtype=np.int32).reshape(-1, 10), fb)
+
+
+def _n_audio(job: VideoJob, sr: int) -> int:
+    if job.wav_sr is None:
+        return int(job.n_samples)
+    plan = resample_plan(job.wav_sr, sr)
+    return resample_out_len(int(job.n_samples), plan.o, plan.n)
+
+
+def _track00(engine, job: VideoJob, dets):
+    """Tracker + crop rectangles of one video (host code): the records and the rows of track 00 in frame order."""
+    if len(dets) != job.n_frames:
+        raise ValueError("one detection array per frame")
+    records = engine.track_faces(dets, job.width, job.height, 0.4, 0.0)  # VideoTiler's tracker settings
+    if not (len(records) and (records[:, 1] == 0).any()):
+        raise FileNotFoundError("no face track 00 (os.listdir(<faces>/00) fails in the reference, get_prob_video.py:79)")
+    rows = np.where(records[:, 1] == 0)[0]
+    return records, rows[np.argsort(records[rows, 0], kind="stable")]
+
+
+def _local_tables(engine, jobs, idx, plans, detector, m, sr, window, padding, max_frames, max_windows, side, passes):
+    """Stages 0 to audio for the videos `idx` (ascending): (stat|dyn rows [sum frames, 14], window logits [sum windows, c])."""
+    dev = engine.device
+    main = torch.cuda.current_stream(dev)
+    win_a = int(window * sr)
+    w_off = np.concatenate([[0], np.cumsum([len(plans[i]["starts"]) for i in idx])]).astype(np.int64)
+    s_off = np.concatenate([[0], np.cumsum([plans[i]["n_audio"] for i in idx])]).astype(np.int64)
+    if s_off[-1] > 2 ** 31 - 1:
+        raise ValueError(f"run_dataset: {int(s_off[-1])} audio samples in one set (the chunker takes 2^31 - 1): split the set")
+    starts = np.concatenate([plans[i]["starts"] + s_off[k] for k, i in enumerate(idx)] or [np.zeros(0, np.int64)])
+    ends = np.concatenate([plans[i]["ends"] + s_off[k] for k, i in enumerate(idx)] or [np.zeros(0, np.int64)])
+    side.wait_stream(main)
+    joined = False
+    try:
+        with torch.cuda.stream(side):
+            wav_all = torch.empty(int(s_off[-1]), dtype=torch.float32, device=dev)
+        a_done, a_out = 0, []
+        pend, n_pend, feats, probs, presents = [], 0, [], [], []
+
+        def audio_passes(ready, flush):
+            nonlocal a_done
+            with torch.cuda.stream(side):
+                while ready - a_done >= (1 if flush else max_windows):
+                    b = min(a_done + max_windows, ready)
+                    chunks = engine.audio_chunks(wav_all, starts[a_done:b], ends[a_done:b], win_a, padding)
+                    a_out.append(engine.audio_forward(chunks, normalize=True, mode=m))
+                    passes["audio"].append(b - a_done)
+                    a_done = b
+
+        def static_passes(flush):
+            nonlocal pend, n_pend
+            while n_pend >= (1 if flush else max_frames):
+                tiles = pend[0] if len(pend) == 1 else torch.cat(pend)
+                _, p, f = engine.static_forward(tiles[:max_frames], m)
+                probs.append(p)
+                feats.append(f)
+                passes["static"].append(int(p.shape[0]))
+                pend = [tiles[max_frames:]] if tiles.shape[0] > max_frames else []
+                n_pend = int(pend[0].shape[0]) if pend else 0
+
+        for k, i in enumerate(idx):
+            job = jobs[i]
+            passes["at"] = i  # the job a failure in this loop belongs to
+            frames, wav = job.load()
+            frames = frames if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames))
+            if tuple(frames.shape) != (job.n_frames, job.height, job.width, 3):
+                raise ValueError(f"video {job.name}: load() gave frames {tuple(frames.shape)}, the job says "
+                                 f"{(job.n_frames, job.height, job.width, 3)}")
+            # audio first, on its own stream: it depends on nothing of the visual branch
+            wav_t = wav if torch.is_tensor(wav) else torch.from_numpy(
+                np.ascontiguousarray(wav, dtype=np.float32) if job.wav_sr is None else np.ascontiguousarray(wav))
+            with torch.cuda.stream(side):
+                wav_d = wav_t.to(dev)
+                wav_d = wav_d.reshape(-1) if job.wav_sr is None else engine.resample(wav_d, job.wav_sr, sr)
+                if int(wav_d.numel()) != plans[i]["n_audio"]:
+                    raise ValueError(f"video {job.name}: load() gave {int(wav_d.numel())} samples at {sr} Hz, the job's "
+                                     f"n_samples / wav_sr give {plans[i]['n_audio']}")
+                wav_all[int(s_off[k]):int(s_off[k + 1])] = wav_d
+            audio_passes(int(w_off[k + 1]), False)
+            # stage 0: the tiles of track 00, in frame order
+            if "records" not in plans[i]:
+                dets = job.detections if job.detections is not None else detector.batch(frames, rgb=False)
+                plans[i]["records"], plans[i]["rows00"] = _track00(engine, job, dets)
+            records, rows = plans[i]["records"], plans[i]["rows00"]
+            present = np.zeros(job.n_frames, dtype=bool)
+            present[records[rows, 0]] = True
+            presents.append(present)
+            rects = torch.from_numpy(records[rows][:, [0, 2, 3, 4, 5]].astype(np.int32))
+            pend.append(engine.crop_tiles(frames, rects, bgr=True))
+            n_pend += len(rows)
+            static_passes(False)
+        passes["at"] = None
+        static_passes(True)
+        audio_passes(int(w_off[-1]), True)
+        # ragged LSTM plan over the whole set, then the per-frame tables by row gathers (video_pipeline.visual_forward)
+        s_src, d_src, win, n_feat = ragged_plan(presents, [jobs[i].fps for i in idx])
+        n = len(s_src)
+        zero = torch.zeros(1, 7, device=dev)
+        if n_feat:
+            assert win.size == 0 or (win.min() >= 0 and win.max() < n_feat)
+            feats_t = feats[0] if len(feats) == 1 else torch.cat(feats)
+            probs_t = probs[0] if len(probs) == 1 else torch.cat(probs)
+            stat = torch.cat([probs_t, zero]).index_select(0, torch.from_numpy(np.where(s_src >= 0, s_src, n_feat)).to(dev))
+            if len(win):
+                win_d = torch.from_numpy(win).to(dev)
+                dl = []
+                for a in range(0, len(win), max_frames):
+                    dl.append(engine.dynamic_forward(engine.gather_windows(feats_t, win_d[a:a + max_frames], validated=True), m))
+                    passes["lstm"].append(int(dl[-1].shape[0]))
+                dyn = torch.cat(dl + [zero]).index_select(0, torch.from_numpy(np.where(d_src >= 0, d_src, len(win))).to(dev))
+            else:
+                dyn = torch.zeros(n, 7, device=dev)
+        else:
+            stat = torch.zeros(n, 7, device=dev)
+            dyn = torch.zeros(n, 7, device=dev)
+        main.wait_stream(side)
+        joined = True
+        c = engine.audio_classes
+        win_logits = (a_out[0] if len(a_out) == 1 else torch.cat(a_out)) if a_out else torch.zeros(0, c, device=dev)
+        win_logits.record_stream(main)
+        return torch.cat([stat, dyn], dim=1), win_logits
+    finally:
+        # a failure in stage 0 or in load() unwinds from here: the audio work already queued on `side` is joined all the same,
+        # so that no launch of this call outlives it (run.run_inference)
+        if not joined:
+            main.wait_stream(side)
+
+
+def run_dataset(engine, jobs: Sequence[VideoJob], detector=None, *, mode: int = MODE_DEFAULT, sr: int = 16000, window: float = 4,
+                step: float = 0.5, padding: str = "mean", weights_prob_model=None, weights_model=(1, 1, 1),
+                ce_weights_type: bool = True, ce_mask: bool = False, max_frames_per_pass: int = 2048,
+                max_windows_per_pass: int = 128, path_save_results: str = "", flag_save_prob: bool = False,
+                skip_failed: bool = False, distributed: bool = False) -> DatasetResults:
+    """`run_inference` for every job of a set, with the videos sharing the GPU passes (module docstring).  Returns a
+    `DatasetResults`: a list with one dict per job, in job order, holding `name` and the keys of `run_inference` -- av / vs / vd
+    / a, compound_prob, static_probs, dynamic_logits, audio_rows, audio_frames, records -- with the bits `run_inference` gives for
+    that video alone, in MODE_F16X3 and in MODE_FP32.  The real-time factor is one figure for the call, on the list's
+    `real_time_factor` attribute: elapsed time over the summed duration of the videos that ran.  `flag_save_prob` writes each
+    video's CSV files as `run_inference` does (io_formats).  Heat maps are not produced on this path.
+
+    Passes: at most `max_frames_per_pass` tiles per static-CNN call (and LSTM windows per LSTM call), at most
+    `max_windows_per_pass` audio windows per audio call; device memory for tiles is one pass plus one video.
+
+    Range contract: the packed computation sits inside ONE `engine.guarded(mode, ...)`.  One counter cannot say which video
+    overflowed, so a set in which any activation leaves fp16's range is repeated in MODE_FP32 AS A WHOLE (every job is loaded
+    a second time); that is the price of one counter read per set instead of one per video.
+
+    Failures: whatever the metadata and given `detections` decide is decided before anything is launched -- a rate pair the
+    resampler does not cover (ValueError), no face track 00 (FileNotFoundError), a tracker error (ValueError naming the frame),
+    audio windows that cover no frame (IndexError); the message names the video.  With a `detector` the track is only known once
+    the video has been decoded, so such a job fails when its turn comes (the side stream is joined on every exit path).
+    `skip_failed`: a failed job's dict is {"name", "error": the exception} and the others proceed; failures found up front cost
+    nothing, one found mid-way repeats the call without that job.
+
+    `distributed` (torch.distributed initialised): rank r runs stages 0 to audio for the videos `dist.shard_videos` gives it
+    (balanced by `dist.video_cost`); an int32 status per video, the stat|dyn rows and the window logits are exchanged with
+    `dist.all_gather_ragged`; fusion runs replicated over the whole set in job order, and every rank returns every video."""
+    start_time = time.time()
+    jobs = list(jobs)
+    if padding not in ("mean", "constant", "repeat"):
+        raise ValueError(f"padding={padding!r}")
+    if max_frames_per_pass < 1 or max_windows_per_pass < 1:
+        raise ValueError("run_dataset: pass sizes >= 1")
+    errors = {}
+
+    def fail(i, e):
+        if not skip_failed:
+            raise type(e)(f"video {jobs[i].name}: {e}") from e
+        errors[i] = e
+
+    # ---- planning: metadata and given detections only; nothing is launched
+    plans = []
+    for i, job in enumerate(jobs):
+        plan = {}
+        plans.append(plan)
+        try:
+            if job.detections is None and detector is None:
+                raise ValueError("give a detector or the per-frame detections")
+            plan["n_audio"] = _n_audio(job, sr)
+            starts, ends, lo, hi = chunk_spans(plan["n_audio"], sr, job.fps, window, step)
+            plan.update(starts=starts, ends=ends, lo=lo, hi=hi)
+            covered_frames(lo, hi, int(job.n_frames))
+            if job.detections is not None:
+                plan["records"], plan["rows00"] = _track00(engine, job, job.detections)
+        except (ValueError, FileNotFoundError, IndexError) as e:
+            fail(i, e)
+
+    world = torch.distributed.get_world_size() if distributed and torch.distributed.is_initialized() else 1
+    rank = torch.distributed.get_rank() if world > 1 else 0
+    shards = adist.shard_videos([adist.video_cost(j, window, detector is not None and j.detections is None, sr, step) for j in jobs], world)
+    side = engine.__dict__.get("_side_stream")
+    if side is None:
+        side = engine.__dict__["_side_stream"] = torch.cuda.Stream(engine.device)
+    passes = {}
+
+    def local(m):
+        """This rank's tables; a job that fails on the way is dropped (skip_failed) and the rest starts over."""
+        while True:
+            mine = [i for i in shards[rank] if i not in errors]
+            passes.update(static=[], lstm=[], audio=[], at=None)
+            if not mine:
+                return (torch.zeros(0, 14, device=engine.device), torch.zeros(0, max(engine.audio_classes, 1), device=engine.device))
+            try:
+                return _local_tables(engine, jobs, mine, plans, detector, m, sr, window, padding, int(max_frames_per_pass),
+                                     int(max_windows_per_pass), side, passes)
+            except (ValueError, FileNotFoundError) as e:
+                bad = passes["at"]
+                if bad is None:
+                    raise
+                if world > 1:
+                    errors[bad] = e  # every rank learns of it from the status exchange and raises (or skips) there
+                else:
+                    fail(bad, e)
+
+    def fuse_all(rows, win_logits, ok):
+        n_f = [int(jobs[i].n_frames) for i in ok]
+        n_w = [len(plans[i]["lo"]) for i in ok]
+        prob, am, _, _ = engine.fuse_videos(rows[:, :7], rows[:, 7:], win_logits, np.concatenate([plans[i]["lo"] for i in ok]),
+                                            np.concatenate([plans[i]["hi"] for i in ok]), n_f, n_w, weights_prob_model,
+                                            weights_model, ce_weights_type, ce_mask, names=[jobs[i].name for i in ok], with_mean=False)
+        return rows, win_logits, prob, am
+
+    if world == 1:
+        def call(m):
+            rows, win_logits = local(m)
+            ok = [i for i in range(len(jobs)) if i not in errors]
+            return (fuse_all(rows, win_logits, ok) if ok else None), ok
+        # MODE_F16X3: one read of the range-contract counter for the whole set (engine.guarded)
+        tables, ok = engine.guarded(mode, call)
+    else:
+        tables, ok = _distributed(engine, jobs, plans, shards, rank, mode, local, fuse_all, errors, skip_failed)
+
+    out = DatasetResults({"name": j.name} for j in jobs)
+    for i, e in errors.items():
+        out[i]["error"] = e
+    if tables is not None:
+        rows, win_logits, prob, am = (t.cpu().numpy() for t in tables)
+        f_at = w_at = 0
+        for i in ok:
+            job, plan = jobs[i], plans[i]
+            f_to, w_to = f_at + int(job.n_frames), w_at + len(plan["lo"])
+            a_rows, a_frames = replicate_per_frame(win_logits[w_at:w_to], plan["lo"], plan["hi"])
+            stat = np.ascontiguousarray(rows[f_at:f_to, :7])
+            dyn = np.ascontiguousarray(rows[f_at:f_to, 7:])
+            if flag_save_prob:
+                io_formats.write_visual_csvs(stat, dyn, path_save_results, job.name)
+                io_formats.write_audio_csv(a_rows, a_frames, path_save_results, "audio", job.name)
+            out[i].update({name.lower(): np.ascontiguousarray(am[k, f_at:f_to]) for k, name in enumerate(MODEL_ORDER)})
+            out[i].update(compound_prob=np.ascontiguousarray(prob[:, f_at:f_to]), static_probs=stat, dynamic_logits=dyn,
+                          audio_rows=a_rows, audio_frames=a_frames, records=plan.get("records"))
+            f_at, w_at = f_to, w_to
+    duration = sum(jobs[i].n_frames / jobs[i].fps for i in ok if jobs[i].fps and jobs[i].fps > 0)
+    out.real_time_factor = (time.time() - start_time) / duration if duration else None
+    passes.pop("at", None)
+    out.passes = passes
+    return out
+
+
+def exchange_tables(rows, win_logits, shards, n_frames, n_windows, force: bool = False):
+    """The two payload collectives of the distributed path: this rank's stat|dyn rows [k,14] and window logits [w,c] (its videos
+    in ascending order) -> the whole set's tables in job order.  n_frames / n_windows: rows per video, 0 for a video that
+    contributes none (a failed one)."""
+    return (adist.merge_shards(adist.all_gather_ragged(rows, force), shards, n_frames),
+            adist.merge_shards(adist.all_gather_ragged(win_logits, force), shards, n_windows))
+
+
+def _distributed(engine, jobs, plans, shards, rank, mode, local, fuse_all, errors, skip_failed):
+    """Per-rank stages, one status exchange, two payload exchanges, replicated fusion.  The status word of a video: bit 0 = the
+    video failed on its rank, bit 1 = its rank saw the range contract broken.  Every rank takes the same decisions from the
+    gathered words: a set with a failure raises everywhere (unless skip_failed), a set with an overflow is repeated in
+    MODE_FP32 on every rank, so the collectives stay matched."""
+    if mode == MODE_F16X3:
+        engine.x3_overflow_clear()
+    rows, win_logits = local(mode)
+    over = mode == MODE_F16X3 and engine.x3_overflow_count(reset=True) > 0
+    mine = shards[rank]
+    word = torch.tensor([[(1 if i in errors else 0) | (2 if over else 0)] for i in mine], dtype=torch.int32,
+                        device=engine.device).reshape(len(mine), 1)
+    status = adist.merge_shards(adist.all_gather_ragged(word), shards, [1] * len(jobs)).reshape(-1).cpu().numpy()
+    for i in np.nonzero(status & 1)[0]:
+        if not skip_failed:
+            raise errors.get(int(i), RuntimeError(f"video {jobs[int(i)].name} failed on another rank"))
+        errors.setdefault(int(i), RuntimeError(f"video {jobs[int(i)].name} failed on another rank"))
+    if (status & 2).any():
+        engine.x3_fallbacks += 1
+        rows, win_logits = local(MODE_FP32)
+    ok = [i for i in range(len(jobs)) if i not in errors]
+    if not ok:
+        return None, ok
+    n_f = [int(j.n_frames) if i not in errors else 0 for i, j in enumerate(jobs)]
+    n_w = [len(plans[i]["lo"]) if i not in errors else 0 for i in range(len(jobs))]
+    rows, win_logits = exchange_tables(rows, win_logits, shards, n_f, n_w)
+    return fuse_all(rows, win_logits, ok), ok

@@ -476,6 +476,64 @@ class Engine:
                                         self._stream()))
         return prob, am
 
+    def fuse_videos(self, stat, dyn_logits, win_logits, frame_lo, frame_hi, frame_counts, win_counts, weights_1=None,
+                    weights_2=(1, 1, 1), ce_weights_type: bool = False, ce_mask: bool = True, names=None, with_mean: bool = True):
+        """`audio_frame_mean` + `fuse` for a set of videos in ONE launch (include/avcer_hip.h avcer_fuse_videos).  stat, dyn_logits
+        [N,7]: the videos' frames one behind the other; win_logits [W,c]: their audio windows one behind the other; frame_lo /
+        frame_hi: HOST integer arrays [W], each window's span in its own video's frame numbering (audio_pipeline.chunk_spans per
+        video, concatenated); frame_counts / win_counts: frames and windows per video.  The covered prefix of every video
+        (fusion.covered_frames) is settled on the host first: a video no window covers raises IndexError, one whose covered frames
+        are not a prefix ValueError -- what `fusion.fuse` raises for it, with the video's name (`names`, default its index) in
+        front -- before anything is launched.  Returns (comp_prob f64 [4,N,7], comp_argmax i32 [4,N], aud_mean f32 [N,c], count
+        i32 [N]); the last two are None unless `with_mean`.  A video's slices equal what the two calls give for it alone, bit for
+        bit.  No host synchronisation."""
+        from .fusion import covered_frames
+
+        stat = self._dev(stat, torch.float32)
+        dyn = self._dev(dyn_logits, torch.float32)
+        win = self._dev(win_logits, torch.float32)
+        lo = np.asarray(frame_lo.cpu() if torch.is_tensor(frame_lo) else frame_lo).reshape(-1).astype(np.int64)
+        hi = np.asarray(frame_hi.cpu() if torch.is_tensor(frame_hi) else frame_hi).reshape(-1).astype(np.int64)
+        fc = np.asarray(frame_counts, dtype=np.int64).reshape(-1)
+        wc = np.asarray(win_counts, dtype=np.int64).reshape(-1)
+        nv, n, w = int(fc.size), int(fc.sum()), int(wc.sum())
+        if nv < 1 or wc.size != nv or (fc < 0).any() or (wc < 0).any():
+            raise ValueError("fuse_videos: frame_counts / win_counts [V] >= 0, V >= 1")
+        if tuple(stat.shape) != (n, 7) or tuple(dyn.shape) != (n, 7) or win.dim() != 2 or int(win.shape[0]) != w or lo.size != w or hi.size != w:
+            raise ValueError("fuse_videos: stat/dyn [sum(frame_counts),7], win_logits [sum(win_counts),c], frame_lo/hi [sum(win_counts)]")
+        c = int(win.shape[1])
+        if not 7 <= c <= 8:
+            raise ValueError(f"fuse_videos: {c} audio classes (7..8)")
+        if not (1 <= n <= 2 ** 31 - 1 and 1 <= w <= 2 ** 31 - 1):
+            raise ValueError(f"fuse_videos: {n} frames and {w} windows (1..2^31-1 each)")
+        f_off = np.concatenate([[0], np.cumsum(fc)])
+        w_off = np.concatenate([[0], np.cumsum(wc)])
+        if len(lo) and (min(lo.min(), hi.min()) < -2 ** 31 or max(lo.max(), hi.max()) > 2 ** 31 - 1):
+            raise ValueError("fuse_videos: a frame span outside int32")
+        n_aud = np.zeros(nv, dtype=np.int32)
+        for v in range(nv):
+            a, b = int(w_off[v]), int(w_off[v + 1])
+            if (np.diff(lo[a:b]) < 0).any() or (np.diff(hi[a:b]) < 0).any():
+                raise ValueError(f"fuse_videos: video {names[v] if names is not None else v}: frame spans must not decrease")
+            try:
+                n_aud[v] = covered_frames(lo[a:b], hi[a:b], int(fc[v])) if fc[v] else 1
+            except (IndexError, ValueError) as e:
+                raise type(e)(f"video {names[v] if names is not None else v}: {e}") from None
+        idx = np.concatenate([lo, hi, f_off, w_off, n_aud]).astype(np.int32)
+        idx_d = torch.from_numpy(idx).to(self.device, non_blocking=True)  # one copy for the five index arrays
+        lo_d, hi_d = idx_d[:w], idx_d[w:2 * w]
+        fo_d, wo_d, na_d = idx_d[2 * w:2 * w + nv + 1], idx_d[2 * w + nv + 1:2 * w + 2 * nv + 2], idx_d[2 * w + 2 * nv + 2:]
+        w1 = (C.c_double * 21)(*np.asarray(weights_1, dtype=np.float64).reshape(21)) if weights_1 else None
+        w2 = (C.c_double * 3)(*[float(x) for x in weights_2])
+        prob = self._new(4, n, 7, dtype=torch.float64)
+        am = self._new(4, n, dtype=torch.int32)
+        mean = self._new(n, c) if with_mean else None
+        cnt = self._new(n, dtype=torch.int32) if with_mean else None
+        self._check(self.lib.avcer_fuse_videos(self.ctx, _ptr(stat), _ptr(dyn), _ptr(win), _ptr(lo_d), _ptr(hi_d), _ptr(fo_d),
+                                               _ptr(wo_d), _ptr(na_d), nv, n, w, c, w1, w2, int(bool(ce_weights_type)),
+                                               int(bool(ce_mask)), _ptr(mean), _ptr(cnt), _ptr(prob), _ptr(am), self._stream()))
+        return prob, am, mean, cnt
+
     def conv_gemm(self, desc: ConvDesc, dtype: int, x, w, scale, bias, residual, y):
         self._check(self.lib.avcer_conv_gemm(self.ctx, C.byref(desc), dtype, _ptr(x), _ptr(w), _ptr(scale), _ptr(bias),
                                              _ptr(residual), _ptr(y), self._stream()))

@@ -71,7 +71,9 @@ enum {
  *   5: avcer_static_forward_cam, avcer_crop_resize_linear, avcer_cam_render (Grad-CAM heat maps).
  *   6: avcer_resample (source audio -> mono at the model's rate).
  *   7: avcer_weight_search_counts (fusion weight search: per-candidate argmax counts).
- *   8: avcer_audio_head_kind, avcer_audio_forward_features, avcer_gru_layer, AVCER_FAM_GRU (the GRU-head audio model ExprModelV1). */
+ *   8: avcer_audio_head_kind, avcer_audio_forward_features, avcer_gru_layer, AVCER_FAM_GRU (the GRU-head audio model ExprModelV1).
+ *      avcer_fuse_videos (fusion of a set of unequal videos in one launch) joined under 8: one more symbol, nothing that
+ *      existed changed; a binary without it is refused by its source hash. */
 #define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
@@ -336,6 +338,30 @@ int avcer_lsap(int nr, int nc, const double* cost_host, int32_t* rows_host, int3
 int avcer_fuse(avcer_ctx* ctx, const float* stat, const float* dyn_logits, const float* aud_mean, int n, int n_aud,
                int aud_c, const double* w1_host, const double* w2_host, int ce_weights_type, int ce_mask,
                double* comp_prob, int32_t* comp_argmax, avcer_stream_t stream);
+
+/* avcer_audio_frame_mean + avcer_fuse for a CONCATENATION of videos in one launch: each frame is fused with the mean of the
+ * windows of ITS OWN video that cover it, so a set of recordings of unequal length is fused at the cost of one launch and
+ * without one video's windows reaching into the next (a window's frame_hi may exceed its video's frame count).
+ *   ref: run.py:85-165 (get_c_expr_db_pred: group mean, tail padding with the last audio row, fusion, compound rule),
+ *        get_prob_audio_8_cl.py:94-101 (a window's logits replicated for the frames [lo, hi) of its video)
+ * stat, dyn_logits f32 [n_frames,7]: all videos' frames one behind the other, VIDEO column order; win_logits f32 [n_windows,c]:
+ * all videos' audio windows one behind the other; frame_lo / frame_hi i32 [n_windows]: each window's span in the numbering of
+ * its own video, neither decreasing within a video (what chunk_spans yields; the kernel bounds its walk with it);
+ * frame_off, win_off i32 [n_videos+1]: prefix offsets of each video's frames / windows (frame_off[n_videos] = n_frames,
+ * win_off[n_videos] = n_windows); n_aud i32 [n_videos]: the leading frames of video v that some window covers, >= 1 -- frames
+ * behind them use the row of frame n_aud[v]-1 (run.py:99-103).  All index arrays are DEVICE pointers; n_frames and n_windows
+ * are passed by value because the launch is sized from them without reading device memory: there is no host synchronisation.
+ * w1_host / w2_host / ce_weights_type / ce_mask as avcer_fuse takes them.
+ * comp_prob f64 [4,n_frames,7], comp_argmax i32 [4,n_frames] (AV, VS, VD, A): for the frames of video v, bit for bit what
+ * avcer_audio_frame_mean + avcer_fuse give for that video alone (windows visited in index order, f64 sum, one rounding).
+ * aud_mean f32 [n_frames,c] and count i32 [n_frames], each optional (NULL): what avcer_audio_frame_mean writes for that video's
+ * frames (no covering window: zeros and 0).
+ * AVCER_EINVAL outside n_videos >= 1, 7 <= c <= 8, 1 <= n_frames, n_windows <= 2^31-1. */
+int avcer_fuse_videos(avcer_ctx* ctx, const float* stat, const float* dyn_logits, const float* win_logits,
+                      const int32_t* frame_lo, const int32_t* frame_hi, const int32_t* frame_off, const int32_t* win_off,
+                      const int32_t* n_aud, int n_videos, int64_t n_frames, int64_t n_windows, int c, const double* w1_host,
+                      const double* w2_host, int ce_weights_type, int ce_mask, float* aud_mean, int32_t* count,
+                      double* comp_prob, int32_t* comp_argmax, avcer_stream_t stream);
 
 /* The contraction kernel itself (implicit-GEMM convolution with fused epilogue), exported for kernel-level
  * parity tests and micro-benchmarks:  Y[m, n] = act(scale[n] * sum_k A[m,k] * W[n,k] + bias[n] (+ R[m,n]))
