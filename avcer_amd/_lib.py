@@ -74,6 +74,7 @@ SIGNATURES = {
                                          C.c_void_p, C.c_void_p, c_stream]),
     "avcer_load_face": (C.c_int, [c_ctx, C.c_void_p, C.c_size_t]),
     "avcer_face_num_priors": (C.c_int, [C.c_int, C.c_int]),
+    "avcer_face_kind": (C.c_int, [c_ctx]),
     "avcer_face_forward": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                      C.c_void_p, C.c_void_p, c_stream]),
     "avcer_face_decode": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
@@ -104,6 +105,7 @@ SIGNATURES = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, c_stream]),
     "avcer_face_nms": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float,
                                  C.c_void_p, C.c_void_p, c_stream]),
+    "avcer_dwsep": (C.c_int, [c_ctx] + [C.c_int] * 7 + [C.c_void_p] * 8 + [C.c_void_p]),
     "avcer_bneck_chain": (C.c_int, [c_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9 +
                           [c_stream]),
     "avcer_stem_pool": (C.c_int, [c_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, c_stream]),

@@ -54,6 +54,7 @@ struct avcer_ctx {
     int device = 0;
     char err[512] = {0};
     Model stat, dyn, aud, face;
+    int face_kind = 0;        // the loaded detector (avcer_face_kind): 0 none, 1 RetinaFace-R50, 2 RetinaFace-MobileNet-0.25
     int aud_classes = 0;
     int aud_head = 0;         // head of the loaded audio model (avcer_audio_head_kind): 0 none, 1 GRU (ExprModelV1), 3 transformer (V2 / V3)
     int static_batch = 1024;  // frames per internal pass of the static CNN (4 GiB buffer-descriptor limit at f32)
@@ -157,6 +158,20 @@ int launch_bneck_tail(avcer_ctx* ctx, int planes, long M, const void* t2, const 
 // h_seq [n, S, 256] f32 and, x3 only, h_sp: the same as sp32 pairs (or null)
 int launch_gru_layer(avcer_ctx* ctx, const float* xp, const void* w, int x3, const float* bhh, int n, int S, float* h_seq, void* h_sp,
                      hipStream_t st);
+
+// ---- mnet.hip (the MobileNet-0.25 detector: plain NHWC f32 activations in both of its modes)
+// u8 frames [n, h, w, 3] -> conv 3x3/2 (3 -> 8) of pixel - mean, BN, LeakyReLU(0.1): y [n, ceil(h/2), ceil(w/2), 8]; wt [27][8]
+int launch_mnet_stem(avcer_ctx* ctx, const uint8_t* frames, int n, int h, int w, int rgb, const float* wt, const float* s, const float* b,
+                     float* y, hipStream_t st);
+// one conv_dw block (depthwise 3x3 at `stride` + BN + leaky, pointwise 1x1 + BN + leaky) in one launch: x [nb, h, w, cin] ->
+// y [nb, ceil(h/stride), ceil(w/stride), cout]; dww [9][cin]; pw = the pointwise weights [ceil64(cout)][ceil32(cin)] (zero-padded)
+// as f32 (x3 = 0) or as their split copy with its trailer (x3 = 1)
+int launch_dwsep(avcer_ctx* ctx, int cin, int cout, int stride, int x3, const float* x, const float* dww, const float* dws,
+                 const float* dwb, const void* pw, const float* pws, const float* pwb, float* y, int nb, int h, int w, hipStream_t st);
+// direct ks x ks convolution (ks 1 or 3, stride 1, same padding) of the neck: wt [ks * ks * cin][cout], cout a multiple of 16;
+// y[pos * y_ld + y_coff + c] = act(acc * s[c] + b[c]) (s null: 1); act 0 none, 1 ReLU, 4 LeakyReLU(0.1)
+int launch_mnet_conv(avcer_ctx* ctx, int ks, const float* x, const float* wt, const float* s, const float* b, float* y, int n, int h, int w,
+                     int cin, int cout, int y_ld, int y_coff, int act, hipStream_t st);
 
 int measure_ceilings(avcer_ctx* ctx, double* mfma_bf16_tflops, double* hbm_copy_tbs, hipStream_t st);
 

@@ -48,18 +48,20 @@ def all_gather_records(rec: torch.Tensor, n_total: int, force: bool = False) -> 
 
 
 # ------------------------------------------------------------------------------------------------ whole videos of unequal length
-def video_cost(job, window: float = 4, detector: bool = False, sr: int = 16000, step: float = 0.5) -> float:
+def video_cost(job, window: float = 4, detector=False, sr: int = 16000, step: float = 0.5) -> float:
     """Algorithmic GFLOP of one video, from its metadata alone (`job`: n_frames, height, width, fps, n_samples, wav_sr): the
     figure `shard_videos` balances.  This is WORK, not measured time: the three models run at different fractions of the
     machine's peak, so equal cost is not equal time; it is what every rank can compute identically without running anything.
     Terms: per frame 7.667 for the static CNN, plus 50.7 * H*W / (640*360) when a
     detector runs; per LSTM evaluation 0.0577; per audio window 44.891 + (91.299 - 44.891) * (window*sr - 32000) / 32000.
-    Every frame is counted as present (the face track is not known before stage 0)."""
+    `detector`: False, True (RetinaFace-R50: 50.7) or the detector's own GFLOP per 640 x 360 frame (MobileNet-0.25: 1.116,
+    `RetinaFacePredictor.gflop_per_frame`).  Every frame is counted as present (the face track is not known before stage 0)."""
     from .audio_pipeline import resample_out_len, resample_plan
     from .video_pipeline import lstm_step
 
     t = int(job.n_frames)
-    per_frame = 7.667 + (50.7 * (job.height * job.width) / (640 * 360) if detector else 0.0)
+    det_gflop = 50.7 if detector is True else float(detector or 0.0)
+    per_frame = 7.667 + det_gflop * (job.height * job.width) / (640 * 360)
     n_lstm = len(range(0, t, max(lstm_step(job.fps), 1)))
     n = int(job.n_samples)
     if getattr(job, "wav_sr", None) is not None:

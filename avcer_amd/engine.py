@@ -122,7 +122,12 @@ class Engine:
         return int(self.lib.avcer_audio_head_kind(self.ctx))
 
     def load_face(self, state_dict):
+        """Either detector: RetinaFace(cfg_re50).state_dict() or RetinaFace(cfg_mnet).state_dict() (packing.pack_face tells them apart)."""
         self._load(self.lib.avcer_load_face, packing.pack_face(state_dict))
+
+    def face_kind(self) -> int:
+        """The loaded detector: 0 none, 1 RetinaFace-R50, 2 RetinaFace-MobileNet-0.25."""
+        return int(self.lib.avcer_face_kind(self.ctx))
 
     def face_forward(self, frames_u8, mode: int = MODE_DEFAULT, rgb: bool = False):
         """frames u8 [N,H,W,3] (BGR unless rgb) -> (loc [N,P,4], conf [N,P,2] softmaxed, landms [N,P,10])."""
@@ -620,6 +625,22 @@ class Engine:
         self._check(self.lib.avcer_bneck_chain(self.ctx, planes, nb, h, w, _ptr(t1), _ptr(x), int(ds_cin), int(out_step), _ptr(out),
                                                _ptr(t1n), _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), _ptr(w1n), _ptr(b1n),
                                                _ptr(w2_frags), self._stream()))
+
+    def dwsep(self, x, dw_w, dw_s, dw_b, pw_w, pw_s, pw_b, stride: int, mode: int = MODE_FP32):
+        """Kernel-level entry of one conv_dw block of MobileNet-0.25 (csrc/mnet.hip): x f32 NHWC [nb,h,w,cin], dw_w [9,cin],
+        pw_w f32 [cout,cin] (padded and, in MODE_F16X3, split here) -> y f32 NHWC [nb,ceil(h/stride),ceil(w/stride),cout]."""
+        x = self._dev(x, torch.float32)
+        nb, h, w, cin = (int(v) for v in x.shape)
+        pw = self._dev(pw_w, torch.float32)
+        cout = int(pw.shape[0])
+        pad = torch.zeros((cout + 63) // 64 * 64, (cin + 31) // 32 * 32, dtype=torch.float32, device=self.device)
+        pad[:cout, :cin] = pw
+        wdev = self.split_weight_rows(pad) if mode == MODE_F16X3 else pad
+        args = [self._dev(t, torch.float32) for t in (dw_w, dw_s, dw_b, pw_s, pw_b)]
+        y = self._new(nb, (h - 1) // stride + 1, (w - 1) // stride + 1, cout)
+        self._check(self.lib.avcer_dwsep(self.ctx, cin, cout, int(stride), int(mode), nb, h, w, _ptr(x), _ptr(args[0]), _ptr(args[1]),
+                                         _ptr(args[2]), _ptr(wdev), _ptr(args[3]), _ptr(args[4]), _ptr(y), self._stream()))
+        return y
 
     def attention(self, qkv, out, n: int, s: int, heads: int, head_dim: int, scale: float, in_kind: int, out_kind: int):
         """Kernel-level entry of the attention kernel: qkv [n, s, 3 * heads * head_dim] -> out [n, s, heads * head_dim];

@@ -23,8 +23,10 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 import torch
+
 from scipy.optimize import linear_sum_assignment
 
+from . import packing
 from .engine import MODE_DEFAULT
 
 # retina_face/config.py:22-39 (cfg_re50)
@@ -102,11 +104,18 @@ class FaceDetections:
 class RetinaFacePredictor:
     """`RetinaFacePredictor(threshold, device, model)` (retina_face_predictor.py:17-108) on the HIP path: the network,
     box decoding and the device-side filter / NMS / top-k (`FaceDetections`).  `state_dict` = RetinaFace(cfg_re50).state_dict() (the file
-    `Resnet50_Final.pth`, with or without the `module.` prefix)."""
+    `Resnet50_Final.pth`, with or without the `module.` prefix) or RetinaFace(cfg_mnet).state_dict() (`mobilenet0.25_Final.pth`:
+    `get_model("mobilenet0.25")`, retina_face_predictor.py:40-52); the two configurations share the priors and the variances, so
+    everything behind the network is the same.  `kind`: 1 = ResNet-50, 2 = MobileNet-0.25 (modes FP32 and F16X3 only)."""
+
+    # algorithmic GFLOP of the network per 640 x 360 frame (DESIGN.md section 5), what dist.video_cost prices a detector at
+    GFLOP_PER_FRAME = {1: 50.7, 2: 1.116}
 
     def __init__(self, engine, state_dict, threshold: float = 0.8, mode: int = MODE_DEFAULT):
         self.engine, self.mode = engine, mode
         engine.load_face(state_dict)
+        self.kind = packing.face_kind(state_dict)
+        self.gflop_per_frame = self.GFLOP_PER_FRAME[self.kind]
         self.post = FaceDetections(engine, threshold=threshold)
 
     def __call__(self, image, rgb: bool = True) -> np.ndarray:

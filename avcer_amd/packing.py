@@ -151,9 +151,77 @@ def permute_rows_for_mfma(w: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(w[idx])
 
 
+MNET_BLOCKS = ((8, 16, 1), (16, 32, 2), (32, 32, 1), (32, 64, 2), (64, 64, 1), (64, 128, 2)) + ((128, 128, 1),) * 5 + (
+    (128, 256, 2), (256, 256, 1))  # the conv_dw blocks of MobileNetV1 (retina_face_net.py:106-125): (cin, cout, stride)
+FACE_KIND_R50, FACE_KIND_MNET = 1, 2  # avcer_face_kind
+
+
+def face_kind(sd) -> int:
+    """Which detector a RetinaFace state dict holds, by key (after the `module.` / wrapper spellings are undone):
+    `body.stage1.0.0.weight` = MobileNet-0.25 (cfg_mnet), `body.conv1.weight` = ResNet-50 (cfg_re50)."""
+    sd = _face_keys(sd)
+    mnet, r50 = "body.stage1.0.0.weight" in sd, "body.conv1.weight" in sd
+    if mnet == r50:
+        raise ValueError("pack_face: the state dict is neither RetinaFace(cfg_re50) (body.conv1.weight) nor RetinaFace(cfg_mnet) "
+                         "(body.stage1.0.0.weight)")
+    return FACE_KIND_MNET if mnet else FACE_KIND_R50
+
+
+def _face_keys(sd):
+    if "state_dict" in sd and not hasattr(sd["state_dict"], "shape"):
+        sd = sd["state_dict"]  # the published checkpoints wrap the weights: {"state_dict": ...}
+    sd = _unwrap(sd)
+    return {(k.split("module.", 1)[-1] if k.startswith("module.") else k): v for k, v in sd.items()}  # predictor.py:28-33
+
+
+def _conv_wt(w) -> np.ndarray:
+    w = _f32(w)  # [O, I, kh, kw] -> [kh*kw*I, O]: the neck's direct convolutions read 16 consecutive output channels per input
+    return np.ascontiguousarray(w.transpose(2, 3, 1, 0)).reshape(-1, w.shape[0])
+
+
+def pack_face_mnet(sd) -> "OrderedDict[str, np.ndarray]":
+    """RetinaFace(cfg_mnet).state_dict() (retina_face.py:46-76, retina_face_net.py:103-125) for csrc/mnet.hip.  Every BatchNorm
+    (eps 1e-5) is folded into a per-channel scale / shift.  `mnet.kind` records the variant in the blob (avcer_face_kind)."""
+    eps = 1e-5
+    out: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    out["mnet.kind"] = np.array([FACE_KIND_MNET], np.float32)
+    out["stem.wt"] = _conv_wt(sd["body.stage1.0.0.weight"])  # [27, 8], taps (ky, kx, c) major
+    out["stem.s"], out["stem.b"] = _bn_fold(sd, "body.stage1.0.1", eps)
+    names = [f"body.stage1.{i}" for i in range(1, 6)] + [f"body.stage2.{i}" for i in range(6)] + [f"body.stage3.{i}" for i in range(2)]
+    for i, (src, (cin, cout, _)) in enumerate(zip(names, MNET_BLOCKS), start=1):
+        dw = _f32(sd[src + ".0.weight"])  # [cin, 1, 3, 3] -> [9, cin]
+        assert dw.shape == (cin, 1, 3, 3), (src, dw.shape)
+        out[f"b{i}.dw.w"] = np.ascontiguousarray(dw.reshape(cin, 9).T)
+        out[f"b{i}.dw.s"], out[f"b{i}.dw.b"] = _bn_fold(sd, src + ".1", eps)
+        # pointwise [cout, cin], zero-padded to whole 64-row / 32-column groups: the shape the split copies exist for
+        pw = np.zeros(((cout + 63) // 64 * 64, (cin + 31) // 32 * 32), np.float32)
+        pw[:cout, :cin] = _f32(sd[src + ".3.weight"]).reshape(cout, cin)
+        out[f"b{i}.pw.w"] = pw
+        out[f"b{i}.pw.s"], out[f"b{i}.pw.b"] = _bn_fold(sd, src + ".4", eps)
+    for i in (1, 2, 3):
+        out[f"fpn.o{i}.wt"] = _conv_wt(sd[f"fpn.output{i}.0.weight"])
+        out[f"fpn.o{i}.s"], out[f"fpn.o{i}.b"] = _bn_fold(sd, f"fpn.output{i}.1", eps)
+    for i in (1, 2):
+        out[f"fpn.m{i}.wt"] = _conv_wt(sd[f"fpn.merge{i}.0.weight"])
+        out[f"fpn.m{i}.s"], out[f"fpn.m{i}.b"] = _bn_fold(sd, f"fpn.merge{i}.1", eps)
+    for i in (1, 2, 3):
+        for src, dst in (("conv3X3", "c3"), ("conv5X5_1", "c51"), ("conv5X5_2", "c52"), ("conv7X7_2", "c72"),
+                         ("conv7x7_3", "c73")):
+            out[f"ssh{i}.{dst}.wt"] = _conv_wt(sd[f"ssh{i}.{src}.0.weight"])
+            out[f"ssh{i}.{dst}.s"], out[f"ssh{i}.{dst}.b"] = _bn_fold(sd, f"ssh{i}.{src}.1", eps)
+    for i in range(3):  # the three 1x1 heads of a level as one [64, 32] matrix: class 0-3, bbox 4-11, landmarks 12-31
+        wh = np.concatenate([_f32(sd[f"{head}.{i}.conv1x1.weight"]).reshape(-1, 64) for head in ("ClassHead", "BboxHead", "LandmarkHead")])
+        out[f"head{i}.wt"] = np.ascontiguousarray(wh.T)
+        out[f"head{i}.b"] = np.concatenate([_f32(sd[f"{head}.{i}.conv1x1.bias"]) for head in ("ClassHead", "BboxHead", "LandmarkHead")])
+    return out
+
+
 def pack_face(sd) -> "OrderedDict[str, np.ndarray]":
-    """RetinaFace(cfg_re50).state_dict() (retina_face/retina_face.py:46-76; `body.*` = torchvision ResNet-50 children)."""
+    """RetinaFace(cfg_re50).state_dict() (retina_face/retina_face.py:46-76; `body.*` = torchvision ResNet-50 children), or
+    RetinaFace(cfg_mnet).state_dict(): told apart by key (face_kind), the latter packed by pack_face_mnet."""
     eps = 1e-5  # torch.nn.BatchNorm2d default, used by torchvision's ResNet and by retina_face_net.py
+    if face_kind(sd) == FACE_KIND_MNET:
+        return pack_face_mnet(_face_keys(sd))
     sd = _unwrap(sd)
     sd = {(k.split("module.", 1)[-1] if k.startswith("module.") else k): v for k, v in sd.items()}  # predictor.py:28-33
     out: "OrderedDict[str, np.ndarray]" = OrderedDict()

@@ -173,6 +173,38 @@ def retina_state_dict(seed: int = 42) -> "OrderedDict[str, np.ndarray]":
     return sd
 
 
+def retina_mnet_state_dict(seed: int = 42) -> "OrderedDict[str, np.ndarray]":
+    """Keys of RetinaFace(cfg_mnet).state_dict() (retina_face.py:46-76, retina_face_net.py:103-125, config.py:3-20): `body.stage{1,2,3}.*`
+    (IntermediateLayerGetter keeps the MobileNetV1 children up to stage3), `fpn.*`, `ssh{1,2,3}.*` at 64 channels and the heads:
+    300 entries, 433 343 values.  The class heads get a larger gain and bias range, so that conf[:, 1] spreads over (0, 1)."""
+    sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    _conv2d(sd, seed, "body.stage1.0.0.weight", 8, 3, 3, gain=2.0 / (60.0 * 60.0))   # pixels minus (104, 117, 123)
+    _bn(sd, seed, "body.stage1.0.1", 8)
+    blocks = ((8, 16), (16, 32), (32, 32), (32, 64), (64, 64), (64, 128)) + ((128, 128),) * 5 + ((128, 256), (256, 256))
+    names = [f"body.stage1.{i}" for i in range(1, 6)] + [f"body.stage2.{i}" for i in range(6)] + [f"body.stage3.{i}" for i in range(2)]
+    for p, (cin, cout) in zip(names, blocks):
+        sd[p + ".0.weight"] = centered(seed, p + ".0.weight", (cin, 1, 3, 3), math.sqrt(2.0 / 9))   # depthwise
+        _bn(sd, seed, p + ".1", cin)
+        _conv2d(sd, seed, p + ".3.weight", cout, cin, 1)
+        _bn(sd, seed, p + ".4", cout)
+    for i, c in enumerate((64, 128, 256), start=1):
+        _conv2d(sd, seed, f"fpn.output{i}.0.weight", 64, c, 1)
+        _bn(sd, seed, f"fpn.output{i}.1", 64)
+    for i in (1, 2):
+        _conv2d(sd, seed, f"fpn.merge{i}.0.weight", 64, 64, 3)
+        _bn(sd, seed, f"fpn.merge{i}.1", 64)
+    for i in (1, 2, 3):
+        for name, co, ci in (("conv3X3", 32, 64), ("conv5X5_1", 16, 64), ("conv5X5_2", 16, 16), ("conv7X7_2", 16, 16),
+                             ("conv7x7_3", 16, 16)):
+            _conv2d(sd, seed, f"ssh{i}.{name}.0.weight", co, ci, 3)
+            _bn(sd, seed, f"ssh{i}.{name}.1", co)
+    for head, n in (("ClassHead", 4), ("BboxHead", 8), ("LandmarkHead", 20)):
+        for i in range(3):
+            _conv2d(sd, seed, f"{head}.{i}.conv1x1.weight", n, 64, 1, gain=4.0 if head == "ClassHead" else 1.0)
+            sd[f"{head}.{i}.conv1x1.bias"] = uniform(seed, f"{head}.{i}.conv1x1.bias", (n,), -0.2, 0.2)
+    return sd
+
+
 def video_frames(seed: int, n: int, h: int, w: int) -> np.ndarray:
     """uint8 BGR video frames [n, h, w, 3] for the detector."""
     return u8(seed, "video", (n, h, w, 3))

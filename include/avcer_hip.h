@@ -73,7 +73,9 @@ enum {
  *   7: avcer_weight_search_counts (fusion weight search: per-candidate argmax counts).
  *   8: avcer_audio_head_kind, avcer_audio_forward_features, avcer_gru_layer, AVCER_FAM_GRU (the GRU-head audio model ExprModelV1).
  *      avcer_fuse_videos (fusion of a set of unequal videos in one launch) joined under 8: one more symbol, nothing that
- *      existed changed; a binary without it is refused by its source hash. */
+ *      existed changed; a binary without it is refused by its source hash.
+ *      avcer_face_kind and avcer_dwsep (the MobileNet-0.25 RetinaFace detector: avcer_load_face / avcer_face_forward take either
+ *      variant's blob) joined under 8 the same way: two more symbols, no struct layout or argument list changed. */
 #define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
@@ -258,6 +260,13 @@ int avcer_audio_frame_mean(avcer_ctx* ctx, const float* win_logits, const int32_
  *   P = avcer_face_num_priors(h, w) rows in PriorBox order; feed them to avcer_face_decode. */
 int avcer_load_face(avcer_ctx* ctx, const void* packed, size_t nbytes);
 int avcer_face_num_priors(int h, int w);
+/* The same entry points serve the reference's second detector, RetinaFace(cfg_mnet) ("mobilenet0.25": MobileNetV1 body,
+ * retina_face_net.py:103-125, FPN / SSH at 64 channels with LeakyReLU(0.1), config.py:3-20): avcer_load_face takes the blob
+ * pack_face makes of that state dict (it records the kind), and avcer_face_forward runs it with the same arguments and the same
+ * P rows -- cfg_mnet and cfg_re50 share min_sizes, steps, variance and clip.  Modes: AVCER_MODE_FP32 and AVCER_MODE_F16X3;
+ * AVCER_MODE_BF16 returns AVCER_EINVAL for this variant.  Loading a blob frees the previous detector and all its lazy copies.
+ * avcer_face_kind: 0 = no detector loaded, 1 = RetinaFace-R50, 2 = RetinaFace-MobileNet-0.25. */
+int avcer_face_kind(const avcer_ctx* ctx);
 int avcer_face_forward(avcer_ctx* ctx, const uint8_t* frames, int n, int h, int w, int rgb, int mode, float* loc,
                        float* conf, float* landms, avcer_stream_t stream);
 
@@ -447,6 +456,16 @@ int avcer_conv_gemm_dual(avcer_ctx* ctx, const avcer_conv_desc* d, int dtype, co
 int avcer_bneck_chain(avcer_ctx* ctx, int planes, int nb, int h, int w, const void* t1, const void* x, int ds_cin, int out_step,
                       void* out, void* t1n, const void* w2, const float* b2, const void* w3, const float* b3, const void* w1n,
                       const float* b1n, const void* w2_frags, avcer_stream_t stream);
+/* One conv_dw block of MobileNet-0.25 (retina_face_net.py:29-38) in ONE launch (csrc/mnet.hip dwsep_kernel), for kernel-level tests:
+ *     T = leaky(dw3x3(X, stride, pad 1) * dw_s + dw_b);  Y = leaky(conv1x1(T) * pw_s + pw_b),  leaky = LeakyReLU(0.1)
+ *   x f32 NHWC [nb,h,w,cin] -> y f32 NHWC [nb,ceil(h/stride),ceil(w/stride),cout]; T never reaches memory.
+ *   (cin, cout, stride): one of (8,16,1) (16,32,2) (32,32,1) (32,64,2) (64,64,1) (64,128,2) (128,128,1) (128,256,2) (256,256,1).
+ *   dw_w f32 [9][cin] (tap-major); dw_s, dw_b [cin]; pw_s, pw_b [cout]; pw_w = the pointwise matrix zero-padded to
+ *   [ceil64(cout)][ceil32(cin)]: f32 in AVCER_MODE_FP32 (f32 MFMA), its avcer_split_weight_rows copy in AVCER_MODE_F16X3 (three
+ *   fp16 MFMAs per term, every depthwise output split as one f32 number, |T| >= 65520 counted by avcer_x3_overflow_count). */
+int avcer_dwsep(avcer_ctx* ctx, int cin, int cout, int stride, int mode, int nb, int h, int w, const float* x, const float* dw_w,
+                const float* dw_s, const float* dw_b, const void* pw_w, const float* pw_s, const float* pw_b, float* y,
+                avcer_stream_t stream);
 int avcer_stem_pool(avcer_ctx* ctx, const void* planes_hi_lo, size_t plane_bytes, const void* w, const float* scale,
                     const float* bias, void* y, int n, avcer_stream_t stream);
 /* The same launch fed with the u8 frames themselves ([n,in_h,in_w,3] RGB; data/utils.py:19-39 -- NEAREST resize to 224, BGR flip,
