@@ -75,6 +75,9 @@ SIGNATURES = {
     "avcer_load_face": (C.c_int, [c_ctx, C.c_void_p, C.c_size_t]),
     "avcer_face_num_priors": (C.c_int, [C.c_int, C.c_int]),
     "avcer_face_kind": (C.c_int, [c_ctx]),
+    "avcer_s3fd_num_priors": (C.c_int, [C.c_int, C.c_int]),
+    "avcer_s3fd_detect": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_float] * 4 + [C.c_int] * 2 +
+                          [C.c_float, C.c_void_p, C.c_void_p, c_stream]),
     "avcer_face_forward": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                      C.c_void_p, C.c_void_p, c_stream]),
     "avcer_face_decode": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
@@ -106,6 +109,9 @@ SIGNATURES = {
     "avcer_face_nms": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float,
                                  C.c_void_p, C.c_void_p, c_stream]),
     "avcer_dwsep": (C.c_int, [c_ctx] + [C.c_int] * 7 + [C.c_void_p] * 8 + [C.c_void_p]),
+    "avcer_s3fd_stem": (C.c_int, [c_ctx, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int, c_stream]),
+    "avcer_maxpool2": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [c_stream]),
+    "avcer_s3fd_head": (C.c_int, [c_ctx, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 7 + [C.c_void_p, C.c_void_p, c_stream]),
     "avcer_bneck_chain": (C.c_int, [c_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9 +
                           [c_stream]),
     "avcer_stem_pool": (C.c_int, [c_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, c_stream]),

@@ -54,7 +54,7 @@ struct avcer_ctx {
     int device = 0;
     char err[512] = {0};
     Model stat, dyn, aud, face;
-    int face_kind = 0;        // the loaded detector (avcer_face_kind): 0 none, 1 RetinaFace-R50, 2 RetinaFace-MobileNet-0.25
+    int face_kind = 0;        // the loaded detector (avcer_face_kind): 0 none, 1 RetinaFace-R50, 2 RetinaFace-MobileNet-0.25, 3 S3FD
     int aud_classes = 0;
     int aud_head = 0;         // head of the loaded audio model (avcer_audio_head_kind): 0 none, 1 GRU (ExprModelV1), 3 transformer (V2 / V3)
     int static_batch = 1024;  // frames per internal pass of the static CNN (4 GiB buffer-descriptor limit at f32)
@@ -172,6 +172,22 @@ int launch_dwsep(avcer_ctx* ctx, int cin, int cout, int stride, int x3, const fl
 // y[pos * y_ld + y_coff + c] = act(acc * s[c] + b[c]) (s null: 1); act 0 none, 1 ReLU, 4 LeakyReLU(0.1)
 int launch_mnet_conv(avcer_ctx* ctx, int ks, const float* x, const float* wt, const float* s, const float* b, float* y, int n, int h, int w,
                      int cin, int cout, int y_ld, int y_coff, int act, hipStream_t st);
+
+// ---- s3fd.hip (the S3FD detector; `kind` = KIND_F32 or KIND_SP32, the storage of the activations)
+// u8 frames [n, h, w, 3] -> conv1_1 3x3 pad 1 (3 -> 64) of RGB pixel - (123, 117, 104) + bias + ReLU: y [n, h, w, 64]; wt [27][64]
+int launch_s3fd_stem(avcer_ctx* ctx, const uint8_t* frames, int n, int h, int w, int rgb, const float* wt, const float* b, void* y, int kind,
+                     hipStream_t st);
+// 2x2 / 2 max-pool, NHWC: y [n, h / 2, w / 2, c], or [n, ceil(h / 2), ceil(w / 2), c] with ceil_mode
+int launch_maxpool2(avcer_ctx* ctx, const void* x, void* y, int n, int h, int w, int c, int ceil_mode, int kind, hipStream_t st);
+// one level's loc + conf 3x3 convolutions, max-out (n_out 8) and softmax: x [nb, h, w, c], wt [9][c][n_out], rows written at
+// f * P + row0; inv: scratch for nb * h * w inverse L2 norms (the level is normalised) or null (it is not)
+int launch_s3fd_head(avcer_ctx* ctx, const void* x, int kind, float* inv, const float* wt, const float* b, int nb, int h, int w, int c,
+                     int n_out, int row0, int P, float* loc, float* conf, hipStream_t st);
+// Detect + the predictor's loop: decode, order, NMS; ws = s3fd_detect_ws_bytes(T, P, nms_top_k) bytes
+size_t s3fd_detect_ws_bytes(int T, int P, int nms_top_k);
+int launch_s3fd_detect(avcer_ctx* ctx, const float* loc, const float* conf, const float* priors, int T, int P, int im_h, int im_w, float var0,
+                       float var1, float conf_thresh, float nms_thresh, int nms_top_k, int top_k, float threshold, void* ws, float* out,
+                       int32_t* out_n, hipStream_t st);
 
 int measure_ceilings(avcer_ctx* ctx, double* mfma_bf16_tflops, double* hbm_copy_tbs, hipStream_t st);
 

@@ -256,7 +256,7 @@ def run_dataset(engine, jobs: Sequence[VideoJob], detector=None, *, mode: int = 
 
     world = torch.distributed.get_world_size() if distributed and torch.distributed.is_initialized() else 1
     rank = torch.distributed.get_rank() if world > 1 else 0
-    # a detector is priced at its own network's work (R50 50.7 GFLOP per 640 x 360 frame, MobileNet-0.25 1.116); one without the
+    # a detector is priced at its own network's work (R50 50.7 GFLOP per 640 x 360 frame, MobileNet-0.25 1.116, S3FD 144.27); one without the
     # attribute counts as R50, as before
     det_cost = False if detector is None else (True if getattr(detector, "kind", 1) == 1 else float(detector.gflop_per_frame))
     shards = adist.shard_videos([adist.video_cost(j, window, det_cost if j.detections is None else False, sr, step) for j in jobs], world)

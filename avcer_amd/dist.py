@@ -54,8 +54,8 @@ def video_cost(job, window: float = 4, detector=False, sr: int = 16000, step: fl
     machine's peak, so equal cost is not equal time; it is what every rank can compute identically without running anything.
     Terms: per frame 7.667 for the static CNN, plus 50.7 * H*W / (640*360) when a
     detector runs; per LSTM evaluation 0.0577; per audio window 44.891 + (91.299 - 44.891) * (window*sr - 32000) / 32000.
-    `detector`: False, True (RetinaFace-R50: 50.7) or the detector's own GFLOP per 640 x 360 frame (MobileNet-0.25: 1.116,
-    `RetinaFacePredictor.gflop_per_frame`).  Every frame is counted as present (the face track is not known before stage 0)."""
+    `detector`: False, True (RetinaFace-R50: 50.7) or the detector's own GFLOP per 640 x 360 frame (MobileNet-0.25: 1.116, S3FD: 144.27;
+    the predictor's `gflop_per_frame`).  Every frame is counted as present (the face track is not known before stage 0)."""
     from .audio_pipeline import resample_out_len, resample_plan
     from .video_pipeline import lstm_step
 

@@ -122,19 +122,27 @@ class Engine:
         return int(self.lib.avcer_audio_head_kind(self.ctx))
 
     def load_face(self, state_dict):
-        """Either detector: RetinaFace(cfg_re50).state_dict() or RetinaFace(cfg_mnet).state_dict() (packing.pack_face tells them apart)."""
+        """Any of the three detectors: RetinaFace(cfg_re50).state_dict(), RetinaFace(cfg_mnet).state_dict() or S3FDNet.state_dict()
+        (packing.pack_face tells them apart)."""
         self._load(self.lib.avcer_load_face, packing.pack_face(state_dict))
 
     def face_kind(self) -> int:
-        """The loaded detector: 0 none, 1 RetinaFace-R50, 2 RetinaFace-MobileNet-0.25."""
+        """The loaded detector: 0 none, 1 RetinaFace-R50, 2 RetinaFace-MobileNet-0.25, 3 S3FD."""
         return int(self.lib.avcer_face_kind(self.ctx))
 
     def face_forward(self, frames_u8, mode: int = MODE_DEFAULT, rgb: bool = False):
-        """frames u8 [N,H,W,3] (BGR unless rgb) -> (loc [N,P,4], conf [N,P,2] softmaxed, landms [N,P,10])."""
+        """frames u8 [N,H,W,3] (BGR unless rgb) -> (loc [N,P,4], conf [N,P,2] softmaxed, landms [N,P,10]).  With the S3FD
+        detector loaded (face_kind 3) P = avcer_s3fd_num_priors(h, w) and there are no landmarks: (loc, conf, None)."""
         x = self._dev(frames_u8, torch.uint8)
         if x.dim() != 4 or x.shape[-1] != 3:
             raise ValueError(f"frames must be [N,H,W,3] uint8, got {tuple(x.shape)}")
         n, h, w = int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
+        if self.face_kind() == 3:
+            p = int(self.lib.avcer_s3fd_num_priors(h, w))
+            loc, conf = self._new(n, p, 4), self._new(n, p, 2)
+            self._check(self.lib.avcer_face_forward(self.ctx, _ptr(x), n, h, w, 1 if rgb else 0, mode, _ptr(loc), _ptr(conf), None,
+                                                    self._stream()))
+            return loc, conf, None
         p = int(self.lib.avcer_face_num_priors(h, w))
         loc, conf, lm = self._new(n, p, 4), self._new(n, p, 2), self._new(n, p, 10)
         self._check(self.lib.avcer_face_forward(self.ctx, _ptr(x), n, h, w, 1 if rgb else 0, mode, _ptr(loc), _ptr(conf),
@@ -392,6 +400,23 @@ class Engine:
                                             int(top_k), float(threshold), _ptr(out), _ptr(cnt), self._stream()))
         return out, cnt
 
+    def s3fd_detect(self, loc, conf, priors, image_size, variance=(0.1, 0.2), conf_thresh: float = 0.05, nms_thresh: float = 0.3,
+                    nms_top_k: int = 5000, top_k: int = 750, threshold: float = 0.8):
+        """S3FD's `Detect` and the predictor's threshold loop for T frames (avcer_s3fd_detect): loc [T,P,4], conf [T,P,2] softmaxed,
+        priors [P,4] -> (rows [T,top_k,5] = x0, y0, x1, y1 in pixels, score; counts [T]); only counts[t] rows of frame t are meaningful."""
+        loc, conf, priors = self._dev(loc, torch.float32), self._dev(conf, torch.float32), self._dev(priors, torch.float32)
+        if loc.dim() == 2:
+            loc, conf = loc[None], conf[None]
+        t, p = int(loc.shape[0]), int(priors.shape[0])
+        if tuple(loc.shape) != (t, p, 4) or tuple(conf.shape) != (t, p, 2) or tuple(priors.shape) != (p, 4):
+            raise ValueError("s3fd_detect: loc [T,P,4], conf [T,P,2], priors [P,4]")
+        out = self._new(t, top_k, 5)
+        cnt = self._new(t, dtype=torch.int32)
+        self._check(self.lib.avcer_s3fd_detect(self.ctx, _ptr(loc), _ptr(conf), _ptr(priors), t, p, int(image_size[0]), int(image_size[1]),
+                                               float(variance[0]), float(variance[1]), float(conf_thresh), float(nms_thresh),
+                                               int(nms_top_k), int(top_k), float(threshold), _ptr(out), _ptr(cnt), self._stream()))
+        return out, cnt
+
     def track_faces(self, dets_per_frame, frame_w: int, frame_h: int, iou_threshold: float = 0.4, minimum_face_size: float = 0.0):
         """The tracker + crop-rectangle loop of `VideoPredictor.process` for a whole video in one native HOST call
         (csrc/track.hip): per-frame detection arrays [k, >= 4] -> records int64 [n, 6] = frame, track directory, x0, y0, x1, y1.
@@ -641,6 +666,43 @@ class Engine:
         self._check(self.lib.avcer_dwsep(self.ctx, cin, cout, int(stride), int(mode), nb, h, w, _ptr(x), _ptr(args[0]), _ptr(args[1]),
                                          _ptr(args[2]), _ptr(wdev), _ptr(args[3]), _ptr(args[4]), _ptr(y), self._stream()))
         return y
+
+    # kernel-level entries of csrc/s3fd.hip.  `sp32` = the activations are sp32 storage (int16 tensors of twice the channels,
+    # avcer_amd/sp32.py) instead of f32
+    def s3fd_stem(self, frames_u8, wt, bias, rgb: bool = False, sp32: bool = False):
+        """u8 frames [n,h,w,3] -> ReLU(conv1_1 of RGB pixel - (123, 117, 104)) as NHWC [n,h,w,64]; wt f32 [27,64], bias [64]."""
+        x = self._dev(frames_u8, torch.uint8)
+        n, h, w = (int(v) for v in x.shape[:3])
+        wt, bias = self._dev(wt, torch.float32), self._dev(bias, torch.float32)
+        y = self._new(n, h, w, 128, dtype=torch.int16) if sp32 else self._new(n, h, w, 64)
+        self._check(self.lib.avcer_s3fd_stem(self.ctx, _ptr(x), n, h, w, 1 if rgb else 0, _ptr(wt), _ptr(bias), _ptr(y), 2 if sp32 else 0,
+                                             self._stream()))
+        return y
+
+    def maxpool2(self, x, ceil_mode: bool = False, sp32: bool = False):
+        """nn.MaxPool2d(2, 2, ceil_mode=ceil_mode) on NHWC x [n,h,w,c] (f32, or int16 [n,h,w,2c] sp32)."""
+        x = self._dev(x, torch.int16 if sp32 else torch.float32)
+        n, h, w = (int(v) for v in x.shape[:3])
+        c = int(x.shape[3]) // (2 if sp32 else 1)
+        oh, ow = ((h + 1) // 2, (w + 1) // 2) if ceil_mode else (h // 2, w // 2)
+        if oh < 1 or ow < 1:
+            raise ValueError(f"maxpool2: a {h} x {w} map has no 2 x 2 window")
+        y = torch.empty(n, oh, ow, int(x.shape[3]), dtype=x.dtype, device=self.device)
+        self._check(self.lib.avcer_maxpool2(self.ctx, _ptr(x), _ptr(y), n, h, w, c, int(ceil_mode), 2 if sp32 else 0, self._stream()))
+        return y
+
+    def s3fd_head(self, x, wt, bias, l2norm: bool, sp32: bool = False):
+        """One S3FD level's heads: NHWC x [nb,h,w,c] (f32, or int16 [nb,h,w,2c] sp32), wt f32 [9,c,8 or 6], bias -> (loc [nb,h*w,4],
+        conf [nb,h*w,2] softmaxed); `l2norm`: every tap is divided by its position's L2 norm + 1e-10."""
+        x = self._dev(x, torch.int16 if sp32 else torch.float32)
+        nb, h, w = (int(v) for v in x.shape[:3])
+        c = int(x.shape[3]) // (2 if sp32 else 1)
+        wt, bias = self._dev(wt, torch.float32), self._dev(bias, torch.float32)
+        loc, conf = self._new(nb, h * w, 4), self._new(nb, h * w, 2)
+        inv = self._new(nb * h * w) if l2norm else None
+        self._check(self.lib.avcer_s3fd_head(self.ctx, _ptr(x), 2 if sp32 else 0, _ptr(inv), _ptr(wt), _ptr(bias), nb, h, w, c,
+                                             int(wt.shape[2]), 0, h * w, _ptr(loc), _ptr(conf), self._stream()))
+        return loc, conf
 
     def attention(self, qkv, out, n: int, s: int, heads: int, head_dim: int, scale: float, in_kind: int, out_kind: int):
         """Kernel-level entry of the attention kernel: qkv [n, s, 3 * heads * head_dim] -> out [n, s, heads * head_dim];

@@ -133,6 +133,101 @@ class RetinaFacePredictor:
         return self.post.batch(loc, conf, lm, size)
 
 
+# s3fd_predictor.py:27-42: get_model("s3fd").config and create_config()'s defaults
+CFG_S3FD = {"min_sizes": (16, 32, 64, 128, 256, 512), "steps": (4, 8, 16, 32, 64, 128), "variance": (0.1, 0.2), "clip": False,
+            "top_k": 750, "conf_thresh": 0.05, "nms_thresh": 0.3, "nms_top_k": 5000}
+
+
+def s3fd_feature_maps(h: int, w: int):
+    """(rows, columns) of the six head inputs of S3FDNet for an h x w frame: two floor pools, the ceil_mode pool (vgg.16), two more
+    floor pools, then the two stride-2 extras (3x3, padding 1).  The rule of `avcer_s3fd_num_priors`."""
+    def ext(v):
+        f = [v // 2 // 2]
+        f.append(-(-f[0] // 2))
+        f.append(f[1] // 2)
+        f.append(f[2] // 2)
+        f.append((f[3] - 1) // 2 + 1)
+        f.append((f[4] - 1) // 2 + 1)
+        return f
+    return list(zip(ext(int(h)), ext(int(w))))
+
+
+@lru_cache(maxsize=8)
+def _s3fd_prior_boxes(h: int, w: int) -> np.ndarray:
+    levels = []
+    for (fh, fw), size, step in zip(s3fd_feature_maps(h, w), CFG_S3FD["min_sizes"], CFG_S3FD["steps"]):
+        # utils.py:189-199 in the same Python-float operations: (j + 0.5) / (imw / step), size / imw
+        cx = ((np.arange(fw, dtype=np.float64) + 0.5) / (w / step))[None, :]
+        cy = ((np.arange(fh, dtype=np.float64) + 0.5) / (h / step))[:, None]
+        lvl = np.stack(np.broadcast_arrays(cx, cy, np.float64(size / w), np.float64(size / h)), axis=-1)
+        levels.append(lvl.reshape(-1, 4))
+    out = np.concatenate(levels).astype(np.float32)
+    if CFG_S3FD["clip"]:
+        out = np.clip(out, 0.0, 1.0)
+    out.setflags(write=False)
+    return out
+
+
+def s3fd_prior_boxes(image_size) -> np.ndarray:
+    """`PriorBox(size, feature_maps, config).forward()` of S3FD (s3fd/utils.py:174-206) for an image of (height, width): one anchor
+    (cx, cy, w, h) per position of the six levels, computed in Python floats and stored as float32 like the reference's."""
+    return _s3fd_prior_boxes(int(image_size[0]), int(image_size[1]))
+
+
+class S3FDPredictor:
+    """`S3FDPredictor(threshold, device, model, config)` (s3fd/s3fd_predictor.py:12-68) on the HIP path: the network
+    (`avcer_face_forward`, detector kind 3) and `Detect` plus the predictor's threshold loop in one device-side call
+    (`avcer_s3fd_detect`).  `state_dict` = S3FDNet.state_dict() (`s3fd_weights.pth`, with or without a `module.` prefix).
+    Results are float32 [k,5] = x0, y0, x1, y1 in pixels, score.  Modes FP32 and F16X3 only.
+
+    When `top_k` boxes all pass the threshold, the reference's loop reads one row past its [top_k, 5] array and raises
+    (s3fd_predictor.py:59); this mirror returns those `top_k` rows."""
+
+    kind = packing.FACE_KIND_S3FD
+    gflop_per_frame = 144.27   # algorithmic GFLOP per 640 x 360 frame (DESIGN.md section 5): what dist.video_cost prices it at
+
+    def __init__(self, engine, state_dict, threshold: float = 0.8, mode: int = MODE_DEFAULT, top_k: int = CFG_S3FD["top_k"],
+                 conf_thresh: float = CFG_S3FD["conf_thresh"], nms_thresh: float = CFG_S3FD["nms_thresh"],
+                 nms_top_k: int = CFG_S3FD["nms_top_k"]):
+        if packing.face_kind(state_dict) != packing.FACE_KIND_S3FD:
+            raise ValueError("S3FDPredictor: not an S3FDNet state dict")
+        self.engine, self.mode, self.threshold = engine, mode, threshold
+        self.top_k, self.conf_thresh, self.nms_thresh, self.nms_top_k = top_k, conf_thresh, nms_thresh, nms_top_k
+        engine.load_face(state_dict)
+        self._priors_dev = {}
+
+    def _rows(self, x, rgb):
+        size = (int(x.shape[1]), int(x.shape[2]))
+        if size not in self._priors_dev:
+            self._priors_dev[size] = torch.from_numpy(np.array(s3fd_prior_boxes(size))).to(self.engine.device)
+        # the x3 mode's range contract: a pass that left fp16's range is repeated in f32 (Engine.guarded)
+        loc, conf, _ = self.engine.guarded(self.mode, lambda m: self.engine.face_forward(x, m, rgb=rgb))
+        return self.engine.s3fd_detect(loc, conf, self._priors_dev[size], size, CFG_S3FD["variance"], self.conf_thresh, self.nms_thresh,
+                                       self.nms_top_k, self.top_k, self.threshold)
+
+    def __call__(self, image, rgb: bool = True) -> np.ndarray:
+        """image u8 [H,W,3] -> detections [k,5] (float32)."""
+        img = image if torch.is_tensor(image) else torch.from_numpy(np.ascontiguousarray(image))
+        rows, cnt = self._rows(img[None], rgb)
+        k = int(cnt[0])
+        return rows[0, :k].cpu().numpy() if k else np.empty((0, 5), dtype=np.float32)
+
+    def batch(self, frames, rgb: bool = False) -> List[np.ndarray]:
+        """frames u8 [T,H,W,3] -> one [k,5] array per frame; the network and the post-processing run once over the batch, and only
+        the kept rows cross to the host, through a page-locked buffer (as in FaceDetections.batch)."""
+        x = frames if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames))
+        rows, cnt = self._rows(x, rgb)
+        cnt = cnt.cpu().numpy()
+        most = int(cnt.max()) if len(cnt) else 0
+        if not most:
+            return [np.empty((0, 5), dtype=np.float32) for _ in range(len(cnt))]
+        host = torch.empty((int(rows.shape[0]), most, 5), dtype=torch.float32, pin_memory=True)
+        host.copy_(rows[:, :most], non_blocking=True)
+        torch.cuda.current_stream(rows.device).synchronize()
+        rows = host.numpy()
+        return [rows[t, :int(cnt[t])] if cnt[t] else np.empty((0, 5), dtype=np.float32) for t in range(len(cnt))]
+
+
 class SimpleFaceTracker:
     """IoU + Hungarian face tracker; ids start at 1, a frame without faces drops every tracklet."""
 

@@ -153,17 +153,28 @@ def permute_rows_for_mfma(w: np.ndarray) -> np.ndarray:
 
 MNET_BLOCKS = ((8, 16, 1), (16, 32, 2), (32, 32, 1), (32, 64, 2), (64, 64, 1), (64, 128, 2)) + ((128, 128, 1),) * 5 + (
     (128, 256, 2), (256, 256, 1))  # the conv_dw blocks of MobileNetV1 (retina_face_net.py:106-125): (cin, cout, stride)
-FACE_KIND_R50, FACE_KIND_MNET = 1, 2  # avcer_face_kind
+FACE_KIND_R50, FACE_KIND_MNET, FACE_KIND_S3FD = 1, 2, 3  # avcer_face_kind
+# S3FDNet (s3fd_net.py:35-105): the convolutions of `vgg` behind conv1_1 as (vgg index, cin, cout, kernel); index 31 is fc6
+# (3x3, dilation 6), 33 is fc7 (1x1); the channels of the six head inputs and the L2Norm module of the first three
+S3FD_CONVS = ((2, 64, 64, 3), (5, 64, 128, 3), (7, 128, 128, 3), (10, 128, 256, 3), (12, 256, 256, 3), (14, 256, 256, 3),
+              (17, 256, 512, 3), (19, 512, 512, 3), (21, 512, 512, 3), (24, 512, 512, 3), (26, 512, 512, 3), (28, 512, 512, 3),
+              (31, 512, 1024, 3), (33, 1024, 1024, 1))
+S3FD_EXTRAS = ((1024, 256, 1), (256, 512, 3), (512, 128, 1), (128, 256, 3))
+S3FD_SOURCES = (256, 512, 512, 1024, 512, 256)
+S3FD_L2NORM = ("L2Norm3_3", "L2Norm4_3", "L2Norm5_3")
 
 
 def face_kind(sd) -> int:
-    """Which detector a RetinaFace state dict holds, by key (after the `module.` / wrapper spellings are undone):
-    `body.stage1.0.0.weight` = MobileNet-0.25 (cfg_mnet), `body.conv1.weight` = ResNet-50 (cfg_re50)."""
+    """Which detector a state dict holds, by key (after the `module.` / wrapper spellings are undone):
+    `body.stage1.0.0.weight` = RetinaFace MobileNet-0.25 (cfg_mnet), `body.conv1.weight` = RetinaFace ResNet-50 (cfg_re50),
+    `vgg.0.weight` and `L2Norm3_3.weight` = S3FD (s3fd_net.py)."""
     sd = _face_keys(sd)
+    if "vgg.0.weight" in sd and "L2Norm3_3.weight" in sd:
+        return FACE_KIND_S3FD
     mnet, r50 = "body.stage1.0.0.weight" in sd, "body.conv1.weight" in sd
     if mnet == r50:
         raise ValueError("pack_face: the state dict is neither RetinaFace(cfg_re50) (body.conv1.weight) nor RetinaFace(cfg_mnet) "
-                         "(body.stage1.0.0.weight)")
+                         "(body.stage1.0.0.weight) nor S3FDNet (vgg.0.weight, L2Norm3_3.weight)")
     return FACE_KIND_MNET if mnet else FACE_KIND_R50
 
 
@@ -216,12 +227,44 @@ def pack_face_mnet(sd) -> "OrderedDict[str, np.ndarray]":
     return out
 
 
+def pack_face_s3fd(sd) -> "OrderedDict[str, np.ndarray]":
+    """S3FDNet.state_dict() (s3fd_net.py:28-105) for csrc/s3fd.hip.  `s3fd.kind` records the variant in the blob (avcer_face_kind).
+    There is no BatchNorm: every convolution keeps its own bias and runs with scale 1.
+      * `stem.wt` [27, 64], taps (ky, kx, c) major: conv1_1, computed from the u8 frame by s3fd_stem_kernel;
+      * `vgg{i}.w` / `ex{i}.w` [cout, kh*kw*cin]: the contractions of the trunk and the extras, the layout of every other conv;
+      * `head{i}.wt` [9, cin, 8 or 6]: one level's `loc` (columns 0-3) and `conf` (columns 4-7 on level 0, 4-5 on the others)
+        convolutions as one direct convolution; on the three L2Norm levels the norm layer's weight[c] is multiplied into the
+        input-channel axis, so the kernel only divides by the position's norm and the normalised tensor never exists."""
+    out: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    out["s3fd.kind"] = np.array([FACE_KIND_S3FD], np.float32)
+    out["stem.wt"] = _conv_wt(sd["vgg.0.weight"])
+    out["stem.b"] = _f32(sd["vgg.0.bias"])
+    for idx, cin, cout, k in S3FD_CONVS:
+        w = _f32(sd[f"vgg.{idx}.weight"])
+        assert w.shape == (cout, cin, k, k), (idx, w.shape)
+        out[f"vgg{idx}.w"], out[f"vgg{idx}.b"] = _conv_w(w), _f32(sd[f"vgg.{idx}.bias"])
+    for i, (cin, cout, k) in enumerate(S3FD_EXTRAS):
+        w = _f32(sd[f"extras.{i}.weight"])
+        assert w.shape == (cout, cin, k, k), (i, w.shape)
+        out[f"ex{i}.w"], out[f"ex{i}.b"] = _conv_w(w), _f32(sd[f"extras.{i}.bias"])
+    for i, c in enumerate(S3FD_SOURCES):
+        w = np.concatenate([_f32(sd[f"loc.{i}.weight"]), _f32(sd[f"conf.{i}.weight"])])   # [8 or 6, c, 3, 3]
+        assert w.shape == (8 if i == 0 else 6, c, 3, 3), (i, w.shape)
+        if i < 3:
+            w = w * _f32(sd[S3FD_L2NORM[i] + ".weight"]).reshape(1, c, 1, 1)
+        out[f"head{i}.wt"] = np.ascontiguousarray(w.transpose(2, 3, 1, 0)).reshape(9, c, w.shape[0]).astype(np.float32)
+        out[f"head{i}.b"] = np.concatenate([_f32(sd[f"loc.{i}.bias"]), _f32(sd[f"conf.{i}.bias"])])
+    return out
+
+
 def pack_face(sd) -> "OrderedDict[str, np.ndarray]":
-    """RetinaFace(cfg_re50).state_dict() (retina_face/retina_face.py:46-76; `body.*` = torchvision ResNet-50 children), or
-    RetinaFace(cfg_mnet).state_dict(): told apart by key (face_kind), the latter packed by pack_face_mnet."""
+    """RetinaFace(cfg_re50).state_dict() (retina_face/retina_face.py:46-76; `body.*` = torchvision ResNet-50 children),
+    RetinaFace(cfg_mnet).state_dict() or S3FDNet.state_dict(): told apart by key (face_kind), the second packed by pack_face_mnet,
+    the third by pack_face_s3fd."""
     eps = 1e-5  # torch.nn.BatchNorm2d default, used by torchvision's ResNet and by retina_face_net.py
-    if face_kind(sd) == FACE_KIND_MNET:
-        return pack_face_mnet(_face_keys(sd))
+    kind = face_kind(sd)
+    if kind != FACE_KIND_R50:
+        return (pack_face_mnet if kind == FACE_KIND_MNET else pack_face_s3fd)(_face_keys(sd))
     sd = _unwrap(sd)
     sd = {(k.split("module.", 1)[-1] if k.startswith("module.") else k): v for k, v in sd.items()}  # predictor.py:28-33
     out: "OrderedDict[str, np.ndarray]" = OrderedDict()

@@ -35,7 +35,7 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
     (44.1 kHz stereo, data/utils.py:46) or float32 [L] / [C, L] -- and is converted, downmixed and resampled to `sr` on the device,
     on the audio stream in front of the chunker (data/utils.py:50-57, Engine.resample).  A rate pair the kernel does not cover
     raises ValueError before any work.
-    `detector`: a `face_tiles.RetinaFacePredictor` (threshold 0.8 in the reference); or pass per-frame `detections`.
+    `detector`: a `face_tiles.RetinaFacePredictor` or `face_tiles.S3FDPredictor` (threshold 0.8 in the reference); or pass per-frame `detections`.
     Defaults follow `run_inference`'s signature (Rule 2 weights on, Rule 1 mask off; `run.py --help` flips them).
     Returns a dict: av / vs / vd / a predictions (int32 [T], compound class per frame), `compound_prob` f64 [4,T,7],
     `static_probs`, `dynamic_logits` [T,7], `audio_rows` / `audio_frames` (the audio table), `records` (face files),

@@ -205,6 +205,46 @@ def retina_mnet_state_dict(seed: int = 42) -> "OrderedDict[str, np.ndarray]":
     return sd
 
 
+# (vgg index, cin, cout, kernel) of the convolutions of S3FDNet.vgg (s3fd_net.py:35-76); index 31 is fc6 (dilation 6), 33 is fc7
+S3FD_VGG = ((0, 3, 64, 3), (2, 64, 64, 3), (5, 64, 128, 3), (7, 128, 128, 3), (10, 128, 256, 3), (12, 256, 256, 3), (14, 256, 256, 3),
+            (17, 256, 512, 3), (19, 512, 512, 3), (21, 512, 512, 3), (24, 512, 512, 3), (26, 512, 512, 3), (28, 512, 512, 3),
+            (31, 512, 1024, 3), (33, 1024, 1024, 1))
+S3FD_EXTRAS = ((1024, 256, 1), (256, 512, 3), (512, 128, 1), (128, 256, 3))   # s3fd_net.py:82-87
+S3FD_SOURCES = (256, 512, 512, 1024, 512, 256)                                # channels of the six head inputs (:89-105)
+S3FD_L2NORM = (("L2Norm3_3", 256, 10.0), ("L2Norm4_3", 512, 8.0), ("L2Norm5_3", 512, 5.0))
+
+
+def s3fd_state_dict(seed: int = 42) -> "OrderedDict[str, np.ndarray]":
+    """Keys of S3FDNet(config).state_dict() (s3fd_net.py:28-105) in its order: `vgg.{0,2,5,...,33}.*`, `L2Norm{3_3,4_3,5_3}.weight`,
+    `extras.{0-3}.*`, `loc.{0-5}.*`, `conf.{0-5}.*`: 65 entries, 22 459 110 values.  There is no BatchNorm in this network, so every
+    convolution has the He gain of a ReLU layer and activations stay O(1) through the thirteen layers of the trunk.  The L2Norm
+    weights sit within 20 % of their initial 10 / 8 / 5.  The `conf` heads are scaled so that the face-minus-background logit has a
+    standard deviation of a few units on every level (on the three normalised levels the input's norm is known: the L2Norm weight), and
+    the face channel's bias is shifted down, which leaves conf[:, 1] spread over (0, 1) with a minority of priors above 0.05."""
+    sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
+
+    def conv(name, cout, cin, k, gain=2.0, std=None):
+        if std is None:
+            _conv2d(sd, seed, name + ".weight", cout, cin, k, gain=gain)
+        else:
+            sd[name + ".weight"] = centered(seed, name + ".weight", (cout, cin, k, k), std)
+        sd[name + ".bias"] = uniform(seed, name + ".bias", (cout,), -0.1, 0.1)
+
+    for idx, cin, cout, k in S3FD_VGG:
+        conv(f"vgg.{idx}", cout, cin, k, gain=2.0 / (60.0 * 60.0) if idx == 0 else 2.0)   # pixels minus (123, 117, 104)
+    for name, c, init in S3FD_L2NORM:
+        sd[name + ".weight"] = uniform(seed, name + ".weight", (c,), 0.8 * init, 1.2 * init)
+    for i, (cin, cout, k) in enumerate(S3FD_EXTRAS):
+        conv(f"extras.{i}", cout, cin, k)
+    for i, c in enumerate(S3FD_SOURCES):
+        conv(f"loc.{i}", 4, c, 3, gain=1.0)
+    for i, c in enumerate(S3FD_SOURCES):
+        # a normalised level's nine taps carry sum x^2 = 9 * weight^2: a per-logit deviation of 5 wants std 5 / (3 * weight)
+        conv(f"conf.{i}", 4 if i == 0 else 2, c, 3, gain=25.0, std=5.0 / (3.0 * S3FD_L2NORM[i][2]) if i < 3 else None)
+        sd[f"conf.{i}.bias"][-1] -= np.float32(8.0)   # the face channel is the last one on every level
+    return sd
+
+
 def video_frames(seed: int, n: int, h: int, w: int) -> np.ndarray:
     """uint8 BGR video frames [n, h, w, 3] for the detector."""
     return u8(seed, "video", (n, h, w, 3))

@@ -75,7 +75,9 @@ enum {
  *      avcer_fuse_videos (fusion of a set of unequal videos in one launch) joined under 8: one more symbol, nothing that
  *      existed changed; a binary without it is refused by its source hash.
  *      avcer_face_kind and avcer_dwsep (the MobileNet-0.25 RetinaFace detector: avcer_load_face / avcer_face_forward take either
- *      variant's blob) joined under 8 the same way: two more symbols, no struct layout or argument list changed. */
+ *      variant's blob) joined under 8 the same way: two more symbols, no struct layout or argument list changed.
+ *      avcer_s3fd_num_priors, avcer_s3fd_detect and the kernel-level entries avcer_s3fd_stem, avcer_maxpool2, avcer_s3fd_head (the
+ *      S3FD detector: avcer_load_face / avcer_face_forward take its blob as kind 3) joined under 8 the same way. */
 #define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
@@ -265,8 +267,22 @@ int avcer_face_num_priors(int h, int w);
  * pack_face makes of that state dict (it records the kind), and avcer_face_forward runs it with the same arguments and the same
  * P rows -- cfg_mnet and cfg_re50 share min_sizes, steps, variance and clip.  Modes: AVCER_MODE_FP32 and AVCER_MODE_F16X3;
  * AVCER_MODE_BF16 returns AVCER_EINVAL for this variant.  Loading a blob frees the previous detector and all its lazy copies.
- * avcer_face_kind: 0 = no detector loaded, 1 = RetinaFace-R50, 2 = RetinaFace-MobileNet-0.25. */
+ * avcer_face_kind: 0 = no detector loaded, 1 = RetinaFace-R50, 2 = RetinaFace-MobileNet-0.25, 3 = S3FD.
+ *
+ * The third detector, S3FD (s3fd/s3fd_net.py: VGG-16 trunk at full frame resolution, fc6 / fc7, four extras, L2Norm on the first
+ * three of six head levels, ONE anchor per position), goes through the same pair: avcer_load_face takes the blob pack_face makes of
+ * S3FDNet.state_dict(), avcer_face_forward runs it.  What differs for kind 3:
+ *   - `rgb` means what it means to S3FDPredictor.__call__ (s3fd_predictor.py:45-52): the network eats RGB minus (123, 117, 104);
+ *     rgb == 0 flips the BGR frame first;
+ *   - there are no landmarks: `landms` must be NULL (non-NULL is AVCER_EINVAL; for kinds 1 and 2 NULL is);
+ *   - loc f32 [n,P,4], conf f32 [n,P,2] (level 0's max-out background label taken, softmaxed) with P = avcer_s3fd_num_priors(h, w)
+ *     rows in the reference's order: level by level, row-major within a level.  Per axis, with floor division: a = h/2, b = a/2,
+ *     f0 = b, f1 = ceil(b/2), f2 = f1/2, f3 = f2/2, f4 = (f3-1)/2+1, f5 = (f4-1)/2+1; P = sum fh_i * fw_i (360 x 640: 19 175);
+ *   - h, w >= 32; AVCER_MODE_FP32 and AVCER_MODE_F16X3 only (AVCER_MODE_BF16 is AVCER_EINVAL).  In AVCER_MODE_F16X3 the trunk's
+ *     activations are sp32 pairs and every contraction epilogue counts for avcer_x3_overflow_count; the stem (conv1_1 from the u8
+ *     frame) and the heads are f32 arithmetic.  Feed loc / conf to avcer_s3fd_detect. */
 int avcer_face_kind(const avcer_ctx* ctx);
+int avcer_s3fd_num_priors(int h, int w);
 int avcer_face_forward(avcer_ctx* ctx, const uint8_t* frames, int n, int h, int w, int rgb, int mode, float* loc,
                        float* conf, float* landms, avcer_stream_t stream);
 
@@ -281,6 +297,20 @@ int avcer_face_forward(avcer_ctx* ctx, const uint8_t* frames, int n, int h, int 
  * given numpy build may visit (and keep) a different member of the tie. */
 int avcer_face_nms(avcer_ctx* ctx, const float* dets, int n_frames, int n_priors, float conf_thresh, float nms_thresh,
                    int nms_top_k, int top_k, float threshold, float* out, int32_t* out_n, avcer_stream_t stream);
+
+/* S3FD's post-processing for a batch of frames, on the device, without a host synchronisation:
+ *   ref: s3fd/utils.py:6-24 (decode), :94-128 (nms_np), :131-171 (Detect), s3fd/s3fd_predictor.py:54-68 (the threshold loop).
+ * loc f32 [n_frames, n_priors, 4] and conf f32 [n_frames, n_priors, 2] as avcer_face_forward writes them for kind 3, priors f32
+ * [n_priors, 4] (PriorBox: face_tiles.s3fd_prior_boxes).  Per frame, in the reference's order: boxes are decoded in NORMALISED
+ * coordinates with its rounding sequence (centre and size, x0 = cx - w/2, x1 = x0 + w); candidates are score > conf_thresh
+ * (strict); they are visited in descending score, at most nms_top_k of them, equal scores HIGHER prior index first (see
+ * avcer_face_nms); greedy NMS with area = (x1-x0)*(y1-y0) -- no "+1" -- keeps a box when iou <= nms_thresh; of the kept boxes
+ * the first min(count, top_k), of those the prefix with score >= threshold; the boxes are multiplied by (w, h, w, h) in f32 last.
+ * out f32 [n_frames, top_k, 5] = x0, y0, x1, y1 in pixels, score; out_n i32 [n_frames] the rows of each frame.
+ * nms_top_k <= 6144, top_k <= 1024, n_frames <= 65535. */
+int avcer_s3fd_detect(avcer_ctx* ctx, const float* loc, const float* conf, const float* priors, int n_frames, int n_priors, int im_h,
+                      int im_w, float var0, float var1, float conf_thresh, float nms_thresh, int nms_top_k, int top_k, float threshold,
+                      float* out, int32_t* out_n, avcer_stream_t stream);
 
 /* Face stage ("next" row f4): the arithmetic either side of the RetinaFace network.
  *   avcer_face_decode  ref: data/face_detection/ibug/face_detection/retina_face/retina_face_predictor.py:70-82,
@@ -466,6 +496,21 @@ int avcer_bneck_chain(avcer_ctx* ctx, int planes, int nb, int h, int w, const vo
 int avcer_dwsep(avcer_ctx* ctx, int cin, int cout, int stride, int mode, int nb, int h, int w, const float* x, const float* dw_w,
                 const float* dw_s, const float* dw_b, const void* pw_w, const float* pw_s, const float* pw_b, float* y,
                 avcer_stream_t stream);
+/* Kernel-level entries of csrc/s3fd.hip, for tests.  `kind`: storage of the activations, 0 = f32, 2 = sp32 (AVCER_MODE_F16X3).
+ *   avcer_s3fd_stem: u8 frames [n,h,w,3] -> ReLU(conv 3x3 pad 1 (3 -> 64) of RGB pixel - (123, 117, 104) + bias): y [n,h,w,64];
+ *     wt f32 [27][64], taps (ky, kx, c) major; rgb == 0: the frames are BGR.
+ *   avcer_maxpool2: nn.MaxPool2d(2, 2, ceil_mode) on NHWC x [n,h,w,c] -> y [n,h/2,w/2,c] (ceil_mode: ceil of both; a window over
+ *     the edge takes the maximum of what exists); c a multiple of 4 (sp32: of 32).
+ *   avcer_s3fd_head: one S3FD level's loc + conf 3x3 convolutions (padding 1) as one direct convolution: x [nb,h,w,c], c a multiple of
+ *     256; wt f32 [9][c][n_out], columns 0-3 loc, 4.. conf; n_out 8 (level 0: conf = (max of columns 4-6, column 7)) or 6; the two
+ *     conf values are softmaxed; rows go to loc [.., n_priors, 4] / conf [.., n_priors, 2] at frame * n_priors + row0.  inv_norm:
+ *     NULL, or scratch for nb*h*w floats: every tap is then multiplied by 1 / (sqrt(sum_c x^2) + 1e-10) of its position (L2Norm
+ *     with its weight folded into wt; an all-zero position contributes 0). */
+int avcer_s3fd_stem(avcer_ctx* ctx, const uint8_t* frames, int n, int h, int w, int rgb, const float* wt, const float* bias, void* y,
+                    int kind, avcer_stream_t stream);
+int avcer_maxpool2(avcer_ctx* ctx, const void* x, void* y, int n, int h, int w, int c, int ceil_mode, int kind, avcer_stream_t stream);
+int avcer_s3fd_head(avcer_ctx* ctx, const void* x, int kind, float* inv_norm, const float* wt, const float* bias, int nb, int h, int w,
+                    int c, int n_out, int row0, int n_priors, float* loc, float* conf, avcer_stream_t stream);
 int avcer_stem_pool(avcer_ctx* ctx, const void* planes_hi_lo, size_t plane_bytes, const void* w, const float* scale,
                     const float* bias, void* y, int n, avcer_stream_t stream);
 /* The same launch fed with the u8 frames themselves ([n,in_h,in_w,3] RGB; data/utils.py:19-39 -- NEAREST resize to 224, BGR flip,
@@ -571,6 +616,9 @@ int avcer_profile_read_launches(avcer_ctx* ctx, int64_t max_n, int32_t* fam, dou
  *     the full [n,7,7,2048];
  *   - "pre", "stem_conv", "l1b0_c2" exist in AVCER_MODE_FP32 / _BF16 only: AVCER_MODE_F16X3 preprocesses inside the fused
  *     stem and keeps conv2 outputs in registers, so those taps do not fire there.
+ * The S3FD detector (NHWC, post-ReLU, in the mode's storage): "s3fd_conv1" (conv1_1, the stem kernel's output), "s3fd_conv3_3",
+ * "s3fd_pool3" (the ceil_mode pool, vgg.16), "s3fd_conv4_3", "s3fd_conv5_3" (the three before their L2Norm), "s3fd_fc7",
+ * "s3fd_ex1" (extras.1 = conv6_2), "s3fd_ex3" (extras.3 = conv7_2).
  * avcer_debug_tap_copied returns the number of bytes copied, or -1 if the tap did not fire (compare it with the size you
  * expect: a short copy means the tensor is smaller than the buffer, e.g. a sub-sampled stage tap). */
 int avcer_debug_tap(avcer_ctx* ctx, const char* name, void* dst_dev, size_t bytes);

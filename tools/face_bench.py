@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""Throughput of the RetinaFace detector network (row f4) on synthetic video frames, per arithmetic mode.
+"""Throughput of the face detector networks (row f4) on synthetic video frames, per arithmetic mode.
 
-    face_bench.py [--model resnet50|mobilenet0.25]     the table of one model (default: resnet50)
-    face_bench.py --compare [--out FILE]               both models on 750 frames of 640 x 360 in ONE process: warmed, alternating,
-                                                       five samples each -> profiles/mnet_face_bench.json; fails unless the
-                                                       MobileNet-0.25 detector is the faster one."""
+    face_bench.py [--model resnet50|mobilenet0.25|s3fd]   the table of one model (default: resnet50)
+    face_bench.py --compare [--out FILE]                  the three models on 750 frames of 640 x 360 in ONE process: warmed,
+                                                          alternating, five samples each -> profiles/s3fd_face_bench.json, with
+                                                          S3FD against RetinaFace-R50 scaled by work and the time of S3FD's MFMA
+                                                          families; fails unless the MobileNet-0.25 detector is the fastest."""
 import argparse
 import json
 import os
@@ -19,7 +20,8 @@ sys.path.insert(0, ROOT)
 from avcer_amd import build, synth  # noqa: E402
 from avcer_amd.engine import Engine, MODE_BF16, MODE_F16X3, MODE_FP32  # noqa: E402
 
-STATE_DICTS = {"resnet50": synth.retina_state_dict, "mobilenet0.25": synth.retina_mnet_state_dict}
+STATE_DICTS = {"resnet50": synth.retina_state_dict, "mobilenet0.25": synth.retina_mnet_state_dict, "s3fd": synth.s3fd_state_dict}
+S3FD_GFLOP, R50_GFLOP = 144.27, 50.7   # algorithmic GFLOP per 640 x 360 frame
 
 
 def mnet_bytes_per_frame(h, w):
@@ -50,6 +52,8 @@ def table(model):
     eng.load_face(synth.to_torch(STATE_DICTS[model](42)))
     modes = (("fp32", MODE_FP32), ("x3", MODE_F16X3)) + ((("bf16", MODE_BF16),) if model == "resnet50" else ())
     for h, w, n in ((360, 640, 32), (720, 1280, 8)):
+        if model == "s3fd":
+            eng.face_forward(torch.from_numpy(synth.video_frames(3, 2, h, w)).cuda(), MODE_FP32)  # lazy copies before the timing
         frames = torch.from_numpy(synth.video_frames(3, 2, h, w)).cuda().repeat(n // 2, 1, 1, 1)
         for name, mode in modes:
             for _ in range(2):
@@ -102,19 +106,34 @@ def compare(out, n=750, h=360, w=640, samples=5, mode=MODE_F16X3):
     res["models"]["mobilenet0.25"].update(bytes_per_frame=b, achieved_tbs=b * n / t / 1e12,
                                           fraction_of_copy_ceiling=b * n / t / 1e12 / copy_tbs if copy_tbs else None)
     print(json.dumps(res))
+    # S3FD against the R50 detector of the same run, scaled by work, and where its time goes: one more pass under the event
+    # profile (one lane, every MFMA launch timed), the rest being the stem, the pools and the heads
+    r50, s3 = res["models"]["resnet50"]["ms_median"], res["models"]["s3fd"]["ms_median"]
+    eng = engines["s3fd"]
+    eng.profile_enable(True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    eng.face_forward(frames, mode)
+    torch.cuda.synchronize()
+    one_lane_ms = (time.perf_counter() - t0) * 1e3
+    fams = eng.profile_read_families()
+    eng.profile_enable(False)
+    res["models"]["s3fd"].update(r50_scaled_by_work_ms=r50 * S3FD_GFLOP / R50_GFLOP, ratio_to_r50_scaled_by_work=s3 / (r50 * S3FD_GFLOP / R50_GFLOP),
+                                 tflops_algorithmic=S3FD_GFLOP * n / s3 / 1e3, profiled_one_lane_ms=one_lane_ms, families=fams)
+    print(json.dumps(res["models"]["s3fd"]))
     if out:
         os.makedirs(os.path.dirname(out), exist_ok=True)
         with open(out, "w") as f:
             json.dump(res, f, indent=1)
             f.write("\n")
-    if not res["models"]["mobilenet0.25"]["ms_median"] < res["models"]["resnet50"]["ms_median"]:
-        raise SystemExit("the MobileNet-0.25 detector is not faster than RetinaFace-R50: something is broken")
+    if not res["models"]["mobilenet0.25"]["ms_median"] < min(r50, s3):
+        raise SystemExit("the MobileNet-0.25 detector is not the fastest of the three: something is broken")
 
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", choices=sorted(STATE_DICTS), default="resnet50")
     ap.add_argument("--compare", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mnet_face_bench.json"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "s3fd_face_bench.json"))
     a = ap.parse_args()
     compare(a.out) if a.compare else table(a.model)
