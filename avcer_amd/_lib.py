@@ -87,6 +87,11 @@ SIGNATURES = {
     "avcer_track_faces": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                                     C.c_void_p, C.POINTER(C.c_int64)]),
     "avcer_lsap": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "avcer_jpeg_probe": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "avcer_jpeg_entropy_batch": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
+                                           C.POINTER(C.c_int64)]),
+    "avcer_jpeg_tiles": (C.c_int, [c_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, c_stream]),
+    "avcer_jpeg_rgb": (C.c_int, [c_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_stream]),
     "avcer_crop_tiles": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                    C.c_void_p, c_stream]),
     "avcer_static_forward_cam": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

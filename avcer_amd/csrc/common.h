@@ -23,7 +23,7 @@ struct DevBuf {
 
 // the context's workspace slots (ws_reserve): one per pipeline, the second lanes of the two ResNets and two utilities
 enum { WS_STATIC = 0, WS_DYNAMIC = 1, WS_AUDIO = 2, WS_FACE = 3, WS_NMS = 4, WS_CEILINGS = 5, WS_STATIC_LANE1 = 6, WS_FACE_LANE1 = 7,
-       WS_GRU = 8, WS_COUNT = 9 };
+       WS_GRU = 8, WS_JPEG = 9, WS_COUNT = 10 };
 
 // how an activation tensor is stored (the `kind` / `act` arguments of the k_* launchers, Net::gemm's akind / okind)
 enum { KIND_F32 = 0, KIND_BF16 = 1, KIND_SP32 = 2 };
@@ -106,6 +106,10 @@ int set_err(avcer_ctx* ctx, int code, const char* fmt, ...);
     } while (0)
 
 int ws_reserve(avcer_ctx* ctx, int slot, size_t bytes, void** out);
+
+// PIL's NEAREST resize to 224 (data/utils.py:34): the source index of output index `o` along an axis of `len` source pixels.
+// The one statement of the rule: crop_tiles_kernel (kernels.hip) and jpeg_tiles_kernel (jpeg.hip) both call it.
+__device__ __forceinline__ int nearest_src(int o, int len) { return min((int)(((double)o + 0.5) * ((double)len / 224.0)), len - 1); }
 
 // ---- gemm.hip
 int launch_conv_gemm(avcer_ctx* ctx, const avcer_conv_desc& d, int dtype, const void* x, const void* w,

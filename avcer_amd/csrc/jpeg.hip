@@ -1,0 +1,734 @@
+// JPEG face crops (`<faces>/<track>/NNNNNN.jpg`, get_prob_video.py:79-100 + data/utils.py:34) without a decoder library:
+//   host   -- marker parsing and Huffman decoding, serial bit-stream work: one native call per batch of files, files spread over a
+//             small thread pool (avcer_jpeg_probe, avcer_jpeg_entropy_batch; ctx may be NULL, no device is touched);
+//   device -- everything behind the coefficients (avcer_jpeg_tiles, avcer_jpeg_rgb): kernel A dequantises and runs the inverse
+//             DCT into u8 component planes, kernel B computes exactly the output pixels asked for (the 224 x 224 NEAREST tile or
+//             the full-size canvas) from them: chroma upsampling at that pixel, YCbCr -> RGB.
+// All of it is integer arithmetic and restates what libjpeg(-turbo) computes with its defaults (JDCT_ISLOW, fancy upsampling):
+// the contract is bit-identity with PIL's decode (tests/test_jpeg_host.py holds the numpy statement of kernels A and B,
+// avcer_amd/jpeg.py pixels_numpy, to PIL; tests/test_gpu_jpeg.py holds the kernels to goldens PIL wrote).
+// A file outside the supported subset (include/avcer_hip.h) is REPORTED as not handled and never guessed at; the caller then
+// decodes it with PIL as before.
+#include "common.h"
+
+#include <algorithm>
+#include <atomic>
+#include <memory>
+#include <new>
+#include <thread>
+
+namespace {
+
+typedef avcer_jpeg_desc Desc;
+
+// ------------------------------------------------------------------------------------------------ host: markers
+enum {  // Desc::reason: why a file is not handled (0 = it is)
+    R_OK = 0, R_NO_SOI = 1, R_MARKER = 2, R_SOF_KIND = 3, R_PRECISION = 4, R_COMPONENTS = 5, R_SAMPLING = 6, R_COLOUR = 7, R_TABLE = 8,
+    R_SCAN = 9, R_TRUNCATED = 10, R_CODE = 11, R_NO_SPACE = 12, R_INDEX = 13, R_RESTART = 14, R_NO_EOI = 15, R_RANGE = 16, R_SIZE = 17
+};
+
+const uint8_t kNatural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                              41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                              30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+struct Huff {
+    bool defined = false;
+    uint8_t bits[17] = {0};
+    uint8_t vals[256] = {0};
+    int32_t maxcode[17];   // largest code of each length, -1 where the length has none
+    int32_t valoff[17];    // vals index of a code = code + valoff[length]
+    uint16_t look[512];    // the next 9 bits -> (length << 8) | symbol, 0: the code is longer
+    bool ok = false;       // a consistent code
+    bool dc_ok = false;    // ... whose symbols are magnitude categories (<= 15)
+};
+
+// libjpeg's jpeg_make_d_derived_tbl: canonical codes from the counts; a count list that over-subscribes a length is an error there
+void derive(Huff& t) {
+    t.ok = t.dc_ok = false;
+    int size[257], code[257], n = 0;
+    for (int l = 1; l <= 16; ++l) {
+        if (n + t.bits[l] > 256) return;
+        for (int i = 0; i < t.bits[l]; ++i) size[n++] = l;
+    }
+    int c = 0, si = n ? size[0] : 0, p = 0;
+    while (p < n) {
+        while (p < n && size[p] == si) code[p++] = c++;
+        if (c > (1 << si)) return;
+        c <<= 1;
+        ++si;
+    }
+    p = 0;
+    memset(t.look, 0, sizeof(t.look));
+    for (int l = 1; l <= 16; ++l) {
+        if (t.bits[l]) {
+            t.valoff[l] = p - code[p];
+            if (l <= 9)
+                for (int i = 0; i < t.bits[l]; ++i) {
+                    const int first = code[p + i] << (9 - l);
+                    for (int k = 0; k < (1 << (9 - l)); ++k) t.look[first + k] = (uint16_t)((l << 8) | t.vals[p + i]);
+                }
+            p += t.bits[l];
+            t.maxcode[l] = code[p - 1];
+        } else {
+            t.maxcode[l] = -1;
+            t.valoff[l] = 0;
+        }
+    }
+    t.ok = true;
+    t.dc_ok = true;
+    for (int i = 0; i < n; ++i) t.dc_ok = t.dc_ok && t.vals[i] <= 15;
+}
+
+struct Header {
+    Desc d;
+    int comp_id[3] = {0, 0, 0};
+    int comp_h[3] = {1, 1, 1}, comp_v[3] = {1, 1, 1};
+    int td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};
+    int restart = 0;
+    Huff dc[4], ac[4];
+    uint16_t q[4][64];
+    bool q_def[4] = {false, false, false, false};
+    size_t scan = 0;  // offset of the first entropy-coded byte
+};
+
+inline int be16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
+
+// Everything up to the first entropy-coded byte.  Returns a reason; on R_OK h.d holds the geometry and the tables of the scan.
+int parse_header(const uint8_t* s, size_t len, Header& h) {
+    h = Header();  // a worker reuses one Header for all its files: no table, id or restart interval of the last one survives
+    Desc& d = h.d;
+    memset(&d, 0, sizeof(d));
+    if (!s || len < 4 || s[0] != 0xFF || s[1] != 0xD8) return R_NO_SOI;
+    size_t p = 2;
+    bool sof = false, jfif = false, adobe = false;
+    int adobe_transform = -1;
+    for (;;) {
+        if (p + 2 > len) return R_TRUNCATED;
+        if (s[p] != 0xFF) return R_MARKER;  // bytes between segments: libjpeg skips them with a warning, this decoder does not guess
+        while (p < len && s[p] == 0xFF) ++p;  // fill bytes
+        if (p >= len) return R_TRUNCATED;
+        const int m = s[p++];
+        if (m == 0x00 || m == 0x01 || (m >= 0xD0 && m <= 0xD9)) return R_MARKER;  // stuffing, TEM, RSTn, SOI, EOI: not in a header
+        if (p + 2 > len) return R_TRUNCATED;
+        const int L = be16(s + p);
+        if (L < 2 || p + (size_t)L > len) return R_TRUNCATED;
+        const uint8_t* b = s + p + 2;
+        const int n = L - 2;
+        p += (size_t)L;
+        if (m == 0xC0 || m == 0xC1) {
+            if (sof || n < 6) return R_MARKER;
+            sof = true;
+            if (b[0] != 8) return R_PRECISION;
+            d.height = be16(b + 1);
+            d.width = be16(b + 3);
+            d.ncomp = b[5];
+            if (d.height == 0 || d.width == 0) return R_SIZE;  // height 0: a DNL segment would follow
+            if (d.ncomp != 1 && d.ncomp != 3) return R_COMPONENTS;
+            if (n != 6 + 3 * d.ncomp) return R_MARKER;
+            for (int c = 0; c < d.ncomp; ++c) {
+                h.comp_id[c] = b[6 + 3 * c];
+                h.comp_h[c] = b[7 + 3 * c] >> 4;
+                h.comp_v[c] = b[7 + 3 * c] & 15;
+                d.tq[c] = b[8 + 3 * c];
+                if (h.comp_h[c] < 1 || h.comp_h[c] > 4 || h.comp_v[c] < 1 || h.comp_v[c] > 4 || d.tq[c] > 3) return R_SAMPLING;
+            }
+            d.hs = h.comp_h[0];
+            d.vs = h.comp_v[0];
+        } else if (m >= 0xC2 && m <= 0xCF && m != 0xC4) {
+            return R_SOF_KIND;  // progressive, lossless, differential, arithmetic (SOF2..15, DAC, JPG)
+        } else if (m == 0xC4) {
+            int o = 0;
+            while (o < n) {
+                if (o + 17 > n) return R_TABLE;
+                const int tc = b[o] >> 4, th = b[o] & 15;
+                if (tc > 1 || th > 3) return R_TABLE;
+                Huff& t = tc ? h.ac[th] : h.dc[th];
+                int count = 0;
+                t.bits[0] = 0;
+                for (int l = 1; l <= 16; ++l) count += (t.bits[l] = b[o + l]);
+                if (count > 256 || o + 17 + count > n) return R_TABLE;
+                memset(t.vals, 0, sizeof(t.vals));
+                memcpy(t.vals, b + o + 17, (size_t)count);
+                t.defined = true;
+                derive(t);
+                o += 17 + count;
+            }
+        } else if (m == 0xDB) {
+            int o = 0;
+            while (o < n) {
+                const int pq = b[o] >> 4, tq = b[o] & 15;
+                if (pq != 0) return R_TABLE;  // 16-bit tables
+                if (tq > 3 || o + 65 > n) return R_TABLE;
+                for (int k = 0; k < 64; ++k) h.q[tq][kNatural[k]] = b[o + 1 + k];
+                h.q_def[tq] = true;
+                o += 65;
+            }
+        } else if (m == 0xDD) {
+            if (n != 2) return R_MARKER;
+            h.restart = be16(b);
+        } else if (m == 0xE0) {
+            if (n >= 14 && memcmp(b, "JFIF\0", 5) == 0) jfif = true;
+        } else if (m == 0xEE) {
+            if (n >= 12 && memcmp(b, "Adobe", 5) == 0) {
+                adobe = true;
+                adobe_transform = b[11];
+            }
+        } else if ((m >= 0xE1 && m <= 0xEF) || m == 0xFE) {
+            // APPn / COM: skipped
+        } else if (m == 0xDA) {
+            if (!sof) return R_MARKER;
+            if (n < 1 || b[0] != d.ncomp || n != 1 + 2 * d.ncomp + 3) return R_SCAN;  // a scan of fewer components: more scans follow
+            for (int c = 0; c < d.ncomp; ++c) {
+                if (b[1 + 2 * c] != h.comp_id[c]) return R_SCAN;
+                h.td[c] = b[2 + 2 * c] >> 4;
+                h.ta[c] = b[2 + 2 * c] & 15;
+                if (h.td[c] > 3 || h.ta[c] > 3) return R_SCAN;
+            }
+            const uint8_t* e = b + 1 + 2 * d.ncomp;
+            if (e[0] != 0 || e[1] != 63 || e[2] != 0) return R_SCAN;
+            h.scan = p;
+            break;
+        } else {
+            return R_MARKER;  // DNL, DHP, EXP, JPGn, reserved
+        }
+    }
+    // colour: one component is grey; three are YCbCr where libjpeg says so (jdapimin.c default_decompress_parms)
+    if (d.ncomp == 3) {
+        if (jfif) {
+        } else if (adobe) {
+            if (adobe_transform != 1) return R_COLOUR;
+        } else if (!(h.comp_id[0] == 1 && h.comp_id[1] == 2 && h.comp_id[2] == 3)) {
+            return R_COLOUR;
+        }
+        if (!((d.hs == 1 && d.vs == 1) || (d.hs == 2 && d.vs == 1) || (d.hs == 2 && d.vs == 2))) return R_SAMPLING;
+        if (h.comp_h[1] != 1 || h.comp_v[1] != 1 || h.comp_h[2] != 1 || h.comp_v[2] != 1) return R_SAMPLING;
+        const int mx = (d.width + 8 * d.hs - 1) / (8 * d.hs), my = (d.height + 8 * d.vs - 1) / (8 * d.vs);
+        d.bw[0] = mx * d.hs;
+        d.bh[0] = my * d.vs;
+        d.bw[1] = d.bw[2] = mx;
+        d.bh[1] = d.bh[2] = my;
+    } else {  // a one-component scan is not interleaved: its MCU is one block whatever the sampling factors say
+        d.bw[0] = (d.width + 7) / 8;
+        d.bh[0] = (d.height + 7) / 8;
+    }
+    d.n_blocks = 0;
+    for (int c = 0; c < d.ncomp; ++c) {
+        if (!h.q_def[d.tq[c]]) return R_TABLE;
+        if (!h.dc[h.td[c]].defined || !h.dc[h.td[c]].dc_ok || !h.ac[h.ta[c]].defined || !h.ac[h.ta[c]].ok) return R_TABLE;
+        memcpy(d.qt[c], h.q[d.tq[c]], sizeof(d.qt[c]));
+        d.n_blocks += (int64_t)d.bw[c] * d.bh[c];
+    }
+    // a block costs at least two bits (a DC code and an end-of-block code, one bit each at the least): a file whose header claims
+    // more blocks than its bytes can hold is cut short, and is refused here, before anybody reserves storage for its claim
+    if (d.n_blocks > 4 * (int64_t)(len - h.scan)) return R_TRUNCATED;
+    return R_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ host: entropy-coded segment
+// Bits of the entropy-coded segment, 0xFF00 unstuffed.  A marker or the end of the file stops the supply: bits past it read
+// as zero but cannot be CONSUMED (`bad`), so a stream that ends early is an error and never a picture.
+struct Bits {
+    const uint8_t* p;
+    const uint8_t* end;
+    uint64_t acc = 0;
+    int n = 0;
+    bool stop = false, bad = false;
+    void fill() {
+        while (n <= 48 && !stop) {
+            if (p >= end) { stop = true; break; }
+            const uint8_t b = *p;
+            if (b == 0xFF) {
+                if (p + 1 >= end || p[1] != 0) { stop = true; break; }
+                p += 2;
+            } else {
+                ++p;
+            }
+            acc = (acc << 8) | b;
+            n += 8;
+        }
+    }
+    inline int peek(int k) {
+        if (n < k) fill();
+        return (int)((n >= k ? acc >> (n - k) : acc << (k - n)) & ((1u << k) - 1));
+    }
+    inline void skip(int k) {
+        if (k > n) { bad = true; n = 0; } else n -= k;
+    }
+    inline int symbol(const Huff& t) {
+        const int e = t.look[peek(9)];
+        if (e) { skip(e >> 8); return e & 255; }
+        const int w = peek(16);
+        for (int l = 10; l <= 16; ++l) {
+            const int c = w >> (16 - l);
+            if (c <= t.maxcode[l]) { skip(l); return t.vals[(c + t.valoff[l]) & 255]; }
+        }
+        bad = true;  // a code the table does not define
+        return 0;
+    }
+    inline int receive_extend(int s) {
+        const int v = peek(s);
+        skip(s);
+        return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
+    }
+    // the end of an interval: pad bits dropped, then the marker (0xFF, fill bytes, code); -1 when there is none
+    int marker() {
+        if (n >= 8) return -1;  // whole unread bytes in front of the marker
+        n = 0;
+        acc = 0;
+        stop = false;
+        if (p >= end || *p != 0xFF) return -1;
+        while (p < end && *p == 0xFF) ++p;
+        return p < end ? *p++ : -1;
+    }
+};
+
+// One 8 x 8 block into `blk` (natural order, not dequantised).  `q`: the component's table, for the range check alone.
+int decode_block(Bits& br, const Huff& dc, const Huff& ac, const uint16_t* q, int& pred, int16_t* blk) {
+    memset(blk, 0, 64 * sizeof(int16_t));
+    const int s = br.symbol(dc);
+    if (br.bad) return R_CODE;
+    if (s) pred += br.receive_extend(s);
+    // libjpeg-turbo's SIMD dequantises in 16 bits: a product outside int16 has no defined picture
+    if (pred < -32768 || pred > 32767 || pred * (int)q[0] < -32768 || pred * (int)q[0] > 32767) return R_RANGE;
+    blk[0] = (int16_t)pred;
+    for (int k = 1; k < 64;) {
+        const int rs = br.symbol(ac);
+        if (br.bad) return R_CODE;
+        const int r = rs >> 4, z = rs & 15;
+        if (z) {
+            k += r;
+            if (k > 63) return R_INDEX;
+            const int v = br.receive_extend(z), nat = kNatural[k];
+            if (v * (int)q[nat] < -32768 || v * (int)q[nat] > 32767) return R_RANGE;
+            blk[nat] = (int16_t)v;
+            ++k;
+        } else if (r == 15) {
+            k += 16;
+            if (k > 64) return R_INDEX;
+        } else {
+            break;
+        }
+    }
+    return br.bad ? R_TRUNCATED : R_OK;
+}
+
+int decode_scan(const uint8_t* s, size_t len, const Header& h, int16_t* out) {
+    const Desc& d = h.d;
+    Bits br;
+    br.p = s + h.scan;
+    br.end = s + len;
+    int pred[3] = {0, 0, 0};
+    const bool inter = d.ncomp == 3;
+    const int mx = inter ? d.bw[1] : d.bw[0], my = inter ? d.bh[1] : d.bh[0];
+    const int ch[3] = {inter ? d.hs : 1, 1, 1}, cv[3] = {inter ? d.vs : 1, 1, 1};
+    int64_t base[3] = {0, (int64_t)d.bw[0] * d.bh[0], (int64_t)d.bw[0] * d.bh[0] + (int64_t)d.bw[1] * d.bh[1]};
+    int left = h.restart, next_rst = 0;
+    for (int y = 0; y < my; ++y)
+        for (int x = 0; x < mx; ++x) {
+            if (h.restart && left == 0) {
+                if (br.marker() != 0xD0 + next_rst) return R_RESTART;
+                next_rst = (next_rst + 1) & 7;
+                left = h.restart;
+                pred[0] = pred[1] = pred[2] = 0;
+            }
+            for (int c = 0; c < d.ncomp; ++c)
+                for (int v = 0; v < cv[c]; ++v)
+                    for (int u = 0; u < ch[c]; ++u) {
+                        const int64_t b = base[c] + (int64_t)(y * cv[c] + v) * d.bw[c] + (x * ch[c] + u);
+                        const int r = decode_block(br, h.dc[h.td[c]], h.ac[h.ta[c]], d.qt[c], pred[c], out + 64 * b);
+                        if (r != R_OK) return r;
+                    }
+            --left;
+        }
+    return br.marker() == 0xD9 ? R_OK : R_NO_EOI;  // anything else behind the scan: another scan, DNL, a cut file
+}
+
+// threads of the entropy pass: what the caller asks for, 16 at most and by default -- never the machine's core count.  The library
+// reads no environment: avcer_amd/jpeg.py turns OMP_NUM_THREADS into the argument.
+int pool_size(int threads) { return threads <= 0 || threads > 16 ? 16 : threads; }
+
+// ------------------------------------------------------------------------------------------------ device
+constexpr int CONST_BITS = 13, PASS1_BITS = 2;
+
+// libjpeg's jidctint.c (jpeg_idct_islow), one 1-D pass: 13-bit constants, DESCALE(x, n) = (x + 2^(n-1)) >> n.  The all-zero-AC
+// shortcuts of both passes (dc << PASS1_BITS; DESCALE(ws0, PASS1_BITS + 3)) ARE this arithmetic's results for such input -- the
+// even part is then (dc << 13) alone and the rounding term divides out -- so they are not restated.
+template <int SHIFT>
+__device__ __forceinline__ void idct_1d(int (&v)[8]) {
+    // Sums and products in uint32_t: modulo 2^32, the same bits as libjpeg's arithmetic wherever that stays inside 32 bits (every
+    // image the range guard passes), and defined -- no signed overflow -- where a corrupt file's does not (its result is discarded).
+    typedef uint32_t U;
+    const auto mul = [](U a, int k) { return a * (U)k; };
+    U z2 = (U)v[2], z3 = (U)v[6];
+    U z1 = mul(z2 + z3, 4433);
+    U tmp2 = z1 + mul(z3, -15137);
+    U tmp3 = z1 + mul(z2, 6270);
+    z2 = (U)v[0];
+    z3 = (U)v[4];
+    U tmp0 = (z2 + z3) << CONST_BITS;
+    U tmp1 = (z2 - z3) << CONST_BITS;
+    const U tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+    tmp0 = (U)v[7];
+    tmp1 = (U)v[5];
+    tmp2 = (U)v[3];
+    tmp3 = (U)v[1];
+    z1 = tmp0 + tmp3;
+    z2 = tmp1 + tmp2;
+    z3 = tmp0 + tmp2;
+    U z4 = tmp1 + tmp3;
+    const U z5 = mul(z3 + z4, 9633);
+    tmp0 = mul(tmp0, 2446);
+    tmp1 = mul(tmp1, 16819);
+    tmp2 = mul(tmp2, 25172);
+    tmp3 = mul(tmp3, 12299);
+    z1 = mul(z1, -7373);
+    z2 = mul(z2, -20995);
+    z3 = mul(z3, -16069) + z5;
+    z4 = mul(z4, -3196) + z5;
+    tmp0 += z1 + z3;
+    tmp1 += z2 + z4;
+    tmp2 += z2 + z3;
+    tmp3 += z1 + z4;
+    constexpr U R = (U)1 << (SHIFT - 1);
+    const auto descale = [](U x) { return (int)(x + R) >> SHIFT; };  // arithmetic shift of the two's-complement value
+    v[0] = descale(tmp10 + tmp3);
+    v[7] = descale(tmp10 - tmp3);
+    v[1] = descale(tmp11 + tmp2);
+    v[6] = descale(tmp11 - tmp2);
+    v[2] = descale(tmp12 + tmp1);
+    v[5] = descale(tmp12 - tmp1);
+    v[3] = descale(tmp13 + tmp0);
+    v[4] = descale(tmp13 - tmp0);
+}
+
+// the image whose coefficient blocks hold block g: the last one that starts at or before it (offsets ascend, avcer_jpeg_entropy_batch)
+__device__ __forceinline__ int image_of_block(const Desc* __restrict__ desc, int n, long g) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (desc[mid].coef_block <= g) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+constexpr int IDCT_THREADS = 256;  // 4 waves, 8 blocks each
+constexpr int WS_LD = 9;           // dwords per row of a block's 8 x 8 workspace in LDS
+
+// Kernel A.  A wave takes 8 consecutive blocks; lane = 8 * block + j.  Lane j loads ROW j of its block's coefficients and of the
+// quantisation table (16 bytes each: the wave reads 1 KiB of coefficients in one instruction), multiplies and leaves the
+// products in LDS; then takes COLUMN j (pass 1), then ROW j (pass 2) and stores that row's 8 samples with one 8-byte store.
+// LDS rows are 9 dwords and blocks 72, so within a 32-lane half both the column access (bank 8 b + j + 9 r) and the row access
+// (bank 8 b + 9 j + k) touch 32 distinct banks: neither pass has a bank conflict.
+//
+// Range guard.  libjpeg's C code (wide integers, a range table that wraps at 10 bits) and its SIMD code (16-bit pair sums,
+// pass-1 results saturated to int16, saturating packs at the end) compute the same picture only while the values stay small:
+// dequantised coefficients and pass-1 results within +-IDCT_PAIR_MAX (any two add up inside int16), samples within [-512, 511]
+// before the +128.  Every picture an encoder wrote is far inside (pass 1 reaches ~4096 for full-swing samples plus the
+// quantisation error); a corrupt stream or table may not be, and then "PIL's decode" depends on how libjpeg was built.  Such an
+// image is not guessed at: its flag is raised, kernel B leaves it zero, and the caller decodes it some other way.
+constexpr int IDCT_PAIR_MAX = 16383;
+
+__global__ void __launch_bounds__(IDCT_THREADS) jpeg_idct_kernel(const int16_t* __restrict__ coeffs, const Desc* __restrict__ desc,
+                                                                 int n, long n_blocks, uint8_t* __restrict__ planes,
+                                                                 int32_t* __restrict__ flags) {
+    __shared__ int ws[IDCT_THREADS / 64][8 * 8 * WS_LD];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = lane >> 3, j = lane & 7;
+    const long g = ((long)blockIdx.x * (IDCT_THREADS / 64) + wave) * 8 + b;
+    int* w = ws[wave] + b * 8 * WS_LD;
+    bool live = false, wild = false;
+    uint8_t* dst = nullptr;
+    int ld = 0, i = 0;
+    if (g < n_blocks) {
+        i = image_of_block(desc, n, g);
+        const Desc* d = desc + i;
+        const long r = g - d->coef_block;
+        if (d->status == AVCER_JPEG_OK && r >= 0 && r < d->n_blocks) {
+            live = true;
+            const long c0 = (long)d->bw[0] * d->bh[0], c1 = c0 + (long)d->bw[1] * d->bh[1];
+            const int c = r < c0 ? 0 : (r < c1 ? 1 : 2);
+            const long rr = r - (c == 0 ? 0 : (c == 1 ? c0 : c1));
+            ld = d->bw[c] * 8;
+            const int by = (int)(rr / d->bw[c]), bx = (int)(rr % d->bw[c]);
+            // the plane mirrors the coefficient storage: 64 bytes per block, component after component
+            dst = planes + 64 * (d->coef_block + (r - rr)) + ((long)by * 8 + j) * ld + bx * 8;
+            const int4 cv = *reinterpret_cast<const int4*>(coeffs + 64 * g + 8 * j);
+            const int4 qv = *reinterpret_cast<const int4*>(d->qt[c] + 8 * j);
+            const int cw[4] = {cv.x, cv.y, cv.z, cv.w}, qw[4] = {qv.x, qv.y, qv.z, qv.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                w[j * WS_LD + 2 * k] = (int)(int16_t)(cw[k] & 0xffff) * (qw[k] & 0xffff);
+                w[j * WS_LD + 2 * k + 1] = (cw[k] >> 16) * (int)((uint32_t)qw[k] >> 16);
+                wild = wild || abs(w[j * WS_LD + 2 * k]) > IDCT_PAIR_MAX || abs(w[j * WS_LD + 2 * k + 1]) > IDCT_PAIR_MAX;
+            }
+        }
+    }
+    __syncthreads();
+    int v[8];
+    if (live) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) v[r] = w[r * WS_LD + j];
+        idct_1d<CONST_BITS - PASS1_BITS>(v);
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            w[r * WS_LD + j] = v[r];
+            wild = wild || abs(v[r]) > IDCT_PAIR_MAX;
+        }
+    }
+    __syncthreads();
+    if (live) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = w[j * WS_LD + k];
+        idct_1d<CONST_BITS + PASS1_BITS + 3>(v);
+        // range limit around +128 (the guard above keeps to where libjpeg's wrapping table and its saturating packs agree)
+        uint32_t lo = 0, hi = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) wild = wild || v[k] < -512 || v[k] > 511;
+        if (wild) flags[i] = 1;  // every lane that sees it stores the same 1
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            lo |= (uint32_t)min(max(v[k] + 128, 0), 255) << (8 * k);
+            hi |= (uint32_t)min(max(v[k + 4] + 128, 0), 255) << (8 * k);
+        }
+        *reinterpret_cast<uint2*>(dst) = make_uint2(lo, hi);
+    }
+}
+
+// what kernel B needs of one image
+struct Planes {
+    const uint8_t* y;
+    const uint8_t* cb;
+    const uint8_t* cr;
+    int ldy, ldc, w, h, dw, dh, hs, vs, ncomp;
+};
+
+__device__ __forceinline__ bool planes_of(const Desc* __restrict__ d, const uint8_t* __restrict__ planes, int flag, Planes& p) {
+    if (d->status != AVCER_JPEG_OK || flag) return false;
+    p.w = d->width;
+    p.h = d->height;
+    p.ncomp = d->ncomp;
+    p.hs = p.ncomp == 3 ? d->hs : 1;
+    p.vs = p.ncomp == 3 ? d->vs : 1;
+    p.dw = (p.w + p.hs - 1) / p.hs;  // libjpeg's downsampled_width / _height of the chroma components
+    p.dh = (p.h + p.vs - 1) / p.vs;
+    p.ldy = d->bw[0] * 8;
+    p.ldc = d->bw[1] * 8;
+    p.y = planes + 64 * d->coef_block;
+    p.cb = p.y + 64L * d->bw[0] * d->bh[0];
+    p.cr = p.cb + 64L * d->bw[1] * d->bh[1];
+    return true;
+}
+
+// One chroma sample at full-resolution position (x, y): libjpeg-turbo's jdsample.c evaluated at that pixel.  h2v1 fancy: the 3:1
+// triangle, rounding +1 towards the left neighbour and +2 towards the right; h2v2 fancy: 3:1 between the nearer and the farther
+// row, then 3:1 between the column sums, +8 / +7, >> 4.  Edge rows and columns replicate (which reproduces libjpeg's special
+// first / last columns exactly).  A component of at most two columns is replicated, not filtered (jinit_upsampler's
+// `downsampled_width > 2`), in both directions.
+__device__ __forceinline__ int chroma_at(const uint8_t* __restrict__ p, int ld, const Planes& g, int x, int y) {
+    if (g.hs == 1) return p[(long)y * ld + x];
+    const int s = x >> 1;
+    if (g.dw <= 2) return p[(long)(g.vs == 2 ? y >> 1 : y) * ld + s];
+    const int sn = (x & 1) ? min(s + 1, g.dw - 1) : max(s - 1, 0);
+    if (g.vs == 1) {
+        const uint8_t* r = p + (long)y * ld;
+        return (3 * r[s] + r[sn] + ((x & 1) ? 2 : 1)) >> 2;
+    }
+    const int t = y >> 1, tn = (y & 1) ? min(t + 1, g.dh - 1) : max(t - 1, 0);
+    const uint8_t* r0 = p + (long)t * ld;
+    const uint8_t* r1 = p + (long)tn * ld;
+    const int cs = 3 * r0[s] + r1[s], cn = 3 * r0[sn] + r1[sn];
+    return (3 * cs + cn + ((x & 1) ? 7 : 8)) >> 4;
+}
+
+__device__ __forceinline__ int clamp255(int v) { return min(max(v, 0), 255); }
+
+// RGB of source pixel (x, y) as r | g << 8 | b << 16: libjpeg's jdcolor.c, 16-bit fixed point, one half added before the shift,
+// the Cb and Cr terms of green combined before it; grey is replicated (PIL's convert("RGB") of mode L)
+__device__ __forceinline__ uint32_t rgb_at(const Planes& g, int x, int y) {
+    const int Y = g.y[(long)y * g.ldy + x];
+    if (g.ncomp == 1) return (uint32_t)Y * 0x010101u;
+    const int cb = chroma_at(g.cb, g.ldc, g, x, y) - 128, cr = chroma_at(g.cr, g.ldc, g, x, y) - 128;
+    const int r = clamp255(Y + ((91881 * cr + 32768) >> 16));
+    const int gg = clamp255(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
+    const int bl = clamp255(Y + ((116130 * cb + 32768) >> 16));
+    return (uint32_t)r | ((uint32_t)gg << 8) | ((uint32_t)bl << 16);
+}
+
+// Kernel B, tiles: tile pixel (y, x) = the decoded image at nearest_src (the rule of avcer_crop_tiles); one thread per 4 tile
+// pixels, three 4-byte stores.  An image that was not decoded yields a zero tile.
+__global__ void jpeg_tiles_kernel(const uint8_t* __restrict__ planes, const Desc* __restrict__ desc, const int32_t* __restrict__ flags,
+                                  int n, uint8_t* __restrict__ tiles) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)n * 224 * 56) return;
+    const int xq = idx % 56;
+    const int y = (idx / 56) % 224;
+    const int t = idx / (56L * 224);
+    uint32_t px[4] = {0, 0, 0, 0};
+    Planes g;
+    if (planes_of(desc + t, planes, flags[t], g)) {
+        const int sy = nearest_src(y, g.h);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) px[j] = rgb_at(g, nearest_src(xq * 4 + j, g.w), sy);
+    }
+    uint32_t* o = reinterpret_cast<uint32_t*>(tiles + ((long)t * 224 + y) * 224 * 3 + xq * 12);
+    o[0] = px[0] | (px[1] << 24);
+    o[1] = (px[1] >> 8) | (px[2] << 16);
+    o[2] = (px[2] >> 16) | (px[3] << 8);
+}
+
+// Kernel B, canvas: the image itself at (0, 0) of its [hmax, wmax] slot, zeros around it; one thread per pixel
+__global__ void jpeg_canvas_kernel(const uint8_t* __restrict__ planes, const Desc* __restrict__ desc, const int32_t* __restrict__ flags,
+                                   int n, int hmax, int wmax, uint8_t* __restrict__ canvas) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)n * hmax * wmax) return;
+    const int x = idx % wmax;
+    const int y = (idx / wmax) % hmax;
+    const int t = idx / ((long)wmax * hmax);
+    uint32_t px = 0;
+    Planes g;
+    if (planes_of(desc + t, planes, flags[t], g) && x < g.w && y < g.h) px = rgb_at(g, x, y);
+    uint8_t* o = canvas + idx * 3;
+    o[0] = (uint8_t)px;
+    o[1] = (uint8_t)(px >> 8);
+    o[2] = (uint8_t)(px >> 16);
+}
+
+// Kernel A into the context's JPEG workspace: the component planes, sized by their own carving (one byte per coefficient)
+int jpeg_planes(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_blocks, const Desc* desc, int n, int32_t* flags, uint8_t** planes,
+                hipStream_t st) {
+    uint8_t* p = nullptr;
+    const auto carve = [&](Arena& a) { p = a.get<uint8_t>(64 * (size_t)n_blocks); };
+    const size_t bytes = Arena().run(carve);
+    void* base = nullptr;
+    TRY(ws_reserve(ctx, WS_JPEG, bytes, &base));
+    if (Arena(base, bytes).run(carve) != bytes || !p) return set_err(ctx, AVCER_ENOMEM, "jpeg workspace arithmetic");
+    HIP_TRY(ctx, hipMemsetAsync(flags, 0, sizeof(int32_t) * (size_t)n, st));
+    const long per = IDCT_THREADS / 64 * 8;
+    jpeg_idct_kernel<<<(unsigned)((n_blocks + per - 1) / per), IDCT_THREADS, 0, st>>>(coeffs, desc, n, (long)n_blocks, p, flags);
+    HIP_TRY(ctx, hipGetLastError());
+    *planes = p;
+    return AVCER_OK;
+}
+
+int jpeg_args(avcer_ctx* ctx, const char* what, const void* coeffs, int64_t n_blocks, const void* desc, int n, const void* flags,
+              const void* out) {
+    if (!ctx) return AVCER_EINVAL;
+    if (!coeffs || !desc || !out || !flags || n <= 0 || n_blocks <= 0 || n_blocks >= (1LL << 34) || ((uintptr_t)coeffs & 15) || ((uintptr_t)desc & 15))
+        return set_err(ctx, AVCER_EINVAL, "%s: bad arguments (n %d, %lld blocks; coefficients and descriptors 16-byte aligned)", what, n,
+                       (long long)n_blocks);
+    return AVCER_OK;
+}
+
+}  // namespace
+
+extern "C" int avcer_jpeg_probe(const uint8_t* bytes, size_t len, avcer_jpeg_desc* info) {
+    if (!info) return AVCER_EINVAL;
+    try {
+        Header* h = new Header();
+        const int r = parse_header(bytes, len, *h);
+        *info = h->d;
+        info->reason = r;
+        info->status = r == R_OK ? AVCER_JPEG_OK : AVCER_JPEG_NOT_HANDLED;
+        delete h;
+    } catch (...) {
+        return AVCER_ENOMEM;
+    }
+    return AVCER_OK;
+}
+
+extern "C" int avcer_jpeg_entropy_batch(avcer_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, int16_t* coeffs,
+                                        int64_t cap_blocks, avcer_jpeg_desc* desc, int threads, int64_t* blocks_needed) {
+    // ctx may be NULL (host-only call, no device needed): errors then come back as the code alone
+    if (n < 0 || (n && (!files || !lens || !desc)) || cap_blocks < 0 || (cap_blocks && !coeffs))
+        return set_err(ctx, AVCER_EINVAL, "jpeg_entropy_batch: bad arguments");
+    try {
+        const int nt = std::min(pool_size(threads), n);
+        // fn(i, h) for every file, files handed out one at a time to nt threads (this one included); h is the thread's one Header
+        // (13 KB of Huffman look-up tables), so the tables in memory are nt sets and not n
+        const auto each_file = [&](const auto& fn) {
+            std::atomic<int> next(0);
+            std::atomic<bool> failed(false);
+            const auto work = [&]() {
+                try {
+                    std::unique_ptr<Header> h(new Header());
+                    for (int i; (i = next.fetch_add(1)) < n;) fn(i, *h);
+                } catch (...) {
+                    failed = true;  // nothing may leave a thread; the files it did not take are taken by the others
+                }
+            };
+            std::vector<std::thread> pool;
+            for (int t = 1; t < nt; ++t) {
+                try {
+                    pool.emplace_back(work);
+                } catch (...) {
+                    break;  // no more threads to be had: the ones running and this one do the work
+                }
+            }
+            work();
+            for (auto& t : pool) t.join();
+            if (failed) throw std::bad_alloc();
+        };
+        // headers first; then, in file order, every supported file gets the next free blocks of the storage, so offsets ascend
+        // (kernel A finds a block's image by them); a file that does not fit is not handled and takes nothing
+        each_file([&](int i, Header& h) {
+            const int r = parse_header(files[i], lens[i] < 0 ? 0 : (size_t)lens[i], h);  // no bytes: R_NO_SOI
+            desc[i] = h.d;
+            desc[i].reason = r;
+        });
+        int64_t used = 0, needed = 0;
+        for (int i = 0; i < n; ++i) {
+            Desc& d = desc[i];
+            int r = d.reason;
+            if (r == R_OK) {
+                needed += d.n_blocks;
+                if (d.n_blocks > cap_blocks - used) r = R_NO_SPACE;
+            }
+            d.coef_block = used;
+            if (r == R_OK) used += d.n_blocks; else d.n_blocks = 0;
+            d.reason = r;
+            d.status = r == R_OK ? AVCER_JPEG_OK : AVCER_JPEG_NOT_HANDLED;
+        }
+        if (blocks_needed) *blocks_needed = needed;
+        // the scans: independent.  The header is parsed again (some hundred bytes) rather than kept for every file of the batch
+        each_file([&](int i, Header& h) {
+            if (desc[i].status != AVCER_JPEG_OK) return;
+            int r = parse_header(files[i], (size_t)lens[i], h);
+            if (r == R_OK) r = decode_scan(files[i], (size_t)lens[i], h, coeffs + 64 * desc[i].coef_block);
+            if (r != R_OK) {
+                desc[i].reason = r;
+                desc[i].status = AVCER_JPEG_NOT_HANDLED;
+            }
+        });
+    } catch (...) {
+        return set_err(ctx, AVCER_ENOMEM, "jpeg_entropy_batch: out of host memory");
+    }
+    return AVCER_OK;
+}
+
+extern "C" int avcer_jpeg_tiles(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_blocks, const avcer_jpeg_desc* desc, int n,
+                                int32_t* flags, uint8_t* tiles, avcer_stream_t stream) {
+    TRY(jpeg_args(ctx, "jpeg_tiles", coeffs, n_blocks, desc, n, flags, tiles));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* planes = nullptr;
+    TRY(jpeg_planes(ctx, coeffs, n_blocks, desc, n, flags, &planes, st));
+    const long total = (long)n * 224 * 56;
+    jpeg_tiles_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(planes, desc, flags, n, tiles);
+    HIP_TRY(ctx, hipGetLastError());
+    return AVCER_OK;
+}
+
+extern "C" int avcer_jpeg_rgb(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_blocks, const avcer_jpeg_desc* desc, int n,
+                              int32_t* flags, uint8_t* canvas, int hmax, int wmax, avcer_stream_t stream) {
+    TRY(jpeg_args(ctx, "jpeg_rgb", coeffs, n_blocks, desc, n, flags, canvas));
+    if (hmax <= 0 || wmax <= 0 || (long)n * hmax * wmax >= (1L << 38))
+        return set_err(ctx, AVCER_EINVAL, "jpeg_rgb: canvas %d x %d x %d", n, hmax, wmax);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* planes = nullptr;
+    TRY(jpeg_planes(ctx, coeffs, n_blocks, desc, n, flags, &planes, st));
+    const long total = (long)n * hmax * wmax;
+    jpeg_canvas_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(planes, desc, flags, n, hmax, wmax, canvas);
+    HIP_TRY(ctx, hipGetLastError());
+    return AVCER_OK;
+}

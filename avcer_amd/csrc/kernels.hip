@@ -513,12 +513,12 @@ __global__ void crop_tiles_kernel(const uint8_t* __restrict__ frames, int T, int
     uint8_t px[12];
     const bool ok = f >= 0 && f < T && x0 >= 0 && y0 >= 0 && cw > 0 && ch > 0 && x0 + cw <= W && y0 + ch <= H;
     if (ok) {
-        const int sy = y0 + min((int)(((double)y + 0.5) * ((double)ch / 224.0)), ch - 1);
+        const int sy = y0 + nearest_src(y, ch);
         const uint8_t* row = frames + ((long)f * H + sy) * W * 3;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int x = xq * 4 + j;
-            const int sx = x0 + min((int)(((double)x + 0.5) * ((double)cw / 224.0)), cw - 1);
+            const int sx = x0 + nearest_src(x, cw);
             const uint8_t* s = row + 3L * sx;
             px[3 * j + 0] = swap_rb ? s[2] : s[0];
             px[3 * j + 1] = s[1];

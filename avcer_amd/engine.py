@@ -12,6 +12,7 @@ import torch
 
 from . import _lib, packing
 from ._lib import SPLIT_TRAILER, AvcerError, ConvDesc
+from .jpeg import DESC as _JPEG_DESC
 
 MODE_FP32 = 0    # exact f32 FMA chains on the f32 MFMA: the reference's own arithmetic, a third of the speed
 MODE_BF16 = 1    # plain bf16 operands: throughput only, misses the 1e-4 parity gate
@@ -21,6 +22,7 @@ MODE_F16X3 = 2   # fp16 hi/lo operand pairs, 3 MFMAs per product: f32-grade resu
 # is the default, MODE_FP32 stays for checkpoints whose activations leave fp16's range (|x| >= 65504 -> NaN outputs).
 MODE_DEFAULT = MODE_F16X3
 PAD_MODES = {"mean": 0, "constant": 1, "repeat": 2}
+_JPEG_DESC_BYTES = _JPEG_DESC.itemsize  # sizeof(struct avcer_jpeg_desc): jpeg.DESC is its one statement on this side
 
 
 def _ptr(t):
@@ -447,6 +449,33 @@ class Engine:
         self._check(self.lib.avcer_crop_tiles(self.ctx, _ptr(x), int(x.shape[0]), int(x.shape[1]), int(x.shape[2]),
                                               _ptr(r), n, 1 if bgr else 0, _ptr(tiles), self._stream()))
         return tiles
+
+    def jpeg_tiles(self, coeffs, desc, n: int, n_blocks: int, out=None):
+        """Coefficients int16 [>= 64 * n_blocks] and descriptors (n records of struct avcer_jpeg_desc as bytes), both on the device
+        as avcer_jpeg_entropy_batch wrote them (avcer_amd/jpeg.py) -> (RGB tiles u8 [n,224,224,3], flags i32 [n] on the device); a tile is zero for a file not decoded: status not OK, or flag 1
+        (the inverse DCT left the range inside which the decode is defined, include/avcer_hip.h)."""
+        if coeffs.dtype != torch.int16 or coeffs.numel() < 64 * n_blocks or desc.dtype != torch.uint8 or desc.numel() < _JPEG_DESC_BYTES * n or \
+                not coeffs.is_cuda or not desc.is_cuda:
+            raise ValueError("jpeg_tiles: coeffs int16 [64 * n_blocks], desc uint8 [sizeof(avcer_jpeg_desc) * n], both on the device")
+        tiles = self._new(n, 224, 224, 3, dtype=torch.uint8) if out is None else out
+        if tuple(tiles.shape) != (n, 224, 224, 3) or tiles.dtype != torch.uint8 or not tiles.is_contiguous():
+            raise ValueError("jpeg_tiles: out must be a contiguous uint8 [n,224,224,3]")
+        flags = self._new(n, dtype=torch.int32)
+        self._check(self.lib.avcer_jpeg_tiles(self.ctx, _ptr(coeffs), int(n_blocks), _ptr(desc), int(n), _ptr(flags), _ptr(tiles),
+                                              self._stream()))
+        return tiles, flags
+
+    def jpeg_rgb(self, coeffs, desc, n: int, n_blocks: int, hmax: int, wmax: int):
+        """The same files at full size -> (canvas u8 [n,hmax,wmax,3] RGB: image i in the top left corner of slot i, zeros around it;
+        flags i32 [n] as jpeg_tiles returns them)."""
+        if coeffs.dtype != torch.int16 or coeffs.numel() < 64 * n_blocks or desc.dtype != torch.uint8 or desc.numel() < _JPEG_DESC_BYTES * n or \
+                not coeffs.is_cuda or not desc.is_cuda:
+            raise ValueError("jpeg_rgb: coeffs int16 [64 * n_blocks], desc uint8 [sizeof(avcer_jpeg_desc) * n], both on the device")
+        canvas = self._new(n, int(hmax), int(wmax), 3, dtype=torch.uint8)
+        flags = self._new(n, dtype=torch.int32)
+        self._check(self.lib.avcer_jpeg_rgb(self.ctx, _ptr(coeffs), int(n_blocks), _ptr(desc), int(n), _ptr(flags), _ptr(canvas), int(hmax),
+                                            int(wmax), self._stream()))
+        return canvas, flags
 
     def crop_resize_linear(self, frames_u8, rects, swap_rb: bool = False, out_h: int = 224, out_w: int = 224):
         """frames u8 [T,H,W,3] + rects i32 [n,5] (frame, x0, y0, x1, y1) -> u8 [n,out_h,out_w,3]: cv2.resize of each crop with

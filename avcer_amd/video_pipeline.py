@@ -170,9 +170,43 @@ def read_face_crops(path_images: str, frame_idx, track: str = "00"):
     return canvas, rects
 
 
+def _read_blob(path: str) -> bytes:
+    with open(path, "rb") as f:
+        return f.read()
+
+
+def read_face_dir_device(engine: Engine, path_images: str, total_frames: int, track: str = "00", threads: int = 0):
+    """`read_face_dir` with the decode on the device (avcer_amd/jpeg.py): the same files, the same meaning, the same
+    FileNotFoundError for a missing track directory -> (frames u8 [total_frames,224,224,3] RGB ON THE DEVICE, bit-identical to
+    read_face_dir's, present bool [total_frames]).  A file the native parser does not handle is decoded by PIL as there.
+    `threads`: host threads of the entropy pass, at most 16 (0: OMP_NUM_THREADS, or 16)."""
+    from . import jpeg
+
+    folder = os.path.join(path_images, track)
+    names = set(os.listdir(folder))
+    idx = [i for i in range(total_frames) if str(i).zfill(6) + ".jpg" in names]
+    present = np.zeros(total_frames, dtype=bool)
+    present[idx] = True
+    tiles, _ = jpeg.decode_tiles(engine, [_read_blob(os.path.join(folder, str(i).zfill(6) + ".jpg")) for i in idx], threads)
+    if len(idx) == total_frames:
+        return tiles, present
+    frames = torch.zeros(total_frames, 224, 224, 3, dtype=torch.uint8, device=engine.device)
+    if idx:
+        frames[torch.as_tensor(idx, device=engine.device)] = tiles
+    return frames, present
+
+
+def read_face_crops_device(engine: Engine, path_images: str, frame_idx, track: str = "00"):
+    """`read_face_crops` with the decode on the device: (canvas u8 [max(m,1), max h, max w, 3] on the device, rects i32 [m,5])."""
+    from . import jpeg
+
+    blobs = [_read_blob(os.path.join(path_images, track, str(int(i)).zfill(6) + ".jpg")) for i in np.asarray(frame_idx).reshape(-1)]
+    return jpeg.decode_canvas(engine, blobs)[0]
+
+
 def preprocess_video_and_predict(engine: Engine, path_images: str = "", save_path: str = "", fps: float = 30, total_frames: int = 0,
                                  flag_save_prob: bool = False, mode: int = MODE_DEFAULT, flag_heatmaps: bool = False,
-                                 model_heatmaps: str = "static"):
+                                 model_heatmaps: str = "static", decode: str = "device"):
     """`get_prob_video.preprocess_video_and_predict` (get_prob_video.py:67-204) with the reference's argument meaning, on the HIP
     path: the face-crop directory of one video in, the two per-frame tables out -- (dynamic logits, static probabilities), float32
     [total_frames, 7] in DICT_EMO_VIDEO column order -- and `dynamic__<video>.csv` / `static__<video>.csv` under `save_path` when
@@ -180,22 +214,41 @@ def preprocess_video_and_predict(engine: Engine, path_images: str = "", save_pat
     `flag_heatmaps`: one Grad-CAM overlay per frame that starts an LSTM evaluation, written as
     `<save_path>/<video>/heatmaps_<model_heatmaps>/NNNNNN.jpg` (avcer_amd/heatmaps.py); the tables are the same as without it.
     The visual call then runs through `engine.guarded`, maps included.  `model_heatmaps` other than "static" / "dynamic" raises
-    ValueError before any work (the reference dies with UnboundLocalError at its first heat-map frame)."""
+    ValueError before any work (the reference dies with UnboundLocalError at its first heat-map frame).
+    `decode`: "device" reads the crops through read_face_dir_device / read_face_crops_device (host entropy pass, HIP pixel pass),
+    "pil" through read_face_dir / read_face_crops; the tiles are bit-identical, so tables, CSV files and heat maps are the same."""
     from . import io_formats
+
+    if decode not in ("device", "pil"):
+        raise ValueError(f"decode must be 'device' or 'pil', got {decode!r}")
+    if decode == "device":
+        def read_dir(p, t):
+            return read_face_dir_device(engine, p, t)
+
+        def read_crops(p, idx):
+            return read_face_crops_device(engine, p, idx)
+    else:
+        def read_dir(p, t):
+            frames, present = read_face_dir(p, t)
+            return torch.from_numpy(frames), present
+
+        def read_crops(p, idx):
+            canvas, rects = read_face_crops(p, idx)
+            return torch.from_numpy(canvas), rects
 
     if flag_heatmaps:
         from . import heatmaps as hm
 
         hm.check_model(model_heatmaps)
-        frames, present = read_face_dir(path_images, total_frames)
+        frames, present = read_dir(path_images, total_frames)
         frame_idx = hm.heatmap_plan(present, fps)[0]
-        canvas, rects = read_face_crops(path_images, frame_idx)
+        canvas, rects = read_crops(path_images, frame_idx)
 
         def call(m):
-            stat, dyn, cam, fidx, rows, cls = hm.visual_forward_cam(engine, torch.from_numpy(frames), present, fps, m, model_heatmaps)
+            stat, dyn, cam, fidx, rows, cls = hm.visual_forward_cam(engine, frames, present, fps, m, model_heatmaps)
             imgs = None
             if len(rows):
-                base = engine.crop_resize_linear(torch.from_numpy(canvas), rects, swap_rb=False)
+                base = engine.crop_resize_linear(canvas, rects, swap_rb=False)
                 imgs = engine.cam_render(cam, rows, cls, base, hm.JET_BGR, hm.IMAGE_WEIGHT)
             return stat, dyn, imgs
 
@@ -206,8 +259,8 @@ def preprocess_video_and_predict(engine: Engine, path_images: str = "", save_pat
             io_formats.write_visual_csvs(stat, dyn, save_path, os.path.basename(path_images))
         return dyn.cpu().numpy(), stat.cpu().numpy()
 
-    frames, present = read_face_dir(path_images, total_frames)
-    stat, dyn = visual_forward(engine, torch.from_numpy(frames), present, fps, mode)
+    frames, present = read_dir(path_images, total_frames)
+    stat, dyn = visual_forward(engine, frames, present, fps, mode)
     if flag_save_prob:
         io_formats.write_visual_csvs(stat, dyn, save_path, os.path.basename(path_images))
     return dyn.cpu().numpy(), stat.cpu().numpy()

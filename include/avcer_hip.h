@@ -77,7 +77,9 @@ enum {
  *      avcer_face_kind and avcer_dwsep (the MobileNet-0.25 RetinaFace detector: avcer_load_face / avcer_face_forward take either
  *      variant's blob) joined under 8 the same way: two more symbols, no struct layout or argument list changed.
  *      avcer_s3fd_num_priors, avcer_s3fd_detect and the kernel-level entries avcer_s3fd_stem, avcer_maxpool2, avcer_s3fd_head (the
- *      S3FD detector: avcer_load_face / avcer_face_forward take its blob as kind 3) joined under 8 the same way. */
+ *      S3FD detector: avcer_load_face / avcer_face_forward take its blob as kind 3) joined under 8 the same way.
+ *      avcer_jpeg_probe, avcer_jpeg_entropy_batch, avcer_jpeg_tiles, avcer_jpeg_rgb and their descriptor struct (JPEG crop files
+ *      decoded behind a host entropy pass) joined under 8 the same way. */
 #define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
@@ -367,6 +369,64 @@ int avcer_cam_render(avcer_ctx* ctx, const float* cam, const int32_t* rows, cons
 int avcer_track_faces(avcer_ctx* ctx, const float* dets_host, int ld, const int32_t* counts_host, int n_frames, int frame_w,
                       int frame_h, double iou_threshold, double minimum_face_size, int64_t* records_host, int64_t* n_records);
 int avcer_lsap(int nr, int nc, const double* cost_host, int32_t* rows_host, int32_t* cols_host);
+
+/* JPEG face crops: the files stage 0 writes and stage 1 reads back,
+ *   ref: data/get_face_images.py:52-63 (cv2.imwrite of `<faces>/<track>/NNNNNN.jpg`), get_prob_video.py:79-100 (the read loop),
+ *        data/utils.py:34 (PIL NEAREST resize to 224 x 224)
+ * decoded without a decoder library, split where the work changes kind: marker parsing and Huffman decoding on the HOST
+ * (avcer_jpeg_probe, avcer_jpeg_entropy_batch: host code and host pointers, ctx may be NULL, no device is touched), everything
+ * behind the coefficients on the DEVICE (avcer_jpeg_tiles, avcer_jpeg_rgb).  The arithmetic is libjpeg's with its defaults --
+ * the "islow" integer inverse DCT, fancy chroma upsampling, 16-bit fixed-point YCbCr -> RGB -- and the contract is bit-identity
+ * with PIL's decode of the same file (libjpeg-turbo): a tolerance of zero, independent of the arithmetic mode.
+ *
+ * Handled (status AVCER_JPEG_OK): SOF0 and 8-bit SOF1, Huffman coded, ONE scan of all components; one component (grey) or three
+ * read as YCbCr (a JFIF segment; else an Adobe segment with transform 1; else the component ids 1, 2, 3); luma sampling 1x1, 2x1
+ * or 2x2 with chroma 1x1; 8-bit quantisation tables; DRI / RSTn, 0xFF00 stuffing, fill bytes; any APPn / COM segments; any
+ * Huffman tables.  EVERYTHING else is AVCER_JPEG_NOT_HANDLED and never guessed at: no SOI at offset 0, progressive / arithmetic /
+ * lossless / 12-bit files, four components, Adobe transform 0 or 2, other sampling factors, several scans, DNL, 16-bit tables,
+ * bytes between segments, a bit stream that ends early, an undefined Huffman code, a coefficient index past 63, a wrong or
+ * missing RSTn, a missing EOI, a dequantised coefficient outside int16, and a file whose blocks do not fit the storage given.
+ * `reason` says which (csrc/jpeg.hip R_*; 12 = no space).  The caller decodes such a file some other way (avcer_amd/jpeg.py: PIL).
+ *
+ * avcer_jpeg_desc: one file.  bw / bh: blocks per component, padded to whole MCUs (a one-component file: ceil(w / 8), ceil(h /
+ * 8)); qt: each component's quantisation table in natural order; hs / vs: the first component's sampling factors as the file
+ * states them; coef_block / n_blocks: where the file's coefficient blocks lie in the storage, in blocks of 64 int16 -- component
+ * after component, raster order over the padded grid, each block in natural (de-zigzagged) order, not dequantised.
+ *
+ * avcer_jpeg_probe: the header of one file (up to its scan) -> *info; coef_block 0.
+ * avcer_jpeg_entropy_batch: n files (files[i], lens[i]) -> desc[n] and the coefficients of every handled file in coeffs (room
+ *   for cap_blocks blocks); files take consecutive blocks in file order, so coef_block ascends; *blocks_needed (may be NULL) =
+ *   what all files with a supported header need together.  Files are decoded independently on min(16, threads) host threads,
+ *   threads <= 0: 16 -- never the machine's core count; the library reads no environment, avcer_amd/jpeg.py passes
+ *   min(16, OMP_NUM_THREADS or 16).  The result does not depend on the thread count.
+ * avcer_jpeg_tiles: coeffs (n_blocks blocks) and desc[n] as the call above wrote them, copied to the device (both 16-byte
+ *   aligned) -> tiles u8 [n,224,224,3] RGB = Image.open(file).convert("RGB").resize((224, 224), NEAREST), avcer_crop_tiles' rule;
+ *   a file that is not AVCER_JPEG_OK yields a zero tile.  Only the source pixels a tile samples are colour-converted.
+ * avcer_jpeg_rgb: the same files at full size -> canvas u8 [n,hmax,wmax,3] RGB, image i in the top left corner of slot i, zeros
+ *   around it (and everywhere for a file that is not OK): the canvas of avcer_crop_resize_linear with rects (i, 0, 0, w, h).
+ * flags i32 [n] (device, written by both calls): 1 where the inverse DCT of file i left the range inside which libjpeg's C and
+ *   SIMD code agree (dequantised coefficients and pass-1 results within +-16383, samples within [-512, 511]: a corrupt stream or
+ *   table, never a picture an encoder wrote); such a file's output is zero and the caller decodes it some other way, as for a
+ *   file that is not OK.  Reading the flags is the caller's only reason to wait for the stream.
+ * Both device calls run two kernels on `stream` (dequantisation + inverse DCT into u8 component planes in the context's
+ * workspace, 64 bytes per block; then the pixels) and do not synchronise with the host. */
+enum { AVCER_JPEG_OK = 0, AVCER_JPEG_NOT_HANDLED = 1 };
+typedef struct avcer_jpeg_desc {
+    int32_t status, reason;
+    int32_t width, height, ncomp;
+    int32_t hs, vs;
+    int32_t bw[3], bh[3];
+    int32_t tq[3];          /* quantisation table id of each component */
+    int64_t coef_block, n_blocks;
+    uint16_t qt[3][64];
+} avcer_jpeg_desc;         /* 464 bytes */
+int avcer_jpeg_probe(const uint8_t* bytes_host, size_t len, avcer_jpeg_desc* info_host);
+int avcer_jpeg_entropy_batch(avcer_ctx* ctx, const uint8_t* const* files_host, const int64_t* lens_host, int n, int16_t* coeffs_host,
+                             int64_t cap_blocks, avcer_jpeg_desc* desc_host, int threads, int64_t* blocks_needed);
+int avcer_jpeg_tiles(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_blocks, const avcer_jpeg_desc* desc, int n, int32_t* flags,
+                     uint8_t* tiles, avcer_stream_t stream);
+int avcer_jpeg_rgb(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_blocks, const avcer_jpeg_desc* desc, int n, int32_t* flags,
+                   uint8_t* canvas, int hmax, int wmax, avcer_stream_t stream);
 
 /* Probability fusion and compound-expression rule.
  *   ref: run.py:25-165 (get_c_expr_db_pred), data/utils.py:125-127 (softmax), :222-241 (get_compound_expression)
