@@ -10,8 +10,6 @@
 
 namespace {
 
-inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
-
 // One axis of cv2's INTER_LINEAR table (resize.cpp, resizeGeneric_ set-up): the source position of destination index d at
 // scale s = src / dst with half-pixel centres, clamped at both borders (weight 0 on the outer tap).
 struct LinTap {

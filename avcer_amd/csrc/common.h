@@ -105,6 +105,16 @@ int set_err(avcer_ctx* ctx, int code, const char* fmt, ...);
         if (_r != AVCER_OK) return _r; \
     } while (0)
 
+// right behind a kernel launch: a launch that failed returns "<name> launch: <HIP's message>" from the launcher
+#define CHECK_LAUNCH(ctx, name)                                                                      \
+    do {                                                                                             \
+        hipError_t _e = hipGetLastError();                                                           \
+        if (_e != hipSuccess) return set_err((ctx), AVCER_EHIP, name " launch: %s", hipGetErrorString(_e)); \
+    } while (0)
+
+// blocks of `b` items that cover `a` items, as a grid dimension: the quotient must fit an int (a < 2^31 * b), which no launcher checks
+inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
 int ws_reserve(avcer_ctx* ctx, int slot, size_t bytes, void** out);
 
 // PIL's NEAREST resize to 224 (data/utils.py:34): the source index of output index `o` along an axis of `len` source pixels.

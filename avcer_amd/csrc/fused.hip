@@ -49,31 +49,6 @@ __device__ __forceinline__ spx8_t ldfrag(const char* tile, int row, int chunk) {
     return *reinterpret_cast<const spx8_t*>(tile + swz(row, chunk));
 }
 
-// 8 f32 values -> fp16 hi / lo fragments (value = hi + lo + O(2^-22))
-__device__ __forceinline__ void split8v(const float (&v)[8], spx8_t& hi, spx8_t& lo, sp_flags_t& ovm) {
-    float a = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; j += 2) {
-        const float x0 = sp_value(v[j]), x1 = sp_value(v[j + 1]);  // one f32 number for both halves (split_dev.h)
-        a = sp_max2(a, x0, x1);
-        const spe_t h0 = (spe_t)x0, h1 = (spe_t)x1;
-        hi[j] = h0;
-        hi[j + 1] = h1;
-        lo[j] = (spe_t)(x0 - (float)h0);
-        lo[j + 1] = (spe_t)(x1 - (float)h1);
-    }
-    sp_flag(ovm, a);  // range contract: |x| < 65504 (split_dev.h sp_commit)
-}
-
-__device__ __forceinline__ void unpack8(const uint4 h, const uint4 l, float (&r)[8]) {
-    const uint32_t wh[4] = {h.x, h.y, h.z, h.w}, wl[4] = {l.x, l.y, l.z, l.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        r[2 * j] = sp2f((uint16_t)(wh[j] & 0xffff)) + sp2f((uint16_t)(wl[j] & 0xffff));
-        r[2 * j + 1] = sp2f((uint16_t)(wh[j] >> 16)) + sp2f((uint16_t)(wl[j] >> 16));
-    }
-}
-
 // 8 consecutive floats from LDS by inline asm.  A ds_read that hipcc can see makes it drain every LDS-DMA in flight first
 // (s_waitcnt vmcnt(0): it cannot prove that the read does not alias the DMA destination), which would undo the counted
 // wait of bneck_tail2_kernel; the table read here was written long before (barriers in between).
@@ -242,7 +217,7 @@ __global__ void __launch_bounds__(256, 2) stem_pool_kernel(const StemParams p) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) if (anynan[j]) m[j] = NAN;  // like torch's max-pool
         spx8_t hi, lo;
-        split8v(m, hi, lo, ovm);
+        sp_split8(m, hi, lo, ovm);
         const long e = (((long)b * 55 + py) * 55 + px) * 64 + c8 * 8;
         char* yp = p.Y + sp32_byte(e);
         *reinterpret_cast<spx8_t*>(yp) = hi;
@@ -452,7 +427,7 @@ __global__ void __launch_bounds__(256, 3) stem_pool_u8_kernel(const StemParams p
 #pragma unroll
                 for (int j = 0; j < 8; ++j) if (anynan[j]) m[j] = NAN;  // like torch's max-pool
                 spx8_t hi, lo;
-                split8v(m, hi, lo, ovm);
+                sp_split8(m, hi, lo, ovm);
                 const long e = (((long)b * (FACE ? p.mh : 55) + py) * (FACE ? p.mw : 55) + px) * 64 + 32 * half + c8 * 8;
                 char* yp = p.Y + sp32_byte(e);
                 *reinterpret_cast<spx8_t*>(yp) = hi;
@@ -674,17 +649,15 @@ __global__ void __launch_bounds__(256, P == 64 ? 3 : 2) bneck_kernel(const Bneck
 #pragma unroll
             for (int t = 0; t < NPT; ++t) {
                 const f32x4_t a4 = acc2c[t];
-                const float x0 = sp_value(relu_nan(__builtin_fmaf(a4[0], s2, b4.x))), x1 = sp_value(relu_nan(__builtin_fmaf(a4[1], s2, b4.y)));
-                const float x2 = sp_value(relu_nan(__builtin_fmaf(a4[2], s2, b4.z))), x3 = sp_value(relu_nan(__builtin_fmaf(a4[3], s2, b4.w)));
-                sp_flag(ovm, sp_max2(sp_max2(0.f, x0, x1), x2, x3));
-                typedef __attribute__((ext_vector_type(4))) spe_t spx4_t;
-                spx4_t h4, l4;
-                h4[0] = (spe_t)x0; h4[1] = (spe_t)x1; h4[2] = (spe_t)x2; h4[3] = (spe_t)x3;
-                l4[0] = (spe_t)(x0 - (float)h4[0]); l4[1] = (spe_t)(x1 - (float)h4[1]);
-                l4[2] = (spe_t)(x2 - (float)h4[2]); l4[3] = (spe_t)(x3 - (float)h4[3]);
+                const float x[4] = {relu_nan(__builtin_fmaf(a4[0], s2, b4.x)), relu_nan(__builtin_fmaf(a4[1], s2, b4.y)),
+                                    relu_nan(__builtin_fmaf(a4[2], s2, b4.z)), relu_nan(__builtin_fmaf(a4[3], s2, b4.w))};
+                float amax = 0.f;
+                uint2 h4, l4;
+                sp_split4(x, amax, h4, l4);
+                sp_flag(ovm, amax);
                 const int row = t * 16 + l15;
-                *reinterpret_cast<spx4_t*>(t2p + swz(row, g) + 8 * half) = h4;
-                *reinterpret_cast<spx4_t*>(t2p + swz(row, 4 + g) + 8 * half) = l4;
+                *reinterpret_cast<uint2*>(t2p + swz(row, g) + 8 * half) = h4;
+                *reinterpret_cast<uint2*>(t2p + swz(row, 4 + g) + 8 * half) = l4;
             }
         }
         __syncthreads();  // T2 is complete
@@ -921,7 +894,7 @@ __global__ void __launch_bounds__(256, P == 64 ? 3 : 2) bneck_kernel(const Bneck
                                 relu_nan(__builtin_fmaf(lo4[2], s2, b0.z)), relu_nan(__builtin_fmaf(lo4[3], s2, b0.w)),
                                 relu_nan(__builtin_fmaf(hi4[0], s2, b1.x)), relu_nan(__builtin_fmaf(hi4[1], s2, b1.y)),
                                 relu_nan(__builtin_fmaf(hi4[2], s2, b1.z)), relu_nan(__builtin_fmaf(hi4[3], s2, b1.w))};
-            split8v(v, t2h[q][t], t2l[q][t], ovm);
+            sp_split8(v, t2h[q][t], t2l[q][t], ovm);
         }
     }
     f32x4_t acc1[NEXT ? P / 16 : 1][NT];
@@ -968,13 +941,13 @@ __global__ void __launch_bounds__(256, P == 64 ? 3 : 2) bneck_kernel(const Bneck
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             float r[8];
-            unpack8(h[t], l[t], r);
+            sp_join8(h[t], l[t], r);
             const f32x4_t lo4 = acc3[0][t], hi4 = acc3[1][t];
             const float v[8] = {relu_nan(__builtin_fmaf(lo4[0], s3, b0.x) + r[0]), relu_nan(__builtin_fmaf(lo4[1], s3, b0.y) + r[1]),
                                 relu_nan(__builtin_fmaf(lo4[2], s3, b0.z) + r[2]), relu_nan(__builtin_fmaf(lo4[3], s3, b0.w) + r[3]),
                                 relu_nan(__builtin_fmaf(hi4[0], s3, b1.x) + r[4]), relu_nan(__builtin_fmaf(hi4[1], s3, b1.y) + r[5]),
                                 relu_nan(__builtin_fmaf(hi4[2], s3, b1.z) + r[6]), relu_nan(__builtin_fmaf(hi4[3], s3, b1.w) + r[7])};
-            split8v(v, oh[t], ol[t], ovm);
+            sp_split8(v, oh[t], ol[t], ovm);
             if (m_ok[t]) {
                 char* yp = p.OUT + (size_t)(SUB == 1 ? x_row[t] : o_row[SUB > 1 ? t : 0]) + G * 128;
                 *reinterpret_cast<spx8_t*>(yp) = oh[t];
@@ -1011,7 +984,7 @@ __global__ void __launch_bounds__(256, P == 64 ? 3 : 2) bneck_kernel(const Bneck
                                     relu_nan(__builtin_fmaf(hi4[0], s1n, b1.x)), relu_nan(__builtin_fmaf(hi4[1], s1n, b1.y)),
                                     relu_nan(__builtin_fmaf(hi4[2], s1n, b1.z)), relu_nan(__builtin_fmaf(hi4[3], s1n, b1.w))};
                 spx8_t hi, lo;
-                split8v(v, hi, lo, ovm);
+                sp_split8(v, hi, lo, ovm);
                 if (m_ok[t]) {
                     char* yp = p.T1N + (long)m_row[t] * (P * 4) + q * 128 + 16 * g;  // m_row == the position wherever m_ok
                     *reinterpret_cast<spx8_t*>(yp) = hi;
@@ -1152,13 +1125,13 @@ __global__ void __launch_bounds__(512, 2) bneck_tail2_kernel(const BneckParams p
         f32x4_t b0, b1;                                                                                                        \
         lds_read8(sbias + P + 32 * (G) + 8 * g, b0, b1);                                                                       \
         float r[8];                                                                                                            \
-        unpack8(__builtin_bit_cast(uint4, H), __builtin_bit_cast(uint4, L), r);                                                \
+        sp_join8(__builtin_bit_cast(uint4, H), __builtin_bit_cast(uint4, L), r);                                                \
         const float v[8] = {relu_nan(__builtin_fmaf(acc3[0][0], s3, b0[0]) + r[0]), relu_nan(__builtin_fmaf(acc3[0][1], s3, b0[1]) + r[1]), \
                             relu_nan(__builtin_fmaf(acc3[0][2], s3, b0[2]) + r[2]), relu_nan(__builtin_fmaf(acc3[0][3], s3, b0[3]) + r[3]), \
                             relu_nan(__builtin_fmaf(acc3[1][0], s3, b1[0]) + r[4]), relu_nan(__builtin_fmaf(acc3[1][1], s3, b1[1]) + r[5]), \
                             relu_nan(__builtin_fmaf(acc3[1][2], s3, b1[2]) + r[6]), relu_nan(__builtin_fmaf(acc3[1][3], s3, b1[3]) + r[7])}; \
         spx8_t oh, ol;                                                                                                       \
-        split8v(v, oh, ol, ovm);                                                                                                    \
+        sp_split8(v, oh, ol, ovm);                                                                                                    \
         /* (oh / ol stay live as the next contraction's operand.  A 16-byte buffer store with its offset in an SGPR whose data  */ \
         /* registers die here would be a hazard on gfx950 that hipcc does not separate: tests/test_build_hygiene.py scans for it) */ \
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, oh), outrs, o_row, (G) * 128, 0);                   \
@@ -1195,7 +1168,7 @@ __global__ void __launch_bounds__(512, 2) bneck_tail2_kernel(const BneckParams p
                             relu_nan(__builtin_fmaf(hi4[0], s1n, b1.x)), relu_nan(__builtin_fmaf(hi4[1], s1n, b1.y)),
                             relu_nan(__builtin_fmaf(hi4[2], s1n, b1.z)), relu_nan(__builtin_fmaf(hi4[3], s1n, b1.w))};
         spx8_t hi, lo;
-        split8v(v, hi, lo, ovm);
+        sp_split8(v, hi, lo, ovm);
         if (m_ok) {
             char* yp = p.T1N + m * (P * 4L) + q * 128 + 16 * g;
             *reinterpret_cast<spx8_t*>(yp) = hi;
@@ -1252,8 +1225,7 @@ int launch_stem_pool(avcer_ctx* ctx, const void* planes, size_t plane_bytes, con
     TRY(prof_begin(ctx, st, &ev0, &ev1, FAM_STEM, 2.0 * n * 112.0 * 112.0 * 64 * 147, (double)n * (2.0 * 230 * 230 * 4 * 2 + 55.0 * 55 * 64 * 4)));
     stem_pool_kernel<<<dim3(n * ST_TY * ST_TX), dim3(256), 0, st>>>(p);
     if (ev1) (void)hipEventRecord(ev1, st);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_err(ctx, AVCER_EHIP, "stem_pool launch: %s", hipGetErrorString(e));
+    CHECK_LAUNCH(ctx, "stem_pool");
     ctx->gemm_launches += 1;
     ctx->gemm_flops += 2.0 * n * 112.0 * 112.0 * 64 * 147;
     return AVCER_OK;
@@ -1272,8 +1244,7 @@ int launch_stem_pool_u8(avcer_ctx* ctx, const uint8_t* frames, int in_h, int in_
     TRY(prof_begin(ctx, st, &ev0, &ev1, FAM_STEM, 2.0 * n * 112.0 * 112.0 * 64 * 147, (double)n * ((double)in_h * in_w * 3 + 55.0 * 55 * 64 * 4)));
     stem_pool_u8_kernel<false><<<dim3(n * ST_TY * ST_TX), dim3(256), 0, st>>>(p);
     if (ev1) (void)hipEventRecord(ev1, st);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_err(ctx, AVCER_EHIP, "stem_pool_u8 launch: %s", hipGetErrorString(e));
+    CHECK_LAUNCH(ctx, "stem_pool_u8");
     ctx->gemm_launches += 1;
     ctx->gemm_flops += 2.0 * n * 112.0 * 112.0 * 64 * 147;
     return AVCER_OK;
@@ -1299,8 +1270,7 @@ int launch_stem_pool_face(avcer_ctx* ctx, const uint8_t* frames, int h, int w, i
     TRY(prof_begin(ctx, st, &ev0, &ev1, FAM_STEM, flops, (double)n * ((double)h * w * 3 + (double)p.mh * p.mw * 64 * 4), (long)n * p.oh * p.ow, 64, 147));
     stem_pool_u8_kernel<true><<<dim3((unsigned)grid), dim3(256), 0, st>>>(p);
     if (ev1) (void)hipEventRecord(ev1, st);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_err(ctx, AVCER_EHIP, "stem_pool_face launch: %s", hipGetErrorString(e));
+    CHECK_LAUNCH(ctx, "stem_pool_face");
     ctx->gemm_launches += 1;
     ctx->gemm_flops += flops;
     return AVCER_OK;
@@ -1372,8 +1342,7 @@ int launch_bneck(avcer_ctx* ctx, int planes, int nb, int h, int w, const void* t
         }
     }
     if (ev1) (void)hipEventRecord(ev1, st);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_err(ctx, AVCER_EHIP, "bneck launch: %s", hipGetErrorString(e));
+    CHECK_LAUNCH(ctx, "bneck");
     ctx->gemm_launches += 1;
     ctx->gemm_flops += 2.0 * (double)M * planes * (planes * (9.0 + 4.0 + (t1n ? 4.0 : 0.0)) + 4.0 * ds_cin);
     return AVCER_OK;
@@ -1397,8 +1366,7 @@ int launch_bneck_tail(avcer_ctx* ctx, int planes, long M, const void* t2, const 
     p.t1_bytes = (unsigned)(M * 4096L);
     bneck_tail2_kernel<256><<<dim3((int)((M + 127) / 128)), dim3(512), 0, st>>>(p);
     if (ev1) (void)hipEventRecord(ev1, st);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_err(ctx, AVCER_EHIP, "bneck_tail launch: %s", hipGetErrorString(e));
+    CHECK_LAUNCH(ctx, "bneck_tail");
     ctx->gemm_launches += 1;
     ctx->gemm_flops += 2.0 * (double)M * planes * planes * 8.0;
     return AVCER_OK;

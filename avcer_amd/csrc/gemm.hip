@@ -122,12 +122,7 @@ __device__ __forceinline__ void finish8(const GemmParams& p, long m, int n0, con
 #pragma unroll
         for (int j = 0; j < 4; ++j) { r[2 * j] = bf2f((bf16_t)(w[j] & 0xffff)); r[2 * j + 1] = bf2f((bf16_t)(w[j] >> 16)); }
     } else {
-        const uint32_t wh[4] = {r0.x, r0.y, r0.z, r0.w}, wl[4] = {r1.x, r1.y, r1.z, r1.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            r[2 * j] = sp2f((uint16_t)(wh[j] & 0xffff)) + sp2f((uint16_t)(wl[j] & 0xffff));
-            r[2 * j + 1] = sp2f((uint16_t)(wh[j] >> 16)) + sp2f((uint16_t)(wl[j] >> 16));
-        }
+        sp_join8(r0, r1, r);
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -150,21 +145,13 @@ __device__ __forceinline__ void finish8(const GemmParams& p, long m, int n0, con
         t.w = (uint32_t)f2bf(v[6]) | ((uint32_t)f2bf(v[7]) << 16);
         *reinterpret_cast<uint4*>(p.Y + e * 2) = t;
     } else {
-        uint32_t h[4], l[4];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = sp_value(v[j]);  // one f32 number for both halves of the pair (split_dev.h)
         float amax = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            amax = sp_max2(amax, v[2 * j], v[2 * j + 1]);
-            const uint16_t h0 = f2sp(v[2 * j]), h1 = f2sp(v[2 * j + 1]);
-            h[j] = (uint32_t)h0 | ((uint32_t)h1 << 16);
-            l[j] = (uint32_t)f2sp(v[2 * j] - sp2f(h0)) | ((uint32_t)f2sp(v[2 * j + 1] - sp2f(h1)) << 16);
-        }
+        uint4 h, l;
+        sp_split8(v, amax, h, l);
         sp_flag(ovm, amax);  // range contract: |x| < 65504 (split_dev.h sp_commit)
         char* yp = p.Y + sp32_byte(e);
-        *reinterpret_cast<uint4*>(yp) = make_uint4(h[0], h[1], h[2], h[3]);
-        *reinterpret_cast<uint4*>(yp + 64) = make_uint4(l[0], l[1], l[2], l[3]);
+        *reinterpret_cast<uint4*>(yp) = h;
+        *reinterpret_cast<uint4*>(yp + 64) = l;
     }
 }
 
@@ -296,22 +283,6 @@ __device__ __forceinline__ void epilogue_direct(const GemmParams& p, f32x4_t (&a
     }
 }
 
-// f32 -> split pair used by MODE 2: x = hi + lo + O(2^-22 |x|) with hi, lo fp16 (round to nearest even; split_dev.h)
-__device__ __forceinline__ void split8(const float4 x, const float4 y, spx8_t& hi, spx8_t& lo, sp_flags_t& ovm) {
-    const float v[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
-    float amax = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; j += 2) amax = sp_max2(amax, v[j], v[j + 1]);
-    sp_flag(ovm, amax);  // range contract: |x| < 65504 (split_dev.h sp_commit)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float w = sp_value(v[j]);  // one f32 number for both halves (split_dev.h)
-        const spe_t h = (spe_t)w;
-        hi[j] = h;
-        lo[j] = (spe_t)(w - (float)h);
-    }
-}
-
 // MODE 0: f32 operands, v_mfma_f32_32x32x2_f32.  MODE 1: bf16 operands, v_mfma_f32_16x16x32_bf16.
 // MODE 2 ("x3"): f32 activations split on the fly into fp16 hi+lo, weights pre-split and pre-scaled (per 32-element K group:
 // 32 hi then 32 lo fp16), a.w ~= ah.wh + ah.wl + al.wh on the f16 MFMA with f32 accumulation -- f32-grade
@@ -360,7 +331,8 @@ __device__ __forceinline__ void mfma_step(const GemmParams& p, const char* smem,
             }
             const float4 x = *reinterpret_cast<const float4*>(sa + swz(row, 2 * g));
             const float4 y = *reinterpret_cast<const float4*>(sa + swz(row, 2 * g + 1));
-            split8(x, y, ahi[fm], alo[fm], ovm);
+            const float v[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+            sp_split8(v, ahi[fm], alo[fm], ovm);  // MODE 2 splits its f32 activations on the fly (split_dev.h)
         }
 #pragma unroll
         for (int fn = 0; fn < NFN; ++fn) {
@@ -957,12 +929,7 @@ __device__ __forceinline__ void finish4(const GemmParams& p, long m, int n0, con
         r[0] = __builtin_bit_cast(float, r0.x); r[1] = __builtin_bit_cast(float, r0.y);
         r[2] = __builtin_bit_cast(float, r1.x); r[3] = __builtin_bit_cast(float, r1.y);
     } else {
-        const uint32_t wh[2] = {r0.x, r0.y}, wl[2] = {r1.x, r1.y};
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            r[2 * j] = sp2f((uint16_t)(wh[j] & 0xffff)) + sp2f((uint16_t)(wl[j] & 0xffff));
-            r[2 * j + 1] = sp2f((uint16_t)(wh[j] >> 16)) + sp2f((uint16_t)(wl[j] >> 16));
-        }
+        sp_join4(r0, r1, r);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -976,21 +943,13 @@ __device__ __forceinline__ void finish4(const GemmParams& p, long m, int n0, con
     if constexpr (OUT == 0) {
         *reinterpret_cast<float4*>(p.Y + e * 4) = make_float4(v[0], v[1], v[2], v[3]);
     } else {
-        uint32_t h[2], l[2];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = sp_value(v[j]);
         float amax = 0.f;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            amax = sp_max2(amax, v[2 * j], v[2 * j + 1]);
-            const uint16_t h0 = f2sp(v[2 * j]), h1 = f2sp(v[2 * j + 1]);
-            h[j] = (uint32_t)h0 | ((uint32_t)h1 << 16);
-            l[j] = (uint32_t)f2sp(v[2 * j] - sp2f(h0)) | ((uint32_t)f2sp(v[2 * j + 1] - sp2f(h1)) << 16);
-        }
+        uint2 h, l;
+        sp_split4(v, amax, h, l);
         sp_flag(ovm, amax);
         char* yp = p.Y + sp32_byte(e);
-        *reinterpret_cast<uint2*>(yp) = make_uint2(h[0], h[1]);
-        *reinterpret_cast<uint2*>(yp + 64) = make_uint2(l[0], l[1]);
+        *reinterpret_cast<uint2*>(yp) = h;
+        *reinterpret_cast<uint2*>(yp + 64) = l;
     }
 }
 
@@ -1324,8 +1283,7 @@ int launch_conv_gemm(avcer_ctx* ctx, const avcer_conv_desc& d, int dtype, const 
         default: launch_skinny<0>(p, st); break;  // sp32 -> f32, a handful of positions
     }
     if (ev1) (void)hipEventRecord(ev1, st);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_err(ctx, AVCER_EHIP, "conv_gemm launch: %s", hipGetErrorString(e));
+    CHECK_LAUNCH(ctx, "conv_gemm");
     ctx->gemm_launches += 1;
     ctx->gemm_flops += 2.0 * (double)M * (double)d.n * (double)K * groups;
     return AVCER_OK;

@@ -1,9 +1,8 @@
 // Device-side helpers shared by the MFMA kernels of libavcer_hip.so (gemm.hip, bneck.hip): LDS-DMA, the searched
-// LDS swizzle, bf16 / sp32 conversions.  gfx950 only.
+// LDS swizzle, the two GELU forms of the epilogues.  The bf16 / sp32 conversions come from act_io.h.  gfx950 only.
 #pragma once
 
-#include "common.h"
-#include "split_dev.h"
+#include "act_io.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
@@ -57,16 +56,5 @@ __device__ __forceinline__ float gelu_fast(float x) {
     const float erfz = __builtin_copysignf(__builtin_fmaf(-p, e, 1.0f), z);
     return 0.5f * x * (1.0f + erfz);
 }
-
-// ReLU that keeps a NaN a NaN like torch (any sign, any payload: the comparison is false for it), in TWO vector instructions
-// (v_cmp_lt + v_cndmask) -- the (v > 0 ? v : (v != v ? v : 0)) form costs four, and the fused bottleneck kernels run this
-// on every element they store.  -0.0 stays -0.0, which no consumer can tell from +0.0.
-__device__ __forceinline__ float relu_nan(float v) { return v < 0.f ? 0.f : v; }
-
-__device__ __forceinline__ bf16_t f2bf(float f) { return __builtin_bit_cast(bf16_t, (__bf16)f); }
-__device__ __forceinline__ float bf2f(bf16_t b) { return __builtin_bit_cast(float, (uint32_t)b << 16); }
-
-// sp32 storage: per aligned group of 32 channels, 32 hi bf16 then 32 lo bf16 (value = hi + lo; 4 bytes per element)
-__device__ __forceinline__ long sp32_byte(long e) { return ((e & ~31L) << 2) + ((e & 31L) << 1); }
 
 }  // namespace

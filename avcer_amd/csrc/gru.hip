@@ -177,16 +177,9 @@ __global__ void __launch_bounds__(GRU_THREADS) gru_layer_kernel(const GruParams 
         // h_t: to the sequence (f32, and sp32 pairs for the next contraction that reads it) and to the LDS tile of the next step
         uint4 hi, lo;
         if constexpr (X3) {
-            uint32_t ph[4], pl[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float a = sp_value(h[j >> 1][2 * (j & 1)]), b = sp_value(h[j >> 1][2 * (j & 1) + 1]);
-                const uint16_t ha = f2sp(a), hb2 = f2sp(b);
-                ph[j] = (uint32_t)ha | ((uint32_t)hb2 << 16);
-                pl[j] = (uint32_t)f2sp(a - sp2f(ha)) | ((uint32_t)f2sp(b - sp2f(hb2)) << 16);
-            }
-            hi = make_uint4(ph[0], ph[1], ph[2], ph[3]);
-            lo = make_uint4(pl[0], pl[1], pl[2], pl[3]);
+            const float h8[8] = {h[0][0], h[0][1], h[0][2], h[0][3], h[1][0], h[1][1], h[1][2], h[1][3]};
+            float hmax = 0.f;  // never read: |h_t| <= 1
+            sp_split8(h8, hmax, hi, lo);
             // units 32 wv + 8 g .. + 7: K group wv of the sp32 row, 16 bytes of its hi half and of its lo half
             *reinterpret_cast<uint4*>(hn + wv * 128 + g * 16) = hi;
             *reinterpret_cast<uint4*>(hn + wv * 128 + g * 16 + 64) = lo;
@@ -231,7 +224,6 @@ int launch_gru_layer(avcer_ctx* ctx, const float* xp, const void* w, int x3, con
     if (x3) gru_layer_kernel<1><<<grid, GRU_THREADS, 0, st>>>(p);
     else gru_layer_kernel<0><<<grid, GRU_THREADS, 0, st>>>(p);
     if (ev1) (void)hipEventRecord(ev1, st);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_err(ctx, AVCER_EHIP, "gru_layer launch: %s", hipGetErrorString(e));
+    CHECK_LAUNCH(ctx, "gru_layer");
     return AVCER_OK;
 }

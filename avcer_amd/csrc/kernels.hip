@@ -1,18 +1,18 @@
 // Element-wise, normalisation, pooling, attention and fusion kernels of the AVCER hot path (gfx950).
 // All of these are HBM/LDS-bound: 16-byte vector accesses, one 64-lane wave per row for reductions,
 // f32 statistics regardless of the activation storage type.
-#include "common.h"
-#include "split_dev.h"
+#include "act_io.h"
 
 #include <cstdlib>
 #include <type_traits>
 
 namespace {
 
-__device__ __forceinline__ bf16_t f2bf(float f) { return __builtin_bit_cast(bf16_t, (__bf16)f); }
-__device__ __forceinline__ float bf2f(bf16_t b) { return __builtin_bit_cast(float, (uint32_t)b << 16); }
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
-// erf from Abramowitz & Stegun 7.1.26: see gemm_dev.h gelu_fast (same code; |gelu_fast - gelu| <= 4.7e-7 on [-8, 8])
+// erf from Abramowitz & Stegun 7.1.26, the arithmetic of gemm_dev.h gelu_fast (|gelu_fast - gelu| <= 4.7e-7 on [-8, 8]).  NOT
+// the same code: the gemm_dev.h pair carries `#pragma clang fp contract(off)` (the forms of one contraction must round
+// alike), this pair does not, so hipcc may contract these into the arithmetic around them in conv0 and LayerNorm.  Merging
+// the two would change what one of the two sides computes; both stay.
 __device__ __forceinline__ float gelu_fast(float x) {
     const float z = x * 0.70710678118654752440f, a = __builtin_fabsf(z);
     const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(0.3275911f, a, 1.0f));
@@ -24,135 +24,6 @@ __device__ __forceinline__ float gelu_fast(float x) {
     const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * a * a);
     const float erfz = __builtin_copysignf(__builtin_fmaf(-p, e, 1.0f), z);
     return 0.5f * x * (1.0f + erfz);
-}
-__device__ __forceinline__ float relu_nan(float v) { return v < 0.f ? 0.f : v; }  // keeps NaN like torch; two instructions (gemm_dev.h)
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-template <typename T> __device__ __forceinline__ float ldf(const T* p, long i);
-template <> __device__ __forceinline__ float ldf<float>(const float* p, long i) { return p[i]; }
-template <> __device__ __forceinline__ float ldf<bf16_t>(const bf16_t* p, long i) { return bf2f(p[i]); }
-// `ovf`: the context's range-contract counter (split_dev.h sp_commit); only the sp32 forms look at it
-template <typename T> __device__ __forceinline__ void stf(T* p, long i, float v, unsigned* ovf = nullptr);
-template <> __device__ __forceinline__ void stf<float>(float* p, long i, float v, unsigned*) { p[i] = v; }
-template <> __device__ __forceinline__ void stf<bf16_t>(bf16_t* p, long i, float v, unsigned*) { p[i] = f2bf(v); }
-
-// load / store 4 consecutive elements
-template <typename T> __device__ __forceinline__ void ld4(const T* p, long i, float* v);
-template <> __device__ __forceinline__ void ld4<float>(const float* p, long i, float* v) {
-    const float4 t = *reinterpret_cast<const float4*>(p + i);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-}
-template <> __device__ __forceinline__ void ld4<bf16_t>(const bf16_t* p, long i, float* v) {
-    const uint2 t = *reinterpret_cast<const uint2*>(p + i);
-    v[0] = bf2f((bf16_t)(t.x & 0xffff)); v[1] = bf2f((bf16_t)(t.x >> 16));
-    v[2] = bf2f((bf16_t)(t.y & 0xffff)); v[3] = bf2f((bf16_t)(t.y >> 16));
-}
-template <typename T> __device__ __forceinline__ void st4(T* p, long i, const float* v, unsigned* ovf = nullptr);
-template <> __device__ __forceinline__ void st4<float>(float* p, long i, const float* v, unsigned*) {
-    *reinterpret_cast<float4*>(p + i) = make_float4(v[0], v[1], v[2], v[3]);
-}
-template <> __device__ __forceinline__ void st4<bf16_t>(bf16_t* p, long i, const float* v, unsigned*) {
-    uint2 t;
-    t.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-    t.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-    *reinterpret_cast<uint2*>(p + i) = t;
-}
-
-// sp32 storage (AVCER_MODE_F16X3 activations): per aligned group of 32 channels, 32 fp16 hi then 32 fp16 lo (split_dev.h),
-// x = hi + lo.  4 bytes per element; element index e lives at byte ((e & ~31) << 2) + ((e & 31) << 1) (+64 for lo).
-struct sp32_t { uint32_t raw; };
-__device__ __forceinline__ long sp32_byte(long e) { return ((e & ~31L) << 2) + ((e & 31L) << 1); }
-template <> __device__ __forceinline__ float ldf<sp32_t>(const sp32_t* p, long i) {
-    const char* b = reinterpret_cast<const char*>(p) + sp32_byte(i);
-    return sp2f(*reinterpret_cast<const uint16_t*>(b)) + sp2f(*reinterpret_cast<const uint16_t*>(b + 64));
-}
-template <> __device__ __forceinline__ void stf<sp32_t>(sp32_t* p, long i, float v, unsigned* ovf) {
-    char* b = reinterpret_cast<char*>(p) + sp32_byte(i);
-    v = sp_value(v);  // one f32 number for both halves (split_dev.h)
-    sp_count_now(ovf, __builtin_fabsf(v));  // range contract: a finite |v| >= 65520 is counted (these kernels are HBM-bound)
-    const uint16_t h = f2sp(v);
-    *reinterpret_cast<uint16_t*>(b) = h;
-    *reinterpret_cast<uint16_t*>(b + 64) = f2sp(v - sp2f(h));
-}
-template <> __device__ __forceinline__ void ld4<sp32_t>(const sp32_t* p, long i, float* v) {
-    const char* b = reinterpret_cast<const char*>(p) + sp32_byte(i);
-    const uint2 h = *reinterpret_cast<const uint2*>(b);
-    const uint2 l = *reinterpret_cast<const uint2*>(b + 64);
-    v[0] = sp2f((uint16_t)(h.x & 0xffff)) + sp2f((uint16_t)(l.x & 0xffff));
-    v[1] = sp2f((uint16_t)(h.x >> 16)) + sp2f((uint16_t)(l.x >> 16));
-    v[2] = sp2f((uint16_t)(h.y & 0xffff)) + sp2f((uint16_t)(l.y & 0xffff));
-    v[3] = sp2f((uint16_t)(h.y >> 16)) + sp2f((uint16_t)(l.y >> 16));
-}
-template <> __device__ __forceinline__ void st4<sp32_t>(sp32_t* p, long i, const float* vin, unsigned* ovf) {
-    char* b = reinterpret_cast<char*>(p) + sp32_byte(i);
-    uint16_t h[4];
-    uint2 hh, ll;
-    float v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = sp_value(vin[j]);  // one f32 number for both halves (split_dev.h)
-    {
-        float amax = 0.f;  // range contract (split_dev.h sp_commit): these kernels are HBM-bound, the test rides along
-        amax = sp_max2(sp_max2(amax, v[0], v[1]), v[2], v[3]);
-        sp_count_now(ovf, amax);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) h[j] = f2sp(v[j]);
-    hh.x = (uint32_t)h[0] | ((uint32_t)h[1] << 16);
-    hh.y = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
-    ll.x = (uint32_t)f2sp(v[0] - sp2f(h[0])) | ((uint32_t)f2sp(v[1] - sp2f(h[1])) << 16);
-    ll.y = (uint32_t)f2sp(v[2] - sp2f(h[2])) | ((uint32_t)f2sp(v[3] - sp2f(h[3])) << 16);
-    *reinterpret_cast<uint2*>(b) = hh;
-    *reinterpret_cast<uint2*>(b + 64) = ll;
-}
-
-// 8 consecutive elements (i a multiple of 8).  The sp32 forms move ONE 16-byte piece per half: 8-byte accesses run at
-// 0.54-0.70 x the 16-byte rate on this part (MI355X_MICROARCH.md), and conv0 / LayerNorm / the average pool were written
-// with the 4-element helpers above (conv0 at 2 x its write floor, the pool at 2 x its read floor: round-4 review, item 7b).
-template <typename T> __device__ __forceinline__ void ld8(const T* p, long i, float* v) {
-    ld4<T>(p, i, v);
-    ld4<T>(p, i + 4, v + 4);
-}
-template <> __device__ __forceinline__ void ld8<sp32_t>(const sp32_t* p, long i, float* v) {
-    const char* b = reinterpret_cast<const char*>(p) + sp32_byte(i);
-    const uint4 h = *reinterpret_cast<const uint4*>(b);
-    const uint4 l = *reinterpret_cast<const uint4*>(b + 64);
-    const uint32_t hw[4] = {h.x, h.y, h.z, h.w}, lw[4] = {l.x, l.y, l.z, l.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        v[2 * j] = sp2f((uint16_t)(hw[j] & 0xffff)) + sp2f((uint16_t)(lw[j] & 0xffff));
-        v[2 * j + 1] = sp2f((uint16_t)(hw[j] >> 16)) + sp2f((uint16_t)(lw[j] >> 16));
-    }
-}
-template <typename T> __device__ __forceinline__ void st8(T* p, long i, const float* v, unsigned* ovf = nullptr) {
-    st4<T>(p, i, v, ovf);
-    st4<T>(p, i + 4, v + 4, ovf);
-}
-template <> __device__ __forceinline__ void st8<sp32_t>(sp32_t* p, long i, const float* vin, unsigned* ovf) {
-    char* b = reinterpret_cast<char*>(p) + sp32_byte(i);
-    float v[8], amax = 0.f;
-    uint32_t hw[4], lw[4];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = sp_value(vin[j]);  // one f32 number for both halves (split_dev.h)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        amax = sp_max2(amax, v[2 * j], v[2 * j + 1]);
-        const uint16_t h0 = f2sp(v[2 * j]), h1 = f2sp(v[2 * j + 1]);
-        hw[j] = (uint32_t)h0 | ((uint32_t)h1 << 16);
-        lw[j] = (uint32_t)f2sp(v[2 * j] - sp2f(h0)) | ((uint32_t)f2sp(v[2 * j + 1] - sp2f(h1)) << 16);
-    }
-    sp_count_now(ovf, amax);  // range contract (split_dev.h)
-    *reinterpret_cast<uint4*>(b) = make_uint4(hw[0], hw[1], hw[2], hw[3]);
-    *reinterpret_cast<uint4*>(b + 64) = make_uint4(lw[0], lw[1], lw[2], lw[3]);
 }
 
 // ------------------------------------------------------------------------------------------------ preprocess
@@ -185,25 +56,13 @@ __global__ void preprocess_kernel(const uint8_t* __restrict__ in, T* __restrict_
 
 // Planar split-fp16 variant (input of stem_pool_kernel): the same zero-bordered image as two fp16 planes
 // [n,230,230,4], hi = bf16(v) and lo = bf16(v - hi), so that one 8-pixel tap row is 64 contiguous bytes per plane.
-__device__ __forceinline__ void st4_planar(bf16_t* hi, bf16_t* lo, long idx, const float* vin, unsigned* ovf = nullptr) {
-    uint16_t h[4];
-    float v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = sp_value(vin[j]);  // one f32 number for both halves (split_dev.h)
-    {
-        float amax = 0.f;  // range contract (split_dev.h sp_commit)
-        amax = sp_max2(sp_max2(amax, v[0], v[1]), v[2], v[3]);
-        sp_count_now(ovf, amax);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) h[j] = f2sp(v[j]);
-    uint2 hh, ll;
-    hh.x = (uint32_t)h[0] | ((uint32_t)h[1] << 16);
-    hh.y = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
-    ll.x = (uint32_t)f2sp(v[0] - sp2f(h[0])) | ((uint32_t)f2sp(v[1] - sp2f(h[1])) << 16);
-    ll.y = (uint32_t)f2sp(v[2] - sp2f(h[2])) | ((uint32_t)f2sp(v[3] - sp2f(h[3])) << 16);
-    *reinterpret_cast<uint2*>(hi + idx * 4) = hh;
-    *reinterpret_cast<uint2*>(lo + idx * 4) = ll;
+__device__ __forceinline__ void st4_planar(bf16_t* hi, bf16_t* lo, long idx, const float* v, unsigned* ovf = nullptr) {
+    float amax = 0.f;
+    uint2 h, l;
+    sp_split4(v, amax, h, l);
+    sp_count_now(ovf, amax);  // range contract (split_dev.h)
+    *reinterpret_cast<uint2*>(hi + idx * 4) = h;
+    *reinterpret_cast<uint2*>(lo + idx * 4) = l;
 }
 
 __global__ void preprocess_planar_kernel(const uint8_t* __restrict__ in, bf16_t* __restrict__ hi, bf16_t* __restrict__ lo, int n,
@@ -1175,15 +1034,12 @@ typedef __attribute__((ext_vector_type(4))) float att_f32x4_t;
 template <int X3> struct AttOp {
     typedef spe_t elem_t;
     typedef spx8_t frag_t;
-    static __device__ __forceinline__ uint16_t bits(float f) { return f2sp(f); }
-    static __device__ __forceinline__ float val(uint16_t b) { return sp2f(b); }
     static __device__ __forceinline__ att_f32x4_t mfma(const frag_t a, const frag_t b, const att_f32x4_t c) { return mfma_sp(a, b, c); }
 };
 template <> struct AttOp<0> {
     typedef __bf16 elem_t;
     typedef att_bf16x8_t frag_t;
     static __device__ __forceinline__ uint16_t bits(float f) { return f2bf(f); }
-    static __device__ __forceinline__ float val(uint16_t b) { return bf2f(b); }
     static __device__ __forceinline__ att_f32x4_t mfma(const frag_t a, const frag_t b, const att_f32x4_t c) {
         return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
     }
@@ -1263,32 +1119,27 @@ __global__ void __launch_bounds__(64 * ATTM_WAVES) attention_mfma_kernel(const T
     for (int u = 0; u < UB; ++u) {
         const int it = (p0 + u) * NTHR + tid;
         const int r = it / (D / 8), c = it % (D / 8);   // key row, chunk of 8 head-dim elements (K rows keep a 128-byte pitch)
-        float kv[8], vv[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {  // one f32 number for both halves of every pair (split_dev.h sp_value)
-            kv[j] = sp_value(kvb[u][j]);
-            vv[j] = sp_value(vvb[u][j]);
-        }
-        if (X3) {  // range contract of the fp16 pairs (split_dev.h sp_commit)
-#pragma unroll
-            for (int j = 0; j < 8; j += 2) amax = sp_max2(sp_max2(amax, kv[j], kv[j + 1]), vv[j], vv[j + 1]);
-        }
-        uint32_t hw[4], lw[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint16_t h0 = Op::bits(kv[2 * j]), h1 = Op::bits(kv[2 * j + 1]);
-            hw[j] = (uint32_t)h0 | ((uint32_t)h1 << 16);
-            lw[j] = (uint32_t)Op::bits(kv[2 * j] - Op::val(h0)) | ((uint32_t)Op::bits(kv[2 * j + 1] - Op::val(h1)) << 16);
-        }
-        *reinterpret_cast<uint4*>(khi + att_swz(r, c)) = make_uint4(hw[0], hw[1], hw[2], hw[3]);
-        if (X3) *reinterpret_cast<uint4*>(klo + att_swz(r, c)) = make_uint4(lw[0], lw[1], lw[2], lw[3]);
         // V^T: key r sits at k-position (r>>5)*32 + ((r&15)>>2)*8 + ((r>>4)&1)*4 + (r&3) of every head-dim row
         const int kpos = (r >> 5) * 32 + ((r & 15) >> 2) * 8 + ((r >> 4) & 1) * 4 + (r & 3);
+        if constexpr (X3) {  // fp16 pairs (split_dev.h); amax: their range contract
+            uint4 hw, lw;
+            sp_split8(kvb[u], amax, hw, lw);
+            *reinterpret_cast<uint4*>(khi + att_swz(r, c)) = hw;
+            *reinterpret_cast<uint4*>(klo + att_swz(r, c)) = lw;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const uint16_t hv = Op::bits(vv[j]);
-            *reinterpret_cast<uint16_t*>(vhi + (8 * c + j) * VROW + kpos * 2) = hv;
-            if (X3) *reinterpret_cast<uint16_t*>(vlo + (8 * c + j) * VROW + kpos * 2) = Op::bits(vv[j] - Op::val(hv));
+            for (int j = 0; j < 8; ++j) {
+                uint16_t hv, lv;
+                sp_split1(vvb[u][j], amax, hv, lv);
+                *reinterpret_cast<uint16_t*>(vhi + (8 * c + j) * VROW + kpos * 2) = hv;
+                *reinterpret_cast<uint16_t*>(vlo + (8 * c + j) * VROW + kpos * 2) = lv;
+            }
+        } else {
+            uint32_t hw[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) hw[j] = (uint32_t)Op::bits(kvb[u][2 * j]) | ((uint32_t)Op::bits(kvb[u][2 * j + 1]) << 16);
+            *reinterpret_cast<uint4*>(khi + att_swz(r, c)) = make_uint4(hw[0], hw[1], hw[2], hw[3]);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) *reinterpret_cast<uint16_t*>(vhi + (8 * c + j) * VROW + kpos * 2) = Op::bits(vvb[u][j]);
         }
     }
     }
@@ -1303,14 +1154,14 @@ __global__ void __launch_bounds__(64 * ATTM_WAVES) attention_mfma_kernel(const T
         frag_t qh[KS], ql[KS];
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            const float (&qv)[8] = qraw[qi][ks];
+            float qv[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float x = sp_value(qv[j] * scale);
-                if (X3) amax = __builtin_fmaxf(amax, __builtin_fabsf(x));
-                const elem_t hh = (elem_t)x;
-                qh[ks][j] = hh;
-                ql[ks][j] = (elem_t)(x - (float)hh);
+            for (int j = 0; j < 8; ++j) qv[j] = qraw[qi][ks][j] * scale;
+            if constexpr (X3) {
+                sp_split8(qv, amax, qh[ks], ql[ks]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) qh[ks][j] = (elem_t)qv[j];
             }
         }
         // ---- scores^T: key tiles x this query tile
@@ -1359,12 +1210,19 @@ __global__ void __launch_bounds__(64 * ATTM_WAVES) attention_mfma_kernel(const T
 #pragma unroll
         for (int kb = 0; kb < NKT / 2; ++kb) {
             frag_t ph, pl;
+            // element by element from the accumulators: through a float[8] copy and sp_split8 the 16-key-tile forms need 27 / 58
+            // more VGPRs and lose an occupancy step
+            float pmax = 0.f;  // never read: probabilities are at most 1
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const float x = sp_value(sc[2 * kb + (j >> 2)][j & 3]);
-                const elem_t hh = (elem_t)x;
-                ph[j] = hh;
-                pl[j] = (elem_t)(x - (float)hh);
+                if constexpr (X3) {
+                    spe_t hh, ll;
+                    sp_split1(sc[2 * kb + (j >> 2)][j & 3], pmax, hh, ll);
+                    ph[j] = hh;
+                    pl[j] = ll;
+                } else {
+                    ph[j] = (elem_t)sc[2 * kb + (j >> 2)][j & 3];
+                }
             }
 #pragma unroll
             for (int tv = 0; tv < TV; ++tv) {
@@ -1430,12 +1288,13 @@ __global__ void mean_time_relu_kernel(const float* __restrict__ x, float* __rest
 __global__ void split_weights_kernel(const float* __restrict__ w, bf16_t* __restrict__ out, size_t n, unsigned* ovf) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float v = sp_value(w[i]);
-    sp_count_now(ovf, __builtin_fabsf(v));  // range contract of an unscaled split (split_dev.h)
-    const uint16_t h = f2sp(v);
+    float amax = 0.f;
+    uint16_t h, l;
+    sp_split1(w[i], amax, h, l);
+    sp_count_now(ovf, amax);  // range contract of an unscaled split (split_dev.h)
     const size_t g = i >> 5, j = i & 31;
     out[g * 64 + j] = h;
-    out[g * 64 + 32 + j] = f2sp(v - sp2f(h));
+    out[g * 64 + 32 + j] = l;
 }
 
 // max |w| of a tensor as float bits (non-negative floats order like their bit patterns; NaN / inf end up largest)
@@ -1479,11 +1338,12 @@ __global__ void split_weight_rows_kernel(const float* __restrict__ w, bf16_t* __
     const int row = i / k, col = i - (size_t)row * k;      // destination row / K index
     const int j = row & 31, t = j >> 4, g = (j >> 2) & 3, r = j & 3;
     const int src = (row & ~31) + 8 * g + 4 * t + r;
-    const float v = sp_value(w[(size_t)src * k + col] * __uint_as_float(sc.x));
-    const uint16_t h = f2sp(v);
+    float amax = 0.f;  // never read: the scale puts every weight under 2^15
+    uint16_t h, l;
+    sp_split1(w[(size_t)src * k + col] * __uint_as_float(sc.x), amax, h, l);
     const size_t o = (size_t)row * k * 2 + (size_t)(col >> 5) * 64 + (col & 31);
     out[o] = h;
-    out[o + 32] = f2sp(v - sp2f(h));
+    out[o + 32] = l;
 }
 
 // The row-split weights once more, in MFMA fragment order for conv_gemm_wd_kernel (gemm.hip): [N/16][K/32][hi, lo][64 lanes]
@@ -1682,15 +1542,7 @@ __global__ void fuse_videos_kernel(const float* __restrict__ stat, const float* 
     }
 }
 
-inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
-
 }  // namespace
-
-#define CHECK_LAUNCH(ctx, name)                                                                      \
-    do {                                                                                             \
-        hipError_t _e = hipGetLastError();                                                           \
-        if (_e != hipSuccess) return set_err((ctx), AVCER_EHIP, name " launch: %s", hipGetErrorString(_e)); \
-    } while (0)
 
 int k_preprocess(avcer_ctx* ctx, const uint8_t* frames, int n, int in_h, int in_w, void* out, int kind, hipStream_t st) {
     const long total = (long)n * PP * PP;

@@ -12,19 +12,11 @@
 //   mnet_conv_kernel   the neck (FPN laterals and merges, SSH branches, merged heads: 64 / 32 / 16 output channels) as direct f32
 //                      convolutions on the VALU, weights [taps * cin][cout] read through wave-uniform addresses.
 // A block's work is fixed by (frame, tile) alone, so a frame's result does not depend on the batch around it.
-#include "common.h"
-#include "split_dev.h"
-
+#include "act_io.h"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-
-#define MNET_CHECK_LAUNCH(ctx, name)                                                                  \
-    do {                                                                                              \
-        hipError_t _e = hipGetLastError();                                                            \
-        if (_e != hipSuccess) return set_err((ctx), AVCER_EHIP, name " launch: %s", hipGetErrorString(_e)); \
-    } while (0)
 
 __device__ __forceinline__ float leaky01(float v) { return v >= 0.f ? v : 0.1f * v; }  // a NaN stays a NaN (0.1 * NaN)
 
@@ -151,19 +143,10 @@ __global__ __launch_bounds__(256) void dwsep_kernel(const float* __restrict__ x,
 #pragma unroll
             for (int j = 0; j < 4; ++j) a[j] = leaky01(__builtin_fmaf(a[j], sc[j], sh[j]));
             if (X3) {
-                // ONE f32 number per split: hi and lo are both taken from the same opaque register
-                uint16_t hi[4], lo[4];
-                float amax = 0.f;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float v = sp_value(a[j]);
-                    hi[j] = f2sp(v);
-                    lo[j] = f2sp(v - sp2f(hi[j]));
-                }
-                amax = sp_max2(sp_max2(amax, a[0], a[1]), a[2], a[3]);
+                float amax = 0.f, a4[4] = {a[0], a[1], a[2], a[3]};
+                uint2 hv, lv;
+                sp_split4(a4, amax, hv, lv);  // split_dev.h: one f32 number per split
                 sp_flag(flags, amax);
-                const uint2 hv = make_uint2(hi[0] | ((unsigned)hi[1] << 16), hi[2] | ((unsigned)hi[3] << 16));
-                const uint2 lv = make_uint2(lo[0] | ((unsigned)lo[1] << 16), lo[2] | ((unsigned)lo[3] << 16));
                 *reinterpret_cast<uint2*>(at + a_off(p, cq >> 1) + (cq & 1) * 8) = hv;        // 32 hi halves: chunks 0-3
                 *reinterpret_cast<uint2*>(at + a_off(p, 4 + (cq >> 1)) + (cq & 1) * 8) = lv;  // 32 lo halves: chunks 4-7
             } else {
@@ -306,7 +289,7 @@ int launch_dwsep_t(avcer_ctx* ctx, int x3, const float* x, const float* dww, con
     if (x3) dwsep_kernel<CIN, COUT, S, true><<<grid, 256, 0, st>>>(x, dww, dws, dwb, pw, pws, pwb, y, h, w, oh, ow, tiles_x, ctx->ovf);
     else dwsep_kernel<CIN, COUT, S, false><<<grid, 256, 0, st>>>(x, dww, dws, dwb, pw, pws, pwb, y, h, w, oh, ow, tiles_x, nullptr);
     if (ev1) (void)hipEventRecord(ev1, st);
-    MNET_CHECK_LAUNCH(ctx, "dwsep");
+    CHECK_LAUNCH(ctx, "dwsep");
     ctx->gemm_launches += 1;
     ctx->gemm_flops += flops;
     return AVCER_OK;
@@ -324,7 +307,7 @@ int launch_mnet_stem(avcer_ctx* ctx, const uint8_t* frames, int n, int h, int w,
     TRY(prof_begin(ctx, st, &ev0, &ev1, FAM_STEM, flops, (double)n * h * w * 3 + (double)total * 8 * 4, total, 8, 27));
     mnet_stem_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(frames, n, h, w, oh, ow, rgb, wt, s, b, y);
     if (ev1) (void)hipEventRecord(ev1, st);
-    MNET_CHECK_LAUNCH(ctx, "mnet_stem");
+    CHECK_LAUNCH(ctx, "mnet_stem");
     ctx->gemm_launches += 1;
     ctx->gemm_flops += flops;
     return AVCER_OK;
@@ -359,7 +342,7 @@ int launch_mnet_conv(avcer_ctx* ctx, int ks, const float* x, const float* wt, co
     const dim3 grid((unsigned)((total + 255) / 256), (unsigned)(cout / 16));
     if (ks == 3) mnet_conv_kernel<3><<<grid, 256, 0, st>>>(x, wt, s, b, y, total, h, w, cin, cout, y_ld, y_coff, act);
     else mnet_conv_kernel<1><<<grid, 256, 0, st>>>(x, wt, s, b, y, total, h, w, cin, cout, y_ld, y_coff, act);
-    MNET_CHECK_LAUNCH(ctx, "mnet_conv");
+    CHECK_LAUNCH(ctx, "mnet_conv");
     ctx->gemm_launches += 1;
     ctx->gemm_flops += 2.0 * (double)total * cout * cin * ks * ks;
     return AVCER_OK;

@@ -16,60 +16,11 @@
 //                        level 0's max-out background label and the 2-class softmax, and writes the rows at the level's offset.
 //   s3fd_decode / order / nms   Detect and the predictor's loop on the device, see below.
 // A wave's work is fixed by (frame, row, tile) alone, so a frame's result does not depend on the batch around it.
-#include "common.h"
-#include "split_dev.h"
+#include "act_io.h"
 
 #include <cmath>
 
 namespace {
-
-#define S3FD_CHECK_LAUNCH(ctx, name)                                                                  \
-    do {                                                                                              \
-        hipError_t _e = hipGetLastError();                                                            \
-        if (_e != hipSuccess) return set_err((ctx), AVCER_EHIP, name " launch: %s", hipGetErrorString(_e)); \
-    } while (0)
-
-inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
-
-__device__ __forceinline__ float relu_nan(float v) { return v < 0.f ? 0.f : v; }  // keeps NaN like torch
-
-// ---- 4 consecutive channels of an NHWC tensor in f32 or sp32 storage (kernels.hip: per aligned group of 32 channels 32 fp16 hi,
-// then 32 fp16 lo; element e at byte ((e & ~31) << 2) + ((e & 31) << 1), +64 for lo)
-struct sp32_t { uint32_t raw; };
-__device__ __forceinline__ long sp32_byte(long e) { return ((e & ~31L) << 2) + ((e & 31L) << 1); }
-template <typename T> __device__ __forceinline__ void ld4(const T* p, long i, float* v);
-template <> __device__ __forceinline__ void ld4<float>(const float* p, long i, float* v) {
-    const float4 t = *reinterpret_cast<const float4*>(p + i);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-}
-template <> __device__ __forceinline__ void ld4<sp32_t>(const sp32_t* p, long i, float* v) {
-    const char* b = reinterpret_cast<const char*>(p) + sp32_byte(i);
-    const uint2 h = *reinterpret_cast<const uint2*>(b);
-    const uint2 l = *reinterpret_cast<const uint2*>(b + 64);
-    v[0] = sp2f((uint16_t)(h.x & 0xffff)) + sp2f((uint16_t)(l.x & 0xffff));
-    v[1] = sp2f((uint16_t)(h.x >> 16)) + sp2f((uint16_t)(l.x >> 16));
-    v[2] = sp2f((uint16_t)(h.y & 0xffff)) + sp2f((uint16_t)(l.y & 0xffff));
-    v[3] = sp2f((uint16_t)(h.y >> 16)) + sp2f((uint16_t)(l.y >> 16));
-}
-template <typename T> __device__ __forceinline__ void st4(T* p, long i, const float* v, unsigned* ovf);
-template <> __device__ __forceinline__ void st4<float>(float* p, long i, const float* v, unsigned*) {
-    *reinterpret_cast<float4*>(p + i) = make_float4(v[0], v[1], v[2], v[3]);
-}
-template <> __device__ __forceinline__ void st4<sp32_t>(sp32_t* p, long i, const float* vin, unsigned* ovf) {
-    char* b = reinterpret_cast<char*>(p) + sp32_byte(i);
-    float v[4];
-    uint16_t h[4], l[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = sp_value(vin[j]);  // one f32 number for both halves (split_dev.h)
-    sp_count_now(ovf, sp_max2(sp_max2(0.f, v[0], v[1]), v[2], v[3]));  // range contract; a null counter counts nothing
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        h[j] = f2sp(v[j]);
-        l[j] = f2sp(v[j] - sp2f(h[j]));
-    }
-    *reinterpret_cast<uint2*>(b) = make_uint2((uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16));
-    *reinterpret_cast<uint2*>(b + 64) = make_uint2((uint32_t)l[0] | ((uint32_t)l[1] << 16), (uint32_t)l[2] | ((uint32_t)l[3] << 16));
-}
 
 // ------------------------------------------------------------------------------------------------ stem (conv1_1)
 // One thread per (pixel, 16 output channels): the four threads of a pixel are neighbours, so a wave writes 16 whole pixels = 4 KiB
@@ -420,7 +371,7 @@ int launch_s3fd_stem(avcer_ctx* ctx, const uint8_t* frames, int n, int h, int w,
     if (kind == KIND_SP32) s3fd_stem_kernel<sp32_t><<<cdiv(npix * 4, 256), 256, 0, st>>>(frames, npix, h, w, rgb, wt, b, (sp32_t*)y, ctx->ovf);
     else if (kind == KIND_F32) s3fd_stem_kernel<float><<<cdiv(npix * 4, 256), 256, 0, st>>>(frames, npix, h, w, rgb, wt, b, (float*)y, nullptr);
     else return set_err(ctx, AVCER_EINVAL, "s3fd_stem: storage kind %d (f32 and sp32 only)", kind);
-    S3FD_CHECK_LAUNCH(ctx, "s3fd_stem");
+    CHECK_LAUNCH(ctx, "s3fd_stem");
     return AVCER_OK;
 }
 
@@ -432,7 +383,7 @@ int launch_maxpool2(avcer_ctx* ctx, const void* x, void* y, int n, int h, int w,
     if (kind == KIND_SP32) maxpool2_kernel<sp32_t><<<grid, 256, 0, st>>>((const sp32_t*)x, (sp32_t*)y, n, h, w, c, oh, ow);
     else if (kind == KIND_F32) maxpool2_kernel<float><<<grid, 256, 0, st>>>((const float*)x, (float*)y, n, h, w, c, oh, ow);
     else return set_err(ctx, AVCER_EINVAL, "maxpool2: storage kind %d (f32 and sp32 only)", kind);
-    S3FD_CHECK_LAUNCH(ctx, "maxpool2");
+    CHECK_LAUNCH(ctx, "maxpool2");
     return AVCER_OK;
 }
 
@@ -445,7 +396,7 @@ int launch_s3fd_head(avcer_ctx* ctx, const void* x, int kind, float* inv, const 
     if (inv != nullptr) {
         if (kind == KIND_SP32) s3fd_invnorm_kernel<sp32_t><<<cdiv(npos, 4), 256, 0, st>>>((const sp32_t*)x, npos, c, inv);
         else s3fd_invnorm_kernel<float><<<cdiv(npos, 4), 256, 0, st>>>((const float*)x, npos, c, inv);
-        S3FD_CHECK_LAUNCH(ctx, "s3fd_invnorm");
+        CHECK_LAUNCH(ctx, "s3fd_invnorm");
     }
     if (kind == KIND_SP32) {
         if (n_out == 8) s3fd_head_kernel<sp32_t, 8><<<grid, 256, 0, st>>>((const sp32_t*)x, inv, wt, b, nb, h, w, c, row0, P, loc, conf);
@@ -454,7 +405,7 @@ int launch_s3fd_head(avcer_ctx* ctx, const void* x, int kind, float* inv, const 
         if (n_out == 8) s3fd_head_kernel<float, 8><<<grid, 256, 0, st>>>((const float*)x, inv, wt, b, nb, h, w, c, row0, P, loc, conf);
         else s3fd_head_kernel<float, 6><<<grid, 256, 0, st>>>((const float*)x, inv, wt, b, nb, h, w, c, row0, P, loc, conf);
     }
-    S3FD_CHECK_LAUNCH(ctx, "s3fd_head");
+    CHECK_LAUNCH(ctx, "s3fd_head");
     return AVCER_OK;
 }
 
@@ -476,13 +427,13 @@ int launch_s3fd_detect(avcer_ctx* ctx, const float* loc, const float* conf, cons
         attr_dev |= 1ull << (ctx->device & 63);
     }
     s3fd_decode_kernel<<<dim3(cdiv(P, 256), T), 256, 0, st>>>(loc, conf, priors, P, var0, var1, dets);
-    S3FD_CHECK_LAUNCH(ctx, "s3fd_decode");
+    CHECK_LAUNCH(ctx, "s3fd_decode");
     int N = 64;  // LDS for the worst case the sort takes; the kernel sorts the next power of two of ITS count
     while (N < P && N < ORDER_LDS) N <<= 1;
     s3fd_order_kernel<<<T, ORDER_THREADS, (size_t)N * 8, st>>>(dets, P, conf_thresh, nms_top_k, keys, order, count);
-    S3FD_CHECK_LAUNCH(ctx, "s3fd_order");
+    CHECK_LAUNCH(ctx, "s3fd_order");
     s3fd_nms_kernel<<<T, S3FD_NMS_THREADS, 0, st>>>(dets, P, order, count, nms_top_k, nms_thresh, top_k, threshold, (float)im_w, (float)im_h,
                                                    out, out_n);
-    S3FD_CHECK_LAUNCH(ctx, "s3fd_nms");
+    CHECK_LAUNCH(ctx, "s3fd_nms");
     return AVCER_OK;
 }

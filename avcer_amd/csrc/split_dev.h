@@ -59,17 +59,14 @@ __device__ __forceinline__ sp_f32x4_t mfma_sp(const spx8_t a, const spx8_t b, co
 // ---- the range contract's run-time signal (round 5; include/avcer_hip.h avcer_x3_overflow_count)
 // An activation of magnitude >= 65520 rounds to +-inf in its fp16 hi half and reaches the output as NaN -- which is also what
 // the reference legitimately returns for an empty audio window, so NaN alone does not tell a caller that the contract broke.
-// Every site that splits an f32 ACTIVATION takes the maximum magnitude of the values it splits (one v_max3_f32 per two
-// values; NaN operands do not move it: the max instructions return the other operand), compares it with the threshold and
+// Every site that splits an f32 ACTIVATION takes the maximum magnitude of the values it splits (sp_split1 below folds each
+// value in with fmaxf; NaN operands do not move it: the max instructions return the other operand), compares it with the threshold and
 // ORs the wave's ballot into a wave-uniform mask (scalar registers: a per-thread running maximum cost the fused kernels 20
 // vector registers and a resident block).  Once, at the end of the kernel, a wave whose mask is not empty adds its lane
 // count to the context's device counter.  Only FINITE values count (an infinite input was counted where it became
 // infinite), so a NaN audio window leaves the counter at 0.
 constexpr float AVCER_SP_OVERFLOW = 65520.f;  // smallest magnitude that rounds to +-inf in fp16 (round to nearest even)
 typedef unsigned long long sp_flags_t;
-__device__ __forceinline__ float sp_max2(float amax, float a, float b) {
-    return __builtin_fmaxf(__builtin_fmaxf(amax, __builtin_fabsf(a)), __builtin_fabsf(b));
-}
 __device__ __forceinline__ bool sp_out_of_range(float amax) { return amax >= AVCER_SP_OVERFLOW && amax < __builtin_inff(); }
 // amax = the largest magnitude of the values this lane has just split
 __device__ __forceinline__ void sp_flag(sp_flags_t& flags, float amax) {
@@ -91,6 +88,79 @@ __device__ __forceinline__ void sp_count_now(unsigned* ovf, float amax) {
     if (ovf != nullptr && sp_out_of_range(amax)) atomicAdd(ovf, 1u);
 #endif
 }
+
+// ---- the pair itself: THE place where an f32 activation becomes (hi, lo).  Every kernel that makes or reads a pair calls one
+// of the functions below, so "one f32 number per split, hi rounded first, lo from v - hi, magnitude into the range
+// contract's maximum" is audited here and nowhere else.  `amax` is the caller's running maximum: it reports it once through
+// sp_flag + sp_commit (MFMA kernels) or sp_count_now (HBM-bound kernels); a site whose values cannot leave the range by
+// construction (scaled weights, softmax probabilities, a GRU state) passes a local it never reads.
+__device__ __forceinline__ void sp_split1(float v, float& amax, spe_t& hi, spe_t& lo) {
+    v = sp_value(v);
+    amax = __builtin_fmaxf(amax, __builtin_fabsf(v));
+    hi = (spe_t)v;
+    lo = (spe_t)(v - (float)hi);
+}
+__device__ __forceinline__ void sp_split1(float v, float& amax, uint16_t& hi, uint16_t& lo) {  // the same as raw bits
+    spe_t h, l;
+    sp_split1(v, amax, h, l);
+    hi = __builtin_bit_cast(uint16_t, h);
+    lo = __builtin_bit_cast(uint16_t, l);
+}
+// two values -> the packed hi word and the packed lo word (a in bits 0-15, b in bits 16-31)
+__device__ __forceinline__ void sp_split2(float a, float b, float& amax, uint32_t& hi, uint32_t& lo) {
+    uint16_t ha, la, hb, lb;
+    sp_split1(a, amax, ha, la);
+    sp_split1(b, amax, hb, lb);
+    hi = (uint32_t)ha | ((uint32_t)hb << 16);
+    lo = (uint32_t)la | ((uint32_t)lb << 16);
+}
+// ... and back
+__device__ __forceinline__ void sp_join2(uint32_t hi, uint32_t lo, float& a, float& b) {
+    a = sp2f((uint16_t)(hi & 0xffff)) + sp2f((uint16_t)(lo & 0xffff));
+    b = sp2f((uint16_t)(hi >> 16)) + sp2f((uint16_t)(lo >> 16));
+}
+// four / eight consecutive values as packed words (the 8- and 16-byte pieces of the sp32 layout below)
+__device__ __forceinline__ void sp_split4(const float* v, float& amax, uint2& hi, uint2& lo) {
+    sp_split2(v[0], v[1], amax, hi.x, lo.x);
+    sp_split2(v[2], v[3], amax, hi.y, lo.y);
+}
+__device__ __forceinline__ void sp_join4(const uint2 hi, const uint2 lo, float* v) {
+    sp_join2(hi.x, lo.x, v[0], v[1]);
+    sp_join2(hi.y, lo.y, v[2], v[3]);
+}
+__device__ __forceinline__ void sp_split8(const float* v, float& amax, uint4& hi, uint4& lo) {
+    sp_split2(v[0], v[1], amax, hi.x, lo.x);
+    sp_split2(v[2], v[3], amax, hi.y, lo.y);
+    sp_split2(v[4], v[5], amax, hi.z, lo.z);
+    sp_split2(v[6], v[7], amax, hi.w, lo.w);
+}
+__device__ __forceinline__ void sp_join8(const uint4 hi, const uint4 lo, float* v) {
+    sp_join2(hi.x, lo.x, v[0], v[1]);
+    sp_join2(hi.y, lo.y, v[2], v[3]);
+    sp_join2(hi.z, lo.z, v[4], v[5]);
+    sp_join2(hi.w, lo.w, v[6], v[7]);
+}
+// eight values as the two MFMA operand fragments (registers, not memory)
+__device__ __forceinline__ void sp_split8(const float (&v)[8], float& amax, spx8_t& hi, spx8_t& lo) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        spe_t h, l;
+        sp_split1(v[j], amax, h, l);
+        hi[j] = h;
+        lo[j] = l;
+    }
+}
+// ... reporting its own maximum into the kernel's flags: the operand split of the MFMA kernels (gemm.hip, fused.hip)
+__device__ __forceinline__ void sp_split8(const float (&v)[8], spx8_t& hi, spx8_t& lo, sp_flags_t& flags) {
+    float amax = 0.f;
+    sp_split8(v, amax, hi, lo);
+    sp_flag(flags, amax);  // range contract: |x| < 65504 (sp_commit)
+}
+
+// sp32 storage (AVCER_MODE_F16X3 activations): per aligned group of 32 channels, 32 hi halves then 32 lo halves, x = hi + lo.
+// 4 bytes per element; element index e lives at byte ((e & ~31) << 2) + ((e & 31) << 1), its lo half 64 bytes further.
+struct sp32_t { uint32_t raw; };
+__device__ __forceinline__ long sp32_byte(long e) { return ((e & ~31L) << 2) + ((e & 31L) << 1); }
 
 // the accumulator multiplier stored behind a split weight matrix of `bytes` bytes (see above)
 __device__ __forceinline__ float split_wmul(const char* w, size_t bytes) { return *reinterpret_cast<const float*>(w + bytes); }
