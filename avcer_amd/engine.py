@@ -465,6 +465,23 @@ class Engine:
                                               self._stream()))
         return tiles, flags
 
+    def jpeg_forward(self, src, rects, desc, n: int, n_blocks: int, bgr: bool = False, out=None):
+        """The forward half of the JPEG encoder (avcer_jpeg_forward): image i is the half-open rectangle rects[i] = (slot, x0, y0, x1, y1)
+        (int32 [n,5] on the device) of src u8 [N,H,W,3] (RGB, or BGR with `bgr`); desc = n records of struct avcer_jpeg_desc as bytes on
+        the device, as avcer_jpeg_plan wrote them -> quantised coefficients int16 [64 * n_blocks] in the layout the decoder reads."""
+        if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[-1] != 3 or not src.is_cuda or not src.is_contiguous():
+            raise ValueError("jpeg_forward: src must be a contiguous uint8 [N,H,W,3] on the device")
+        if rects.dtype != torch.int32 or tuple(rects.shape) != (n, 5) or not rects.is_cuda or not rects.is_contiguous():
+            raise ValueError("jpeg_forward: rects must be a contiguous int32 [n,5] on the device")
+        if desc.dtype != torch.uint8 or desc.numel() < _JPEG_DESC_BYTES * n or not desc.is_cuda:
+            raise ValueError("jpeg_forward: desc uint8 [sizeof(avcer_jpeg_desc) * n] on the device")
+        coeffs = self._new(64 * int(n_blocks), dtype=torch.int16) if out is None else out
+        if coeffs.dtype != torch.int16 or coeffs.numel() < 64 * n_blocks or not coeffs.is_cuda or not coeffs.is_contiguous():
+            raise ValueError("jpeg_forward: out must be a contiguous int16 [>= 64 * n_blocks] on the device")
+        self._check(self.lib.avcer_jpeg_forward(self.ctx, _ptr(src), int(src.shape[0]), int(src.shape[1]), int(src.shape[2]), _ptr(rects),
+                                                _ptr(desc), int(n), 1 if bgr else 0, _ptr(coeffs), int(n_blocks), self._stream()))
+        return coeffs
+
     def jpeg_rgb(self, coeffs, desc, n: int, n_blocks: int, hmax: int, wmax: int):
         """The same files at full size -> (canvas u8 [n,hmax,wmax,3] RGB: image i in the top left corner of slot i, zeros around it;
         flags i32 [n] as jpeg_tiles returns them)."""

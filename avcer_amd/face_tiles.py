@@ -18,6 +18,7 @@ network runs on the same implicit-GEMM kernel as the recognition models (`avcer_
 from __future__ import annotations
 
 import math
+import os
 from functools import lru_cache
 from typing import List, Optional, Sequence
 
@@ -306,7 +307,10 @@ class VideoTiler:
         self.engine = engine
         self.face_tracker = SimpleFaceTracker(iou_threshold=0.4, minimum_face_size=0.0)
 
-    def process(self, frames_bgr, dets_per_frame: Sequence[np.ndarray]):
+    def process(self, frames_bgr, dets_per_frame: Sequence[np.ndarray], save_path: Optional[str] = None, video_name: Optional[str] = None):
+        """`save_path` and `video_name` given: the crops are also written as the reference's face folders (write_face_crops)."""
+        if (save_path is None) != (video_name is None):
+            raise ValueError("give both save_path and video_name, or neither")
         frames = frames_bgr if torch.is_tensor(frames_bgr) else torch.from_numpy(np.ascontiguousarray(frames_bgr))
         if frames.dim() != 4 or frames.shape[-1] != 3 or frames.dtype != torch.uint8:
             raise ValueError("frames must be uint8 [T,H,W,3] (BGR, as cv2 decodes them)")
@@ -320,7 +324,35 @@ class VideoTiler:
         if not len(records):
             return records, torch.zeros((0, 224, 224, 3), dtype=torch.uint8, device=self.engine.device)
         rects = torch.from_numpy(records[:, [0, 2, 3, 4, 5]].astype(np.int32))
+        if save_path is not None:
+            frames = frames.to(self.engine.device)  # one copy for both consumers
+            write_face_crops(self.engine, frames, records, save_path, video_name)
         return records, self.engine.crop_tiles(frames, rects, bgr=True)
+
+
+def face_crop_paths(records: np.ndarray, save_path: str, video_name: str) -> List[str]:
+    """get_face_images.py:58-60: `<save_path>/<video_name>/<track:02d>/<frame:06d>.jpg` of every record, in record order."""
+    return [os.path.join(save_path, video_name, str(int(t)).zfill(2), str(int(f)).zfill(6) + ".jpg") for f, t in records[:, :2]]
+
+
+def write_face_crops(engine, frames_bgr, records: np.ndarray, save_path: str, video_name: str, quality: int = 95) -> List[str]:
+    """Stage 0's face folders (`VideoPredictor.process`, get_face_images.py:52-63): for every record of `VideoTiler.process` the
+    half-open crop `fr[y0:y1, x0:x1]` of its frame, written where the reference's cv2.imwrite writes it (JPEG quality 95, 4:2:0:
+    cv2's defaults).  The crops are encoded straight out of the BGR frames on the device (jpeg.encode_images); no crop and no
+    frame is copied to the host.  Returns the paths in record order."""
+    from . import jpeg
+
+    records = np.asarray(records).reshape(-1, 6)
+    paths = face_crop_paths(records, save_path, video_name)
+    if not paths:
+        return paths
+    blobs = jpeg.encode_images(engine, frames_bgr, records[:, [0, 2, 3, 4, 5]], bgr=True, quality=quality, subsampling=2)
+    for folder in sorted({os.path.dirname(p) for p in paths}):
+        os.makedirs(folder, exist_ok=True)
+    for p, blob in zip(paths, blobs):
+        with open(p, "wb") as f:
+            f.write(blob)
+    return paths
 
 
 def track_clip(records: np.ndarray, tiles: torch.Tensor, track: int, total_frames: int):

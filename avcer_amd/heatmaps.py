@@ -141,18 +141,29 @@ def heatmap_dir(save_path: str, video_name: str, model_heatmaps: str) -> str:
     return os.path.join(save_path, video_name, f"heatmaps_{model_heatmaps}")
 
 
-def write_heatmaps(folder: str, frame_idx, images_bgr) -> list:
+def write_heatmaps(folder: str, frame_idx, images_bgr, engine=None) -> list:
     """cv2.imwrite(<folder>/<NNNNNN>.jpg, overlay) for every heat-map frame (get_prob_video.py:154): JPEG quality 95 (cv2's
-    default) through PIL, the BGR array flipped to RGB first so that the file's colours are the reference's."""
+    default), the BGR array flipped to RGB first so that the file's colours are the reference's.  With an `engine` and overlays on
+    the device the files come from jpeg.encode_images (forward pass on the device, Huffman coding on host threads); else from
+    PIL, one file at a time.  The bytes are the same either way."""
+    os.makedirs(folder, exist_ok=True)
+    idx = np.asarray(frame_idx).reshape(-1)
+    paths = [os.path.join(folder, str(int(i)).zfill(6) + ".jpg") for i in idx]
+    if engine is not None and torch.is_tensor(images_bgr) and images_bgr.is_cuda:
+        from . import jpeg
+
+        m, h, w = min(len(paths), int(images_bgr.shape[0])), int(images_bgr.shape[1]), int(images_bgr.shape[2])
+        rects = np.array([(i, 0, 0, w, h) for i in range(m)], dtype=np.int32).reshape(m, 5)
+        for p, blob in zip(paths, jpeg.encode_images(engine, images_bgr, rects, bgr=True, quality=95, subsampling=2)):
+            with open(p, "wb") as f:
+                f.write(blob)
+        return paths[:m]
     from PIL import Image
 
-    os.makedirs(folder, exist_ok=True)
     imgs = images_bgr.cpu().numpy() if torch.is_tensor(images_bgr) else np.asarray(images_bgr)
-    paths = []
-    for i, img in zip(np.asarray(frame_idx).reshape(-1), imgs):
-        p = os.path.join(folder, str(int(i)).zfill(6) + ".jpg")
+    paths = paths[:len(imgs)]
+    for p, img in zip(paths, imgs):
         Image.fromarray(np.ascontiguousarray(img[..., ::-1])).save(p, quality=95)
-        paths.append(p)
     return paths
 
 

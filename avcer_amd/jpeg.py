@@ -1,4 +1,5 @@
-"""JPEG face crops decoded behind a host entropy pass (csrc/jpeg.hip, include/avcer_hip.h "JPEG face crops").
+"""JPEG face crops decoded behind a host entropy pass, and encoded in front of one (csrc/jpeg.hip, include/avcer_hip.h "JPEG
+face crops").  Decoding first; `encode_images` and its numpy statement `forward_numpy` are in the second half of this file.
 
 `decode_tiles` / `decode_canvas` take the bytes of n files.  One native host call parses the markers and Huffman-decodes every file
 the parser supports (a small thread pool, files are independent); the int16 coefficients and the per-file descriptors go to the
@@ -285,3 +286,226 @@ def decode_canvas(engine, blobs, threads: int = 0):
         canvas[i, :img.shape[0], :img.shape[1]] = torch.from_numpy(img).to(dev)
     rects = np.array([(i, 0, 0, w, h) for i, (w, h) in enumerate(sizes)], dtype=np.int32).reshape(n, 5)
     return (canvas, rects), paths
+
+
+# ==================================================================================================== encoding
+# The mirror image of the above (include/avcer_hip.h "JPEG face crops", encoding): the device computes the quantised coefficients
+# of every image (colour conversion, chroma downsampling, forward DCT, quantisation: avcer_jpeg_forward), the host writes the
+# files (avcer_jpeg_write_batch: headers, Huffman coding).  The contract is byte-identity with
+# PIL.Image.fromarray(rgb).save(f, "JPEG", quality=quality, subsampling=subsampling) (libjpeg-turbo, standard Huffman tables).
+HEADER_BYTES = 623  # csrc/jpeg.hip: SOI, APP0, two DQT, SOF0, four DHT, SOS
+R_ENC_SIZE = 18  # csrc/jpeg.hip: an image of zero width or height, or of more than 65535 pixels a side
+
+# libjpeg's jcparam.c: the two tables of the standard's annex K in natural order
+_STD_LUMA = np.array([16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87,
+                      80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72,
+                      92, 95, 98, 112, 100, 103, 99], dtype=np.int64)
+_STD_CHROMA = np.array([17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99,
+                        99, 99, 99] + [99] * 32, dtype=np.int64)
+SAMPLING = {0: (1, 1), 1: (2, 1), 2: (2, 2)}  # PIL's `subsampling` -> the luma sampling factors (hs, vs); chroma is 1 x 1
+
+
+def quant_tables_numpy(quality: int) -> np.ndarray:
+    """jpeg_set_quality(quality, force_baseline): u16 [2, 64], luma and chroma, natural order (avcer_jpeg_quant_tables)."""
+    q = min(max(int(quality), 1), 100)
+    scale = 5000 // q if q < 50 else 200 - 2 * q
+    return np.stack([np.clip((t * scale + 50) // 100, 1, 255) for t in (_STD_LUMA, _STD_CHROMA)]).astype(np.uint16)
+
+
+def plan_numpy(sizes, quality: int, subsampling: int) -> np.ndarray:
+    """avcer_jpeg_plan in numpy: DESC records of images of `sizes` [(w, h)] (tests; the product path calls the library)."""
+    hs, vs = SAMPLING[int(subsampling)]
+    qt = quant_tables_numpy(quality)
+    desc = np.zeros(len(sizes), dtype=DESC)
+    at = 0
+    for d, (w, h) in zip(desc, sizes):
+        d["width"], d["height"], d["ncomp"], d["hs"], d["vs"] = w, h, 3, hs, vs
+        d["coef_block"] = at
+        if not (0 < w <= 65535 and 0 < h <= 65535):
+            d["status"], d["reason"] = NOT_HANDLED, R_ENC_SIZE
+            continue
+        mx, my = -(-w // (8 * hs)), -(-h // (8 * vs))
+        d["bw"], d["bh"], d["tq"] = (mx * hs, mx, mx), (my * vs, my, my), (0, 1, 1)
+        d["qt"][0], d["qt"][1], d["qt"][2] = qt[0], qt[1], qt[1]
+        d["n_blocks"] = mx * my * (hs * vs + 2)
+        at += int(d["n_blocks"])
+    return desc
+
+
+def _fdct_1d(d, first):
+    """libjpeg's jfdctint.c (jpeg_fdct_islow), one 1-D pass along axis 0 of an int64 array [8, ...]: 13-bit constants; the first pass
+    leaves its results scaled up by 2^PASS1_BITS = 4, the second takes that out again (and leaves the factor 8 of the 2-D DCT)."""
+    tmp0, tmp7, tmp1, tmp6 = d[0] + d[7], d[0] - d[7], d[1] + d[6], d[1] - d[6]
+    tmp2, tmp5, tmp3, tmp4 = d[2] + d[5], d[2] - d[5], d[3] + d[4], d[3] - d[4]
+    tmp10, tmp13, tmp11, tmp12 = tmp0 + tmp3, tmp0 - tmp3, tmp1 + tmp2, tmp1 - tmp2
+    sh = 11 if first else 15
+    ds = lambda x: (x + (1 << (sh - 1))) >> sh
+    o0, o4 = ((tmp10 + tmp11) << 2, (tmp10 - tmp11) << 2) if first else ((tmp10 + tmp11 + 2) >> 2, (tmp10 - tmp11 + 2) >> 2)
+    z1 = (tmp12 + tmp13) * 4433
+    o2, o6 = ds(z1 + tmp13 * 6270), ds(z1 + tmp12 * (-15137))
+    z1, z2, z3, z4 = tmp4 + tmp7, tmp5 + tmp6, tmp4 + tmp6, tmp5 + tmp7
+    z5 = (z3 + z4) * 9633
+    tmp4, tmp5, tmp6, tmp7 = tmp4 * 2446, tmp5 * 16819, tmp6 * 25172, tmp7 * 12299
+    z1, z2, z3, z4 = z1 * -7373, z2 * -20995, z3 * -16069 + z5, z4 * -3196 + z5
+    return np.stack([o0, ds(tmp7 + z1 + z4), o2, ds(tmp6 + z2 + z3), o4, ds(tmp5 + z2 + z4), o6, ds(tmp4 + z1 + z3)])
+
+
+def _forward_plane(p, qt):
+    """A sample plane u8-valued [8 bh, 8 bw] -> quantised blocks int16 [bh, bw, 64] (natural order): minus 128, rows, columns, then
+    jcdctmgr.c's division by 8 q, halves rounded away from zero."""
+    bh, bw = p.shape[0] // 8, p.shape[1] // 8
+    x = p.astype(np.int64).reshape(bh, 8, bw, 8).transpose(3, 0, 2, 1) - 128   # [col, bh, bw, row]
+    x = _fdct_1d(x, True)                                                      # [u, bh, bw, row]
+    x = _fdct_1d(x.transpose(3, 1, 2, 0), False)                               # [v, bh, bw, u]
+    x = x.transpose(1, 2, 0, 3).reshape(bh, bw, 64)
+    q8 = qt.astype(np.int64).reshape(1, 1, 64) * 8
+    return (np.sign(x) * ((np.abs(x) + (q8 >> 1)) // q8)).astype(np.int16)
+
+
+def _edge(a, rows, cols):
+    """`a` with its last row and column repeated out to [rows, cols]."""
+    return a[np.minimum(np.arange(rows), a.shape[0] - 1)][:, np.minimum(np.arange(cols), a.shape[1] - 1)]
+
+
+def forward_numpy(images, quality: int = 95, subsampling: int = 2):
+    """avcer_jpeg_forward stated in numpy (for the tests; not a product path): RGB images u8 [h, w, 3] -> (coefficients int16
+    [blocks, 64] in the layout of avcer_jpeg_entropy_batch, DESC records).  libjpeg's forward path: jccolor.c (16-bit fixed point),
+    jcsample.c (box filter, alternating bias), jcprepct.c's edges, jfdctint.c, jcdctmgr.c, and jccoefct.c's dummy blocks."""
+    desc = plan_numpy([(im.shape[1], im.shape[0]) for im in images], quality, subsampling)
+    out = np.zeros((int((desc["coef_block"] + desc["n_blocks"]).max()) if len(desc) else 0, 64), dtype=np.int16)
+    for im, d in zip(images, desc):
+        if d["status"] != OK:
+            continue
+        h, w = im.shape[:2]
+        hs, vs = int(d["hs"]), int(d["vs"])
+        r, g, b = (im[..., c].astype(np.int64) for c in range(3))
+        y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16
+        cb = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16
+        cr = (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16
+        at = int(d["coef_block"])
+        bw, bh = int(d["bw"][0]), int(d["bh"][0])
+        yb = _forward_plane(_edge(y, 8 * bh, 8 * bw), d["qt"][0])
+        # dummy blocks -- those that only pad the component to whole MCUs: no AC, the DC of the block coded before them in the MCU.
+        # A real row's dummy (the odd column past the last real one) follows its left neighbour; a dummy row (the odd row past the
+        # last real one) takes, in every block, the DC of the LAST block of the row above in its MCU
+        wb, hb = -(-w // 8), -(-h // 8)
+        for by in range(bh):
+            for bx in range(bw):
+                if by < hb and bx < wb:
+                    continue
+                sy, sx = (by, bx - 1) if by < hb else (by - 1, bx // hs * hs + hs - 1)
+                sx -= sx >= wb
+                yb[by, bx] = 0
+                yb[by, bx, 0] = yb[sy, sx, 0]
+        out[at:at + bw * bh] = yb.reshape(-1, 64)
+        at += bw * bh
+        cw, chh = int(d["bw"][1]), int(d["bh"][1])
+        for c, p in ((1, cb), (2, cr)):
+            # jcprepct.c: the last input row is repeated only to complete the row group (an odd height under 4:2:0), the last
+            # DOWNSAMPLED row is then repeated down to the MCU; columns are repeated before downsampling (expand_right_edge)
+            p = _edge(p, h + (h % vs), 8 * cw * hs)
+            if hs == 2 and vs == 1:
+                p = (p[:, 0::2] + p[:, 1::2] + (np.arange(8 * cw) & 1)[None]) >> 1
+            elif hs == 2:
+                p = (p[0::2, 0::2] + p[0::2, 1::2] + p[1::2, 0::2] + p[1::2, 1::2] + (1 + (np.arange(8 * cw) & 1))[None]) >> 2
+            out[at:at + cw * chh] = _forward_plane(_edge(p, 8 * chh, 8 * cw), d["qt"][c]).reshape(-1, 64)
+            at += cw * chh
+    return out, desc
+
+
+def quant_tables(lib, quality: int) -> np.ndarray:
+    """avcer_jpeg_quant_tables: u16 [2, 64], luma and chroma, natural order."""
+    qt = np.zeros((2, 64), dtype=np.uint16)
+    rc = lib.avcer_jpeg_quant_tables(int(quality), qt.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise ValueError(f"avcer_jpeg_quant_tables({quality}) failed: {rc}")
+    return qt
+
+
+def plan(lib, sizes, quality: int = 95, subsampling: int = 2, desc: np.ndarray | None = None):
+    """avcer_jpeg_plan: image sizes [(w, h)] -> (DESC records, written into `desc[:n]` when given; the blocks they need together)."""
+    sizes = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32).reshape(-1, 2))
+    n = len(sizes)
+    desc = np.zeros(n, dtype=DESC) if desc is None else desc
+    assert desc.dtype == DESC and desc.flags.c_contiguous and len(desc) >= n
+    need = C.c_int64(0)
+    rc = lib.avcer_jpeg_plan(sizes.ctypes.data_as(C.c_void_p), n, int(subsampling), int(quality), desc.ctypes.data_as(C.c_void_p),
+                             C.byref(need))
+    if rc != 0:
+        raise ValueError(f"avcer_jpeg_plan failed: {rc} (quality {quality} in 1..100, subsampling {subsampling} in 0, 1, 2)")
+    return desc[:n], int(need.value)
+
+
+def write_batch(lib, coeffs: np.ndarray, desc: np.ndarray, out: np.ndarray, threads: int = 0, ctx=None, cap_bytes: int | None = None):
+    """avcer_jpeg_write_batch: the coefficient storage and DESC records -> the files back to back in `out` (u8, room for `cap_bytes`,
+    default all of it).  Returns (offsets i64 [n + 1], the bytes all files need together); `desc` gets the status and reason of a
+    file that was not written."""
+    n = len(desc)
+    cap = out.size if cap_bytes is None else int(cap_bytes)
+    assert coeffs.dtype == np.int16 and coeffs.flags.c_contiguous and desc.dtype == DESC and desc.flags.c_contiguous
+    assert out.dtype == np.uint8 and out.flags.c_contiguous and cap <= out.size
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    need = C.c_int64(0)
+    rc = lib.avcer_jpeg_write_batch(ctx, coeffs.ctypes.data_as(C.c_void_p), desc.ctypes.data_as(C.c_void_p), n,
+                                    out.ctypes.data_as(C.c_void_p), cap, offsets.ctypes.data_as(C.c_void_p), host_threads(int(threads)),
+                                    C.byref(need))
+    if rc != 0:
+        raise RuntimeError(f"avcer_jpeg_write_batch failed: {rc}")
+    return offsets, int(need.value)
+
+
+def _encode_rects(src, rects) -> np.ndarray:
+    """`rects` as int32 [n,5] = (slot, x0, y0, x1, y1), checked against `src` [N,H,W,3]: a zero-area rectangle or one that leaves
+    its frame raises ValueError naming the image."""
+    r = np.ascontiguousarray(np.asarray(rects.cpu() if torch.is_tensor(rects) else rects, dtype=np.int64).reshape(-1, 5))
+    n_src, h, w = (int(v) for v in src.shape[:3])
+    for i, (slot, x0, y0, x1, y1) in enumerate(r):
+        if x1 <= x0 or y1 <= y0:
+            raise ValueError(f"image {i}: empty rectangle ({x0}, {y0}, {x1}, {y1})")
+        if not (0 <= slot < n_src and 0 <= x0 and x1 <= w and 0 <= y0 and y1 <= h):
+            raise ValueError(f"image {i}: rectangle ({x0}, {y0}, {x1}, {y1}) of slot {slot} leaves the source [{n_src},{h},{w},3]")
+    return r.astype(np.int32)
+
+
+def encode_images(engine, src, rects, bgr: bool = False, quality: int = 95, subsampling: int = 2, threads: int = 0) -> list:
+    """JPEG files of n images cut out of `src` (u8 [N,H,W,3], moved to the device if it is not there): image i is the half-open
+    rectangle rects[i] = (slot, x0, y0, x1, y1).  Returns the n files as bytes, byte-identical to
+    PIL.Image.fromarray(rgb).save(f, "JPEG", quality=quality, subsampling=subsampling).  plan (host) -> descriptors to the device
+    -> avcer_jpeg_forward -> coefficients into the pinned staging of the engine -> avcer_jpeg_write_batch (host threads)."""
+    src = src if torch.is_tensor(src) else torch.from_numpy(np.array(src))  # a copy: torch.from_numpy wants a writable array
+    if src.dim() != 4 or src.shape[-1] != 3 or src.dtype != torch.uint8:
+        raise ValueError("src must be uint8 [N,H,W,3]")
+    r = _encode_rects(src, rects)
+    n = len(r)
+    if n == 0:
+        return []
+    dev = engine.device
+    st = engine.__dict__.setdefault("_jpeg_staging", _Staging())
+    sizes = np.stack([r[:, 3] - r[:, 1], r[:, 4] - r[:, 2]], axis=1)
+    st.reserve(int(((sizes[:, 0].astype(np.int64) + 15) // 8 * ((sizes[:, 1] + 15) // 8)).sum()) * 3, n)  # an upper bound of the plan
+    desc, blocks = plan(engine.lib, sizes, quality, subsampling, st.desc.numpy()[:DESC.itemsize * n].view(DESC))
+    if (desc["status"] != OK).any():
+        i = int(np.nonzero(desc["status"] != OK)[0][0])
+        raise ValueError(f"image {i}: {int(desc['width'][i])} x {int(desc['height'][i])} pixels cannot be a JPEG file (1..65535 a side)")
+    host = desc.copy()
+    d_dev = st.desc[:DESC.itemsize * n].to(dev, non_blocking=True)
+    r_dev = torch.from_numpy(r).to(dev)
+    coeffs = engine.jpeg_forward(src.to(dev).contiguous(), r_dev, d_dev, n, blocks, bgr=bgr)
+    st.coeffs[:64 * blocks].copy_(coeffs[:64 * blocks], non_blocking=True)
+    st.event = torch.cuda.Event()
+    st.event.record(torch.cuda.current_stream(dev))
+    st.event.synchronize()  # the coefficients are on the host: the one wait of this call
+    c_host = st.coeffs.numpy()[:64 * blocks]
+    # a block of a photograph costs some 17 bytes at quality 95 (untouched pages of the buffer cost nothing); grow and repeat when
+    # the guess was short
+    out = np.empty(HEADER_BYTES * n + 40 * blocks, dtype=np.uint8)
+    while True:
+        d = host.copy()
+        offsets, need = write_batch(engine.lib, c_host, d, out, threads, engine.ctx)
+        if not (d["reason"] == R_NO_SPACE).any():
+            break
+        out = np.empty(need, dtype=np.uint8)
+    if (d["status"] != OK).any():
+        i = int(np.nonzero(d["status"] != OK)[0][0])
+        raise RuntimeError(f"image {i} was not written: reason {int(d['reason'][i])} (csrc/jpeg.hip R_*)")
+    return [out[offsets[i]:offsets[i + 1]].tobytes() for i in range(n)]

@@ -19,7 +19,7 @@ import torch
 from . import io_formats
 from .audio_pipeline import audio_forward, replicate_per_frame, resample_plan
 from .engine import MODE_DEFAULT
-from .face_tiles import VideoTiler, track_clip
+from .face_tiles import VideoTiler, track_clip, write_face_crops
 from .fusion import MODEL_ORDER, fuse
 from .video_pipeline import visual_forward
 
@@ -28,7 +28,8 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
                   path_save_results: str = "", name_video: str = "video", flag_save_prob: bool = False,
                   weights_prob_model=None, weights_model=(1, 1, 1), ce_weights_type: bool = True, ce_mask: bool = False,
                   sr: int = 16000, window: float = 4, step: float = 0.5, padding: str = "mean", mode: int = MODE_DEFAULT,
-                  flag_heatmaps: bool = False, model_heatmaps: str = "static", wav_sr: Optional[int] = None):
+                  flag_heatmaps: bool = False, model_heatmaps: str = "static", wav_sr: Optional[int] = None,
+                  path_save_faces: Optional[str] = None):
     """engine: an `Engine` with the static, dynamic and audio weights loaded.  frames_bgr u8 [T,H,W,3] as cv2 decodes
     them; wav float32 [L] mono at `sr`; fps as `int(cv2.CAP_PROP_FPS)` gives it (get_face_images.py:23).
     `wav_sr`: `wav` is source audio at that rate instead -- int16 [L] / [L, C] as the frames lie in the WAV file ffmpeg writes
@@ -45,7 +46,10 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
     class the static or the dynamic model (`model_heatmaps`) chose; the base image is the crop cut from the frames on the device
     and resized with cv2's INTER_LINEAR.  Written as `<path_save_results>/<name_video>/heatmaps_<model>/NNNNNN.jpg` when
     `path_save_results` is given.  A `model_heatmaps` other than "static" / "dynamic" raises ValueError before any work (the
-    reference dies with UnboundLocalError at its first heat-map frame)."""
+    reference dies with UnboundLocalError at its first heat-map frame).
+    `path_save_faces`: stage 0's output on disk as well (get_face_images.py:52-63): every detection's crop as
+    `<path_save_faces>/<name_video>/<track:02d>/<frame:06d>.jpg`, encoded from the frames on the device
+    (face_tiles.write_face_crops); `out["face_files"]` lists the paths in record order.  Off by default."""
     if flag_heatmaps:
         from . import heatmaps as hm
 
@@ -84,6 +88,8 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
             if "clip" not in host:
                 dets = detections if detections is not None else detector.batch(frames, rgb=False)  # get_face_images.py:49
                 records, tiles = VideoTiler(engine).process(frames, dets)
+                if path_save_faces:
+                    host["face_files"] = write_face_crops(engine, frames, records, path_save_faces, name_video)
                 if not (len(records) and (records[:, 1] == 0).any()):
                     raise FileNotFoundError("no face track 00 (os.listdir(<faces>/00) fails in the reference, get_prob_video.py:79)")
                 host["records"] = records
@@ -130,10 +136,12 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
     out = {name.lower(): am[i] for i, name in enumerate(MODEL_ORDER)}
     out.update(compound_prob=prob.cpu().numpy(), static_probs=static_probs.cpu().numpy(),
                dynamic_logits=dynamic_logits.cpu().numpy(), audio_rows=rows, audio_frames=aud_frames, records=records)
+    if "face_files" in host:
+        out["face_files"] = host["face_files"]
     if maps is not None:
         out["heatmaps"] = (maps[0].astype(np.int32), maps[1].cpu().numpy())
         if path_save_results:
-            hm.write_heatmaps(hm.heatmap_dir(path_save_results, name_video, model_heatmaps), maps[0], maps[1])
+            hm.write_heatmaps(hm.heatmap_dir(path_save_results, name_video, model_heatmaps), maps[0], maps[1], engine=engine)
     # "Real-time factor for compound expression prediction" as run.py:304-307 prints it: elapsed / video duration (the
     # device -> host copies above have synchronised the stream, so the clock covers all the work); None where the
     # container reported no frame rate

@@ -254,7 +254,7 @@ def preprocess_video_and_predict(engine: Engine, path_images: str = "", save_pat
 
         stat, dyn, imgs = engine.guarded(mode, call)
         if imgs is not None:
-            hm.write_heatmaps(hm.heatmap_dir(save_path, os.path.basename(path_images), model_heatmaps), frame_idx, imgs)
+            hm.write_heatmaps(hm.heatmap_dir(save_path, os.path.basename(path_images), model_heatmaps), frame_idx, imgs, engine=engine)
         if flag_save_prob:
             io_formats.write_visual_csvs(stat, dyn, save_path, os.path.basename(path_images))
         return dyn.cpu().numpy(), stat.cpu().numpy()

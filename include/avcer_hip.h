@@ -79,7 +79,9 @@ enum {
  *      avcer_s3fd_num_priors, avcer_s3fd_detect and the kernel-level entries avcer_s3fd_stem, avcer_maxpool2, avcer_s3fd_head (the
  *      S3FD detector: avcer_load_face / avcer_face_forward take its blob as kind 3) joined under 8 the same way.
  *      avcer_jpeg_probe, avcer_jpeg_entropy_batch, avcer_jpeg_tiles, avcer_jpeg_rgb and their descriptor struct (JPEG crop files
- *      decoded behind a host entropy pass) joined under 8 the same way. */
+ *      decoded behind a host entropy pass) joined under 8 the same way.
+ *      avcer_jpeg_quant_tables, avcer_jpeg_plan, avcer_jpeg_forward, avcer_jpeg_write_batch (the same files WRITTEN: forward pass
+ *      on the device, entropy coding on the host) joined under 8 the same way: four more symbols, the descriptor unchanged. */
 #define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
@@ -370,7 +372,7 @@ int avcer_track_faces(avcer_ctx* ctx, const float* dets_host, int ld, const int3
                       int frame_h, double iou_threshold, double minimum_face_size, int64_t* records_host, int64_t* n_records);
 int avcer_lsap(int nr, int nc, const double* cost_host, int32_t* rows_host, int32_t* cols_host);
 
-/* JPEG face crops: the files stage 0 writes and stage 1 reads back,
+/* JPEG face crops, decoding: the files stage 0 writes and stage 1 reads back,
  *   ref: data/get_face_images.py:52-63 (cv2.imwrite of `<faces>/<track>/NNNNNN.jpg`), get_prob_video.py:79-100 (the read loop),
  *        data/utils.py:34 (PIL NEAREST resize to 224 x 224)
  * decoded without a decoder library, split where the work changes kind: marker parsing and Huffman decoding on the HOST
@@ -427,6 +429,48 @@ int avcer_jpeg_tiles(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_blocks, co
                      uint8_t* tiles, avcer_stream_t stream);
 int avcer_jpeg_rgb(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_blocks, const avcer_jpeg_desc* desc, int n, int32_t* flags,
                    uint8_t* canvas, int hmax, int wmax, avcer_stream_t stream);
+
+/* The other direction: the JPEG wire format between stages 0 and 1 is written by this library as well as read.  The face folders
+ * of stage 0 and the heat maps,
+ *   ref: data/get_face_images.py:52-63 (cv2.imwrite of every detection's crop), get_prob_video.py:154 (cv2.imwrite of an overlay)
+ * encoded without an encoder library, split at the same place: colour conversion, chroma downsampling, the forward DCT and the
+ * quantisation on the DEVICE (avcer_jpeg_forward, one launch per batch, images cut straight out of the decoded frames), headers
+ * and Huffman coding on the HOST (avcer_jpeg_quant_tables, avcer_jpeg_plan, avcer_jpeg_write_batch: host code and host pointers,
+ * ctx may be NULL, no device is touched).  The arithmetic is libjpeg's -- 16-bit fixed-point RGB -> YCbCr, the box filter with
+ * its alternating bias, the "islow" forward DCT, division by 8 q with halves away from zero -- and the contract is BYTE-identity
+ * with PIL.Image.fromarray(rgb).save(f, "JPEG", quality=quality, subsampling=subsampling) (libjpeg-turbo): a tolerance of zero,
+ * independent of the arithmetic mode.
+ *
+ * Written: baseline, three components YCbCr, luma sampling 1x1 / 2x1 / 2x2 (`subsampling` 0 / 1 / 2, PIL's numbering), quality
+ * 1..100, the standard Huffman tables, one scan, a JFIF 1.01 header.  Not written: grey, optimised tables, restart markers,
+ * progressive files, EXIF and comments.
+ *
+ * Both directions share avcer_jpeg_desc and the coefficient layout.  Edges follow jcprepct.c: columns repeat the last pixel,
+ * luma rows the last row; chroma rows under 2x2 repeat the last input row only to make the height even and the last DOWNSAMPLED
+ * row from there down.  Dummy blocks (those that only pad luma to whole MCUs) are final when avcer_jpeg_forward returns: zero AC
+ * and the DC of the block libjpeg codes before them in the MCU (jccoefct.c); avcer_jpeg_write_batch codes what it is given.
+ *
+ * avcer_jpeg_quant_tables: jpeg_set_quality(quality, force_baseline) -> qt[0] luma, qt[1] chroma, natural order.
+ * avcer_jpeg_plan: n image sizes (sizes[2 i] = width, sizes[2 i + 1] = height) -> desc[n] as the decoder's entropy pass would
+ *   fill them for the files to be written (ncomp 3, hs / vs, MCU-padded bw / bh, tq 0 1 1, qt); images take consecutive blocks in
+ *   image order, so coef_block ascends; *blocks_needed (may be NULL) = their sum.  A width or height of zero or above 65535:
+ *   AVCER_JPEG_NOT_HANDLED, reason 18, no blocks.
+ * avcer_jpeg_forward: image i is the half-open rectangle rects[i] = (slot, x0, y0, x1, y1) (device i32 [n,5]; x1 - x0 and y1 - y0
+ *   are desc[i].width and .height) of src u8 [N,H,W,3] (RGB, or BGR with bgr != 0); desc[n] as avcer_jpeg_plan wrote them, copied
+ *   to the device (16-byte aligned, as coeffs) -> coeffs int16 [n_blocks, 64].  One kernel on `stream`, no synchronisation with
+ *   the host.  Coordinates are clamped to the tensor: a wrong rectangle yields wrong pixels, never a read outside src.
+ * avcer_jpeg_write_batch: coeffs and desc[n] on the HOST -> the files, back to back in out (room for cap_bytes); file i is
+ *   out[offsets[i] .. offsets[i + 1]) (offsets host i64 [n + 1]).  Files are written independently on min(16, threads) host
+ *   threads, threads <= 0: 16 -- never the machine's core count; the result does not depend on the thread count.  A file that
+ *   is not written has no bytes and its desc[i] turns AVCER_JPEG_NOT_HANDLED with the reason: 12 = it does not fit cap_bytes
+ *   (*bytes_needed, may be NULL, = what all files need together; nothing is written past cap_bytes), 16 = a coefficient the
+ *   standard tables cannot code, 19 = a descriptor avcer_jpeg_plan did not write.  desc[i] already NOT_HANDLED is skipped. */
+int avcer_jpeg_quant_tables(int quality, uint16_t qt[2][64]);
+int avcer_jpeg_plan(const int32_t* sizes_host, int n, int subsampling, int quality, avcer_jpeg_desc* desc_host, int64_t* blocks_needed);
+int avcer_jpeg_forward(avcer_ctx* ctx, const uint8_t* src, int N, int H, int W, const int32_t* rects, const avcer_jpeg_desc* desc, int n,
+                       int bgr, int16_t* coeffs, int64_t n_blocks, avcer_stream_t stream);
+int avcer_jpeg_write_batch(avcer_ctx* ctx, const int16_t* coeffs_host, avcer_jpeg_desc* desc_host, int n, uint8_t* out_host,
+                           int64_t cap_bytes, int64_t* offsets_host, int threads, int64_t* bytes_needed);
 
 /* Probability fusion and compound-expression rule.
  *   ref: run.py:25-165 (get_c_expr_db_pred), data/utils.py:125-127 (softmax), :222-241 (get_compound_expression)
