@@ -9,6 +9,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/avcer_hip.h"
@@ -32,6 +33,17 @@ struct Storage { int kind; size_t es; };  // es: bytes per element
 inline Storage mode_storage(int mode) {
     return mode == AVCER_MODE_BF16 ? Storage{KIND_BF16, 2} : Storage{mode == AVCER_MODE_F16X3 ? KIND_SP32 : KIND_F32, 4};
 }
+// A kind as an element type, for the launchers: with_storage<Ts...>(kind, f) calls f(storage_tag<T>{}) with the T among Ts that
+// stores `kind` (float / bf16_t / sp32_t of split_dev.h), so a launcher writes its launch expression once, on
+// `typename decltype(tag)::type`.  Ts are the storages the kernel is built for; a launcher that takes fewer than three rejects
+// the others in front, and any kind that is left goes to the first of Ts, as the last `else` of a hand-written chain did.
+struct sp32_t;
+template <typename T> struct storage_tag { using type = T; };
+template <typename T> constexpr int storage_kind = std::is_same<T, bf16_t>::value ? KIND_BF16 : std::is_same<T, sp32_t>::value ? KIND_SP32 : KIND_F32;
+template <typename T0, typename... Ts, typename F> void with_storage(int kind, F&& f) {
+    if (!((kind == storage_kind<Ts> ? (f(storage_tag<Ts>{}), true) : false) || ...)) f(storage_tag<T0>{});
+}
+template <typename F> void with_storage(int kind, F&& f) { with_storage<float, bf16_t, sp32_t>(kind, f); }
 
 // One packed tensor of a weight blob, resident on the device in f32 and (lazily) in bf16.
 struct Tensor {
@@ -118,8 +130,21 @@ inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 int ws_reserve(avcer_ctx* ctx, int slot, size_t bytes, void** out);
 
 // PIL's NEAREST resize to 224 (data/utils.py:34): the source index of output index `o` along an axis of `len` source pixels.
-// The one statement of the rule: crop_tiles_kernel (kernels.hip) and jpeg_tiles_kernel (jpeg.hip) both call it.
+// The one statement of the rule: preprocess_kernel, crop_tiles_kernel (kernels.hip) and jpeg_tiles_kernel (jpeg.hip) call it.
 __device__ __forceinline__ int nearest_src(int o, int len) { return min((int)(((double)o + 0.5) * ((double)len / 224.0)), len - 1); }
+
+// Rounds a grid of 256-thread blocks takes on the chip's block slots (two per CU: `slots` = 2 x the CU count the context
+// read from the device at creation, 512 on a whole MI355X), as the form / tile choices model them.
+// Calibrated on tools/ab_layers.py (profiles/r03_ab_layers*.txt, 128- against 112-row tiles of the same layer): a grid of
+// at most one block per CU runs in 0.62 of a round (a block alone on its CU is that much faster); behind whole rounds, a
+// partial round that still fits one block per CU (fraction f <= 0.5) costs 0.25 + 0.7 f -- the whole rounds end ragged and
+// absorb part of it --, a larger one a whole round (some CU runs two blocks from start to end).
+inline double grid_rounds(long tiles, long slots) {
+    const long whole = tiles / slots, rest = tiles % slots;
+    if (whole == 0) return 2 * tiles <= slots ? 0.62 : 1.0;
+    const double f = (double)rest / (double)slots;
+    return (double)whole + (rest == 0 ? 0.0 : (2 * rest <= slots ? 0.25 + 0.7 * f : 1.0));
+}
 
 // ---- gemm.hip
 int launch_conv_gemm(avcer_ctx* ctx, const avcer_conv_desc& d, int dtype, const void* x, const void* w,
@@ -143,19 +168,6 @@ int launch_stem_pool_face(avcer_ctx* ctx, const uint8_t* frames, int h, int w, i
 // conv2 + conv3 (+ residual) of one bottleneck and conv1 of the next block (t1n / w1n null when there is none);
 // ds_cin = 0: x [M][4 planes] is the residual; ds_cin = 64: x [M][64] is the downsample operand and w3 is [4 planes][planes + 64];
 // all activations sp32, weights split-fp16 (scaled, row-permuted) with the BN scale folded in (packing.py: *.wf, c3d.w)
-// Rounds a grid of 256-thread blocks takes on the chip's block slots (two per CU: `slots` = 2 x the CU count the context
-// read from the device at creation, 512 on a whole MI355X), as the form / tile choices model them.
-// Calibrated on tools/ab_layers.py (profiles/r03_ab_layers*.txt, 128- against 112-row tiles of the same layer): a grid of
-// at most one block per CU runs in 0.62 of a round (a block alone on its CU is that much faster); behind whole rounds, a
-// partial round that still fits one block per CU (fraction f <= 0.5) costs 0.25 + 0.7 f -- the whole rounds end ragged and
-// absorb part of it --, a larger one a whole round (some CU runs two blocks from start to end).
-inline double grid_rounds(long tiles, long slots) {
-    const long whole = tiles / slots, rest = tiles % slots;
-    if (whole == 0) return 2 * tiles <= slots ? 0.62 : 1.0;
-    const double f = (double)rest / (double)slots;
-    return (double)whole + (rest == 0 ? 0.0 : (2 * rest <= slots ? 0.25 + 0.7 * f : 1.0));
-}
-
 // w2_frags: the conv2 weights once more in MFMA fragment order (k_weight_frags), or null: selects the spatial-tile form
 // where it applies (planes 64, 55 x 55 images, a next conv1)
 int launch_bneck(avcer_ctx* ctx, int planes, int nb, int h, int w, const void* t1, const void* x, int ds_cin, int out_step,
@@ -191,8 +203,6 @@ int launch_mnet_conv(avcer_ctx* ctx, int ks, const float* x, const float* wt, co
 // u8 frames [n, h, w, 3] -> conv1_1 3x3 pad 1 (3 -> 64) of RGB pixel - (123, 117, 104) + bias + ReLU: y [n, h, w, 64]; wt [27][64]
 int launch_s3fd_stem(avcer_ctx* ctx, const uint8_t* frames, int n, int h, int w, int rgb, const float* wt, const float* b, void* y, int kind,
                      hipStream_t st);
-// 2x2 / 2 max-pool, NHWC: y [n, h / 2, w / 2, c], or [n, ceil(h / 2), ceil(w / 2), c] with ceil_mode
-int launch_maxpool2(avcer_ctx* ctx, const void* x, void* y, int n, int h, int w, int c, int ceil_mode, int kind, hipStream_t st);
 // one level's loc + conf 3x3 convolutions, max-out (n_out 8) and softmax: x [nb, h, w, c], wt [9][c][n_out], rows written at
 // f * P + row0; inv: scratch for nb * h * w inverse L2 norms (the level is normalised) or null (it is not)
 int launch_s3fd_head(avcer_ctx* ctx, const void* x, int kind, float* inv, const float* wt, const float* b, int nb, int h, int w, int c,
@@ -205,10 +215,12 @@ int launch_s3fd_detect(avcer_ctx* ctx, const float* loc, const float* conf, cons
 
 int measure_ceilings(avcer_ctx* ctx, double* mfma_bf16_tflops, double* hbm_copy_tbs, hipStream_t st);
 
-// ---- kernels.hip (element-wise / reduction kernels; T selects f32 (0) or bf16 (1) activations)
-// kind: 0 = f32 [n,230,230,4], 1 = bf16, 3 = planar fp16 hi / lo (two [n,230,230,4] planes, the stem_pool input)
+// ---- kernels.hip (element-wise / reduction kernels; `kind` / `*_kind` = KIND_F32, KIND_BF16 or KIND_SP32, the storage of the activations)
+// u8 frames -> the zero-bordered image [n,230,230,4] of the stem; kind: KIND_F32 or KIND_BF16
 int k_preprocess(avcer_ctx*, const uint8_t* frames, int n, int in_h, int in_w, void* out, int kind, hipStream_t);
-int k_maxpool3s2(avcer_ctx*, const void* x, void* y, int n, int h, int w, int c, int oh, int ow, int kind, hipStream_t);
+// k x k / 2 max-pool with padding `pad` (0 or 1), NHWC: x [n, h, w, c] -> y [n, oh, ow, c], oh / ow the caller's (floor or ceil); a tap
+// outside the input does not exist.  Built for what is called: k = 2 on f32 / sp32 (S3FD), k = 3 on f32 / bf16 (the two ResNet stems)
+int k_maxpool(avcer_ctx*, const void* x, void* y, int n, int h, int w, int c, int k, int pad, int oh, int ow, int kind, hipStream_t);
 int k_avgpool_hw(avcer_ctx*, const void* x, float* y, void* y_sp32, int n, int hw, int c, int kind, hipStream_t);
 // Grad-CAM of layer 4 for all 7 classes (kernels.hip): x = layer 4's output [n,7,7,2048] in storage `kind`, probs [n,7],
 // h = fc1's pre-ReLU output [n,512], w1 = fc1.w [512,2048], w2 = fc2.w [7,512], g = scratch f32 [n,7,2048] -> cam f32 [n,7,49]
@@ -238,6 +250,8 @@ int k_fuse_videos(avcer_ctx*, const float* stat, const float* dyn, const float* 
                   const int32_t* frame_off, const int32_t* win_off, const int32_t* n_aud, int n_videos, int n, int n_win, int c,
                   const double* w, int has_w1, int cwt, int cmask, float* aud_mean, int32_t* count, double* comp_prob,
                   int32_t* comp_argmax, hipStream_t);
+// the same image from a preprocessed f32 tensor [n,3,224,224]; kind: KIND_F32, KIND_BF16, or 3 = planar fp16 hi / lo (two
+// [n,230,230,4] planes, the stem_pool input)
 int k_pack_nchw(avcer_ctx*, const float* x, int n, void* out, int kind, hipStream_t);
 int k_gather_windows(avcer_ctx*, const float* feats, const int32_t* idx, int nwin, float* out, hipStream_t);
 int k_audio_chunks(avcer_ctx*, const float* wav, const int32_t* starts, const int32_t* ends, int n, int window, int mode,
@@ -250,7 +264,6 @@ int k_face_decode(avcer_ctx*, const float* loc, const float* conf, const float* 
 int k_face_nms(avcer_ctx*, const float* dets, int T, int P, float conf_thresh, float nms_thresh, int nms_top_k, int top_k,
                float threshold, int32_t* order, int32_t* count, float* out, int32_t* out_n, hipStream_t);
 int k_face_pre(avcer_ctx*, const uint8_t* frames, int n, int h, int w, int ph, int pw, int rgb, void* out, int bf16, hipStream_t);
-int k_maxpool3s2p1(avcer_ctx*, const void* x, void* y, int n, int h, int w, int c, int oh, int ow, int kind, hipStream_t);
 int k_upsample_add(avcer_ctx*, void* y, const void* coarse, int n, int h, int w, int ch, int cw, int c, int kind, hipStream_t);
 int k_face_head(avcer_ctx*, const float* hd, int ld, int n, int hw, int row0, int P, float* loc, float* conf, float* landms,
                 hipStream_t);

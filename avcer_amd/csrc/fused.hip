@@ -245,7 +245,7 @@ __global__ void __launch_bounds__(256, 2) stem_pool_kernel(const StemParams p) {
 // (4 py0 - 5, 4 px0 - 5); stem row -1 / column -1 and those past the map are the pool's padding and are skipped).  The net's
 // input is pixel - (104, 117, 123): INTEGER means, so the mean-subtracted value itself is exact in fp16 -- no lo half, two
 // MFMAs per product, zero padding is exactly zero and no border classes are needed (the BN shift is the plain one).
-// Replaces face_pre_kernel + the f32-input stem contraction + maxpool3s2p1_kernel: 0.9 + 7.9 + 3.2 ms per 750 frames of
+// Replaces face_pre_kernel + the f32-input stem contraction + the padded 3x3 / 2 max-pool (maxpool_kernel): 0.9 + 7.9 + 3.2 ms per 750 frames of
 // 640 x 360 (profiles/r06_face_trace_before_stem.txt), the stem map [n,180,320,64] written and read once each for nothing.
 template <bool FACE>
 __global__ void __launch_bounds__(256, 3) stem_pool_u8_kernel(const StemParams p) {

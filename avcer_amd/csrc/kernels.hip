@@ -41,12 +41,8 @@ __global__ void preprocess_kernel(const uint8_t* __restrict__ in, T* __restrict_
     const int b = idx / ((long)PP * PP);
     float v[4] = {0.f, 0.f, 0.f, 0.f};
     if (y >= 2 && y < 226 && x >= 2 && x < 226) {
-        int sy = y - 2, sx = x - 2;
-        if (in_h != 224 || in_w != 224) {  // PIL NEAREST: src = floor((dst + 0.5) * in / out)
-            sy = min((int)(((double)sy + 0.5) * ((double)in_h / 224.0)), in_h - 1);
-            sx = min((int)(((double)sx + 0.5) * ((double)in_w / 224.0)), in_w - 1);
-        }
-        const uint8_t* px = in + (((long)b * in_h + sy) * in_w + sx) * 3;
+        // PIL NEAREST (common.h); at 224 source pixels it is the identity
+        const uint8_t* px = in + (((long)b * in_h + nearest_src(y - 2, in_h)) * in_w + nearest_src(x - 2, in_w)) * 3;
         v[0] = (float)px[2] - 91.4953f;
         v[1] = (float)px[1] - 103.8827f;
         v[2] = (float)px[0] - 131.0912f;
@@ -54,9 +50,9 @@ __global__ void preprocess_kernel(const uint8_t* __restrict__ in, T* __restrict_
     st4<T>(out, idx * 4, v);
 }
 
-// Planar split-fp16 variant (input of stem_pool_kernel): the same zero-bordered image as two fp16 planes
+// Planar split-fp16 store (input of stem_pool_kernel): the same zero-bordered image as two fp16 planes
 // [n,230,230,4], hi = bf16(v) and lo = bf16(v - hi), so that one 8-pixel tap row is 64 contiguous bytes per plane.
-__device__ __forceinline__ void st4_planar(bf16_t* hi, bf16_t* lo, long idx, const float* v, unsigned* ovf = nullptr) {
+__device__ __forceinline__ void st4_planar(bf16_t* hi, bf16_t* lo, long idx, const float* v, unsigned* ovf) {
     float amax = 0.f;
     uint2 h, l;
     sp_split4(v, amax, h, l);
@@ -65,49 +61,10 @@ __device__ __forceinline__ void st4_planar(bf16_t* hi, bf16_t* lo, long idx, con
     *reinterpret_cast<uint2*>(lo + idx * 4) = l;
 }
 
-__global__ void preprocess_planar_kernel(const uint8_t* __restrict__ in, bf16_t* __restrict__ hi, bf16_t* __restrict__ lo, int n,
-                                         int in_h, int in_w) {
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long total = (long)n * PP * PP;
-    if (idx >= total) return;
-    const int x = idx % PP;
-    const int y = (idx / PP) % PP;
-    const int b = idx / ((long)PP * PP);
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-    if (y >= 2 && y < 226 && x >= 2 && x < 226) {
-        int sy = y - 2, sx = x - 2;
-        if (in_h != 224 || in_w != 224) {  // PIL NEAREST: src = floor((dst + 0.5) * in / out)
-            sy = min((int)(((double)sy + 0.5) * ((double)in_h / 224.0)), in_h - 1);
-            sx = min((int)(((double)sx + 0.5) * ((double)in_w / 224.0)), in_w - 1);
-        }
-        const uint8_t* px = in + (((long)b * in_h + sy) * in_w + sx) * 3;
-        v[0] = (float)px[2] - 91.4953f;
-        v[1] = (float)px[1] - 103.8827f;
-        v[2] = (float)px[0] - 131.0912f;
-    }
-    st4_planar(hi, lo, idx, v);
-}
-
-__global__ void pack_nchw_planar_kernel(const float* __restrict__ in, bf16_t* __restrict__ hi, bf16_t* __restrict__ lo, int n,
-                                        unsigned* ovf) {
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long total = (long)n * PP * PP;
-    if (idx >= total) return;
-    const int x = idx % PP;
-    const int y = (idx / PP) % PP;
-    const int b = idx / ((long)PP * PP);
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-    if (y >= 2 && y < 226 && x >= 2 && x < 226) {
-        const long o = (long)b * 3 * 224 * 224 + (long)(y - 2) * 224 + (x - 2);
-        v[0] = in[o]; v[1] = in[o + 224 * 224]; v[2] = in[o + 2 * 224 * 224];
-    }
-    st4_planar(hi, lo, idx, v, ovf);  // arbitrary floats: the one input that can break the fp16 range by itself
-}
-
 // Same zero-bordered image from an ALREADY preprocessed float tensor [n,3,224,224] (the tensor the reference's
-// pth_model_static is called with, get_prob_video.py:103-109).
-template <typename T>
-__global__ void pack_nchw_kernel(const float* __restrict__ in, T* __restrict__ out, int n) {
+// pth_model_static is called with, get_prob_video.py:103-109), in storage T (lo null) or as the two planes out / lo.
+template <typename T, bool PLANAR>
+__global__ void pack_nchw_kernel(const float* __restrict__ in, T* __restrict__ out, T* __restrict__ lo, int n, unsigned* ovf) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long total = (long)n * PP * PP;
     if (idx >= total) return;
@@ -119,7 +76,8 @@ __global__ void pack_nchw_kernel(const float* __restrict__ in, T* __restrict__ o
         const long o = (long)b * 3 * 224 * 224 + (long)(y - 2) * 224 + (x - 2);
         v[0] = in[o]; v[1] = in[o + 224 * 224]; v[2] = in[o + 2 * 224 * 224];
     }
-    st4<T>(out, idx * 4, v);
+    if constexpr (PLANAR) st4_planar(out, lo, idx, v, ovf);  // arbitrary floats: the one input that can break the fp16 range by itself
+    else st4<T>(out, idx * 4, v);
 }
 
 // ------------------------------------------------------------------------------------------------ face stage (row f4)
@@ -417,37 +375,6 @@ __global__ void face_pre_kernel(const uint8_t* __restrict__ in, T* __restrict__ 
     st4<T>(out, idx * 4, v);
 }
 
-// torchvision ResNet max-pool: 3x3, stride 2, padding 1 (padded taps never win); NHWC.
-template <typename T>
-__global__ void maxpool3s2p1_kernel(const T* __restrict__ x, T* __restrict__ y, int n, int h, int w, int c, int oh, int ow) {
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int c4 = c / 4;
-    const long total = (long)n * oh * ow * c4;
-    if (idx >= total) return;
-    const int cc = (idx % c4) * 4;
-    long t = idx / c4;
-    const int ox = t % ow; t /= ow;
-    const int oy = t % oh;
-    const int b = t / oh;
-    float m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    bool nan[4] = {false, false, false, false};
-    for (int dy = 0; dy < 3; ++dy) {
-        const int iy = oy * 2 - 1 + dy;
-        if (iy < 0 || iy >= h) continue;
-        for (int dx = 0; dx < 3; ++dx) {
-            const int ix = ox * 2 - 1 + dx;
-            if (ix < 0 || ix >= w) continue;
-            float v[4];
-            ld4<T>(x, (((long)b * h + iy) * w + ix) * c + cc, v);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { m[j] = fmaxf(m[j], v[j]); nan[j] |= v[j] != v[j]; }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) if (nan[j]) m[j] = NAN;
-    st4<T>(y, (((long)b * oh + oy) * ow + ox) * c + cc, m);
-}
-
 // retina_face_net.py:92-98: y += nearest-upsampled coarser level (F.interpolate(mode="nearest"): src = floor(dst*in/out))
 template <typename T>
 __global__ void upsample_add_kernel(T* __restrict__ y, const T* __restrict__ coarse, int n, int h, int w, int ch, int cw, int c,
@@ -541,30 +468,41 @@ __global__ void audio_chunks_kernel(const float* __restrict__ wav, const int32_t
 }
 
 // ------------------------------------------------------------------------------------------------ pooling
-// video.py:103,117: MaxPool2d(3, stride 2), no padding; NHWC.
-template <typename T>
-__global__ void maxpool3s2_kernel(const T* __restrict__ x, T* __restrict__ y, int n, int h, int w, int c, int oh, int ow) {
+// The one max-pool on NHWC: a K x K window (K 2 or 3) at stride 2 behind `pad` (0 or 1) rows / columns of padding; one thread per
+// output position and 4 channels.  video.py:103,117 MaxPool2d(3, 2); torchvision's ResNet MaxPool2d(3, 2, 1); S3FD's
+// nn.MaxPool2d(2, 2[, ceil_mode=True]) (vgg.16).  oh / ow are the caller's (floor or ceil); a tap outside the input does not
+// exist: it is loaded from the nearest pixel inside, so that the K * K loads are in flight together, and left out of the maximum.
+// Taps in row-major order; a NaN in the window is the result, like torch.
+template <typename T, int K>
+__global__ void maxpool_kernel(const T* __restrict__ x, T* __restrict__ y, int n, int h, int w, int c, int oh, int ow, int pad) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const int c4 = c / 4;
-    const long total = (long)n * oh * ow * c4;
-    if (idx >= total) return;
-    const int cc = (idx % c4) * 4;
+    if (idx >= (long)n * oh * ow * c4) return;
+    const int cc = (int)(idx % c4) * 4;
     long t = idx / c4;
-    const int ox = t % ow; t /= ow;
-    const int oy = t % oh;
-    const int b = t / oh;
+    const int ox = (int)(t % ow); t /= ow;
+    const int oy = (int)(t % oh);
+    const long b = t / oh;
     float m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
     bool nan[4] = {false, false, false, false};
-    for (int dy = 0; dy < 3; ++dy)
-        for (int dx = 0; dx < 3; ++dx) {
-            float v[4];
-            ld4<T>(x, (((long)b * h + oy * 2 + dy) * w + ox * 2 + dx) * c + cc, v);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { m[j] = fmaxf(m[j], v[j]); nan[j] |= v[j] != v[j]; }
+    for (int dy = 0; dy < K; ++dy) {
+#pragma unroll
+        for (int dx = 0; dx < K; ++dx) {
+            const int iy = 2 * oy - pad + dy, ix = 2 * ox - pad + dx;
+            const bool in = iy >= 0 && iy < h && ix >= 0 && ix < w;
+            float v[4];
+            ld4<T>(x, ((b * h + min(max(iy, 0), h - 1)) * w + min(max(ix, 0), w - 1)) * c + cc, v);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {  // selects, no branch around a load: -inf never wins and leaves m's bits alone
+                m[j] = fmaxf(m[j], in ? v[j] : -INFINITY);
+                nan[j] |= in & (v[j] != v[j]);
+            }
         }
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) if (nan[j]) m[j] = NAN;
-    st4<T>(y, (((long)b * oh + oy) * ow + ox) * c + cc, m);
+    st4<T>(y, ((b * oh + oy) * ow + ox) * c + cc, m, nullptr);  // a maximum of stored values: nothing new to count
 }
 
 // video.py:110,124: AdaptiveAvgPool2d((1,1)) over hw positions of an NHWC tensor -> f32 [n,c]
@@ -949,8 +887,9 @@ __global__ void add_pe_kernel(const float* __restrict__ x, const float* __restri
 // 8 waves share one head's K/V image (~105 KiB f32 at S=199): two waves per SIMD hide the LDS latency of the score loop
 constexpr int ATT_WAVES = 8;
 constexpr int ATT_THREADS = ATT_WAVES * 64;
-template <typename T, typename TO, int D>
-__global__ void __launch_bounds__(ATT_THREADS) attention_kernel(const T* __restrict__ qkv, TO* __restrict__ out, int s, int heads,
+// The exact-f32 form (f32 in, f32 out); the bf16 and split-fp16 modes run attention_mfma_kernel below.
+template <int D>
+__global__ void __launch_bounds__(ATT_THREADS) attention_kernel(const float* __restrict__ qkv, float* __restrict__ out, int s, int heads,
                                                       float scale) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     constexpr int KP = D + 4;
@@ -961,13 +900,13 @@ __global__ void __launch_bounds__(ATT_THREADS) attention_kernel(const T* __restr
     const int b = blockIdx.x / heads, h = blockIdx.x % heads;
     const int e = heads * D;
     const long rowstride = 3L * e;
-    const T* base = qkv + (long)b * s * rowstride + h * D;
+    const float* base = qkv + (long)b * s * rowstride + h * D;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     for (int i = tid; i < s * (D / 4); i += ATT_THREADS) {
         const int r = i / (D / 4), c4 = (i % (D / 4)) * 4;
         float kv[4], vv[4];
-        ld4<T>(base, (long)r * rowstride + e + c4, kv);
-        ld4<T>(base, (long)r * rowstride + 2 * e + c4, vv);
+        ld4<float>(base, (long)r * rowstride + e + c4, kv);
+        ld4<float>(base, (long)r * rowstride + 2 * e + c4, vv);
         *reinterpret_cast<float4*>(ks + r * KP + c4) = make_float4(kv[0], kv[1], kv[2], kv[3]);
         *reinterpret_cast<float4*>(vs + r * D + c4) = make_float4(vv[0], vv[1], vv[2], vv[3]);
     }
@@ -975,7 +914,7 @@ __global__ void __launch_bounds__(ATT_THREADS) attention_kernel(const T* __restr
     float* pw = ps + wv * 256;
     float* qw = qs + wv * D;
     for (int qi = wv; qi < s; qi += ATT_WAVES) {
-        if (lane < D) qw[lane] = ldf<T>(base, (long)qi * rowstride + lane) * scale;
+        if (lane < D) qw[lane] = ldf<float>(base, (long)qi * rowstride + lane) * scale;
         __builtin_amdgcn_wave_barrier();
         float sc[4];
         float mx = -INFINITY;
@@ -1014,7 +953,7 @@ __global__ void __launch_bounds__(ATT_THREADS) attention_kernel(const T* __restr
             for (int j = half; j < s; j += 2) o += pw[j] * vs[j * D + c];
             o += __shfl_xor(o, 32, 64);
         }
-        if (lane < D) stf<TO>(out, ((long)b * s + qi) * e + h * D + lane, o / den);
+        if (lane < D) stf<float>(out, ((long)b * s + qi) * e + h * D + lane, o / den);
         __builtin_amdgcn_wave_barrier();
     }
 }
@@ -1546,22 +1485,28 @@ __global__ void fuse_videos_kernel(const float* __restrict__ stat, const float* 
 
 int k_preprocess(avcer_ctx* ctx, const uint8_t* frames, int n, int in_h, int in_w, void* out, int kind, hipStream_t st) {
     const long total = (long)n * PP * PP;
-    if (kind == 3)
-        preprocess_planar_kernel<<<cdiv(total, 256), 256, 0, st>>>(frames, (bf16_t*)out, (bf16_t*)out + total * 4, n, in_h, in_w);
-    else if (kind == 1) preprocess_kernel<bf16_t><<<cdiv(total, 256), 256, 0, st>>>(frames, (bf16_t*)out, n, in_h, in_w);
-    else preprocess_kernel<float><<<cdiv(total, 256), 256, 0, st>>>(frames, (float*)out, n, in_h, in_w);
+    with_storage<float, bf16_t>(kind, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        preprocess_kernel<T><<<cdiv(total, 256), 256, 0, st>>>(frames, (T*)out, n, in_h, in_w);
+    });
     CHECK_LAUNCH(ctx, "preprocess");
     return AVCER_OK;
 }
 
-// `kind` of activation storage: 0 = f32, 1 = bf16, 2 = sp32
-int k_maxpool3s2(avcer_ctx* ctx, const void* x, void* y, int n, int h, int w, int c, int oh, int ow, int kind, hipStream_t st) {
-    const long total = (long)n * oh * ow * (c / 4);
-    const int grid = cdiv(total, 256);
-    if (kind == 1) maxpool3s2_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)x, (bf16_t*)y, n, h, w, c, oh, ow);
-    else if (kind == 2) maxpool3s2_kernel<sp32_t><<<grid, 256, 0, st>>>((const sp32_t*)x, (sp32_t*)y, n, h, w, c, oh, ow);
-    else maxpool3s2_kernel<float><<<grid, 256, 0, st>>>((const float*)x, (float*)y, n, h, w, c, oh, ow);
-    CHECK_LAUNCH(ctx, "maxpool3s2");
+int k_maxpool(avcer_ctx* ctx, const void* x, void* y, int n, int h, int w, int c, int k, int pad, int oh, int ow, int kind, hipStream_t st) {
+    if (c % 4 || (kind == KIND_SP32 && c % 32)) return set_err(ctx, AVCER_EINVAL, "maxpool%d: %d channels", k, c);
+    if (oh < 1 || ow < 1) return set_err(ctx, AVCER_EINVAL, "maxpool%d: a %d x %d map has no %d x %d window", k, h, w, k, k);
+    // built for what is called: 2 x 2 on f32 / sp32 (S3FD), 3 x 3 on f32 / bf16 (the ResNet stems; in the x3 mode they pool in the stem kernel)
+    if ((k != 2 && k != 3) || pad < 0 || pad > 1 || kind == (k == 2 ? KIND_BF16 : KIND_SP32))
+        return set_err(ctx, AVCER_EINVAL, "maxpool%d: no kernel for padding %d in storage kind %d", k, pad, kind);
+    const int grid = cdiv((long)n * oh * ow * (c / 4), 256);
+    auto launch = [&](auto tag, auto kk) {
+        using T = typename decltype(tag)::type;
+        maxpool_kernel<T, decltype(kk)::value><<<grid, 256, 0, st>>>((const T*)x, (T*)y, n, h, w, c, oh, ow, pad);
+    };
+    if (k == 2) with_storage<float, sp32_t>(kind, [&](auto tag) { launch(tag, std::integral_constant<int, 2>{}); });
+    else with_storage<float, bf16_t>(kind, [&](auto tag) { launch(tag, std::integral_constant<int, 3>{}); });
+    CHECK_LAUNCH(ctx, "maxpool");
     return AVCER_OK;
 }
 
@@ -1571,9 +1516,10 @@ int k_avgpool_hw(avcer_ctx* ctx, const void* x, float* y, void* y_sp32, int n, i
     // 64 threads per block: one frame per call is 256 threads, and four CUs run them in the time of one
     const int grid = cdiv(total, 64);
     sp32_t* ysp = (sp32_t*)y_sp32;
-    if (kind == 1) avgpool_kernel<bf16_t><<<grid, 64, 0, st>>>((const bf16_t*)x, y, ysp, n, hw, c, ctx->ovf);
-    else if (kind == 2) avgpool_kernel<sp32_t><<<grid, 64, 0, st>>>((const sp32_t*)x, y, ysp, n, hw, c, ctx->ovf);
-    else avgpool_kernel<float><<<grid, 64, 0, st>>>((const float*)x, y, ysp, n, hw, c, ctx->ovf);
+    with_storage(kind, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        avgpool_kernel<T><<<grid, 64, 0, st>>>((const T*)x, y, ysp, n, hw, c, ctx->ovf);
+    });
     CHECK_LAUNCH(ctx, "avgpool");
     return AVCER_OK;
 }
@@ -1582,9 +1528,10 @@ int k_cam_maps(avcer_ctx* ctx, const void* x, const float* probs, const float* h
                float* cam, int n, int kind, hipStream_t st) {
     cam_grad_kernel<<<dim3(cdiv(n, CAM_FR), 2048 / 256), 256, 0, st>>>(probs, h, w1, w2, g, n);
     CHECK_LAUNCH(ctx, "cam_grad");
-    if (kind == 1) cam_map_kernel<bf16_t><<<n, 256, 0, st>>>((const bf16_t*)x, g, cam);
-    else if (kind == 2) cam_map_kernel<sp32_t><<<n, 256, 0, st>>>((const sp32_t*)x, g, cam);
-    else cam_map_kernel<float><<<n, 256, 0, st>>>((const float*)x, g, cam);
+    with_storage(kind, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        cam_map_kernel<T><<<n, 256, 0, st>>>((const T*)x, g, cam);
+    });
     CHECK_LAUNCH(ctx, "cam_map");
     return AVCER_OK;
 }
@@ -1616,9 +1563,10 @@ int k_conv0_ln_gelu(avcer_ctx* ctx, const float* x, const float* w, const float*
                     void* y, int n, int t_in, int t_out, int kind, hipStream_t st) {
     const int spb = 64;
     dim3 grid(cdiv(t_out, spb), n);
-    if (kind == 1) conv0_ln_gelu_kernel<bf16_t><<<grid, 256, 0, st>>>(x, w, b, g, beta, (bf16_t*)y, t_in, t_out, spb, nullptr);
-    else if (kind == 2) conv0_ln_gelu_kernel<sp32_t><<<grid, 256, 0, st>>>(x, w, b, g, beta, (sp32_t*)y, t_in, t_out, spb, ctx->ovf);
-    else conv0_ln_gelu_kernel<float><<<grid, 256, 0, st>>>(x, w, b, g, beta, (float*)y, t_in, t_out, spb, nullptr);
+    with_storage(kind, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        conv0_ln_gelu_kernel<T><<<grid, 256, 0, st>>>(x, w, b, g, beta, (T*)y, t_in, t_out, spb, ctx->ovf);
+    });
     CHECK_LAUNCH(ctx, "conv0_ln_gelu");
     return AVCER_OK;
 }
@@ -1641,16 +1589,12 @@ int ln_launch(avcer_ctx* ctx, const void* x, const void* res, const float* g, co
 // in_kind: storage of x / res (0 f32, 1 bf16, 2 sp32); yb_kind: storage of the operand copy yb (1 bf16, 2 sp32)
 int k_layernorm(avcer_ctx* ctx, const void* x, const void* res, const float* g, const float* b, void* yf, void* yb,
                 int64_t rows, int c, float eps, int act, int in_kind, int yb_kind, hipStream_t st) {
-    int r;
-    if (yb_kind == 2) {
-        if (in_kind == 2) r = ln_launch<sp32_t, sp32_t>(ctx, x, res, g, b, yf, yb, rows, c, eps, act, st);
-        else if (in_kind == 1) r = ln_launch<bf16_t, sp32_t>(ctx, x, res, g, b, yf, yb, rows, c, eps, act, st);
-        else r = ln_launch<float, sp32_t>(ctx, x, res, g, b, yf, yb, rows, c, eps, act, st);
-    } else {
-        if (in_kind == 2) r = ln_launch<sp32_t, bf16_t>(ctx, x, res, g, b, yf, yb, rows, c, eps, act, st);
-        else if (in_kind == 1) r = ln_launch<bf16_t, bf16_t>(ctx, x, res, g, b, yf, yb, rows, c, eps, act, st);
-        else r = ln_launch<float, bf16_t>(ctx, x, res, g, b, yf, yb, rows, c, eps, act, st);
-    }
+    int r = AVCER_OK;
+    with_storage<bf16_t, sp32_t>(yb_kind, [&](auto ob) {
+        with_storage(in_kind, [&](auto ti) {
+            r = ln_launch<typename decltype(ti)::type, typename decltype(ob)::type>(ctx, x, res, g, b, yf, yb, rows, c, eps, act, st);
+        });
+    });
     if (r != AVCER_OK) return r;
     CHECK_LAUNCH(ctx, "layernorm");
     return AVCER_OK;
@@ -1659,11 +1603,28 @@ int k_layernorm(avcer_ctx* ctx, const void* x, const void* res, const float* g, 
 int k_add_pe(avcer_ctx* ctx, const float* x, const float* pe, float* yf, void* yb, int n, int s, int c, int yb_kind,
              hipStream_t st) {
     const long total4 = (long)n * s * c / 4;
-    if (yb_kind == 2) add_pe_kernel<sp32_t><<<cdiv(total4, 256), 256, 0, st>>>(x, pe, yf, (sp32_t*)yb, total4, s, c, ctx->ovf);
-    else add_pe_kernel<bf16_t><<<cdiv(total4, 256), 256, 0, st>>>(x, pe, yf, (bf16_t*)yb, total4, s, c, nullptr);
+    with_storage<bf16_t, sp32_t>(yb_kind, [&](auto tag) {
+        using OB = typename decltype(tag)::type;
+        add_pe_kernel<OB><<<cdiv(total4, 256), 256, 0, st>>>(x, pe, yf, (OB*)yb, total4, s, c, ctx->ovf);
+    });
     CHECK_LAUNCH(ctx, "add_pe");
     return AVCER_OK;
 }
+
+namespace {
+// More than 64 KiB of dynamic LDS is an attribute of the kernel PER DEVICE: raised to the chip's 160 KiB before KERNEL's first
+// launch on the context's device (one bit per device index)
+template <auto KERNEL>
+int big_lds_once(avcer_ctx* ctx) {
+    static uint64_t done = 0;
+    const uint64_t bit = 1ull << (ctx->device & 63);
+    if (!(done & bit)) {
+        HIP_TRY(ctx, hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        done |= bit;
+    }
+    return AVCER_OK;
+}
+}  // namespace
 
 // in_kind: storage of qkv (0 f32, 1 bf16); out_kind: storage of the context vectors (0 f32, 1 bf16, 2 sp32)
 int k_attention(avcer_ctx* ctx, const void* qkv, void* out, int n, int s, int heads, int d, float scale, int in_kind,
@@ -1680,12 +1641,7 @@ int k_attention(avcer_ctx* ctx, const void* qkv, void* out, int n, int s, int he
         const size_t lds_m = (size_t)sp * 128 * (x3 ? 2 : 1) + (size_t)d * (sp * 2 + 16) * (x3 ? 2 : 1);
 #define ATTM(T, TO, NKT, X3, D)                                                                                       \
     do {                                                                                                              \
-        static uint64_t attr_dev = 0; /* the attribute is per device: one bit per device index */                    \
-        if (!((attr_dev >> (ctx->device & 63)) & 1)) {                                                                \
-            HIP_TRY(ctx, hipFuncSetAttribute((const void*)attention_mfma_kernel<T, TO, NKT, X3, D>,                   \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));               \
-            attr_dev |= 1ull << (ctx->device & 63);                                                                   \
-        }                                                                                                             \
+        TRY((big_lds_once<attention_mfma_kernel<T, TO, NKT, X3, D>>(ctx)));                                           \
         attention_mfma_kernel<T, TO, NKT, X3, D><<<grid, 64 * ATTM_WAVES, lds_m, st>>>((const T*)qkv, (TO*)out, s, heads, scale, ctx->ovf); \
     } while (0)
 #define ATTM_D(T, TO, NKT, X3) do { if (d == 64) ATTM(T, TO, NKT, X3, 64); else ATTM(T, TO, NKT, X3, 32); } while (0)
@@ -1697,20 +1653,13 @@ int k_attention(avcer_ctx* ctx, const void* qkv, void* out, int n, int s, int he
         return AVCER_OK;
     }
     const size_t lds = ((size_t)s * (d + 4) + (size_t)s * d + ATT_WAVES * 256 + ATT_WAVES * d) * sizeof(float);
-#define ATT(T, TO, D)                                                                                                \
-    do {                                                                                                             \
-        static uint64_t attr_dev = 0;                                                                                \
-        if (!((attr_dev >> (ctx->device & 63)) & 1)) {                                                               \
-            HIP_TRY(ctx, hipFuncSetAttribute((const void*)attention_kernel<T, TO, D>,                                \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));              \
-            attr_dev |= 1ull << (ctx->device & 63);                                                                  \
-        }                                                                                                            \
-        attention_kernel<T, TO, D><<<grid, ATT_THREADS, lds, st>>>((const T*)qkv, (TO*)out, s, heads, scale);        \
-    } while (0)
-    if (in_kind == 1) { if (d == 64) ATT(bf16_t, bf16_t, 64); else ATT(bf16_t, bf16_t, 32); }
-    else if (out_kind == 2) { if (d == 64) ATT(float, sp32_t, 64); else ATT(float, sp32_t, 32); }
-    else { if (d == 64) ATT(float, float, 64); else ATT(float, float, 32); }
-#undef ATT
+    if (d == 64) {
+        TRY(big_lds_once<attention_kernel<64>>(ctx));
+        attention_kernel<64><<<grid, ATT_THREADS, lds, st>>>((const float*)qkv, (float*)out, s, heads, scale);
+    } else {
+        TRY(big_lds_once<attention_kernel<32>>(ctx));
+        attention_kernel<32><<<grid, ATT_THREADS, lds, st>>>((const float*)qkv, (float*)out, s, heads, scale);
+    }
     CHECK_LAUNCH(ctx, "attention");
     return AVCER_OK;
 }
@@ -1821,19 +1770,11 @@ int k_face_nms(avcer_ctx* ctx, const float* dets, int T, int P, float conf_thres
 int k_face_pre(avcer_ctx* ctx, const uint8_t* frames, int n, int h, int w, int ph, int pw, int rgb, void* out, int bf16,
                hipStream_t st) {
     const long total = (long)n * ph * pw;
-    if (bf16) face_pre_kernel<bf16_t><<<cdiv(total, 256), 256, 0, st>>>(frames, (bf16_t*)out, n, h, w, ph, pw, rgb);
-    else face_pre_kernel<float><<<cdiv(total, 256), 256, 0, st>>>(frames, (float*)out, n, h, w, ph, pw, rgb);
+    with_storage<float, bf16_t>(bf16 ? KIND_BF16 : KIND_F32, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        face_pre_kernel<T><<<cdiv(total, 256), 256, 0, st>>>(frames, (T*)out, n, h, w, ph, pw, rgb);
+    });
     CHECK_LAUNCH(ctx, "face_pre");
-    return AVCER_OK;
-}
-
-int k_maxpool3s2p1(avcer_ctx* ctx, const void* x, void* y, int n, int h, int w, int c, int oh, int ow, int kind, hipStream_t st) {
-    const long total = (long)n * oh * ow * (c / 4);
-    const int grid = cdiv(total, 256);
-    if (kind == 1) maxpool3s2p1_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)x, (bf16_t*)y, n, h, w, c, oh, ow);
-    else if (kind == 2) maxpool3s2p1_kernel<sp32_t><<<grid, 256, 0, st>>>((const sp32_t*)x, (sp32_t*)y, n, h, w, c, oh, ow);
-    else maxpool3s2p1_kernel<float><<<grid, 256, 0, st>>>((const float*)x, (float*)y, n, h, w, c, oh, ow);
-    CHECK_LAUNCH(ctx, "maxpool3s2p1");
     return AVCER_OK;
 }
 
@@ -1841,9 +1782,10 @@ int k_upsample_add(avcer_ctx* ctx, void* y, const void* coarse, int n, int h, in
                    hipStream_t st) {
     const long total = (long)n * h * w * (c / 4);
     const int grid = cdiv(total, 256);
-    if (kind == 1) upsample_add_kernel<bf16_t><<<grid, 256, 0, st>>>((bf16_t*)y, (const bf16_t*)coarse, n, h, w, ch, cw, c, nullptr);
-    else if (kind == 2) upsample_add_kernel<sp32_t><<<grid, 256, 0, st>>>((sp32_t*)y, (const sp32_t*)coarse, n, h, w, ch, cw, c, ctx->ovf);
-    else upsample_add_kernel<float><<<grid, 256, 0, st>>>((float*)y, (const float*)coarse, n, h, w, ch, cw, c, nullptr);
+    with_storage(kind, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        upsample_add_kernel<T><<<grid, 256, 0, st>>>((T*)y, (const T*)coarse, n, h, w, ch, cw, c, ctx->ovf);
+    });
     CHECK_LAUNCH(ctx, "upsample_add");
     return AVCER_OK;
 }
@@ -1857,9 +1799,11 @@ int k_face_head(avcer_ctx* ctx, const float* hd, int ld, int n, int hw, int row0
 
 int k_pack_nchw(avcer_ctx* ctx, const float* x, int n, void* out, int kind, hipStream_t st) {
     const long total = (long)n * PP * PP;
-    if (kind == 3) pack_nchw_planar_kernel<<<cdiv(total, 256), 256, 0, st>>>(x, (bf16_t*)out, (bf16_t*)out + total * 4, n, ctx->ovf);
-    else if (kind == 1) pack_nchw_kernel<bf16_t><<<cdiv(total, 256), 256, 0, st>>>(x, (bf16_t*)out, n);
-    else pack_nchw_kernel<float><<<cdiv(total, 256), 256, 0, st>>>(x, (float*)out, n);
+    if (kind == 3) pack_nchw_kernel<bf16_t, true><<<cdiv(total, 256), 256, 0, st>>>(x, (bf16_t*)out, (bf16_t*)out + total * 4, n, ctx->ovf);
+    else with_storage<float, bf16_t>(kind, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        pack_nchw_kernel<T, false><<<cdiv(total, 256), 256, 0, st>>>(x, (T*)out, nullptr, n, nullptr);
+    });
     CHECK_LAUNCH(ctx, "pack_nchw");
     return AVCER_OK;
 }

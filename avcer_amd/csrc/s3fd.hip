@@ -6,8 +6,6 @@
 // NHWC f32 (AVCER_MODE_FP32) or sp32 pairs (AVCER_MODE_F16X3).  Here:
 //   s3fd_stem_kernel     u8 frame -> (optional BGR flip) pixel - integer mean -> conv1_1 3x3 pad 1 (3 -> 64, K = 27) + bias + ReLU ->
 //                        the mode's storage.  f32 VALU in both modes: the launch is bound by its 256 bytes of output per pixel.
-//   maxpool2_kernel      2x2 / 2 max-pool on NHWC in either storage; with ceil_mode a window that hangs over the edge takes the
-//                        maximum of what exists (vgg.16).
 //   s3fd_invnorm_kernel  1 / (sqrt(sum_c x^2) + 1e-10) per position of an L2Norm level (one wave per position).
 //   s3fd_head_kernel     one level's `loc` and `conf` 3x3 convolutions as ONE direct f32 convolution with 8 (level 0) or 6 outputs:
 //                        a wave owns 8 neighbouring positions of a row, its lanes share the input channels, every tap is scaled by
@@ -66,40 +64,6 @@ __global__ __launch_bounds__(256) void s3fd_stem_kernel(const uint8_t* __restric
     for (int o = 0; o < 16; ++o) acc[o] = relu_nan(acc[o]);
 #pragma unroll
     for (int q = 0; q < 4; ++q) st4<T>(y, pix * 64 + c0 + 4 * q, acc + 4 * q, ovf);
-}
-
-// ------------------------------------------------------------------------------------------------ 2x2 / 2 max-pool
-// nn.MaxPool2d(2, 2[, ceil_mode=True]) on NHWC; one thread per output position and 4 channels.  oh / ow are the caller's
-// (floor or ceil of h / 2, w / 2); taps outside the input do not exist.  A NaN in the window is the result, like torch.
-template <typename T>
-__global__ void maxpool2_kernel(const T* __restrict__ x, T* __restrict__ y, int n, int h, int w, int c, int oh, int ow) {
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int c4 = c / 4;
-    if (idx >= (long)n * oh * ow * c4) return;
-    const int cc = (int)(idx % c4) * 4;
-    long t = idx / c4;
-    const int ox = (int)(t % ow); t /= ow;
-    const int oy = (int)(t % oh);
-    const long b = t / oh;
-    float m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    bool nan[4] = {false, false, false, false};
-#pragma unroll
-    for (int dy = 0; dy < 2; ++dy) {
-        const int iy = 2 * oy + dy;
-        if (iy >= h) continue;
-#pragma unroll
-        for (int dx = 0; dx < 2; ++dx) {
-            const int ix = 2 * ox + dx;
-            if (ix >= w) continue;
-            float v[4];
-            ld4<T>(x, ((b * h + iy) * w + ix) * c + cc, v);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { m[j] = fmaxf(m[j], v[j]); nan[j] |= v[j] != v[j]; }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) if (nan[j]) m[j] = NAN;
-    st4<T>(y, ((b * oh + oy) * ow + ox) * c + cc, m, nullptr);  // a maximum of stored values: nothing new to count
 }
 
 // ------------------------------------------------------------------------------------------------ heads
@@ -368,22 +332,12 @@ __global__ void __launch_bounds__(S3FD_NMS_THREADS) s3fd_nms_kernel(const float*
 int launch_s3fd_stem(avcer_ctx* ctx, const uint8_t* frames, int n, int h, int w, int rgb, const float* wt, const float* b, void* y, int kind,
                      hipStream_t st) {
     const long npix = (long)n * h * w;
-    if (kind == KIND_SP32) s3fd_stem_kernel<sp32_t><<<cdiv(npix * 4, 256), 256, 0, st>>>(frames, npix, h, w, rgb, wt, b, (sp32_t*)y, ctx->ovf);
-    else if (kind == KIND_F32) s3fd_stem_kernel<float><<<cdiv(npix * 4, 256), 256, 0, st>>>(frames, npix, h, w, rgb, wt, b, (float*)y, nullptr);
-    else return set_err(ctx, AVCER_EINVAL, "s3fd_stem: storage kind %d (f32 and sp32 only)", kind);
+    if (kind != KIND_F32 && kind != KIND_SP32) return set_err(ctx, AVCER_EINVAL, "s3fd_stem: storage kind %d (f32 and sp32 only)", kind);
+    with_storage<float, sp32_t>(kind, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        s3fd_stem_kernel<T><<<cdiv(npix * 4, 256), 256, 0, st>>>(frames, npix, h, w, rgb, wt, b, (T*)y, ctx->ovf);
+    });
     CHECK_LAUNCH(ctx, "s3fd_stem");
-    return AVCER_OK;
-}
-
-int launch_maxpool2(avcer_ctx* ctx, const void* x, void* y, int n, int h, int w, int c, int ceil_mode, int kind, hipStream_t st) {
-    const int oh = ceil_mode ? (h + 1) / 2 : h / 2, ow = ceil_mode ? (w + 1) / 2 : w / 2;
-    if (c % 4 || (kind == KIND_SP32 && c % 32)) return set_err(ctx, AVCER_EINVAL, "maxpool2: %d channels", c);
-    if (oh < 1 || ow < 1) return set_err(ctx, AVCER_EINVAL, "maxpool2: a %d x %d map has no 2 x 2 window", h, w);
-    const unsigned grid = cdiv((long)n * oh * ow * (c / 4), 256);
-    if (kind == KIND_SP32) maxpool2_kernel<sp32_t><<<grid, 256, 0, st>>>((const sp32_t*)x, (sp32_t*)y, n, h, w, c, oh, ow);
-    else if (kind == KIND_F32) maxpool2_kernel<float><<<grid, 256, 0, st>>>((const float*)x, (float*)y, n, h, w, c, oh, ow);
-    else return set_err(ctx, AVCER_EINVAL, "maxpool2: storage kind %d (f32 and sp32 only)", kind);
-    CHECK_LAUNCH(ctx, "maxpool2");
     return AVCER_OK;
 }
 
@@ -394,17 +348,17 @@ int launch_s3fd_head(avcer_ctx* ctx, const void* x, int kind, float* inv, const 
     const long npos = (long)nb * h * w;
     const unsigned grid = cdiv((long)nb * h * ((w + 7) / 8), 4);
     if (inv != nullptr) {
-        if (kind == KIND_SP32) s3fd_invnorm_kernel<sp32_t><<<cdiv(npos, 4), 256, 0, st>>>((const sp32_t*)x, npos, c, inv);
-        else s3fd_invnorm_kernel<float><<<cdiv(npos, 4), 256, 0, st>>>((const float*)x, npos, c, inv);
+        with_storage<float, sp32_t>(kind, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            s3fd_invnorm_kernel<T><<<cdiv(npos, 4), 256, 0, st>>>((const T*)x, npos, c, inv);
+        });
         CHECK_LAUNCH(ctx, "s3fd_invnorm");
     }
-    if (kind == KIND_SP32) {
-        if (n_out == 8) s3fd_head_kernel<sp32_t, 8><<<grid, 256, 0, st>>>((const sp32_t*)x, inv, wt, b, nb, h, w, c, row0, P, loc, conf);
-        else s3fd_head_kernel<sp32_t, 6><<<grid, 256, 0, st>>>((const sp32_t*)x, inv, wt, b, nb, h, w, c, row0, P, loc, conf);
-    } else {
-        if (n_out == 8) s3fd_head_kernel<float, 8><<<grid, 256, 0, st>>>((const float*)x, inv, wt, b, nb, h, w, c, row0, P, loc, conf);
-        else s3fd_head_kernel<float, 6><<<grid, 256, 0, st>>>((const float*)x, inv, wt, b, nb, h, w, c, row0, P, loc, conf);
-    }
+    with_storage<float, sp32_t>(kind, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if (n_out == 8) s3fd_head_kernel<T, 8><<<grid, 256, 0, st>>>((const T*)x, inv, wt, b, nb, h, w, c, row0, P, loc, conf);
+        else s3fd_head_kernel<T, 6><<<grid, 256, 0, st>>>((const T*)x, inv, wt, b, nb, h, w, c, row0, P, loc, conf);
+    });
     CHECK_LAUNCH(ctx, "s3fd_head");
     return AVCER_OK;
 }

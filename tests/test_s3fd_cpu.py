@@ -173,19 +173,24 @@ def test_abi_and_symbols():
 
 
 def test_s3fd_kernels_use_no_scratch_and_do_not_spill():
+    """Every kernel of s3fd.hip, and the detector's 2 x 2 pool, which is the shared maxpool_kernel of kernels.hip (all of its instances)."""
     exe = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(exe):
         pytest.skip("hipcc not available")
-    out = os.path.join(tempfile.mkdtemp(prefix="avcer_asm_"), "s3fd.hip.s")
     flags = [f for f in build.FLAGS if f not in ("-fPIC", "-shared")]
-    r = subprocess.run([exe] + flags + ["-S", "--cuda-device-only", "-o", out, os.path.join(build.CSRC, "s3fd.hip")],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kernels = re.findall(r"- \.agpr_count:.*?\.wavefront_size", open(out).read(), re.S)
-    assert len(kernels) == 2 + 2 + 2 + 4 + 3  # stem, pool and inverse norm x two storages, the head x two storages x 8 / 6 outputs, Detect
+    # s3fd.hip: stem and inverse norm x two storages, the head x two storages x 8 / 6 outputs, Detect; kernels.hip: the pool, 2 x 2 on
+    # f32 / sp32 and 3 x 3 on f32 / bf16
     bad = []
-    for k in kernels:
-        g = lambda key: re.search(r"\." + key + r":\s+(\S+)", k).group(1)
-        if int(g("private_segment_fixed_size")) or int(g("vgpr_spill_count")) or int(g("sgpr_spill_count")):
-            bad.append((g("name"), g("private_segment_fixed_size"), g("vgpr_spill_count"), g("sgpr_spill_count")))
+    for src, only, count in (("s3fd.hip", "", 2 + 2 + 4 + 3), ("kernels.hip", "maxpool_kernel", 2 + 2)):
+        out = os.path.join(tempfile.mkdtemp(prefix="avcer_asm_"), src + ".s")
+        r = subprocess.run([exe] + flags + ["-S", "--cuda-device-only", "-o", out, os.path.join(build.CSRC, src)],
+                           capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        kernels = re.findall(r"- \.agpr_count:.*?\.wavefront_size", open(out).read(), re.S)
+        g = lambda k, key: re.search(r"\." + key + r":\s+(\S+)", k).group(1)
+        kernels = [k for k in kernels if only in g(k, "name")]
+        assert len(kernels) == count, (src, [g(k, "name") for k in kernels])
+        for k in kernels:
+            if int(g(k, "private_segment_fixed_size")) or int(g(k, "vgpr_spill_count")) or int(g(k, "sgpr_spill_count")):
+                bad.append((g(k, "name"), g(k, "private_segment_fixed_size"), g(k, "vgpr_spill_count"), g(k, "sgpr_spill_count")))
     assert not bad, bad
