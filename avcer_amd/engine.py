@@ -482,6 +482,22 @@ class Engine:
                                                 _ptr(desc), int(n), 1 if bgr else 0, _ptr(coeffs), int(n_blocks), self._stream()))
         return coeffs
 
+    def jpeg_pack(self, coeffs, desc, n: int, blocks: int, cap_bytes: int):
+        """The entropy-coding half of the JPEG encoder on the device (avcer_jpeg_pack): coefficients int16 [>= 64 * blocks] as
+        jpeg_forward leaves them and desc = n records of struct avcer_jpeg_desc as bytes, both on the device -> (out u8 [cap_bytes]:
+        the files back to back, offsets i64 [n + 1], status i32 [n]: 0 or the reason a file has no bytes, bytes_needed i64 [1]), all on
+        the device.  Byte-identical to avcer_jpeg_write_batch on the same arrays."""
+        if coeffs.dtype != torch.int16 or coeffs.numel() < 64 * blocks or desc.dtype != torch.uint8 or desc.numel() < _JPEG_DESC_BYTES * n or \
+                not coeffs.is_cuda or not desc.is_cuda or not coeffs.is_contiguous() or not desc.is_contiguous():
+            raise ValueError("jpeg_pack: coeffs int16 [64 * blocks], desc uint8 [sizeof(avcer_jpeg_desc) * n], both contiguous on the device")
+        out = self._new(int(cap_bytes), dtype=torch.uint8)
+        offsets = self._new(int(n) + 1, dtype=torch.int64)
+        status = self._new(int(n), dtype=torch.int32)
+        need = self._new(1, dtype=torch.int64)
+        self._check(self.lib.avcer_jpeg_pack(self.ctx, _ptr(coeffs), int(blocks), _ptr(desc), int(n), _ptr(out) if cap_bytes else None,
+                                             int(cap_bytes), _ptr(offsets), _ptr(status), _ptr(need), self._stream()))
+        return out, offsets, status, need
+
     def jpeg_rgb(self, coeffs, desc, n: int, n_blocks: int, hmax: int, wmax: int):
         """The same files at full size -> (canvas u8 [n,hmax,wmax,3] RGB: image i in the top left corner of slot i, zeros around it;
         flags i32 [n] as jpeg_tiles returns them)."""

@@ -307,8 +307,10 @@ class VideoTiler:
         self.engine = engine
         self.face_tracker = SimpleFaceTracker(iou_threshold=0.4, minimum_face_size=0.0)
 
-    def process(self, frames_bgr, dets_per_frame: Sequence[np.ndarray], save_path: Optional[str] = None, video_name: Optional[str] = None):
-        """`save_path` and `video_name` given: the crops are also written as the reference's face folders (write_face_crops)."""
+    def process(self, frames_bgr, dets_per_frame: Sequence[np.ndarray], save_path: Optional[str] = None, video_name: Optional[str] = None,
+                entropy: str = "host"):
+        """`save_path` and `video_name` given: the crops are also written as the reference's face folders (write_face_crops, which
+        takes `entropy`)."""
         if (save_path is None) != (video_name is None):
             raise ValueError("give both save_path and video_name, or neither")
         frames = frames_bgr if torch.is_tensor(frames_bgr) else torch.from_numpy(np.ascontiguousarray(frames_bgr))
@@ -326,7 +328,7 @@ class VideoTiler:
         rects = torch.from_numpy(records[:, [0, 2, 3, 4, 5]].astype(np.int32))
         if save_path is not None:
             frames = frames.to(self.engine.device)  # one copy for both consumers
-            write_face_crops(self.engine, frames, records, save_path, video_name)
+            write_face_crops(self.engine, frames, records, save_path, video_name, entropy=entropy)
         return records, self.engine.crop_tiles(frames, rects, bgr=True)
 
 
@@ -335,18 +337,20 @@ def face_crop_paths(records: np.ndarray, save_path: str, video_name: str) -> Lis
     return [os.path.join(save_path, video_name, str(int(t)).zfill(2), str(int(f)).zfill(6) + ".jpg") for f, t in records[:, :2]]
 
 
-def write_face_crops(engine, frames_bgr, records: np.ndarray, save_path: str, video_name: str, quality: int = 95) -> List[str]:
+def write_face_crops(engine, frames_bgr, records: np.ndarray, save_path: str, video_name: str, quality: int = 95,
+                     entropy: str = "host") -> List[str]:
     """Stage 0's face folders (`VideoPredictor.process`, get_face_images.py:52-63): for every record of `VideoTiler.process` the
     half-open crop `fr[y0:y1, x0:x1]` of its frame, written where the reference's cv2.imwrite writes it (JPEG quality 95, 4:2:0:
     cv2's defaults).  The crops are encoded straight out of the BGR frames on the device (jpeg.encode_images); no crop and no
-    frame is copied to the host.  Returns the paths in record order."""
+    frame is copied to the host.  `entropy`: where the Huffman coding runs, "host" or "device" (jpeg.encode_images; the files are the
+    same).  Returns the paths in record order."""
     from . import jpeg
 
     records = np.asarray(records).reshape(-1, 6)
     paths = face_crop_paths(records, save_path, video_name)
     if not paths:
         return paths
-    blobs = jpeg.encode_images(engine, frames_bgr, records[:, [0, 2, 3, 4, 5]], bgr=True, quality=quality, subsampling=2)
+    blobs = jpeg.encode_images(engine, frames_bgr, records[:, [0, 2, 3, 4, 5]], bgr=True, quality=quality, subsampling=2, entropy=entropy)
     for folder in sorted({os.path.dirname(p) for p in paths}):
         os.makedirs(folder, exist_ok=True)
     for p, blob in zip(paths, blobs):

@@ -141,11 +141,12 @@ def heatmap_dir(save_path: str, video_name: str, model_heatmaps: str) -> str:
     return os.path.join(save_path, video_name, f"heatmaps_{model_heatmaps}")
 
 
-def write_heatmaps(folder: str, frame_idx, images_bgr, engine=None) -> list:
+def write_heatmaps(folder: str, frame_idx, images_bgr, engine=None, entropy: str = "host") -> list:
     """cv2.imwrite(<folder>/<NNNNNN>.jpg, overlay) for every heat-map frame (get_prob_video.py:154): JPEG quality 95 (cv2's
     default), the BGR array flipped to RGB first so that the file's colours are the reference's.  With an `engine` and overlays on
     the device the files come from jpeg.encode_images (forward pass on the device, Huffman coding on host threads); else from
-    PIL, one file at a time.  The bytes are the same either way."""
+    PIL, one file at a time.  `entropy` = "device" moves the Huffman coding to the device as well (jpeg.encode_images).  The bytes
+    are the same either way."""
     os.makedirs(folder, exist_ok=True)
     idx = np.asarray(frame_idx).reshape(-1)
     paths = [os.path.join(folder, str(int(i)).zfill(6) + ".jpg") for i in idx]
@@ -154,7 +155,7 @@ def write_heatmaps(folder: str, frame_idx, images_bgr, engine=None) -> list:
 
         m, h, w = min(len(paths), int(images_bgr.shape[0])), int(images_bgr.shape[1]), int(images_bgr.shape[2])
         rects = np.array([(i, 0, 0, w, h) for i in range(m)], dtype=np.int32).reshape(m, 5)
-        for p, blob in zip(paths, jpeg.encode_images(engine, images_bgr, rects, bgr=True, quality=95, subsampling=2)):
+        for p, blob in zip(paths, jpeg.encode_images(engine, images_bgr, rects, bgr=True, quality=95, subsampling=2, entropy=entropy)):
             with open(p, "wb") as f:
                 f.write(blob)
         return paths[:m]

@@ -169,6 +169,7 @@ class _Staging:
     def __init__(self):
         self.coeffs = None
         self.desc = None
+        self.files = None  # encode_images(entropy="device"): the files on their way to the host
         self.event = None
 
     def reserve(self, blocks: int, n: int):
@@ -178,6 +179,11 @@ class _Staging:
             self.coeffs = torch.empty(64 * (blocks + blocks // 4 + 1024), dtype=torch.int16, pin_memory=True)
         if self.desc is None or self.desc.numel() < DESC.itemsize * n:
             self.desc = torch.empty(DESC.itemsize * (n + n // 4 + 64), dtype=torch.uint8, pin_memory=True)
+
+    def reserve_files(self, nbytes: int):
+        if self.files is None or self.files.numel() < nbytes:
+            self.files = torch.empty(nbytes + nbytes // 4 + 4096, dtype=torch.uint8, pin_memory=True)
+        return self.files
 
 
 def _pil_rgb(blob: bytes) -> np.ndarray:
@@ -291,7 +297,8 @@ def decode_canvas(engine, blobs, threads: int = 0):
 # ==================================================================================================== encoding
 # The mirror image of the above (include/avcer_hip.h "JPEG face crops", encoding): the device computes the quantised coefficients
 # of every image (colour conversion, chroma downsampling, forward DCT, quantisation: avcer_jpeg_forward), the host writes the
-# files (avcer_jpeg_write_batch: headers, Huffman coding).  The contract is byte-identity with
+# files (avcer_jpeg_write_batch: headers, Huffman coding) -- or, with entropy="device", the device does (avcer_jpeg_pack) and only
+# the files cross to the host.  The contract is byte-identity with
 # PIL.Image.fromarray(rgb).save(f, "JPEG", quality=quality, subsampling=subsampling) (libjpeg-turbo, standard Huffman tables).
 HEADER_BYTES = 623  # csrc/jpeg.hip: SOI, APP0, two DQT, SOF0, four DHT, SOS
 R_ENC_SIZE = 18  # csrc/jpeg.hip: an image of zero width or height, or of more than 65535 pixels a side
@@ -467,11 +474,49 @@ def _encode_rects(src, rects) -> np.ndarray:
     return r.astype(np.int32)
 
 
-def encode_images(engine, src, rects, bgr: bool = False, quality: int = 95, subsampling: int = 2, threads: int = 0) -> list:
+def _not_written(status, reason):
+    i = int(np.nonzero(status != OK)[0][0])
+    return RuntimeError(f"image {i} was not written: reason {int(reason[i])} (csrc/jpeg.hip R_*)")
+
+
+def _pack_to_host(engine, st, coeffs, d_dev, n: int, blocks: int) -> list:
+    """The device entropy coder behind avcer_jpeg_forward: avcer_jpeg_pack, then offsets and statuses to the host, then exactly the
+    bytes of the files through the pinned staging of the engine."""
+    dev = engine.device
+    cap = HEADER_BYTES * n + 40 * blocks  # the guess of the host path; repeated once with what the files need when it was short
+    small = torch.empty(2 * n + 2, dtype=torch.int64, pin_memory=True)  # offsets [n + 1], bytes_needed, status [n] as i32 pairs
+    for attempt in range(2):
+        out, offsets, status, need = engine.jpeg_pack(coeffs, d_dev, n, blocks, cap)
+        small[:n + 1].copy_(offsets, non_blocking=True)
+        small[n + 1:n + 2].copy_(need, non_blocking=True)
+        s_host = small[n + 2:].view(torch.int32)[:n]
+        s_host.copy_(status, non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+        offs, reason = small[:n + 1].numpy(), s_host.numpy()
+        if attempt == 0 and (reason == R_NO_SPACE).any():
+            cap = int(small[n + 1])
+            continue
+        break
+    if (reason != OK).any():
+        raise _not_written(reason, reason)
+    total = int(offs[n])
+    host = st.reserve_files(total)
+    host[:total].copy_(out[:total], non_blocking=True)
+    torch.cuda.current_stream(dev).synchronize()
+    blob = host.numpy()
+    return [blob[offs[i]:offs[i + 1]].tobytes() for i in range(n)]
+
+
+def encode_images(engine, src, rects, bgr: bool = False, quality: int = 95, subsampling: int = 2, threads: int = 0,
+                  entropy: str = "host") -> list:
     """JPEG files of n images cut out of `src` (u8 [N,H,W,3], moved to the device if it is not there): image i is the half-open
     rectangle rects[i] = (slot, x0, y0, x1, y1).  Returns the n files as bytes, byte-identical to
     PIL.Image.fromarray(rgb).save(f, "JPEG", quality=quality, subsampling=subsampling).  plan (host) -> descriptors to the device
-    -> avcer_jpeg_forward -> coefficients into the pinned staging of the engine -> avcer_jpeg_write_batch (host threads)."""
+    -> avcer_jpeg_forward -> coefficients into the pinned staging of the engine -> avcer_jpeg_write_batch (host threads).
+    entropy="device": the coefficients stay where they are, avcer_jpeg_pack writes the files on the device and only their bytes
+    cross (`threads` is then unused); the files are the same."""
+    if entropy not in ("host", "device"):
+        raise ValueError(f'entropy must be "host" or "device", not {entropy!r}')
     src = src if torch.is_tensor(src) else torch.from_numpy(np.array(src))  # a copy: torch.from_numpy wants a writable array
     if src.dim() != 4 or src.shape[-1] != 3 or src.dtype != torch.uint8:
         raise ValueError("src must be uint8 [N,H,W,3]")
@@ -491,6 +536,10 @@ def encode_images(engine, src, rects, bgr: bool = False, quality: int = 95, subs
     d_dev = st.desc[:DESC.itemsize * n].to(dev, non_blocking=True)
     r_dev = torch.from_numpy(r).to(dev)
     coeffs = engine.jpeg_forward(src.to(dev).contiguous(), r_dev, d_dev, n, blocks, bgr=bgr)
+    if entropy == "device":
+        st.event = torch.cuda.Event()  # the descriptors were copied out of the pinned staging
+        st.event.record(torch.cuda.current_stream(dev))
+        return _pack_to_host(engine, st, coeffs, d_dev, n, blocks)
     st.coeffs[:64 * blocks].copy_(coeffs[:64 * blocks], non_blocking=True)
     st.event = torch.cuda.Event()
     st.event.record(torch.cuda.current_stream(dev))
@@ -506,6 +555,5 @@ def encode_images(engine, src, rects, bgr: bool = False, quality: int = 95, subs
             break
         out = np.empty(need, dtype=np.uint8)
     if (d["status"] != OK).any():
-        i = int(np.nonzero(d["status"] != OK)[0][0])
-        raise RuntimeError(f"image {i} was not written: reason {int(d['reason'][i])} (csrc/jpeg.hip R_*)")
+        raise _not_written(d["status"], d["reason"])
     return [out[offsets[i]:offsets[i + 1]].tobytes() for i in range(n)]

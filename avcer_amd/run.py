@@ -29,7 +29,7 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
                   weights_prob_model=None, weights_model=(1, 1, 1), ce_weights_type: bool = True, ce_mask: bool = False,
                   sr: int = 16000, window: float = 4, step: float = 0.5, padding: str = "mean", mode: int = MODE_DEFAULT,
                   flag_heatmaps: bool = False, model_heatmaps: str = "static", wav_sr: Optional[int] = None,
-                  path_save_faces: Optional[str] = None):
+                  path_save_faces: Optional[str] = None, jpeg_entropy: str = "host"):
     """engine: an `Engine` with the static, dynamic and audio weights loaded.  frames_bgr u8 [T,H,W,3] as cv2 decodes
     them; wav float32 [L] mono at `sr`; fps as `int(cv2.CAP_PROP_FPS)` gives it (get_face_images.py:23).
     `wav_sr`: `wav` is source audio at that rate instead -- int16 [L] / [L, C] as the frames lie in the WAV file ffmpeg writes
@@ -49,7 +49,11 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
     reference dies with UnboundLocalError at its first heat-map frame).
     `path_save_faces`: stage 0's output on disk as well (get_face_images.py:52-63): every detection's crop as
     `<path_save_faces>/<name_video>/<track:02d>/<frame:06d>.jpg`, encoded from the frames on the device
-    (face_tiles.write_face_crops); `out["face_files"]` lists the paths in record order.  Off by default."""
+    (face_tiles.write_face_crops); `out["face_files"]` lists the paths in record order.  Off by default.
+    `jpeg_entropy`: where those files are Huffman-coded, "host" (the default) or "device" (jpeg.encode_images); the files are the
+    same.  Any other value raises ValueError before any work."""
+    if jpeg_entropy not in ("host", "device"):
+        raise ValueError(f'jpeg_entropy must be "host" or "device", not {jpeg_entropy!r}')
     if flag_heatmaps:
         from . import heatmaps as hm
 
@@ -89,7 +93,7 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
                 dets = detections if detections is not None else detector.batch(frames, rgb=False)  # get_face_images.py:49
                 records, tiles = VideoTiler(engine).process(frames, dets)
                 if path_save_faces:
-                    host["face_files"] = write_face_crops(engine, frames, records, path_save_faces, name_video)
+                    host["face_files"] = write_face_crops(engine, frames, records, path_save_faces, name_video, entropy=jpeg_entropy)
                 if not (len(records) and (records[:, 1] == 0).any()):
                     raise FileNotFoundError("no face track 00 (os.listdir(<faces>/00) fails in the reference, get_prob_video.py:79)")
                 host["records"] = records

@@ -81,7 +81,8 @@ enum {
  *      avcer_jpeg_probe, avcer_jpeg_entropy_batch, avcer_jpeg_tiles, avcer_jpeg_rgb and their descriptor struct (JPEG crop files
  *      decoded behind a host entropy pass) joined under 8 the same way.
  *      avcer_jpeg_quant_tables, avcer_jpeg_plan, avcer_jpeg_forward, avcer_jpeg_write_batch (the same files WRITTEN: forward pass
- *      on the device, entropy coding on the host) joined under 8 the same way: four more symbols, the descriptor unchanged. */
+ *      on the device, entropy coding on the host) joined under 8 the same way: four more symbols, the descriptor unchanged.
+ *      avcer_jpeg_pack (entropy coding on the device: whole files leave it) joined under 8 the same way: one more symbol. */
 #define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
@@ -436,7 +437,7 @@ int avcer_jpeg_rgb(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_blocks, cons
  * encoded without an encoder library, split at the same place: colour conversion, chroma downsampling, the forward DCT and the
  * quantisation on the DEVICE (avcer_jpeg_forward, one launch per batch, images cut straight out of the decoded frames), headers
  * and Huffman coding on the HOST (avcer_jpeg_quant_tables, avcer_jpeg_plan, avcer_jpeg_write_batch: host code and host pointers,
- * ctx may be NULL, no device is touched).  The arithmetic is libjpeg's -- 16-bit fixed-point RGB -> YCbCr, the box filter with
+ * ctx may be NULL, no device is touched).  avcer_jpeg_pack, below them, is the same writer on the device.  The arithmetic is libjpeg's -- 16-bit fixed-point RGB -> YCbCr, the box filter with
  * its alternating bias, the "islow" forward DCT, division by 8 q with halves away from zero -- and the contract is BYTE-identity
  * with PIL.Image.fromarray(rgb).save(f, "JPEG", quality=quality, subsampling=subsampling) (libjpeg-turbo): a tolerance of zero,
  * independent of the arithmetic mode.
@@ -471,6 +472,26 @@ int avcer_jpeg_forward(avcer_ctx* ctx, const uint8_t* src, int N, int H, int W, 
                        int bgr, int16_t* coeffs, int64_t n_blocks, avcer_stream_t stream);
 int avcer_jpeg_write_batch(avcer_ctx* ctx, const int16_t* coeffs_host, avcer_jpeg_desc* desc_host, int n, uint8_t* out_host,
                            int64_t cap_bytes, int64_t* offsets_host, int threads, int64_t* bytes_needed);
+
+/* avcer_jpeg_pack: avcer_jpeg_write_batch on the DEVICE -- headers, Huffman coding with the standard tables, byte stuffing, EOI --
+ * so that the files, and not 128 bytes of coefficients per block, cross to the host.  Same contract, same bytes: file i is
+ * byte-identical to what avcer_jpeg_write_batch writes from the same coefficients and descriptor (and so to PIL's file), whatever
+ * n is and whichever other files share the call.
+ *   coeffs int16 [n_blocks, 64] as avcer_jpeg_forward leaves them and desc[n] as avcer_jpeg_plan wrote them, both on the device
+ *   (desc 16-byte aligned, not modified).  The files' block ranges may come in any order but lie inside the n_blocks blocks and
+ *   share none: the n_blocks of the files of one call add up to at most n_blocks (a file past that sum is status 19).
+ *   out u8 [cap_bytes], offsets i64 [n + 1], status i32 [n], bytes_needed i64 [1]: on the device.  File i is
+ *   out[offsets[i] .. offsets[i + 1]); status[i] is 0 for a file that was written, else the reason, and such a file has no bytes
+ *   and disturbs no other: 12 = it does not fit cap_bytes (files take the next free bytes in file order, as in
+ *   avcer_jpeg_write_batch; nothing is written past cap_bytes), 16 = a coefficient the standard tables cannot code (more than 11
+ *   bits of DC difference, 10 of AC), 17 = a scan of more than 2^32 - 64 bits (512 MiB: bit offsets inside a file are 32 bits
+ *   wide; such a file is reported, never wrapped; byte offsets are 64 bits wide), 19 = a descriptor avcer_jpeg_plan did not write
+ *   or blocks outside the storage; a desc[i] that is already NOT_HANDLED is skipped and reports its own reason.  *bytes_needed =
+ *   what all codable files need together (those of status 0 or 12).
+ *   Seven kernels on `stream`, no synchronisation with the host; scratch (212 bytes per block: an unstuffed block is at most
+ *   ceil((20 + 63 * 26) / 8) = 208) comes from the context's JPEG workspace.  n_blocks < 2^31. */
+int avcer_jpeg_pack(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_blocks, const avcer_jpeg_desc* desc, int n, uint8_t* out,
+                    int64_t cap_bytes, int64_t* offsets, int32_t* status, int64_t* bytes_needed, avcer_stream_t stream);
 
 /* Probability fusion and compound-expression rule.
  *   ref: run.py:25-165 (get_c_expr_db_pred), data/utils.py:125-127 (softmax), :222-241 (get_compound_expression)
