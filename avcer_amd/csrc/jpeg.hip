@@ -9,7 +9,10 @@
 // avcer_amd/jpeg.py pixels_numpy, to PIL; tests/test_gpu_jpeg.py holds the kernels to goldens PIL wrote).
 // A file outside the supported subset (include/avcer_hip.h) is REPORTED as not handled and never guessed at; the caller then
 // decodes it with PIL as before.
+// The Huffman decoding runs on the device as well when asked to (avcer_jpeg_scan_batch + avcer_jpeg_unpack, at the end of this file:
+// the host then parses headers only); the host pass above is its oracle.
 #include "common.h"
+#include "jpeg_sync_dev.h"
 
 #include <algorithm>
 #include <atomic>
@@ -1661,5 +1664,647 @@ extern "C" int avcer_jpeg_pack(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_
     HIP_TRY(ctx, hipGetLastError());
     pack_write_kernel<<<(unsigned)n, PACK_THREADS, 0, st>>>(desc, wb, status, fbits, flen, bits, offsets, out);
     HIP_TRY(ctx, hipGetLastError());
+    return AVCER_OK;
+}
+
+// ================================================================================================ entropy decoding on the device
+// avcer_jpeg_unpack: decode_scan / decode_block / Bits above as self-synchronising subsequence decoding (Klein & Wiseman; Weissenberger
+// & Schmidt, "Accelerating JPEG Decompression on GPUs"), shaped for thousands of small independent files: a WORKGROUP takes a file
+// and nothing ever waits for another workgroup.  The host (avcer_jpeg_scan_batch) parses the headers and copies the entropy-coded
+// bytes; it does not walk them.  Phases of a workgroup, all counted loops with workgroup barriers between them:
+//   marker   every byte gets its class from its neighbours (jsync::byte_class); prefix sums of the data bytes and of the stops give
+//            the UNSTUFFED stream (words, first byte on top) and the list of stops: where the bit supply ends and which marker code
+//            stands there.  Segment j (restart interval j, or the whole scan) is the data between stop j - 1 and stop j; a marker
+//            where none is due therefore ends its segment's bits, exactly as Bits::fill does.
+//   units    a segment is cut into subsequences of sub_bits; THREADS consecutive subsequences of the file are decoded side by side,
+//            one thread each.  The first subsequence of a segment enters with the true state (the segment's first bit, slot 0, k 0),
+//            thread 0 of a later unit of the same segment with the converged exit of the unit before; every other thread enters
+//            with its left neighbour's last exit ("fresh block at my first bit" while that is unknown or an error).  Rounds repeat
+//            until no exit changed.  Then every exit is the decode of the true chain: thread 0's entry is true, so its exit is final
+//            after round 1, thread i's after round i + 1 by induction, and "nothing changed" means every thread decoded from the
+//            exit its neighbour holds.  At most THREADS + 2 rounds; a thread whose entry did not change does not decode again.
+//            A decode that meets an undefined code or the end of the bits parks at its subsequence's end, not synchronised.
+//   write    a prefix sum of the finished blocks gives each subsequence the ordinal of its first block in the segment; the threads
+//            decode once more from their final entry states and write AC values and DC differences to the zeroed storage
+//            (jsync::storage_block: decode_scan's interleave).  A subsequence behind an error of the true chain writes nothing.
+//            The decode ends with the segment's last block; fewer than 8 bits may be left, and the stop's code must be the one due.
+//   predict  per component, a segmented prefix sum along the scan (restarting at every segment) turns differences into DC values;
+//            decode_block's range checks of the prediction follow.
+// Every defect carries its place in scan order (jsync::defect); the smallest is the file's reason, as the host pass returns at the
+// first one.  Coefficients of a file that is not OK are unspecified, as they are there.
+namespace {
+namespace js = jsync;
+static_assert(js::R_SCAN == R_SCAN && js::R_TRUNCATED == R_TRUNCATED && js::R_CODE == R_CODE && js::R_INDEX == R_INDEX &&
+              js::R_RESTART == R_RESTART && js::R_NO_EOI == R_NO_EOI && js::R_RANGE == R_RANGE && js::R_SIZE == R_SIZE &&
+              js::R_TABLE == R_TABLE, "one set of reasons");
+static_assert(js::THREADS == PACK_THREADS, "block_scan is written for this many threads");
+static_assert(sizeof(avcer_jpeg_tab) == 288 && sizeof(avcer_jpeg_scan) == 48, "layout of the ABI structs");
+
+// where file i keeps its stops and segments in the per-block scratch arrays: n_blocks + 2 entries of its own (a file has at most
+// as many segments as MCUs, and the segment table one entry more)
+__host__ __device__ inline int64_t seg_scratch(const Desc& d, int i) { return d.coef_block + 2 * (int64_t)i; }
+
+__global__ void unpack_tabs_kernel(const avcer_jpeg_tab* __restrict__ tabs, int n_tabs, js::DTab* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_tabs) js::derive_tab(tabs[i], out[i]);
+}
+
+// inclusive maxima along the threads of a workgroup (every thread calls it); `tot`: PACK_WAVES values of LDS, free again on return
+__device__ __forceinline__ int32_t block_scan_max(int32_t v, int32_t* tot) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int32_t o = __shfl_up(v, d, 64);
+        if (lane >= d) v = max(v, o);
+    }
+    if (lane == 63) tot[wave] = v;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < PACK_WAVES; ++k)
+        if (k < wave) v = max(v, tot[k]);
+    __syncthreads();
+    return v;
+}
+
+// inclusive sums modulo 2^32 along the threads of a workgroup that start again at every thread with `f` set; *carry: the running
+// sum in front of thread 0, and behind the last thread on return (the same value in every thread)
+__device__ __forceinline__ uint32_t block_scan_segmented(uint32_t v, bool f, uint32_t* totv, uint32_t* totf, uint32_t* carry) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t ff = f ? 1u : 0u;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t ov = __shfl_up(v, d, 64), of = __shfl_up(ff, d, 64);
+        if (lane >= d) {
+            if (!ff) v += ov;
+            ff |= of;
+        }
+    }
+    if (lane == 63) {
+        totv[wave] = v;
+        totf[wave] = ff;
+    }
+    __syncthreads();
+    uint32_t acc = *carry, mine = 0;
+#pragma unroll
+    for (int k = 0; k < PACK_WAVES; ++k) {
+        if (k == wave) mine = acc;
+        acc = totf[k] ? totv[k] : acc + totv[k];
+    }
+    __syncthreads();
+    *carry = acc;
+    return ff ? v : v + mine;
+}
+
+__global__ void __launch_bounds__(js::THREADS) unpack_kernel(const uint8_t* __restrict__ bytes, int64_t n_bytes,
+                                                             const avcer_jpeg_scan* __restrict__ scan, const js::DTab* __restrict__ dtabs,
+                                                             int n_tabs, Desc* desc, int16_t* __restrict__ coeffs, int64_t n_blocks,
+                                                             int32_t* __restrict__ status, int sub, uint8_t* __restrict__ comp,
+                                                             int32_t* __restrict__ stop_pos, int32_t* __restrict__ stop_code,
+                                                             int32_t* __restrict__ seg_sub) {
+    __shared__ js::DTab tabs[6];
+    __shared__ js::State exits[js::THREADS];
+    __shared__ int32_t pex[js::THREADS];
+    __shared__ uint32_t tot[PACK_WAVES], totf[PACK_WAVES];
+    __shared__ unsigned long long errkey;
+    __shared__ js::State carry_state;
+    __shared__ long long carry_ord;
+    const int i = blockIdx.x, t = threadIdx.x;
+    Desc& d = desc[i];
+    if (d.status != AVCER_JPEG_OK) {  // the whole workgroup
+        if (t == 0) status[i] = d.status;
+        return;
+    }
+    const avcer_jpeg_scan sc = scan[i];
+    js::File f;
+    int r = js::check_file(d, sc, n_bytes, n_tabs, n_blocks, f);
+    if (r == R_OK)
+        for (int c = 0; c < f.ncomp; ++c)
+            if (!dtabs[sc.dc[c]].dc_ok || !dtabs[sc.ac[c]].ok) r = R_TABLE;
+    if (r != R_OK) {  // the whole workgroup
+        if (t == 0) {
+            d.reason = r;
+            d.status = status[i] = AVCER_JPEG_NOT_HANDLED;
+        }
+        return;
+    }
+    for (int c = 0; c < f.ncomp; ++c)
+        for (int k = 0; k < 2; ++k) {
+            const uint32_t* src = reinterpret_cast<const uint32_t*>(dtabs + (k ? sc.ac[c] : sc.dc[c]));
+            uint32_t* dst = reinterpret_cast<uint32_t*>(tabs + 2 * c + k);
+            for (int x = t; x < (int)(sizeof(js::DTab) / 4); x += js::THREADS) dst[x] = src[x];
+        }
+    const int64_t sb = seg_scratch(d, i);
+    const int32_t nseg = f.nseg;
+    for (int j = t; j < nseg; j += js::THREADS) stop_code[sb + j] = -1;
+    int16_t* const fc = coeffs + 64 * d.coef_block;
+    {
+        uint4* z = reinterpret_cast<uint4*>(fc);
+        for (int64_t x = t; x < 8 * d.n_blocks; x += js::THREADS) z[x] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    if (t == 0) {
+        errkey = js::NO_DEFECT;
+        carry_state.pos = 0;
+        carry_state.sk = js::NOSYNC;
+        carry_ord = 0;
+    }
+    __syncthreads();
+
+    // ---- marker: 16 bytes a thread and turn
+    const uint8_t* fb = bytes + sc.offset;
+    uint8_t* cw = comp + sc.offset;
+    const int32_t nb = (int32_t)sc.nbytes;
+    int32_t total_data = 0, all_stops = 0;
+    for (int32_t c0 = 0; c0 < nb; c0 += 16 * js::THREADS) {
+        const int32_t p0 = c0 + 16 * t;
+        const int cnt = max(0, min(16, nb - p0));
+        uint8_t b[16];
+        if (cnt == 16) {
+            const uint4 v = *reinterpret_cast<const uint4*>(fb + p0);
+            const uint32_t vw[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int k = 0; k < 16; ++k) b[k] = (uint8_t)(vw[k >> 2] >> (8 * (k & 3)));
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) b[k] = k < cnt ? fb[p0 + k] : (uint8_t)0;
+        }
+        int prev2 = cnt && p0 >= 2 ? fb[p0 - 2] : 0, prev = cnt && p0 >= 1 ? fb[p0 - 1] : 0;
+        const bool hn = p0 + 16 < nb;
+        const int nx = hn ? fb[p0 + 16] : 0;
+        uint64_t cls = 0;
+        uint32_t nd = 0, ns = 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (k < cnt) {
+                const int cl = js::byte_class(prev2, prev, b[k], k < 15 ? k + 1 < cnt : hn, k < 15 ? b[(k + 1) & 15] : nx);
+                nd += cl == js::B_DATA;
+                ns += cl == js::B_STOP;
+                cls |= (uint64_t)cl << (3 * k);
+                prev2 = prev;
+                prev = b[k];
+            }
+        uint32_t total;
+        const uint32_t incl = block_scan(nd | (ns << 16), tot, &total);  // at most 4096 data bytes and 2048 stops a turn
+        int32_t dpos = total_data + (int32_t)((incl & 0xffff) - nd), spos = all_stops + (int32_t)((incl >> 16) - ns);
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (k < cnt) {
+                const int cl = (int)(cls >> (3 * k)) & 7;
+                if (cl == js::B_DATA) {
+                    cw[dpos ^ 3] = b[k];
+                    ++dpos;
+                } else if (cl == js::B_STOP) {
+                    if (spos < nseg) stop_pos[sb + spos] = dpos;
+                    ++spos;
+                } else if (cl == js::B_CODE) {
+                    if (spos >= 1 && spos <= nseg) stop_code[sb + spos - 1] = b[k];
+                }
+            }
+        total_data += (int32_t)(total & 0xffff);
+        all_stops += (int32_t)(total >> 16);
+    }
+    const int32_t nstops = min(all_stops, nseg);
+    __syncthreads();
+
+    // ---- segments: the data bytes of segment j, its first subsequence among the file's
+    const auto seg_lo = [&](int j) { return j == 0 ? 0 : (j - 1 < nstops ? stop_pos[sb + j - 1] : total_data); };
+    const auto seg_hi = [&](int j) { return j < nstops ? stop_pos[sb + j] : total_data; };
+    int32_t total_sub = 0;
+    for (int32_t j0 = 0; j0 < nseg; j0 += js::THREADS) {
+        const int32_t j = j0 + t;
+        uint32_t ns = 0;
+        if (j < nseg) ns = (uint32_t)max(1, (8 * (seg_hi(j) - seg_lo(j)) + sub - 1) / sub);
+        uint32_t total;
+        const uint32_t incl = block_scan(ns, tot, &total);
+        if (j < nseg) seg_sub[sb + j] = total_sub + (int32_t)(incl - ns);
+        total_sub += (int32_t)total;
+    }
+    if (t == 0) seg_sub[sb + nseg] = total_sub;
+    __syncthreads();
+
+    // ---- units
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(cw);
+    for (int32_t b0 = 0; b0 < total_sub; b0 += js::THREADS) {
+        const int32_t s = b0 + t;
+        const bool live = s < total_sub;
+        int32_t j = 0, start = 0, stop = 0, end = 0, sf = 0;
+        bool first = false, last = false;
+        if (live) {
+            int32_t lo = 0, hi = nseg - 1;
+            while (lo < hi) {
+                const int32_t mid = (lo + hi + 1) >> 1;
+                if (seg_sub[sb + mid] <= s) lo = mid; else hi = mid - 1;
+            }
+            j = lo;
+            const int32_t m = s - seg_sub[sb + j];
+            sf = seg_sub[sb + j] - b0;
+            start = 8 * seg_lo(j) + m * sub;
+            end = 8 * seg_hi(j);
+            first = m == 0;
+            last = s + 1 == seg_sub[sb + j + 1];
+            stop = last ? js::NO_STOP : start + sub;
+        }
+        const bool is_true = live && (first || t == 0);
+        const js::State true_in = first ? js::State{start, 0} : carry_state;
+        const js::State fresh = {start, 0}, park = {last ? end : stop, js::NOSYNC};
+        js::State mine = park, last_in = {-1, -2};
+        int32_t cnt = 0;
+        exits[t] = park;
+        __syncthreads();
+        for (int round = 0; round < js::THREADS + 2; ++round) {
+            js::State in = is_true ? true_in : (t > 0 ? exits[t - 1] : fresh);
+            if (in.sk == js::NOSYNC) in = fresh;
+            int changed = 0;
+            if (live && !js::same(in, last_in)) {
+                js::Result o;
+                js::run<false>(w, end, stop, in, tabs, f, 0, 0, 0, nullptr, &d, o);
+                const js::State e = o.err ? park : o.exit;
+                changed = !js::same(e, mine);
+                mine = e;
+                cnt = o.blocks;
+                last_in = in;
+            }
+            __syncthreads();  // every thread has read its neighbour's exit
+            if (changed) exits[t] = mine;
+            if (!__syncthreads_or(changed)) break;
+        }
+        // ---- write
+        const js::State in = is_true ? true_in : (t > 0 ? exits[t - 1] : fresh);
+        // a thread behind a not-synchronised entry in its segment is behind an error of the true chain
+        const int32_t lastflag = block_scan_max(live && in.sk == js::NOSYNC ? t : -1, reinterpret_cast<int32_t*>(tot));
+        const bool valid = live && lastflag < max(sf, 0);
+        uint32_t total;
+        const uint32_t incl = block_scan((uint32_t)(live ? cnt : 0), tot, &total);
+        pex[t] = (int32_t)(incl - (uint32_t)(live ? cnt : 0));
+        __syncthreads();
+        long long ord = 0;
+        if (live) ord = sf >= 0 ? (long long)(pex[t] - pex[sf]) : carry_ord + pex[t];
+        if (valid) {
+            const int64_t mcu0 = (int64_t)j * f.rst;
+            const int64_t limit = (min(mcu0 + f.rst, (int64_t)f.nmcu) - mcu0) * f.bpm;
+            js::Result o;
+            js::run<true>(w, end, stop, in, tabs, f, ord, limit, mcu0, fc, &d, o);
+            if (o.err) atomicMin(&errkey, js::defect(mcu0 * f.bpm + o.err_ord, o.err_stage, o.err));
+            if (o.done_pos >= 0) {
+                const int code = j < nstops ? stop_code[sb + j] : -1;
+                if (end - o.done_pos >= 8 || code != (j == nseg - 1 ? 0xD9 : 0xD0 + (j & 7)))
+                    atomicMin(&errkey, js::defect(mcu0 * f.bpm + limit - 1, 3, j == nseg - 1 ? R_NO_EOI : R_RESTART));
+            }
+        }
+        __syncthreads();  // carry_* and exits are read
+        if (t == js::THREADS - 1 && live) {
+            carry_state = valid && mine.sk != js::NOSYNC ? mine : park;
+            carry_ord = ord + cnt;
+        }
+        __syncthreads();
+    }
+
+    // ---- predict
+    for (int c = 0; c < f.ncomp; ++c) {
+        const int per = c == 0 && f.ncomp == 3 ? f.hs * f.vs : 1, slot0 = c == 0 ? 0 : f.hs * f.vs + c - 1;
+        const int64_t count = (int64_t)f.nmcu * per;
+        uint32_t carry = 0;
+        for (int64_t q0 = 0; q0 < count; q0 += js::THREADS) {
+            const int64_t q = q0 + t, mcu = q / per;
+            const int slot = slot0 + (int)(q % per);
+            int16_t* blk = nullptr;
+            uint32_t v = 0;
+            bool fl = false;
+            if (q < count) {
+                blk = fc + 64 * js::storage_block(f, mcu, slot);
+                v = (uint32_t)(int32_t)blk[0];
+                fl = q % per == 0 && mcu % f.rst == 0;
+            }
+            const int32_t pred = (int32_t)block_scan_segmented(v, fl, tot, totf, &carry);
+            if (q < count) {
+                // exact up to and including the first block out of range (sums are modulo 2^32); later ones lose to it
+                const int64_t pq = (int64_t)pred * (int64_t)d.qt[c][0];
+                if (pred < -32768 || pred > 32767 || pq < -32768 || pq > 32767) atomicMin(&errkey, js::defect(mcu * f.bpm + slot, 1, R_RANGE));
+                blk[0] = (int16_t)pred;
+            }
+        }
+    }
+    __syncthreads();
+    if (t == 0) {
+        const unsigned long long key = errkey;
+        if (key != js::NO_DEFECT) {
+            d.reason = (int32_t)(key & 31);
+            d.status = AVCER_JPEG_NOT_HANDLED;
+        }
+        status[i] = key != js::NO_DEFECT ? AVCER_JPEG_NOT_HANDLED : AVCER_JPEG_OK;
+    }
+}
+
+// One file of avcer_jpeg_unpack_host: the phases of unpack_kernel as loops over its threads.  Returns the reason.
+int unpack_file_host(const uint8_t* bytes, int64_t n_bytes, const avcer_jpeg_scan& sc, const js::DTab* dtabs, int n_tabs, const Desc& d,
+                     int16_t* coeffs, int64_t n_blocks, int sub) {
+    js::File f;
+    const int r = js::check_file(d, sc, n_bytes, n_tabs, n_blocks, f);
+    if (r != R_OK) return r;
+    js::DTab tabs[6];
+    for (int c = 0; c < f.ncomp; ++c) {
+        if (!dtabs[sc.dc[c]].dc_ok || !dtabs[sc.ac[c]].ok) return R_TABLE;
+        tabs[2 * c] = dtabs[sc.dc[c]];
+        tabs[2 * c + 1] = dtabs[sc.ac[c]];
+    }
+    const int32_t nseg = f.nseg, nb = (int32_t)sc.nbytes;
+    std::vector<int32_t> stop_pos((size_t)nseg, 0), stop_code((size_t)nseg, -1), seg_sub((size_t)nseg + 1, 0);
+    int16_t* const fc = coeffs + 64 * d.coef_block;
+    memset(fc, 0, sizeof(int16_t) * 64 * (size_t)d.n_blocks);
+    unsigned long long errkey = js::NO_DEFECT;
+    // ---- marker
+    const uint8_t* fb = bytes + sc.offset;
+    std::vector<uint32_t> words(((size_t)nb + 3) / 4 + 1, 0u);
+    uint8_t* cw = reinterpret_cast<uint8_t*>(words.data());
+    int32_t total_data = 0, all_stops = 0;
+    for (int32_t p = 0; p < nb; ++p) {
+        const int cl = js::byte_class(p >= 2 ? fb[p - 2] : 0, p >= 1 ? fb[p - 1] : 0, fb[p], p + 1 < nb, p + 1 < nb ? fb[p + 1] : 0);
+        if (cl == js::B_DATA) {
+            cw[total_data ^ 3] = fb[p];
+            ++total_data;
+        } else if (cl == js::B_STOP) {
+            if (all_stops < nseg) stop_pos[(size_t)all_stops] = total_data;
+            ++all_stops;
+        } else if (cl == js::B_CODE) {
+            if (all_stops >= 1 && all_stops <= nseg) stop_code[(size_t)all_stops - 1] = fb[p];
+        }
+    }
+    const int32_t nstops = std::min(all_stops, nseg);
+    // ---- segments
+    const auto seg_lo = [&](int j) { return j == 0 ? 0 : (j - 1 < nstops ? stop_pos[(size_t)j - 1] : total_data); };
+    const auto seg_hi = [&](int j) { return j < nstops ? stop_pos[(size_t)j] : total_data; };
+    int32_t total_sub = 0;
+    for (int32_t j = 0; j < nseg; ++j) {
+        seg_sub[(size_t)j] = total_sub;
+        total_sub += std::max(1, (8 * (seg_hi(j) - seg_lo(j)) + sub - 1) / sub);
+    }
+    seg_sub[(size_t)nseg] = total_sub;
+    // ---- units
+    const uint32_t* w = words.data();
+    constexpr int T = js::THREADS;
+    struct Thread {
+        bool live, first, last, is_true, valid;
+        int32_t j, start, stop, end, sf, cnt;
+        js::State true_in, fresh, park, mine, last_in, in;
+        long long ord;
+    };
+    std::vector<Thread> th((size_t)T);
+    std::vector<js::State> exits((size_t)T), next((size_t)T);
+    js::State carry_state = {0, js::NOSYNC};
+    long long carry_ord = 0;
+    for (int32_t b0 = 0; b0 < total_sub; b0 += T) {
+        for (int t = 0; t < T; ++t) {
+            Thread& x = th[(size_t)t];
+            x = Thread();
+            const int32_t s = b0 + t;
+            x.live = s < total_sub;
+            if (x.live) {
+                x.j = (int32_t)(std::upper_bound(seg_sub.begin(), seg_sub.begin() + nseg, s) - seg_sub.begin()) - 1;
+                const int32_t m = s - seg_sub[(size_t)x.j];
+                x.sf = seg_sub[(size_t)x.j] - b0;
+                x.start = 8 * seg_lo(x.j) + m * sub;
+                x.end = 8 * seg_hi(x.j);
+                x.first = m == 0;
+                x.last = s + 1 == seg_sub[(size_t)x.j + 1];
+                x.stop = x.last ? js::NO_STOP : x.start + sub;
+            }
+            x.is_true = x.live && (x.first || t == 0);
+            x.true_in = x.first ? js::State{x.start, 0} : carry_state;
+            x.fresh = js::State{x.start, 0};
+            x.park = js::State{x.last ? x.end : x.stop, js::NOSYNC};
+            x.mine = x.park;
+            x.last_in = js::State{-1, -2};
+            exits[(size_t)t] = x.park;
+        }
+        for (int round = 0; round < T + 2; ++round) {
+            bool any = false;
+            next = exits;
+            for (int t = 0; t < T; ++t) {
+                Thread& x = th[(size_t)t];
+                js::State in = x.is_true ? x.true_in : (t > 0 ? exits[(size_t)t - 1] : x.fresh);
+                if (in.sk == js::NOSYNC) in = x.fresh;
+                if (x.live && !js::same(in, x.last_in)) {
+                    js::Result o;
+                    js::run<false>(w, x.end, x.stop, in, tabs, f, 0, 0, 0, nullptr, &d, o);
+                    const js::State e = o.err ? x.park : o.exit;
+                    if (!js::same(e, x.mine)) {
+                        any = true;
+                        next[(size_t)t] = e;
+                    }
+                    x.mine = e;
+                    x.cnt = o.blocks;
+                    x.last_in = in;
+                }
+            }
+            exits = next;
+            if (!any) break;
+        }
+        // ---- write
+        int32_t lastflag = -1, pre = 0;
+        std::vector<int32_t> pex((size_t)T, 0);
+        for (int t = 0; t < T; ++t) {
+            Thread& x = th[(size_t)t];
+            x.in = x.is_true ? x.true_in : (t > 0 ? exits[(size_t)t - 1] : x.fresh);
+            if (x.live && x.in.sk == js::NOSYNC) lastflag = t;
+            x.valid = x.live && lastflag < std::max(x.sf, 0);
+            pex[(size_t)t] = pre;
+            pre += x.live ? x.cnt : 0;
+        }
+        for (int t = 0; t < T; ++t) {
+            Thread& x = th[(size_t)t];
+            if (x.live) x.ord = x.sf >= 0 ? (long long)(pex[(size_t)t] - pex[(size_t)x.sf]) : carry_ord + pex[(size_t)t];
+            if (!x.valid) continue;
+            const int64_t mcu0 = (int64_t)x.j * f.rst;
+            const int64_t limit = (std::min(mcu0 + f.rst, (int64_t)f.nmcu) - mcu0) * f.bpm;
+            js::Result o;
+            js::run<true>(w, x.end, x.stop, x.in, tabs, f, x.ord, limit, mcu0, fc, &d, o);
+            if (o.err) errkey = std::min(errkey, js::defect(mcu0 * f.bpm + o.err_ord, o.err_stage, o.err));
+            if (o.done_pos >= 0) {
+                const int code = x.j < nstops ? stop_code[(size_t)x.j] : -1;
+                if (x.end - o.done_pos >= 8 || code != (x.j == nseg - 1 ? 0xD9 : 0xD0 + (x.j & 7)))
+                    errkey = std::min(errkey, js::defect(mcu0 * f.bpm + limit - 1, 3, x.j == nseg - 1 ? R_NO_EOI : R_RESTART));
+            }
+        }
+        const Thread& z = th[(size_t)T - 1];
+        if (z.live) {
+            carry_state = z.valid && z.mine.sk != js::NOSYNC ? z.mine : z.park;
+            carry_ord = z.ord + z.cnt;
+        }
+    }
+    // ---- predict
+    for (int c = 0; c < f.ncomp; ++c) {
+        const int per = c == 0 && f.ncomp == 3 ? f.hs * f.vs : 1, slot0 = c == 0 ? 0 : f.hs * f.vs + c - 1;
+        const int64_t count = (int64_t)f.nmcu * per;
+        uint32_t sum = 0;
+        for (int64_t q = 0; q < count; ++q) {
+            const int64_t mcu = q / per;
+            const int slot = slot0 + (int)(q % per);
+            int16_t* blk = fc + 64 * js::storage_block(f, mcu, slot);
+            const uint32_t v = (uint32_t)(int32_t)blk[0];
+            sum = q % per == 0 && mcu % f.rst == 0 ? v : sum + v;
+            const int32_t pred = (int32_t)sum;
+            const int64_t pq = (int64_t)pred * (int64_t)d.qt[c][0];
+            if (pred < -32768 || pred > 32767 || pq < -32768 || pq > 32767) errkey = std::min(errkey, js::defect(mcu * f.bpm + slot, 1, R_RANGE));
+            blk[0] = (int16_t)pred;
+        }
+    }
+    return errkey == js::NO_DEFECT ? R_OK : (int)(errkey & 31);
+}
+
+int unpack_args(avcer_ctx* ctx, const char* what, const void* bytes, int64_t n_bytes, const void* scan, const void* tabs, int n_tabs,
+                const void* desc, int n, const void* coeffs, int64_t n_blocks, const void* status, int sub_bits, bool device) {
+    const uintptr_t a16 = device ? 15 : 0;  // the kernel moves 16 bytes at a time
+    if (!bytes || !scan || !tabs || !desc || !coeffs || !status || n <= 0 || n_tabs <= 0 || n_bytes <= 0 || n_blocks <= 0 ||
+        n_blocks >= (1LL << 31) - 2 * (int64_t)n || ((uintptr_t)bytes & a16) || ((uintptr_t)coeffs & (a16 | 1)) ||
+        ((uintptr_t)desc & (a16 | 7)) || ((uintptr_t)scan & 7) || ((uintptr_t)status & 3) ||
+        (sub_bits != 0 && (sub_bits < 128 || sub_bits > js::MAX_SUB_BITS || sub_bits % 32 != 0)))
+        return set_err(ctx, AVCER_EINVAL,
+                       "%s: bad arguments (n %d, %d tables, %lld bytes, %lld blocks < 2^31; sub_bits %d: 0 or a multiple of 32 in [128, 2^20]; "
+                       "bytes, coefficients and descriptors 16-byte aligned)",
+                       what, n, n_tabs, (long long)n_bytes, (long long)n_blocks, sub_bits);
+    return AVCER_OK;
+}
+
+}  // namespace
+
+extern "C" int avcer_jpeg_scan_batch(avcer_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, uint8_t* bytes, int64_t cap_bytes,
+                                     avcer_jpeg_desc* desc, avcer_jpeg_scan* scan, avcer_jpeg_tab* tabs, int cap_tabs, int threads,
+                                     int32_t* n_tabs, int64_t* bytes_needed, int64_t* blocks_needed) {
+    // ctx may be NULL (host-only call, no device needed): errors then come back as the code alone
+    if (n < 0 || (n && (!files || !lens || !desc || !scan)) || cap_bytes < 0 || (cap_bytes && !bytes) || cap_tabs < 0 || (cap_tabs && !tabs) ||
+        !n_tabs)
+        return set_err(ctx, AVCER_EINVAL, "jpeg_scan_batch: bad arguments");
+    try {
+        struct Found {  // what the header of one file says beyond its descriptor
+            avcer_jpeg_tab tab[6];  // [2 c] the DC and [2 c + 1] the AC table of component c, as their DHT segments state them
+            size_t at = 0;          // the first entropy-coded byte
+            int restart = 0;
+        };
+        std::vector<Found> found((size_t)n);
+        const int nt = std::max(1, std::min(pool_size(threads), n));
+        each_index(n, nt, [&](int i) {
+            std::unique_ptr<Header> h(new Header());
+            const int r = parse_header(files[i], lens[i] < 0 ? 0 : (size_t)lens[i], *h);  // no bytes: R_NO_SOI
+            desc[i] = h->d;
+            desc[i].reason = r;
+            if (r != R_OK) return;
+            Found& fo = found[(size_t)i];
+            memset(fo.tab, 0, sizeof(fo.tab));
+            for (int c = 0; c < h->d.ncomp; ++c)
+                for (int k = 0; k < 2; ++k) {
+                    const Huff& t = k ? h->ac[h->ta[c]] : h->dc[h->td[c]];
+                    memcpy(fo.tab[2 * c + k].bits, t.bits, sizeof(t.bits));
+                    fo.tab[2 * c + k].bits[0] = 0;
+                    memcpy(fo.tab[2 * c + k].vals, t.vals, sizeof(t.vals));
+                }
+            fo.at = h->scan;
+            fo.restart = h->restart;
+        });
+        // in file order: blocks as in avcer_jpeg_entropy_batch, the next free 16-byte aligned bytes, tables by content
+        std::map<std::string, int> seen;
+        std::vector<const avcer_jpeg_tab*> list;
+        int64_t used_blocks = 0, need_blocks = 0, used_bytes = 0, need_bytes = 0;
+        for (int i = 0; i < n; ++i) {
+            Desc& d = desc[i];
+            int r = d.reason;
+            memset(&scan[i], 0, sizeof(scan[i]));
+            if (r == R_OK) {
+                const Found& fo = found[(size_t)i];
+                const int64_t nb = lens[i] - (int64_t)fo.at, room = (nb + 15) & ~(int64_t)15;
+                need_blocks += d.n_blocks;
+                need_bytes += room;
+                bool fits = room <= cap_bytes - used_bytes;
+                avcer_jpeg_scan s;
+                memset(&s, 0, sizeof(s));
+                for (int c = 0; c < d.ncomp; ++c)
+                    for (int k = 0; k < 2; ++k) {
+                        const avcer_jpeg_tab* t = &fo.tab[2 * c + k];
+                        const auto at = seen.emplace(std::string(reinterpret_cast<const char*>(t), sizeof(*t)), (int)list.size());
+                        if (at.second) list.push_back(t);
+                        (k ? s.ac : s.dc)[c] = at.first->second;
+                        fits = fits && at.first->second < cap_tabs;
+                    }
+                if (fits) {
+                    s.offset = used_bytes;
+                    s.nbytes = nb;
+                    s.restart = fo.restart;
+                    scan[i] = s;
+                    used_bytes += room;
+                } else {
+                    r = R_NO_SPACE;
+                }
+            }
+            d.coef_block = used_blocks;
+            if (r == R_OK) used_blocks += d.n_blocks; else d.n_blocks = 0;
+            d.reason = r;
+            d.status = r == R_OK ? AVCER_JPEG_OK : AVCER_JPEG_NOT_HANDLED;
+        }
+        for (size_t k = 0; k < list.size() && (int)k < cap_tabs; ++k) tabs[k] = *list[k];
+        *n_tabs = (int32_t)list.size();
+        if (bytes_needed) *bytes_needed = need_bytes;
+        if (blocks_needed) *blocks_needed = need_blocks;
+        each_index(n, nt, [&](int i) {
+            if (desc[i].status != AVCER_JPEG_OK) return;
+            const avcer_jpeg_scan& s = scan[i];
+            memcpy(bytes + s.offset, files[i] + found[(size_t)i].at, (size_t)s.nbytes);
+            memset(bytes + s.offset + s.nbytes, 0, (size_t)(((s.nbytes + 15) & ~(int64_t)15) - s.nbytes));
+        });
+    } catch (...) {
+        return set_err(ctx, AVCER_ENOMEM, "jpeg_scan_batch: out of host memory");
+    }
+    return AVCER_OK;
+}
+
+extern "C" int avcer_jpeg_unpack(avcer_ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const avcer_jpeg_scan* scan, const avcer_jpeg_tab* tabs,
+                                 int n_tabs, avcer_jpeg_desc* desc, int n, int16_t* coeffs, int64_t n_blocks, int32_t* status, int sub_bits,
+                                 avcer_stream_t stream) {
+    if (!ctx) return AVCER_EINVAL;
+    TRY(unpack_args(ctx, "jpeg_unpack", bytes, n_bytes, scan, tabs, n_tabs, desc, n, coeffs, n_blocks, status, sub_bits, true));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    js::DTab* dtabs = nullptr;
+    uint8_t* comp = nullptr;
+    int32_t *stop_pos = nullptr, *stop_code = nullptr, *seg_sub = nullptr;
+    const size_t per_block = (size_t)n_blocks + 2 * (size_t)n;
+    const auto carve = [&](Arena& a) {
+        dtabs = a.get<js::DTab>(sizeof(js::DTab) * (size_t)n_tabs);       // the derived tables
+        comp = a.get<uint8_t>((size_t)n_bytes + 16);                      // the unstuffed bytes, file by file where `bytes` has them
+        stop_pos = a.get<int32_t>(sizeof(int32_t) * per_block);           // per segment: the data bytes in front of its stop,
+        stop_code = a.get<int32_t>(sizeof(int32_t) * per_block);          // ... the marker code there (-1: none),
+        seg_sub = a.get<int32_t>(sizeof(int32_t) * per_block);            // ... its first subsequence among the file's
+    };
+    const size_t ws = Arena().run(carve);
+    void* base = nullptr;
+    TRY(ws_reserve(ctx, WS_JPEG, ws, &base));
+    if (Arena(base, ws).run(carve) != ws || !seg_sub || ((uintptr_t)comp & 15)) return set_err(ctx, AVCER_ENOMEM, "jpeg_unpack workspace arithmetic");
+    unpack_tabs_kernel<<<(unsigned)((n_tabs + 63) / 64), 64, 0, st>>>(tabs, n_tabs, dtabs);
+    HIP_TRY(ctx, hipGetLastError());
+    unpack_kernel<<<(unsigned)n, js::THREADS, 0, st>>>(bytes, n_bytes, scan, dtabs, n_tabs, desc, coeffs, n_blocks, status,
+                                                        sub_bits ? sub_bits : js::DEFAULT_SUB_BITS, comp, stop_pos, stop_code, seg_sub);
+    HIP_TRY(ctx, hipGetLastError());
+    return AVCER_OK;
+}
+
+extern "C" int avcer_jpeg_unpack_host(avcer_ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const avcer_jpeg_scan* scan,
+                                      const avcer_jpeg_tab* tabs, int n_tabs, avcer_jpeg_desc* desc, int n, int16_t* coeffs, int64_t n_blocks,
+                                      int32_t* status, int sub_bits) {
+    // ctx may be NULL.  Not a product path (include/avcer_hip.h): the device algorithm, phase by phase, for tests and sanitisers
+    if (int rc = unpack_args(ctx, "jpeg_unpack_host", bytes, n_bytes, scan, tabs, n_tabs, desc, n, coeffs, n_blocks, status, sub_bits, false)) return rc;
+    try {
+        std::vector<js::DTab> dtabs((size_t)n_tabs);
+        for (int k = 0; k < n_tabs; ++k) js::derive_tab(tabs[k], dtabs[(size_t)k]);
+        each_index(n, std::min(pool_size(0), n), [&](int i) {
+            if (desc[i].status == AVCER_JPEG_OK) {
+                const int r = unpack_file_host(bytes, n_bytes, scan[i], dtabs.data(), n_tabs, desc[i], coeffs, n_blocks,
+                                               sub_bits ? sub_bits : js::DEFAULT_SUB_BITS);
+                if (r != R_OK) {
+                    desc[i].reason = r;
+                    desc[i].status = AVCER_JPEG_NOT_HANDLED;
+                }
+            }
+            status[i] = desc[i].status;
+        });
+    } catch (...) {
+        return set_err(ctx, AVCER_ENOMEM, "jpeg_unpack_host: out of host memory");
+    }
     return AVCER_OK;
 }

@@ -498,6 +498,29 @@ class Engine:
                                              int(cap_bytes), _ptr(offsets), _ptr(status), _ptr(need), self._stream()))
         return out, offsets, status, need
 
+    def jpeg_unpack(self, data, scan, tabs, n_tabs: int, desc, n: int, n_blocks: int, sub_bits: int = 0, out=None):
+        """The Huffman decode of the JPEG reader on the device (avcer_jpeg_unpack): data u8 = the entropy-coded bytes, scan and tabs
+        = n records of struct avcer_jpeg_scan and n_tabs of struct avcer_jpeg_tab as bytes, desc = n records of struct avcer_jpeg_desc
+        as bytes, all on the device as avcer_jpeg_scan_batch wrote them (avcer_amd/jpeg.py) -> (coefficients int16 [64 * n_blocks],
+        status i32 [n]), both on the device; status and reason of `desc` are updated in place.  Exactly what
+        avcer_jpeg_entropy_batch computes from the same files.  sub_bits: bits per subsequence, 0 = the library's default, else a
+        multiple of 32 of at least 128; the result does not depend on it."""
+        from .jpeg import SCAN as _SCAN, TAB as _TAB
+
+        for name, x, size in (("data", data, 1), ("scan", scan, _SCAN.itemsize * n), ("tabs", tabs, _TAB.itemsize * n_tabs),
+                              ("desc", desc, _JPEG_DESC_BYTES * n)):
+            if x.dtype != torch.uint8 or x.numel() < size or not x.is_cuda or not x.is_contiguous():
+                raise ValueError(f"jpeg_unpack: {name} must be a contiguous uint8 tensor of at least {size} bytes on the device")
+        if n <= 0 or n_tabs <= 0 or n_blocks <= 0 or sub_bits < 0 or (sub_bits and (sub_bits < 128 or sub_bits % 32)):
+            raise ValueError("jpeg_unpack: n, n_tabs and n_blocks positive; sub_bits 0 or a multiple of 32 of at least 128")
+        coeffs = self._new(64 * int(n_blocks), dtype=torch.int16) if out is None else out
+        if coeffs.dtype != torch.int16 or coeffs.numel() < 64 * n_blocks or not coeffs.is_cuda or not coeffs.is_contiguous():
+            raise ValueError("jpeg_unpack: out must be a contiguous int16 [>= 64 * n_blocks] on the device")
+        status = self._new(int(n), dtype=torch.int32)
+        self._check(self.lib.avcer_jpeg_unpack(self.ctx, _ptr(data), int(data.numel()), _ptr(scan), _ptr(tabs), int(n_tabs), _ptr(desc),
+                                               int(n), _ptr(coeffs), int(n_blocks), _ptr(status), int(sub_bits), self._stream()))
+        return coeffs, status
+
     def jpeg_rgb(self, coeffs, desc, n: int, n_blocks: int, hmax: int, wmax: int):
         """The same files at full size -> (canvas u8 [n,hmax,wmax,3] RGB: image i in the top left corner of slot i, zeros around it;
         flags i32 [n] as jpeg_tiles returns them)."""

@@ -10,6 +10,10 @@ result is bit-identical to `PIL.Image.open(...).convert("RGB")` (libjpeg-turbo's
 A file the parser does not handle -- a PNG under a .jpg name, a progressive or CMYK file, a truncated one, ... -- goes through the
 PIL lines of `video_pipeline.read_face_dir` unchanged; what PIL does with it (decode it, or raise OSError) is what the caller sees.
 Both functions also return, per file, which path served it: "device" or "pil".
+
+With entropy="device" the host parses the headers only (`scan_batch`), the files' entropy-coded bytes cross instead of the
+coefficients, and `Engine.jpeg_unpack` Huffman-decodes them on the device (csrc/jpeg.hip avcer_jpeg_unpack); tiles, canvas and paths
+are the same.
 """
 from __future__ import annotations
 
@@ -28,6 +32,10 @@ DESC = np.dtype([("status", "<i4"), ("reason", "<i4"), ("width", "<i4"), ("heigh
                  ("vs", "<i4"), ("bw", "<i4", 3), ("bh", "<i4", 3), ("tq", "<i4", 3), ("coef_block", "<i8"), ("n_blocks", "<i8"),
                  ("qt", "<u2", (3, 64))])
 assert DESC.itemsize == 464
+# struct avcer_jpeg_scan, struct avcer_jpeg_tab (the device entropy decoder's view of a file and of a Huffman table)
+SCAN = np.dtype([("offset", "<i8"), ("nbytes", "<i8"), ("restart", "<i4"), ("dc", "<i4", 3), ("ac", "<i4", 3), ("pad", "<i4")])
+TAB = np.dtype([("bits", "u1", 17), ("vals", "u1", 256), ("pad", "u1", 15)])
+assert SCAN.itemsize == 48 and TAB.itemsize == 288
 
 
 def probe(lib, blob: bytes) -> np.ndarray:
@@ -65,6 +73,47 @@ def entropy_batch(lib, blobs, coeffs: np.ndarray, desc: np.ndarray, threads: int
     if rc != 0:
         raise RuntimeError(f"avcer_jpeg_entropy_batch failed: {rc}")
     return int(need.value)
+
+
+def scan_batch(lib, blobs, data: np.ndarray, desc: np.ndarray, scan: np.ndarray, tabs: np.ndarray, threads: int = 0, ctx=None,
+               cap_bytes: int | None = None, cap_tabs: int | None = None):
+    """avcer_jpeg_scan_batch: the files `blobs` -> `desc[:n]` as entropy_batch leaves them before its scan walk, `scan[:n]` (SCAN
+    records), the batch's Huffman tables de-duplicated in `tabs` (TAB records) and every handled file's entropy-coded bytes in `data`
+    (u8, room for `cap_bytes`, default all of it).  The host walks no bit stream.  Returns (tables, bytes, blocks) that all files
+    with a supported header need together; a file that did not fit `data` or `tabs` has reason R_NO_SPACE."""
+    n = len(blobs)
+    files = (C.c_char_p * max(n, 1))(*blobs)
+    lens = np.array([len(b) for b in blobs], dtype=np.int64)
+    cap_b = data.size if cap_bytes is None else int(cap_bytes)
+    cap_t = len(tabs) if cap_tabs is None else int(cap_tabs)
+    assert data.dtype == np.uint8 and data.flags.c_contiguous and cap_b <= data.size
+    assert desc.dtype == DESC and desc.flags.c_contiguous and len(desc) >= n
+    assert scan.dtype == SCAN and scan.flags.c_contiguous and len(scan) >= n
+    assert tabs.dtype == TAB and tabs.flags.c_contiguous and cap_t <= len(tabs)
+    n_tabs, need_bytes, need_blocks = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+    rc = lib.avcer_jpeg_scan_batch(ctx, C.cast(files, C.c_void_p), lens.ctypes.data_as(C.c_void_p), n, data.ctypes.data_as(C.c_void_p),
+                                   cap_b, desc.ctypes.data_as(C.c_void_p), scan.ctypes.data_as(C.c_void_p),
+                                   tabs.ctypes.data_as(C.c_void_p), cap_t, host_threads(int(threads)), C.byref(n_tabs),
+                                   C.byref(need_bytes), C.byref(need_blocks))
+    if rc != 0:
+        raise RuntimeError(f"avcer_jpeg_scan_batch failed: {rc}")
+    return int(n_tabs.value), int(need_bytes.value), int(need_blocks.value)
+
+
+def unpack_host(lib, data: np.ndarray, scan: np.ndarray, tabs: np.ndarray, desc: np.ndarray, n_blocks: int, sub_bits: int = 0):
+    """avcer_jpeg_unpack_host: the device entropy decoder's algorithm as host loops (for the tests; not a product path).  The
+    arrays as scan_batch wrote them -> (coefficients int16 [n_blocks, 64], status i32 [n]); `desc` gets status and reason."""
+    n = len(desc)
+    assert data.dtype == np.uint8 and data.flags.c_contiguous and scan.dtype == SCAN and scan.flags.c_contiguous and len(scan) >= n
+    assert tabs.dtype == TAB and tabs.flags.c_contiguous and desc.dtype == DESC and desc.flags.c_contiguous
+    coeffs = np.zeros((int(n_blocks), 64), dtype=np.int16)
+    status = np.zeros(n, dtype=np.int32)
+    rc = lib.avcer_jpeg_unpack_host(None, data.ctypes.data_as(C.c_void_p), data.size, scan.ctypes.data_as(C.c_void_p),
+                                    tabs.ctypes.data_as(C.c_void_p), len(tabs), desc.ctypes.data_as(C.c_void_p), n,
+                                    coeffs.ctypes.data_as(C.c_void_p), int(n_blocks), status.ctypes.data_as(C.c_void_p), int(sub_bits))
+    if rc != 0:
+        raise RuntimeError(f"avcer_jpeg_unpack_host failed: {rc}")
+    return coeffs, status
 
 
 # ---------------------------------------------------------------------------------------------------- numpy statement (tests)
@@ -170,6 +219,7 @@ class _Staging:
         self.coeffs = None
         self.desc = None
         self.files = None  # encode_images(entropy="device"): the files on their way to the host
+        self.wire = None   # decode_*(entropy="device"): descriptors, scan records, tables and entropy-coded bytes, one copy
         self.event = None
 
     def reserve(self, blocks: int, n: int):
@@ -179,6 +229,13 @@ class _Staging:
             self.coeffs = torch.empty(64 * (blocks + blocks // 4 + 1024), dtype=torch.int16, pin_memory=True)
         if self.desc is None or self.desc.numel() < DESC.itemsize * n:
             self.desc = torch.empty(DESC.itemsize * (n + n // 4 + 64), dtype=torch.uint8, pin_memory=True)
+
+    def reserve_wire(self, nbytes: int):
+        if self.event is not None:
+            self.event.synchronize()
+        if self.wire is None or self.wire.numel() < nbytes:
+            self.wire = torch.empty(nbytes + nbytes // 4 + 4096, dtype=torch.uint8, pin_memory=True)
+        return self.wire
 
     def reserve_files(self, nbytes: int):
         if self.files is None or self.files.numel() < nbytes:
@@ -228,9 +285,49 @@ def _to_device(engine, blobs, threads: int):
     return c_dev, d_dev, used, host
 
 
-def _flags_to_host(engine, flags):
+TABS_ROOM = 64  # tables a batch may carry before the staging is grown: a folder one encoder wrote carries four
+
+
+def _to_device_unpacked(engine, blobs, threads: int, sub_bits: int = 0):
+    """entropy="device": headers on the host (scan_batch; no bit stream is walked), ONE copy of descriptors, scan records, tables
+    and entropy-coded bytes, avcer_jpeg_unpack -> (coeffs on the device, desc on the device, n_blocks, desc records on the host as the
+    HEADERS left them, status i32 [n] on the device: what the device decode made of every file)."""
+    st = engine.__dict__.setdefault("_jpeg_staging", _Staging())
+    n = len(blobs)
+    cap_bytes, cap_tabs = sum(len(b) for b in blobs) + 16 * n, TABS_ROOM
+    while True:
+        at_scan = DESC.itemsize * n
+        at_tabs = at_scan + SCAN.itemsize * n
+        at_data = at_tabs + TAB.itemsize * cap_tabs  # every part starts 16-byte aligned: 464, 48 and 288 are multiples of 16
+        wire = st.reserve_wire(at_data + cap_bytes).numpy()
+        desc, scan = wire[:at_scan].view(DESC), wire[at_scan:at_tabs].view(SCAN)
+        n_tabs, need_bytes, _ = scan_batch(engine.lib, blobs, wire[at_data:at_data + cap_bytes], desc, scan,
+                                           wire[at_tabs:at_data].view(TAB), threads, engine.ctx)
+        if not (desc["reason"] == R_NO_SPACE).any():
+            break
+        cap_bytes, cap_tabs = max(cap_bytes, need_bytes), max(cap_tabs, n_tabs)
+    host = desc.copy()
+    used = int((desc["coef_block"] + desc["n_blocks"]).max()) if n else 0
+    if used == 0:
+        return None, None, 0, host, None
+    ok = scan[desc["status"] == OK]
+    n_bytes = int((ok["offset"] + ((ok["nbytes"] + 15) & ~15)).max())
+    dev = engine.device
+    w_dev = st.wire[:at_data + n_bytes].to(dev, non_blocking=True)
+    st.event = torch.cuda.Event()
+    st.event.record(torch.cuda.current_stream(dev))
+    d_dev = w_dev[:at_scan]
+    c_dev, status = engine.jpeg_unpack(w_dev[at_data:], w_dev[at_scan:at_tabs], w_dev[at_tabs:at_data], min(n_tabs, cap_tabs), d_dev, n, used,
+                                       sub_bits)
+    return c_dev, d_dev, used, host, status
+
+
+def _flags_to_host(engine, flags, status=None):
     """Queues the copy of kernel A's per-file flags (i32 [n] on the device) into pinned memory and returns the function that
-    waits for it and hands out the numpy array: the caller does its other host work in between."""
+    waits for it and hands out the numpy array: the caller does its other host work in between.  With `status` (i32 [n] on the
+    device, avcer_jpeg_unpack's) a file the device decode refused counts as flagged: the same copy, the same wait."""
+    if status is not None:
+        flags = flags | (status != OK).to(flags.dtype)
     host = torch.empty(flags.shape, dtype=flags.dtype, pin_memory=True)
     host.copy_(flags, non_blocking=True)
     done = torch.cuda.Event()
@@ -243,21 +340,35 @@ def _flags_to_host(engine, flags):
     return wait
 
 
-def decode_tiles(engine, blobs, threads: int = 0):
+def _check_entropy(entropy):
+    if entropy not in ("host", "device"):
+        raise ValueError(f'entropy must be "host" or "device", not {entropy!r}')
+
+
+def decode_tiles(engine, blobs, threads: int = 0, entropy: str = "host"):
     """The files `blobs` -> (tiles u8 [n,224,224,3] RGB on the device, paths): tile i is
-    Image.open(file i).convert("RGB").resize((224, 224), NEAREST); paths[i] is "device" or "pil"."""
+    Image.open(file i).convert("RGB").resize((224, 224), NEAREST); paths[i] is "device" or "pil".
+    entropy="device": the host parses the headers only and the files' bytes cross, avcer_jpeg_unpack Huffman-decodes them on the
+    device (`threads` then serves the header pass); tiles and paths are the same."""
+    _check_entropy(entropy)
     n = len(blobs)
     tiles = torch.empty(n, 224, 224, 3, dtype=torch.uint8, device=engine.device)
     if n == 0:
         return tiles, []
-    c_dev, d_dev, used, desc = _to_device(engine, blobs, threads)
+    if entropy == "device":
+        c_dev, d_dev, used, desc, refused = _to_device_unpacked(engine, blobs, threads)
+    else:
+        c_dev, d_dev, used, desc = _to_device(engine, blobs, threads)
+        refused = None
     status = desc["status"].copy()
-    flags = _flags_to_host(engine, engine.jpeg_tiles(c_dev, d_dev, n, used, out=tiles)[1]) if used else None
+    flags = _flags_to_host(engine, engine.jpeg_tiles(c_dev, d_dev, n, used, out=tiles)[1], refused) if used else None
     # the files the parser refused go through PIL while the kernels run; only then the range guard of kernel A is read (the one
     # wait of this call: `paths` cannot be known before it), and a file it flagged follows them
     host = {i: _pil_tile(blobs[i]) for i in range(n) if status[i] != OK}
     if flags is not None:
         for i in np.nonzero(flags())[0]:
+            if int(i) in host:  # refused by its header already
+                continue
             status[i] = NOT_HANDLED
             host[int(i)] = _pil_tile(blobs[i])
     if host:
@@ -266,21 +377,28 @@ def decode_tiles(engine, blobs, threads: int = 0):
     return tiles, ["device" if s == OK else "pil" for s in status]
 
 
-def decode_canvas(engine, blobs, threads: int = 0):
+def decode_canvas(engine, blobs, threads: int = 0, entropy: str = "host"):
     """The files `blobs` at full size -> ((canvas u8 [max(n,1), max h, max w, 3] on the device, rects i32 [n,5] = (i, 0, 0, w, h)),
-    paths): the layout of video_pipeline.read_face_crops, the input of Engine.crop_resize_linear."""
+    paths): the layout of video_pipeline.read_face_crops, the input of Engine.crop_resize_linear.  `entropy`: as in decode_tiles."""
+    _check_entropy(entropy)
     n = len(blobs)
     dev = engine.device
     if n == 0:
         return (torch.zeros(1, 1, 1, 3, dtype=torch.uint8, device=dev), np.zeros((0, 5), dtype=np.int32)), []
-    c_dev, d_dev, used, desc = _to_device(engine, blobs, threads)
+    if entropy == "device":
+        c_dev, d_dev, used, desc, refused = _to_device_unpacked(engine, blobs, threads)
+    else:
+        c_dev, d_dev, used, desc = _to_device(engine, blobs, threads)
+        refused = None
     status = desc["status"].copy()
     rest = {i: _pil_rgb(blobs[i]) for i in range(n) if status[i] != OK}
     sizes = [(rest[i].shape[1], rest[i].shape[0]) if i in rest else (int(desc["width"][i]), int(desc["height"][i])) for i in range(n)]
     wmax, hmax = max(s[0] for s in sizes), max(s[1] for s in sizes)
     if used:
         canvas, flags = engine.jpeg_rgb(c_dev, d_dev, n, used, hmax, wmax)
-        for i in np.nonzero(_flags_to_host(engine, flags)())[0]:  # the range guard of kernel A; such a file's slot is zero so far
+        for i in np.nonzero(_flags_to_host(engine, flags, refused)())[0]:  # the range guard of kernel A; such a file's slot is zero so far
+            if int(i) in rest:  # refused by its header already
+                continue
             status[i] = NOT_HANDLED
             rest[int(i)] = _pil_rgb(blobs[i])
             if rest[int(i)].shape[:2] != (sizes[i][1], sizes[i][0]):

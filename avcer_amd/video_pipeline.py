@@ -175,11 +175,12 @@ def _read_blob(path: str) -> bytes:
         return f.read()
 
 
-def read_face_dir_device(engine: Engine, path_images: str, total_frames: int, track: str = "00", threads: int = 0):
+def read_face_dir_device(engine: Engine, path_images: str, total_frames: int, track: str = "00", threads: int = 0, entropy: str = "host"):
     """`read_face_dir` with the decode on the device (avcer_amd/jpeg.py): the same files, the same meaning, the same
     FileNotFoundError for a missing track directory -> (frames u8 [total_frames,224,224,3] RGB ON THE DEVICE, bit-identical to
     read_face_dir's, present bool [total_frames]).  A file the native parser does not handle is decoded by PIL as there.
-    `threads`: host threads of the entropy pass, at most 16 (0: OMP_NUM_THREADS, or 16)."""
+    `threads`: host threads of the entropy pass, at most 16 (0: OMP_NUM_THREADS, or 16).  `entropy`: where the files are
+    Huffman-decoded, "host" (the default) or "device" (jpeg.decode_tiles); the tiles are the same."""
     from . import jpeg
 
     folder = os.path.join(path_images, track)
@@ -187,7 +188,7 @@ def read_face_dir_device(engine: Engine, path_images: str, total_frames: int, tr
     idx = [i for i in range(total_frames) if str(i).zfill(6) + ".jpg" in names]
     present = np.zeros(total_frames, dtype=bool)
     present[idx] = True
-    tiles, _ = jpeg.decode_tiles(engine, [_read_blob(os.path.join(folder, str(i).zfill(6) + ".jpg")) for i in idx], threads)
+    tiles, _ = jpeg.decode_tiles(engine, [_read_blob(os.path.join(folder, str(i).zfill(6) + ".jpg")) for i in idx], threads, entropy=entropy)
     if len(idx) == total_frames:
         return tiles, present
     frames = torch.zeros(total_frames, 224, 224, 3, dtype=torch.uint8, device=engine.device)
@@ -196,17 +197,17 @@ def read_face_dir_device(engine: Engine, path_images: str, total_frames: int, tr
     return frames, present
 
 
-def read_face_crops_device(engine: Engine, path_images: str, frame_idx, track: str = "00"):
+def read_face_crops_device(engine: Engine, path_images: str, frame_idx, track: str = "00", entropy: str = "host"):
     """`read_face_crops` with the decode on the device: (canvas u8 [max(m,1), max h, max w, 3] on the device, rects i32 [m,5])."""
     from . import jpeg
 
     blobs = [_read_blob(os.path.join(path_images, track, str(int(i)).zfill(6) + ".jpg")) for i in np.asarray(frame_idx).reshape(-1)]
-    return jpeg.decode_canvas(engine, blobs)[0]
+    return jpeg.decode_canvas(engine, blobs, entropy=entropy)[0]
 
 
 def preprocess_video_and_predict(engine: Engine, path_images: str = "", save_path: str = "", fps: float = 30, total_frames: int = 0,
                                  flag_save_prob: bool = False, mode: int = MODE_DEFAULT, flag_heatmaps: bool = False,
-                                 model_heatmaps: str = "static", decode: str = "device"):
+                                 model_heatmaps: str = "static", decode: str = "device", jpeg_entropy: str = "host"):
     """`get_prob_video.preprocess_video_and_predict` (get_prob_video.py:67-204) with the reference's argument meaning, on the HIP
     path: the face-crop directory of one video in, the two per-frame tables out -- (dynamic logits, static probabilities), float32
     [total_frames, 7] in DICT_EMO_VIDEO column order -- and `dynamic__<video>.csv` / `static__<video>.csv` under `save_path` when
@@ -216,17 +217,20 @@ def preprocess_video_and_predict(engine: Engine, path_images: str = "", save_pat
     The visual call then runs through `engine.guarded`, maps included.  `model_heatmaps` other than "static" / "dynamic" raises
     ValueError before any work (the reference dies with UnboundLocalError at its first heat-map frame).
     `decode`: "device" reads the crops through read_face_dir_device / read_face_crops_device (host entropy pass, HIP pixel pass),
-    "pil" through read_face_dir / read_face_crops; the tiles are bit-identical, so tables, CSV files and heat maps are the same."""
+    "pil" through read_face_dir / read_face_crops; the tiles are bit-identical, so tables, CSV files and heat maps are the same.
+    `jpeg_entropy` (with decode="device"): where the files are Huffman-decoded, "host" (the default) or "device"; the same tiles."""
     from . import io_formats
 
     if decode not in ("device", "pil"):
         raise ValueError(f"decode must be 'device' or 'pil', got {decode!r}")
+    if jpeg_entropy not in ("host", "device"):
+        raise ValueError(f'jpeg_entropy must be "host" or "device", not {jpeg_entropy!r}')
     if decode == "device":
         def read_dir(p, t):
-            return read_face_dir_device(engine, p, t)
+            return read_face_dir_device(engine, p, t, entropy=jpeg_entropy)
 
         def read_crops(p, idx):
-            return read_face_crops_device(engine, p, idx)
+            return read_face_crops_device(engine, p, idx, entropy=jpeg_entropy)
     else:
         def read_dir(p, t):
             frames, present = read_face_dir(p, t)

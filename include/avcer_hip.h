@@ -82,7 +82,9 @@ enum {
  *      decoded behind a host entropy pass) joined under 8 the same way.
  *      avcer_jpeg_quant_tables, avcer_jpeg_plan, avcer_jpeg_forward, avcer_jpeg_write_batch (the same files WRITTEN: forward pass
  *      on the device, entropy coding on the host) joined under 8 the same way: four more symbols, the descriptor unchanged.
- *      avcer_jpeg_pack (entropy coding on the device: whole files leave it) joined under 8 the same way: one more symbol. */
+ *      avcer_jpeg_pack (entropy coding on the device: whole files leave it) joined under 8 the same way: one more symbol.
+ *      avcer_jpeg_scan_batch, avcer_jpeg_unpack, avcer_jpeg_unpack_host with their structs avcer_jpeg_tab and avcer_jpeg_scan: entropy
+ *      DECODING on the device, joined under 8 the same way: three more symbols, the descriptor unchanged. */
 #define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
@@ -492,6 +494,58 @@ int avcer_jpeg_write_batch(avcer_ctx* ctx, const int16_t* coeffs_host, avcer_jpe
  *   ceil((20 + 63 * 26) / 8) = 208) comes from the context's JPEG workspace.  n_blocks < 2^31. */
 int avcer_jpeg_pack(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_blocks, const avcer_jpeg_desc* desc, int n, uint8_t* out,
                     int64_t cap_bytes, int64_t* offsets, int32_t* status, int64_t* bytes_needed, avcer_stream_t stream);
+
+/* Huffman DECODING on the device: avcer_jpeg_entropy_batch's scan walk as self-synchronising subsequence decoding (Klein & Wiseman;
+ * Weissenberger & Schmidt), so that the files' bytes, and not 128 bytes of coefficients per block, cross to the device, and no
+ * host thread walks a bit stream.  Same contract as avcer_jpeg_entropy_batch, tolerance zero: the same status and reason for every
+ * file, the same coefficients for every file that is OK.  avcer_jpeg_tiles and avcer_jpeg_rgb run behind it unchanged.
+ *
+ * avcer_jpeg_tab: one Huffman table as its DHT segment states it (bits[l] = codes of length l, bits[0] unused; the symbols).
+ * avcer_jpeg_scan: one file's entropy-coded bytes -- bytes[offset .. offset + nbytes), offset a multiple of 16 -- its restart
+ *   interval (0: none) and, per component, the index of its DC and AC table in the call's table list.
+ *
+ * avcer_jpeg_scan_batch (HOST code and host pointers, ctx may be NULL, no device is touched): the headers of n files -> desc[n]
+ *   exactly as avcer_jpeg_entropy_batch leaves them before its scan walk (the same reasons, the same refusal of a header that
+ *   claims more blocks than its bytes can hold, coef_block in file order), scan[n], the tables of the batch de-duplicated by
+ *   content in tabs (a folder one encoder wrote carries four), and a copy of every handled file's bytes from its first
+ *   entropy-coded byte to its end in bytes_host, back to back, each start 16-byte aligned.  The entropy-coded bytes are NOT walked:
+ *   markers are found on the device.  A file whose bytes do not fit cap_bytes, or whose tables do not fit cap_tabs, is reason 12 and
+ *   takes nothing; *bytes_needed, *n_tabs (it may exceed cap_tabs; that many are never written) and *blocks_needed say what all
+ *   files with a supported header need together.  threads: as in avcer_jpeg_entropy_batch (<= 0 or > 16: 16).
+ *
+ * avcer_jpeg_unpack: bytes u8 [n_bytes] (16-byte aligned), scan[n], tabs[n_tabs] and desc[n] as the call above wrote them, copied
+ *   to the DEVICE -> coeffs int16 [n_blocks, 64] (16-byte aligned; every OK file's blocks are written, zeros included), status i32
+ *   [n] = the file's status; desc[i].status and .reason are updated in place.  A desc[i] that is already NOT_HANDLED is skipped.
+ *   sub_bits: bits per subsequence, 0 = the default (512), else a multiple of 32 in [128, 2^20].  The result does not depend on it.
+ *   A workgroup takes a file: marker pass (0xFF00 unstuffed, the marker sequence kept), then units of up to 256 consecutive
+ *   subsequences, one thread each, decoded in rounds until no exit state changes -- at most 258 rounds, a counted loop --, a write
+ *   pass, and a segmented prefix sum that turns DC differences into DC values.  No workgroup waits for another, the host reads
+ *   nothing in between.  Two kernels on `stream`; scratch (n_bytes + 12 n_blocks + a few KB) comes from the context's JPEG
+ *   workspace.  n_blocks < 2^31, a file's entropy-coded bytes at most 2^27 (else reason 17).  A scan record or descriptor the call
+ *   above cannot have written is reason 9 and nothing is read through it.
+ *
+ * avcer_jpeg_unpack_host: the same phases as plain loops over the "threads" of a workgroup, on HOST pointers, no stream, ctx may be
+ *   NULL.  NOT a product path: it exists so that the algorithm can be tested and run under a sanitiser on a machine without a GPU. */
+typedef struct avcer_jpeg_tab {
+    uint8_t bits[17];
+    uint8_t vals[256];
+    uint8_t pad[15];
+} avcer_jpeg_tab;          /* 288 bytes */
+typedef struct avcer_jpeg_scan {
+    int64_t offset, nbytes;
+    int32_t restart;
+    int32_t dc[3], ac[3];
+    int32_t pad;
+} avcer_jpeg_scan;         /* 48 bytes */
+int avcer_jpeg_scan_batch(avcer_ctx* ctx, const uint8_t* const* files_host, const int64_t* lens_host, int n, uint8_t* bytes_host,
+                          int64_t cap_bytes, avcer_jpeg_desc* desc_host, avcer_jpeg_scan* scan_host, avcer_jpeg_tab* tabs_host, int cap_tabs,
+                          int threads, int32_t* n_tabs, int64_t* bytes_needed, int64_t* blocks_needed);
+int avcer_jpeg_unpack(avcer_ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const avcer_jpeg_scan* scan, const avcer_jpeg_tab* tabs,
+                      int n_tabs, avcer_jpeg_desc* desc, int n, int16_t* coeffs, int64_t n_blocks, int32_t* status, int sub_bits,
+                      avcer_stream_t stream);
+int avcer_jpeg_unpack_host(avcer_ctx* ctx, const uint8_t* bytes_host, int64_t n_bytes, const avcer_jpeg_scan* scan_host,
+                           const avcer_jpeg_tab* tabs_host, int n_tabs, avcer_jpeg_desc* desc_host, int n, int16_t* coeffs_host,
+                           int64_t n_blocks, int32_t* status_host, int sub_bits);
 
 /* Probability fusion and compound-expression rule.
  *   ref: run.py:25-165 (get_c_expr_db_pred), data/utils.py:125-127 (softmax), :222-241 (get_compound_expression)
