@@ -136,6 +136,10 @@ SIGNATURES = {
     "avcer_stem_pool": (C.c_int, [c_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, c_stream]),
     "avcer_stem_pool_u8": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      c_stream]),
+    "avcer_attention_long": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
+                                       c_stream]),
+    "avcer_set_audio_max_tokens": (C.c_int, [c_ctx, C.c_int]),
+    "avcer_audio_max_tokens": (C.c_int, [c_ctx]),
     "avcer_attention": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
                                   c_stream]),
     "avcer_measure_ceilings": (C.c_int, [c_ctx, C.POINTER(C.c_double), C.POINTER(C.c_double), c_stream]),

@@ -129,6 +129,28 @@ def chunk_spans(n_samples: int, sr: int, fps: float, window: float, step: float)
     return a[:, 0], a[:, 1], a[:, 2], a[:, 3]
 
 
+def window_tokens(n_samples: int) -> int:
+    """wav2vec2 tokens of a window of `n_samples` samples: the seven convolutions of its feature extractor (kernels 10, 3, 3, 3, 3,
+    2, 2; strides 5, 2, 2, 2, 2, 2, 2; no padding), i.e. (n - 400) // 320 + 1 from 400 samples on.  0 below the receptive field."""
+    n = int(n_samples)
+    for k, s in ((10, 5), (3, 2), (3, 2), (3, 2), (3, 2), (2, 2), (2, 2)):
+        if n < k:
+            return 0
+        n = (n - k) // s + 1
+    return n
+
+
+def check_window(engine: Engine, window: float, sr: int) -> int:
+    """The token count of a `window`-second window at `sr`, settled before any work: ValueError when it is more than the engine's
+    loaded audio model accepts (Engine.load_audio(sd, max_tokens=...))."""
+    tokens = window_tokens(int(window * sr))
+    limit = engine.audio_max_tokens
+    if tokens > limit:
+        raise ValueError(f"window={window} s at {sr} Hz is {tokens} tokens, more than the loaded audio model's max_tokens={limit}: "
+                         f"load it with Engine.load_audio(state_dict, max_tokens={tokens}) or more (at most 5000)")
+    return tokens
+
+
 def audio_forward(engine: Engine, wav: torch.Tensor, sr: int = 16000, fps: float = 25, window: float = 4,
                   step: float = 0.5, padding: str = "mean", mode: int = MODE_DEFAULT, wav_sr: int | None = None):
     """wav f32 [L] (mono, already at `sr`); or, with `wav_sr` given, source audio at `wav_sr` as Engine.resample takes it (int16
@@ -138,6 +160,7 @@ def audio_forward(engine: Engine, wav: torch.Tensor, sr: int = 16000, fps: float
     empty chunk is NaN, data/utils.py:76-82)."""
     if padding not in ("mean", "constant", "repeat"):
         raise ValueError(f"padding={padding!r}")
+    check_window(engine, window, sr)
     wav = wav.reshape(-1) if wav_sr is None else engine.resample(wav, wav_sr, sr)
     starts, ends, lo, hi = chunk_spans(int(wav.numel()), sr, fps, window, step)
     chunks = engine.audio_chunks(wav, starts, ends, int(window * sr), padding)
@@ -164,10 +187,13 @@ def preprocess_audio_and_predict(engine: Engine, path_video: str = "", fps: floa
     on the HIP path (the engine holds the audio weights): the WAV beside `path_video` in, the per-frame table out -- (rows float32
     [m, C], frame index int64 [m]), one row per (window, frame) pair as the reference's DataFrame holds them -- and
     `<save_path>/<MODEL_NAME>/<video>.csv` when `flag_save_prob`.  A missing WAV raises FileNotFoundError, a sample-rate pair the
-    resampling kernel does not cover ValueError, both before anything is launched."""
+    resampling kernel does not cover ValueError, a `window` of more tokens than the loaded model's max_tokens ValueError, all
+    before anything is launched."""
     from . import io_formats
 
-    pcm, wav_sr = load_wav(_wav_path(path_video))
+    path_wav = _wav_path(path_video)
+    check_window(engine, window, sr)
+    pcm, wav_sr = load_wav(path_wav)
     resample_plan(wav_sr, sr)
     src = torch.from_numpy(pcm)
     logits, lo, hi = engine.guarded(mode, lambda m: audio_forward(engine, src, sr, fps, window, step, padding, m, wav_sr=wav_sr))

@@ -69,6 +69,7 @@ struct avcer_ctx {
     int face_kind = 0;        // the loaded detector (avcer_face_kind): 0 none, 1 RetinaFace-R50, 2 RetinaFace-MobileNet-0.25, 3 S3FD
     int aud_classes = 0;
     int aud_head = 0;         // head of the loaded audio model (avcer_audio_head_kind): 0 none, 1 GRU (ExprModelV1), 3 transformer (V2 / V3)
+    int aud_max_tokens = 256; // longest audio window the forward accepts, in tokens (avcer_set_audio_max_tokens; reset by avcer_load_audio)
     int static_batch = 1024;  // frames per internal pass of the static CNN (4 GiB buffer-descriptor limit at f32)
     int static_back = 0;      // frames per back pass of the static CNN (0: two front passes; avcer_set_static_back_batch)
     int static_lanes = 2;     // calls of lane_min .. lane_max frames as two half-batches on two streams (avcer_set_static_lanes)
@@ -237,6 +238,9 @@ int k_layernorm(avcer_ctx*, const void* x, const void* res, const float* g, cons
                 int64_t rows, int c, float eps, int act, int in_kind, int yb_kind, hipStream_t);
 int k_add_pe(avcer_ctx*, const float* x, const float* pe, float* yf, void* yb, int n, int s, int c, int yb_kind, hipStream_t);
 int k_attention(avcer_ctx*, const void* qkv, void* out, int n, int s, int heads, int d, float scale, int in_kind,
+                int out_kind, hipStream_t);
+// the same for 1 <= s <= AVCER_AUDIO_MAX_TOKENS: key tiles streamed through LDS, running softmax (attention_long.hip)
+int k_attention_long(avcer_ctx*, const void* qkv, void* out, int n, int s, int heads, int d, float scale, int in_kind,
                 int out_kind, hipStream_t);
 int k_maxpool1d_relu(avcer_ctx*, const float* x, float* y, void* y_sp32, int n, int t_in, int t_out, int c, int k, hipStream_t);
 int k_mean_time_relu(avcer_ctx*, const float* x, float* y, int n, int t, int c, hipStream_t);

@@ -2,6 +2,7 @@
 // All of these are HBM/LDS-bound: 16-byte vector accesses, one 64-lane wave per row for reductions,
 // f32 statistics regardless of the activation storage type.
 #include "act_io.h"
+#include "attention_dev.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -967,27 +968,7 @@ __global__ void __launch_bounds__(ATT_THREADS) attention_kernel(const float* __r
 //                         key block b once V^T is stored with k-index 8g+e <-> key 32b + 16(e>>2) + 4g + (e&3)
 // X3 = 1: every product as hi.hi + hi.lo + lo.hi of fp16 pairs (f32-grade, as conv_gemm MODE 2/3; split_dev.h: scores and
 // exponentials are O(1), nothing here needs a scale); X3 = 0: bf16 operands.
-typedef __attribute__((ext_vector_type(8))) __bf16 att_bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float att_f32x4_t;
-// operand element by arithmetic: the split type (fp16) in the x3 form, bf16 in the plain form
-template <int X3> struct AttOp {
-    typedef spe_t elem_t;
-    typedef spx8_t frag_t;
-    static __device__ __forceinline__ att_f32x4_t mfma(const frag_t a, const frag_t b, const att_f32x4_t c) { return mfma_sp(a, b, c); }
-};
-template <> struct AttOp<0> {
-    typedef __bf16 elem_t;
-    typedef att_bf16x8_t frag_t;
-    static __device__ __forceinline__ uint16_t bits(float f) { return f2bf(f); }
-    static __device__ __forceinline__ att_f32x4_t mfma(const frag_t a, const frag_t b, const att_f32x4_t c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-    }
-};
-
-__device__ __forceinline__ int att_swz(int row, int chunk) {
-    return row * 128 + ((chunk ^ (int)((0x32765410u >> (((row >> 1) & 7) * 4)) & 7u)) << 4);
-}
-
+// (AttOp, att_swz: attention_dev.h, shared with the streaming kernels of attention_long.hip)
 constexpr int ATTM_WAVES = 8;  // one query tile per wave at 99 tokens (7 tiles): the four-wave form ran two rounds of 2 / 2 / 2 / 1
 template <typename T, typename TO, int NKT, int X3, int D>
 __global__ void __launch_bounds__(64 * ATTM_WAVES) attention_mfma_kernel(const T* __restrict__ qkv, TO* __restrict__ out, int s, int heads,
@@ -1610,21 +1591,6 @@ int k_add_pe(avcer_ctx* ctx, const float* x, const float* pe, float* yf, void* y
     CHECK_LAUNCH(ctx, "add_pe");
     return AVCER_OK;
 }
-
-namespace {
-// More than 64 KiB of dynamic LDS is an attribute of the kernel PER DEVICE: raised to the chip's 160 KiB before KERNEL's first
-// launch on the context's device (one bit per device index)
-template <auto KERNEL>
-int big_lds_once(avcer_ctx* ctx) {
-    static uint64_t done = 0;
-    const uint64_t bit = 1ull << (ctx->device & 63);
-    if (!(done & bit)) {
-        HIP_TRY(ctx, hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        done |= bit;
-    }
-    return AVCER_OK;
-}
-}  // namespace
 
 // in_kind: storage of qkv (0 f32, 1 bf16); out_kind: storage of the context vectors (0 f32, 1 bf16, 2 sp32)
 int k_attention(avcer_ctx* ctx, const void* qkv, void* out, int n, int s, int heads, int d, float scale, int in_kind,

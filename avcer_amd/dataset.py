@@ -24,7 +24,7 @@ import torch
 
 from . import dist as adist
 from . import io_formats
-from .audio_pipeline import chunk_spans, replicate_per_frame, resample_out_len, resample_plan
+from .audio_pipeline import check_window, chunk_spans, replicate_per_frame, resample_out_len, resample_plan
 from .engine import MODE_DEFAULT, MODE_F16X3, MODE_FP32
 from .fusion import MODEL_ORDER, covered_frames
 from .video_pipeline import plan_clip
@@ -230,6 +230,7 @@ def run_dataset(engine, jobs: Sequence[VideoJob], detector=None, *, mode: int = 
         raise ValueError(f"padding={padding!r}")
     if max_frames_per_pass < 1 or max_windows_per_pass < 1:
         raise ValueError("run_dataset: pass sizes >= 1")
+    check_window(engine, window, sr)
     errors = {}
 
     def fail(i, e):

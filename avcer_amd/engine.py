@@ -114,9 +114,18 @@ class Engine:
     def load_dynamic(self, state_dict):
         self._load(self.lib.avcer_load_dynamic, packing.pack_dynamic(state_dict))
 
-    def load_audio(self, state_dict):
-        self._load(self.lib.avcer_load_audio, packing.pack_audio(state_dict))
+    def load_audio(self, state_dict, max_tokens: int = packing.PE_ROWS):
+        """`max_tokens`: the longest window this model will be asked for, in wav2vec2 tokens (one per 20 ms: 256 = 5.1 s, the
+        default, up to 5000 = 100 s, the reference's own limit): that many rows of `pe` are packed, and the forward accepts
+        windows up to it (avcer_set_audio_max_tokens).  Windows of at most 256 tokens give the same bits whatever it is."""
+        self._load(self.lib.avcer_load_audio, packing.pack_audio(state_dict, pe_rows=max_tokens))
+        self._check(self.lib.avcer_set_audio_max_tokens(self.ctx, int(max_tokens)))
         self.audio_classes = self.lib.avcer_audio_num_classes(self.ctx)
+
+    @property
+    def audio_max_tokens(self) -> int:
+        """The longest audio window the loaded model accepts, in tokens (load_audio's max_tokens)."""
+        return int(self.lib.avcer_audio_max_tokens(self.ctx))
 
     @property
     def audio_head_kind(self) -> int:
@@ -794,6 +803,11 @@ class Engine:
         storage kinds 0 = f32, 1 = bf16, 2 = sp32 (int16 tensor of twice the elements)."""
         self._check(self.lib.avcer_attention(self.ctx, _ptr(qkv), _ptr(out), n, s, heads, head_dim, float(scale), in_kind,
                                              out_kind, self._stream()))
+
+    def attention_long(self, qkv, out, n: int, s: int, heads: int, head_dim: int, scale: float, in_kind: int, out_kind: int):
+        """The same for 1 <= s <= 5000 (avcer_attention_long): the kernels that stream key tiles through LDS, at any s."""
+        self._check(self.lib.avcer_attention_long(self.ctx, _ptr(qkv), _ptr(out), n, s, heads, head_dim, float(scale), in_kind,
+                                                  out_kind, self._stream()))
 
     def measure_ceilings(self):
         """(f16 MFMA TFLOP/s of a register-only v_mfma_f32_16x16x32_f16 loop, TB/s of a 1 GiB streaming copy) measured on this GPU."""

@@ -79,14 +79,15 @@ class AudioModel:
     """Drop-in for `audio_model`: every head the reference builds on the wav2vec2 trunk, in eval mode -- ExprModelV3 (8 classes,
     architectures/audio_8_cl.py:131-190), ExprModelV2 (the 7-class twin, audio_7_cl.py) and ExprModelV1 (the two-layer GRU head,
     audio_8_cl.py:18-72 / audio_7_cl.py:18-72); which one is decided by the state dict's keys (packing.pack_audio).
-    Input is the already normalised window, exactly what the reference passes (get_prob_audio_8_cl.py:87-92)."""
+    Input is the already normalised window, exactly what the reference passes (get_prob_audio_8_cl.py:87-92), of any length
+    up to `max_tokens` tokens (one per 20 ms; 256 by default, at most 5000: the rows of the reference's `pe` buffer)."""
 
-    def __init__(self, engine: Engine, state_dict, mode: int = MODE_DEFAULT):
-        self.engine, self.mode = engine, mode
-        engine.load_audio(state_dict)
+    def __init__(self, engine: Engine, state_dict, mode: int = MODE_DEFAULT, max_tokens: int = 256):
+        self.engine, self.mode, self.max_tokens = engine, mode, max_tokens
+        engine.load_audio(state_dict, max_tokens=max_tokens)
 
     def load_state_dict(self, state_dict):
-        self.engine.load_audio(state_dict)
+        self.engine.load_audio(state_dict, max_tokens=self.max_tokens)
 
     def eval(self):
         return self

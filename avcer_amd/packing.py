@@ -23,7 +23,8 @@ import numpy as np
 STATIC_BN_EPS = 1e-3   # architectures/video.py:21 (eps=0.001 on every BatchNorm2d)
 AUDIO_BN_EPS = 1e-5    # torch.nn.BatchNorm1d default, architectures/audio_8_cl.py:150,154
 RESNET_STAGES = ((64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2))
-PE_ROWS = 256          # attention kernel limit: S <= 256 tokens
+PE_ROWS = 256          # rows of `pe` packed by default: the whole-head attention kernels' limit, S <= 256 tokens
+PE_ROWS_MAX = 5000      # rows of the reference's buffer (attention_layers.py:194-211) = AVCER_AUDIO_MAX_TOKENS
 
 
 def _np(v) -> np.ndarray:
@@ -335,12 +336,16 @@ def pos_conv_weight(sd) -> np.ndarray:
     return torch._weight_norm(torch.from_numpy(v), torch.from_numpy(g), 2).numpy()
 
 
-def pack_audio(sd) -> "OrderedDict[str, np.ndarray]":
+def pack_audio(sd, pe_rows: int = PE_ROWS) -> "OrderedDict[str, np.ndarray]":
     """ExprModelV3 / ExprModelV2 state_dict (architectures/audio_8_cl.py:131-190, audio_7_cl.py) or the GRU-head ExprModelV1's
     (audio_8_cl.py:18-72, audio_7_cl.py:18-72: recognised by its gru.weight_ih_l0 key, the others by tl1.*), bare or inside the
     trainer's {"model_state_dict": ...} checkpoint; the positional-conv weight norm in any of its three spellings
     (torch >= 2.1 parametrizations.weight.original0/1, torch 2.0-style weight_g / weight_v as the published checkpoint was
-    written under torch 2.1.2 + transformers 4.36.2, or an already materialised .weight)."""
+    written under torch 2.1.2 + transformers 4.36.2, or an already materialised .weight).
+    `pe_rows`: how many rows of the transformer head's positional-encoding buffer are packed, i.e. the longest window in tokens
+    the packed model can serve (Engine.load_audio(sd, max_tokens=...)); PE_ROWS .. PE_ROWS_MAX.  The GRU head has no such buffer."""
+    if isinstance(pe_rows, bool) or not isinstance(pe_rows, (int, np.integer)) or not PE_ROWS <= pe_rows <= PE_ROWS_MAX:
+        raise ValueError(f"pack_audio: pe_rows={pe_rows!r} outside [{PE_ROWS}, {PE_ROWS_MAX}]")
     sd = _unwrap(sd)
     out: "OrderedDict[str, np.ndarray]" = OrderedDict()
     w2 = "wav2vec2."
@@ -382,7 +387,9 @@ def pack_audio(sd) -> "OrderedDict[str, np.ndarray]":
         _pack_audio_head(sd, out)
         return out
     pe = _f32(sd["tl1.positional_encoding.pe"]).reshape(-1, 1024)
-    out["pe"] = np.ascontiguousarray(pe[:PE_ROWS])
+    if pe.shape[0] < pe_rows:
+        raise ValueError(f"pack_audio: pe_rows={pe_rows}, but tl1.positional_encoding.pe has {pe.shape[0]} rows")
+    out["pe"] = np.ascontiguousarray(pe[:pe_rows])
     for l in (1, 2):
         t = f"tl{l}."
         a = t + "self_attention."

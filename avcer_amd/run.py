@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import io_formats
-from .audio_pipeline import audio_forward, replicate_per_frame, resample_plan
+from .audio_pipeline import audio_forward, check_window, replicate_per_frame, resample_plan
 from .engine import MODE_DEFAULT
 from .face_tiles import VideoTiler, track_clip, write_face_crops
 from .fusion import MODEL_ORDER, fuse
@@ -35,7 +35,8 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
     `wav_sr`: `wav` is source audio at that rate instead -- int16 [L] / [L, C] as the frames lie in the WAV file ffmpeg writes
     (44.1 kHz stereo, data/utils.py:46) or float32 [L] / [C, L] -- and is converted, downmixed and resampled to `sr` on the device,
     on the audio stream in front of the chunker (data/utils.py:50-57, Engine.resample).  A rate pair the kernel does not cover
-    raises ValueError before any work.
+    raises ValueError before any work, and so does a `window` of more tokens than the loaded audio model accepts
+    (Engine.load_audio(sd, max_tokens=...); the message names max_tokens).
     `detector`: a `face_tiles.RetinaFacePredictor` or `face_tiles.S3FDPredictor` (threshold 0.8 in the reference); or pass per-frame `detections`.
     Defaults follow `run_inference`'s signature (Rule 2 weights on, Rule 1 mask off; `run.py --help` flips them).
     Returns a dict: av / vs / vd / a predictions (int32 [T], compound class per frame), `compound_prob` f64 [4,T,7],
@@ -58,6 +59,7 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
         from . import heatmaps as hm
 
         hm.check_model(model_heatmaps)
+    check_window(engine, window, sr)
     start_time = time.time()                                                # run.py:200
     frames = frames_bgr if torch.is_tensor(frames_bgr) else torch.from_numpy(np.ascontiguousarray(frames_bgr))
     total_frames = int(frames.shape[0])

@@ -84,7 +84,9 @@ enum {
  *      on the device, entropy coding on the host) joined under 8 the same way: four more symbols, the descriptor unchanged.
  *      avcer_jpeg_pack (entropy coding on the device: whole files leave it) joined under 8 the same way: one more symbol.
  *      avcer_jpeg_scan_batch, avcer_jpeg_unpack, avcer_jpeg_unpack_host with their structs avcer_jpeg_tab and avcer_jpeg_scan: entropy
- *      DECODING on the device, joined under 8 the same way: three more symbols, the descriptor unchanged. */
+ *      DECODING on the device, joined under 8 the same way: three more symbols, the descriptor unchanged.
+ *      avcer_attention_long, avcer_set_audio_max_tokens, avcer_audio_max_tokens (audio windows past 256 tokens: attention that
+ *      streams key tiles through LDS) joined under 8 the same way: three more symbols, nothing that existed changed. */
 #define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
@@ -184,6 +186,27 @@ int avcer_audio_head_kind(const avcer_ctx* ctx);
  *        audio_expr_models_7_cl.py:63,130,205; consumed at net_trainer.py:512 */
 int avcer_audio_forward_features(avcer_ctx* ctx, const float* wav, int n, int t, int normalize, int mode,
                                  float* logits, float* features, avcer_stream_t stream);
+
+/* The longest window, in wav2vec2 tokens (one per 320 samples: 20 ms), that avcer_audio_forward / _features accept for the loaded
+ * audio model.  Default 256 (about 5.1 s), what the attention kernels that keep a whole head's K and V in LDS can hold; range
+ * 256 .. AVCER_AUDIO_MAX_TOKENS (5000 = 100 s, the rows of the reference's `pe` buffer, attention_layers.py:194-211 -- its own and
+ * only length limit).  Windows of at most 256 tokens run the same launches as before whatever the limit is (bit-identical
+ * results); longer ones run avcer_attention_long's kernels.  AVCER_ESTATE without a loaded audio model; AVCER_EINVAL outside
+ * the range, or when the loaded transformer head's `pe` tensor has fewer rows (packing.pack_audio(sd, pe_rows=...)); the GRU head
+ * has no such tensor.  avcer_load_audio resets the limit to 256: it belongs to the loaded model.
+ *
+ * Windows per pass: min(n, 128) at <= 256 tokens (unchanged launches, unchanged bits); max(1, 128 * 256 / tokens) above, so a
+ * pass never holds more than the 32768 token rows of 128 x 256 and the carved workspace stays what it was: 128 windows of 256
+ * tokens carve 9.8 GiB in the f32 and x3 modes (extractor layers 0-2: 4.0 + 2 x 2.0 GiB; 32768 token rows x 56 KiB: 1.75 GiB).
+ * PEAK at 5000 tokens (one pass = 6 windows of 1 600 080 samples): 9.0 GiB in the f32 and x3 modes (extractor 3.66 + 2 x 1.83 GiB,
+ * 30000 token rows 1.6 GiB, the normalised waveform and the head 0.1 GiB), 4.8 GiB in the bf16 mode.  A pass is shortened further
+ * where its largest contraction operand, the first extractor layer's output [windows, samples / 5, 512], would reach the 4 GiB
+ * range of a buffer descriptor (6 x 320015 x 512 x 4 B = 3.66 GiB fits); every other avcer_conv_desc of the audio path is smaller.
+ * Nothing else of the forward has a fixed extent in the token count: add-PE, the positional conv, the max-pool, the head's
+ * convolutions and the GRU layer's time loop are shaped by it (64-bit element indices throughout). */
+#define AVCER_AUDIO_MAX_TOKENS 5000
+int avcer_set_audio_max_tokens(avcer_ctx* ctx, int tokens);
+int avcer_audio_max_tokens(const avcer_ctx* ctx);
 
 /* Window slicing + padding of one waveform.
  *   ref: get_prob_audio_8_cl.py:78-86, data/utils.py:63-71 (pad_wav, "repeat"), :74-89 (pad_wav_zeros, "mean"/"constant")
@@ -744,6 +767,14 @@ int avcer_gru_layer(avcer_ctx* ctx, const float* xp, const float* w_hh, const fl
 
 int avcer_attention(avcer_ctx* ctx, const void* qkv, void* out, int n, int s, int heads, int head_dim, float scale,
                     int in_kind, int out_kind, avcer_stream_t stream);
+/* The same function for 1 <= s <= AVCER_AUDIO_MAX_TOKENS, same tensors and storage combinations (csrc/attention_long.hip; DESIGN.md section 5, "Audio windows past 256 tokens"): one
+ * workgroup per (row block, head, block of AVCER_ATT_LONG_QB queries); key tiles of AVCER_ATT_LONG_KT keys pass through LDS, and
+ * every query row keeps a running maximum, a running denominator and rescaled accumulators (the tail tile is masked).  It always
+ * runs the streaming kernels, also at s <= 256, where avcer_attention and the forward passes run the whole-head ones. */
+#define AVCER_ATT_LONG_KT 128
+#define AVCER_ATT_LONG_QB 128
+int avcer_attention_long(avcer_ctx* ctx, const void* qkv, void* out, int n, int s, int heads, int head_dim, float scale,
+                         int in_kind, int out_kind, avcer_stream_t stream);
 
 /* Measured ceilings of the GPU this context lives on (about 0.2 s): dense 16-bit MFMA issue rate of a register-only
  * v_mfma_f32_16x16x32_f16 loop in TFLOP/s (the instruction of AVCER_MODE_F16X3; the bf16 form issues at the same rate,
