@@ -1,8 +1,7 @@
-// Element-wise, normalisation, pooling, attention and fusion kernels of the AVCER hot path (gfx950).
+// Element-wise, normalisation, pooling and fusion kernels of the AVCER hot path (gfx950).
 // All of these are HBM/LDS-bound: 16-byte vector accesses, one 64-lane wave per row for reductions,
 // f32 statistics regardless of the activation storage type.
 #include "act_io.h"
-#include "attention_dev.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -881,294 +880,6 @@ __global__ void add_pe_kernel(const float* __restrict__ x, const float* __restri
     if (yb) st4<OB>(yb, e, v, ovf);
 }
 
-// ------------------------------------------------------------------------------------------------ attention
-// softmax(q k^T * scale) v for one (batch, head) per workgroup; S <= 256, d in {32, 64}.
-// wav2vec2 encoder self-attention (16 x 64) and attention_layers.py:10-38 (32 x 32, 16 x 64).
-// K (rows padded by 4 floats: conflict-free b128 row reads) and V live in LDS as f32; each wave owns query rows.
-// 8 waves share one head's K/V image (~105 KiB f32 at S=199): two waves per SIMD hide the LDS latency of the score loop
-constexpr int ATT_WAVES = 8;
-constexpr int ATT_THREADS = ATT_WAVES * 64;
-// The exact-f32 form (f32 in, f32 out); the bf16 and split-fp16 modes run attention_mfma_kernel below.
-template <int D>
-__global__ void __launch_bounds__(ATT_THREADS) attention_kernel(const float* __restrict__ qkv, float* __restrict__ out, int s, int heads,
-                                                      float scale) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    constexpr int KP = D + 4;
-    float* ks = reinterpret_cast<float*>(smem_raw);           // [s][KP]
-    float* vs = ks + (long)s * KP;                            // [s][D]
-    float* ps = vs + (long)s * D;                             // [ATT_WAVES][256]
-    float* qs = ps + ATT_WAVES * 256;                         // [ATT_WAVES][D]
-    const int b = blockIdx.x / heads, h = blockIdx.x % heads;
-    const int e = heads * D;
-    const long rowstride = 3L * e;
-    const float* base = qkv + (long)b * s * rowstride + h * D;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    for (int i = tid; i < s * (D / 4); i += ATT_THREADS) {
-        const int r = i / (D / 4), c4 = (i % (D / 4)) * 4;
-        float kv[4], vv[4];
-        ld4<float>(base, (long)r * rowstride + e + c4, kv);
-        ld4<float>(base, (long)r * rowstride + 2 * e + c4, vv);
-        *reinterpret_cast<float4*>(ks + r * KP + c4) = make_float4(kv[0], kv[1], kv[2], kv[3]);
-        *reinterpret_cast<float4*>(vs + r * D + c4) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-    }
-    __syncthreads();
-    float* pw = ps + wv * 256;
-    float* qw = qs + wv * D;
-    for (int qi = wv; qi < s; qi += ATT_WAVES) {
-        if (lane < D) qw[lane] = ldf<float>(base, (long)qi * rowstride + lane) * scale;
-        __builtin_amdgcn_wave_barrier();
-        float sc[4];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            const int j = jj * 64 + lane;
-            float a = -INFINITY;
-            if (j < s) {
-                a = 0.f;
-#pragma unroll
-                for (int c = 0; c < D; c += 4) {
-                    const float4 kk = *reinterpret_cast<const float4*>(ks + j * KP + c);
-                    const float4 qq = *reinterpret_cast<const float4*>(qw + c);
-                    a += qq.x * kk.x + qq.y * kk.y + qq.z * kk.z + qq.w * kk.w;
-                }
-            }
-            sc[jj] = a;
-            mx = fmaxf(mx, a);
-        }
-        mx = wave_max(mx);
-        float den = 0.f;
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            const int j = jj * 64 + lane;
-            const float pv = j < s ? expf(sc[jj] - mx) : 0.f;
-            pw[j] = pv;
-            den += pv;
-        }
-        den = wave_sum(den);
-        __builtin_amdgcn_wave_barrier();
-        float o = 0.f;
-        if constexpr (D == 64) {
-            for (int j = 0; j < s; ++j) o += pw[j] * vs[j * D + lane];
-        } else {
-            const int c = lane & 31, half = lane >> 5;
-            for (int j = half; j < s; j += 2) o += pw[j] * vs[j * D + c];
-            o += __shfl_xor(o, 32, 64);
-        }
-        if (lane < D) stf<float>(out, ((long)b * s + qi) * e + h * D + lane, o / den);
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
-// ---- MFMA attention for 64-wide heads (wav2vec2 encoder layers, TransformerLayer 2) ---------------------------------
-// One workgroup (8 waves) per (window, head).  K is kept in LDS as 16-bit rows (GEMM swizzle; fp16 in the x3 form, bf16 else), V transposed and key-
-// permuted, both as hi (+ lo in the split mode) planes.  Each wave takes 16-query tiles:
-//   S^T tile = K . Q^T   (swapped operands: a lane then holds, for ONE query lane&15, the keys 16t + 4(lane>>4) + r)
-//   softmax over keys     in-lane over its registers + 2 shuffles across the four lane groups
-//   O^T tile = V^T . P^T  the exponentiated accumulators of key tiles (2b, 2b+1) ARE the B operand of the PV MFMA for
-//                         key block b once V^T is stored with k-index 8g+e <-> key 32b + 16(e>>2) + 4g + (e&3)
-// X3 = 1: every product as hi.hi + hi.lo + lo.hi of fp16 pairs (f32-grade, as conv_gemm MODE 2/3; split_dev.h: scores and
-// exponentials are O(1), nothing here needs a scale); X3 = 0: bf16 operands.
-// (AttOp, att_swz: attention_dev.h, shared with the streaming kernels of attention_long.hip)
-constexpr int ATTM_WAVES = 8;  // one query tile per wave at 99 tokens (7 tiles): the four-wave form ran two rounds of 2 / 2 / 2 / 1
-template <typename T, typename TO, int NKT, int X3, int D>
-__global__ void __launch_bounds__(64 * ATTM_WAVES) attention_mfma_kernel(const T* __restrict__ qkv, TO* __restrict__ out, int s, int heads,
-                                                           float scale, unsigned* ovf) {
-    static_assert(D == 64 || D == 32, "head dimension 64 (wav2vec2 layers, tl2) or 32 (tl1)");
-    using Op = AttOp<X3>;
-    using frag_t = typename Op::frag_t;
-    using elem_t = typename Op::elem_t;
-    constexpr int KS = D / 32;               // 32-wide K-steps of Q.K^T
-    constexpr int TV = D / 16;               // 16-row tiles of V^T / O^T
-    constexpr int SP = NKT * 16;             // padded key count
-    constexpr int VROW = SP * 2 + 16;        // bytes per V^T row (16-byte pad against bank conflicts)
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    char* khi = smem_raw;                    // [SP][128 B]
-    char* klo = khi + SP * 128;
-    char* vhi = klo + (X3 ? SP * 128 : 0);   // [D][VROW]
-    char* vlo = vhi + D * VROW;
-    const int b = blockIdx.x / heads, h = blockIdx.x % heads;
-    const int e = heads * D;
-    const long rowstride = 3L * e;
-    const T* base = qkv + (long)b * s * rowstride + h * D;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int g = lane >> 4, q16 = lane & 15;
-
-    // Every global load of the block is issued before the first one is needed: a block is a chain of HBM round trips
-    // otherwise (four staging passes, then one per query tile: ~6 x 2.5 us against ~4 us of arithmetic -- the launch ran at
-    // a third of its present speed).  First the query rows of this wave's tiles (tile wv, wv + 8, ...), raw; then K / V in
-    // batches of up to four staging passes.
-    const int nqt = (s + 15) >> 4;
-    constexpr int NTHR = 64 * ATTM_WAVES;
-    constexpr int QI = NKT / ATTM_WAVES;     // query tiles per wave
-    float qraw[QI][KS][8];
-#pragma unroll
-    for (int qi = 0; qi < QI; ++qi) {
-        const int qrow = (wv + ATTM_WAVES * qi) * 16 + q16;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            if (qrow < s) {
-                ld4<T>(base, (long)qrow * rowstride + 32 * ks + 8 * g, qraw[qi][ks]);
-                ld4<T>(base, (long)qrow * rowstride + 32 * ks + 8 * g + 4, qraw[qi][ks] + 4);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) qraw[qi][ks][j] = 0.f;
-            }
-        }
-    }
-    // ---- stage K (row-major) and V (transposed + permuted) as 16-bit planes
-    constexpr int ITEMS = SP * (D / 8), PASSES = ITEMS / NTHR, UB = PASSES < 4 ? PASSES : 4;
-    static_assert(ITEMS % NTHR == 0 && PASSES % UB == 0 && NKT % ATTM_WAVES == 0, "whole staging passes, whole batches");
-    float amax = 0.f;  // largest finite magnitude this thread split into an fp16 pair
-    for (int p0 = 0; p0 < PASSES; p0 += UB) {
-    float kvb[UB][8], vvb[UB][8];
-#pragma unroll
-    for (int u = 0; u < UB; ++u) {
-        const int it = (p0 + u) * NTHR + tid;
-        const int r = it / (D / 8), c = it % (D / 8);
-        if (r < s) {
-            ld4<T>(base, (long)r * rowstride + e + 8 * c, kvb[u]);
-            ld4<T>(base, (long)r * rowstride + e + 8 * c + 4, kvb[u] + 4);
-            ld4<T>(base, (long)r * rowstride + 2 * e + 8 * c, vvb[u]);
-            ld4<T>(base, (long)r * rowstride + 2 * e + 8 * c + 4, vvb[u] + 4);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { kvb[u][j] = 0.f; vvb[u][j] = 0.f; }
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < UB; ++u) {
-        const int it = (p0 + u) * NTHR + tid;
-        const int r = it / (D / 8), c = it % (D / 8);   // key row, chunk of 8 head-dim elements (K rows keep a 128-byte pitch)
-        // V^T: key r sits at k-position (r>>5)*32 + ((r&15)>>2)*8 + ((r>>4)&1)*4 + (r&3) of every head-dim row
-        const int kpos = (r >> 5) * 32 + ((r & 15) >> 2) * 8 + ((r >> 4) & 1) * 4 + (r & 3);
-        if constexpr (X3) {  // fp16 pairs (split_dev.h); amax: their range contract
-            uint4 hw, lw;
-            sp_split8(kvb[u], amax, hw, lw);
-            *reinterpret_cast<uint4*>(khi + att_swz(r, c)) = hw;
-            *reinterpret_cast<uint4*>(klo + att_swz(r, c)) = lw;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                uint16_t hv, lv;
-                sp_split1(vvb[u][j], amax, hv, lv);
-                *reinterpret_cast<uint16_t*>(vhi + (8 * c + j) * VROW + kpos * 2) = hv;
-                *reinterpret_cast<uint16_t*>(vlo + (8 * c + j) * VROW + kpos * 2) = lv;
-            }
-        } else {
-            uint32_t hw[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) hw[j] = (uint32_t)Op::bits(kvb[u][2 * j]) | ((uint32_t)Op::bits(kvb[u][2 * j + 1]) << 16);
-            *reinterpret_cast<uint4*>(khi + att_swz(r, c)) = make_uint4(hw[0], hw[1], hw[2], hw[3]);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) *reinterpret_cast<uint16_t*>(vhi + (8 * c + j) * VROW + kpos * 2) = Op::bits(vvb[u][j]);
-        }
-    }
-    }
-    __syncthreads();
-
-#pragma unroll
-    for (int qi = 0; qi < QI; ++qi) {
-        const int tq = wv + ATTM_WAVES * qi;
-        if (tq >= nqt) break;
-        const int qrow = tq * 16 + q16;
-        // ---- Q fragments (B operand): this lane's query row, head-dim 32ks + 8g .. +7, pre-scaled
-        frag_t qh[KS], ql[KS];
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            float qv[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) qv[j] = qraw[qi][ks][j] * scale;
-            if constexpr (X3) {
-                sp_split8(qv, amax, qh[ks], ql[ks]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) qh[ks][j] = (elem_t)qv[j];
-            }
-        }
-        // ---- scores^T: key tiles x this query tile
-        att_f32x4_t sc[NKT];
-#pragma unroll
-        for (int t = 0; t < NKT; ++t) {
-            sc[t] = att_f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const int off = att_swz(t * 16 + q16, ks * 4 + g);
-                const frag_t kh = *reinterpret_cast<const frag_t*>(khi + off);
-                if (X3) {
-                    const frag_t kl = *reinterpret_cast<const frag_t*>(klo + off);
-                    sc[t] = Op::mfma(kl, qh[ks], sc[t]);
-                    sc[t] = Op::mfma(kh, ql[ks], sc[t]);
-                }
-                sc[t] = Op::mfma(kh, qh[ks], sc[t]);
-            }
-        }
-        // ---- softmax over keys (register r of tile t is key 16t + 4g + r); padded keys contribute nothing
-        float mx = -INFINITY;
-#pragma unroll
-        for (int t = 0; t < NKT; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (16 * t + 4 * g + r >= s) sc[t][r] = -INFINITY;
-                mx = fmaxf(mx, sc[t][r]);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        float den = 0.f;
-#pragma unroll
-        for (int t = 0; t < NKT; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float pv = (16 * t + 4 * g + r < s) ? expf(sc[t][r] - mx) : 0.f;
-                sc[t][r] = pv;
-                den += pv;
-            }
-        den += __shfl_xor(den, 16, 64);
-        den += __shfl_xor(den, 32, 64);
-        // ---- O^T = V^T . P^T over key blocks of 32
-        att_f32x4_t oc[TV];
-#pragma unroll
-        for (int tv = 0; tv < TV; ++tv) oc[tv] = att_f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kb = 0; kb < NKT / 2; ++kb) {
-            frag_t ph, pl;
-            // element by element from the accumulators: through a float[8] copy and sp_split8 the 16-key-tile forms need 27 / 58
-            // more VGPRs and lose an occupancy step
-            float pmax = 0.f;  // never read: probabilities are at most 1
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                if constexpr (X3) {
-                    spe_t hh, ll;
-                    sp_split1(sc[2 * kb + (j >> 2)][j & 3], pmax, hh, ll);
-                    ph[j] = hh;
-                    pl[j] = ll;
-                } else {
-                    ph[j] = (elem_t)sc[2 * kb + (j >> 2)][j & 3];
-                }
-            }
-#pragma unroll
-            for (int tv = 0; tv < TV; ++tv) {
-                const int off = (tv * 16 + q16) * VROW + (kb * 4 + g) * 16;
-                const frag_t vh = *reinterpret_cast<const frag_t*>(vhi + off);
-                if (X3) {
-                    const frag_t vl = *reinterpret_cast<const frag_t*>(vlo + off);
-                    oc[tv] = Op::mfma(vl, ph, oc[tv]);
-                    oc[tv] = Op::mfma(vh, pl, oc[tv]);
-                }
-                oc[tv] = Op::mfma(vh, ph, oc[tv]);
-            }
-        }
-        // ---- normalise and store: registers of tile tv are head-dim 16tv + 4g + r of query lane&15
-        if (qrow < s) {
-            const float inv = 1.f / den;
-#pragma unroll
-            for (int tv = 0; tv < TV; ++tv) {
-                float o4[4] = {oc[tv][0] * inv, oc[tv][1] * inv, oc[tv][2] * inv, oc[tv][3] * inv};
-                st4<TO>(out, ((long)b * s + qrow) * e + h * D + 16 * tv + 4 * g, o4, ovf);
-            }
-        }
-    }
-    if (X3) sp_count_now(ovf, amax);
-}
-
 // ------------------------------------------------------------------------------------------------ audio head
 // audio_8_cl.py:151-152: MaxPool1d(5) (stride 5, floor) then ReLU over time of [n, t_in, c].
 // ysp: the same values once more as sp32 pairs (the operand of the head's second convolution in the x3 mode)
@@ -1589,44 +1300,6 @@ int k_add_pe(avcer_ctx* ctx, const float* x, const float* pe, float* yf, void* y
         add_pe_kernel<OB><<<cdiv(total4, 256), 256, 0, st>>>(x, pe, yf, (OB*)yb, total4, s, c, ctx->ovf);
     });
     CHECK_LAUNCH(ctx, "add_pe");
-    return AVCER_OK;
-}
-
-// in_kind: storage of qkv (0 f32, 1 bf16); out_kind: storage of the context vectors (0 f32, 1 bf16, 2 sp32)
-int k_attention(avcer_ctx* ctx, const void* qkv, void* out, int n, int s, int heads, int d, float scale, int in_kind,
-                int out_kind, hipStream_t st) {
-    if (s > 256 || s < 1) return set_err(ctx, AVCER_EINVAL, "attention: S=%d outside [1,256]", s);
-    if (d != 32 && d != 64) return set_err(ctx, AVCER_EINVAL, "attention: head dim %d", d);
-    if (in_kind == 2 || (in_kind == 1) != (out_kind == 1))
-        return set_err(ctx, AVCER_EINVAL, "attention: unsupported storage combination %d -> %d", in_kind, out_kind);
-    const int grid = n * heads;
-    // bf16 / split-fp16 modes: QK^T and PV on the MFMA, 64- and 32-wide heads (the f32 mode keeps exact f32 arithmetic)
-    if (in_kind == 1 || out_kind == 2) {
-        const int nkt = s <= 128 ? 8 : 16;
-        const int sp = nkt * 16, x3 = out_kind == 2;
-        const size_t lds_m = (size_t)sp * 128 * (x3 ? 2 : 1) + (size_t)d * (sp * 2 + 16) * (x3 ? 2 : 1);
-#define ATTM(T, TO, NKT, X3, D)                                                                                       \
-    do {                                                                                                              \
-        TRY((big_lds_once<attention_mfma_kernel<T, TO, NKT, X3, D>>(ctx)));                                           \
-        attention_mfma_kernel<T, TO, NKT, X3, D><<<grid, 64 * ATTM_WAVES, lds_m, st>>>((const T*)qkv, (TO*)out, s, heads, scale, ctx->ovf); \
-    } while (0)
-#define ATTM_D(T, TO, NKT, X3) do { if (d == 64) ATTM(T, TO, NKT, X3, 64); else ATTM(T, TO, NKT, X3, 32); } while (0)
-        if (x3) { if (nkt == 8) ATTM_D(float, sp32_t, 8, 1); else ATTM_D(float, sp32_t, 16, 1); }
-        else { if (nkt == 8) ATTM_D(bf16_t, bf16_t, 8, 0); else ATTM_D(bf16_t, bf16_t, 16, 0); }
-#undef ATTM_D
-#undef ATTM
-        CHECK_LAUNCH(ctx, "attention_mfma");
-        return AVCER_OK;
-    }
-    const size_t lds = ((size_t)s * (d + 4) + (size_t)s * d + ATT_WAVES * 256 + ATT_WAVES * d) * sizeof(float);
-    if (d == 64) {
-        TRY(big_lds_once<attention_kernel<64>>(ctx));
-        attention_kernel<64><<<grid, ATT_THREADS, lds, st>>>((const float*)qkv, (float*)out, s, heads, scale);
-    } else {
-        TRY(big_lds_once<attention_kernel<32>>(ctx));
-        attention_kernel<32><<<grid, ATT_THREADS, lds, st>>>((const float*)qkv, (float*)out, s, heads, scale);
-    }
-    CHECK_LAUNCH(ctx, "attention");
     return AVCER_OK;
 }
 

@@ -767,7 +767,7 @@ int avcer_gru_layer(avcer_ctx* ctx, const float* xp, const float* w_hh, const fl
 
 int avcer_attention(avcer_ctx* ctx, const void* qkv, void* out, int n, int s, int heads, int head_dim, float scale,
                     int in_kind, int out_kind, avcer_stream_t stream);
-/* The same function for 1 <= s <= AVCER_AUDIO_MAX_TOKENS, same tensors and storage combinations (csrc/attention_long.hip; DESIGN.md section 5, "Audio windows past 256 tokens"): one
+/* The same function for 1 <= s <= AVCER_AUDIO_MAX_TOKENS, same tensors and storage combinations (csrc/attention.hip; DESIGN.md section 5, "Audio windows past 256 tokens"): one
  * workgroup per (row block, head, block of AVCER_ATT_LONG_QB queries); key tiles of AVCER_ATT_LONG_KT keys pass through LDS, and
  * every query row keeps a running maximum, a running denominator and rescaled accumulators (the tail tile is masked).  It always
  * runs the streaming kernels, also at s <= 256, where avcer_attention and the forward passes run the whole-head ones. */

@@ -1,4 +1,4 @@
-"""avcer_attention_long (csrc/attention_long.hip) against float64: softmax(Q K^T * scale) V with key tiles of KT = 128 keys streamed
+"""avcer_attention_long (csrc/attention.hip) against float64: softmax(Q K^T * scale) V with key tiles of KT = 128 keys streamed
 through LDS and a running softmax per query row, one workgroup per (window, head, block of QB = 128 queries), in the three
 arithmetic forms: exact f32 on the VALU, bf16 MFMA, x3 MFMA (f32 in, sp32 out).
 
@@ -189,3 +189,23 @@ def test_argument_errors(engine):
     for s, d, kinds in ((5001, 64, (0, 0)), (0, 64, (0, 0)), (64, 48, (0, 0)), (64, 64, (0, 1)), (64, 64, (2, 2))):
         with pytest.raises(AvcerError):
             engine.attention_long(x, x, 1, s, 1, d, 0.125, *kinds)
+
+
+@pytest.mark.parametrize("kinds", [(0, 0), (0, 2), (1, 1)], ids=["f32", "x3", "bf16"])
+@pytest.mark.parametrize("d", [64, 32])
+@pytest.mark.parametrize("s", [1, 17, 99, KT])
+def test_one_key_tile_is_the_whole_head_kernel(engine, s, d, kinds):
+    """Up to KT keys the streamed kernels see one key tile: the factor on the running sums is exp(-inf) = 0 on zeros, the image
+    has the 8 MFMA key tiles of the whole-head kernel at s <= 128, and every sum is formed in the same order, so engine.attention
+    and engine.attention_long return the same bits."""
+    n, (ik, ok) = 2, kinds
+    qkv = _random_case(s, d, n)[0]
+    x = (qkv.to(torch.bfloat16) if ik == 1 else qkv).to(engine.device)
+    shape, dtype = ((n, s, 2 * HEADS * d), torch.int16) if ok == 2 else ((n, s, HEADS * d), torch.bfloat16 if ok == 1 else torch.float32)
+    outs = []
+    for fn in (engine.attention, engine.attention_long):
+        o = torch.zeros(shape, dtype=dtype, device=engine.device)
+        fn(x, o, n, s, HEADS, d, 1.0 / d ** 0.5, ik, ok)
+        outs.append(o)
+    torch.cuda.synchronize()
+    assert torch.equal(outs[0], outs[1])
