@@ -98,6 +98,10 @@ SIGNATURES = {
                                      C.c_int64, c_stream]),
     "avcer_jpeg_write_batch": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
                                          C.POINTER(C.c_int64)]),
+    "avcer_jpeg_roundtrip_tiles": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, c_stream]),
+    "avcer_jpeg_roundtrip_rgb": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_stream]),
     "avcer_jpeg_pack": (C.c_int, [c_ctx, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                   C.c_void_p, c_stream]),
     "avcer_jpeg_scan_batch": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -432,6 +432,41 @@ constexpr int WS_LD = 9;           // dwords per row of a block's 8 x 8 workspac
 // image is not guessed at: its flag is raised, kernel B leaves it zero, and the caller decodes it some other way.
 constexpr int IDCT_PAIR_MAX = 16383;
 
+// Kernel A behind the dequantisation, for every lane of the workgroup (it holds the two barriers): `w` is the lane's block in LDS
+// with the dequantised row j written by this lane, `wild` what the range guard has seen so far.  Column pass, row pass, the guard,
+// and row j of the block's samples to `dst` with one 8-byte store; `flag` is the image's.
+__device__ __forceinline__ void idct_block_store(int* w, int j, bool live, bool wild, uint8_t* dst, int32_t* flag) {
+    __syncthreads();
+    int v[8];
+    if (live) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) v[r] = w[r * WS_LD + j];
+        idct_1d<CONST_BITS - PASS1_BITS>(v);
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            w[r * WS_LD + j] = v[r];
+            wild = wild || abs(v[r]) > IDCT_PAIR_MAX;
+        }
+    }
+    __syncthreads();
+    if (live) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = w[j * WS_LD + k];
+        idct_1d<CONST_BITS + PASS1_BITS + 3>(v);
+        // range limit around +128 (the guard above keeps to where libjpeg's wrapping table and its saturating packs agree)
+        uint32_t lo = 0, hi = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) wild = wild || v[k] < -512 || v[k] > 511;
+        if (wild) *flag = 1;  // every lane that sees it stores the same 1
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            lo |= (uint32_t)min(max(v[k] + 128, 0), 255) << (8 * k);
+            hi |= (uint32_t)min(max(v[k + 4] + 128, 0), 255) << (8 * k);
+        }
+        *reinterpret_cast<uint2*>(dst) = make_uint2(lo, hi);
+    }
+}
+
 __global__ void __launch_bounds__(IDCT_THREADS) jpeg_idct_kernel(const int16_t* __restrict__ coeffs, const Desc* __restrict__ desc,
                                                                  int n, long n_blocks, uint8_t* __restrict__ planes,
                                                                  int32_t* __restrict__ flags) {
@@ -467,35 +502,7 @@ __global__ void __launch_bounds__(IDCT_THREADS) jpeg_idct_kernel(const int16_t* 
             }
         }
     }
-    __syncthreads();
-    int v[8];
-    if (live) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] = w[r * WS_LD + j];
-        idct_1d<CONST_BITS - PASS1_BITS>(v);
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            w[r * WS_LD + j] = v[r];
-            wild = wild || abs(v[r]) > IDCT_PAIR_MAX;
-        }
-    }
-    __syncthreads();
-    if (live) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = w[j * WS_LD + k];
-        idct_1d<CONST_BITS + PASS1_BITS + 3>(v);
-        // range limit around +128 (the guard above keeps to where libjpeg's wrapping table and its saturating packs agree)
-        uint32_t lo = 0, hi = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) wild = wild || v[k] < -512 || v[k] > 511;
-        if (wild) flags[i] = 1;  // every lane that sees it stores the same 1
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            lo |= (uint32_t)min(max(v[k] + 128, 0), 255) << (8 * k);
-            hi |= (uint32_t)min(max(v[k + 4] + 128, 0), 255) << (8 * k);
-        }
-        *reinterpret_cast<uint2*>(dst) = make_uint2(lo, hi);
-    }
+    idct_block_store(w, j, live, wild, dst, flags + i);
 }
 
 // what kernel B needs of one image
@@ -597,15 +604,23 @@ __global__ void jpeg_canvas_kernel(const uint8_t* __restrict__ planes, const Des
     o[2] = (uint8_t)(px >> 16);
 }
 
-// Kernel A into the context's JPEG workspace: the component planes, sized by their own carving (one byte per coefficient)
-int jpeg_planes(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_blocks, const Desc* desc, int n, int32_t* flags, uint8_t** planes,
-                hipStream_t st) {
+// The component planes in the context's JPEG workspace, sized by their own carving (one byte per coefficient)
+int jpeg_plane_ws(avcer_ctx* ctx, int64_t n_blocks, uint8_t** planes) {
     uint8_t* p = nullptr;
     const auto carve = [&](Arena& a) { p = a.get<uint8_t>(64 * (size_t)n_blocks); };
     const size_t bytes = Arena().run(carve);
     void* base = nullptr;
     TRY(ws_reserve(ctx, WS_JPEG, bytes, &base));
     if (Arena(base, bytes).run(carve) != bytes || !p) return set_err(ctx, AVCER_ENOMEM, "jpeg workspace arithmetic");
+    *planes = p;
+    return AVCER_OK;
+}
+
+// Kernel A into them
+int jpeg_planes(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_blocks, const Desc* desc, int n, int32_t* flags, uint8_t** planes,
+                hipStream_t st) {
+    uint8_t* p = nullptr;
+    TRY(jpeg_plane_ws(ctx, n_blocks, &p));
     HIP_TRY(ctx, hipMemsetAsync(flags, 0, sizeof(int32_t) * (size_t)n, st));
     const long per = IDCT_THREADS / 64 * 8;
     jpeg_idct_kernel<<<(unsigned)((n_blocks + per - 1) / per), IDCT_THREADS, 0, st>>>(coeffs, desc, n, (long)n_blocks, p, flags);
@@ -1008,6 +1023,16 @@ __device__ __forceinline__ int ycc_at(const uint8_t* __restrict__ px, int c, int
 
 constexpr int FWD_THREADS = 256;  // 4 waves, 8 blocks each
 
+// the descriptor's three components are grids of blocks that fill its n_blocks, inside the storage: what a store into the
+// component planes relies on (a descriptor avcer_jpeg_plan wrote passes; the full check is plan_consistent)
+__device__ __forceinline__ bool planes_fit(const Desc& d, long n_blocks) {
+    if (d.bw[0] < 1 || d.bw[1] < 1 || d.bw[2] < 1 || d.bh[0] < 1 || d.bh[1] < 1 || d.bh[2] < 1 || d.bw[0] > 16384 || d.bw[1] > 16384 ||
+        d.bw[2] > 16384 || d.bh[0] > 16384 || d.bh[1] > 16384 || d.bh[2] > 16384)
+        return false;
+    const long all = (long)d.bw[0] * d.bh[0] + (long)d.bw[1] * d.bh[1] + (long)d.bw[2] * d.bh[2];
+    return d.coef_block >= 0 && d.n_blocks == all && all <= n_blocks - d.coef_block;
+}
+
 // The forward kernel, shaped like jpeg_idct_kernel.  A wave takes 8 consecutive blocks of the coefficient storage; lane = 8 *
 // block + j.  Lane j fetches the source pixels of ROW j of its block -- 8 for luma and for chroma at 1 x 1, 16 under 4:2:2, two
 // rows of 16 under 4:2:0 -- straight from the rectangle of the frame (single-byte loads: a row starts at any byte), converts
@@ -1023,19 +1048,26 @@ constexpr int FWD_THREADS = 256;  // 4 waves, 8 blocks each
 // block whose DC it inherits -- a real row's dummy on its left neighbour, a dummy row's on the last block of the row above in its
 // MCU -- and keeps the DC alone.  Frame, slot and coordinates are clamped to the tensor: a wrong rectangle reads wrong pixels,
 // never outside `src`.
-__global__ void __launch_bounds__(FWD_THREADS) jpeg_forward_kernel(const uint8_t* __restrict__ src, int N, int H, int W,
-                                                                   const int32_t* __restrict__ rects, const Desc* __restrict__ desc, int n,
-                                                                   int bgr, int16_t* __restrict__ coeffs, long n_blocks) {
-    __shared__ int ws[FWD_THREADS / 64][8 * 8 * WS_LD];
+//
+// PLANES (avcer_jpeg_roundtrip_*): the lane does not stop at row j of the quantised block.  It multiplies it by the table row it
+// has just divided by, leaves the products where it read the row from (its own dwords of LDS: no barrier) and goes on as kernel A
+// of the decoder does behind its dequantisation (idct_block_store): the block's samples reach the component planes without the
+// coefficients having left the chip.  `coeffs` may then be null; given, they are stored as well, dummy blocks included.
+template <bool PLANES>
+__device__ __forceinline__ void forward_block(int (&ws)[FWD_THREADS / 64][8 * 8 * WS_LD], const uint8_t* __restrict__ src, int N, int H,
+                                              int W, const int32_t* __restrict__ rects, const Desc* __restrict__ desc, int n, int bgr,
+                                              int16_t* __restrict__ coeffs, long n_blocks, uint8_t* __restrict__ planes,
+                                              int32_t* __restrict__ flags) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = lane >> 3, j = lane & 7;
     const long g = ((long)blockIdx.x * (FWD_THREADS / 64) + wave) * 8 + b;
     int* w = ws[wave] + b * 8 * WS_LD;
-    bool live = false, dummy = false;
+    bool live = false, dummy = false, wild = false;
     const uint16_t* qrow = nullptr;
-    int v[8];
+    uint8_t* dst = nullptr;  // PLANES: row j of the block in its component plane; null where the descriptor's geometry has no room for it
+    int v[8], i = 0;
     if (g < n_blocks) {
-        const int i = image_of_block(desc, n, g);
+        i = image_of_block(desc, n, g);
         const Desc* d = desc + i;
         const long r = g - d->coef_block;
         if (d->status == AVCER_JPEG_OK && r >= 0 && r < d->n_blocks) {
@@ -1045,6 +1077,8 @@ __global__ void __launch_bounds__(FWD_THREADS) jpeg_forward_kernel(const uint8_t
             const long rr = r - (c == 0 ? 0 : (c == 1 ? c0 : c1));
             int by = (int)(rr / d->bw[c]), bx = (int)(rr % d->bw[c]);
             const int wd = d->width, ht = d->height;
+            if (PLANES && planes_fit(*d, n_blocks) && rr < (long)d->bw[c] * d->bh[c])
+                dst = planes + 64 * (d->coef_block + (r - rr)) + ((long)by * 8 + j) * (d->bw[c] * 8) + bx * 8;  // as jpeg_idct_kernel
             const int hs = c ? d->hs : 1, vs = c ? d->vs : 1;  // source pixels per sample of this component
             if (c == 0) {
                 const int wb = (wd + 7) >> 3, hb = (ht + 7) >> 3;
@@ -1093,6 +1127,7 @@ __global__ void __launch_bounds__(FWD_THREADS) jpeg_forward_kernel(const uint8_t
         const int4 qv = *reinterpret_cast<const int4*>(qrow);
         const int qw[4] = {qv.x, qv.y, qv.z, qv.w};
         uint32_t o[4];
+        int dq[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             // jcdctmgr.c: divide by 8 q, halves away from zero
@@ -1102,10 +1137,44 @@ __global__ void __launch_bounds__(FWD_THREADS) jpeg_forward_kernel(const uint8_t
             int q = x < 0 ? -(int)a : (int)a;
             if (dummy && (j | k)) q = 0;
             if (k & 1) o[k >> 1] |= (uint32_t)q << 16; else o[k >> 1] = (uint32_t)q & 0xffff;
+            dq[k] = (int)(int16_t)q * (int)(q8 >> 3);  // what the decoder multiplies: the int16 it would read, and q
         }
-        *reinterpret_cast<uint4*>(coeffs + 64 * g + 8 * j) = make_uint4(o[0], o[1], o[2], o[3]);
+        if (!PLANES || coeffs) *reinterpret_cast<uint4*>(coeffs + 64 * g + 8 * j) = make_uint4(o[0], o[1], o[2], o[3]);
+        if (PLANES) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                w[j * WS_LD + k] = dq[k];
+                wild = wild || abs(dq[k]) > IDCT_PAIR_MAX;
+            }
+        }
     }
+    if (PLANES) idct_block_store(w, j, live && dst, wild, dst, flags + i);
 }
+
+__global__ void __launch_bounds__(FWD_THREADS) jpeg_forward_kernel(const uint8_t* __restrict__ src, int N, int H, int W,
+                                                                   const int32_t* __restrict__ rects, const Desc* __restrict__ desc, int n,
+                                                                   int bgr, int16_t* __restrict__ coeffs, long n_blocks) {
+    __shared__ int ws[FWD_THREADS / 64][8 * 8 * WS_LD];
+    forward_block<false>(ws, src, N, H, W, rects, desc, n, bgr, coeffs, n_blocks, nullptr, nullptr);
+}
+
+__global__ void __launch_bounds__(FWD_THREADS) jpeg_roundtrip_kernel(const uint8_t* __restrict__ src, int N, int H, int W,
+                                                                     const int32_t* __restrict__ rects, const Desc* __restrict__ desc, int n,
+                                                                     int bgr, int16_t* __restrict__ coeffs, long n_blocks,
+                                                                     uint8_t* __restrict__ planes, int32_t* __restrict__ flags) {
+    __shared__ int ws[FWD_THREADS / 64][8 * 8 * WS_LD];
+    forward_block<true>(ws, src, N, H, W, rects, desc, n, bgr, coeffs, n_blocks, planes, flags);
+}
+
+// The flags of avcer_jpeg_roundtrip_*, before the kernel above runs: 0, or 1 for a descriptor avcer_jpeg_plan did not write or
+// whose blocks leave the storage -- kernel B reads the planes through the descriptor's geometry, so it must not see such an image
+__global__ void roundtrip_check_kernel(const Desc* __restrict__ desc, int n, long n_blocks, int32_t* __restrict__ flags) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Desc& d = desc[i];
+    flags[i] = d.status == AVCER_JPEG_OK && !(plan_consistent(d) && d.n_blocks <= n_blocks - d.coef_block) ? 1 : 0;
+}
+
 
 // ------------------------------------------------------------------------------------------------ device: entropy coding
 // avcer_jpeg_pack: write_file / encode_block / BitWriter above on the device, byte for byte.  A WAVE codes one 8 x 8 block, lane k
@@ -1621,6 +1690,57 @@ extern "C" int avcer_jpeg_forward(avcer_ctx* ctx, const uint8_t* src, int N, int
     const long per = FWD_THREADS / 64 * 8;
     jpeg_forward_kernel<<<(unsigned)((n_blocks + per - 1) / per), FWD_THREADS, 0, (hipStream_t)stream>>>(src, N, H, W, rects, desc, n, bgr ? 1 : 0,
                                                                                                         coeffs, (long)n_blocks);
+    HIP_TRY(ctx, hipGetLastError());
+    return AVCER_OK;
+}
+
+namespace {
+
+// avcer_jpeg_roundtrip_*: arguments, workspace, the flags and the fused kernel; *planes is what kernel B then reads
+int jpeg_roundtrip_planes(avcer_ctx* ctx, const char* what, const uint8_t* src, int N, int H, int W, const int32_t* rects, const Desc* desc,
+                          int n, int bgr, int16_t* coeffs, int64_t n_blocks, int32_t* flags, const void* out, uint8_t** planes,
+                          hipStream_t st) {
+    if (!ctx) return AVCER_EINVAL;
+    if (!src || !rects || !desc || !flags || !out || n <= 0 || N <= 0 || H <= 0 || W <= 0 || n_blocks <= 0 || n_blocks >= (1LL << 34) ||
+        ((uintptr_t)coeffs & 15) || ((uintptr_t)desc & 15) || ((uintptr_t)rects & 3) || ((uintptr_t)flags & 3))
+        return set_err(ctx, AVCER_EINVAL, "%s: bad arguments (n %d, frames %d x %d x %d, %lld blocks; coefficients and descriptors 16-byte aligned)",
+                       what, n, N, H, W, (long long)n_blocks);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    TRY(jpeg_plane_ws(ctx, n_blocks, planes));
+    roundtrip_check_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(desc, n, (long)n_blocks, flags);
+    HIP_TRY(ctx, hipGetLastError());
+    const long per = FWD_THREADS / 64 * 8;
+    jpeg_roundtrip_kernel<<<(unsigned)((n_blocks + per - 1) / per), FWD_THREADS, 0, st>>>(src, N, H, W, rects, desc, n, bgr ? 1 : 0, coeffs,
+                                                                                           (long)n_blocks, *planes, flags);
+    HIP_TRY(ctx, hipGetLastError());
+    return AVCER_OK;
+}
+
+}  // namespace
+
+extern "C" int avcer_jpeg_roundtrip_tiles(avcer_ctx* ctx, const uint8_t* src, int N, int H, int W, const int32_t* rects,
+                                          const avcer_jpeg_desc* desc, int n, int bgr, int16_t* coeffs, int64_t n_blocks, int32_t* flags,
+                                          uint8_t* tiles, avcer_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* planes = nullptr;
+    TRY(jpeg_roundtrip_planes(ctx, "jpeg_roundtrip_tiles", src, N, H, W, rects, desc, n, bgr, coeffs, n_blocks, flags, tiles, &planes, st));
+    const long total = (long)n * 224 * 56;
+    jpeg_tiles_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(planes, desc, flags, n, tiles);
+    HIP_TRY(ctx, hipGetLastError());
+    return AVCER_OK;
+}
+
+extern "C" int avcer_jpeg_roundtrip_rgb(avcer_ctx* ctx, const uint8_t* src, int N, int H, int W, const int32_t* rects,
+                                        const avcer_jpeg_desc* desc, int n, int bgr, int16_t* coeffs, int64_t n_blocks, int32_t* flags,
+                                        uint8_t* canvas, int hmax, int wmax, avcer_stream_t stream) {
+    if (!ctx) return AVCER_EINVAL;
+    if (hmax <= 0 || wmax <= 0 || n <= 0 || (long)n * hmax * wmax >= (1L << 38))
+        return set_err(ctx, AVCER_EINVAL, "jpeg_roundtrip_rgb: canvas %d x %d x %d", n, hmax, wmax);
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* planes = nullptr;
+    TRY(jpeg_roundtrip_planes(ctx, "jpeg_roundtrip_rgb", src, N, H, W, rects, desc, n, bgr, coeffs, n_blocks, flags, canvas, &planes, st));
+    const long total = (long)n * hmax * wmax;
+    jpeg_canvas_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(planes, desc, flags, n, hmax, wmax, canvas);
     HIP_TRY(ctx, hipGetLastError());
     return AVCER_OK;
 }

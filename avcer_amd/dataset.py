@@ -26,6 +26,7 @@ from . import dist as adist
 from . import io_formats
 from .audio_pipeline import check_window, chunk_spans, replicate_per_frame, resample_out_len, resample_plan
 from .engine import MODE_DEFAULT, MODE_F16X3, MODE_FP32
+from .face_tiles import check_via_jpeg
 from .fusion import MODEL_ORDER, covered_frames
 from .video_pipeline import plan_clip
 
@@ -87,7 +88,7 @@ def _track00(engine, job: VideoJob, dets):
     return records, rows[np.argsort(records[rows, 0], kind="stable")]
 
 
-def _local_tables(engine, jobs, idx, plans, detector, m, sr, window, padding, max_frames, max_windows, side, passes):
+def _local_tables(engine, jobs, idx, plans, detector, m, sr, window, padding, max_frames, max_windows, side, passes, via_jpeg=False):
     """Stages 0 to audio for the videos `idx` (ascending): (stat|dyn rows [sum frames, 14], window logits [sum windows, c])."""
     dev = engine.device
     main = torch.cuda.current_stream(dev)
@@ -155,7 +156,12 @@ def _local_tables(engine, jobs, idx, plans, detector, m, sr, window, padding, ma
             present[records[rows, 0]] = True
             presents.append(present)
             rects = torch.from_numpy(records[rows][:, [0, 2, 3, 4, 5]].astype(np.int32))
-            pend.append(engine.crop_tiles(frames, rects, bgr=True))
+            if via_jpeg:  # the tiles as stage 1 of the reference reads them back from stage 0's files (run_inference's faces_via_jpeg)
+                from . import jpeg
+
+                pend.append(jpeg.roundtrip_tiles(engine, frames, rects, bgr=True, quality=95, subsampling=2))
+            else:
+                pend.append(engine.crop_tiles(frames, rects, bgr=True))
             n_pend += len(rows)
             static_passes(False)
         passes["at"] = None
@@ -199,13 +205,17 @@ def run_dataset(engine, jobs: Sequence[VideoJob], detector=None, *, mode: int = 
                 step: float = 0.5, padding: str = "mean", weights_prob_model=None, weights_model=(1, 1, 1),
                 ce_weights_type: bool = True, ce_mask: bool = False, max_frames_per_pass: int = 2048,
                 max_windows_per_pass: int = 128, path_save_results: str = "", flag_save_prob: bool = False,
-                skip_failed: bool = False, distributed: bool = False) -> DatasetResults:
+                skip_failed: bool = False, distributed: bool = False, faces_via_jpeg: bool = False) -> DatasetResults:
     """`run_inference` for every job of a set, with the videos sharing the GPU passes (module docstring).  Returns a
     `DatasetResults`: a list with one dict per job, in job order, holding `name` and the keys of `run_inference` -- av / vs / vd
     / a, compound_prob, static_probs, dynamic_logits, audio_rows, audio_frames, records -- with the bits `run_inference` gives for
     that video alone, in MODE_F16X3 and in MODE_FP32.  The real-time factor is one figure for the call, on the list's
     `real_time_factor` attribute: elapsed time over the summed duration of the videos that ran.  `flag_save_prob` writes each
     video's CSV files as `run_inference` does (io_formats).  Heat maps are not produced on this path.
+
+    `faces_via_jpeg` (for the call, as the other options): `run_inference`'s option of that name for every job -- the tiles of track
+    00 are what reading stage 0's JPEG files back gives; the results are those of `run_inference(..., faces_via_jpeg=True)` for each
+    video alone.  Off by default; anything but a bool raises ValueError before any work.
 
     Passes: at most `max_frames_per_pass` tiles per static-CNN call (and LSTM windows per LSTM call), at most
     `max_windows_per_pass` audio windows per audio call; device memory for tiles is one pass plus one video.
@@ -230,6 +240,7 @@ def run_dataset(engine, jobs: Sequence[VideoJob], detector=None, *, mode: int = 
         raise ValueError(f"padding={padding!r}")
     if max_frames_per_pass < 1 or max_windows_per_pass < 1:
         raise ValueError("run_dataset: pass sizes >= 1")
+    check_via_jpeg(faces_via_jpeg)
     check_window(engine, window, sr)
     errors = {}
 
@@ -275,7 +286,7 @@ def run_dataset(engine, jobs: Sequence[VideoJob], detector=None, *, mode: int = 
                 return (torch.zeros(0, 14, device=engine.device), torch.zeros(0, max(engine.audio_classes, 1), device=engine.device))
             try:
                 return _local_tables(engine, jobs, mine, plans, detector, m, sr, window, padding, int(max_frames_per_pass),
-                                     int(max_windows_per_pass), side, passes)
+                                     int(max_windows_per_pass), side, passes, bool(faces_via_jpeg))
             except (ValueError, FileNotFoundError) as e:
                 bad = passes["at"]
                 if bad is None:

@@ -491,6 +491,41 @@ class Engine:
                                                 _ptr(desc), int(n), 1 if bgr else 0, _ptr(coeffs), int(n_blocks), self._stream()))
         return coeffs
 
+    def _jpeg_roundtrip_args(self, what, src, rects, desc, n, n_blocks, keep_coeffs):
+        if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[-1] != 3 or not src.is_cuda or not src.is_contiguous():
+            raise ValueError(f"{what}: src must be a contiguous uint8 [N,H,W,3] on the device")
+        if rects.dtype != torch.int32 or tuple(rects.shape) != (n, 5) or not rects.is_cuda or not rects.is_contiguous():
+            raise ValueError(f"{what}: rects must be a contiguous int32 [n,5] on the device")
+        if desc.dtype != torch.uint8 or desc.numel() < _JPEG_DESC_BYTES * n or not desc.is_cuda or n <= 0 or n_blocks <= 0:
+            raise ValueError(f"{what}: desc uint8 [sizeof(avcer_jpeg_desc) * n] on the device, n and n_blocks positive")
+        return (self._new(64 * int(n_blocks), dtype=torch.int16) if keep_coeffs else None), self._new(int(n), dtype=torch.int32)
+
+    def jpeg_roundtrip_tiles(self, src, rects, desc, n: int, n_blocks: int, bgr: bool = False, keep_coeffs: bool = False):
+        """The crops as the JPEG files of them would read back, without the files (avcer_jpeg_roundtrip_tiles): arguments as
+        jpeg_forward takes them -> (RGB tiles u8 [n,224,224,3] as jpeg_tiles gives them for the files jpeg.encode_images writes,
+        flags i32 [n], the quantised coefficients int16 [64 * n_blocks] of jpeg_forward when `keep_coeffs`, else None)."""
+        coeffs, flags = self._jpeg_roundtrip_args("jpeg_roundtrip_tiles", src, rects, desc, n, n_blocks, keep_coeffs)
+        tiles = self._new(int(n), 224, 224, 3, dtype=torch.uint8)
+        self._check(self.lib.avcer_jpeg_roundtrip_tiles(self.ctx, _ptr(src), int(src.shape[0]), int(src.shape[1]), int(src.shape[2]),
+                                                        _ptr(rects), _ptr(desc), int(n), 1 if bgr else 0,
+                                                        _ptr(coeffs) if keep_coeffs else None, int(n_blocks), _ptr(flags), _ptr(tiles),
+                                                        self._stream()))
+        return tiles, flags, coeffs
+
+    def jpeg_roundtrip_rgb(self, src, rects, desc, n: int, n_blocks: int, hmax: int, wmax: int, bgr: bool = False,
+                           keep_coeffs: bool = False):
+        """The same round trip at full size (avcer_jpeg_roundtrip_rgb) -> (canvas u8 [n,hmax,wmax,3] RGB as jpeg_rgb gives it, flags,
+        coefficients or None)."""
+        coeffs, flags = self._jpeg_roundtrip_args("jpeg_roundtrip_rgb", src, rects, desc, n, n_blocks, keep_coeffs)
+        if hmax <= 0 or wmax <= 0:
+            raise ValueError("jpeg_roundtrip_rgb: canvas sizes positive")
+        canvas = self._new(int(n), int(hmax), int(wmax), 3, dtype=torch.uint8)
+        self._check(self.lib.avcer_jpeg_roundtrip_rgb(self.ctx, _ptr(src), int(src.shape[0]), int(src.shape[1]), int(src.shape[2]),
+                                                      _ptr(rects), _ptr(desc), int(n), 1 if bgr else 0,
+                                                      _ptr(coeffs) if keep_coeffs else None, int(n_blocks), _ptr(flags), _ptr(canvas),
+                                                      int(hmax), int(wmax), self._stream()))
+        return canvas, flags, coeffs
+
     def jpeg_pack(self, coeffs, desc, n: int, blocks: int, cap_bytes: int):
         """The entropy-coding half of the JPEG encoder on the device (avcer_jpeg_pack): coefficients int16 [>= 64 * blocks] as
         jpeg_forward leaves them and desc = n records of struct avcer_jpeg_desc as bytes, both on the device -> (out u8 [cap_bytes]:

@@ -13,7 +13,11 @@ of frames, only the kept rows return to the host) and the crop + NEAREST resize 
 frame, is sequential in time and stays on the host, as in the reference (scipy there too).  The RetinaFace-R50
 network runs on the same implicit-GEMM kernel as the recognition models (`avcer_face_forward`, mirror
 `RetinaFacePredictor` below).  Tiles go straight to `avcer_static_forward`; the reference's JPEG file round trip
-(cv2.imwrite -> PIL.Image.open) is gone, which is the only intended difference.  Video decoding is not part of this build.
+(cv2.imwrite -> PIL.Image.open) is gone, which is the only intended difference -- and with `via_jpeg=True`
+(`VideoTiler.process`; `faces_via_jpeg` of run_inference and run_dataset) that difference is gone as well: every tile is then what
+reading the crop's JPEG file back gives (quality 95, 4:2:0, libjpeg-turbo's arithmetic on both sides, bit for bit what PIL writes
+and reads; cv2 is not among this project's dependencies, the claim about it ends at the shared libjpeg defaults), computed on the
+device without the file (jpeg.roundtrip_tiles).  Video decoding is not part of this build.
 """
 from __future__ import annotations
 
@@ -308,9 +312,13 @@ class VideoTiler:
         self.face_tracker = SimpleFaceTracker(iou_threshold=0.4, minimum_face_size=0.0)
 
     def process(self, frames_bgr, dets_per_frame: Sequence[np.ndarray], save_path: Optional[str] = None, video_name: Optional[str] = None,
-                entropy: str = "host"):
+                entropy: str = "host", via_jpeg: bool = False):
         """`save_path` and `video_name` given: the crops are also written as the reference's face folders (write_face_crops, which
-        takes `entropy`)."""
+        takes `entropy`).
+        `via_jpeg`: the tiles are what stage 1 of the reference reads back from those files (jpeg.roundtrip_tiles on the same
+        half-open rectangles, BGR in, quality 95, 4:2:0) instead of the raw crops; files asked for in the same call are packed
+        from that pass's coefficients.  Anything but a bool raises ValueError before any work."""
+        check_via_jpeg(via_jpeg)
         if (save_path is None) != (video_name is None):
             raise ValueError("give both save_path and video_name, or neither")
         frames = frames_bgr if torch.is_tensor(frames_bgr) else torch.from_numpy(np.ascontiguousarray(frames_bgr))
@@ -325,6 +333,8 @@ class VideoTiler:
         records = self.engine.track_faces(dets_per_frame, w, h, self.face_tracker.iou_threshold, self.face_tracker.minimum_face_size)
         if not len(records):
             return records, torch.zeros((0, 224, 224, 3), dtype=torch.uint8, device=self.engine.device)
+        if via_jpeg:
+            return records, roundtrip_face_tiles(self.engine, frames, records, save_path, video_name, entropy=entropy)[0]
         rects = torch.from_numpy(records[:, [0, 2, 3, 4, 5]].astype(np.int32))
         if save_path is not None:
             frames = frames.to(self.engine.device)  # one copy for both consumers
@@ -332,9 +342,23 @@ class VideoTiler:
         return records, self.engine.crop_tiles(frames, rects, bgr=True)
 
 
+def check_via_jpeg(value) -> None:
+    """The `via_jpeg` / `faces_via_jpeg` option is a bool; anything else is a ValueError (before any work, at every entry point)."""
+    if not isinstance(value, (bool, np.bool_)):
+        raise ValueError(f"faces_via_jpeg / via_jpeg must be True or False, not {value!r}")
+
+
 def face_crop_paths(records: np.ndarray, save_path: str, video_name: str) -> List[str]:
     """get_face_images.py:58-60: `<save_path>/<video_name>/<track:02d>/<frame:06d>.jpg` of every record, in record order."""
     return [os.path.join(save_path, video_name, str(int(t)).zfill(2), str(int(f)).zfill(6) + ".jpg") for f, t in records[:, :2]]
+
+
+def _write_files(paths: List[str], blobs) -> None:
+    for folder in sorted({os.path.dirname(p) for p in paths}):
+        os.makedirs(folder, exist_ok=True)
+    for p, blob in zip(paths, blobs):
+        with open(p, "wb") as f:
+            f.write(blob)
 
 
 def write_face_crops(engine, frames_bgr, records: np.ndarray, save_path: str, video_name: str, quality: int = 95,
@@ -351,12 +375,27 @@ def write_face_crops(engine, frames_bgr, records: np.ndarray, save_path: str, vi
     if not paths:
         return paths
     blobs = jpeg.encode_images(engine, frames_bgr, records[:, [0, 2, 3, 4, 5]], bgr=True, quality=quality, subsampling=2, entropy=entropy)
-    for folder in sorted({os.path.dirname(p) for p in paths}):
-        os.makedirs(folder, exist_ok=True)
-    for p, blob in zip(paths, blobs):
-        with open(p, "wb") as f:
-            f.write(blob)
+    _write_files(paths, blobs)
     return paths
+
+
+def roundtrip_face_tiles(engine, frames_bgr, records: np.ndarray, save_path: Optional[str] = None, video_name: Optional[str] = None,
+                         quality: int = 95, entropy: str = "host"):
+    """The tiles of `records` as the reference's stage 1 reads them back from stage 0's files (jpeg.roundtrip_tiles: the rectangles
+    of write_face_crops, BGR in, 4:2:0) -> (tiles u8 [n,224,224,3] RGB on the device, the paths written or None).  With `save_path`
+    and `video_name` the files of write_face_crops are written too, packed from the coefficients of the same pass: no second forward
+    pass runs."""
+    from . import jpeg
+
+    jpeg._check_entropy(entropy)
+    records = np.asarray(records).reshape(-1, 6)
+    rects = records[:, [0, 2, 3, 4, 5]]
+    if save_path is None or not len(records):
+        return jpeg.roundtrip_tiles(engine, frames_bgr, rects, bgr=True, quality=quality, subsampling=2), None
+    tiles, coeffs, d_dev, desc = jpeg.roundtrip_tiles(engine, frames_bgr, rects, bgr=True, quality=quality, subsampling=2, keep_coeffs=True)
+    paths = face_crop_paths(records, save_path, video_name)
+    _write_files(paths, jpeg.files_from_coeffs(engine, coeffs, d_dev, desc, entropy=entropy))
+    return tiles, paths
 
 
 def track_clip(records: np.ndarray, tiles: torch.Tensor, track: int, total_frames: int):

@@ -14,6 +14,9 @@ Both functions also return, per file, which path served it: "device" or "pil".
 With entropy="device" the host parses the headers only (`scan_batch`), the files' entropy-coded bytes cross instead of the
 coefficients, and `Engine.jpeg_unpack` Huffman-decodes them on the device (csrc/jpeg.hip avcer_jpeg_unpack); tiles, canvas and paths
 are the same.
+
+`roundtrip_tiles` / `roundtrip_canvas` (the last part of this file) are decode(encode(crop)) without a file: the crop as the
+reference's stage 1 sees it, from one fused kernel and the decoder's pixel kernel.
 """
 from __future__ import annotations
 
@@ -625,23 +628,17 @@ def _pack_to_host(engine, st, coeffs, d_dev, n: int, blocks: int) -> list:
     return [blob[offs[i]:offs[i + 1]].tobytes() for i in range(n)]
 
 
-def encode_images(engine, src, rects, bgr: bool = False, quality: int = 95, subsampling: int = 2, threads: int = 0,
-                  entropy: str = "host") -> list:
-    """JPEG files of n images cut out of `src` (u8 [N,H,W,3], moved to the device if it is not there): image i is the half-open
-    rectangle rects[i] = (slot, x0, y0, x1, y1).  Returns the n files as bytes, byte-identical to
-    PIL.Image.fromarray(rgb).save(f, "JPEG", quality=quality, subsampling=subsampling).  plan (host) -> descriptors to the device
-    -> avcer_jpeg_forward -> coefficients into the pinned staging of the engine -> avcer_jpeg_write_batch (host threads).
-    entropy="device": the coefficients stay where they are, avcer_jpeg_pack writes the files on the device and only their bytes
-    cross (`threads` is then unused); the files are the same."""
-    if entropy not in ("host", "device"):
-        raise ValueError(f'entropy must be "host" or "device", not {entropy!r}')
+def _plan_to_device(engine, src, rects, quality, subsampling):
+    """What every call that cuts images out of `src` does first: the checks, avcer_jpeg_plan on the host, source, rectangles and
+    descriptors on the device.  Returns None for no image, else (src, rects i32 [n,5], descriptors as bytes) on the device, the
+    DESC records on the host, n, the blocks of the plan, and the engine's staging."""
     src = src if torch.is_tensor(src) else torch.from_numpy(np.array(src))  # a copy: torch.from_numpy wants a writable array
     if src.dim() != 4 or src.shape[-1] != 3 or src.dtype != torch.uint8:
         raise ValueError("src must be uint8 [N,H,W,3]")
     r = _encode_rects(src, rects)
     n = len(r)
     if n == 0:
-        return []
+        return None
     dev = engine.device
     st = engine.__dict__.setdefault("_jpeg_staging", _Staging())
     sizes = np.stack([r[:, 3] - r[:, 1], r[:, 4] - r[:, 2]], axis=1)
@@ -653,11 +650,25 @@ def encode_images(engine, src, rects, bgr: bool = False, quality: int = 95, subs
     host = desc.copy()
     d_dev = st.desc[:DESC.itemsize * n].to(dev, non_blocking=True)
     r_dev = torch.from_numpy(r).to(dev)
-    coeffs = engine.jpeg_forward(src.to(dev).contiguous(), r_dev, d_dev, n, blocks, bgr=bgr)
+    return src.to(dev).contiguous(), r_dev, d_dev, host, n, blocks, st
+
+
+def files_from_coeffs(engine, coeffs, d_dev, host: np.ndarray, threads: int = 0, entropy: str = "host") -> list:
+    """The entropy-coding half of encode_images: coefficients int16 [>= 64 * blocks] on the device as avcer_jpeg_forward (or a
+    round trip with keep_coeffs) left them, their descriptors on the device (`d_dev`) and on the host (`host`, DESC records) -> the
+    n files as bytes."""
+    _check_entropy(entropy)
+    dev = engine.device
+    st = engine.__dict__.setdefault("_jpeg_staging", _Staging())
+    n = len(host)
+    blocks = int((host["coef_block"] + host["n_blocks"]).max()) if n else 0
+    if n == 0:
+        return []
     if entropy == "device":
         st.event = torch.cuda.Event()  # the descriptors were copied out of the pinned staging
         st.event.record(torch.cuda.current_stream(dev))
         return _pack_to_host(engine, st, coeffs, d_dev, n, blocks)
+    st.reserve(blocks, n)
     st.coeffs[:64 * blocks].copy_(coeffs[:64 * blocks], non_blocking=True)
     st.event = torch.cuda.Event()
     st.event.record(torch.cuda.current_stream(dev))
@@ -675,3 +686,89 @@ def encode_images(engine, src, rects, bgr: bool = False, quality: int = 95, subs
     if (d["status"] != OK).any():
         raise _not_written(d["status"], d["reason"])
     return [out[offsets[i]:offsets[i + 1]].tobytes() for i in range(n)]
+
+
+def encode_images(engine, src, rects, bgr: bool = False, quality: int = 95, subsampling: int = 2, threads: int = 0,
+                  entropy: str = "host") -> list:
+    """JPEG files of n images cut out of `src` (u8 [N,H,W,3], moved to the device if it is not there): image i is the half-open
+    rectangle rects[i] = (slot, x0, y0, x1, y1).  Returns the n files as bytes, byte-identical to
+    PIL.Image.fromarray(rgb).save(f, "JPEG", quality=quality, subsampling=subsampling).  plan (host) -> descriptors to the device
+    -> avcer_jpeg_forward -> coefficients into the pinned staging of the engine -> avcer_jpeg_write_batch (host threads).
+    entropy="device": the coefficients stay where they are, avcer_jpeg_pack writes the files on the device and only their bytes
+    cross (`threads` is then unused); the files are the same."""
+    _check_entropy(entropy)
+    planned = _plan_to_device(engine, src, rects, quality, subsampling)
+    if planned is None:
+        return []
+    src_d, r_dev, d_dev, host, n, blocks, _ = planned
+    coeffs = engine.jpeg_forward(src_d, r_dev, d_dev, n, blocks, bgr=bgr)
+    return files_from_coeffs(engine, coeffs, d_dev, host, threads, entropy)
+
+
+# ==================================================================================================== the round trip
+# What stage 1 of the reference sees of a face crop is the JPEG file stage 0 wrote of it, read back (include/avcer_hip.h "The round
+# trip without the file").  Huffman coding is lossless, so that picture is decode(encode(crop)) = the pixel pass of the decoder on
+# the coefficients of the encoder's forward pass: no file, no entropy pass.  cv2 is not among this project's dependencies: the claim
+# is identity with PIL on both sides (libjpeg-turbo, the defaults cv2.imwrite uses: quality 95, 4:2:0).
+def roundtrip_numpy(images, quality: int = 95, subsampling: int = 2):
+    """The CPU statement of the round trip (for the tests; not a product path): RGB images u8 [h, w, 3] -> per image
+    Image.open(the file Image.save(..., "JPEG", quality, subsampling) writes of it).convert("RGB"), u8 [h, w, 3]."""
+    return pixels_numpy(*forward_numpy(images, quality, subsampling))
+
+
+def check_roundtrip_options(lib, quality, subsampling):
+    """ValueError for a quality or a subsampling avcer_jpeg_plan refuses (asked of the call itself, with no image)."""
+    plan(lib, np.zeros((0, 2), dtype=np.int32), quality, subsampling)
+
+
+def _roundtrip(engine, src, rects, bgr, quality, subsampling, keep_coeffs, launch):
+    check_roundtrip_options(engine.lib, quality, subsampling)
+    planned = _plan_to_device(engine, src, rects, quality, subsampling)
+    if planned is None:
+        return None
+    src_d, r_dev, d_dev, host, n, blocks, st = planned
+    out, flags, coeffs = launch(src_d, r_dev, d_dev, host, n, blocks)
+    st.event = torch.cuda.Event()  # the descriptors were copied out of the pinned staging
+    st.event.record(torch.cuda.current_stream(engine.device))
+    # the one wait of the call.  An encoder's own coefficients cannot leave the inverse DCT's range (include/avcer_hip.h): a flag is
+    # an error of this library, and a zero tile must not reach a network as if it were a face
+    bad = np.nonzero(_flags_to_host(engine, flags)())[0]
+    if len(bad):
+        raise RuntimeError(f"image {int(bad[0])}: the JPEG round trip left the range of the inverse DCT (flag 1, include/avcer_hip.h)")
+    return out, coeffs, d_dev, host
+
+
+def roundtrip_tiles(engine, src, rects, bgr: bool = False, quality: int = 95, subsampling: int = 2, keep_coeffs: bool = False):
+    """n images cut out of `src` (u8 [N,H,W,3]; image i is the half-open rectangle rects[i] = (slot, x0, y0, x1, y1)) as their JPEG
+    files would read back: tiles u8 [n,224,224,3] RGB on the device, tile i bit-identical to
+    decode_tiles(engine, encode_images(engine, src, rects, bgr, quality, subsampling))[0][i] -- to
+    Image.open(file).convert("RGB").resize((224, 224), NEAREST) of the file PIL writes of the image.  One fused kernel (forward DCT,
+    quantisation, dequantisation, inverse DCT per block) and the decoder's pixel kernel; no file, no entropy pass, and the
+    coefficients stay on the chip.
+    keep_coeffs: returns (tiles, coeffs, d_dev, desc) instead -- the quantised coefficients int16 [64 * blocks] on the device exactly
+    as avcer_jpeg_forward stores them, with their descriptors on the device and on the host: files_from_coeffs writes the files
+    from them without a second forward pass.
+    A quality or subsampling avcer_jpeg_plan refuses, an empty rectangle or one that leaves its frame: ValueError before any launch."""
+    got = _roundtrip(engine, src, rects, bgr, quality, subsampling, keep_coeffs,
+                     lambda s, r, d, host, n, blocks: engine.jpeg_roundtrip_tiles(s, r, d, n, blocks, bgr=bgr, keep_coeffs=keep_coeffs))
+    if got is None:
+        tiles = torch.empty(0, 224, 224, 3, dtype=torch.uint8, device=engine.device)
+        return (tiles, torch.empty(0, dtype=torch.int16, device=engine.device), None, np.zeros(0, dtype=DESC)) if keep_coeffs else tiles
+    return got if keep_coeffs else got[0]
+
+
+def roundtrip_canvas(engine, src, rects, bgr: bool = False, quality: int = 95, subsampling: int = 2, keep_coeffs: bool = False):
+    """The full-size twin of roundtrip_tiles: (canvas u8 [max(n,1), max h, max w, 3] RGB on the device, rects i32 [n,5] = (i, 0, 0, w,
+    h)) in the layout of decode_canvas, image i bit-identical to Image.open(file).convert("RGB"); with keep_coeffs
+    ((canvas, rects), coeffs, d_dev, desc)."""
+    def launch(s, r, d, host, n, blocks):
+        return engine.jpeg_roundtrip_rgb(s, r, d, n, blocks, int(host["height"].max()), int(host["width"].max()), bgr=bgr,
+                                         keep_coeffs=keep_coeffs)
+
+    got = _roundtrip(engine, src, rects, bgr, quality, subsampling, keep_coeffs, launch)
+    if got is None:
+        out = (torch.zeros(1, 1, 1, 3, dtype=torch.uint8, device=engine.device), np.zeros((0, 5), dtype=np.int32))
+        return (out, torch.empty(0, dtype=torch.int16, device=engine.device), None, np.zeros(0, dtype=DESC)) if keep_coeffs else out
+    canvas, coeffs, d_dev, host = got
+    out = (canvas, np.array([(i, 0, 0, int(d["width"]), int(d["height"])) for i, d in enumerate(host)], dtype=np.int32).reshape(-1, 5))
+    return (out, coeffs, d_dev, host) if keep_coeffs else out

@@ -19,7 +19,7 @@ import torch
 from . import io_formats
 from .audio_pipeline import audio_forward, check_window, replicate_per_frame, resample_plan
 from .engine import MODE_DEFAULT
-from .face_tiles import VideoTiler, track_clip, write_face_crops
+from .face_tiles import VideoTiler, check_via_jpeg, face_crop_paths, track_clip, write_face_crops
 from .fusion import MODEL_ORDER, fuse
 from .video_pipeline import visual_forward
 
@@ -29,7 +29,7 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
                   weights_prob_model=None, weights_model=(1, 1, 1), ce_weights_type: bool = True, ce_mask: bool = False,
                   sr: int = 16000, window: float = 4, step: float = 0.5, padding: str = "mean", mode: int = MODE_DEFAULT,
                   flag_heatmaps: bool = False, model_heatmaps: str = "static", wav_sr: Optional[int] = None,
-                  path_save_faces: Optional[str] = None, jpeg_entropy: str = "host"):
+                  path_save_faces: Optional[str] = None, jpeg_entropy: str = "host", faces_via_jpeg: bool = False):
     """engine: an `Engine` with the static, dynamic and audio weights loaded.  frames_bgr u8 [T,H,W,3] as cv2 decodes
     them; wav float32 [L] mono at `sr`; fps as `int(cv2.CAP_PROP_FPS)` gives it (get_face_images.py:23).
     `wav_sr`: `wav` is source audio at that rate instead -- int16 [L] / [L, C] as the frames lie in the WAV file ffmpeg writes
@@ -52,9 +52,16 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
     `<path_save_faces>/<name_video>/<track:02d>/<frame:06d>.jpg`, encoded from the frames on the device
     (face_tiles.write_face_crops); `out["face_files"]` lists the paths in record order.  Off by default.
     `jpeg_entropy`: where those files are Huffman-coded, "host" (the default) or "device" (jpeg.encode_images); the files are the
-    same.  Any other value raises ValueError before any work."""
+    same.  Any other value raises ValueError before any work.
+    `faces_via_jpeg`: the visual models see every face crop as the reference's stage 1 does -- read back from the JPEG file stage 0
+    writes of it (quality 95, 4:2:0; get_face_images.py:52-63, get_prob_video.py:93-109) -- instead of the raw crop: the results
+    are then, bit for bit in the same arithmetic mode, those of `preprocess_video_and_predict` on the folder `path_save_faces`
+    writes.  Computed on the device without the files (jpeg.roundtrip_tiles); with `path_save_faces` the files are packed from the
+    same pass's coefficients, with `flag_heatmaps` the base image is the linear resize of the round-tripped crop
+    (data/utils.py:105).  Off by default: nothing changes then.  Anything but a bool raises ValueError before any work."""
     if jpeg_entropy not in ("host", "device"):
         raise ValueError(f'jpeg_entropy must be "host" or "device", not {jpeg_entropy!r}')
+    check_via_jpeg(faces_via_jpeg)
     if flag_heatmaps:
         from . import heatmaps as hm
 
@@ -93,8 +100,14 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
             # (2) faces -> tracks -> tiles (get_face_images.py:38-63), then the visual models on track 00
             if "clip" not in host:
                 dets = detections if detections is not None else detector.batch(frames, rgb=False)  # get_face_images.py:49
-                records, tiles = VideoTiler(engine).process(frames, dets)
-                if path_save_faces:
+                if faces_via_jpeg:
+                    records, tiles = VideoTiler(engine).process(frames, dets, path_save_faces or None, name_video if path_save_faces else None,
+                                                                entropy=jpeg_entropy, via_jpeg=True)
+                    if path_save_faces:
+                        host["face_files"] = face_crop_paths(records, path_save_faces, name_video)
+                else:
+                    records, tiles = VideoTiler(engine).process(frames, dets)
+                if path_save_faces and not faces_via_jpeg:
                     host["face_files"] = write_face_crops(engine, frames, records, path_save_faces, name_video, entropy=jpeg_entropy)
                 if not (len(records) and (records[:, 1] == 0).any()):
                     raise FileNotFoundError("no face track 00 (os.listdir(<faces>/00) fails in the reference, get_prob_video.py:79)")
@@ -110,7 +123,12 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
                     at = {int(f): k for k, f in enumerate(r00[:, 0])}
                     pick = r00[[at[int(f)] for f in fidx]]
                     rects = torch.from_numpy(pick[:, [0, 2, 3, 4, 5]].astype(np.int32))
-                    base = engine.crop_resize_linear(frames, rects, swap_rb=True)
+                    if faces_via_jpeg:  # cv2.resize of the read-back crop (get_prob_video.py:99-100, data/utils.py:105)
+                        from . import jpeg
+
+                        base = engine.crop_resize_linear(*jpeg.roundtrip_canvas(engine, frames, rects, bgr=True), swap_rb=False)
+                    else:
+                        base = engine.crop_resize_linear(frames, rects, swap_rb=True)
                     maps = (fidx, engine.cam_render(cam, rows, cls, base, hm.JET_BGR, hm.IMAGE_WEIGHT))
                 else:
                     maps = (fidx, torch.zeros((0, 224, 224, 3), dtype=torch.uint8, device=dev))

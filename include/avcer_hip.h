@@ -86,7 +86,9 @@ enum {
  *      avcer_jpeg_scan_batch, avcer_jpeg_unpack, avcer_jpeg_unpack_host with their structs avcer_jpeg_tab and avcer_jpeg_scan: entropy
  *      DECODING on the device, joined under 8 the same way: three more symbols, the descriptor unchanged.
  *      avcer_attention_long, avcer_set_audio_max_tokens, avcer_audio_max_tokens (audio windows past 256 tokens: attention that
- *      streams key tiles through LDS) joined under 8 the same way: three more symbols, nothing that existed changed. */
+ *      streams key tiles through LDS) joined under 8 the same way: three more symbols, nothing that existed changed.
+ *      avcer_jpeg_roundtrip_tiles, avcer_jpeg_roundtrip_rgb (face crops as the files of stage 0 hold them, without the files)
+ *      joined under 8 the same way: two more symbols, the descriptor unchanged. */
 #define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
@@ -517,6 +519,36 @@ int avcer_jpeg_write_batch(avcer_ctx* ctx, const int16_t* coeffs_host, avcer_jpe
  *   ceil((20 + 63 * 26) / 8) = 208) comes from the context's JPEG workspace.  n_blocks < 2^31. */
 int avcer_jpeg_pack(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_blocks, const avcer_jpeg_desc* desc, int n, uint8_t* out,
                     int64_t cap_bytes, int64_t* offsets, int32_t* status, int64_t* bytes_needed, avcer_stream_t stream);
+
+/* The round trip without the file: what stage 1 of the reference sees of a crop is not the crop but the JPEG file stage 0 wrote
+ * of it, read back,
+ *   ref: data/get_face_images.py:52-63 (cv2.imwrite, quality 95, 4:2:0), get_prob_video.py:93-109 and data/utils.py:19-39 (read
+ *        back, NEAREST to 224 x 224), data/utils.py:105 (the heat-map base image: cv2.resize of the read-back crop)
+ * and Huffman coding is lossless, so that picture is quantise -> dequantise with libjpeg's arithmetic on both sides: no file and
+ * no entropy pass is needed to compute it.  The contract is bit-identity with Image.open(file).convert("RGB") of the file
+ * jpeg.encode_images (avcer_jpeg_forward + avcer_jpeg_write_batch, so PIL's Image.save) would write of the same rectangle: a
+ * tolerance of zero, independent of the arithmetic mode.
+ *
+ * avcer_jpeg_roundtrip_tiles: src, N, H, W, rects, desc, n, bgr as avcer_jpeg_forward takes them (desc as avcer_jpeg_plan wrote
+ *   them, 16-byte aligned on the device) -> tiles u8 [n,224,224,3] RGB as avcer_jpeg_tiles would give them for those files.
+ * avcer_jpeg_roundtrip_rgb: the same images at full size -> canvas u8 [n,hmax,wmax,3] as avcer_jpeg_rgb would give it.
+ * coeffs: NULL, or int16 [n_blocks, 64] (16-byte aligned) that receives exactly what avcer_jpeg_forward stores for the same call,
+ *   dummy blocks included: one pass then serves the tiles and avcer_jpeg_pack / avcer_jpeg_write_batch.
+ * flags i32 [n] (device, written by both calls): as avcer_jpeg_tiles writes them -- an encoder's own coefficients cannot leave the
+ *   range, so a 1 there would be a finding about the kernel -- and 1 as well for a descriptor avcer_jpeg_plan did not write or
+ *   whose blocks lie outside the n_blocks blocks: such an image's output is zero and nothing is stored or read through its
+ *   geometry.  A desc[i] that is NOT_HANDLED yields zeros and flag 0, as in avcer_jpeg_tiles.
+ * Both calls run three kernels on `stream` -- the flags; the forward path of avcer_jpeg_forward per 8 x 8 block, unchanged, with the
+ * dequantisation and the inverse DCT of avcer_jpeg_tiles' first kernel behind it in the same lanes, storing u8 component planes
+ * into the context's JPEG workspace (64 bytes per block; the coefficients do not leave the chip unless `coeffs` asks for them);
+ * then avcer_jpeg_tiles' / avcer_jpeg_rgb's second kernel, unchanged -- and do not synchronise with the host.  Errors: AVCER_EINVAL
+ * for a NULL or misaligned pointer or a size out of range (avcer_last_error names the call), as the neighbouring calls. */
+int avcer_jpeg_roundtrip_tiles(avcer_ctx* ctx, const uint8_t* src, int N, int H, int W, const int32_t* rects, const avcer_jpeg_desc* desc,
+                               int n, int bgr, int16_t* coeffs_or_null, int64_t n_blocks, int32_t* flags, uint8_t* tiles,
+                               avcer_stream_t stream);
+int avcer_jpeg_roundtrip_rgb(avcer_ctx* ctx, const uint8_t* src, int N, int H, int W, const int32_t* rects, const avcer_jpeg_desc* desc,
+                             int n, int bgr, int16_t* coeffs_or_null, int64_t n_blocks, int32_t* flags, uint8_t* canvas, int hmax,
+                             int wmax, avcer_stream_t stream);
 
 /* Huffman DECODING on the device: avcer_jpeg_entropy_batch's scan walk as self-synchronising subsequence decoding (Klein & Wiseman;
  * Weissenberger & Schmidt), so that the files' bytes, and not 128 bytes of coefficients per block, cross to the device, and no
