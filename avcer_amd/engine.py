@@ -780,6 +780,12 @@ class Engine:
                                                _ptr(t1n), _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), _ptr(w1n), _ptr(b1n),
                                                _ptr(w2_frags), self._stream()))
 
+    def bneck_tail(self, planes: int, m: int, t2, x, out, t1n, w3, b3, w1n, b1n):
+        """Kernel-level entry of the stage-3 tail (csrc/fused.hip bneck_tail2_kernel); all tensors already on the device: t2 sp32
+        [m,256], x / out sp32 [m,1024], t1n sp32 [m,256]; w3 [1024,256] and w1n [256,1024] from `split_weight_rows`."""
+        self._check(self.lib.avcer_bneck_tail(self.ctx, int(planes), int(m), _ptr(t2), _ptr(x), _ptr(out), _ptr(t1n), _ptr(w3),
+                                              _ptr(b3), _ptr(w1n), _ptr(b1n), self._stream()))
+
     def dwsep(self, x, dw_w, dw_s, dw_b, pw_w, pw_s, pw_b, stride: int, mode: int = MODE_FP32):
         """Kernel-level entry of one conv_dw block of MobileNet-0.25 (csrc/mnet.hip): x f32 NHWC [nb,h,w,cin], dw_w [9,cin],
         pw_w f32 [cout,cin] (padded and, in MODE_F16X3, split here) -> y f32 NHWC [nb,ceil(h/stride),ceil(w/stride),cout]."""

@@ -88,7 +88,8 @@ enum {
  *      avcer_attention_long, avcer_set_audio_max_tokens, avcer_audio_max_tokens (audio windows past 256 tokens: attention that
  *      streams key tiles through LDS) joined under 8 the same way: three more symbols, nothing that existed changed.
  *      avcer_jpeg_roundtrip_tiles, avcer_jpeg_roundtrip_rgb (face crops as the files of stage 0 hold them, without the files)
- *      joined under 8 the same way: two more symbols, the descriptor unchanged. */
+ *      joined under 8 the same way: two more symbols, the descriptor unchanged.
+ *      avcer_bneck_tail (the stage-3 tail kernel on caller tensors, for kernel-level tests) joined under 8 the same way: one more symbol. */
 #define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
@@ -713,6 +714,15 @@ int avcer_conv_gemm_dual(avcer_ctx* ctx, const avcer_conv_desc* d, int dtype, co
  *   conv2 output channels split across the block's waves so that every weight fragment goes straight into the registers of
  *   ONE wave); results are bit-identical to the form without it.
  *
+ * avcer_bneck_tail: stage 3 (planes 256), where conv2 stays a contraction launch of its own: conv3 + residual + ReLU and the next
+ *   block's conv1 in ONE launch (bneck_tail2_kernel),
+ *     OUT = relu(conv1x1(T2) + b3 + X);  T1N = relu(conv1x1(OUT) + b1n)
+ *   ref: architectures/video.py:49-58 (the second half of Bottleneck.forward) and :45-46 of the next block, BatchNorm folded.
+ *   t2 sp32 [M][256]; x / out sp32 [M][1024]; t1n sp32 [M][256] (required); w3 [1024][256], w1n [256][1024]: BN scale folded
+ *   into the rows, then split by avcer_split_weight_rows; b3 [1024] / b1n [256] f32.  planes must be 256, M >= 1 and below
+ *   2^20 - 1 positions (OUT is stored through a 4 GiB buffer descriptor).  The forward passes run it above 16384 positions per
+ *   call and the same two contractions as avcer_conv_gemm launches below (bit-identical results).
+ *
  * avcer_stem_pool: conv 7x7/2 (TF-"same" padding) + BN + ReLU + max-pool 3x3/2 in one launch,
  *   ref: architectures/video.py:63-90,98-103,116-117.  planes_hi_lo: two fp16 planes [n,230,230,4] (hi, then lo plane_bytes
  *   later) of the zero-bordered preprocessed image as avcer_static_forward builds it; w split [64][7*32] (tap rows of
@@ -720,6 +730,8 @@ int avcer_conv_gemm_dual(avcer_ctx* ctx, const avcer_conv_desc* d, int dtype, co
 int avcer_bneck_chain(avcer_ctx* ctx, int planes, int nb, int h, int w, const void* t1, const void* x, int ds_cin, int out_step,
                       void* out, void* t1n, const void* w2, const float* b2, const void* w3, const float* b3, const void* w1n,
                       const float* b1n, const void* w2_frags, avcer_stream_t stream);
+int avcer_bneck_tail(avcer_ctx* ctx, int planes, int64_t M, const void* t2, const void* x, void* out, void* t1n, const void* w3,
+                     const float* b3, const void* w1n, const float* b1n, avcer_stream_t stream);
 /* One conv_dw block of MobileNet-0.25 (retina_face_net.py:29-38) in ONE launch (csrc/mnet.hip dwsep_kernel), for kernel-level tests:
  *     T = leaky(dw3x3(X, stride, pad 1) * dw_s + dw_b);  Y = leaky(conv1x1(T) * pw_s + pw_b),  leaky = LeakyReLU(0.1)
  *   x f32 NHWC [nb,h,w,cin] -> y f32 NHWC [nb,ceil(h/stride),ceil(w/stride),cout]; T never reaches memory.
