@@ -130,6 +130,23 @@ inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 int ws_reserve(avcer_ctx* ctx, int slot, size_t bytes, void** out);
 
+// An allocation sized by its own layout (arena.h): `carve` is measured, alloc(bytes, &p) provides that many bytes, and `carve`
+// runs again on exactly those -- so no size is stated twice, and a carving that differs between its two runs is an error.
+// A carving that takes nothing allocates nothing.
+template <class Alloc, class Carve>
+int carve_measured(avcer_ctx* ctx, const char* what, const Alloc& alloc, const Carve& carve) {
+    const size_t bytes = Arena().run(carve);
+    void* p = nullptr;
+    if (bytes) TRY(alloc(bytes, &p));
+    return Arena(p, bytes).run(carve) == bytes ? AVCER_OK : set_err(ctx, AVCER_ENOMEM, "%s workspace arithmetic", what);
+}
+
+// The workspace of a forward pass: slot `slot` grown to what `carve` takes (ws_reserve's policy), then carved
+template <class Carve>
+int ws_carve(avcer_ctx* ctx, int slot, const char* what, const Carve& carve) {
+    return carve_measured(ctx, what, [&](size_t bytes, void** p) { return ws_reserve(ctx, slot, bytes, p); }, carve);
+}
+
 // PIL's NEAREST resize to 224 (data/utils.py:34): the source index of output index `o` along an axis of `len` source pixels.
 // The one statement of the rule: preprocess_kernel, crop_tiles_kernel (kernels.hip) and jpeg_tiles_kernel (jpeg.hip) call it.
 __device__ __forceinline__ int nearest_src(int o, int len) { return min((int)(((double)o + 0.5) * ((double)len / 224.0)), len - 1); }

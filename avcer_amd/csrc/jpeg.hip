@@ -606,14 +606,7 @@ __global__ void jpeg_canvas_kernel(const uint8_t* __restrict__ planes, const Des
 
 // The component planes in the context's JPEG workspace, sized by their own carving (one byte per coefficient)
 int jpeg_plane_ws(avcer_ctx* ctx, int64_t n_blocks, uint8_t** planes) {
-    uint8_t* p = nullptr;
-    const auto carve = [&](Arena& a) { p = a.get<uint8_t>(64 * (size_t)n_blocks); };
-    const size_t bytes = Arena().run(carve);
-    void* base = nullptr;
-    TRY(ws_reserve(ctx, WS_JPEG, bytes, &base));
-    if (Arena(base, bytes).run(carve) != bytes || !p) return set_err(ctx, AVCER_ENOMEM, "jpeg workspace arithmetic");
-    *planes = p;
-    return AVCER_OK;
+    return ws_carve(ctx, WS_JPEG, "jpeg", [&](Arena& a) { *planes = a.get<uint8_t>(64 * (size_t)n_blocks); });
 }
 
 // Kernel A into them
@@ -1247,34 +1240,49 @@ constexpr PackTables make_pack_tables() {
 static_assert(make_pack_tables().head[HEAD_SOF + 1] == 0xC0 && make_pack_tables().head[HEADER_BYTES - 2] == 63, "header layout");
 __device__ const PackTables kPack = make_pack_tables();
 
-// inclusive sums along the lanes of a wave
-template <class T>
-__device__ __forceinline__ T wave_scan(T v, int lane) {
+// The combine rules of the scans below, op(a, b) with `a` what stands in front of `b`: sums, maxima, and sums that start again at
+// every element with its flag set -- a (value, flag) pair under the usual associative operator, values modulo 2^32
+struct ScanSum {
+    template <class T> __device__ T operator()(T a, T b) const { return a + b; }
+};
+struct ScanMax {
+    template <class T> __device__ T operator()(T a, T b) const { return max(a, b); }
+};
+struct SegSum { uint32_t v, f; };
+struct ScanSeg {
+    __device__ SegSum operator()(SegSum a, SegSum b) const { return SegSum{b.f ? b.v : a.v + b.v, a.f | b.f}; }
+};
+template <class T> __device__ __forceinline__ T shfl_up(T x, int d) { return __shfl_up(x, d, 64); }
+__device__ __forceinline__ SegSum shfl_up(SegSum x, int d) { return SegSum{__shfl_up(x.v, d, 64), __shfl_up(x.f, d, 64)}; }
+
+// inclusive scan under `op` (sums unless stated) along the lanes of a wave
+template <class T, class Op = ScanSum>
+__device__ __forceinline__ T wave_scan(T v, int lane, Op op = Op()) {
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
-        const T o = __shfl_up(v, d, 64);
-        if (lane >= d) v += o;
+        const T o = shfl_up(v, d);
+        if (lane >= d) v = op(o, v);
     }
     return v;
 }
 
-// inclusive sums along the PACK_THREADS threads of a workgroup (every thread calls it), *total = the last of them; `tot`:
-// PACK_WAVES values of LDS, free again on return
-template <class T>
-__device__ __forceinline__ T block_scan(T v, T* tot, T* total) {
+// the same along the PACK_THREADS threads of a workgroup (every thread calls it), *total = the last of them; `tot`: PACK_WAVES
+// values of LDS, free again on return
+template <class T, class Op = ScanSum>
+__device__ __forceinline__ T block_scan(T v, T* tot, T* total, Op op = Op()) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    v = wave_scan(v, lane);
+    v = wave_scan(v, lane, op);
     if (lane == 63) tot[wave] = v;
     __syncthreads();
-    T add = 0, all = 0;
+    T all = tot[0], mine = v;
 #pragma unroll
-    for (int k = 0; k < PACK_WAVES; ++k) {
-        if (k < wave) add += tot[k];
-        all += tot[k];
+    for (int k = 1; k < PACK_WAVES; ++k) {
+        if (k == wave) mine = op(all, v);
+        all = op(all, tot[k]);
     }
     __syncthreads();
     *total = all;
-    return v + add;
+    return mine;
 }
 
 // the file that holds work item w: the last one that starts at or before it (wb ascends; a file without items starts where the
@@ -1757,18 +1765,14 @@ extern "C" int avcer_jpeg_pack(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_
     int64_t *wb = nullptr, *fbits = nullptr, *flen = nullptr;
     int32_t* range = nullptr;
     uint32_t *nbits = nullptr, *bits = nullptr;
-    const auto carve = [&](Arena& a) {
+    TRY(ws_carve(ctx, WS_JPEG, "jpeg_pack", [&](Arena& a) {
         wb = a.get<int64_t>(sizeof(int64_t) * ((size_t)n + 1));      // first work item of every file, and the end of the last
         fbits = a.get<int64_t>(sizeof(int64_t) * (size_t)n);         // bits of every file's scan
         flen = a.get<int64_t>(sizeof(int64_t) * (size_t)n);          // bytes of every file
         range = a.get<int32_t>(sizeof(int32_t) * (size_t)n);         // a coefficient without a code was seen
         nbits = a.get<uint32_t>(sizeof(uint32_t) * (size_t)n_blocks);  // per item: its bit count, then its bit offset in the file
         bits = a.get<uint32_t>(sizeof(uint32_t) * BLOCK_WORDS * (size_t)n_blocks);  // the unstuffed scans, BLOCK_WORDS per item
-    };
-    const size_t bytes = Arena().run(carve);
-    void* base = nullptr;
-    TRY(ws_reserve(ctx, WS_JPEG, bytes, &base));
-    if (Arena(base, bytes).run(carve) != bytes || !bits) return set_err(ctx, AVCER_ENOMEM, "jpeg_pack workspace arithmetic");
+    }));
     const unsigned per_item = (unsigned)((n_blocks + PACK_WAVES - 1) / PACK_WAVES);
     pack_check_kernel<<<1, PACK_THREADS, 0, st>>>(desc, n, n_blocks, wb, status, range);
     HIP_TRY(ctx, hipGetLastError());
@@ -1829,52 +1833,6 @@ __global__ void unpack_tabs_kernel(const avcer_jpeg_tab* __restrict__ tabs, int 
     if (i < n_tabs) js::derive_tab(tabs[i], out[i]);
 }
 
-// inclusive maxima along the threads of a workgroup (every thread calls it); `tot`: PACK_WAVES values of LDS, free again on return
-__device__ __forceinline__ int32_t block_scan_max(int32_t v, int32_t* tot) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int32_t o = __shfl_up(v, d, 64);
-        if (lane >= d) v = max(v, o);
-    }
-    if (lane == 63) tot[wave] = v;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < PACK_WAVES; ++k)
-        if (k < wave) v = max(v, tot[k]);
-    __syncthreads();
-    return v;
-}
-
-// inclusive sums modulo 2^32 along the threads of a workgroup that start again at every thread with `f` set; *carry: the running
-// sum in front of thread 0, and behind the last thread on return (the same value in every thread)
-__device__ __forceinline__ uint32_t block_scan_segmented(uint32_t v, bool f, uint32_t* totv, uint32_t* totf, uint32_t* carry) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t ff = f ? 1u : 0u;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t ov = __shfl_up(v, d, 64), of = __shfl_up(ff, d, 64);
-        if (lane >= d) {
-            if (!ff) v += ov;
-            ff |= of;
-        }
-    }
-    if (lane == 63) {
-        totv[wave] = v;
-        totf[wave] = ff;
-    }
-    __syncthreads();
-    uint32_t acc = *carry, mine = 0;
-#pragma unroll
-    for (int k = 0; k < PACK_WAVES; ++k) {
-        if (k == wave) mine = acc;
-        acc = totf[k] ? totv[k] : acc + totv[k];
-    }
-    __syncthreads();
-    *carry = acc;
-    return ff ? v : v + mine;
-}
-
 __global__ void __launch_bounds__(js::THREADS) unpack_kernel(const uint8_t* __restrict__ bytes, int64_t n_bytes,
                                                              const avcer_jpeg_scan* __restrict__ scan, const js::DTab* __restrict__ dtabs,
                                                              int n_tabs, Desc* desc, int16_t* __restrict__ coeffs, int64_t n_blocks,
@@ -1884,10 +1842,10 @@ __global__ void __launch_bounds__(js::THREADS) unpack_kernel(const uint8_t* __re
     __shared__ js::DTab tabs[6];
     __shared__ js::State exits[js::THREADS];
     __shared__ int32_t pex[js::THREADS];
-    __shared__ uint32_t tot[PACK_WAVES], totf[PACK_WAVES];
+    __shared__ uint32_t tot[PACK_WAVES];
+    __shared__ SegSum segtot[PACK_WAVES];
     __shared__ unsigned long long errkey;
-    __shared__ js::State carry_state;
-    __shared__ long long carry_ord;
+    __shared__ js::Carry carry;
     const int i = blockIdx.x, t = threadIdx.x;
     Desc& d = desc[i];
     if (d.status != AVCER_JPEG_OK) {  // the whole workgroup
@@ -1915,23 +1873,21 @@ __global__ void __launch_bounds__(js::THREADS) unpack_kernel(const uint8_t* __re
         }
     const int64_t sb = seg_scratch(d, i);
     const int32_t nseg = f.nseg;
-    for (int j = t; j < nseg; j += js::THREADS) stop_code[sb + j] = -1;
-    int16_t* const fc = coeffs + 64 * d.coef_block;
+    js::View v = {&f, tabs, &d, coeffs + 64 * d.coef_block, reinterpret_cast<uint32_t*>(comp + sc.offset), stop_pos + sb, stop_code + sb,
+                  seg_sub + sb, sub, 0, 0};
+    for (int j = t; j < nseg; j += js::THREADS) v.stop_code[j] = -1;
     {
-        uint4* z = reinterpret_cast<uint4*>(fc);
+        uint4* z = reinterpret_cast<uint4*>(v.fc);
         for (int64_t x = t; x < 8 * d.n_blocks; x += js::THREADS) z[x] = make_uint4(0u, 0u, 0u, 0u);
     }
     if (t == 0) {
         errkey = js::NO_DEFECT;
-        carry_state.pos = 0;
-        carry_state.sk = js::NOSYNC;
-        carry_ord = 0;
+        carry = js::Carry{js::State{0, js::NOSYNC}, 0};
     }
     __syncthreads();
 
     // ---- marker: 16 bytes a thread and turn
     const uint8_t* fb = bytes + sc.offset;
-    uint8_t* cw = comp + sc.offset;
     const int32_t nb = (int32_t)sc.nbytes;
     int32_t total_data = 0, all_stops = 0;
     for (int32_t c0 = 0; c0 < nb; c0 += 16 * js::THREADS) {
@@ -1939,8 +1895,8 @@ __global__ void __launch_bounds__(js::THREADS) unpack_kernel(const uint8_t* __re
         const int cnt = max(0, min(16, nb - p0));
         uint8_t b[16];
         if (cnt == 16) {
-            const uint4 v = *reinterpret_cast<const uint4*>(fb + p0);
-            const uint32_t vw[4] = {v.x, v.y, v.z, v.w};
+            const uint4 q = *reinterpret_cast<const uint4*>(fb + p0);
+            const uint32_t vw[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
             for (int k = 0; k < 16; ++k) b[k] = (uint8_t)(vw[k >> 2] >> (8 * (k & 3)));
         } else {
@@ -1967,139 +1923,78 @@ __global__ void __launch_bounds__(js::THREADS) unpack_kernel(const uint8_t* __re
         int32_t dpos = total_data + (int32_t)((incl & 0xffff) - nd), spos = all_stops + (int32_t)((incl >> 16) - ns);
 #pragma unroll
         for (int k = 0; k < 16; ++k)
-            if (k < cnt) {
-                const int cl = (int)(cls >> (3 * k)) & 7;
-                if (cl == js::B_DATA) {
-                    cw[dpos ^ 3] = b[k];
-                    ++dpos;
-                } else if (cl == js::B_STOP) {
-                    if (spos < nseg) stop_pos[sb + spos] = dpos;
-                    ++spos;
-                } else if (cl == js::B_CODE) {
-                    if (spos >= 1 && spos <= nseg) stop_code[sb + spos - 1] = b[k];
-                }
-            }
+            if (k < cnt) js::place_byte(v, (int)(cls >> (3 * k)) & 7, b[k], dpos, spos);
         total_data += (int32_t)(total & 0xffff);
         all_stops += (int32_t)(total >> 16);
     }
-    const int32_t nstops = min(all_stops, nseg);
+    v.total_data = total_data;
+    v.nstops = min(all_stops, nseg);
     __syncthreads();
 
-    // ---- segments: the data bytes of segment j, its first subsequence among the file's
-    const auto seg_lo = [&](int j) { return j == 0 ? 0 : (j - 1 < nstops ? stop_pos[sb + j - 1] : total_data); };
-    const auto seg_hi = [&](int j) { return j < nstops ? stop_pos[sb + j] : total_data; };
+    // ---- segments: the first subsequence of segment j among the file's
     int32_t total_sub = 0;
     for (int32_t j0 = 0; j0 < nseg; j0 += js::THREADS) {
         const int32_t j = j0 + t;
-        uint32_t ns = 0;
-        if (j < nseg) ns = (uint32_t)max(1, (8 * (seg_hi(j) - seg_lo(j)) + sub - 1) / sub);
+        const uint32_t ns = j < nseg ? (uint32_t)js::seg_subs(v, j) : 0u;
         uint32_t total;
         const uint32_t incl = block_scan(ns, tot, &total);
-        if (j < nseg) seg_sub[sb + j] = total_sub + (int32_t)(incl - ns);
+        if (j < nseg) v.seg_sub[j] = total_sub + (int32_t)(incl - ns);
         total_sub += (int32_t)total;
     }
-    if (t == 0) seg_sub[sb + nseg] = total_sub;
+    if (t == 0) v.seg_sub[nseg] = total_sub;
     __syncthreads();
 
     // ---- units
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(cw);
     for (int32_t b0 = 0; b0 < total_sub; b0 += js::THREADS) {
-        const int32_t s = b0 + t;
-        const bool live = s < total_sub;
-        int32_t j = 0, start = 0, stop = 0, end = 0, sf = 0;
-        bool first = false, last = false;
-        if (live) {
-            int32_t lo = 0, hi = nseg - 1;
-            while (lo < hi) {
-                const int32_t mid = (lo + hi + 1) >> 1;
-                if (seg_sub[sb + mid] <= s) lo = mid; else hi = mid - 1;
-            }
-            j = lo;
-            const int32_t m = s - seg_sub[sb + j];
-            sf = seg_sub[sb + j] - b0;
-            start = 8 * seg_lo(j) + m * sub;
-            end = 8 * seg_hi(j);
-            first = m == 0;
-            last = s + 1 == seg_sub[sb + j + 1];
-            stop = last ? js::NO_STOP : start + sub;
-        }
-        const bool is_true = live && (first || t == 0);
-        const js::State true_in = first ? js::State{start, 0} : carry_state;
-        const js::State fresh = {start, 0}, park = {last ? end : stop, js::NOSYNC};
-        js::State mine = park, last_in = {-1, -2};
-        int32_t cnt = 0;
-        exits[t] = park;
+        const js::Sub x = js::locate(v, b0 + t, b0, t, total_sub, carry.state);
+        js::Round rd = js::before_rounds(x);
+        exits[t] = x.park();
         __syncthreads();
         for (int round = 0; round < js::THREADS + 2; ++round) {
-            js::State in = is_true ? true_in : (t > 0 ? exits[t - 1] : fresh);
-            if (in.sk == js::NOSYNC) in = fresh;
-            int changed = 0;
-            if (live && !js::same(in, last_in)) {
-                js::Result o;
-                js::run<false>(w, end, stop, in, tabs, f, 0, 0, 0, nullptr, &d, o);
-                const js::State e = o.err ? park : o.exit;
-                changed = !js::same(e, mine);
-                mine = e;
-                cnt = o.blocks;
-                last_in = in;
-            }
+            const int changed = js::round_step(v, x, js::entry(x, t, exits), rd);
             __syncthreads();  // every thread has read its neighbour's exit
-            if (changed) exits[t] = mine;
+            if (changed) exits[t] = rd.mine;
             if (!__syncthreads_or(changed)) break;
         }
         // ---- write
-        const js::State in = is_true ? true_in : (t > 0 ? exits[t - 1] : fresh);
-        // a thread behind a not-synchronised entry in its segment is behind an error of the true chain
-        const int32_t lastflag = block_scan_max(live && in.sk == js::NOSYNC ? t : -1, reinterpret_cast<int32_t*>(tot));
-        const bool valid = live && lastflag < max(sf, 0);
+        const js::State in = js::entry(x, t, exits);
+        int32_t top;
+        const int32_t lastflag = block_scan(js::unsynced(x, t, in), reinterpret_cast<int32_t*>(tot), &top, ScanMax());
+        const bool valid = js::valid(x, lastflag);
         uint32_t total;
-        const uint32_t incl = block_scan((uint32_t)(live ? cnt : 0), tot, &total);
-        pex[t] = (int32_t)(incl - (uint32_t)(live ? cnt : 0));
+        pex[t] = (int32_t)(block_scan((uint32_t)rd.cnt, tot, &total) - (uint32_t)rd.cnt);
         __syncthreads();
-        long long ord = 0;
-        if (live) ord = sf >= 0 ? (long long)(pex[t] - pex[sf]) : carry_ord + pex[t];
+        const long long ord = js::entry_ordinal(x, t, pex, carry.ord);
         if (valid) {
-            const int64_t mcu0 = (int64_t)j * f.rst;
-            const int64_t limit = (min(mcu0 + f.rst, (int64_t)f.nmcu) - mcu0) * f.bpm;
-            js::Result o;
-            js::run<true>(w, end, stop, in, tabs, f, ord, limit, mcu0, fc, &d, o);
-            if (o.err) atomicMin(&errkey, js::defect(mcu0 * f.bpm + o.err_ord, o.err_stage, o.err));
-            if (o.done_pos >= 0) {
-                const int code = j < nstops ? stop_code[sb + j] : -1;
-                if (end - o.done_pos >= 8 || code != (j == nseg - 1 ? 0xD9 : 0xD0 + (j & 7)))
-                    atomicMin(&errkey, js::defect(mcu0 * f.bpm + limit - 1, 3, j == nseg - 1 ? R_NO_EOI : R_RESTART));
-            }
+            const unsigned long long key = js::write_step(v, x, in, ord);
+            if (key != js::NO_DEFECT) atomicMin(&errkey, key);
         }
-        __syncthreads();  // carry_* and exits are read
-        if (t == js::THREADS - 1 && live) {
-            carry_state = valid && mine.sk != js::NOSYNC ? mine : park;
-            carry_ord = ord + cnt;
-        }
+        __syncthreads();  // carry and exits are read
+        if (t == js::THREADS - 1 && x.live) carry = js::hand_over(x, valid, rd, ord);
         __syncthreads();
     }
 
     // ---- predict
     for (int c = 0; c < f.ncomp; ++c) {
-        const int per = c == 0 && f.ncomp == 3 ? f.hs * f.vs : 1, slot0 = c == 0 ? 0 : f.hs * f.vs + c - 1;
-        const int64_t count = (int64_t)f.nmcu * per;
-        uint32_t carry = 0;
+        const int64_t count = js::predict_count(f, c);
+        SegSum sum = {0u, 0u};  // the running prediction in front of thread 0
         for (int64_t q0 = 0; q0 < count; q0 += js::THREADS) {
-            const int64_t q = q0 + t, mcu = q / per;
-            const int slot = slot0 + (int)(q % per);
+            const int64_t q = q0 + t;
+            js::Item it = {};
             int16_t* blk = nullptr;
-            uint32_t v = 0;
-            bool fl = false;
+            SegSum mine = {0u, 0u}, all;
             if (q < count) {
-                blk = fc + 64 * js::storage_block(f, mcu, slot);
-                v = (uint32_t)(int32_t)blk[0];
-                fl = q % per == 0 && mcu % f.rst == 0;
+                it = js::predict_item(f, c, q);
+                blk = v.fc + 64 * js::storage_block(f, it.mcu, it.slot);
+                mine = SegSum{(uint32_t)(int32_t)blk[0], it.restart};
             }
-            const int32_t pred = (int32_t)block_scan_segmented(v, fl, tot, totf, &carry);
+            mine = ScanSeg()(sum, block_scan(mine, segtot, &all, ScanSeg()));
+            sum = ScanSeg()(sum, all);
             if (q < count) {
                 // exact up to and including the first block out of range (sums are modulo 2^32); later ones lose to it
-                const int64_t pq = (int64_t)pred * (int64_t)d.qt[c][0];
-                if (pred < -32768 || pred > 32767 || pq < -32768 || pq > 32767) atomicMin(&errkey, js::defect(mcu * f.bpm + slot, 1, R_RANGE));
-                blk[0] = (int16_t)pred;
+                const unsigned long long key = js::predict_check(v, c, it, (int32_t)mine.v);
+                if (key != js::NO_DEFECT) atomicMin(&errkey, key);
+                blk[0] = (int16_t)(int32_t)mine.v;
             }
         }
     }
@@ -2114,7 +2009,9 @@ __global__ void __launch_bounds__(js::THREADS) unpack_kernel(const uint8_t* __re
     }
 }
 
-// One file of avcer_jpeg_unpack_host: the phases of unpack_kernel as loops over its threads.  Returns the reason.
+// One file of avcer_jpeg_unpack_host: the driver of unpack_kernel once more, with the threads of a unit as a loop.  Every decision
+// is the kernel's own (the per-thread functions of jpeg_sync_dev.h); here are only the running sums that stand in for its scans,
+// the loop ends that stand in for its barriers, and std::min for its atomicMin.  Returns the reason.
 int unpack_file_host(const uint8_t* bytes, int64_t n_bytes, const avcer_jpeg_scan& sc, const js::DTab* dtabs, int n_tabs, const Desc& d,
                      int16_t* coeffs, int64_t n_blocks, int sub) {
     js::File f;
@@ -2128,143 +2025,73 @@ int unpack_file_host(const uint8_t* bytes, int64_t n_bytes, const avcer_jpeg_sca
     }
     const int32_t nseg = f.nseg, nb = (int32_t)sc.nbytes;
     std::vector<int32_t> stop_pos((size_t)nseg, 0), stop_code((size_t)nseg, -1), seg_sub((size_t)nseg + 1, 0);
-    int16_t* const fc = coeffs + 64 * d.coef_block;
-    memset(fc, 0, sizeof(int16_t) * 64 * (size_t)d.n_blocks);
+    std::vector<uint32_t> words(((size_t)nb + 3) / 4 + 1, 0u);
+    js::View v = {&f, tabs, &d, coeffs + 64 * d.coef_block, words.data(), stop_pos.data(), stop_code.data(), seg_sub.data(), sub, 0, 0};
+    memset(v.fc, 0, sizeof(int16_t) * 64 * (size_t)d.n_blocks);
     unsigned long long errkey = js::NO_DEFECT;
     // ---- marker
     const uint8_t* fb = bytes + sc.offset;
-    std::vector<uint32_t> words(((size_t)nb + 3) / 4 + 1, 0u);
-    uint8_t* cw = reinterpret_cast<uint8_t*>(words.data());
     int32_t total_data = 0, all_stops = 0;
     for (int32_t p = 0; p < nb; ++p) {
         const int cl = js::byte_class(p >= 2 ? fb[p - 2] : 0, p >= 1 ? fb[p - 1] : 0, fb[p], p + 1 < nb, p + 1 < nb ? fb[p + 1] : 0);
-        if (cl == js::B_DATA) {
-            cw[total_data ^ 3] = fb[p];
-            ++total_data;
-        } else if (cl == js::B_STOP) {
-            if (all_stops < nseg) stop_pos[(size_t)all_stops] = total_data;
-            ++all_stops;
-        } else if (cl == js::B_CODE) {
-            if (all_stops >= 1 && all_stops <= nseg) stop_code[(size_t)all_stops - 1] = fb[p];
-        }
+        js::place_byte(v, cl, fb[p], total_data, all_stops);
     }
-    const int32_t nstops = std::min(all_stops, nseg);
+    v.total_data = total_data;
+    v.nstops = std::min(all_stops, nseg);
     // ---- segments
-    const auto seg_lo = [&](int j) { return j == 0 ? 0 : (j - 1 < nstops ? stop_pos[(size_t)j - 1] : total_data); };
-    const auto seg_hi = [&](int j) { return j < nstops ? stop_pos[(size_t)j] : total_data; };
     int32_t total_sub = 0;
     for (int32_t j = 0; j < nseg; ++j) {
         seg_sub[(size_t)j] = total_sub;
-        total_sub += std::max(1, (8 * (seg_hi(j) - seg_lo(j)) + sub - 1) / sub);
+        total_sub += js::seg_subs(v, j);
     }
     seg_sub[(size_t)nseg] = total_sub;
     // ---- units
-    const uint32_t* w = words.data();
     constexpr int T = js::THREADS;
-    struct Thread {
-        bool live, first, last, is_true, valid;
-        int32_t j, start, stop, end, sf, cnt;
-        js::State true_in, fresh, park, mine, last_in, in;
-        long long ord;
-    };
-    std::vector<Thread> th((size_t)T);
-    std::vector<js::State> exits((size_t)T), next((size_t)T);
-    js::State carry_state = {0, js::NOSYNC};
-    long long carry_ord = 0;
+    std::vector<js::Sub> th((size_t)T);
+    std::vector<js::Round> rs((size_t)T);
+    std::vector<js::State> exits((size_t)T);
+    std::vector<int32_t> pex((size_t)T);
+    js::Carry carry = {js::State{0, js::NOSYNC}, 0};
     for (int32_t b0 = 0; b0 < total_sub; b0 += T) {
         for (int t = 0; t < T; ++t) {
-            Thread& x = th[(size_t)t];
-            x = Thread();
-            const int32_t s = b0 + t;
-            x.live = s < total_sub;
-            if (x.live) {
-                x.j = (int32_t)(std::upper_bound(seg_sub.begin(), seg_sub.begin() + nseg, s) - seg_sub.begin()) - 1;
-                const int32_t m = s - seg_sub[(size_t)x.j];
-                x.sf = seg_sub[(size_t)x.j] - b0;
-                x.start = 8 * seg_lo(x.j) + m * sub;
-                x.end = 8 * seg_hi(x.j);
-                x.first = m == 0;
-                x.last = s + 1 == seg_sub[(size_t)x.j + 1];
-                x.stop = x.last ? js::NO_STOP : x.start + sub;
-            }
-            x.is_true = x.live && (x.first || t == 0);
-            x.true_in = x.first ? js::State{x.start, 0} : carry_state;
-            x.fresh = js::State{x.start, 0};
-            x.park = js::State{x.last ? x.end : x.stop, js::NOSYNC};
-            x.mine = x.park;
-            x.last_in = js::State{-1, -2};
-            exits[(size_t)t] = x.park;
+            th[(size_t)t] = js::locate(v, b0 + t, b0, t, total_sub, carry.state);
+            rs[(size_t)t] = js::before_rounds(th[(size_t)t]);
+            exits[(size_t)t] = th[(size_t)t].park();
         }
         for (int round = 0; round < T + 2; ++round) {
             bool any = false;
-            next = exits;
-            for (int t = 0; t < T; ++t) {
-                Thread& x = th[(size_t)t];
-                js::State in = x.is_true ? x.true_in : (t > 0 ? exits[(size_t)t - 1] : x.fresh);
-                if (in.sk == js::NOSYNC) in = x.fresh;
-                if (x.live && !js::same(in, x.last_in)) {
-                    js::Result o;
-                    js::run<false>(w, x.end, x.stop, in, tabs, f, 0, 0, 0, nullptr, &d, o);
-                    const js::State e = o.err ? x.park : o.exit;
-                    if (!js::same(e, x.mine)) {
-                        any = true;
-                        next[(size_t)t] = e;
-                    }
-                    x.mine = e;
-                    x.cnt = o.blocks;
-                    x.last_in = in;
-                }
-            }
-            exits = next;
+            for (int t = 0; t < T; ++t) any |= js::round_step(v, th[(size_t)t], js::entry(th[(size_t)t], t, exits.data()), rs[(size_t)t]);
+            for (int t = 0; t < T; ++t) exits[(size_t)t] = rs[(size_t)t].mine;  // behind the barrier: every entry has been read
             if (!any) break;
         }
         // ---- write
-        int32_t lastflag = -1, pre = 0;
-        std::vector<int32_t> pex((size_t)T, 0);
+        int32_t pre = 0;
         for (int t = 0; t < T; ++t) {
-            Thread& x = th[(size_t)t];
-            x.in = x.is_true ? x.true_in : (t > 0 ? exits[(size_t)t - 1] : x.fresh);
-            if (x.live && x.in.sk == js::NOSYNC) lastflag = t;
-            x.valid = x.live && lastflag < std::max(x.sf, 0);
             pex[(size_t)t] = pre;
-            pre += x.live ? x.cnt : 0;
+            pre += rs[(size_t)t].cnt;
         }
+        int32_t lastflag = -1;
         for (int t = 0; t < T; ++t) {
-            Thread& x = th[(size_t)t];
-            if (x.live) x.ord = x.sf >= 0 ? (long long)(pex[(size_t)t] - pex[(size_t)x.sf]) : carry_ord + pex[(size_t)t];
-            if (!x.valid) continue;
-            const int64_t mcu0 = (int64_t)x.j * f.rst;
-            const int64_t limit = (std::min(mcu0 + f.rst, (int64_t)f.nmcu) - mcu0) * f.bpm;
-            js::Result o;
-            js::run<true>(w, x.end, x.stop, x.in, tabs, f, x.ord, limit, mcu0, fc, &d, o);
-            if (o.err) errkey = std::min(errkey, js::defect(mcu0 * f.bpm + o.err_ord, o.err_stage, o.err));
-            if (o.done_pos >= 0) {
-                const int code = x.j < nstops ? stop_code[(size_t)x.j] : -1;
-                if (x.end - o.done_pos >= 8 || code != (x.j == nseg - 1 ? 0xD9 : 0xD0 + (x.j & 7)))
-                    errkey = std::min(errkey, js::defect(mcu0 * f.bpm + limit - 1, 3, x.j == nseg - 1 ? R_NO_EOI : R_RESTART));
-            }
-        }
-        const Thread& z = th[(size_t)T - 1];
-        if (z.live) {
-            carry_state = z.valid && z.mine.sk != js::NOSYNC ? z.mine : z.park;
-            carry_ord = z.ord + z.cnt;
+            const js::Sub& x = th[(size_t)t];
+            const js::State in = js::entry(x, t, exits.data());
+            lastflag = std::max(lastflag, js::unsynced(x, t, in));
+            const bool valid = js::valid(x, lastflag);
+            const long long ord = js::entry_ordinal(x, t, pex.data(), carry.ord);
+            if (valid) errkey = std::min(errkey, js::write_step(v, x, in, ord));
+            if (t == T - 1 && x.live) carry = js::hand_over(x, valid, rs[(size_t)t], ord);
         }
     }
     // ---- predict
     for (int c = 0; c < f.ncomp; ++c) {
-        const int per = c == 0 && f.ncomp == 3 ? f.hs * f.vs : 1, slot0 = c == 0 ? 0 : f.hs * f.vs + c - 1;
-        const int64_t count = (int64_t)f.nmcu * per;
+        const int64_t count = js::predict_count(f, c);
         uint32_t sum = 0;
         for (int64_t q = 0; q < count; ++q) {
-            const int64_t mcu = q / per;
-            const int slot = slot0 + (int)(q % per);
-            int16_t* blk = fc + 64 * js::storage_block(f, mcu, slot);
-            const uint32_t v = (uint32_t)(int32_t)blk[0];
-            sum = q % per == 0 && mcu % f.rst == 0 ? v : sum + v;
-            const int32_t pred = (int32_t)sum;
-            const int64_t pq = (int64_t)pred * (int64_t)d.qt[c][0];
-            if (pred < -32768 || pred > 32767 || pq < -32768 || pq > 32767) errkey = std::min(errkey, js::defect(mcu * f.bpm + slot, 1, R_RANGE));
-            blk[0] = (int16_t)pred;
+            const js::Item it = js::predict_item(f, c, q);
+            int16_t* blk = v.fc + 64 * js::storage_block(f, it.mcu, it.slot);
+            const uint32_t dv = (uint32_t)(int32_t)blk[0];
+            sum = it.restart ? dv : sum + dv;
+            errkey = std::min(errkey, js::predict_check(v, c, it, (int32_t)sum));
+            blk[0] = (int16_t)(int32_t)sum;
         }
     }
     return errkey == js::NO_DEFECT ? R_OK : (int)(errkey & 31);
@@ -2385,17 +2212,13 @@ extern "C" int avcer_jpeg_unpack(avcer_ctx* ctx, const uint8_t* bytes, int64_t n
     uint8_t* comp = nullptr;
     int32_t *stop_pos = nullptr, *stop_code = nullptr, *seg_sub = nullptr;
     const size_t per_block = (size_t)n_blocks + 2 * (size_t)n;
-    const auto carve = [&](Arena& a) {
+    TRY(ws_carve(ctx, WS_JPEG, "jpeg_unpack", [&](Arena& a) {
         dtabs = a.get<js::DTab>(sizeof(js::DTab) * (size_t)n_tabs);       // the derived tables
         comp = a.get<uint8_t>((size_t)n_bytes + 16);                      // the unstuffed bytes, file by file where `bytes` has them
         stop_pos = a.get<int32_t>(sizeof(int32_t) * per_block);           // per segment: the data bytes in front of its stop,
         stop_code = a.get<int32_t>(sizeof(int32_t) * per_block);          // ... the marker code there (-1: none),
         seg_sub = a.get<int32_t>(sizeof(int32_t) * per_block);            // ... its first subsequence among the file's
-    };
-    const size_t ws = Arena().run(carve);
-    void* base = nullptr;
-    TRY(ws_reserve(ctx, WS_JPEG, ws, &base));
-    if (Arena(base, ws).run(carve) != ws || !seg_sub || ((uintptr_t)comp & 15)) return set_err(ctx, AVCER_ENOMEM, "jpeg_unpack workspace arithmetic");
+    }));
     unpack_tabs_kernel<<<(unsigned)((n_tabs + 63) / 64), 64, 0, st>>>(tabs, n_tabs, dtabs);
     HIP_TRY(ctx, hipGetLastError());
     unpack_kernel<<<(unsigned)n, js::THREADS, 0, st>>>(bytes, n_bytes, scan, dtabs, n_tabs, desc, coeffs, n_blocks, status,

@@ -1,8 +1,11 @@
 // Self-synchronising Huffman decoding of a JPEG scan (avcer_jpeg_unpack, csrc/jpeg.hip): the pieces that the device kernel and its
-// host statement avcer_jpeg_unpack_host share -- the byte classes of the marker pass, the derived Huffman table, the bit reader over
-// the unstuffed bytes, ONE subsequence's decode from an entry state, the state comparison and the block-ordinal -> storage mapping.
-// Everything is __host__ __device__ and integer; the phases around them (prefix sums, rounds, hand-over) are written twice, as a
-// workgroup in jpeg.hip's kernel and as plain loops over "threads" in the host statement.
+// host statement avcer_jpeg_unpack_host share, which is every decision of the algorithm -- the byte classes of the marker pass and
+// where a classified byte goes, the derived Huffman table, the bit reader over the unstuffed bytes, the cut of a segment into
+// subsequences, where a subsequence lies and what it enters with, ONE subsequence's decode from an entry state, a round's step, the
+// write step with its marker check, the hand-over between units, the DC prediction's items and range check, the block-ordinal ->
+// storage mapping.  Everything is __host__ __device__, integer and free of barriers.  Written per side is only how the threads of a
+// unit run and combine: jpeg.hip's kernel loads 16 bytes a thread, scans across the workgroup, waits at barriers and takes the
+// smallest defect with atomicMin; the host statement loops over the "threads" with running sums and std::min.
 //
 // Semantics are those of Bits / decode_block / decode_scan in jpeg.hip, restated on the UNSTUFFED bytes of one segment (a restart
 // interval, or the whole scan): bits behind the segment's end read as zero and cannot be consumed (`bad`).
@@ -311,5 +314,161 @@ JS_HD void run(const uint32_t* w, int32_t end, int32_t stop, State in, const DTa
 // (3); the reason rides in the low bits, the smallest key is the file's reason.
 constexpr unsigned long long NO_DEFECT = ~0ULL;
 JS_HD unsigned long long defect(int64_t g, int stage, int reason) { return ((unsigned long long)(4 * g + stage) << 5) | (unsigned)reason; }
+
+// ------------------------------------------------------------------------------------------------ the phases, thread by thread
+// One file as its phases see it.  The per-segment arrays are the file's own: f.nseg entries, seg_sub one more.
+struct View {
+    const File* f;
+    const DTab* tabs;             // [2 c] the DC and [2 c + 1] the AC table of component c
+    const avcer_jpeg_desc* d;
+    int16_t* fc;                  // the file's coefficient blocks, zeroed
+    uint32_t* w;                  // its unstuffed bytes (peek32)
+    int32_t *stop_pos, *stop_code;  // per segment: the data bytes in front of its stop, the marker code there (-1: none)
+    int32_t* seg_sub;             // ... its first subsequence among the file's; [f.nseg]: all of them
+    int32_t sub;                  // bits of a subsequence
+    int32_t nstops, total_data;   // behind the marker pass: the stops that end a segment, the data bytes
+};
+
+// marker pass: byte `b` of class `cl`, behind dpos data bytes and spos stops
+JS_HD void place_byte(const View& v, int cl, uint8_t b, int32_t& dpos, int32_t& spos) {
+    if (cl == B_DATA) {
+        reinterpret_cast<uint8_t*>(v.w)[dpos ^ 3] = b;
+        ++dpos;
+    } else if (cl == B_STOP) {
+        if (spos < v.f->nseg) v.stop_pos[spos] = dpos;
+        ++spos;
+    } else if (cl == B_CODE) {
+        if (spos >= 1 && spos <= v.f->nseg) v.stop_code[spos - 1] = b;
+    }
+}
+
+// segments: the data bytes [seg_lo, seg_hi) of segment j, and the subsequences it is cut into
+JS_HD int32_t seg_lo(const View& v, int j) { return j == 0 ? 0 : (j - 1 < v.nstops ? v.stop_pos[j - 1] : v.total_data); }
+JS_HD int32_t seg_hi(const View& v, int j) { return j < v.nstops ? v.stop_pos[j] : v.total_data; }
+JS_HD int32_t seg_subs(const View& v, int j) {
+    const int32_t n = (8 * (seg_hi(v, j) - seg_lo(v, j)) + v.sub - 1) / v.sub;
+    return n > 1 ? n : 1;
+}
+
+// Subsequence s of the file as thread t of the unit that begins at subsequence b0 holds it
+struct Sub {
+    bool live;               // there is such a subsequence
+    bool first, last;        // of its segment
+    bool is_true;            // its entry is known: the segment's start, or the hand-over of the unit before
+    int32_t j;               // its segment
+    int32_t start, stop;     // its bits; the last of a segment has NO_STOP
+    int32_t end;             // the segment's bits end here
+    int32_t sf;              // the thread that holds the segment's first subsequence: negative when a unit before does
+    State true_in;           // the known entry
+    // "a block begins at my first bit"; where a failed decode rests, not synchronised.  Derived where they are used: as fields they
+    // cost unpack_kernel the registers that keep five of its workgroups on a CU
+    JS_HD State fresh() const { return State{start, 0}; }
+    JS_HD State park() const { return State{last ? end : stop, NOSYNC}; }
+};
+
+JS_HD Sub locate(const View& v, int32_t s, int32_t b0, int t, int32_t total_sub, const State& carry_state) {
+    Sub x = {};
+    x.live = s < total_sub;
+    if (x.live) {
+        int32_t lo = 0, hi = v.f->nseg - 1;  // the last segment that begins at or before s
+        while (lo < hi) {
+            const int32_t mid = (lo + hi + 1) >> 1;
+            if (v.seg_sub[mid] <= s) lo = mid; else hi = mid - 1;
+        }
+        x.j = lo;
+        const int32_t m = s - v.seg_sub[lo];
+        x.sf = v.seg_sub[lo] - b0;
+        x.start = 8 * seg_lo(v, lo) + m * v.sub;
+        x.end = 8 * seg_hi(v, lo);
+        x.first = m == 0;
+        x.last = s + 1 == v.seg_sub[lo + 1];
+        x.stop = x.last ? NO_STOP : x.start + v.sub;
+    }
+    x.is_true = x.live && (x.first || t == 0);
+    x.true_in = x.first ? x.fresh() : carry_state;
+    return x;
+}
+
+// The state thread t enters with; exits: every thread's last exit
+JS_HD State entry(const Sub& x, int t, const State* exits) { return x.is_true ? x.true_in : (t > 0 ? exits[t - 1] : x.fresh()); }
+
+// What a thread keeps from round to round: its exit, the entry that gave it, the blocks that decode finished
+struct Round {
+    State mine, last_in;
+    int32_t cnt;
+};
+JS_HD Round before_rounds(const Sub& x) { return Round{x.park(), State{-1, -2}, 0}; }
+
+// One round of one thread: decodes again only if its entry `in` changed.  True when its exit changed.
+JS_HD bool round_step(const View& v, const Sub& x, State in, Round& r) {
+    if (in.sk == NOSYNC) in = x.fresh();
+    if (!x.live || same(in, r.last_in)) return false;
+    Result o;
+    run<false>(v.w, x.end, x.stop, in, v.tabs, *v.f, 0, 0, 0, nullptr, v.d, o);
+    const State e = o.err ? x.park() : o.exit;
+    const bool changed = !same(e, r.mine);
+    r.mine = e;
+    r.cnt = o.blocks;
+    r.last_in = in;
+    return changed;
+}
+
+// write: a thread behind a not-synchronised final entry `in` in its segment is behind an error of the true chain.  The inclusive
+// maximum of unsynced() along the threads is `lastflag`.
+JS_HD int32_t unsynced(const Sub& x, int t, const State& in) { return x.live && in.sk == NOSYNC ? t : -1; }
+JS_HD bool valid(const Sub& x, int32_t lastflag) { return x.live && lastflag < (x.sf > 0 ? x.sf : 0); }
+
+// The ordinal, inside its segment, of the block thread t enters in.  pex: the blocks the threads in front of each thread finished;
+// carry_ord: those of the units before, for the segment that thread 0 continues
+JS_HD long long entry_ordinal(const Sub& x, int t, const int32_t* pex, long long carry_ord) {
+    if (!x.live) return 0;
+    return x.sf >= 0 ? (long long)(pex[t] - pex[x.sf]) : carry_ord + pex[t];
+}
+
+// The last decode of a valid thread, from its final entry: writes its blocks and returns its defect, or NO_DEFECT
+JS_HD unsigned long long write_step(const View& v, const Sub& x, const State& in, long long ord) {
+    const File& f = *v.f;
+    const int64_t mcu0 = (int64_t)x.j * f.rst;
+    const int64_t limit = ((mcu0 + f.rst < f.nmcu ? mcu0 + f.rst : (int64_t)f.nmcu) - mcu0) * f.bpm;
+    Result o;
+    run<true>(v.w, x.end, x.stop, in, v.tabs, f, ord, limit, mcu0, v.fc, v.d, o);
+    if (o.err) return defect(mcu0 * f.bpm + o.err_ord, o.err_stage, o.err);  // err and done_pos exclude each other: one defect at the most
+    if (o.done_pos >= 0) {  // behind the segment's last block: fewer than 8 bits are left, and the stop's code is the one due
+        const bool final = x.j == f.nseg - 1;
+        const int code = x.j < v.nstops ? v.stop_code[x.j] : -1;
+        if (x.end - o.done_pos >= 8 || code != (final ? 0xD9 : 0xD0 + (x.j & 7)))
+            return defect(mcu0 * f.bpm + limit - 1, 3, final ? R_NO_EOI : R_RESTART);
+    }
+    return NO_DEFECT;
+}
+
+// What the last thread of a unit, if live, hands to thread 0 of the next
+struct Carry {
+    State state;    // its converged exit, or its park
+    long long ord;  // the ordinal of the block that exit stands in
+};
+JS_HD Carry hand_over(const Sub& x, bool valid, const Round& r, long long ord) {
+    return Carry{valid && r.mine.sk != NOSYNC ? r.mine : x.park(), ord + r.cnt};
+}
+
+// predict: component c's blocks in scan order are items 0 .. predict_count - 1
+struct Item {
+    int64_t mcu;
+    int slot;
+    bool restart;  // the prediction starts again here
+};
+JS_HD int blocks_per_mcu(const File& f, int c) { return c == 0 && f.ncomp == 3 ? f.hs * f.vs : 1; }
+JS_HD int64_t predict_count(const File& f, int c) { return (int64_t)f.nmcu * blocks_per_mcu(f, c); }
+JS_HD Item predict_item(const File& f, int c, int64_t q) {
+    const int per = blocks_per_mcu(f, c), at = (int)(q % per);
+    const int64_t mcu = q / per;
+    return Item{mcu, (c == 0 ? 0 : f.hs * f.vs + c - 1) + at, at == 0 && mcu % f.rst == 0};
+}
+// decode_block's range checks of the DC value `pred` of component c's block `it`: the defect, or NO_DEFECT
+JS_HD unsigned long long predict_check(const View& v, int c, const Item& it, int32_t pred) {
+    const int64_t pq = (int64_t)pred * (int64_t)v.d->qt[c][0];
+    const bool fine = pred >= -32768 && pred <= 32767 && pq >= -32768 && pq <= 32767;
+    return fine ? NO_DEFECT : defect(it.mcu * v.f->bpm + it.slot, 1, R_RANGE);
+}
 
 }  // namespace jsync

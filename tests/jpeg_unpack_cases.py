@@ -89,6 +89,13 @@ def defects(files):
     mid += rst[mid - 1] == 0xFF  # not between a 0xFF and its stuffed zero
     assert marks[4] + 2 < mid < marks[5]
     out.append(("rst3: a stray FF D3 inside an interval", rst[:mid] + b"\xff\xd3" + rst[mid:], -1))
+    # a segment without a data byte still is a subsequence to decode (jsync::seg_subs: at least one)
+    out.append(("rst3: an empty interval", rst[:m + 2] + bytes([0xFF, 0xD0 + ((rst[m + 1] + 1) & 7)]) + rst[m + 2:], -1))
+    # exactly 8 bits behind a segment's last block (jsync::write_step: fewer than 8 may be left): a zero byte in front of a marker
+    # whose segment ends without padding -- padding bits are ones, so an even last byte has none
+    even = [p for p in marks + [len(rst) - 2] if rst[p - 1] % 2 == 0 and not (rst[p - 1] == 0 and rst[p - 2] == 0xFF)]
+    assert even
+    out.append(("rst3: a byte too many in front of a marker", rst[:even[0]] + b"\x00" + rst[even[0]:], -1))
     return out
 
 
