@@ -1,0 +1,321 @@
+"""Motion-JPEG / PCM AVI files read and written on the host: the container in front of `jpeg.decode_frames` (no device, no
+dependency beyond numpy).
+
+What is read is the AVI that `ffmpeg -i clip.mp4 -c:v mjpeg -q:v 2 -c:a pcm_s16le -ar 44100 -ac 2 clip.avi` writes -- exactly as
+`audio_pipeline.convert_mp4_to_mp3` reads "the WAV that ffmpeg writes": a RIFF `AVI ` form with a `hdrl` list (`avih`, one `strl`
+list per stream holding `strh` and `strf`) and a `movi` list whose `NNdc` / `NNdb` chunks are baseline JPEG files, one per frame,
+interleaved with the `NNwb` chunks of 16-bit PCM.  `open_avi` maps the file (mmap) and hands the frames out as memoryviews of the
+mapping: no frame byte is copied on the way to the native header pass.
+
+Everything else is refused with a ValueError that names the file and the reason, before any frame is touched: another codec,
+another audio format, a second video stream, OpenDML (files past 1 GiB: `AVIX` segments, `indx` / `ix##` indexes), a chunk that
+runs past the end of the file.  H.264 / MP4 is out of reach without a codec library and is not pretended.
+
+`write_avi` is the inverse (tests, tools/avi_bench.py, users who want the format).
+"""
+from __future__ import annotations
+
+import mmap
+import os
+import struct
+from typing import Optional, Sequence
+
+import numpy as np
+
+WAVE_FORMAT_PCM = 1
+AVIF_HASINDEX, AVIF_ISINTERLEAVED = 0x10, 0x100
+AVIIF_KEYFRAME = 0x10
+
+
+class AviFile:
+    """An open Motion-JPEG AVI file (see `open_avi`).  `frames[i]` is a memoryview of the mapping and stays valid until `close()`
+    (or the end of the `with` block); `pcm` is an array of its own."""
+
+    def __init__(self, path, mapping, view, width, height, rate, scale, frames, audio_rate, audio_channels, pcm):
+        self.path = path
+        self._map, self._view = mapping, view
+        self.width, self.height = int(width), int(height)
+        self.rate, self.scale = int(rate), int(scale)
+        self.fps = self.rate / self.scale
+        self.frames = frames
+        self.n_frames = len(frames)
+        self.audio_rate, self.audio_channels = audio_rate, audio_channels
+        self.pcm = pcm
+
+    def close(self):
+        for f in self.frames:
+            f.release()
+        self.frames = []
+        if self._view is not None:
+            self._view.release()
+            self._view = None
+        if self._map is not None:
+            self._map.close()
+            self._map = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _walk(view, at, end, refuse):
+    """The chunks of view[at:end): (fourcc, list type or None, first data byte, data length).  Chunks are padded to even length;
+    a header or a body that runs past `end` is refused."""
+    while at < end:
+        if at + 8 > end:
+            raise refuse(f"a chunk header at byte {at} runs past the end of its list")
+        cc = bytes(view[at:at + 4])
+        size = struct.unpack_from("<I", view, at + 4)[0]
+        if at + 8 + size > end:
+            raise refuse(f"chunk {cc!r} at byte {at} ({size} bytes) runs past the end of the file")
+        kind = None
+        if cc in (b"LIST", b"RIFF"):
+            if size < 4:
+                raise refuse(f"list at byte {at} has no type")
+            kind = bytes(view[at + 8:at + 12])
+        yield cc, kind, at + 8, size
+        at += 8 + size + (size & 1)
+
+
+def _parse(view, path):
+    def refuse(reason):
+        return ValueError(f"{path}: {reason}")
+
+    n = len(view)
+    if n < 12 or bytes(view[0:4]) != b"RIFF" or bytes(view[8:12]) != b"AVI ":
+        raise refuse("not a RIFF AVI file")
+    riff = struct.unpack_from("<I", view, 4)[0]
+    if 8 + riff > n:
+        raise refuse(f"the RIFF form ({riff} bytes) runs past the end of the file ({n} bytes)")
+    end = 8 + riff
+    if end + (end & 1) + 12 <= n and bytes(view[end + (end & 1):end + (end & 1) + 4]) == b"RIFF":
+        raise refuse("OpenDML file (a second RIFF segment, AVIX); only plain AVI up to 1 GiB is read")
+    streams = []  # per strl, in file order: dict(type, handler, scale, rate, strf fields)
+    movi = None
+    for cc, kind, at, size in _walk(view, 12, end, refuse):
+        if cc == b"LIST" and kind == b"hdrl":
+            for cc2, kind2, at2, size2 in _walk(view, at + 4, at + size, refuse):
+                if not (cc2 == b"LIST" and kind2 == b"strl"):
+                    continue  # avih (not trusted: the movi walk counts the frames), JUNK, odml lists, ...
+                s = {}
+                for cc3, _, at3, size3 in _walk(view, at2 + 4, at2 + size2, refuse):
+                    if cc3 == b"strh":
+                        if size3 < 36:
+                            raise refuse("a strh chunk of fewer than 36 bytes")
+                        s["type"], s["handler"] = bytes(view[at3:at3 + 4]), bytes(view[at3 + 4:at3 + 8])
+                        s["scale"], s["rate"] = struct.unpack_from("<II", view, at3 + 20)
+                    elif cc3 == b"strf":
+                        s["strf"] = (at3, size3)
+                    elif cc3 == b"indx":
+                        raise refuse("OpenDML file (an indx chunk); only plain AVI up to 1 GiB is read")
+                    # vprp, strn, strd, JUNK, unknown: skipped
+                if "type" not in s or "strf" not in s:
+                    raise refuse("a stream list without strh or strf")
+                streams.append(s)
+        elif cc == b"LIST" and kind == b"movi" and movi is None:
+            movi = (at + 4, at + size)
+        # idx1 is optional and not trusted; JUNK, LIST INFO, unknown chunks: skipped
+    video = [i for i, s in enumerate(streams) if s["type"] == b"vids"]
+    audio = [i for i, s in enumerate(streams) if s["type"] == b"auds"]
+    if not video:
+        raise refuse("no video stream")
+    if len(video) > 1:
+        raise refuse(f"{len(video)} video streams; one is read")
+    v = streams[video[0]]
+    at, size = v["strf"]
+    if size < 40:
+        raise refuse("the video stream's strf is no BITMAPINFOHEADER")
+    width, height = struct.unpack_from("<ii", view, at + 4)
+    comp = bytes(view[at + 16:at + 20])
+    if comp.upper() != b"MJPG":
+        raise refuse(f"video biCompression {comp!r}: only MJPG (Motion-JPEG) is read")
+    if v["handler"].upper() != b"MJPG":
+        raise refuse(f"video handler {v['handler']!r}: only MJPG (Motion-JPEG) is read")
+    if v["scale"] <= 0 or v["rate"] <= 0 or width <= 0 or height == 0:
+        raise refuse(f"video stream of {width} x {height} at {v['rate']} / {v['scale']} frames per second")
+    a_rate = a_ch = None
+    if audio:
+        a = streams[audio[0]]
+        at, size = a["strf"]
+        if size < 16:
+            raise refuse("the audio stream's strf is no WAVEFORMAT")
+        tag, a_ch, a_rate, _, _, bits = struct.unpack_from("<HHIIHH", view, at)
+        if tag != WAVE_FORMAT_PCM or bits != 16:
+            raise refuse(f"audio format tag {tag} with {bits} bits: only WAVE_FORMAT_PCM (1) with 16 bits is read")
+        if a_ch < 1 or a_rate < 1:
+            raise refuse(f"audio stream of {a_ch} channels at {a_rate} Hz")
+    if movi is None:
+        raise refuse("no movi list")
+    # the movi walk is the source of truth: frames and PCM in file order (`rec ` lists hold chunks of their own)
+    frames, sound = [], []
+
+    def walk_movi(lo, hi, top=True):
+        for cc, kind, at, size in _walk(view, lo, hi, refuse):
+            if cc == b"LIST":
+                if kind == b"rec " and top:  # (rec lists do not nest)
+                    walk_movi(at + 4, at + size, False)
+                continue  # LIST INFO, unknown lists
+            if cc[:2] == b"ix":
+                raise refuse("OpenDML file (an ix## index chunk in movi); only plain AVI up to 1 GiB is read")
+            if not cc[:2].isdigit():
+                continue  # JUNK, unknown
+            stream, what = int(cc[:2]), cc[2:]
+            if stream == video[0] and what in (b"dc", b"db"):
+                if size == 0:  # a dropped frame: the previous one again
+                    if not frames:
+                        raise refuse("the first video chunk is empty (a dropped frame with no predecessor)")
+                    frames.append(frames[-1])
+                else:
+                    frames.append((at, size))
+            elif audio and stream == audio[0] and what == b"wb":
+                sound.append((at, size))
+
+    walk_movi(*movi)
+    return dict(width=width, height=abs(height), rate=v["rate"], scale=v["scale"], frames=frames, sound=sound, audio_rate=a_rate,
+                audio_channels=a_ch)
+
+
+def open_avi(path) -> AviFile:
+    """The Motion-JPEG AVI file `path` -> AviFile: width, height, rate, scale (the video stream's dwRate / dwScale), fps = rate /
+    scale, n_frames, frames (one zero-copy memoryview per video chunk, in file order; an empty chunk repeats its predecessor),
+    audio_rate, audio_channels and pcm (int16 [L, C]: the audio chunks joined, cut to whole sample frames; None, with both fields
+    None, when there is no audio stream).  Stream numbers follow the order of the strl lists.  ValueError naming the file and
+    the reason for anything outside that (the module's docstring), raised before a frame is looked at."""
+    path = os.fspath(path)
+    with open(path, "rb") as f:
+        if os.fstat(f.fileno()).st_size == 0:
+            raise ValueError(f"{path}: not a RIFF AVI file (empty)")
+        mapping = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+    view = memoryview(mapping)
+    try:
+        p = _parse(view, path)
+        frames = [view[at:at + size] for at, size in p["frames"]]
+        pcm = None
+        if p["audio_rate"] is not None:
+            ch = p["audio_channels"]
+            parts = [np.frombuffer(view[at:at + size], dtype=np.uint8) for at, size in p["sound"]]
+            raw = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+            whole = raw.size // (2 * ch) * (2 * ch)
+            pcm = raw[:whole].copy().view("<i2").reshape(-1, ch)
+            del parts, raw
+    except BaseException:
+        view.release()
+        mapping.close()
+        raise
+    return AviFile(path, mapping, view, p["width"], p["height"], p["rate"], p["scale"], frames, p["audio_rate"], p["audio_channels"], pcm)
+
+
+# ---------------------------------------------------------------------------------------------------- writing
+def jpeg_size(blob) -> tuple:
+    """(width, height) of a JPEG file from its frame header (SOF0 .. SOF15 but DHT / JPG / DAC); ValueError when there is none."""
+    b = bytes(blob[:65536]) if len(blob) > 65536 else bytes(blob)
+    p = 2
+    if b[:2] != b"\xff\xd8":
+        raise ValueError("not a JPEG file (no SOI)")
+    while p + 4 <= len(b):
+        if b[p] != 0xFF:
+            break
+        m = b[p + 1]
+        if m == 0xFF:
+            p += 1
+            continue
+        length = (b[p + 2] << 8) | b[p + 3]
+        if 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
+            if p + 9 > len(b):
+                break
+            return (b[p + 7] << 8) | b[p + 8], (b[p + 5] << 8) | b[p + 6]
+        p += 2 + length
+    raise ValueError("no frame header in the JPEG file")
+
+
+def _chunk(cc: bytes, body: bytes) -> bytes:
+    return cc + struct.pack("<I", len(body)) + body + (b"\0" if len(body) & 1 else b"")
+
+
+def _list(kind: bytes, body: bytes, cc: bytes = b"LIST") -> bytes:
+    return cc + struct.pack("<I", 4 + len(body)) + kind + body
+
+
+def build_avi(jpeg_blobs: Sequence, rate: int, scale: int = 1, pcm: Optional[np.ndarray] = None, audio_rate: int = 44100,
+              index: bool = True, audio_first: bool = False, movi_extra: Sequence = (), strl_extra: bytes = b"") -> bytes:
+    """The bytes `write_avi` writes.  Two options beyond it, for tests of the reader: `audio_first` puts the audio stream's strl in
+    front of the video's (audio is then stream 00, video 01); `movi_extra` = [(k, raw bytes)], raw chunks or lists placed in movi
+    in front of frame k's chunk (k = the frame count: at the end); `strl_extra`: raw chunks behind the video stream's strf (vprp,
+    JUNK, ...)."""
+    blobs = [bytes(b) for b in jpeg_blobs]
+    first = next((b for b in blobs if b), None)
+    if first is None:
+        raise ValueError("write_avi: no frame")
+    rate, scale = int(rate), int(scale)
+    if rate <= 0 or scale <= 0:
+        raise ValueError("write_avi: rate and scale positive")
+    width, height = jpeg_size(first)
+    n = len(blobs)
+    if pcm is not None:
+        pcm = np.asarray(pcm)
+        if pcm.dtype != np.int16 or pcm.ndim not in (1, 2):
+            raise ValueError("write_avi: pcm int16 [L] or [L, C]")
+        pcm = np.ascontiguousarray(pcm.reshape(len(pcm), -1)).astype("<i2", copy=False)
+    vs, as_ = (1, 0) if (audio_first and pcm is not None) else (0, 1)
+    vid, aud = b"%02ddc" % vs, b"%02dwb" % as_
+    movi, entries = [b"movi"], []
+    at = 4  # idx1 offsets count from the 'movi' fourcc
+    extra = {}
+    for k, raw in movi_extra:
+        extra.setdefault(int(k), []).append(bytes(raw))
+
+    def put(cc, body, flags=AVIIF_KEYFRAME):
+        nonlocal at
+        c = _chunk(cc, body)
+        entries.append(cc + struct.pack("<III", flags, at, len(body)))
+        movi.append(c)
+        at += len(c)
+
+    for k in range(n + 1):
+        for raw in extra.get(k, ()):
+            movi.append(raw)
+            at += len(raw)
+        if k == n:
+            break
+        put(vid, blobs[k], AVIIF_KEYFRAME if blobs[k] else 0)
+        if pcm is not None:  # the samples of about this frame's duration; the last frame takes what is left
+            lo = min(len(pcm), k * audio_rate * scale // rate)
+            hi = len(pcm) if k == n - 1 else min(len(pcm), (k + 1) * audio_rate * scale // rate)
+            if hi > lo:
+                put(aud, pcm[lo:hi].tobytes())
+    movi_body = b"".join(movi)
+    biggest = max(len(b) for b in blobs)
+    strl_v = _list(b"strl", _chunk(b"strh", struct.pack("<4s4sIHHIIIIIIIIhhhh", b"vids", b"MJPG", 0, 0, 0, 0, scale, rate, 0, n, biggest,
+                                                        0xFFFFFFFF, 0, 0, 0, width, height)) +
+                   _chunk(b"strf", struct.pack("<IiiHH4sIiiII", 40, width, height, 1, 24, b"MJPG", width * height * 3, 0, 0, 0, 0)) + bytes(strl_extra))
+    lists = [strl_v]
+    if pcm is not None:
+        ch = pcm.shape[1]
+        strl_a = _list(b"strl", _chunk(b"strh", struct.pack("<4s4sIHHIIIIIIIIhhhh", b"auds", b"\1\0\0\0", 0, 0, 0, 0, 1, audio_rate, 0, len(pcm),
+                                                            0, 0xFFFFFFFF, 2 * ch, 0, 0, 0, 0)) +
+                       _chunk(b"strf", struct.pack("<HHIIHH", WAVE_FORMAT_PCM, ch, audio_rate, audio_rate * 2 * ch, 2 * ch, 16)))
+        lists = [strl_a, strl_v] if vs == 1 else [strl_v, strl_a]
+    avih = _chunk(b"avih", struct.pack("<14I", max(1, 1000000 * scale // rate), 0, 0, (AVIF_HASINDEX if index else 0) | AVIF_ISINTERLEAVED, n, 0,
+                                       len(lists), biggest, width, height, 0, 0, 0, 0))
+    body = _list(b"hdrl", avih + b"".join(lists)) + b"LIST" + struct.pack("<I", len(movi_body)) + movi_body
+    if len(movi_body) & 1:
+        body += b"\0"
+    if index:
+        body += _chunk(b"idx1", b"".join(entries))
+    if len(body) + 4 >= 1 << 30:
+        raise ValueError("write_avi: more than 1 GiB; OpenDML is not written")
+    return _list(b"AVI ", body, b"RIFF")
+
+
+def write_avi(path, jpeg_blobs: Sequence, rate: int, scale: int = 1, pcm: Optional[np.ndarray] = None, audio_rate: int = 44100,
+              index: bool = True):
+    """Writes the Motion-JPEG AVI file `path`: one `00dc` chunk per JPEG file of `jpeg_blobs` (an empty one is a dropped frame)
+    at `rate` / `scale` frames per second, `pcm` (int16 [L] or [L, C] at `audio_rate`) as stream 01, interleaved in chunks of about
+    one video frame's duration, and an `idx1` index when asked.  `open_avi` of the file gives the same bytes and the same samples.
+    Returns `path`."""
+    data = build_avi(jpeg_blobs, rate, scale, pcm, audio_rate, index)
+    with open(path, "wb") as f:
+        f.write(data)
+    return path

@@ -35,6 +35,27 @@ constexpr uint8_t kNatural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25
                               41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                               30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
+// The four DHT segments as libjpeg writes them (the standard's tables K.3 - K.6), marker and length included: DC 0, AC 0, DC 1, AC 1.
+// The ONE statement of these tables: the writer emits them (encoding, below), and the reader assumes them for a table a scan
+// references and no DHT segment defined when AVCER_JPEG_STD_TABLES asks for it (MJPEG frames, parse_header)
+constexpr uint8_t kDhtDc0[33] = {255, 196, 0, 31, 0, 0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+constexpr uint8_t kDhtDc1[33] = {255, 196, 0, 31, 1, 0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+constexpr uint8_t kDhtAc0[183] = {
+    255, 196, 0,   181, 16,  0,   2,   1,   3,   3,   2,   4,   3,   5,   5,   4,   4,   0,   0,   1,   125, 1,   2,   3,   0,   4,   17,
+    5,   18,  33,  49,  65,  6,   19,  81,  97,  7,   34,  113, 20,  50,  129, 145, 161, 8,   35,  66,  177, 193, 21,  82,  209, 240, 36,
+    51,  98,  114, 130, 9,   10,  22,  23,  24,  25,  26,  37,  38,  39,  40,  41,  42,  52,  53,  54,  55,  56,  57,  58,  67,  68,  69,
+    70,  71,  72,  73,  74,  83,  84,  85,  86,  87,  88,  89,  90,  99,  100, 101, 102, 103, 104, 105, 106, 115, 116, 117, 118, 119, 120,
+    121, 122, 131, 132, 133, 134, 135, 136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163, 164, 165, 166, 167, 168, 169,
+    170, 178, 179, 180, 181, 182, 183, 184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213, 214, 215, 216, 217,
+    218, 225, 226, 227, 228, 229, 230, 231, 232, 233, 234, 241, 242, 243, 244, 245, 246, 247, 248, 249, 250};
+constexpr uint8_t kDhtAc1[183] = {
+    255, 196, 0,   181, 17,  0,   2,   1,   2,   4,   4,   3,   4,   7,   5,   4,   4,   0,   1,   2,   119, 0,   1,   2,   3,   17,  4,
+    5,   33,  49,  6,   18,  65,  81,  7,   97,  113, 19,  34,  50,  129, 8,   20,  66,  145, 161, 177, 193, 9,   35,  51,  82,  240, 21,
+    98,  114, 209, 10,  22,  36,  52,  225, 37,  241, 23,  24,  25,  26,  38,  39,  40,  41,  42,  53,  54,  55,  56,  57,  58,  67,  68,
+    69,  70,  71,  72,  73,  74,  83,  84,  85,  86,  87,  88,  89,  90,  99,  100, 101, 102, 103, 104, 105, 106, 115, 116, 117, 118, 119,
+    120, 121, 122, 130, 131, 132, 133, 134, 135, 136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163, 164, 165, 166, 167,
+    168, 169, 170, 178, 179, 180, 181, 182, 183, 184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213, 214, 215,
+    216, 217, 218, 226, 227, 228, 229, 230, 231, 232, 233, 234, 242, 243, 244, 245, 246, 247, 248, 249, 250};
 struct Huff {
     bool defined = false;
     uint8_t bits[17] = {0};
@@ -97,8 +118,21 @@ struct Header {
 
 inline int be16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
 
+// One annex-K table into `t`, from its DHT segment above (marker, length, class / id, 16 counts, the symbols)
+void assume_std(Huff& t, const uint8_t* seg, int count) {
+    t.bits[0] = 0;
+    memcpy(t.bits + 1, seg + 5, 16);
+    memset(t.vals, 0, sizeof(t.vals));
+    memcpy(t.vals, seg + 21, (size_t)count);
+    t.defined = true;
+    derive(t);
+}
+
 // Everything up to the first entropy-coded byte.  Returns a reason; on R_OK h.d holds the geometry and the tables of the scan.
-int parse_header(const uint8_t* s, size_t len, Header& h) {
+// std_tables (AVCER_JPEG_STD_TABLES): a table 0 or 1 the scan references and no DHT segment of the file defined is the standard's
+// annex-K table of that class and id -- what libjpeg-turbo (jdhuff.c, std_huff_tables) and ffmpeg's mjpeg2jpeg assume for Motion-JPEG
+// frames.  A table the file defines is the file's; ids 2 and 3 have no standard table and stay R_TABLE.
+int parse_header(const uint8_t* s, size_t len, Header& h, bool std_tables = false) {
     h = Header();  // a worker reuses one Header for all its files: no table, id or restart interval of the last one survives
     Desc& d = h.d;
     memset(&d, 0, sizeof(d));
@@ -216,6 +250,11 @@ int parse_header(const uint8_t* s, size_t len, Header& h) {
         d.bh[0] = (d.height + 7) / 8;
     }
     d.n_blocks = 0;
+    if (std_tables)
+        for (int c = 0; c < d.ncomp; ++c) {
+            if (h.td[c] < 2 && !h.dc[h.td[c]].defined) assume_std(h.dc[h.td[c]], h.td[c] ? kDhtDc1 : kDhtDc0, (int)sizeof(kDhtDc0) - 21);
+            if (h.ta[c] < 2 && !h.ac[h.ta[c]].defined) assume_std(h.ac[h.ta[c]], h.ta[c] ? kDhtAc1 : kDhtAc0, (int)sizeof(kDhtAc0) - 21);
+        }
     for (int c = 0; c < d.ncomp; ++c) {
         if (!h.q_def[d.tq[c]]) return R_TABLE;
         if (!h.dc[h.td[c]].defined || !h.dc[h.td[c]].dc_ok || !h.ac[h.ta[c]].defined || !h.ac[h.ta[c]].ok) return R_TABLE;
@@ -604,6 +643,121 @@ __global__ void jpeg_canvas_kernel(const uint8_t* __restrict__ planes, const Des
     o[2] = (uint8_t)(px >> 16);
 }
 
+// Kernel B, frames: whole video frames [n, H, W, 3], every image exactly W x H, channel order as asked.  Shaped by the store: a
+// thread owns one 16-byte ALIGNED piece of one output row (rows are 3 W bytes and start wherever that leaves them, so the pieces
+// are counted from the row's first aligned address down; the first and last piece of a row are cut to the row and go out as byte
+// stores, every piece between as one 16-byte store).  A piece holds bytes of at most 6 pixels; they lie inside the 8 pixels
+// [e, e + 8), e even, which are 4 horizontal chroma pairs: with 2 x subsampling the thread reads the 6 chroma columns s - 1 .. s + 4
+// ONCE (for 2 x 2: both rows, folded into the column sums 3 near + far), and every pair takes its two outputs from three of them
+// -- jdsample.c's h2v1 / h2v2 fancy upsampling, the arithmetic of chroma_at.  Columns and pixels past the picture's edge are
+// clamped (the clamp IS libjpeg's edge rule for the columns; pixels out there belong to no byte of the row and are dropped).
+constexpr int FRAME_THREADS = 256;
+
+__device__ __forceinline__ uint32_t frame_px(int Y, int cb, int cr, bool bgr) {
+    const int r = clamp255(Y + ((91881 * cr + 32768) >> 16));
+    const int g = clamp255(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
+    const int b = clamp255(Y + ((116130 * cb + 32768) >> 16));
+    return (uint32_t)(bgr ? b : r) | ((uint32_t)g << 8) | ((uint32_t)(bgr ? r : b) << 16);
+}
+
+__global__ void frames_size_kernel(const Desc* __restrict__ desc, int n, int H, int W, int32_t* __restrict__ flags) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && desc[i].status == AVCER_JPEG_OK && (desc[i].width != W || desc[i].height != H)) flags[i] = 2;
+}
+
+__global__ void __launch_bounds__(FRAME_THREADS) jpeg_frames_kernel(const uint8_t* __restrict__ planes, const Desc* __restrict__ desc,
+                                                                    const int32_t* __restrict__ flags, int n, int H, int W, int per_row,
+                                                                    int bgr, uint8_t* __restrict__ frames) {
+    const long idx = (long)blockIdx.x * FRAME_THREADS + threadIdx.x;
+    if (idx >= (long)n * H * per_row) return;
+    const int piece = (int)(idx % per_row);
+    const long row = idx / per_row;  // t * H + y
+    const int y = (int)(row % H), t = (int)(row / H);
+    uint8_t* const out = frames + row * 3L * W;
+    // the piece in bytes of the row: [wb, wb + 16), wb < 0 where the row starts inside its first aligned piece
+    const int wb = 16 * piece - (int)((uintptr_t)out & 15);
+    if (wb >= 3 * W) return;
+    uint32_t o4[4] = {0, 0, 0, 0};
+    Planes g;
+    if (planes_of(desc + t, planes, flags[t], g)) {  // flag 2 (another size) included: such a frame is zero
+        const int x0 = wb >= 0 ? wb / 3 : -((2 - wb) / 3);  // floor
+        const int e = x0 & ~1;
+        int cb[8], cr[8];
+        if (g.ncomp == 1) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) cb[j] = cr[j] = 0;
+        } else if (g.hs == 2 && g.dw > 2) {
+            const int s0 = (e >> 1) - 1;
+            int colb[6], colr[6];
+            int bias_even, bias_odd, shift;
+            if (g.vs == 2) {
+                const int ty = y >> 1, tn = (y & 1) ? min(ty + 1, g.dh - 1) : max(ty - 1, 0);
+                const long r0 = (long)ty * g.ldc, r1 = (long)tn * g.ldc;
+#pragma unroll
+                for (int k = 0; k < 6; ++k) {
+                    const int s = min(max(s0 + k, 0), g.dw - 1);
+                    colb[k] = 3 * g.cb[r0 + s] + g.cb[r1 + s];
+                    colr[k] = 3 * g.cr[r0 + s] + g.cr[r1 + s];
+                }
+                bias_even = 8, bias_odd = 7, shift = 4;
+            } else {
+                const long r0 = (long)y * g.ldc;
+#pragma unroll
+                for (int k = 0; k < 6; ++k) {
+                    const int s = min(max(s0 + k, 0), g.dw - 1);
+                    colb[k] = g.cb[r0 + s];
+                    colr[k] = g.cr[r0 + s];
+                }
+                bias_even = 1, bias_odd = 2, shift = 2;
+            }
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {  // pair p: chroma column s0 + 1 + p, its left neighbour for the even pixel, its right for the odd
+                cb[2 * p] = ((3 * colb[p + 1] + colb[p] + bias_even) >> shift) - 128;
+                cb[2 * p + 1] = ((3 * colb[p + 1] + colb[p + 2] + bias_odd) >> shift) - 128;
+                cr[2 * p] = ((3 * colr[p + 1] + colr[p] + bias_even) >> shift) - 128;
+                cr[2 * p + 1] = ((3 * colr[p + 1] + colr[p + 2] + bias_odd) >> shift) - 128;
+            }
+        } else {  // chroma at full width, or a component of at most two columns (replicated, not filtered): the sample of that pixel
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int x = min(max(e + j, 0), g.w - 1);
+                cb[j] = chroma_at(g.cb, g.ldc, g, x, y) - 128;
+                cr[j] = chroma_at(g.cr, g.ldc, g, x, y) - 128;
+            }
+        }
+        uint32_t px[8];
+        const uint8_t* yr = g.y + (long)y * g.ldy;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int Y = yr[min(max(e + j, 0), g.w - 1)];
+            px[j] = g.ncomp == 1 ? (uint32_t)Y * 0x010101u : frame_px(Y, cb[j], cr[j], bgr != 0);
+        }
+        // the 24 bytes of the 8 pixels, then the 16 of them that start at byte wb - 3 e (0 .. 5)
+        uint32_t d[7];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            d[3 * q] = px[4 * q] | (px[4 * q + 1] << 24);
+            d[3 * q + 1] = (px[4 * q + 1] >> 8) | (px[4 * q + 2] << 16);
+            d[3 * q + 2] = (px[4 * q + 2] >> 16) | (px[4 * q + 3] << 8);
+        }
+        d[6] = 0;
+        const int off = wb - 3 * e, sh = 8 * (off & 3);
+        const bool up = off >= 4;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t lo = up ? d[k + 1] : d[k], hi = up ? d[k + 2] : d[k + 1];
+            o4[k] = (uint32_t)((((uint64_t)hi << 32) | lo) >> sh);
+        }
+    }
+    if (wb >= 0 && wb + 16 <= 3 * W) {
+        *reinterpret_cast<uint4*>(out + wb) = make_uint4(o4[0], o4[1], o4[2], o4[3]);
+    } else {  // a row's first or last piece: only the bytes that are the row's
+#pragma unroll
+        for (int m = 0; m < 16; ++m)
+            if (wb + m >= 0 && wb + m < 3 * W) out[wb + m] = (uint8_t)(o4[m >> 2] >> (8 * (m & 3)));
+    }
+}
+
 // The component planes in the context's JPEG workspace, sized by their own carving (one byte per coefficient)
 int jpeg_plane_ws(avcer_ctx* ctx, int64_t n_blocks, uint8_t** planes) {
     return ws_carve(ctx, WS_JPEG, "jpeg", [&](Arena& a) { *planes = a.get<uint8_t>(64 * (size_t)n_blocks); });
@@ -648,10 +802,12 @@ extern "C" int avcer_jpeg_probe(const uint8_t* bytes, size_t len, avcer_jpeg_des
     return AVCER_OK;
 }
 
-extern "C" int avcer_jpeg_entropy_batch(avcer_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, int16_t* coeffs,
-                                        int64_t cap_blocks, avcer_jpeg_desc* desc, int threads, int64_t* blocks_needed) {
+namespace {
+int entropy_batch(avcer_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, int16_t* coeffs, int64_t cap_blocks,
+                  avcer_jpeg_desc* desc, int threads, int hflags, int64_t* blocks_needed) {
+    const bool std_tables = (hflags & AVCER_JPEG_STD_TABLES) != 0;
     // ctx may be NULL (host-only call, no device needed): errors then come back as the code alone
-    if (n < 0 || (n && (!files || !lens || !desc)) || cap_blocks < 0 || (cap_blocks && !coeffs))
+    if (n < 0 || (n && (!files || !lens || !desc)) || cap_blocks < 0 || (cap_blocks && !coeffs) || (hflags & ~AVCER_JPEG_STD_TABLES))
         return set_err(ctx, AVCER_EINVAL, "jpeg_entropy_batch: bad arguments");
     try {
         const int nt = std::min(pool_size(threads), n);
@@ -683,7 +839,7 @@ extern "C" int avcer_jpeg_entropy_batch(avcer_ctx* ctx, const uint8_t* const* fi
         // headers first; then, in file order, every supported file gets the next free blocks of the storage, so offsets ascend
         // (kernel A finds a block's image by them); a file that does not fit is not handled and takes nothing
         each_file([&](int i, Header& h) {
-            const int r = parse_header(files[i], lens[i] < 0 ? 0 : (size_t)lens[i], h);  // no bytes: R_NO_SOI
+            const int r = parse_header(files[i], lens[i] < 0 ? 0 : (size_t)lens[i], h, std_tables);  // no bytes: R_NO_SOI
             desc[i] = h.d;
             desc[i].reason = r;
         });
@@ -704,7 +860,7 @@ extern "C" int avcer_jpeg_entropy_batch(avcer_ctx* ctx, const uint8_t* const* fi
         // the scans: independent.  The header is parsed again (some hundred bytes) rather than kept for every file of the batch
         each_file([&](int i, Header& h) {
             if (desc[i].status != AVCER_JPEG_OK) return;
-            int r = parse_header(files[i], (size_t)lens[i], h);
+            int r = parse_header(files[i], (size_t)lens[i], h, std_tables);
             if (r == R_OK) r = decode_scan(files[i], (size_t)lens[i], h, coeffs + 64 * desc[i].coef_block);
             if (r != R_OK) {
                 desc[i].reason = r;
@@ -715,6 +871,17 @@ extern "C" int avcer_jpeg_entropy_batch(avcer_ctx* ctx, const uint8_t* const* fi
         return set_err(ctx, AVCER_ENOMEM, "jpeg_entropy_batch: out of host memory");
     }
     return AVCER_OK;
+}
+}  // namespace
+
+extern "C" int avcer_jpeg_entropy_batch(avcer_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, int16_t* coeffs,
+                                        int64_t cap_blocks, avcer_jpeg_desc* desc, int threads, int64_t* blocks_needed) {
+    return entropy_batch(ctx, files, lens, n, coeffs, cap_blocks, desc, threads, 0, blocks_needed);
+}
+
+extern "C" int avcer_jpeg_entropy_batch_ex(avcer_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, int16_t* coeffs,
+                                           int64_t cap_blocks, avcer_jpeg_desc* desc, int threads, int hflags, int64_t* blocks_needed) {
+    return entropy_batch(ctx, files, lens, n, coeffs, cap_blocks, desc, threads, hflags, blocks_needed);
 }
 
 extern "C" int avcer_jpeg_tiles(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_blocks, const avcer_jpeg_desc* desc, int n,
@@ -745,6 +912,25 @@ extern "C" int avcer_jpeg_rgb(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_b
     return AVCER_OK;
 }
 
+extern "C" int avcer_jpeg_frames(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_blocks, const avcer_jpeg_desc* desc, int n,
+                                 int32_t* flags, uint8_t* frames, int H, int W, int bgr, avcer_stream_t stream) {
+    TRY(jpeg_args(ctx, "jpeg_frames", coeffs, n_blocks, desc, n, flags, frames));
+    if (H <= 0 || W <= 0 || H > 65535 || W > 65535 || (long)n * H * W >= (1L << 36))
+        return set_err(ctx, AVCER_EINVAL, "jpeg_frames: frames %d x %d x %d (1..65535 a side, fewer than 2^36 pixels)", n, H, W);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* planes = nullptr;
+    TRY(jpeg_planes(ctx, coeffs, n_blocks, desc, n, flags, &planes, st));
+    frames_size_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(desc, n, H, W, flags);
+    HIP_TRY(ctx, hipGetLastError());
+    const int per_row = (3 * W + 15) / 16 + 1;  // aligned 16-byte pieces a row of 3 W bytes can touch
+    const long total = (long)n * H * per_row;
+    jpeg_frames_kernel<<<(unsigned)((total + FRAME_THREADS - 1) / FRAME_THREADS), FRAME_THREADS, 0, st>>>(planes, desc, flags, n, H, W, per_row,
+                                                                                                        bgr, frames);
+    HIP_TRY(ctx, hipGetLastError());
+    return AVCER_OK;
+}
+
 // ================================================================================================ encoding
 // The mirror image of the above: the device computes the quantised coefficients of every image straight from the decoded frames
 // (avcer_jpeg_forward: one launch per batch), the host writes the files (avcer_jpeg_write_batch: headers and Huffman coding, a
@@ -767,25 +953,7 @@ const uint8_t kStdLuma[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26
 const uint8_t kStdChroma[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
                                 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
 
-// The four DHT segments as libjpeg writes them (the standard's tables K.3 - K.6), marker and length included: DC 0, AC 0, DC 1, AC 1
-constexpr uint8_t kDhtDc0[33] = {255, 196, 0, 31, 0, 0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
-constexpr uint8_t kDhtDc1[33] = {255, 196, 0, 31, 1, 0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
-constexpr uint8_t kDhtAc0[183] = {
-    255, 196, 0,   181, 16,  0,   2,   1,   3,   3,   2,   4,   3,   5,   5,   4,   4,   0,   0,   1,   125, 1,   2,   3,   0,   4,   17,
-    5,   18,  33,  49,  65,  6,   19,  81,  97,  7,   34,  113, 20,  50,  129, 145, 161, 8,   35,  66,  177, 193, 21,  82,  209, 240, 36,
-    51,  98,  114, 130, 9,   10,  22,  23,  24,  25,  26,  37,  38,  39,  40,  41,  42,  52,  53,  54,  55,  56,  57,  58,  67,  68,  69,
-    70,  71,  72,  73,  74,  83,  84,  85,  86,  87,  88,  89,  90,  99,  100, 101, 102, 103, 104, 105, 106, 115, 116, 117, 118, 119, 120,
-    121, 122, 131, 132, 133, 134, 135, 136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163, 164, 165, 166, 167, 168, 169,
-    170, 178, 179, 180, 181, 182, 183, 184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213, 214, 215, 216, 217,
-    218, 225, 226, 227, 228, 229, 230, 231, 232, 233, 234, 241, 242, 243, 244, 245, 246, 247, 248, 249, 250};
-constexpr uint8_t kDhtAc1[183] = {
-    255, 196, 0,   181, 17,  0,   2,   1,   2,   4,   4,   3,   4,   7,   5,   4,   4,   0,   1,   2,   119, 0,   1,   2,   3,   17,  4,
-    5,   33,  49,  6,   18,  65,  81,  7,   97,  113, 19,  34,  50,  129, 8,   20,  66,  145, 161, 177, 193, 9,   35,  51,  82,  240, 21,
-    98,  114, 209, 10,  22,  36,  52,  225, 37,  241, 23,  24,  25,  26,  38,  39,  40,  41,  42,  53,  54,  55,  56,  57,  58,  67,  68,
-    69,  70,  71,  72,  73,  74,  83,  84,  85,  86,  87,  88,  89,  90,  99,  100, 101, 102, 103, 104, 105, 106, 115, 116, 117, 118, 119,
-    120, 121, 122, 130, 131, 132, 133, 134, 135, 136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163, 164, 165, 166, 167,
-    168, 169, 170, 178, 179, 180, 181, 182, 183, 184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213, 214, 215,
-    216, 217, 218, 226, 227, 228, 229, 230, 231, 232, 233, 234, 242, 243, 244, 245, 246, 247, 248, 249, 250};
+// (the four DHT segments of the standard's annex K, kDhtDc0 .. kDhtAc1, stand at the top of this file: the reader implies them too)
 constexpr size_t HEADER_BYTES = 2 + 18 + 2 * 69 + 19 + 2 * (33 + 183) + 14;  // SOI, APP0, two DQT, SOF0, four DHT, SOS: 623
 
 // code and length of every symbol of one DHT segment (jpeg_make_c_derived_tbl: canonical codes in the order of the values)
@@ -2113,12 +2281,14 @@ int unpack_args(avcer_ctx* ctx, const char* what, const void* bytes, int64_t n_b
 
 }  // namespace
 
-extern "C" int avcer_jpeg_scan_batch(avcer_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, uint8_t* bytes, int64_t cap_bytes,
-                                     avcer_jpeg_desc* desc, avcer_jpeg_scan* scan, avcer_jpeg_tab* tabs, int cap_tabs, int threads,
-                                     int32_t* n_tabs, int64_t* bytes_needed, int64_t* blocks_needed) {
+namespace {
+int scan_batch(avcer_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, uint8_t* bytes, int64_t cap_bytes,
+               avcer_jpeg_desc* desc, avcer_jpeg_scan* scan, avcer_jpeg_tab* tabs, int cap_tabs, int threads, int hflags, int32_t* n_tabs,
+               int64_t* bytes_needed, int64_t* blocks_needed) {
+    const bool std_tables = (hflags & AVCER_JPEG_STD_TABLES) != 0;
     // ctx may be NULL (host-only call, no device needed): errors then come back as the code alone
     if (n < 0 || (n && (!files || !lens || !desc || !scan)) || cap_bytes < 0 || (cap_bytes && !bytes) || cap_tabs < 0 || (cap_tabs && !tabs) ||
-        !n_tabs)
+        !n_tabs || (hflags & ~AVCER_JPEG_STD_TABLES))
         return set_err(ctx, AVCER_EINVAL, "jpeg_scan_batch: bad arguments");
     try {
         struct Found {  // what the header of one file says beyond its descriptor
@@ -2130,7 +2300,7 @@ extern "C" int avcer_jpeg_scan_batch(avcer_ctx* ctx, const uint8_t* const* files
         const int nt = std::max(1, std::min(pool_size(threads), n));
         each_index(n, nt, [&](int i) {
             std::unique_ptr<Header> h(new Header());
-            const int r = parse_header(files[i], lens[i] < 0 ? 0 : (size_t)lens[i], *h);  // no bytes: R_NO_SOI
+            const int r = parse_header(files[i], lens[i] < 0 ? 0 : (size_t)lens[i], *h, std_tables);  // no bytes: R_NO_SOI
             desc[i] = h->d;
             desc[i].reason = r;
             if (r != R_OK) return;
@@ -2199,6 +2369,19 @@ extern "C" int avcer_jpeg_scan_batch(avcer_ctx* ctx, const uint8_t* const* files
         return set_err(ctx, AVCER_ENOMEM, "jpeg_scan_batch: out of host memory");
     }
     return AVCER_OK;
+}
+}  // namespace
+
+extern "C" int avcer_jpeg_scan_batch(avcer_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, uint8_t* bytes, int64_t cap_bytes,
+                                     avcer_jpeg_desc* desc, avcer_jpeg_scan* scan, avcer_jpeg_tab* tabs, int cap_tabs, int threads,
+                                     int32_t* n_tabs, int64_t* bytes_needed, int64_t* blocks_needed) {
+    return scan_batch(ctx, files, lens, n, bytes, cap_bytes, desc, scan, tabs, cap_tabs, threads, 0, n_tabs, bytes_needed, blocks_needed);
+}
+
+extern "C" int avcer_jpeg_scan_batch_ex(avcer_ctx* ctx, const uint8_t* const* files, const int64_t* lens, int n, uint8_t* bytes,
+                                        int64_t cap_bytes, avcer_jpeg_desc* desc, avcer_jpeg_scan* scan, avcer_jpeg_tab* tabs, int cap_tabs,
+                                        int threads, int hflags, int32_t* n_tabs, int64_t* bytes_needed, int64_t* blocks_needed) {
+    return scan_batch(ctx, files, lens, n, bytes, cap_bytes, desc, scan, tabs, cap_tabs, threads, hflags, n_tabs, bytes_needed, blocks_needed);
 }
 
 extern "C" int avcer_jpeg_unpack(avcer_ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const avcer_jpeg_scan* scan, const avcer_jpeg_tab* tabs,

@@ -6,6 +6,7 @@ the hot path runs inside libavcer_hip.so.  All methods raise AvcerError on a non
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 
 import numpy as np
 import torch
@@ -29,7 +30,21 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+_LIVE = {}  # device index -> weak references to the engines created for it, oldest first (Engine.live)
+
+
 class Engine:
+    @staticmethod
+    def live(device: int | None = None):
+        """The youngest engine of `device` (default: torch's current device) that is still alive, for code that is called without
+        one (a dataset.VideoJob's load); RuntimeError when there is none."""
+        device = torch.cuda.current_device() if device is None else int(device)
+        refs = _LIVE.get(device, [])
+        refs[:] = [r for r in refs if r() is not None]
+        if not refs:
+            raise RuntimeError(f"no Engine is alive for device {device}")
+        return refs[-1]()
+
     def __init__(self, device: int = 0):
         if not torch.cuda.is_available():
             raise RuntimeError("avcer_amd needs a ROCm GPU (gfx950); there is no CPU path")
@@ -42,6 +57,7 @@ class Engine:
         if rc != 0:
             raise AvcerError(rc, "avcer_ctx_create failed")
         self.ctx = ctx
+        _LIVE.setdefault(int(device), []).append(weakref.ref(self))
         self.audio_classes = 0
         self.x3_fallbacks = 0  # calls `guarded` had to repeat in MODE_FP32 (the x3 range contract was broken)
         self._resample_cache = {}  # (orig_freq, new_freq) -> (plan, taps [span, n] and first [n] on the device): Engine.resample
@@ -576,6 +592,21 @@ class Engine:
         self._check(self.lib.avcer_jpeg_rgb(self.ctx, _ptr(coeffs), int(n_blocks), _ptr(desc), int(n), _ptr(flags), _ptr(canvas), int(hmax),
                                             int(wmax), self._stream()))
         return canvas, flags
+
+    def jpeg_frames(self, coeffs, desc, n: int, n_blocks: int, height: int, width: int, bgr: bool = True, out=None):
+        """The same files as video frames (avcer_jpeg_frames) -> (frames u8 [n,height,width,3] in BGR order, or RGB with bgr=False;
+        flags i32 [n]: 1 as jpeg_tiles returns it, 2 for a decoded file of another size than width x height; such a frame is zero)."""
+        if coeffs.dtype != torch.int16 or coeffs.numel() < 64 * n_blocks or desc.dtype != torch.uint8 or desc.numel() < _JPEG_DESC_BYTES * n or \
+                not coeffs.is_cuda or not desc.is_cuda:
+            raise ValueError("jpeg_frames: coeffs int16 [64 * n_blocks], desc uint8 [sizeof(avcer_jpeg_desc) * n], both on the device")
+        frames = self._new(n, int(height), int(width), 3, dtype=torch.uint8) if out is None else out
+        if tuple(frames.shape) != (n, int(height), int(width), 3) or frames.dtype != torch.uint8 or not frames.is_contiguous() or \
+                not frames.is_cuda:
+            raise ValueError("jpeg_frames: out must be a contiguous uint8 [n,height,width,3] on the device")
+        flags = self._new(n, dtype=torch.int32)
+        self._check(self.lib.avcer_jpeg_frames(self.ctx, _ptr(coeffs), int(n_blocks), _ptr(desc), int(n), _ptr(flags), _ptr(frames),
+                                               int(height), int(width), 1 if bgr else 0, self._stream()))
+        return frames, flags
 
     def crop_resize_linear(self, frames_u8, rects, swap_rb: bool = False, out_h: int = 224, out_w: int = 224):
         """frames u8 [T,H,W,3] + rects i32 [n,5] (frame, x0, y0, x1, y1) -> u8 [n,out_h,out_w,3]: cv2.resize of each crop with

@@ -15,6 +15,9 @@ With entropy="device" the host parses the headers only (`scan_batch`), the files
 coefficients, and `Engine.jpeg_unpack` Huffman-decodes them on the device (csrc/jpeg.hip avcer_jpeg_unpack); tiles, canvas and paths
 are the same.
 
+`decode_frames` is the same path for the frames of a Motion-JPEG video (avcer_amd/avi.py): whole frames of one size in BGR or
+RGB order (avcer_jpeg_frames), in passes, frames without DHT segments decoded with the standard's tables.
+
 `roundtrip_tiles` / `roundtrip_canvas` (the last part of this file) are decode(encode(crop)) without a file: the crop as the
 reference's stage 1 sees it, from one fused kernel and the decoder's pixel kernel.
 """
@@ -60,33 +63,49 @@ def host_threads(threads: int = 0) -> int:
     return min(16, threads) if threads > 0 else 16
 
 
-def entropy_batch(lib, blobs, coeffs: np.ndarray, desc: np.ndarray, threads: int = 0, ctx=None, cap_blocks: int | None = None) -> int:
-    """avcer_jpeg_entropy_batch: the files `blobs` -> coefficients in `coeffs` (int16, room for `cap_blocks` blocks of 64, default all
-    of it) and `desc[:n]` (DESC records).  Returns the blocks all files with a supported header need together."""
+STD_TABLES = 1  # AVCER_JPEG_STD_TABLES
+
+
+def _file_pointers(blobs):
+    """The files as the native calls take them: (pointer array, lengths i64, what keeps the pointers alive).  `bytes` go as they
+    are; any other buffer (a memoryview of a mapped AVI file, read-only) goes by its address: nothing is copied."""
     n = len(blobs)
-    files = (C.c_char_p * max(n, 1))(*blobs)
     lens = np.array([len(b) for b in blobs], dtype=np.int64)
+    if all(isinstance(b, bytes) for b in blobs):
+        return (C.c_char_p * max(n, 1))(*blobs), lens, blobs
+    keep = [np.frombuffer(b, dtype=np.uint8) for b in blobs]
+    return (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in keep]), lens, keep
+
+
+def entropy_batch(lib, blobs, coeffs: np.ndarray, desc: np.ndarray, threads: int = 0, ctx=None, cap_blocks: int | None = None,
+                  std_tables: bool = False) -> int:
+    """avcer_jpeg_entropy_batch: the files `blobs` -> coefficients in `coeffs` (int16, room for `cap_blocks` blocks of 64, default all
+    of it) and `desc[:n]` (DESC records).  Returns the blocks all files with a supported header need together.
+    std_tables: avcer_jpeg_entropy_batch_ex with AVCER_JPEG_STD_TABLES -- a Huffman table the scan references and no DHT defined is
+    the standard's (Motion-JPEG frames)."""
+    n = len(blobs)
+    files, lens, _keep = _file_pointers(blobs)
     need = C.c_int64(0)
     cap = coeffs.size // 64 if cap_blocks is None else int(cap_blocks)
     assert coeffs.dtype == np.int16 and coeffs.flags.c_contiguous and cap * 64 <= coeffs.size
     assert desc.dtype == DESC and desc.flags.c_contiguous and len(desc) >= n
-    rc = lib.avcer_jpeg_entropy_batch(ctx, C.cast(files, C.c_void_p), lens.ctypes.data_as(C.c_void_p), n,
-                                      coeffs.ctypes.data_as(C.c_void_p), cap, desc.ctypes.data_as(C.c_void_p), host_threads(int(threads)),
-                                      C.byref(need))
+    args = (ctx, C.cast(files, C.c_void_p), lens.ctypes.data_as(C.c_void_p), n, coeffs.ctypes.data_as(C.c_void_p), cap,
+            desc.ctypes.data_as(C.c_void_p), host_threads(int(threads)))
+    rc = lib.avcer_jpeg_entropy_batch_ex(*args, STD_TABLES, C.byref(need)) if std_tables else lib.avcer_jpeg_entropy_batch(*args, C.byref(need))
     if rc != 0:
         raise RuntimeError(f"avcer_jpeg_entropy_batch failed: {rc}")
     return int(need.value)
 
 
 def scan_batch(lib, blobs, data: np.ndarray, desc: np.ndarray, scan: np.ndarray, tabs: np.ndarray, threads: int = 0, ctx=None,
-               cap_bytes: int | None = None, cap_tabs: int | None = None):
+               cap_bytes: int | None = None, cap_tabs: int | None = None, std_tables: bool = False):
     """avcer_jpeg_scan_batch: the files `blobs` -> `desc[:n]` as entropy_batch leaves them before its scan walk, `scan[:n]` (SCAN
     records), the batch's Huffman tables de-duplicated in `tabs` (TAB records) and every handled file's entropy-coded bytes in `data`
     (u8, room for `cap_bytes`, default all of it).  The host walks no bit stream.  Returns (tables, bytes, blocks) that all files
-    with a supported header need together; a file that did not fit `data` or `tabs` has reason R_NO_SPACE."""
+    with a supported header need together; a file that did not fit `data` or `tabs` has reason R_NO_SPACE.
+    std_tables: avcer_jpeg_scan_batch_ex with AVCER_JPEG_STD_TABLES, as in entropy_batch."""
     n = len(blobs)
-    files = (C.c_char_p * max(n, 1))(*blobs)
-    lens = np.array([len(b) for b in blobs], dtype=np.int64)
+    files, lens, _keep = _file_pointers(blobs)
     cap_b = data.size if cap_bytes is None else int(cap_bytes)
     cap_t = len(tabs) if cap_tabs is None else int(cap_tabs)
     assert data.dtype == np.uint8 and data.flags.c_contiguous and cap_b <= data.size
@@ -94,10 +113,10 @@ def scan_batch(lib, blobs, data: np.ndarray, desc: np.ndarray, scan: np.ndarray,
     assert scan.dtype == SCAN and scan.flags.c_contiguous and len(scan) >= n
     assert tabs.dtype == TAB and tabs.flags.c_contiguous and cap_t <= len(tabs)
     n_tabs, need_bytes, need_blocks = C.c_int32(0), C.c_int64(0), C.c_int64(0)
-    rc = lib.avcer_jpeg_scan_batch(ctx, C.cast(files, C.c_void_p), lens.ctypes.data_as(C.c_void_p), n, data.ctypes.data_as(C.c_void_p),
-                                   cap_b, desc.ctypes.data_as(C.c_void_p), scan.ctypes.data_as(C.c_void_p),
-                                   tabs.ctypes.data_as(C.c_void_p), cap_t, host_threads(int(threads)), C.byref(n_tabs),
-                                   C.byref(need_bytes), C.byref(need_blocks))
+    args = (ctx, C.cast(files, C.c_void_p), lens.ctypes.data_as(C.c_void_p), n, data.ctypes.data_as(C.c_void_p), cap_b,
+            desc.ctypes.data_as(C.c_void_p), scan.ctypes.data_as(C.c_void_p), tabs.ctypes.data_as(C.c_void_p), cap_t, host_threads(int(threads)))
+    outs = (C.byref(n_tabs), C.byref(need_bytes), C.byref(need_blocks))
+    rc = lib.avcer_jpeg_scan_batch_ex(*args, STD_TABLES, *outs) if std_tables else lib.avcer_jpeg_scan_batch(*args, *outs)
     if rc != 0:
         raise RuntimeError(f"avcer_jpeg_scan_batch failed: {rc}")
     return int(n_tabs.value), int(need_bytes.value), int(need_blocks.value)
@@ -261,7 +280,7 @@ def _pil_tile(blob: bytes) -> np.ndarray:
         return np.asarray(img.convert("RGB").resize((224, 224), Image.Resampling.NEAREST))
 
 
-def _to_device(engine, blobs, threads: int):
+def _to_device(engine, blobs, threads: int, std_tables: bool = False):
     """Host entropy pass + copies: (coeffs on the device, desc on the device, n_blocks, desc records on the host)."""
     st = engine.__dict__.setdefault("_jpeg_staging", _Staging())
     n = len(blobs)
@@ -272,7 +291,7 @@ def _to_device(engine, blobs, threads: int):
     while True:
         coeffs = st.coeffs.numpy()
         desc = st.desc.numpy()[:DESC.itemsize * n].view(DESC)
-        need = entropy_batch(engine.lib, blobs, coeffs, desc, threads, engine.ctx)
+        need = entropy_batch(engine.lib, blobs, coeffs, desc, threads, engine.ctx, std_tables=std_tables)
         if not (desc["reason"] == R_NO_SPACE).any():
             break
         st.reserve(need, n)
@@ -291,7 +310,7 @@ def _to_device(engine, blobs, threads: int):
 TABS_ROOM = 64  # tables a batch may carry before the staging is grown: a folder one encoder wrote carries four
 
 
-def _to_device_unpacked(engine, blobs, threads: int, sub_bits: int = 0):
+def _to_device_unpacked(engine, blobs, threads: int, sub_bits: int = 0, std_tables: bool = False):
     """entropy="device": headers on the host (scan_batch; no bit stream is walked), ONE copy of descriptors, scan records, tables
     and entropy-coded bytes, avcer_jpeg_unpack -> (coeffs on the device, desc on the device, n_blocks, desc records on the host as the
     HEADERS left them, status i32 [n] on the device: what the device decode made of every file)."""
@@ -305,7 +324,7 @@ def _to_device_unpacked(engine, blobs, threads: int, sub_bits: int = 0):
         wire = st.reserve_wire(at_data + cap_bytes).numpy()
         desc, scan = wire[:at_scan].view(DESC), wire[at_scan:at_tabs].view(SCAN)
         n_tabs, need_bytes, _ = scan_batch(engine.lib, blobs, wire[at_data:at_data + cap_bytes], desc, scan,
-                                           wire[at_tabs:at_data].view(TAB), threads, engine.ctx)
+                                           wire[at_tabs:at_data].view(TAB), threads, engine.ctx, std_tables=std_tables)
         if not (desc["reason"] == R_NO_SPACE).any():
             break
         cap_bytes, cap_tabs = max(cap_bytes, need_bytes), max(cap_tabs, n_tabs)
@@ -413,6 +432,68 @@ def decode_canvas(engine, blobs, threads: int = 0, entropy: str = "host"):
         canvas[i, :img.shape[0], :img.shape[1]] = torch.from_numpy(img).to(dev)
     rects = np.array([(i, 0, 0, w, h) for i, (w, h) in enumerate(sizes)], dtype=np.int32).reshape(n, 5)
     return (canvas, rects), paths
+
+
+def _pil_frame(blob, i: int, height: int, width: int, bgr: bool) -> np.ndarray:
+    """Frame i through PIL, in the channel order asked for; OSError naming the frame where PIL cannot read it or reads another size."""
+    try:
+        img = _pil_rgb(blob)
+    except Exception as e:  # PIL raises OSError and its subclasses, SyntaxError or ValueError on some broken files
+        raise OSError(f"frame {i}: neither the device path nor PIL can read it ({type(e).__name__}: {e})") from e
+    if img.shape[:2] != (height, width):
+        two = bytes(blob).find(b"\xff\xd8", 2) >= 0 and 2 * img.shape[0] in (height, height - 1, height + 1)
+        why = " -- two SOI markers: interlaced two-field Motion-JPEG (AVI1 field pairs) is not read" if two else ""
+        raise OSError(f"frame {i}: a picture of {img.shape[1]} x {img.shape[0]}, the video is {width} x {height}{why}")
+    return np.ascontiguousarray(img[:, :, ::-1]) if bgr else img
+
+
+def decode_frames(engine, blobs, height: int, width: int, bgr: bool = True, entropy: str = "device", threads: int = 0,
+                  frames_per_pass: int = 64, std_tables: bool = True):
+    """The frames of a Motion-JPEG video (`avi.open_avi(path).frames`, or any n JPEG files of one size; bytes or buffers, nothing
+    is copied in Python) -> (frames u8 [n, height, width, 3] on the device, paths): frame i is
+    Image.open(file i).convert("RGB"), channels flipped with `bgr` (the order cv2 hands the reference, run_inference's frames_bgr);
+    paths[i] is "device" or "pil".  The frames never exist on the host.
+    Works in passes of at most `frames_per_pass` files, so coefficient and plane storage is that of a pass, not of the video; the
+    result does not depend on `frames_per_pass`, `threads` or `entropy` ("device": the Huffman decode runs on the device too,
+    avcer_jpeg_unpack; "host": avcer_jpeg_entropy_batch).  std_tables: a frame without DHT segments is decoded with the standard's
+    annex-K tables (AVCER_JPEG_STD_TABLES), as Motion-JPEG producers mean it.
+    A frame the device path reports -- header refused, flag 1 (range guard), flag 2 (another size) -- goes through PIL, as in
+    decode_canvas; one PIL cannot read either, or reads at another size, raises OSError naming the frame index."""
+    _check_entropy(entropy)
+    n, height, width, per = len(blobs), int(height), int(width), int(frames_per_pass)
+    if height <= 0 or width <= 0 or per <= 0:
+        raise ValueError("decode_frames: height, width and frames_per_pass positive")
+    dev = engine.device
+    frames = torch.empty(n, height, width, 3, dtype=torch.uint8, device=dev)
+    paths = []
+
+    def settle(lo, part, status, wait):
+        """The pass behind the one just queued: its flags are read now, and what the device did not decode goes through PIL."""
+        flagged = wait() if wait is not None else np.ones(len(part), dtype=np.int32)
+        rest = [k for k in range(len(part)) if status[k] != OK or flagged[k]]
+        if rest:
+            host = np.stack([_pil_frame(part[k], lo + k, height, width, bgr) for k in rest])
+            frames[torch.as_tensor([lo + k for k in rest], device=dev)] = torch.from_numpy(host).to(dev)
+        paths.extend("pil" if (status[k] != OK or flagged[k]) else "device" for k in range(len(part)))
+
+    behind = None
+    for lo in range(0, n, per):
+        part = blobs[lo:lo + per]
+        if entropy == "device":
+            c_dev, d_dev, used, desc, refused = _to_device_unpacked(engine, part, threads, std_tables=std_tables)
+        else:
+            c_dev, d_dev, used, desc = _to_device(engine, part, threads, std_tables=std_tables)
+            refused = None
+        wait = None
+        if used:
+            wait = _flags_to_host(engine, engine.jpeg_frames(c_dev, d_dev, len(part), used, height, width, bgr=bgr, out=frames[lo:lo + len(part)])[1],
+                                  refused)
+        if behind is not None:
+            settle(*behind)
+        behind = (lo, part, desc["status"].copy(), wait)
+    if behind is not None:
+        settle(*behind)
+    return frames, paths
 
 
 # ==================================================================================================== encoding

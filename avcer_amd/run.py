@@ -24,6 +24,45 @@ from .fusion import MODEL_ORDER, fuse
 from .video_pipeline import visual_forward
 
 
+def run_inference_file(engine, path, detector=None, detections: Optional[Sequence[np.ndarray]] = None, fps: Optional[float] = None,
+                       frames_per_pass: int = 64, **kw):
+    """`run_inference` on a recording: the reference's first line, `VideoPredictor.process` opening a video file
+    (data/get_face_images.py:19-24, 44-47), for the one container this project reads without a decoder library -- the Motion-JPEG /
+    PCM AVI file that `ffmpeg -i clip.mp4 -c:v mjpeg -q:v 2 -c:a pcm_s16le -ar 44100 -ac 2 clip.avi` writes (avcer_amd/avi.py).
+    open_avi -> jpeg.decode_frames (the frames are decoded on the device and never exist on the host) ->
+    run_inference(engine, frames, avi.pcm, fps, wav_sr=avi.audio_rate, name_video=<stem of path>, **kw).
+    `fps` defaults to int(rate / scale), what int(cv2.CAP_PROP_FPS) gives the reference (get_face_images.py:23).
+    A file without an audio stream raises ValueError unless `wav=` (with `wav_sr=`, or mono at `sr`) is passed; a rate pair the
+    resampler does not cover raises before any decode, as in run_inference; what the container refuses: avi.open_avi.
+    Each frame is PIL's decode of it (libjpeg-turbo), bit for bit; cv2 reads Motion-JPEG through ffmpeg's own decoder and colour
+    conversion, which is not among this project's dependencies and is not claimed.
+    Returns run_inference's dict; `real_time_factor` includes demux and decode."""
+    from . import jpeg
+    from .avi import open_avi
+
+    start_time = time.time()
+    with open_avi(path) as avi:
+        if "wav" in kw:
+            wav, wav_sr = kw.pop("wav"), kw.pop("wav_sr", None)
+        elif avi.pcm is None:
+            raise ValueError(f"{avi.path}: no audio stream (pass wav= and wav_sr= to give the audio some other way)")
+        else:
+            wav, wav_sr = avi.pcm, kw.pop("wav_sr", avi.audio_rate)
+        if wav_sr is not None:
+            resample_plan(wav_sr, kw.get("sr", 16000))
+        check_window(engine, kw.get("window", 4), kw.get("sr", 16000))
+        if detections is None and detector is None:
+            raise ValueError("give a detector or the per-frame detections")
+        fps = int(avi.rate / avi.scale) if fps is None else fps
+        frames, _ = jpeg.decode_frames(engine, avi.frames, avi.height, avi.width, bgr=True, frames_per_pass=frames_per_pass)
+        n_frames = avi.n_frames
+    kw.setdefault("name_video", os.path.splitext(os.path.basename(os.fspath(path)))[0])
+    out = run_inference(engine, frames, wav, fps, detector=detector, detections=detections, wav_sr=wav_sr, **kw)
+    duration = n_frames / fps if (fps and fps > 0 and n_frames > 0) else None
+    out["real_time_factor"] = (time.time() - start_time) / duration if duration else None
+    return out
+
+
 def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections: Optional[Sequence[np.ndarray]] = None,
                   path_save_results: str = "", name_video: str = "video", flag_save_prob: bool = False,
                   weights_prob_model=None, weights_model=(1, 1, 1), ce_weights_type: bool = True, ce_mask: bool = False,

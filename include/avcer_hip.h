@@ -89,7 +89,10 @@ enum {
  *      streams key tiles through LDS) joined under 8 the same way: three more symbols, nothing that existed changed.
  *      avcer_jpeg_roundtrip_tiles, avcer_jpeg_roundtrip_rgb (face crops as the files of stage 0 hold them, without the files)
  *      joined under 8 the same way: two more symbols, the descriptor unchanged.
- *      avcer_bneck_tail (the stage-3 tail kernel on caller tensors, for kernel-level tests) joined under 8 the same way: one more symbol. */
+ *      avcer_bneck_tail (the stage-3 tail kernel on caller tensors, for kernel-level tests) joined under 8 the same way: one more symbol.
+ *      avcer_jpeg_frames, avcer_jpeg_entropy_batch_ex, avcer_jpeg_scan_batch_ex and the flag AVCER_JPEG_STD_TABLES (Motion-JPEG frames
+ *      of an AVI file decoded into the frame batch) joined under 8 the same way: three more symbols, no struct or argument list
+ *      that existed changed. */
 #define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
@@ -459,6 +462,33 @@ int avcer_jpeg_tiles(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_blocks, co
 int avcer_jpeg_rgb(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_blocks, const avcer_jpeg_desc* desc, int n, int32_t* flags,
                    uint8_t* canvas, int hmax, int wmax, avcer_stream_t stream);
 
+/* Motion-JPEG frames: the video stream of an AVI file is a list of baseline JPEG files (avcer_amd/avi.py), decoded by the calls
+ * above and below into the batch the detector and the crop kernels read,
+ *   ref: data/get_face_images.py:19-24, 44-47 (cv2.VideoCapture: the frames of a recording, BGR)
+ * with two additions.  The contract stays bit-identity with PIL's decode of each frame (libjpeg-turbo), tolerance zero; what cv2
+ * would decode of the same stream (ffmpeg's own MJPEG decoder and colour conversion) is not claimed.
+ *
+ * AVCER_JPEG_STD_TABLES (a bit of `hflags`): many Motion-JPEG producers omit the DHT segments; a Huffman table 0 or 1 that the scan
+ *   references and no DHT segment of the file defined is then the table of that class and id of the standard's annex K (K.3 -
+ *   K.6) -- the rule of libjpeg-turbo and of ffmpeg's mjpeg2jpeg filter.  A table the file defines is the file's own; ids 2 and 3
+ *   have no standard table and stay reason 8.  csrc/jpeg.hip holds ONE statement of the four tables, the writer's.
+ * avcer_jpeg_entropy_batch_ex / avcer_jpeg_scan_batch_ex (below, beside avcer_jpeg_scan_batch): avcer_jpeg_entropy_batch /
+ *   avcer_jpeg_scan_batch with `hflags` (0 or AVCER_JPEG_STD_TABLES; any other bit: AVCER_EINVAL); with hflags 0 they ARE those
+ *   calls.  Host code and host pointers, ctx may be NULL.  The calls without the argument do not change: a file without DHT stays
+ *   AVCER_JPEG_NOT_HANDLED, reason 8, through them.  An assumed table reaches avcer_jpeg_unpack as any other: it is in tabs[].
+ * avcer_jpeg_frames: coeffs, n_blocks, desc[n], flags as avcer_jpeg_rgb takes them -> frames u8 [n,H,W,3], frame i = file i, in
+ *   RGB order or, with bgr != 0, in BGR order (what cv2 hands the reference).  EVERY file must be exactly W x H: a file that is
+ *   AVCER_JPEG_OK and of another size gets flags[i] = 2 and a zero frame (flag 2 wins over flag 1); a file that is not OK or
+ *   whose flag is 1 yields a zero frame as in avcer_jpeg_rgb.  Every byte of `frames` is written, none outside; `frames` needs no
+ *   alignment (aligned 16-byte stores along each row, byte stores at a row's two ends).  H, W in 1..65535, n H W < 2^36.
+ *   Three kernels on `stream` -- avcer_jpeg_rgb's first (dequantisation + inverse DCT into the u8 component planes of the context's
+ *   JPEG workspace, 64 bytes per block), the size check, the pixels -- and no synchronisation with the host. */
+#define AVCER_JPEG_STD_TABLES 1
+int avcer_jpeg_entropy_batch_ex(avcer_ctx* ctx, const uint8_t* const* files_host, const int64_t* lens_host, int n, int16_t* coeffs_host,
+                                int64_t cap_blocks, avcer_jpeg_desc* desc_host, int threads, int hflags, int64_t* blocks_needed);
+int avcer_jpeg_frames(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_blocks, const avcer_jpeg_desc* desc, int n, int32_t* flags,
+                      uint8_t* frames, int H, int W, int bgr, avcer_stream_t stream);
+
 /* The other direction: the JPEG wire format between stages 0 and 1 is written by this library as well as read.  The face folders
  * of stage 0 and the heat maps,
  *   ref: data/get_face_images.py:52-63 (cv2.imwrite of every detection's crop), get_prob_video.py:154 (cv2.imwrite of an overlay)
@@ -596,6 +626,11 @@ typedef struct avcer_jpeg_scan {
 int avcer_jpeg_scan_batch(avcer_ctx* ctx, const uint8_t* const* files_host, const int64_t* lens_host, int n, uint8_t* bytes_host,
                           int64_t cap_bytes, avcer_jpeg_desc* desc_host, avcer_jpeg_scan* scan_host, avcer_jpeg_tab* tabs_host, int cap_tabs,
                           int threads, int32_t* n_tabs, int64_t* bytes_needed, int64_t* blocks_needed);
+/* with hflags (AVCER_JPEG_STD_TABLES, "Motion-JPEG frames" above); a video whose encoder optimised its tables per frame carries up
+ * to 4 n distinct tables: size cap_tabs from *n_tabs by the two-call pattern */
+int avcer_jpeg_scan_batch_ex(avcer_ctx* ctx, const uint8_t* const* files_host, const int64_t* lens_host, int n, uint8_t* bytes_host,
+                             int64_t cap_bytes, avcer_jpeg_desc* desc_host, avcer_jpeg_scan* scan_host, avcer_jpeg_tab* tabs_host,
+                             int cap_tabs, int threads, int hflags, int32_t* n_tabs, int64_t* bytes_needed, int64_t* blocks_needed);
 int avcer_jpeg_unpack(avcer_ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const avcer_jpeg_scan* scan, const avcer_jpeg_tab* tabs,
                       int n_tabs, avcer_jpeg_desc* desc, int n, int16_t* coeffs, int64_t n_blocks, int32_t* status, int sub_bits,
                       avcer_stream_t stream);
