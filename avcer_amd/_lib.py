@@ -124,7 +124,9 @@ SIGNATURES = {
                                            C.c_int, C.c_void_p, c_stream]),
     "avcer_cam_render": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double,
                                    C.c_void_p, c_stream]),
-    "avcer_fuse": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+    "avcer_annotate_frames": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                        C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, c_stream]),
+    "avcer_fuse":(C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                              C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_stream]),
     "avcer_fuse_videos": (C.c_int, [c_ctx] + [C.c_void_p] * 8 + [C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
                                     C.c_int, C.c_int] + [C.c_void_p] * 4 + [c_stream]),

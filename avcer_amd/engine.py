@@ -647,6 +647,36 @@ class Engine:
                                                   _ptr(out), self._stream()))
         return out
 
+    def annotate(self, frames, items, masks, table):
+        """The result video's drawing (avcer_annotate_frames): `items` -- annotate.ITEM records sorted by frame, or a list of
+        annotate.outline / fill / mask records -- drawn IN PLACE into frames u8 [n,H,W,3] on the device, one after another per frame,
+        exactly as annotate.draw_numpy draws them; masks u8 [bytes] (the coverage masks back to back; moved to the device if they are
+        not there) and table int [k,3] = offset, width, height per mask (annotate.pack_masks).  Every item is checked on the host
+        first: a frame outside [0, n), x1 < x0 or y1 < y0, a width below 1, a coverage outside 1..255, a mask index or scale out of
+        range raise ValueError naming the item, before any launch.  Returns `frames`."""
+        from . import annotate as an
+
+        if not (torch.is_tensor(frames) and frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and
+                frames.shape[-1] == 3 and frames.is_contiguous()):
+            raise ValueError("annotate: frames must be a contiguous uint8 [n,H,W,3] on the device")
+        n, h, w = (int(v) for v in frames.shape[:3])
+        items = an.as_items(items)
+        table = np.ascontiguousarray(np.asarray(table.cpu() if torch.is_tensor(table) else table, dtype=np.int32).reshape(-1, 3))
+        m_dev = self._dev(masks, torch.uint8).reshape(-1)
+        an.check_items(items, n, table, int(m_dev.numel()))
+        if n == 0 or h == 0 or w == 0:
+            return frames
+        work, n_tiles = an.work_table(items, table, n, h, w)
+        if not len(items) or not n_tiles:
+            return frames
+        n_i, n_w = 12 * len(items), work.size
+        ints = np.concatenate([items.view(np.int32).reshape(-1), work.reshape(-1), table.reshape(-1)])
+        d = torch.from_numpy(ints).to(self.device, non_blocking=True)  # one copy for items, launch plan and mask table
+        self._check(self.lib.avcer_annotate_frames(self.ctx, _ptr(frames), n, h, w, _ptr(d), len(items), _ptr(m_dev) if m_dev.numel() else None,
+                                                   int(m_dev.numel()), _ptr(d[n_i + n_w:]) if len(table) else None, len(table),
+                                                   _ptr(d[n_i:]), len(work), int(n_tiles), self._stream()))
+        return frames
+
     def fuse(self, stat, dyn_logits, aud_mean, n_aud: int, weights_1=None, weights_2=(1, 1, 1),
              ce_weights_type: bool = False, ce_mask: bool = True):
         stat = self._dev(stat, torch.float32)

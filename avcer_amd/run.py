@@ -5,7 +5,8 @@ What the reference does through files -- cv2.VideoCapture frames, JPEG crops und
 wav at 16 kHz, CSV tables when `flag_save_prob` -- is replaced by arrays: decoded BGR frames `[T,H,W,3]` u8 and a mono
 waveform at 16 kHz -- or the source audio as it lies in the WAV file, with its rate (`wav_sr`) -- go in; per-frame predictions
 come out.  Grad-CAM heat maps (`flag_heatmaps`) come back as arrays and are written as JPEG files when a results path is given.
-Plotting is not part of this build.
+The result video (`path_save_video`) is drawn on the device and written as a Motion-JPEG AVI file (avcer_amd/annotate.py); the
+reference's matplotlib plots are not part of this build.
 """
 from __future__ import annotations
 
@@ -36,6 +37,8 @@ def run_inference_file(engine, path, detector=None, detections: Optional[Sequenc
     resampler does not cover raises before any decode, as in run_inference; what the container refuses: avi.open_avi.
     Each frame is PIL's decode of it (libjpeg-turbo), bit for bit; cv2 reads Motion-JPEG through ffmpeg's own decoder and colour
     conversion, which is not among this project's dependencies and is not claimed.
+    `path_save_video=`: the result video (run_inference) with the source's own rate / scale pair and its PCM: the output has the
+    source's timing and sound, sample for sample.
     Returns run_inference's dict; `real_time_factor` includes demux and decode."""
     from . import jpeg
     from .avi import open_avi
@@ -56,7 +59,10 @@ def run_inference_file(engine, path, detector=None, detections: Optional[Sequenc
         fps = int(avi.rate / avi.scale) if fps is None else fps
         frames, _ = jpeg.decode_frames(engine, avi.frames, avi.height, avi.width, bgr=True, frames_per_pass=frames_per_pass)
         n_frames = avi.n_frames
+        timing = (avi.rate, avi.scale)
     kw.setdefault("name_video", os.path.splitext(os.path.basename(os.fspath(path)))[0])
+    if kw.get("path_save_video"):
+        kw.setdefault("video_timing", timing)  # the source's own rate / scale pair, not the rounded fps
     out = run_inference(engine, frames, wav, fps, detector=detector, detections=detections, wav_sr=wav_sr, **kw)
     duration = n_frames / fps if (fps and fps > 0 and n_frames > 0) else None
     out["real_time_factor"] = (time.time() - start_time) / duration if duration else None
@@ -68,7 +74,9 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
                   weights_prob_model=None, weights_model=(1, 1, 1), ce_weights_type: bool = True, ce_mask: bool = False,
                   sr: int = 16000, window: float = 4, step: float = 0.5, padding: str = "mean", mode: int = MODE_DEFAULT,
                   flag_heatmaps: bool = False, model_heatmaps: str = "static", wav_sr: Optional[int] = None,
-                  path_save_faces: Optional[str] = None, jpeg_entropy: str = "host", faces_via_jpeg: bool = False):
+                  path_save_faces: Optional[str] = None, jpeg_entropy: str = "host", faces_via_jpeg: bool = False,
+                  path_save_video: Optional[str] = None, video_model: str = "av", video_quality: int = 90, video_panel: bool = False,
+                  video_timing: Optional[Sequence[int]] = None):
     """engine: an `Engine` with the static, dynamic and audio weights loaded.  frames_bgr u8 [T,H,W,3] as cv2 decodes
     them; wav float32 [L] mono at `sr`; fps as `int(cv2.CAP_PROP_FPS)` gives it (get_face_images.py:23).
     `wav_sr`: `wav` is source audio at that rate instead -- int16 [L] / [L, C] as the frames lie in the WAV file ffmpeg writes
@@ -97,7 +105,17 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
     are then, bit for bit in the same arithmetic mode, those of `preprocess_video_and_predict` on the folder `path_save_faces`
     writes.  Computed on the device without the files (jpeg.roundtrip_tiles); with `path_save_faces` the files are packed from the
     same pass's coefficients, with `flag_heatmaps` the base image is the linear resize of the round-tripped crop
-    (data/utils.py:105).  Off by default: nothing changes then.  Anything but a bool raises ValueError before any work."""
+    (data/utils.py:105).  Off by default: nothing changes then.  Anything but a bool raises ValueError before any work.
+    `path_save_video`: the result video (video/visualization.py, get_visualization.py:40-118) as a Motion-JPEG AVI file at that
+    path, written behind the fusion from what is already on the device (annotate.write_result_video: every record's box, the label
+    "<class>: <p>%" of `video_model`'s prediction on track 00, with `video_panel` a bar per class in the top left corner; JPEG
+    quality `video_quality`); `out["result_video"]` is the path.  The frame rate is `fps` (or `video_timing` = the container's exact
+    (rate, scale) pair); the sound is `wav` when it was given as int16 source audio with `wav_sr`, else there is none.  The
+    drawing is PIL's ImageDraw, bit for bit, not cv2's.  `video_model`: "av", "vs", "vd" or "a"; anything else raises ValueError
+    before any work.  Off by default: nothing changes then."""
+    video_models = [m.lower() for m in MODEL_ORDER]
+    if video_model not in video_models:
+        raise ValueError(f"video_model must be one of {' / '.join(video_models)}, not {video_model!r}")
     if jpeg_entropy not in ("host", "device"):
         raise ValueError(f'jpeg_entropy must be "host" or "device", not {jpeg_entropy!r}')
     check_via_jpeg(faces_via_jpeg)
@@ -205,6 +223,22 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
         out["heatmaps"] = (maps[0].astype(np.int32), maps[1].cpu().numpy())
         if path_save_results:
             hm.write_heatmaps(hm.heatmap_dir(path_save_results, name_video, model_heatmaps), maps[0], maps[1], engine=engine)
+    if path_save_video:
+        from fractions import Fraction
+
+        from .annotate import write_result_video
+
+        if video_timing is None:
+            fr = Fraction(fps).limit_denominator(100000)
+            video_timing = (fr.numerator, fr.denominator)
+        pcm = None
+        if wav_sr is not None:  # source audio as it lay in the file: muxed sample for sample
+            src_wav = wav.cpu().numpy() if torch.is_tensor(wav) else np.asarray(wav)
+            pcm = src_wav if src_wav.dtype == np.int16 else None
+        out["result_video"] = write_result_video(engine, frames, records, out[video_model], out["compound_prob"][video_models.index(video_model)],
+                                                 path_save_video, int(video_timing[0]), int(video_timing[1]), pcm=pcm,
+                                                 audio_rate=int(wav_sr) if pcm is not None else 44100, quality=video_quality,
+                                                 entropy="device", panel=video_panel)
     # "Real-time factor for compound expression prediction" as run.py:304-307 prints it: elapsed / video duration (the
     # device -> host copies above have synchronised the stream, so the clock covers all the work); None where the
     # container reported no frame rate

@@ -92,7 +92,9 @@ enum {
  *      avcer_bneck_tail (the stage-3 tail kernel on caller tensors, for kernel-level tests) joined under 8 the same way: one more symbol.
  *      avcer_jpeg_frames, avcer_jpeg_entropy_batch_ex, avcer_jpeg_scan_batch_ex and the flag AVCER_JPEG_STD_TABLES (Motion-JPEG frames
  *      of an AVI file decoded into the frame batch) joined under 8 the same way: three more symbols, no struct or argument list
- *      that existed changed. */
+ *      that existed changed.
+ *      avcer_annotate_frames (the result video's boxes and labels drawn into the frame batch) and its record struct avcer_draw_item
+ *      joined under 8 the same way: one more symbol. */
 #define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
@@ -389,6 +391,41 @@ int avcer_crop_resize_linear(avcer_ctx* ctx, const uint8_t* frames, int n_frames
                              int swap_rb, int out_h, int out_w, uint8_t* out, avcer_stream_t stream);
 int avcer_cam_render(avcer_ctx* ctx, const float* cam, const int32_t* rows, const int32_t* cls, const uint8_t* base_rgb, int n,
                      const uint8_t* lut_bgr, double image_weight, uint8_t* out_bgr, avcer_stream_t stream);
+
+/* The drawing of the result video (video/functions/get_visualization.py:40-118: face boxes and "<label>: <p>%" lines on every
+ * frame), in place in the frame batch on the device.  The claim is identity with PIL's ImageDraw, tolerance zero (avcer_amd/annotate.py
+ * draw_numpy is the statement both sides are held to); cv2's anti-aliased lines and Hershey font are NOT reproduced.
+ * One record per drawn item, 12 x int32: */
+enum { AVCER_DRAW_OUTLINE = 0, AVCER_DRAW_FILL = 1, AVCER_DRAW_MASK = 2 };
+typedef struct avcer_draw_item {
+    int32_t frame;     /* which frame of the batch, 0 .. n-1 */
+    int32_t kind;      /* AVCER_DRAW_* */
+    int32_t x0, y0;    /* OUTLINE, FILL: first corner (inclusive); MASK: where the mask's top left pixel goes */
+    int32_t x1, y1;    /* OUTLINE, FILL: last corner (inclusive), x1 >= x0 and y1 >= y0; MASK: unused */
+    int32_t arg;       /* OUTLINE: border width t >= 1; FILL: coverage 1..255; MASK: integer scale k >= 1 */
+    int32_t mask;      /* MASK: index into the mask table; else unused */
+    int32_t colour[3]; /* 0..255 each, in the frame's own channel order (the kernel does not know BGR from RGB) */
+    int32_t pad;
+} avcer_draw_item;
+/*   OUTLINE = ImageDraw.rectangle((x0,y0,x1,y1), outline=colour, width=t): rows y0 .. y0+t-1 and y1-t+1 .. y1 over x0 .. x1, and
+ *     columns x0 .. x0+t-1 and x1-t+1 .. x1 between them; the border grows inward and the box is solid once 2t reaches a side (PIL
+ *     lets the rows run past the box when t exceeds its height, and so does this).
+ *   FILL = ImageDraw.bitmap((x0,y0), Image.new("L", (x1-x0+1, y1-y0+1), c), fill=colour): a rectangle of constant coverage.
+ *   MASK = ImageDraw.bitmap((x0,y0), mask.resize((k*w, k*h), NEAREST), fill=colour): coverage masks[offset + (dy/k)*w + dx/k] with
+ *     (offset, w, h) = table[3*mask ..]; the masks are u8 and lie back to back in `masks` (masks_bytes in all).
+ *   Blend, per channel, PIL's BLEND8: t = dst*(255-c) + colour*c + 128, dst = ((t >> 8) + t) >> 8 (the sum rounded once).
+ * Everything is clipped to its frame; an item wholly outside draws nothing; nothing outside `frames` u8 [n,h,w,3] is written, and
+ * pixels no item covers are neither read nor written.
+ * Order: `items` [m] are sorted by frame, and a frame's result is that of drawing its items one after another in list order,
+ * whatever their overlap.  One thread owns one pixel and walks the frame's items; the launch is laid out by `work`, int32
+ * [n_work, 8] sorted by frame, one row per frame that has items: frame, first item, one past its last item, x and y of the top left
+ * pixel of the area its items cover (clipped to the frame), 64-pixel tiles per row of that area, the number of 64 x 4 tiles of all
+ * rows before this one, 0.  n_tiles = the tiles of all rows.  avcer_amd/annotate.py work_table builds it.  items, masks, table and
+ * work are DEVICE pointers; the caller has checked the items (Engine.annotate raises ValueError naming the item).  A record that
+ * is out of range all the same is skipped by the kernel, never followed.  m = 0 or n_tiles = 0: nothing is launched. */
+int avcer_annotate_frames(avcer_ctx* ctx, uint8_t* frames, int n, int h, int w, const avcer_draw_item* items, int m, const uint8_t* masks,
+                          int64_t masks_bytes, const int32_t* table, int n_masks, const int32_t* work, int n_work, int64_t n_tiles,
+                          avcer_stream_t stream);
 
 /* The face tracker between detector and tiles, for a whole video in ONE call -- HOST code and HOST pointers (the tracker is
  * sequential in time and sees a handful of boxes per frame; the reference runs it on the host too):
