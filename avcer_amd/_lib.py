@@ -87,6 +87,11 @@ SIGNATURES = {
     "avcer_track_faces": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                                     C.c_void_p, C.POINTER(C.c_int64)]),
     "avcer_lsap": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "avcer_tracker_create": (C.c_void_p, [C.c_double, C.c_double]),
+    "avcer_tracker_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p,
+                                     C.POINTER(C.c_int64)]),
+    "avcer_tracker_last_error": (C.c_char_p, [C.c_void_p]),
+    "avcer_tracker_destroy": (None, [C.c_void_p]),
     "avcer_jpeg_probe": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "avcer_jpeg_entropy_batch": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
                                            C.POINTER(C.c_int64)]),

@@ -2,7 +2,7 @@
 "<label>: <p>%" line drawn on every frame, on the device, and the frames written as a Motion-JPEG AVI file.
 
 decode -> draw -> encode: `jpeg.decode_frames` left the frames on the device, `draw` (avcer_annotate_frames, csrc/annotate.hip) draws
-into a copy of them there, the JPEG encoder turns the copy into files, and only file bytes cross to the host (`avi.write_avi`).
+into a copy of them there, the JPEG encoder turns the copy into files, and only file bytes cross to the host (`avi.AviWriter`).
 
 The reference draws with cv2 (LINE_AA rectangles, the Hershey font).  cv2 is not among this project's dependencies; as everywhere
 else the claim is identity with PIL, here `ImageDraw`, with tolerance zero -- `draw_numpy` is the statement the kernel and PIL are
@@ -359,45 +359,70 @@ def write_result_video(engine, frames, records, pred, prob, path, rate, scale=1,
                        entropy="device", frames_per_pass=64, bgr=True, font=None, panel=False):
     """The result video of `frames` (uint8 [T, H, W, 3], on the device or moved there; BGR unless bgr=False) as the Motion-JPEG AVI
     file `path` at `rate` / `scale` frames per second, with `pcm` (int16 [L] / [L, C] at `audio_rate`) as its sound: `layout(records,
-    pred, prob, H, W, font, panel)` drawn on every frame.  In passes of `frames_per_pass`: the pass is copied into a scratch buffer
-    of the engine (the caller's frames are never modified), drawn there (`draw`), encoded as whole-frame rectangles
-    (jpeg._plan_to_device / Engine.jpeg_forward / jpeg.files_from_coeffs: the files are PIL's `save(quality=quality,
-    subsampling=subsampling)` of the drawn frames, byte for byte, under both `entropy` values) and the files are collected; then
-    avi.write_avi.  The device holds one pass of copies and coefficients at a time; only file bytes cross to the host.  What
-    write_avi refuses (more than 1 GiB) propagates, and no partial file is left.  Returns `path`."""
+    pred, prob, H, W, font, panel)` drawn on every frame.  `frames` may also be a frame SOURCE -- a callable returning an iterator, or
+    an iterator, of device passes uint8 [k, H, W, 3] in frame order (run_inference_file's streamed call decodes the file a second
+    time this way) -- so that the video never has to exist as one tensor; the file is the same.  In passes of `frames_per_pass`:
+    the pass is copied into a scratch buffer of the engine (the caller's frames are never modified), drawn there (`draw`), encoded
+    as whole-frame rectangles (jpeg._plan_to_device / Engine.jpeg_forward / jpeg.files_from_coeffs: the files are PIL's
+    `save(quality=quality, subsampling=subsampling)` of the drawn frames, byte for byte, under both `entropy` values) and appended
+    to the file (avi.AviWriter; the header is patched at the end).  The device holds one pass of copies and coefficients at a time;
+    only file bytes cross to the host, and the host keeps the index alone.  What AviWriter refuses (a file past 4 GiB: OSError)
+    propagates, and no partial file is left, whatever the failure.  Returns `path`."""
     import torch
 
     from . import jpeg
-    from .avi import write_avi
+    from .avi import AviWriter
 
     jpeg._check_entropy(entropy)
     if int(frames_per_pass) < 1:
         raise ValueError("frames_per_pass must be at least 1")
-    src = frames if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames))
-    if src.dim() != 4 or src.shape[-1] != 3 or src.dtype != torch.uint8:
-        raise ValueError("frames must be uint8 [T, H, W, 3]")
-    total, height, width = (int(v) for v in src.shape[:3])
-    items, masks = layout(records, pred, prob, height, width, font, panel)
-    flat, table = pack_masks(masks)
-    check_items(items, max(total, 1), table, len(flat))
-    flat_d = torch.from_numpy(flat).to(engine.device)
-    per = height * width * 3
-    fpp = min(int(frames_per_pass), max(total, 1))
-    scratch = engine.__dict__.get("_annotate_scratch")
-    if scratch is None or scratch.numel() < fpp * per:
-        scratch = engine.__dict__["_annotate_scratch"] = torch.empty(fpp * per, dtype=torch.uint8, device=engine.device)
-    blobs = []
-    for lo in range(0, total, fpp):
-        k = min(fpp, total - lo)
-        buf = scratch[:k * per].view(k, height, width, 3)
-        buf.copy_(src[lo:lo + k], non_blocking=True)
-        sel = items[(items["frame"] >= lo) & (items["frame"] < lo + k)].copy()
-        sel["frame"] -= lo
-        engine.annotate(buf, sel, flat_d, table)
-        rects = np.zeros((k, 5), dtype=np.int32)
-        rects[:, 0], rects[:, 3], rects[:, 4] = np.arange(k), width, height
-        src_d, r_dev, d_dev, host, n, blocks, _ = jpeg._plan_to_device(engine, buf, rects, quality, subsampling)
-        coeffs = engine.jpeg_forward(src_d, r_dev, d_dev, n, blocks, bgr=bgr)
-        blobs.extend(jpeg.files_from_coeffs(engine, coeffs, d_dev, host, 0, entropy))
-        del coeffs
-    return write_avi(path, blobs, rate, scale, pcm, audio_rate)
+    if callable(frames) or (hasattr(frames, "__next__") and not torch.is_tensor(frames)):
+        source, whole = iter(frames() if callable(frames) else frames), False
+    else:
+        src = frames if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames))
+        if src.dim() != 4 or src.shape[-1] != 3 or src.dtype != torch.uint8:
+            raise ValueError("frames must be uint8 [T, H, W, 3]")
+        source, whole = iter((src,)), True
+    writer, state, lo = None, None, 0
+    try:
+        for part in source:
+            if part.dim() != 4 or part.shape[-1] != 3 or part.dtype != torch.uint8:
+                raise ValueError("frames must be uint8 [T, H, W, 3]")
+            if state is None:
+                height, width = int(part.shape[1]), int(part.shape[2])
+                items, masks = layout(records, pred, prob, height, width, font, panel)
+                flat, table = pack_masks(masks)
+                # a source's length is not known in front: its items are held to the last frame they name
+                check_items(items, max(int(part.shape[0]), 1) if whole else int(items["frame"].max()) + 1 if len(items) else 1, table, len(flat))
+                state = (items, torch.from_numpy(flat).to(engine.device), table)
+                writer = AviWriter(path, width, height, rate, scale, audio_rate, pcm=pcm)
+            elif (int(part.shape[1]), int(part.shape[2])) != (height, width):
+                raise ValueError(f"a pass of {int(part.shape[2])} x {int(part.shape[1])} frames behind {width} x {height}")
+            items, flat_d, table = state
+            per = height * width * 3
+            fpp = min(int(frames_per_pass), max(int(part.shape[0]), 1))
+            scratch = engine.__dict__.get("_annotate_scratch")
+            if scratch is None or scratch.numel() < fpp * per:
+                scratch = engine.__dict__["_annotate_scratch"] = torch.empty(fpp * per, dtype=torch.uint8, device=engine.device)
+            for at in range(0, int(part.shape[0]), fpp):
+                k = min(fpp, int(part.shape[0]) - at)
+                buf = scratch[:k * per].view(k, height, width, 3)
+                buf.copy_(part[at:at + k], non_blocking=True)
+                sel = items[(items["frame"] >= lo) & (items["frame"] < lo + k)].copy()
+                sel["frame"] -= lo
+                engine.annotate(buf, sel, flat_d, table)
+                rects = np.zeros((k, 5), dtype=np.int32)
+                rects[:, 0], rects[:, 3], rects[:, 4] = np.arange(k), width, height
+                src_d, r_dev, d_dev, host, n, blocks, _ = jpeg._plan_to_device(engine, buf, rects, quality, subsampling)
+                coeffs = engine.jpeg_forward(src_d, r_dev, d_dev, n, blocks, bgr=bgr)
+                writer.add_frames(jpeg.files_from_coeffs(engine, coeffs, d_dev, host, 0, entropy))
+                del coeffs
+                lo += k
+            del part
+        if writer is None:
+            raise ValueError("write_avi: no frame")
+        return writer.close()
+    except BaseException:
+        if writer is not None:
+            writer.__exit__(Exception)
+        raise

@@ -152,20 +152,33 @@ def check_window(engine: Engine, window: float, sr: int) -> int:
 
 
 def audio_forward(engine: Engine, wav: torch.Tensor, sr: int = 16000, fps: float = 25, window: float = 4,
-                  step: float = 0.5, padding: str = "mean", mode: int = MODE_DEFAULT, wav_sr: int | None = None):
+                  step: float = 0.5, padding: str = "mean", mode: int = MODE_DEFAULT, wav_sr: int | None = None,
+                  windows_per_pass: int | None = None):
     """wav f32 [L] (mono, already at `sr`); or, with `wav_sr` given, source audio at `wav_sr` as Engine.resample takes it (int16
     [L] / [L, C] or float32 [L] / [C, L]), brought to mono at `sr` on the device first (data/utils.py:50-57).
     Returns (window_logits [n_win, C], frame_lo [n_win], frame_hi [n_win]).
     An empty tail window (len(wav) % (step*sr) == 0) yields NaN logits, as in the reference ('mean' padding of an
-    empty chunk is NaN, data/utils.py:76-82)."""
+    empty chunk is NaN, data/utils.py:76-82).
+    `windows_per_pass`: the windows go through Engine.audio_chunks / Engine.audio_forward in groups of that many and the logits are
+    concatenated -- the same logits, with the chunk buffer and the model's workspace those of a group (None: one call for all)."""
     if padding not in ("mean", "constant", "repeat"):
         raise ValueError(f"padding={padding!r}")
+    if windows_per_pass is not None and (isinstance(windows_per_pass, bool) or not isinstance(windows_per_pass, (int, np.integer))
+                                         or windows_per_pass < 1):
+        raise ValueError(f"audio_windows_per_pass must be an integer >= 1, not {windows_per_pass!r}")
     check_window(engine, window, sr)
     wav = wav.reshape(-1) if wav_sr is None else engine.resample(wav, wav_sr, sr)
     starts, ends, lo, hi = chunk_spans(int(wav.numel()), sr, fps, window, step)
-    chunks = engine.audio_chunks(wav, starts, ends, int(window * sr), padding)
-    logits = engine.audio_forward(chunks, normalize=True, mode=mode)
-    return logits, lo, hi
+    if windows_per_pass is None or len(starts) <= windows_per_pass:
+        chunks = engine.audio_chunks(wav, starts, ends, int(window * sr), padding)
+        logits = engine.audio_forward(chunks, normalize=True, mode=mode)
+        return logits, lo, hi
+    parts = []
+    for a in range(0, len(starts), int(windows_per_pass)):
+        b = a + int(windows_per_pass)
+        chunks = engine.audio_chunks(wav, starts[a:b], ends[a:b], int(window * sr), padding)
+        parts.append(engine.audio_forward(chunks, normalize=True, mode=mode))
+    return torch.cat(parts), lo, hi
 
 
 def replicate_per_frame(logits: np.ndarray, lo, hi):

@@ -11,7 +11,9 @@ Everything else is refused with a ValueError that names the file and the reason,
 another audio format, a second video stream, OpenDML (files past 1 GiB: `AVIX` segments, `indx` / `ix##` indexes), a chunk that
 runs past the end of the file.  H.264 / MP4 is out of reach without a codec library and is not pretended.
 
-`write_avi` is the inverse (tests, tools/avi_bench.py, users who want the format).
+`write_avi` is the inverse (tests, tools/avi_bench.py, users who want the format); `AviWriter` is the same file written as the frames
+come (the result video of a recording that is never whole in memory): chunks appended, the header sizes and `idx1` patched at
+close.  Plain AVI only, below 4 GiB: OpenDML (`AVIX`) is neither read nor written.
 """
 from __future__ import annotations
 
@@ -254,10 +256,7 @@ def build_avi(jpeg_blobs: Sequence, rate: int, scale: int = 1, pcm: Optional[np.
     width, height = jpeg_size(first)
     n = len(blobs)
     if pcm is not None:
-        pcm = np.asarray(pcm)
-        if pcm.dtype != np.int16 or pcm.ndim not in (1, 2):
-            raise ValueError("write_avi: pcm int16 [L] or [L, C]")
-        pcm = np.ascontiguousarray(pcm.reshape(len(pcm), -1)).astype("<i2", copy=False)
+        pcm = _as_pcm(pcm)
     vs, as_ = (1, 0) if (audio_first and pcm is not None) else (0, 1)
     vid, aud = b"%02ddc" % vs, b"%02dwb" % as_
     movi, entries = [b"movi"], []
@@ -287,19 +286,9 @@ def build_avi(jpeg_blobs: Sequence, rate: int, scale: int = 1, pcm: Optional[np.
                 put(aud, pcm[lo:hi].tobytes())
     movi_body = b"".join(movi)
     biggest = max(len(b) for b in blobs)
-    strl_v = _list(b"strl", _chunk(b"strh", struct.pack("<4s4sIHHIIIIIIIIhhhh", b"vids", b"MJPG", 0, 0, 0, 0, scale, rate, 0, n, biggest,
-                                                        0xFFFFFFFF, 0, 0, 0, width, height)) +
-                   _chunk(b"strf", struct.pack("<IiiHH4sIiiII", 40, width, height, 1, 24, b"MJPG", width * height * 3, 0, 0, 0, 0)) + bytes(strl_extra))
-    lists = [strl_v]
-    if pcm is not None:
-        ch = pcm.shape[1]
-        strl_a = _list(b"strl", _chunk(b"strh", struct.pack("<4s4sIHHIIIIIIIIhhhh", b"auds", b"\1\0\0\0", 0, 0, 0, 0, 1, audio_rate, 0, len(pcm),
-                                                            0, 0xFFFFFFFF, 2 * ch, 0, 0, 0, 0)) +
-                       _chunk(b"strf", struct.pack("<HHIIHH", WAVE_FORMAT_PCM, ch, audio_rate, audio_rate * 2 * ch, 2 * ch, 16)))
-        lists = [strl_a, strl_v] if vs == 1 else [strl_v, strl_a]
-    avih = _chunk(b"avih", struct.pack("<14I", max(1, 1000000 * scale // rate), 0, 0, (AVIF_HASINDEX if index else 0) | AVIF_ISINTERLEAVED, n, 0,
-                                       len(lists), biggest, width, height, 0, 0, 0, 0))
-    body = _list(b"hdrl", avih + b"".join(lists)) + b"LIST" + struct.pack("<I", len(movi_body)) + movi_body
+    hdrl = _hdrl(n, biggest, width, height, rate, scale, None if pcm is None else (len(pcm), pcm.shape[1]), audio_rate, index,
+                 audio_first=vs == 1, strl_extra=bytes(strl_extra))
+    body = hdrl + b"LIST" + struct.pack("<I", len(movi_body)) + movi_body
     if len(movi_body) & 1:
         body += b"\0"
     if index:
@@ -309,13 +298,195 @@ def build_avi(jpeg_blobs: Sequence, rate: int, scale: int = 1, pcm: Optional[np.
     return _list(b"AVI ", body, b"RIFF")
 
 
+def _hdrl(n: int, biggest: int, width: int, height: int, rate: int, scale: int, sound, audio_rate: int, index: bool,
+          audio_first: bool = False, strl_extra: bytes = b"") -> bytes:
+    """The `hdrl` list of a file of `n` frames, the largest of `biggest` bytes; `sound` = (sample frames, channels) or None.  Its
+    length does not depend on `n`, `biggest` or the sample count: AviWriter writes it once with zeros and once more at close."""
+    strl_v = _list(b"strl", _chunk(b"strh", struct.pack("<4s4sIHHIIIIIIIIhhhh", b"vids", b"MJPG", 0, 0, 0, 0, scale, rate, 0, n, biggest,
+                                                        0xFFFFFFFF, 0, 0, 0, width, height)) +
+                   _chunk(b"strf", struct.pack("<IiiHH4sIiiII", 40, width, height, 1, 24, b"MJPG", width * height * 3, 0, 0, 0, 0)) + strl_extra)
+    lists = [strl_v]
+    if sound is not None:
+        length, ch = sound
+        strl_a = _list(b"strl", _chunk(b"strh", struct.pack("<4s4sIHHIIIIIIIIhhhh", b"auds", b"\1\0\0\0", 0, 0, 0, 0, 1, audio_rate, 0, length,
+                                                            0, 0xFFFFFFFF, 2 * ch, 0, 0, 0, 0)) +
+                       _chunk(b"strf", struct.pack("<HHIIHH", WAVE_FORMAT_PCM, ch, audio_rate, audio_rate * 2 * ch, 2 * ch, 16)))
+        lists = [strl_a, strl_v] if audio_first else [strl_v, strl_a]
+    avih = _chunk(b"avih", struct.pack("<14I", max(1, 1000000 * scale // rate), 0, 0, (AVIF_HASINDEX if index else 0) | AVIF_ISINTERLEAVED, n, 0,
+                                       len(lists), biggest, width, height, 0, 0, 0, 0))
+    return _list(b"hdrl", avih + b"".join(lists))
+
+
+# A plain AVI file is one RIFF form, and a RIFF size is 32 bits: the whole file stays below 4 GiB.  (ffmpeg changes to OpenDML
+# past 1 GiB already; neither side of this module speaks it.)  A module constant so that a test can lower it.
+AVI_MAX_BYTES = (1 << 32) - 1
+
+
+def _as_pcm(pcm) -> np.ndarray:
+    pcm = np.asarray(pcm)
+    if pcm.dtype != np.int16 or pcm.ndim not in (1, 2):
+        raise ValueError("write_avi: pcm int16 [L] or [L, C]")
+    return np.ascontiguousarray(pcm.reshape(len(pcm), -1)).astype("<i2", copy=False)
+
+
+class AviWriter:
+    """`write_avi` for frames that arrive in pieces: `add_frames(blobs)` appends one `00dc` chunk per JPEG file (an empty one is a
+    dropped frame) as it comes, `close()` appends the `idx1` index and writes the header once more with the frame count, the
+    largest frame and the list sizes -- the file is then, byte for byte, what `write_avi` writes from the same blobs and PCM, however
+    they were cut into calls.  Only the index (16 bytes per chunk) is kept in memory.
+
+    The sound is needed UP FRONT, as `pcm=` here or through `set_pcm(pcm)` before the first frame (int16 [L] / [L, C] at
+    `audio_rate`; `channels`, when given, must be its channel count): every frame is followed by the samples of its own duration,
+    and whether there is an audio stream decides the header's length.  The last frame takes the samples that are left, so the
+    audio chunk of the newest frame is written when the next frame arrives, or at close.
+
+    A plain AVI file cannot pass 4 GiB (AVI_MAX_BYTES): when an append would take the finished file -- the sound still owed and the
+    index included -- past it, OSError names the limit and the partial file is removed; so is the file of a writer that is closed
+    without one non-empty frame (ValueError), or left through an exception of its `with` block.  OpenDML is not written."""
+
+    def __init__(self, path, width: int, height: int, rate: int, scale: int = 1, audio_rate: int = 44100, channels: Optional[int] = None,
+                 pcm: Optional[np.ndarray] = None, index: bool = True):
+        self.path = path
+        self.width, self.height, self.rate, self.scale = int(width), int(height), int(rate), int(scale)
+        if self.rate <= 0 or self.scale <= 0:
+            raise ValueError("write_avi: rate and scale positive")
+        if self.width <= 0 or self.height <= 0:
+            raise ValueError("write_avi: width and height positive")
+        self.audio_rate, self.channels, self.index = int(audio_rate), channels, bool(index)
+        self.n_frames = 0
+        self._pcm = None
+        self._file = None
+        self._entries = []
+        self._biggest = 0
+        self._seen = False   # a non-empty frame has been written
+        self._at = 4         # idx1 offsets count from the 'movi' fourcc
+        self._closed = False
+        if pcm is not None:
+            self.set_pcm(pcm)
+
+    def set_pcm(self, pcm):
+        if self._file is not None or self._closed:
+            raise ValueError("AviWriter: the sound must be set before the first frame (the header's length depends on it)")
+        pcm = _as_pcm(pcm)
+        if self.channels is not None and int(self.channels) != pcm.shape[1]:
+            raise ValueError(f"AviWriter: pcm of {pcm.shape[1]} channels, channels={self.channels}")
+        self._pcm = pcm
+
+    def _sound(self):
+        return None if self._pcm is None else (len(self._pcm), self._pcm.shape[1])
+
+    def _open(self):
+        self._file = open(self.path, "wb")
+        hdrl = _hdrl(0, 0, self.width, self.height, self.rate, self.scale, self._sound(), self.audio_rate, self.index)
+        self._file.write(b"RIFF\0\0\0\0AVI " + hdrl + b"LIST\0\0\0\0movi")
+        self._movi = 12 + len(hdrl) + 8  # the file offset of the 'movi' fourcc
+
+    def _fail(self, error):
+        self._closed = True
+        if self._file is not None:
+            self._file.close()
+            self._file = None
+            try:
+                os.remove(self.path)
+            except OSError:
+                pass
+        return error
+
+    def _span(self, k: int, last: bool):
+        """The samples behind frame k: about its duration's worth; the last frame takes what is left."""
+        size = len(self._pcm)
+        lo = min(size, k * self.audio_rate * self.scale // self.rate)
+        hi = size if last else min(size, (k + 1) * self.audio_rate * self.scale // self.rate)
+        return lo, hi
+
+    def _put(self, cc: bytes, body, flags: int):
+        size = len(body)
+        self._entries.append(cc + struct.pack("<III", flags, self._at, size))
+        self._file.write(cc + struct.pack("<I", size))
+        self._file.write(body)
+        if size & 1:
+            self._file.write(b"\0")
+        self._at += 8 + size + (size & 1)
+
+    def _put_sound(self, k: int, last: bool):
+        if self._pcm is not None:
+            lo, hi = self._span(k, last)
+            if hi > lo:
+                self._put(b"01wb", self._pcm[lo:hi].tobytes(), AVIIF_KEYFRAME)
+
+    def _room(self, size: int):
+        """Refuses (OSError) the append of a video chunk of `size` bytes when the file, finished right behind it, would pass the limit."""
+        owed = 0
+        if self._pcm is not None:  # everything from the newest frame's first sample on is still to be written, in at most ...
+            left = 2 * self._pcm.shape[1] * (len(self._pcm) - self._span(max(self.n_frames - 1, 0), False)[0])
+            owed = left + 9 * 2  # ... two chunks (that frame's, and the new last frame's)
+        index = 8 + 16 * (len(self._entries) + 3) if self.index else 0
+        end = self._movi + self._at + 8 + size + 1 + owed + 1 + index
+        if end > AVI_MAX_BYTES:
+            raise self._fail(OSError(f"{self.path}: frame {self.n_frames} would take the file to {end} bytes, past the {AVI_MAX_BYTES} bytes "
+                                     "(4 GiB) a plain AVI file can have; OpenDML is not written"))
+
+    def add_frames(self, blobs: Sequence):
+        """One video chunk per item of `blobs` (bytes-like; empty: a dropped frame), behind the frames already written."""
+        if self._closed:
+            raise ValueError("AviWriter: closed")
+        for blob in blobs:
+            if self._file is None:
+                self._open()
+            self._room(len(blob))
+            if self.n_frames:
+                self._put_sound(self.n_frames - 1, False)
+            self._put(b"00dc", blob, AVIIF_KEYFRAME if len(blob) else 0)
+            self._biggest = max(self._biggest, len(blob))
+            self._seen = self._seen or len(blob) > 0
+            self.n_frames += 1
+        return self
+
+    def close(self):
+        """The last frame's sound, the index, the header with its final counts.  Returns `path`."""
+        if self._closed:
+            return self.path
+        if not self._seen:
+            raise self._fail(ValueError("write_avi: no frame"))
+        f = self._file
+        self._put_sound(self.n_frames - 1, True)
+        if self._at & 1:  # (cannot happen, every chunk is padded; build_avi says the same)
+            f.write(b"\0")
+        if self.index:
+            body = b"".join(self._entries)
+            f.write(b"idx1" + struct.pack("<I", len(body)) + body)
+        end = f.tell()
+        hdrl = _hdrl(self.n_frames, self._biggest, self.width, self.height, self.rate, self.scale, self._sound(), self.audio_rate, self.index)
+        f.seek(0)
+        f.write(b"RIFF" + struct.pack("<I", end - 8) + b"AVI " + hdrl + b"LIST" + struct.pack("<I", self._at))
+        f.close()
+        self._file, self._closed = None, True
+        return self.path
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, kind, *exc):
+        if kind is None:
+            self.close()
+        elif not self._closed:
+            self._fail(None)
+
+
 def write_avi(path, jpeg_blobs: Sequence, rate: int, scale: int = 1, pcm: Optional[np.ndarray] = None, audio_rate: int = 44100,
               index: bool = True):
     """Writes the Motion-JPEG AVI file `path`: one `00dc` chunk per JPEG file of `jpeg_blobs` (an empty one is a dropped frame)
     at `rate` / `scale` frames per second, `pcm` (int16 [L] or [L, C] at `audio_rate`) as stream 01, interleaved in chunks of about
     one video frame's duration, and an `idx1` index when asked.  `open_avi` of the file gives the same bytes and the same samples.
+    One AviWriter fed everything at once: the picture size is the first frame's own, and a file past 4 GiB is its OSError.
     Returns `path`."""
-    data = build_avi(jpeg_blobs, rate, scale, pcm, audio_rate, index)
-    with open(path, "wb") as f:
-        f.write(data)
+    first = next((b for b in jpeg_blobs if len(b)), None)
+    if first is None:
+        raise ValueError("write_avi: no frame")
+    rate, scale = int(rate), int(scale)
+    if rate <= 0 or scale <= 0:
+        raise ValueError("write_avi: rate and scale positive")
+    width, height = jpeg_size(first)
+    with AviWriter(path, width, height, rate, scale, audio_rate, pcm=pcm, index=index) as w:
+        w.add_frames(jpeg_blobs)
     return path

@@ -16,7 +16,10 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstdarg>
+#include <cstdio>
 #include <limits>
+#include <new>
 #include <numeric>
 
 namespace {
@@ -219,20 +222,51 @@ extern "C" int avcer_lsap(int nr, int nc, const double* cost, int32_t* rows, int
     return AVCER_OK;
 }
 
-extern "C" int avcer_track_faces(avcer_ctx* ctx, const float* dets, int ld, const int32_t* counts, int n_frames, int frame_w,
-                                 int frame_h, double iou_threshold, double minimum_face_size, int64_t* records, int64_t* n_records) {
-    // ctx may be NULL (host-only call, no device needed): errors then come back as the code alone
-    if (!counts || !records || !n_records || n_frames < 0 || ld < 4 || frame_w <= 0 || frame_h <= 0)
-        return set_err(ctx, AVCER_EINVAL, "track_faces: bad arguments");
+// The resumable form: what one video's tracker carries from one push to the next -- the live tracklets (boxes, areas, ids; empty
+// after a frame without faces, which is the whole "dropped on an empty frame" state) and the tracklet counter -- behind an opaque
+// handle, plus the text of its last error (there is no context on this path).
+struct avcer_tracker {
     Tracker tr;
-    tr.iou_threshold = iou_threshold;
-    tr.minimum_face_size = minimum_face_size;
+    bool failed = false;
+    char err[256] = {0};
+};
+
+static int tracker_err(avcer_tracker* h, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(h->err, sizeof(h->err), fmt, ap);
+    va_end(ap);
+    h->failed = true;
+    return AVCER_EINVAL;
+}
+
+extern "C" avcer_tracker* avcer_tracker_create(double iou_threshold, double minimum_face_size) {
+    avcer_tracker* h = new (std::nothrow) avcer_tracker;
+    if (h) {
+        h->tr.iou_threshold = iou_threshold;
+        h->tr.minimum_face_size = minimum_face_size;
+    }
+    return h;
+}
+
+extern "C" void avcer_tracker_destroy(avcer_tracker* h) { delete h; }
+
+extern "C" const char* avcer_tracker_last_error(const avcer_tracker* h) { return h ? h->err : ""; }
+
+extern "C" int avcer_tracker_push(avcer_tracker* h, const float* dets, int ld, const int32_t* counts, int n_frames, int64_t first_frame,
+                                  int frame_w, int frame_h, int64_t* records, int64_t* n_records) {
+    if (!h) return AVCER_EINVAL;
+    if (h->failed) return AVCER_EINVAL;  // the text of the first error stands: the tracklets behind it are not a video's any more
+    if (!counts || !records || !n_records || n_frames < 0 || first_frame < 0 || ld < 4 || frame_w <= 0 || frame_h <= 0)
+        return tracker_err(h, "track_faces: bad arguments");
+    Tracker& tr = h->tr;
     std::vector<int> tids;
     size_t row = 0;
     int64_t n_out = 0;
     for (int t = 0; t < n_frames; ++t) {
         const int n = counts[t];
-        if (n < 0 || (n > 0 && !dets)) return set_err(ctx, AVCER_EINVAL, "track_faces: frame %d has %d detections", t, n);
+        const long long frame = (long long)first_frame + t;
+        if (n < 0 || (n > 0 && !dets)) return tracker_err(h, "track_faces: frame %lld has %d detections", frame, n);
         const float* fb = dets ? dets + row * (size_t)ld : nullptr;
         tr.step(fb, ld, n, tids);
         for (int r = 0; r < n; ++r) {
@@ -241,15 +275,27 @@ extern "C" int avcer_track_faces(avcer_ctx* ctx, const float* dets, int ld, cons
             slice_range(f2i(b[0]), f2i(b[2]), frame_w, x0, x1);
             slice_range(f2i(b[1]), f2i(b[3]), frame_h, y0, y1);
             if (tids[r] == 0)
-                return set_err(ctx, AVCER_EINVAL, "frame %d: a zero-area detection has no track id (TypeError in the reference)", t);
+                return tracker_err(h, "frame %lld: a zero-area detection has no track id (TypeError in the reference)", frame);
             if (x1 <= x0 || y1 <= y0)
-                return set_err(ctx, AVCER_EINVAL, "frame %d: empty crop (%lld, %lld, %lld, %lld) (cv2.imwrite fails in the reference)", t,
-                               x0, y0, x1, y1);
+                return tracker_err(h, "frame %lld: empty crop (%lld, %lld, %lld, %lld) (cv2.imwrite fails in the reference)", frame, x0,
+                                   y0, x1, y1);
             int64_t* o = records + 6 * n_out++;
-            o[0] = t; o[1] = tids[r] - 1; o[2] = x0; o[3] = y0; o[4] = x1; o[5] = y1;
+            o[0] = frame; o[1] = tids[r] - 1; o[2] = x0; o[3] = y0; o[4] = x1; o[5] = y1;
         }
         row += (size_t)n;
     }
     *n_records = n_out;
     return AVCER_OK;
+}
+
+// A whole video in one call: create, one push, destroy.
+extern "C" int avcer_track_faces(avcer_ctx* ctx, const float* dets, int ld, const int32_t* counts, int n_frames, int frame_w,
+                                 int frame_h, double iou_threshold, double minimum_face_size, int64_t* records, int64_t* n_records) {
+    // ctx may be NULL (host-only call, no device needed): errors then come back as the code alone
+    avcer_tracker* h = avcer_tracker_create(iou_threshold, minimum_face_size);
+    if (!h) return set_err(ctx, AVCER_ENOMEM, "track_faces: out of host memory");
+    int rc = avcer_tracker_push(h, dets, ld, counts, n_frames, 0, frame_w, frame_h, records, n_records);
+    if (rc != AVCER_OK) rc = set_err(ctx, rc, "%s", h->err);
+    avcer_tracker_destroy(h);
+    return rc;
 }

@@ -30,6 +30,56 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _pack_detections(dets_per_frame):
+    """Per-frame detection arrays [k, >= 4] -> (boxes f32 [max(total, 1), 4] back to back, counts i32 [frames], an int64 record
+    buffer [max(total, 1), 6]): the host arguments of avcer_track_faces / avcer_tracker_push."""
+    counts = np.fromiter((len(d) for d in dets_per_frame), dtype=np.int32, count=len(dets_per_frame))
+    total = int(counts.sum())
+    boxes = np.zeros((max(total, 1), 4), dtype=np.float32)
+    if total:
+        np.concatenate([np.asarray(d, dtype=np.float32).reshape(len(d), -1)[:, :4] for d in dets_per_frame if len(d)], out=boxes[:total])
+    return boxes, counts, np.empty((max(total, 1), 6), dtype=np.int64)
+
+
+class FaceTracker:
+    """The face tracker behind a handle (include/avcer_hip.h avcer_tracker_*; host code, no device): the live tracklets, the
+    tracklet counter and the effect of an empty frame are carried from one `push` to the next, so a video pushed in pieces of any
+    size gives the records of `Engine.track_faces` on the whole.  `lib`: the loaded library (Engine.tracker() passes its own).
+    `frames`: how many frames have been pushed, the index the next push starts at."""
+
+    def __init__(self, lib, iou_threshold: float = 0.4, minimum_face_size: float = 0.0):
+        self.lib, self.frames = lib, 0
+        self._h = lib.avcer_tracker_create(float(iou_threshold), float(minimum_face_size))
+        if not self._h:
+            raise MemoryError("avcer_tracker_create failed")
+
+    def push(self, dets_per_frame, frame_w: int, frame_h: int) -> np.ndarray:
+        """The next len(dets_per_frame) frames -> their records int64 [n, 6] = frame (of the whole video), track directory, x0, y0,
+        x1, y1.  ValueError naming the frame where the reference raises (zero-area detection, empty crop); the tracker takes no
+        push after that."""
+        if not self._h:
+            raise ValueError("the tracker is closed")
+        boxes, counts, rec = _pack_detections(dets_per_frame)
+        n = C.c_int64(0)
+        rc = self.lib.avcer_tracker_push(self._h, boxes.ctypes.data_as(C.c_void_p), 4, counts.ctypes.data_as(C.c_void_p), len(counts),
+                                         self.frames, int(frame_w), int(frame_h), rec.ctypes.data_as(C.c_void_p), C.byref(n))
+        if rc != 0:
+            raise ValueError(self.lib.avcer_tracker_last_error(self._h).decode("utf-8", "replace"))
+        self.frames += len(counts)
+        return rec[:int(n.value)]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.avcer_tracker_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 _LIVE = {}  # device index -> weak references to the engines created for it, oldest first (Engine.live)
 
 
@@ -448,12 +498,7 @@ class Engine:
         """The tracker + crop-rectangle loop of `VideoPredictor.process` for a whole video in one native HOST call
         (csrc/track.hip): per-frame detection arrays [k, >= 4] -> records int64 [n, 6] = frame, track directory, x0, y0, x1, y1.
         Raises ValueError where the reference raises (zero-area detection, empty crop)."""
-        counts = np.fromiter((len(d) for d in dets_per_frame), dtype=np.int32, count=len(dets_per_frame))
-        total = int(counts.sum())
-        boxes = np.zeros((max(total, 1), 4), dtype=np.float32)
-        if total:
-            np.concatenate([np.asarray(d, dtype=np.float32).reshape(len(d), -1)[:, :4] for d in dets_per_frame if len(d)], out=boxes[:total])
-        rec = np.empty((max(total, 1), 6), dtype=np.int64)
+        boxes, counts, rec = _pack_detections(dets_per_frame)
         n = C.c_int64(0)
         rc = self.lib.avcer_track_faces(self.ctx, boxes.ctypes.data_as(C.c_void_p), 4, counts.ctypes.data_as(C.c_void_p), len(counts),
                                         int(frame_w), int(frame_h), float(iou_threshold), float(minimum_face_size),
@@ -462,6 +507,12 @@ class Engine:
             raise ValueError(self.lib.avcer_last_error(self.ctx).decode("utf-8", "replace"))
         self._check(rc)
         return rec[:int(n.value)]
+
+    def tracker(self, iou_threshold: float = 0.4, minimum_face_size: float = 0.0) -> "FaceTracker":
+        """`track_faces` for a video that arrives in passes: a `FaceTracker` whose `.push(dets_per_frame, w, h)` takes the next
+        frames and returns their records, with the frame index counted over the whole video.  All pushes together give what one
+        track_faces call on the whole gives."""
+        return FaceTracker(self.lib, iou_threshold, minimum_face_size)
 
     def crop_tiles(self, frames_u8, rects, bgr: bool = True):
         """frames u8 [T,H,W,3] + rects i32 [n,5] (frame, x0, y0, x1, y1; validated by the caller) -> RGB tiles [n,224,224,3]."""

@@ -362,34 +362,43 @@ def _write_files(paths: List[str], blobs) -> None:
 
 
 def write_face_crops(engine, frames_bgr, records: np.ndarray, save_path: str, video_name: str, quality: int = 95,
-                     entropy: str = "host") -> List[str]:
+                     entropy: str = "host", frame_base: int = 0) -> List[str]:
     """Stage 0's face folders (`VideoPredictor.process`, get_face_images.py:52-63): for every record of `VideoTiler.process` the
     half-open crop `fr[y0:y1, x0:x1]` of its frame, written where the reference's cv2.imwrite writes it (JPEG quality 95, 4:2:0:
     cv2's defaults).  The crops are encoded straight out of the BGR frames on the device (jpeg.encode_images); no crop and no
     frame is copied to the host.  `entropy`: where the Huffman coding runs, "host" or "device" (jpeg.encode_images; the files are the
-    same).  Returns the paths in record order."""
+    same).  `frame_base`: `frames_bgr` is one pass of a longer video and holds its frames from that index on; the records (and the
+    file names) keep the video's own frame index.  Returns the paths in record order."""
     from . import jpeg
 
     records = np.asarray(records).reshape(-1, 6)
     paths = face_crop_paths(records, save_path, video_name)
     if not paths:
         return paths
-    blobs = jpeg.encode_images(engine, frames_bgr, records[:, [0, 2, 3, 4, 5]], bgr=True, quality=quality, subsampling=2, entropy=entropy)
+    blobs = jpeg.encode_images(engine, frames_bgr, pass_rects(records, frame_base), bgr=True, quality=quality, subsampling=2, entropy=entropy)
     _write_files(paths, blobs)
     return paths
 
 
+def pass_rects(records: np.ndarray, frame_base: int = 0) -> np.ndarray:
+    """records [n,6] -> the kernels' rectangles int64 [n,5] = (frame - frame_base, x0, y0, x1, y1): the frame index rebased to a pass
+    that starts at frame `frame_base` of the video."""
+    rects = np.asarray(records).reshape(-1, 6)[:, [0, 2, 3, 4, 5]].copy()
+    rects[:, 0] -= int(frame_base)
+    return rects
+
+
 def roundtrip_face_tiles(engine, frames_bgr, records: np.ndarray, save_path: Optional[str] = None, video_name: Optional[str] = None,
-                         quality: int = 95, entropy: str = "host"):
+                         quality: int = 95, entropy: str = "host", frame_base: int = 0):
     """The tiles of `records` as the reference's stage 1 reads them back from stage 0's files (jpeg.roundtrip_tiles: the rectangles
     of write_face_crops, BGR in, 4:2:0) -> (tiles u8 [n,224,224,3] RGB on the device, the paths written or None).  With `save_path`
     and `video_name` the files of write_face_crops are written too, packed from the coefficients of the same pass: no second forward
-    pass runs."""
+    pass runs.  `frame_base`: as in write_face_crops."""
     from . import jpeg
 
     jpeg._check_entropy(entropy)
     records = np.asarray(records).reshape(-1, 6)
-    rects = records[:, [0, 2, 3, 4, 5]]
+    rects = pass_rects(records, frame_base)
     if save_path is None or not len(records):
         return jpeg.roundtrip_tiles(engine, frames_bgr, rects, bgr=True, quality=quality, subsampling=2), None
     tiles, coeffs, d_dev, desc = jpeg.roundtrip_tiles(engine, frames_bgr, rects, bgr=True, quality=quality, subsampling=2, keep_coeffs=True)

@@ -173,7 +173,7 @@ def visual_forward_cam(engine, frames_u8: torch.Tensor, present, fps: float, mod
     """`video_pipeline.visual_forward` of ONE clip with the maps: frames u8 [T,H,W,3] RGB tiles, present [T].  Returns
     (static_probs [T,7], dynamic_logits [T,7], cam f32 [n_present,7,7,7], frame_idx int64 [m], rows int64 [m], cls int32 [m] on
     the device).  The tables are the ones visual_forward computes (the same kernels), the maps come with them."""
-    from .video_pipeline import _device_plan
+    from .video_pipeline import _device_plan, _tables
 
     present = np.ascontiguousarray(np.asarray(present, dtype=bool).reshape(1, -1))
     t = present.shape[1]
@@ -182,22 +182,19 @@ def visual_forward_cam(engine, frames_u8: torch.Tensor, present, fps: float, mod
     dev = engine.device
     flat = frames_u8.reshape(t, *frames_u8.shape[-3:])
     cam = torch.zeros(0, 7, 7, 7, device=dev)
-    cls = torch.zeros(0, dtype=torch.int32, device=dev)
+    probs = feats = None
     if plan.n_feat:
         frames_sel = flat.to(dev) if plan.sel is None else flat.to(dev).index_select(0, plan.sel)
         _, probs, feats, cam = engine.static_forward_cam(frames_sel, mode)
-        stat = torch.cat([probs, plan.zero_row]).index_select(0, plan.s_src)
-        dl = None
-        if plan.n_win:
-            dl = engine.dynamic_forward(engine.gather_windows(feats, plan.win, validated=True), mode)
-            dyn = torch.cat([dl, plan.zero_row]).index_select(0, plan.d_src)
-        else:
-            dyn = torch.zeros(t, 7, device=dev)
-        if len(rows):
-            r = torch.from_numpy(rows).to(dev)
-            w = torch.from_numpy(win).to(dev)
-            cls = choose_classes(model_heatmaps, probs.index_select(0, r), None if dl is None else dl.index_select(0, w))
-    else:
-        stat = torch.zeros(t, 7, device=dev)
-        dyn = torch.zeros(t, 7, device=dev)
-    return stat, dyn, cam, frame_idx, rows, cls
+    stat, dyn, dl = _tables(engine, plan, probs, feats, t, mode)
+    return stat, dyn, cam, frame_idx, rows, heatmap_classes(engine, model_heatmaps, probs, dl, rows, win)
+
+
+def heatmap_classes(engine, model_heatmaps: str, probs, dl, rows, win) -> torch.Tensor:
+    """The class of every heat-map frame, int32 [m] on the device: `choose_classes` on the rows `rows` of the static
+    probabilities of the present frames and on the windows `win` of the LSTM's logits (both from heatmap_plan)."""
+    if probs is None or not len(rows):
+        return torch.zeros(0, dtype=torch.int32, device=engine.device)
+    r = torch.from_numpy(np.asarray(rows)).to(engine.device)
+    w = torch.from_numpy(np.asarray(win)).to(engine.device)
+    return choose_classes(model_heatmaps, probs.index_select(0, r), None if dl is None else dl.index_select(0, w))

@@ -20,13 +20,13 @@ import torch
 from . import io_formats
 from .audio_pipeline import audio_forward, check_window, replicate_per_frame, resample_plan
 from .engine import MODE_DEFAULT
-from .face_tiles import VideoTiler, check_via_jpeg, face_crop_paths, track_clip, write_face_crops
+from .face_tiles import VideoTiler, check_via_jpeg, face_crop_paths, pass_rects, roundtrip_face_tiles, track_clip, write_face_crops
 from .fusion import MODEL_ORDER, fuse
 from .video_pipeline import visual_forward
 
 
 def run_inference_file(engine, path, detector=None, detections: Optional[Sequence[np.ndarray]] = None, fps: Optional[float] = None,
-                       frames_per_pass: int = 64, **kw):
+                       frames_per_pass: int = 64, stream_frames: Optional[int] = None, audio_windows_per_pass: int = 128, **kw):
     """`run_inference` on a recording: the reference's first line, `VideoPredictor.process` opening a video file
     (data/get_face_images.py:19-24, 44-47), for the one container this project reads without a decoder library -- the Motion-JPEG /
     PCM AVI file that `ffmpeg -i clip.mp4 -c:v mjpeg -q:v 2 -c:a pcm_s16le -ar 44100 -ac 2 clip.avi` writes (avcer_amd/avi.py).
@@ -39,10 +39,25 @@ def run_inference_file(engine, path, detector=None, detections: Optional[Sequenc
     conversion, which is not among this project's dependencies and is not claimed.
     `path_save_video=`: the result video (run_inference) with the source's own rate / scale pair and its PCM: the output has the
     source's timing and sound, sample for sample.
+    `stream_frames`: None (the default) decodes the whole file onto the device and calls run_inference, so memory grows with the
+    recording (6.2 MB per 1920 x 1080 frame, and the detector's outputs as much again).  An integer N >= 1 runs the file through the
+    same pipeline in passes of N frames instead (_run_streamed): at most N decoded frames -- one pass buffer, decode and compute are
+    not overlapped -- are alive on the device, whatever the length, and the dict, the CSV files, the face folders, the heat maps and
+    the result video are the in-memory call's, bit for bit.  Only the PCM of the whole file stays on the device (30 minutes of
+    44.1 kHz stereo: 318 MB), and the audio windows go through the model `audio_windows_per_pass` at a time (streamed calls only).
+    With `path_save_video` the file is decoded a second time behind the fusion, which the labels need.  "No face track 00" is
+    known at the end of the sweep and raises the same FileNotFoundError there.  Anything but None or an int >= 1 (0, a negative, a
+    bool, a float) raises ValueError naming stream_frames before the file is opened.  run_dataset / video_job_from_avi stay
+    in-memory.
     Returns run_inference's dict; `real_time_factor` includes demux and decode."""
     from . import jpeg
     from .avi import open_avi
 
+    if stream_frames is not None and (isinstance(stream_frames, (bool, np.bool_)) or not isinstance(stream_frames, (int, np.integer))
+                                      or stream_frames < 1):
+        raise ValueError(f"stream_frames must be None or an integer >= 1, not {stream_frames!r}")
+    if isinstance(audio_windows_per_pass, (bool, np.bool_)) or not isinstance(audio_windows_per_pass, (int, np.integer)) or audio_windows_per_pass < 1:
+        raise ValueError(f"audio_windows_per_pass must be an integer >= 1, not {audio_windows_per_pass!r}")
     start_time = time.time()
     with open_avi(path) as avi:
         if "wav" in kw:
@@ -57,6 +72,12 @@ def run_inference_file(engine, path, detector=None, detections: Optional[Sequenc
         if detections is None and detector is None:
             raise ValueError("give a detector or the per-frame detections")
         fps = int(avi.rate / avi.scale) if fps is None else fps
+        if stream_frames is not None:
+            kw.setdefault("name_video", os.path.splitext(os.path.basename(os.fspath(path)))[0])
+            if kw.get("path_save_video"):
+                kw.setdefault("video_timing", (avi.rate, avi.scale))
+            return _run_streamed(engine, avi, wav, wav_sr, fps, detector, detections, int(stream_frames), int(audio_windows_per_pass),
+                                 frames_per_pass, start_time, **kw)
         frames, _ = jpeg.decode_frames(engine, avi.frames, avi.height, avi.width, bgr=True, frames_per_pass=frames_per_pass)
         n_frames = avi.n_frames
         timing = (avi.rate, avi.scale)
@@ -113,17 +134,7 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
     (rate, scale) pair); the sound is `wav` when it was given as int16 source audio with `wav_sr`, else there is none.  The
     drawing is PIL's ImageDraw, bit for bit, not cv2's.  `video_model`: "av", "vs", "vd" or "a"; anything else raises ValueError
     before any work.  Off by default: nothing changes then."""
-    video_models = [m.lower() for m in MODEL_ORDER]
-    if video_model not in video_models:
-        raise ValueError(f"video_model must be one of {' / '.join(video_models)}, not {video_model!r}")
-    if jpeg_entropy not in ("host", "device"):
-        raise ValueError(f'jpeg_entropy must be "host" or "device", not {jpeg_entropy!r}')
-    check_via_jpeg(faces_via_jpeg)
-    if flag_heatmaps:
-        from . import heatmaps as hm
-
-        hm.check_model(model_heatmaps)
-    check_window(engine, window, sr)
+    hm = _check_options(engine, video_model, jpeg_entropy, faces_via_jpeg, flag_heatmaps, model_heatmaps, window, sr)
     start_time = time.time()                                                # run.py:200
     frames = frames_bgr if torch.is_tensor(frames_bgr) else torch.from_numpy(np.ascontiguousarray(frames_bgr))
     total_frames = int(frames.shape[0])
@@ -139,10 +150,7 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
         wav_t = wav if torch.is_tensor(wav) else torch.from_numpy(np.ascontiguousarray(wav))
     dev = engine.device
     wav_t = wav_t.to(dev)
-    main = torch.cuda.current_stream(dev)
-    side = engine.__dict__.get("_side_stream")
-    if side is None:
-        side = engine.__dict__["_side_stream"] = torch.cuda.Stream(dev)
+    main, side = torch.cuda.current_stream(dev), _side_stream(engine)
     host = {}  # detector / tracker / crop results: independent of the arithmetic mode, computed once
 
     def gpu_work(m):
@@ -207,7 +215,46 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
 
     # MODE_F16X3: one read of the range-contract counter behind the last launch; a video during which an activation left fp16's
     # range is run again in MODE_FP32 (engine.guarded)
-    static_probs, dynamic_logits, win_logits, lo, hi, prob, am, maps = engine.guarded(mode, gpu_work)
+    out = _results(engine, engine.guarded(mode, gpu_work), host, frames, wav, wav_sr, fps, path_save_results, name_video, flag_save_prob, model_heatmaps, path_save_video, video_model, video_quality,
+                   video_panel, video_timing)
+    # "Real-time factor for compound expression prediction" as run.py:304-307 prints it: elapsed / video duration (the
+    # device -> host copies above have synchronised the stream, so the clock covers all the work); None where the
+    # container reported no frame rate
+    out["real_time_factor"] = (time.time() - start_time) / duration if duration else None
+    return out
+
+
+def _check_options(engine, video_model, jpeg_entropy, faces_via_jpeg, flag_heatmaps, model_heatmaps, window, sr):
+    """What run_inference refuses before any work, in its order; returns the heat-map module when `flag_heatmaps`, else None."""
+    video_models = [m.lower() for m in MODEL_ORDER]
+    if video_model not in video_models:
+        raise ValueError(f"video_model must be one of {' / '.join(video_models)}, not {video_model!r}")
+    if jpeg_entropy not in ("host", "device"):
+        raise ValueError(f'jpeg_entropy must be "host" or "device", not {jpeg_entropy!r}')
+    check_via_jpeg(faces_via_jpeg)
+    hm = None
+    if flag_heatmaps:
+        from . import heatmaps as hm
+
+        hm.check_model(model_heatmaps)
+    check_window(engine, window, sr)
+    return hm
+
+
+def _side_stream(engine):
+    """The engine's second stream: the audio branch runs on it beside the visual one."""
+    side = engine.__dict__.get("_side_stream")
+    if side is None:
+        side = engine.__dict__["_side_stream"] = torch.cuda.Stream(engine.device)
+    return side
+
+
+def _results(engine, res, host, frames, wav, wav_sr, fps, path_save_results, name_video, flag_save_prob, model_heatmaps, path_save_video,
+             video_model, video_quality, video_panel, video_timing):
+    """Everything behind the guarded device work, for the in-memory and the streamed call alike: the tables to the host, the CSV
+    files, the heat-map files, the result video.  `res` is gpu_work's tuple; `frames`: the decoded frames, or -- streamed -- a
+    callable that yields them once more in passes (annotate.write_result_video)."""
+    static_probs, dynamic_logits, win_logits, lo, hi, prob, am, maps = res
     records = host["records"]
     rows, aud_frames = replicate_per_frame(win_logits.cpu().numpy(), lo, hi)
     if flag_save_prob:
@@ -220,6 +267,8 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
     if "face_files" in host:
         out["face_files"] = host["face_files"]
     if maps is not None:
+        from . import heatmaps as hm
+
         out["heatmaps"] = (maps[0].astype(np.int32), maps[1].cpu().numpy())
         if path_save_results:
             hm.write_heatmaps(hm.heatmap_dir(path_save_results, name_video, model_heatmaps), maps[0], maps[1], engine=engine)
@@ -235,12 +284,145 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
         if wav_sr is not None:  # source audio as it lay in the file: muxed sample for sample
             src_wav = wav.cpu().numpy() if torch.is_tensor(wav) else np.asarray(wav)
             pcm = src_wav if src_wav.dtype == np.int16 else None
+        video_models = [m.lower() for m in MODEL_ORDER]
         out["result_video"] = write_result_video(engine, frames, records, out[video_model], out["compound_prob"][video_models.index(video_model)],
                                                  path_save_video, int(video_timing[0]), int(video_timing[1]), pcm=pcm,
                                                  audio_rate=int(wav_sr) if pcm is not None else 44100, quality=video_quality,
                                                  entropy="device", panel=video_panel)
-    # "Real-time factor for compound expression prediction" as run.py:304-307 prints it: elapsed / video duration (the
-    # device -> host copies above have synchronised the stream, so the clock covers all the work); None where the
-    # container reported no frame rate
+    return out
+
+
+def _options(**kw):
+    """run_inference's keyword options with its own defaults (one statement of them), `kw` laid over; an unknown name is the
+    TypeError the call itself would raise."""
+    import inspect
+    from types import SimpleNamespace
+
+    opts = {k: p.default for k, p in inspect.signature(run_inference).parameters.items() if p.default is not inspect.Parameter.empty}
+    unknown = sorted(set(kw) - set(opts))
+    if unknown:
+        raise TypeError(f"run_inference() got an unexpected keyword argument {unknown[0]!r}")
+    opts.update(kw)
+    return SimpleNamespace(**opts)
+
+
+def _run_streamed(engine, avi, wav, wav_sr, fps, detector, detections, stream_frames: int, audio_windows_per_pass: int, frames_per_pass: int,
+                  start_time: float, **kw):
+    """`run_inference` on the open recording `avi` in passes of `stream_frames` frames (run_inference_file's `stream_frames`): the
+    same results, bit for bit, with one pass of decoded frames on the device at a time.
+
+    Per pass: jpeg.decode_frames -> detector (or the pass's slice of `detections`) -> the resumable tracker (Engine.tracker) -> the
+    crop rectangles, their frame index rebased to the pass -> crop_tiles / roundtrip_face_tiles / write_face_crops -> the static CNN
+    on the pass's tiles of track 00.  Kept between passes: the detections and records (host), and per frame of track 00 the static
+    CNN's 7 probabilities and 512 features (2076 bytes); with `flag_heatmaps`, per heat-map frame (one in lstm_step(fps)) its 7
+    raw maps [7,7,7] and its base image [224,224,3] -- as large as the overlays that are returned.  Which class a map shows may
+    depend on the LSTM ("dynamic"), which runs behind the sweep, so the overlays of both `model_heatmaps` are rendered there, from
+    what was kept.  Behind the last pass: video_pipeline.visual_from_static (plan_clip's windows over all features, one LSTM
+    call), the audio branch joined, fuse.  With `path_save_video` the file is decoded a SECOND time, pass by pass, for
+    annotate.write_result_video: the labels need the fused predictions.  Decode and compute are not overlapped: one pass buffer is
+    alive at a time."""
+    from . import jpeg
+    from .video_pipeline import lstm_step, visual_from_static
+
+    o = _options(**kw)
+    hm = _check_options(engine, o.video_model, o.jpeg_entropy, o.faces_via_jpeg, o.flag_heatmaps, o.model_heatmaps, o.window, o.sr)
+    total, height, width, per = avi.n_frames, avi.height, avi.width, int(stream_frames)
+    duration = total / fps if (fps and fps > 0 and total > 0) else None
+    if detections is not None and len(detections) != total:
+        raise ValueError("one detection array per frame")
+    dev = engine.device
+    wav_t = (wav if torch.is_tensor(wav) else torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32 if wav_sr is None else None))).to(dev)
+    main, side = torch.cuda.current_stream(dev), _side_stream(engine)
+    save = (o.path_save_faces, o.name_video) if o.path_save_faces else (None, None)
+    host = {}  # detections, records and face files of every pass: independent of the arithmetic mode, computed once
+
+    def decode(a):
+        return jpeg.decode_frames(engine, avi.frames[a:a + per], height, width, bgr=True, frames_per_pass=frames_per_pass)[0]
+
+    def gpu_work(m):
+        side.wait_stream(main)
+        wav_t.record_stream(side)
+        joined = False
+        try:
+            with torch.cuda.stream(side):
+                win_logits, lo, hi = audio_forward(engine, wav_t, o.sr, fps, o.window, o.step, o.padding, m, wav_sr=wav_sr,
+                                                   windows_per_pass=audio_windows_per_pass)
+            first = "records" not in host
+            if first:
+                tracker, passes, files = engine.tracker(0.4, 0.0), [], []  # VideoTiler's tracker
+            present = np.zeros(total, dtype=bool)
+            every = lstm_step(fps)
+            if every <= 0:
+                raise ZeroDivisionError("integer division or modulo by zero")  # as plan_clip: `curr_idx_frame % step`
+            probs, feats, cams, bases = [], [], [], []
+            for k, a in enumerate(range(0, total, per)):
+                frames = decode(a)
+                if first:
+                    dets = detections[a:a + per] if detections is not None else detector.batch(frames, rgb=False)
+                    records = tracker.push(dets, width, height)
+                    passes.append(records)
+                else:
+                    records = host["passes"][k]
+                if len(records):
+                    if o.faces_via_jpeg:
+                        tiles, paths = roundtrip_face_tiles(engine, frames, records, *(save if first else (None, None)), entropy=o.jpeg_entropy,
+                                                            frame_base=a)
+                    else:
+                        tiles = engine.crop_tiles(frames, torch.from_numpy(pass_rects(records, a).astype(np.int32)), bgr=True)
+                        paths = write_face_crops(engine, frames, records, *save, entropy=o.jpeg_entropy, frame_base=a) if first and save[0] else None
+                    if first and save[0]:
+                        files.extend(paths)
+                    sel = np.flatnonzero(records[:, 1] == 0)
+                    if len(sel):
+                        r00 = records[sel]
+                        present[r00[:, 0]] = True
+                        tiles00 = tiles if len(sel) == len(records) else tiles.index_select(0, torch.from_numpy(sel).to(dev))
+                        if o.flag_heatmaps:
+                            _, p, f, cam = engine.static_forward_cam(tiles00, m)
+                            pick = np.flatnonzero(r00[:, 0] % every == 0)
+                            if len(pick):
+                                cams.append(cam.index_select(0, torch.from_numpy(pick).to(dev)))
+                                rects = torch.from_numpy(pass_rects(r00[pick], a).astype(np.int32))
+                                if o.faces_via_jpeg:  # cv2.resize of the read-back crop, as in run_inference
+                                    bases.append(engine.crop_resize_linear(*jpeg.roundtrip_canvas(engine, frames, rects, bgr=True), swap_rb=False))
+                                else:
+                                    bases.append(engine.crop_resize_linear(frames, rects, swap_rb=True))
+                        else:
+                            _, p, f = engine.static_forward(tiles00, m)
+                        probs.append(p)
+                        feats.append(f)
+                    del tiles
+                del frames
+            if first:
+                tracker.close()
+                records = np.concatenate(passes) if passes else np.zeros((0, 6), dtype=np.int64)
+                if save[0]:
+                    host["face_files"] = files
+                if not present.any():
+                    raise FileNotFoundError("no face track 00 (os.listdir(<faces>/00) fails in the reference, get_prob_video.py:79)")
+                host["passes"], host["records"] = passes, records
+            probs, feats = torch.cat(probs), torch.cat(feats)
+            static_probs, dynamic_logits, dl = visual_from_static(engine, probs, feats, present, fps, m, with_windows=True)
+            maps = None
+            if o.flag_heatmaps:
+                fidx, rows, win = hm.heatmap_plan(present, fps)
+                if len(rows):
+                    cls = hm.heatmap_classes(engine, o.model_heatmaps, probs, dl, rows, win)
+                    maps = (fidx, engine.cam_render(torch.cat(cams), np.arange(len(rows)), cls, torch.cat(bases), hm.JET_BGR, hm.IMAGE_WEIGHT))
+                else:
+                    maps = (fidx, torch.zeros((0, 224, 224, 3), dtype=torch.uint8, device=dev))
+            main.wait_stream(side)
+            joined = True
+            win_logits.record_stream(main)
+            prob, am = fuse(engine, static_probs, dynamic_logits, win_logits, lo, hi, o.weights_prob_model, o.weights_model, o.ce_weights_type,
+                            o.ce_mask)
+            return static_probs, dynamic_logits, win_logits, lo, hi, prob, am, maps
+        finally:
+            if not joined:  # as in run_inference: no launch of this video outlives the call
+                main.wait_stream(side)
+
+    res = engine.guarded(o.mode, gpu_work)
+    out = _results(engine, res, host, lambda: (decode(a) for a in range(0, total, per)), wav, wav_sr, fps, o.path_save_results, o.name_video,
+                   o.flag_save_prob, o.model_heatmaps, o.path_save_video, o.video_model, o.video_quality, o.video_panel, o.video_timing)
     out["real_time_factor"] = (time.time() - start_time) / duration if duration else None
     return out

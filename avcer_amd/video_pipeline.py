@@ -112,20 +112,46 @@ def visual_forward(engine: Engine, frames_u8: torch.Tensor, present, fps: float,
     plan = _device_plan(engine, present, fps)
     dev = engine.device
     flat = frames_u8.reshape(n * t, *frames_u8.shape[2:])
+    probs = feats = None
     if plan.n_feat:
         frames_sel = flat.to(dev) if plan.sel is None else flat.to(dev).index_select(0, plan.sel)
         _, probs, feats = engine.static_forward(frames_sel, mode)
+    stat, dyn, _ = _tables(engine, plan, probs, feats, n * t, mode)
+    stat, dyn = stat.view(n, t, 7), dyn.view(n, t, 7)
+    return (stat[0], dyn[0]) if single else (stat, dyn)
+
+
+def _tables(engine: Engine, plan: _DevicePlan, probs, feats, rows: int, mode: int):
+    """The window logic's one statement: the static CNN's outputs of the present frames (probs [n_feat,7], feats [n_feat,512], in
+    frame order; None when there is none) -> (static table [rows,7], dynamic table [rows,7], the LSTM's logits per window or
+    None): the LSTM over the plan's windows, hold-last / zeros rows gathered as the plan says (get_prob_video.py:157-178)."""
+    dev = engine.device
+    dl = None
+    if plan.n_feat:
         stat = torch.cat([probs, plan.zero_row]).index_select(0, plan.s_src)
         if plan.n_win:
             dl = engine.dynamic_forward(engine.gather_windows(feats, plan.win, validated=True), mode)
             dyn = torch.cat([dl, plan.zero_row]).index_select(0, plan.d_src)
         else:
-            dyn = torch.zeros(n * t, 7, device=dev)
+            dyn = torch.zeros(rows, 7, device=dev)
     else:
-        stat = torch.zeros(n * t, 7, device=dev)
-        dyn = torch.zeros(n * t, 7, device=dev)
-    stat, dyn = stat.view(n, t, 7), dyn.view(n, t, 7)
-    return (stat[0], dyn[0]) if single else (stat, dyn)
+        stat = torch.zeros(rows, 7, device=dev)
+        dyn = torch.zeros(rows, 7, device=dev)
+    return stat, dyn, dl
+
+
+def visual_from_static(engine: Engine, probs, feats, present, fps: float, mode: int = MODE_DEFAULT, with_windows: bool = False):
+    """`visual_forward` behind the static CNN, for a caller that ran it in passes and kept only its outputs: probs [n_feat,7] and
+    feats [n_feat,512] (Engine.static_forward) of the PRESENT frames of one clip in frame order, present bool [T] -> (static_probs
+    [T,7], dynamic_logits [T,7]), the tables visual_forward returns for that clip -- the same plan, the same LSTM call.
+    `with_windows`: the LSTM's logits per window [n_win,7] (None when there is no window) as a third value."""
+    present = np.ascontiguousarray(np.asarray(present, dtype=bool).reshape(1, -1))
+    plan = _device_plan(engine, present, fps)
+    n_rows = 0 if probs is None else int(probs.shape[0])
+    if n_rows != plan.n_feat or (plan.n_feat and int(feats.shape[0]) != plan.n_feat):
+        raise ValueError(f"visual_from_static: {n_rows} rows of static outputs for {plan.n_feat} present frames")
+    stat, dyn, dl = _tables(engine, plan, probs, feats, present.shape[1], mode)
+    return (stat, dyn, dl) if with_windows else (stat, dyn)
 
 
 def read_face_dir(path_images: str, total_frames: int, track: str = "00"):

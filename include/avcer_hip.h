@@ -94,7 +94,9 @@ enum {
  *      of an AVI file decoded into the frame batch) joined under 8 the same way: three more symbols, no struct or argument list
  *      that existed changed.
  *      avcer_annotate_frames (the result video's boxes and labels drawn into the frame batch) and its record struct avcer_draw_item
- *      joined under 8 the same way: one more symbol. */
+ *      joined under 8 the same way: one more symbol.
+ *      avcer_tracker_create, avcer_tracker_push, avcer_tracker_last_error, avcer_tracker_destroy (the face tracker behind a handle:
+ *      a video pushed in passes) joined under 8 the same way: four more symbols; avcer_track_faces keeps its argument list. */
 #define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
@@ -440,6 +442,20 @@ int avcer_annotate_frames(avcer_ctx* ctx, uint8_t* frames, int n, int h, int w, 
 int avcer_track_faces(avcer_ctx* ctx, const float* dets_host, int ld, const int32_t* counts_host, int n_frames, int frame_w,
                       int frame_h, double iou_threshold, double minimum_face_size, int64_t* records_host, int64_t* n_records);
 int avcer_lsap(int nr, int nc, const double* cost_host, int32_t* rows_host, int32_t* cols_host);
+
+/* The same tracker, resumable: a video pushed in pieces gives the records of the whole.  The handle is HOST state -- the live
+ * tracklets (boxes, areas, ids), the tracklet counter, and with them what an empty frame did (it drops every tracklet; the counter
+ * runs on) -- carried from one push to the next.  avcer_tracker_push takes the next n_frames frames of the video, the first of
+ * which is frame `first_frame` (>= 0) of the whole: arguments as avcer_track_faces, records carry the GLOBAL frame index and
+ * errors name it; records_host needs room for this push's sum(counts) rows.  After an error the handle takes no further push
+ * (AVCER_EINVAL, the first error's text stands).  avcer_tracker_last_error: the text of the handle's last error ("" when none).
+ * avcer_tracker_create returns NULL when host memory is out.  avcer_track_faces is create + one push + destroy. */
+typedef struct avcer_tracker avcer_tracker;
+avcer_tracker* avcer_tracker_create(double iou_threshold, double minimum_face_size);
+int avcer_tracker_push(avcer_tracker* tracker, const float* dets_host, int ld, const int32_t* counts_host, int n_frames,
+                       int64_t first_frame, int frame_w, int frame_h, int64_t* records_host, int64_t* n_records);
+const char* avcer_tracker_last_error(const avcer_tracker* tracker);
+void avcer_tracker_destroy(avcer_tracker* tracker);
 
 /* JPEG face crops, decoding: the files stage 0 writes and stage 1 reads back,
  *   ref: data/get_face_images.py:52-63 (cv2.imwrite of `<faces>/<track>/NNNNNN.jpg`), get_prob_video.py:79-100 (the read loop),
