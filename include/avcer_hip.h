@@ -947,7 +947,8 @@ int avcer_profile_read_launches(avcer_ctx* ctx, int64_t max_n, int32_t* fam, dou
 
 /* Debug aid for parity tests: arm a one-shot tap; the next forward pass copies up to `bytes` raw bytes of the
  * named intermediate activation (first sub-batch) into dst_dev.  Names: static "pre", "stem_conv", "stem",
- * "l1b0_c1", "l1b0_c2", "l1b0", "layer1".."layer4", "avgpool"; audio "norm", "conv0", "extract", "proj",
+ * "l1b0_c1", "l1b0_c2", "l1b0", "layer1".."layer4", "avgpool"; LSTM "lstm_h1" (layer 1's h of all steps, [n,10,512] f32) and
+ * "lstm_h2" (layer 2's h after the last step, [n,256] f32), in every mode; audio "norm", "conv0", "extract", "proj",
  * "posconv", "layer0".."layer11", "w2v", "tl1", "tl2", "td0", "mp", "td4", "pooled".  Activations are NHWC / time-major,
  * f32 in AVCER_MODE_FP32, bf16 in AVCER_MODE_BF16 and sp32 (fp16 hi / lo per 32 channels, see avcer_conv_gemm) in
  * AVCER_MODE_F16X3 (residual streams "proj".."tl2", "avgpool" and the heads are always f32).

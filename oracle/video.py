@@ -91,6 +91,83 @@ def resnet50_forward(sd, x, taps: dict | None = None):
     return logits, feats
 
 
+def state_dict64(sd):
+    """The state dict with every floating-point tensor in float64 (exact: each float32 is a float64)."""
+    return {k: v.double() if v.is_floating_point() else v for k, v in sd.items()}
+
+
+def stem64(sd64, x, taps: dict | None = None, eps: float = BN_EPS):
+    """stem() in the dtype of its arguments, with the launch-level taps of the library (NCHW): "pre" (the preprocessed image
+    inside its TF-"same" zero border: 3 rows / columns after the image, 2 before it, so for 224 x 224 the [n, 3, 229, 229] tensor
+    whose NHWC form is the view [:, :229, :229, :3] of the library's 230 x 230 x 4 tap; the 230th row / column and the fourth
+    channel are the library's own zero fill, read by no output), "stem_conv" (conv 7x7/2 + BN + ReLU), "stem" (after the
+    3x3/2 max-pool)."""
+    ph = _same_pad(x.shape[-2], 7, 2)
+    pw = _same_pad(x.shape[-1], 7, 2)
+    x = F.pad(x, [pw // 2, pw - pw // 2, ph // 2, ph - ph // 2])
+    if taps is not None:
+        taps["pre"] = x
+    p = "batch_norm1"
+    x = F.conv2d(x, sd64["conv_layer_s2_same.weight"], None, 2)
+    x = F.relu(F.batch_norm(x, sd64[p + ".running_mean"], sd64[p + ".running_var"], sd64[p + ".weight"], sd64[p + ".bias"],
+                            False, 0.0, eps))
+    if taps is not None:
+        taps["stem_conv"] = x
+    x = F.max_pool2d(x, 3, 2)
+    if taps is not None:
+        taps["stem"] = x
+    return x
+
+
+def resnet50_forward64(sd64, x, taps: dict | None = None, hook=None):
+    """resnet50_forward in the dtype of its arguments (float64 with state_dict64(sd) and x.double(), so that a comparison against it
+    measures the library's rounding alone), with one tap per launch of the library's forward, every one at EVERY position (NCHW;
+    the library holds the last block of stages 1-3 at even positions only: the caller selects [:, :, ::2, ::2]; a 3x3 / stride-2 /
+    pad-1 convolution samples the centres of the stride-1 one at even positions, so the stride-1 "c2:" below is the reference of
+    the library's strided conv2 as well):
+      "pre" "stem_conv" "stem"                       stem64
+      "c1:l<s>.<b>." "c2:l<s>.<b>." "c3:l<s>.<b>."   a block's conv1 / conv2 (+ BN + ReLU) and conv3 + BN + shortcut + ReLU
+      "blk<s>_<b>"                                   the block's output (the same tensor as its "c3:")
+      "layer1" .. "layer4" "avgpool"                 as resnet50_forward
+      "feats" "logits" "probs"                       fc1 before ReLU, fc2, softmax
+    Returns (logits, feats).
+
+    hook: None, or a dict of deliberate departures that tests/test_gpu_visual_stages.py's docstring records (used to show that the
+    bounds there catch them; never set by a committed test): "eps": {block prefix: BN eps of that block}, "stride_on_conv2":
+    {block prefix} (torchvision's stride placement), "avgpool_positions": the number of positions layer4's mean is taken over."""
+    hook = hook or {}
+    x = stem64(sd64, x, taps)
+    for li, (planes, blocks, stride) in enumerate(RESNET_STAGES, start=1):
+        for b in range(blocks):
+            p = f"layer{li}.{b}"
+            eps = hook.get("eps", {}).get(p, BN_EPS)
+            s = stride if b == 0 else 1
+            s1, s2 = (1, s) if p in hook.get("stride_on_conv2", ()) else (s, 1)
+
+            def bn(v, q):
+                return F.batch_norm(v, sd64[q + ".running_mean"], sd64[q + ".running_var"], sd64[q + ".weight"], sd64[q + ".bias"],
+                                    False, 0.0, eps)
+
+            c1 = F.relu(bn(F.conv2d(x, sd64[p + ".conv1.weight"], None, s1), p + ".batch_norm1"))
+            c2 = F.relu(bn(F.conv2d(c1, sd64[p + ".conv2.weight"], None, s2, 1), p + ".batch_norm2"))
+            y = bn(F.conv2d(c2, sd64[p + ".conv3.weight"]), p + ".batch_norm3")
+            if b == 0:
+                x = bn(F.conv2d(x, sd64[p + ".i_downsample.0.weight"], None, s), p + ".i_downsample.1")
+            x = F.relu(y + x)
+            if taps is not None:
+                k = f"l{li}.{b}."
+                taps["c1:" + k], taps["c2:" + k], taps["c3:" + k], taps[f"blk{li}_{b}"] = c1, c2, x, x
+        if taps is not None:
+            taps[f"layer{li}"] = x
+    npos = hook.get("avgpool_positions")
+    x = x.flatten(2).mean(2) if npos is None else x.flatten(2)[:, :, :npos].mean(2)
+    feats = F.linear(x, sd64["fc1.weight"], sd64["fc1.bias"])
+    logits = F.linear(F.relu(feats), sd64["fc2.weight"], sd64["fc2.bias"])
+    if taps is not None:
+        taps.update(avgpool=x, feats=feats, logits=logits, probs=F.softmax(logits, dim=1))
+    return logits, feats
+
+
 def _lstm_layer(x, w_ih, w_hh, b_ih, b_hh):
     """torch.nn.LSTM single layer, batch_first, zero initial state, gate order i,f,g,o."""
     n, t, _ = x.shape
@@ -115,6 +192,41 @@ def lstm_forward(sd, x):
     x = _lstm_layer(x, sd["lstm2.weight_ih_l0"], sd["lstm2.weight_hh_l0"],
                     sd["lstm2.bias_ih_l0"], sd["lstm2.bias_hh_l0"])
     return F.linear(x[:, -1, :], sd["fc.weight"], sd["fc.bias"])
+
+
+def _lstm_layer64(x, w_ih, w_hh, b_ih, b_hh):
+    """_lstm_layer with the library's grouping: xp = W_ih x + (b_ih + b_hh) for all steps, then g_t = xp_t + W_hh h_{t-1}.
+    Returns (h [n,T,H], xp [n,T,4H], W_hh h_0 [n,4H]: the recurrent projection step 1 uses, no bias)."""
+    n, t, _ = x.shape
+    hid = w_hh.shape[1]
+    c = x.new_zeros(n, hid)
+    xp = F.linear(x, w_ih, b_ih + b_hh)
+    hp1 = None
+    outs = []
+    for s in range(t):
+        g = xp[:, s]
+        if s > 0:
+            hp = F.linear(outs[-1], w_hh)
+            hp1 = hp if s == 1 else hp1
+            g = g + hp
+        i, f, gg, o = g.chunk(4, dim=1)
+        c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(gg)
+        outs.append(torch.sigmoid(o) * torch.tanh(c))
+    return torch.stack(outs, dim=1), xp, hp1
+
+
+def lstm_forward64(sd64, x, taps: dict | None = None):
+    """lstm_forward in the dtype of its arguments, with the tensors the library's launches write: "xp1" [n,10,2048] / "xp2"
+    [n,10,1024] (input projections of all steps, both biases included), "hp1_t1" / "hp2_t1" (W_hh h_0 of step 1, no bias), "h1"
+    [n,10,512], "h2" [n,256] (last step), "logits"."""
+    h1, xp1, hp1 = _lstm_layer64(x, sd64["lstm1.weight_ih_l0"], sd64["lstm1.weight_hh_l0"],
+                                 sd64["lstm1.bias_ih_l0"], sd64["lstm1.bias_hh_l0"])
+    h2, xp2, hp2 = _lstm_layer64(h1, sd64["lstm2.weight_ih_l0"], sd64["lstm2.weight_hh_l0"],
+                                 sd64["lstm2.bias_ih_l0"], sd64["lstm2.bias_hh_l0"])
+    logits = F.linear(h2[:, -1, :], sd64["fc.weight"], sd64["fc.bias"])
+    if taps is not None:
+        taps.update(xp1=xp1, hp1_t1=hp1, h1=h1, xp2=xp2, hp2_t1=hp2, h2=h2[:, -1, :], logits=logits)
+    return logits
 
 
 def lstm_step(fps: float) -> int:
