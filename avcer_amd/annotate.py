@@ -302,10 +302,24 @@ def layout(records, pred, prob, height: int, width: int, font=None, panel: bool 
        (else 0); by = y0 - bh, above the box, or y0 + lw, inside under the top border, when y0 - bh < 0.  Items: FILL (bx, by,
        bx+bw-1, by+bh-1) BLACK coverage 160; MASK name at (bx + lw, by + lw + top_name); MASK number at (bx + lw + advance(name),
        by + lw + top_number); both MAGENTA, scale 1.
-    Tracks other than 0 get their box and no label.  Each distinct mask appears once in `masks`."""
+    In this positional form (pred, prob arrays) tracks other than 0 get their box and no label.  Each distinct mask appears once in
+    `masks`.
+
+    Per-track form: `pred` and `prob` are dicts {track directory: pred int [T]} / {track directory: prob [T, 7]} with the same
+    keys.  Every record of a track in the dict gets, behind its own box, the label of step 3 from that track's arrays; the other
+    tracks keep a bare box; the panel of step 1 shows the dict's FIRST track.  The positional form is the dict {0: ...}."""
     records = np.asarray(records, dtype=np.int64).reshape(-1, 6)
-    pred = np.asarray(pred).reshape(-1)
-    prob = np.asarray(prob, dtype=np.float64).reshape(len(pred), -1)
+    if isinstance(pred, dict) != isinstance(prob, dict):
+        raise ValueError("layout: pred and prob are both arrays (track 00) or both dicts keyed by track")
+    if not isinstance(pred, dict):
+        pred, prob = {0: pred}, {0: prob}
+    if not pred or list(pred) != list(prob):
+        raise ValueError("layout: pred and prob need the same tracks in the same order, at least one")
+    by_track = {}
+    for k in pred:
+        p = np.asarray(pred[k]).reshape(-1)
+        by_track[int(k)] = (p, np.asarray(prob[k], dtype=np.float64).reshape(len(p), -1))
+    pred, prob = next(iter(by_track.values()))  # the panel's
     lw = line_width(height, width)
     cache = label_masks(default_font(lw) if font is None else font)
     masks, index = [], {}
@@ -339,11 +353,12 @@ def layout(records, pred, prob, height: int, width: int, font=None, panel: bool 
         for r in by_frame.get(t, ()):
             x0, y0, x1, y1 = (int(v) for v in r[2:6])
             out.append(outline(t, (x0, y0, x1, y1), MAGENTA, lw))
-            if int(r[1]) != 0 or t >= len(pred):
+            tpred, tprob = by_track.get(int(r[1]), ((), None))
+            if t >= len(tpred):
                 continue
-            c = int(pred[t])
+            c = int(tpred[t])
             jn, an, topn, advn = names[c]
-            jp, ap, topp, _ = use("%.2f%%" % (float(prob[t, c]) * 100))
+            jp, ap, topp, _ = use("%.2f%%" % (float(tprob[t, c]) * 100))
             tw, th = advn + ap.shape[1], max(topn + an.shape[0], topp + ap.shape[0])
             bw, bh = tw + 2 * lw, th + 2 * lw
             bx = x0 + (x1 - x0 + 1) // 2 - bw // 2
@@ -356,7 +371,7 @@ def layout(records, pred, prob, height: int, width: int, font=None, panel: bool 
 
 
 def write_result_video(engine, frames, records, pred, prob, path, rate, scale=1, pcm=None, audio_rate=44100, quality=90, subsampling=2,
-                       entropy="device", frames_per_pass=64, bgr=True, font=None, panel=False):
+                       entropy="device", frames_per_pass=64, bgr=True, font=None, panel=False, tracks=None):
     """The result video of `frames` (uint8 [T, H, W, 3], on the device or moved there; BGR unless bgr=False) as the Motion-JPEG AVI
     file `path` at `rate` / `scale` frames per second, with `pcm` (int16 [L] / [L, C] at `audio_rate`) as its sound: `layout(records,
     pred, prob, H, W, font, panel)` drawn on every frame.  `frames` may also be a frame SOURCE -- a callable returning an iterator, or
@@ -367,12 +382,26 @@ def write_result_video(engine, frames, records, pred, prob, path, rate, scale=1,
     `save(quality=quality, subsampling=subsampling)` of the drawn frames, byte for byte, under both `entropy` values) and appended
     to the file (avi.AviWriter; the header is patched at the end).  The device holds one pass of copies and coefficients at a time;
     only file bytes cross to the host, and the host keeps the index alone.  What AviWriter refuses (a file past 4 GiB: OSError)
-    propagates, and no partial file is left, whatever the failure.  Returns `path`."""
+    propagates, and no partial file is left, whatever the failure.
+    `tracks`: None -- `pred` / `prob` are arrays and label track 00 (or dicts, taken as they are: `layout`) --, "all" or a list of
+    track directories (face_tiles.check_tracks): `pred` and `prob` are then dicts keyed by track, and the tracks named ("all": every
+    key, ascending) are labelled, each from its own arrays; the panel shows the first.  A named track the dicts do not hold raises
+    ValueError before any work.  Returns `path`."""
     import torch
 
     from . import jpeg
     from .avi import AviWriter
+    from .face_tiles import check_tracks
 
+    tracks = check_tracks(tracks)
+    if tracks is not None:
+        if not (isinstance(pred, dict) and isinstance(prob, dict)):
+            raise ValueError("write_result_video: with tracks=, pred and prob are dicts keyed by track")
+        keys = tuple(sorted(pred)) if tracks == "all" else tracks
+        missing = [k for k in keys if k not in pred or k not in prob]
+        if missing or not keys:
+            raise ValueError(f"write_result_video: no prediction for track {missing[0]:02d}" if missing else "write_result_video: no track")
+        pred, prob = {k: pred[k] for k in keys}, {k: prob[k] for k in keys}
     jpeg._check_entropy(entropy)
     if int(frames_per_pass) < 1:
         raise ValueError("frames_per_pass must be at least 1")

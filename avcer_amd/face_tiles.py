@@ -348,6 +348,47 @@ def check_via_jpeg(value) -> None:
         raise ValueError(f"faces_via_jpeg / via_jpeg must be True or False, not {value!r}")
 
 
+def check_tracks(tracks, flag_heatmaps: bool = False):
+    """The `tracks` option of run_inference / run_inference_file / annotate.write_result_video -> None, "all" or a tuple of ints.
+    None: track directory 00 alone, the reference's walk (get_prob_video.py:79-94).  "all": every track directory stage 0 writes.
+    A list / tuple / array of distinct non-negative ints: those track directories (tid - 1, the folder numbers), in that order.
+    Anything else -- another string, an empty list, a bool, a float, a negative, a repeat -- is a ValueError before any work, and so
+    is `flag_heatmaps` beside it: heat maps are drawn for track 00 alone."""
+    if tracks is None:
+        return None
+    if flag_heatmaps:
+        raise ValueError("flag_heatmaps and tracks cannot be combined: heat maps are made for track 00 only (tracks=None)")
+    if isinstance(tracks, str):
+        if tracks != "all":
+            raise ValueError(f'tracks must be None, "all" or a list of track numbers, not {tracks!r}')
+        return "all"
+    if not isinstance(tracks, (list, tuple, np.ndarray)) or np.ndim(tracks) != 1 or len(tracks) == 0:
+        raise ValueError(f'tracks must be None, "all" or a non-empty list of track numbers, not {tracks!r}')
+    for k in tracks:
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or k < 0:
+            raise ValueError(f"tracks: {k!r} is not a track number (an int >= 0)")
+    out = tuple(int(k) for k in tracks)
+    if len(set(out)) != len(out):
+        raise ValueError(f"tracks: a track is named twice in {list(out)}")
+    return out
+
+
+def select_tracks(records: np.ndarray, tracks):
+    """`tracks` as check_tracks returns it -> the tuple of track directories it means for these records: "all" = every distinct
+    records[:, 1], ascending.  A named track without a record, or "all" without any record, is the FileNotFoundError the reference's
+    os.listdir of that folder raises (get_prob_video.py:79)."""
+    have = sorted({int(t) for t in np.asarray(records).reshape(-1, 6)[:, 1]})
+    if isinstance(tracks, str):
+        if not have:
+            raise FileNotFoundError("no face track (os.listdir(<faces>/00) fails in the reference, get_prob_video.py:79)")
+        return tuple(have)
+    for k in tracks:
+        if k not in have:
+            raise FileNotFoundError(f"no face track {k:02d} (os.listdir(<faces>/{k:02d}) fails, as in get_prob_video.py:79); the tracks are "
+                                    f"{', '.join('%02d' % t for t in have) or 'none'}")
+    return tuple(tracks)
+
+
 def face_crop_paths(records: np.ndarray, save_path: str, video_name: str) -> List[str]:
     """get_face_images.py:58-60: `<save_path>/<video_name>/<track:02d>/<frame:06d>.jpg` of every record, in record order."""
     return [os.path.join(save_path, video_name, str(int(t)).zfill(2), str(int(f)).zfill(6) + ".jpg") for f, t in records[:, :2]]

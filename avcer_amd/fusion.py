@@ -59,6 +59,21 @@ def fuse(engine: Engine, stat_probs, dyn_logits, win_logits, frame_lo, frame_hi,
     return engine.fuse(stat_probs, dyn_logits, mean, n_aud, weights_1, weights_2, ce_weights_type, ce_mask)
 
 
+def fuse_tracks(engine: Engine, stat_probs, dyn_logits, win_logits, frame_lo, frame_hi, weights_1=WEIGHTS_AV_1,
+                weights_2=(1, 1, 1), ce_weights_type: bool = False, ce_mask: bool = True):
+    """`fuse` for K face tracks of ONE video in one launch (Engine.fuse_videos, a segment per track): stat_probs, dyn_logits [K,n,7];
+    the video's window logits and spans are every track's, repeated per segment on the device (a few KB).  Returns (comp_prob f64
+    [4,K,n,7], comp_argmax i32 [4,K,n]); track i's slices are what `fuse` gives for its tables, bit for bit.  A video no window
+    covers raises what `fuse` raises."""
+    k, n = int(stat_probs.shape[0]), int(stat_probs.shape[1])
+    covered_frames(frame_lo, frame_hi, n)
+    lo, hi = np.asarray(frame_lo).reshape(-1), np.asarray(frame_hi).reshape(-1)
+    prob, am, _, _ = engine.fuse_videos(stat_probs.reshape(k * n, 7), dyn_logits.reshape(k * n, 7), win_logits.repeat(k, 1), np.tile(lo, k),
+                                        np.tile(hi, k), [n] * k, [len(lo)] * k, weights_1, weights_2, ce_weights_type, ce_mask,
+                                        with_mean=False)
+    return prob.view(4, k, n, 7), am.view(4, k, n)
+
+
 def fuse_clips(engine: Engine, stat_probs, dyn_logits, clip_audio_logits, weights_1=WEIGHTS_AV_1,
                weights_2=(1, 1, 1), ce_weights_type: bool = False, ce_mask: bool = True):
     """Batch of N clips of T frames with ONE audio window each covering all T frames (the benchmark clip of

@@ -20,9 +20,10 @@ import torch
 from . import io_formats
 from .audio_pipeline import audio_forward, check_window, replicate_per_frame, resample_plan
 from .engine import MODE_DEFAULT
-from .face_tiles import VideoTiler, check_via_jpeg, face_crop_paths, pass_rects, roundtrip_face_tiles, track_clip, write_face_crops
-from .fusion import MODEL_ORDER, fuse
-from .video_pipeline import visual_forward
+from .face_tiles import (VideoTiler, check_tracks, check_via_jpeg, face_crop_paths, pass_rects, roundtrip_face_tiles, select_tracks, track_clip,
+                         write_face_crops)
+from .fusion import MODEL_ORDER, fuse, fuse_tracks
+from .video_pipeline import tracks_plan, visual_forward, visual_from_static, visual_from_static_tracks
 
 
 def run_inference_file(engine, path, detector=None, detections: Optional[Sequence[np.ndarray]] = None, fps: Optional[float] = None,
@@ -49,6 +50,8 @@ def run_inference_file(engine, path, detector=None, detections: Optional[Sequenc
     known at the end of the sweep and raises the same FileNotFoundError there.  Anything but None or an int >= 1 (0, a negative, a
     bool, a float) raises ValueError naming stream_frames before the file is opened.  run_dataset / video_job_from_avi stay
     in-memory.
+    `tracks=` (run_inference) is refused, where it is refused, before the file is opened, and holds for both paths: streamed, a
+    named track that never appeared raises its FileNotFoundError at the end of the sweep, as "no face track 00" does.
     Returns run_inference's dict; `real_time_factor` includes demux and decode."""
     from . import jpeg
     from .avi import open_avi
@@ -58,6 +61,7 @@ def run_inference_file(engine, path, detector=None, detections: Optional[Sequenc
         raise ValueError(f"stream_frames must be None or an integer >= 1, not {stream_frames!r}")
     if isinstance(audio_windows_per_pass, (bool, np.bool_)) or not isinstance(audio_windows_per_pass, (int, np.integer)) or audio_windows_per_pass < 1:
         raise ValueError(f"audio_windows_per_pass must be an integer >= 1, not {audio_windows_per_pass!r}")
+    check_tracks(kw.get("tracks"), kw.get("flag_heatmaps", False))
     start_time = time.time()
     with open_avi(path) as avi:
         if "wav" in kw:
@@ -97,7 +101,7 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
                   flag_heatmaps: bool = False, model_heatmaps: str = "static", wav_sr: Optional[int] = None,
                   path_save_faces: Optional[str] = None, jpeg_entropy: str = "host", faces_via_jpeg: bool = False,
                   path_save_video: Optional[str] = None, video_model: str = "av", video_quality: int = 90, video_panel: bool = False,
-                  video_timing: Optional[Sequence[int]] = None):
+                  video_timing: Optional[Sequence[int]] = None, tracks=None):
     """engine: an `Engine` with the static, dynamic and audio weights loaded.  frames_bgr u8 [T,H,W,3] as cv2 decodes
     them; wav float32 [L] mono at `sr`; fps as `int(cv2.CAP_PROP_FPS)` gives it (get_face_images.py:23).
     `wav_sr`: `wav` is source audio at that rate instead -- int16 [L] / [L, C] as the frames lie in the WAV file ffmpeg writes
@@ -133,7 +137,24 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
     quality `video_quality`); `out["result_video"]` is the path.  The frame rate is `fps` (or `video_timing` = the container's exact
     (rate, scale) pair); the sound is `wav` when it was given as int16 source audio with `wav_sr`, else there is none.  The
     drawing is PIL's ImageDraw, bit for bit, not cv2's.  `video_model`: "av", "vs", "vd" or "a"; anything else raises ValueError
-    before any work.  Off by default: nothing changes then."""
+    before any work.  Off by default: nothing changes then.
+    `tracks`: which face tracks the visual models and the fusion run on.  None (the default): track directory 00 alone, as the
+    reference (get_prob_video.py:79-94 walks `<faces>/00/`; get_face_images.py:73-76 leaves choosing a "target face" among the
+    folders to the user) -- today's call, unchanged.  "all": every track directory stage 0 writes, ascending.  A list of distinct
+    ints >= 0: those directories (tid - 1, the folder numbers), in that order.  Every selected track is treated as the reference
+    would treat it were its folder named `00` -- its own present mask, hold / zero / reset rule and LSTM windows
+    (video_pipeline.tracks_plan); the audio table is the video's -- and its tables are, bit for bit, what
+    `visual_forward(engine, *track_clip(records, tiles, k, T), fps, mode)` and `fusion.fuse` on them give.  Detector, tracker,
+    crops and the audio branch run once; ONE static CNN call takes the selected tracks' tiles, ONE LSTM call all their windows, ONE
+    fusion launch a segment per track (fusion.fuse_tracks); the range contract is read once for all of it.
+    `out["tracks"]` = {track: dict of av / vs / vd / a / compound_prob / static_probs / dynamic_logits / present (bool [T])} in the
+    order selected; the top-level keys are the FIRST selected track's (`audio_rows`, `audio_frames`, `records`, `face_files` are the
+    video's, as ever).  `flag_save_prob` writes the first track under today's names and every other track k through the same
+    writers as the video `<name_video>__t<kk>`; the result video labels every selected track from its own prediction, the panel
+    shows the first.  A named track without a record raises FileNotFoundError naming it before the visual models run, "all" without
+    any record the same; anything that is not None, "all" or such a list, and `flag_heatmaps` together with `tracks` (heat maps
+    stay with track 00), raises ValueError before any work."""
+    tracks = check_tracks(tracks, flag_heatmaps)
     hm = _check_options(engine, video_model, jpeg_entropy, faces_via_jpeg, flag_heatmaps, model_heatmaps, window, sr)
     start_time = time.time()                                                # run.py:200
     frames = frames_bgr if torch.is_tensor(frames_bgr) else torch.from_numpy(np.ascontiguousarray(frames_bgr))
@@ -174,13 +195,24 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
                     records, tiles = VideoTiler(engine).process(frames, dets)
                 if path_save_faces and not faces_via_jpeg:
                     host["face_files"] = write_face_crops(engine, frames, records, path_save_faces, name_video, entropy=jpeg_entropy)
-                if not (len(records) and (records[:, 1] == 0).any()):
-                    raise FileNotFoundError("no face track 00 (os.listdir(<faces>/00) fails in the reference, get_prob_video.py:79)")
-                host["records"] = records
-                host["clip"] = track_clip(records, tiles, 0, total_frames)
+                if tracks is not None:
+                    # the selected tracks as one ragged set of clips: their tiles alone, track after track (no dense clip per track)
+                    tp = tracks_plan(records, select_tracks(records, tracks), total_frames, fps)
+                    host["records"], host["tracks_plan"] = records, tp
+                    host["clip"] = (tiles if len(tp.rows) == len(tiles) and (np.diff(tp.rows) == 1).all() else
+                                    tiles.index_select(0, torch.from_numpy(tp.rows).to(dev)), tp)
+                else:
+                    if not (len(records) and (records[:, 1] == 0).any()):
+                        raise FileNotFoundError("no face track 00 (os.listdir(<faces>/00) fails in the reference, get_prob_video.py:79)")
+                    host["records"] = records
+                    host["clip"] = track_clip(records, tiles, 0, total_frames)
             clip, present = host["clip"]
             maps = None
-            if flag_heatmaps:
+            if tracks is not None:
+                # ONE static CNN sweep over all tracks' tiles, ONE LSTM call over all tracks' windows (video_pipeline.tracks_plan)
+                _, probs, feats = engine.static_forward(clip, m)
+                static_probs, dynamic_logits = visual_from_static_tracks(engine, probs, feats, present, fps, m)
+            elif flag_heatmaps:
                 static_probs, dynamic_logits, cam, fidx, rows, cls = hm.visual_forward_cam(engine, clip, present, fps, m, model_heatmaps)
                 if len(rows):
                     recs = host["records"]
@@ -203,8 +235,8 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
             main.wait_stream(side)
             joined = True
             win_logits.record_stream(main)
-            prob, am = fuse(engine, static_probs, dynamic_logits, win_logits, lo, hi, weights_prob_model, weights_model,
-                            ce_weights_type, ce_mask)                                                # run.py:25-189
+            prob, am = (fuse if tracks is None else fuse_tracks)(engine, static_probs, dynamic_logits, win_logits, lo, hi, weights_prob_model,
+                                                                 weights_model, ce_weights_type, ce_mask)  # run.py:25-189
             return static_probs, dynamic_logits, win_logits, lo, hi, prob, am, maps
         finally:
             # the reference's failure paths (no face track, a detector error) unwind from here: the audio branch already queued
@@ -257,13 +289,32 @@ def _results(engine, res, host, frames, wav, wav_sr, fps, path_save_results, nam
     static_probs, dynamic_logits, win_logits, lo, hi, prob, am, maps = res
     records = host["records"]
     rows, aud_frames = replicate_per_frame(win_logits.cpu().numpy(), lo, hi)
+    tp = host.get("tracks_plan")
+    am, prob, static_probs, dynamic_logits = am.cpu().numpy(), prob.cpu().numpy(), static_probs.cpu().numpy(), dynamic_logits.cpu().numpy()
+    per_track = None
+    if tp is not None:
+        # [.., K, T, ..] tables of the selected tracks: a dict per track; the first one is the call's top level, under today's names
+        per_track = {}
+        for i, k in enumerate(tp.tracks):
+            one = {name.lower(): am[j, i].copy() for j, name in enumerate(MODEL_ORDER)}
+            one.update(compound_prob=prob[:, i].copy(), static_probs=static_probs[i].copy(),
+                       dynamic_logits=dynamic_logits[i].copy(), present=tp.present[i].copy())
+            per_track[k] = one
+        # the top level holds arrays of its own, as with tracks=None: editing one in place leaves out["tracks"] alone
+        first = per_track[tp.tracks[0]]
+        am, prob = np.stack([first[name.lower()] for name in MODEL_ORDER]), first["compound_prob"].copy()
+        static_probs, dynamic_logits = first["static_probs"].copy(), first["dynamic_logits"].copy()
     if flag_save_prob:
         io_formats.write_visual_csvs(static_probs, dynamic_logits, path_save_results, name_video)
         io_formats.write_audio_csv(rows, aud_frames, path_save_results, "audio", name_video)
-    am = am.cpu().numpy()
+        for k in (tp.tracks[1:] if tp is not None else ()):  # the other tracks: the same files, as the video `<name_video>__t<kk>`
+            io_formats.write_visual_csvs(per_track[k]["static_probs"], per_track[k]["dynamic_logits"], path_save_results, f"{name_video}__t{k:02d}")
+            io_formats.write_audio_csv(rows, aud_frames, path_save_results, "audio", f"{name_video}__t{k:02d}")
     out = {name.lower(): am[i] for i, name in enumerate(MODEL_ORDER)}
-    out.update(compound_prob=prob.cpu().numpy(), static_probs=static_probs.cpu().numpy(),
-               dynamic_logits=dynamic_logits.cpu().numpy(), audio_rows=rows, audio_frames=aud_frames, records=records)
+    out.update(compound_prob=prob, static_probs=static_probs, dynamic_logits=dynamic_logits, audio_rows=rows, audio_frames=aud_frames,
+               records=records)
+    if per_track is not None:
+        out["tracks"] = per_track
     if "face_files" in host:
         out["face_files"] = host["face_files"]
     if maps is not None:
@@ -285,10 +336,16 @@ def _results(engine, res, host, frames, wav, wav_sr, fps, path_save_results, nam
             src_wav = wav.cpu().numpy() if torch.is_tensor(wav) else np.asarray(wav)
             pcm = src_wav if src_wav.dtype == np.int16 else None
         video_models = [m.lower() for m in MODEL_ORDER]
-        out["result_video"] = write_result_video(engine, frames, records, out[video_model], out["compound_prob"][video_models.index(video_model)],
-                                                 path_save_video, int(video_timing[0]), int(video_timing[1]), pcm=pcm,
-                                                 audio_rate=int(wav_sr) if pcm is not None else 44100, quality=video_quality,
-                                                 entropy="device", panel=video_panel)
+        j = video_models.index(video_model)
+        if per_track is None:
+            pred, prob_model, labelled = out[video_model], out["compound_prob"][j], None
+        else:  # a label per selected track, from its own prediction
+            pred = {k: one[video_model] for k, one in per_track.items()}
+            prob_model = {k: one["compound_prob"][j] for k, one in per_track.items()}
+            labelled = tp.tracks
+        out["result_video"] = write_result_video(engine, frames, records, pred, prob_model, path_save_video, int(video_timing[0]),
+                                                 int(video_timing[1]), pcm=pcm, audio_rate=int(wav_sr) if pcm is not None else 44100,
+                                                 quality=video_quality, entropy="device", panel=video_panel, tracks=labelled)
     return out
 
 
@@ -317,14 +374,18 @@ def _run_streamed(engine, avi, wav, wav_sr, fps, detector, detections, stream_fr
     CNN's 7 probabilities and 512 features (2076 bytes); with `flag_heatmaps`, per heat-map frame (one in lstm_step(fps)) its 7
     raw maps [7,7,7] and its base image [224,224,3] -- as large as the overlays that are returned.  Which class a map shows may
     depend on the LSTM ("dynamic"), which runs behind the sweep, so the overlays of both `model_heatmaps` are rendered there, from
-    what was kept.  Behind the last pass: video_pipeline.visual_from_static (plan_clip's windows over all features, one LSTM
-    call), the audio branch joined, fuse.  With `path_save_video` the file is decoded a SECOND time, pass by pass, for
+    what was kept.  With `tracks` the static CNN takes the pass's tiles of the SELECTED tracks and those 2076 bytes are kept per
+    record of a selected track -- with "all" per record, since which tracks there are is known at the end only --, in record
+    order; behind the sweep they are gathered track after track as video_pipeline.tracks_plan lays them out.  Behind the last
+    pass: video_pipeline.visual_from_static / visual_from_static_tracks (plan_clip's windows over all features, one LSTM call), the
+    audio branch joined, fuse (fuse_tracks).  With `path_save_video` the file is decoded a SECOND time, pass by pass, for
     annotate.write_result_video: the labels need the fused predictions.  Decode and compute are not overlapped: one pass buffer is
     alive at a time."""
     from . import jpeg
-    from .video_pipeline import lstm_step, visual_from_static
+    from .video_pipeline import lstm_step
 
     o = _options(**kw)
+    tracks = check_tracks(o.tracks, o.flag_heatmaps)
     hm = _check_options(engine, o.video_model, o.jpeg_entropy, o.faces_via_jpeg, o.flag_heatmaps, o.model_heatmaps, o.window, o.sr)
     total, height, width, per = avi.n_frames, avi.height, avi.width, int(stream_frames)
     duration = total / fps if (fps and fps > 0 and total > 0) else None
@@ -355,6 +416,7 @@ def _run_streamed(engine, avi, wav, wav_sr, fps, detector, detections, stream_fr
             if every <= 0:
                 raise ZeroDivisionError("integer division or modulo by zero")  # as plan_clip: `curr_idx_frame % step`
             probs, feats, cams, bases = [], [], [], []
+            kept, n_rec = [], 0  # `tracks`: the records (numbered through the video) whose static outputs are kept
             for k, a in enumerate(range(0, total, per)):
                 frames = decode(a)
                 if first:
@@ -372,10 +434,16 @@ def _run_streamed(engine, avi, wav, wav_sr, fps, detector, detections, stream_fr
                         paths = write_face_crops(engine, frames, records, *save, entropy=o.jpeg_entropy, frame_base=a) if first and save[0] else None
                     if first and save[0]:
                         files.extend(paths)
-                    sel = np.flatnonzero(records[:, 1] == 0)
+                    if tracks is None:
+                        sel = np.flatnonzero(records[:, 1] == 0)
+                    else:  # "all": which tracks there are is known at the end only, so every record is kept
+                        sel = np.arange(len(records)) if tracks == "all" else np.flatnonzero(np.isin(records[:, 1], tracks))
                     if len(sel):
                         r00 = records[sel]
-                        present[r00[:, 0]] = True
+                        if tracks is None:
+                            present[r00[:, 0]] = True
+                        else:
+                            kept.append(sel + n_rec)
                         tiles00 = tiles if len(sel) == len(records) else tiles.index_select(0, torch.from_numpy(sel).to(dev))
                         if o.flag_heatmaps:
                             _, p, f, cam = engine.static_forward_cam(tiles00, m)
@@ -392,17 +460,29 @@ def _run_streamed(engine, avi, wav, wav_sr, fps, detector, detections, stream_fr
                         probs.append(p)
                         feats.append(f)
                     del tiles
+                    n_rec += len(records)
                 del frames
             if first:
                 tracker.close()
                 records = np.concatenate(passes) if passes else np.zeros((0, 6), dtype=np.int64)
                 if save[0]:
                     host["face_files"] = files
-                if not present.any():
+                if tracks is not None:
+                    host["tracks_plan"] = tracks_plan(records, select_tracks(records, tracks), total, fps)
+                elif not present.any():
                     raise FileNotFoundError("no face track 00 (os.listdir(<faces>/00) fails in the reference, get_prob_video.py:79)")
                 host["passes"], host["records"] = passes, records
             probs, feats = torch.cat(probs), torch.cat(feats)
-            static_probs, dynamic_logits, dl = visual_from_static(engine, probs, feats, present, fps, m, with_windows=True)
+            if tracks is not None:
+                # what was kept lies in record order; the plan wants it track after track
+                tp = host["tracks_plan"]
+                pos = np.searchsorted(np.concatenate(kept), tp.rows)
+                if len(pos) != len(probs) or (np.diff(pos) != 1).any():
+                    pos = torch.from_numpy(pos).to(dev)
+                    probs, feats = probs.index_select(0, pos), feats.index_select(0, pos)
+                static_probs, dynamic_logits = visual_from_static_tracks(engine, probs, feats, tp, fps, m)
+            else:
+                static_probs, dynamic_logits, dl = visual_from_static(engine, probs, feats, present, fps, m, with_windows=True)
             maps = None
             if o.flag_heatmaps:
                 fidx, rows, win = hm.heatmap_plan(present, fps)
@@ -414,8 +494,8 @@ def _run_streamed(engine, avi, wav, wav_sr, fps, detector, detections, stream_fr
             main.wait_stream(side)
             joined = True
             win_logits.record_stream(main)
-            prob, am = fuse(engine, static_probs, dynamic_logits, win_logits, lo, hi, o.weights_prob_model, o.weights_model, o.ce_weights_type,
-                            o.ce_mask)
+            prob, am = (fuse if tracks is None else fuse_tracks)(engine, static_probs, dynamic_logits, win_logits, lo, hi, o.weights_prob_model,
+                                                                 o.weights_model, o.ce_weights_type, o.ce_mask)
             return static_probs, dynamic_logits, win_logits, lo, hi, prob, am, maps
         finally:
             if not joined:  # as in run_inference: no launch of this video outlives the call

@@ -63,24 +63,66 @@ def plan_clip(present, fps: float, feat_base: int = 0, win_base: int = 0) -> Cli
     return plan
 
 
+def clips_plan(present, fps: float):
+    """`plan_clip` over the rows of present bool [n,T], row numbers counted through the set: (static_src int64 [n*T], dyn_src int64
+    [n*T], windows int32 [n_win,10], feat_off int64 [n+1], win_off int64 [n+1]); -1 = the zero row, as in ClipPlan.  Clip c owns the
+    feature rows feat_off[c]..feat_off[c+1] and the LSTM windows win_off[c]..win_off[c+1]."""
+    present = np.asarray(present, dtype=bool)
+    s_src, d_src, win, f_off, w_off = [], [], [], [0], [0]
+    for row in present:
+        p = plan_clip(row, fps, f_off[-1], w_off[-1])
+        f_off.append(f_off[-1] + int(row.sum()))
+        w_off.append(w_off[-1] + len(p.windows))
+        s_src += p.static_src
+        d_src += p.dyn_src
+        win += p.windows
+    return (np.asarray(s_src, dtype=np.int64), np.asarray(d_src, dtype=np.int64), np.asarray(win, dtype=np.int32).reshape(-1, 10),
+            np.asarray(f_off, dtype=np.int64), np.asarray(w_off, dtype=np.int64))
+
+
+@dataclass
+class TracksPlan:
+    """The face tracks `tracks` of one video as one ragged set of clips (tracks_plan)."""
+    tracks: tuple            # the track directories, in the order asked for
+    rows: np.ndarray         # int64 [n_feat]: the record (= tile) of every feature row, track after track, each in frame order
+    present: np.ndarray      # bool [K,T]: present[i, t] = track tracks[i] has a crop of frame t
+    static_src: np.ndarray   # clips_plan(present, fps)
+    dyn_src: np.ndarray
+    windows: np.ndarray
+    feat_off: np.ndarray
+    win_off: np.ndarray
+
+
+def tracks_plan(records, tracks, total_frames: int, fps: float) -> TracksPlan:
+    """Every track directory of `tracks` as the reference would walk it were it named `00` (get_prob_video.py:79-178): its own
+    present mask over the video's `total_frames` frames and `plan_clip` of that mask, laid out one behind the other (clips_plan),
+    so that ONE static CNN call over the tiles `rows`, ONE LSTM call over `windows` and two row gathers give all tracks' tables.
+    records int64 [n,6] = frame, track directory, box (face_tiles.VideoTiler); host arithmetic only."""
+    records = np.asarray(records, dtype=np.int64).reshape(-1, 6)
+    present = np.zeros((len(tracks), int(total_frames)), dtype=bool)
+    rows = []
+    for i, k in enumerate(tracks):
+        r = np.flatnonzero(records[:, 1] == int(k))
+        r = r[np.argsort(records[r, 0], kind="stable")]
+        present[i, records[r, 0]] = True
+        rows.append(r)
+    rows = np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)
+    return TracksPlan(tuple(int(k) for k in tracks), rows, present, *clips_plan(present, fps))
+
+
 class _DevicePlan:
     """Index tensors of one (present mask, fps) combination, resident on the device.  Building them costs Python loops
     and host->device copies that serialise behind in-flight GPU work, so they are cached per mask."""
 
-    def __init__(self, engine: Engine, present: np.ndarray, fps: float):
+    def __init__(self, engine: Engine, present: np.ndarray, fps: float, host=None):
         n, t = present.shape
-        plans, fb, wb = [], 0, 0
-        for c in range(n):
-            p = plan_clip(present[c], fps, fb, wb)
-            fb += int(present[c].sum())
-            wb += len(p.windows)
-            plans.append(p)
+        s_src, d_src, win, f_off, w_off = clips_plan(present, fps) if host is None else host
+        fb, wb = int(f_off[-1]), int(w_off[-1])
         dev = engine.device
         self.n_feat, self.n_win = fb, wb
         self.sel = None if fb == n * t else torch.from_numpy(np.nonzero(present.reshape(-1))[0]).to(dev)
-        s_src = np.array([i if i >= 0 else fb for p in plans for i in p.static_src], dtype=np.int64)
-        d_src = np.array([i if i >= 0 else wb for p in plans for i in p.dyn_src], dtype=np.int64)
-        win = np.array([w for p in plans for w in p.windows], dtype=np.int32).reshape(-1, 10)
+        s_src = np.where(s_src >= 0, s_src, fb)
+        d_src = np.where(d_src >= 0, d_src, wb)
         assert win.size == 0 or (win.min() >= 0 and win.max() < max(fb, 1))
         self.s_src = torch.from_numpy(s_src).to(dev)
         self.d_src = torch.from_numpy(d_src).to(dev)
@@ -88,15 +130,16 @@ class _DevicePlan:
         self.zero_row = torch.zeros(1, 7, device=dev)
 
 
-def _device_plan(engine: Engine, present: np.ndarray, fps: float) -> _DevicePlan:
-    """Index plans live ON the Engine object (they hold tensors of its device), so they die with it."""
+def _device_plan(engine: Engine, present: np.ndarray, fps: float, host=None) -> _DevicePlan:
+    """Index plans live ON the Engine object (they hold tensors of its device), so they die with it.  `host`: clips_plan(present,
+    fps) where the caller has it already."""
     cache = engine.__dict__.setdefault("_plan_cache", {})
     key = (present.shape, present.tobytes(), float(fps))
     plan = cache.get(key)
     if plan is None:
         if len(cache) > 64:
             cache.clear()
-        plan = cache[key] = _DevicePlan(engine, present, fps)
+        plan = cache[key] = _DevicePlan(engine, present, fps, host)
     return plan
 
 
@@ -152,6 +195,18 @@ def visual_from_static(engine: Engine, probs, feats, present, fps: float, mode: 
         raise ValueError(f"visual_from_static: {n_rows} rows of static outputs for {plan.n_feat} present frames")
     stat, dyn, dl = _tables(engine, plan, probs, feats, present.shape[1], mode)
     return (stat, dyn, dl) if with_windows else (stat, dyn)
+
+
+def visual_from_static_tracks(engine: Engine, probs, feats, tp: TracksPlan, fps: float, mode: int = MODE_DEFAULT):
+    """`visual_from_static` for the face tracks of a `tracks_plan`: probs [n_feat,7] and feats [n_feat,512] are the static CNN's
+    outputs of the plan's tiles `tp.rows`, in that order -> (static_probs [K,T,7], dynamic_logits [K,T,7]).  One LSTM call holds all
+    tracks' windows; track i's tables are what visual_from_static gives for that track alone, bit for bit (the same `_tables`)."""
+    present = np.ascontiguousarray(tp.present)
+    plan = _device_plan(engine, present, fps, (tp.static_src, tp.dyn_src, tp.windows, tp.feat_off, tp.win_off))
+    if int(probs.shape[0]) != plan.n_feat or int(feats.shape[0]) != plan.n_feat:
+        raise ValueError(f"visual_from_static_tracks: {int(probs.shape[0])} rows of static outputs for {plan.n_feat} tiles of the plan")
+    stat, dyn, _ = _tables(engine, plan, probs, feats, present.size, mode)
+    return stat.view(*present.shape, 7), dyn.view(*present.shape, 7)
 
 
 def read_face_dir(path_images: str, total_frames: int, track: str = "00"):
