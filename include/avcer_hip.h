@@ -961,7 +961,9 @@ int avcer_profile_read_launches(avcer_ctx* ctx, int64_t max_n, int32_t* fam, dou
  *     stem and keeps conv2 outputs in registers, so those taps do not fire there.
  * The S3FD detector (NHWC, post-ReLU, in the mode's storage): "s3fd_conv1" (conv1_1, the stem kernel's output), "s3fd_conv3_3",
  * "s3fd_pool3" (the ceil_mode pool, vgg.16), "s3fd_conv4_3", "s3fd_conv5_3" (the three before their L2Norm), "s3fd_fc7",
- * "s3fd_ex1" (extras.1 = conv6_2), "s3fd_ex3" (extras.3 = conv7_2).
+ * "s3fd_ex1" (extras.1 = conv6_2), "s3fd_ex3" (extras.3 = conv7_2); the four floor pools "s3fd_pool1" (vgg.4), "s3fd_pool2"
+ * (vgg.9), "s3fd_pool4" (vgg.23), "s3fd_pool5" (vgg.30); every contraction by its weight name, "out:vgg2.w" .. "out:vgg33.w",
+ * "out:ex0.w" .. "out:ex3.w".
  * avcer_debug_tap_copied returns the number of bytes copied, or -1 if the tap did not fire (compare it with the size you
  * expect: a short copy means the tensor is smaller than the buffer, e.g. a sub-sampled stage tap). */
 int avcer_debug_tap(avcer_ctx* ctx, const char* name, void* dst_dev, size_t bytes);

@@ -6,7 +6,8 @@ S3FDPredictor.__call__ produced (tests/golden/make_golden_s3fd.py):
     (:8-25) on conv3_3 / conv4_3 / conv5_3, the four extras (:82-87, :139-142), the `loc` / `conf` heads (:89-105), the max-out
     background label of level 0 (:148-149) and the 2-class softmax (:171); preprocessing s3fd_predictor.py:45-52;
   * post-processing: utils.py:6-24 (decode), :94-128 (nms_np), :131-171 (Detect), s3fd_predictor.py:54-68 (the threshold loop).
-f32 and float64 entry points; `taps` collects NCHW intermediates named like the library's debug taps without their "s3fd_" prefix.
+f32 and float64 entry points; `taps` collects NCHW intermediates named like the library's debug taps without their "s3fd_" prefix,
+one per launch (LAUNCHES); `hook` lets a test change one launch's output on the way.
 """
 from __future__ import annotations
 
@@ -33,28 +34,90 @@ def l2norm(x, weight):
     return weight.view(1, -1, 1, 1) * torch.div(x, norm)
 
 
-def trunk(sd, x, taps=None):
-    """The six head inputs (the first three already normalised)."""
+LAUNCHES = ("conv1",) + tuple(f"out:vgg{k}.w" for k in CONVS[1:]) + tuple(f"out:ex{k}.w" for k in range(4)) + tuple(f"pool{k}" for k in range(1, 6))
+POOL_NAMES = {4: "pool1", 9: "pool2", 16: "pool3", 23: "pool4", 30: "pool5"}
+POOL_INPUT = {"pool1": "out:vgg2.w", "pool2": "out:vgg7.w", "pool3": "out:vgg14.w", "pool4": "out:vgg21.w", "pool5": "out:vgg28.w"}
+STEM = ("conv1", None, "vgg.0", 1, 1, 1)   # conv1_1 as a row of contractions(): its input is the preprocessed frame
+
+
+def conv_geometry(k):
+    """(stride, padding, dilation) of vgg.k: fc6 (vgg.31) is dilated by 6 with padding 6, fc7 (vgg.33) is 1 x 1."""
+    return (1, 6, 6) if k == 31 else (1, 0, 1) if k == 33 else (1, 1, 1)
+
+
+def trunk(sd, x, taps=None, hook=None):
+    """The six head inputs (the first three already normalised).
+
+    taps: every launch's output under the library's tap name without its "s3fd_" prefix -- "conv1", "out:vgg2.w" .. "out:vgg33.w",
+    "out:ex0.w" .. "out:ex3.w", "pool1" .. "pool5" (LAUNCHES) -- the eight older names as aliases of the same tensors, and the three
+    L2-normalised sources "l2norm0" .. "l2norm2".
+    hook(name, tensor) -> tensor: called with each launch's name and output before anything reads it; what it returns goes on.
+    tests/test_gpu_s3fd_stages.py plants its deliberate departures through it; None changes nothing."""
     sources = []
+
+    def put(name, t, *aliases):
+        if hook is not None:
+            t = hook(name, t)
+        if taps is not None:
+            for n_ in (name,) + aliases:
+                taps[n_] = t
+        return t
+
     for k in range(35):
         if k in POOLS:
-            x = F.max_pool2d(x, 2, 2, ceil_mode=POOLS[k])
+            x = put(POOL_NAMES[k], F.max_pool2d(x, 2, 2, ceil_mode=POOLS[k]))
         elif k in CONVS:
-            dil = 6 if k == 31 else 1
-            pad = 6 if k == 31 else (0 if k == 33 else 1)
+            _, pad, dil = conv_geometry(k)
             x = F.relu(F.conv2d(x, sd[f"vgg.{k}.weight"], sd[f"vgg.{k}.bias"], padding=pad, dilation=dil))
-        if taps is not None and k in TAPS:
-            taps[TAPS[k]] = x
+            x = put("conv1" if k == 0 else f"out:vgg{k}.w", x, *((TAPS[k],) if k in TAPS and k else ()))
         if k in (14, 21, 28):
             sources.append(l2norm(x, sd[{14: "L2Norm3_3", 21: "L2Norm4_3", 28: "L2Norm5_3"}[k] + ".weight"]))
+            if taps is not None:
+                taps[f"l2norm{len(sources) - 1}"] = sources[-1]
     sources.append(x)
     for k in range(4):
         x = F.relu(F.conv2d(x, sd[f"extras.{k}.weight"], sd[f"extras.{k}.bias"], stride=2 if k % 2 else 1, padding=1 if k % 2 else 0))
+        x = put(f"out:ex{k}.w", x, *((f"ex{k}",) if k % 2 else ()))
         if k % 2:
             sources.append(x)
-            if taps is not None:
-                taps[f"ex{k}"] = x
     return sources
+
+
+def contractions():
+    """The 18 contraction launches behind the stem, in launch order: (tap name, input tap name, state-dict prefix, stride, padding,
+    dilation).  A launch's input is the launch in front of it (a pool where there is one)."""
+    out, prev = [], "conv1"
+    for k in range(1, 35):
+        if k in POOLS:
+            prev = POOL_NAMES[k]
+        elif k in CONVS:
+            out.append((f"out:vgg{k}.w", prev, f"vgg.{k}") + conv_geometry(k))
+            prev = out[-1][0]
+    for k in range(4):
+        out.append((f"out:ex{k}.w", prev, f"extras.{k}", 2 if k % 2 else 1, 1 if k % 2 else 0, 1))
+        prev = out[-1][0]
+    return out
+
+
+def launch64(sd, spec, x, hook=None):
+    """One contraction launch (a row of contractions(), or STEM) in float64 on its own input x [n,c,h,w]:
+    (ReLU(conv(x) + b), sum |x| |w|, |b| as [1,n,1,1], K).  The second and third are what a rounding bound of the launch scales with,
+    K is the number of products per output.  `hook` as in trunk: it sees this launch's name and output."""
+    name, _, p, stride, pad, dil = spec
+    w, b = sd[p + ".weight"].double(), sd[p + ".bias"].double()
+    x = x.double()
+    with torch.no_grad():
+        ref = F.relu(F.conv2d(x, w, b, stride=stride, padding=pad, dilation=dil))
+        sxw = F.conv2d(x.abs(), w.abs(), None, stride=stride, padding=pad, dilation=dil)
+    if hook is not None:
+        ref = hook(name, ref)
+    return ref, sxw, b.abs().view(1, -1, 1, 1), int(w[0].numel())
+
+
+def pool64(name, x, hook=None):
+    """One pool launch on its own input (any dtype: a maximum is exact)."""
+    y = F.max_pool2d(x, 2, 2, ceil_mode=name == "pool3")
+    return hook(name, y) if hook is not None else y
 
 
 def heads(sd, sources):
@@ -69,22 +132,27 @@ def heads(sd, sources):
     return out
 
 
-def s3fd_forward(sd, x, taps=None):
-    """S3FDNet.forward up to the call of Detect: (loc [n,P,4], conf [n,P,2] softmaxed, feature maps [(h, w)] * 6)."""
+def s3fd_forward(sd, x, taps=None, hook=None):
+    """S3FDNet.forward up to the call of Detect: (loc [n,P,4], conf [n,P,2] softmaxed, feature maps [(h, w)] * 6).  `taps` also
+    receives the pre-softmax head outputs of each level, "head_loc0" .. "head_loc5" [n,h,w,4] and "head_conf0" .. [n,h,w,2]."""
     with torch.no_grad():
-        hd = heads(sd, trunk(sd, x, taps))
+        hd = heads(sd, trunk(sd, x, taps, hook))
+        if taps is not None:
+            for i, (l, c) in enumerate(hd):
+                taps[f"head_loc{i}"], taps[f"head_conf{i}"] = l, c
         n = x.shape[0]
         loc = torch.cat([l.reshape(n, -1) for l, _ in hd], 1).view(n, -1, 4)
         conf = torch.cat([c.reshape(n, -1) for _, c in hd], 1).view(n, -1, 2)
     return loc, F.softmax(conf, dim=-1), [tuple(l.shape[1:3]) for l, _ in hd]
 
 
-def s3fd_forward64(sd, frames_bgr_u8, taps=None):
-    """s3fd_forward of u8 BGR frames [h,w,3] or [n,h,w,3] in float64: a comparison against it measures the library's rounding alone."""
-    sd64 = {k: v.double() if v.is_floating_point() else v for k, v in sd.items()}
+def s3fd_forward64(sd, frames_bgr_u8, taps=None, hook=None, dtype=torch.float64):
+    """s3fd_forward of u8 BGR frames [h,w,3] or [n,h,w,3] in float64: a comparison against it measures the library's rounding alone.
+    dtype=torch.float32 runs the same function in float32: the CPU's own rounding of the graph, the yardstick of the stage tests."""
+    sdt = {k: v.to(dtype) if v.is_floating_point() else v for k, v in sd.items()}
     fr = frames_bgr_u8 if frames_bgr_u8.ndim == 4 else frames_bgr_u8[None]
-    x = torch.cat([preprocess(f, False, torch.float64) for f in fr])
-    return s3fd_forward(sd64, x, taps)
+    x = torch.cat([preprocess(f, False, dtype) for f in fr])
+    return s3fd_forward(sdt, x, taps, hook)
 
 
 def num_priors(h: int, w: int) -> int:

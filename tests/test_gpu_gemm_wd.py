@@ -67,6 +67,10 @@ CONVS = [
     (1, 14, 14, 64, 3, 3, 1, 1, 1, 256, 1),     # one image, two chunks: the shortest K loop
     (13, 7, 7, 512, 3, 3, 1, 1, 1, 512, 1),     # stage 4 conv2: 128 positions span four images
     (2, 28, 28, 128, 3, 3, 1, 1, 1, 256, 1),    # stage 2 geometry
+    # the S3FD detector's fc6: 3 x 3, dilation 6, zero padding 6
+    (2, 4, 6, 64, 3, 3, 1, 6, 6, 256, 1),       # only the centre tap is in bounds
+    (2, 7, 13, 64, 3, 3, 1, 6, 6, 256, 1),      # one row / column of dilated taps in bounds, rows != columns
+    (1, 22, 40, 128, 3, 3, 1, 6, 6, 256, 1),    # the 640 x 360 map: rows that cross tile borders
 ]
 
 
@@ -117,6 +121,10 @@ SKINNY_CONVS = [
     (2, 9, 9, 128, 3, 3, 1, 1, 1, 64, 0),       # every position next to a border, two images in one row tile
     (1, 31, 1, 128, 4, 1, 3, 0, 2, 64, 0),      # un-padded Conv1d, dilated, several taps (the audio head's kind)
     (1, 28, 28, 128, 1, 1, 2, 0, 1, 128, 1),    # strided 1x1
+    # the S3FD detector's fc6: 3 x 3, dilation 6, zero padding 6 (48, 182 and 880 positions: the skinny launcher takes all three)
+    (2, 4, 6, 64, 3, 3, 1, 6, 6, 256, 1),       # only the centre tap is in bounds
+    (2, 7, 13, 64, 3, 3, 1, 6, 6, 256, 1),      # one row / column of dilated taps in bounds, rows != columns
+    (1, 22, 40, 128, 3, 3, 1, 6, 6, 256, 1),    # the 640 x 360 map: rows that cross tile borders
 ]
 
 

@@ -99,6 +99,11 @@ CONVS = [
     (1, 55, 55, 64, 3, 3, 1, 1, 1, 64, 1),
     (2, 31, 1, 64, 5, 1, 3, 0, 2, 64, 0),    # Conv1d k5 s3 dil2 (audio head)
     (2, 40, 1, 64, 2, 1, 2, 0, 1, 64, 2),    # Conv1d k2 s2 + gelu (feature extractor)
+    # the S3FD detector's fc6: 3 x 3, dilation 6, zero padding 6
+    (2, 4, 6, 64, 3, 3, 1, 6, 6, 256, 1),    # only the centre tap is in bounds
+    (2, 7, 13, 64, 3, 3, 1, 6, 6, 256, 1),   # one row / column of dilated taps in bounds, rows != columns
+    (1, 22, 40, 128, 3, 3, 1, 6, 6, 256, 1),  # the 640 x 360 map: rows that cross tile borders
+    (2, 7, 13, 64, 3, 3, 1, (6, 1), (6, 1), 256, 1),  # dil_h 6 / pad_h 6, dil_w 1 / pad_w 1: a swap of the two axes shows
 ]
 
 
@@ -106,11 +111,13 @@ CONVS = [
 @pytest.mark.parametrize("cfg", CONVS)
 def test_conv(engine, dtype, cfg):
     b, h, w_, c, kh, kw, s, p, dil, n, act = cfg
-    g = torch.Generator().manual_seed(sum(cfg))
+    g = torch.Generator().manual_seed(sum(v if isinstance(v, int) else sum(v) for v in cfg))
     x = torch.randn(b, h, w_, c, generator=g)
     w = torch.randn(n, kh, kw, c, generator=g) / (kh * kw * c) ** 0.5
     scale, bias = torch.rand(n, generator=g) + 0.5, torch.randn(n, generator=g)
     sw, pw, dw = (1, 0, 1) if w_ == 1 else (s, p, dil)
+    if isinstance(p, tuple):  # (h, w) pairs: padding and dilation that differ between the axes
+        (p, pw), (dil, dw) = p, dil
     oh = (h + 2 * p - dil * (kh - 1) - 1) // s + 1
     ow = (w_ + 2 * pw - dw * (kw - 1) - 1) // sw + 1
     res = torch.randn(b, oh, ow, n, generator=g)

@@ -60,6 +60,72 @@ def test_restatement_matches_the_reference_class(name):
     assert 0 < n_cand < conf.shape[1] // 4  # the synthetic heads leave a minority of priors above the floor, not all of them
 
 
+def test_every_launch_is_tapped_and_the_old_names_are_aliases():
+    taps, seen = {}, []
+    s3fd_ref.s3fd_forward(SD, s3fd_ref.preprocess(_frame("a")), taps, hook=lambda name, t: seen.append(name) or t)
+    assert tuple(sorted(seen)) == tuple(sorted(s3fd_ref.LAUNCHES)) and len(s3fd_ref.LAUNCHES) == 24
+    assert seen[:3] == ["conv1", "out:vgg2.w", "pool1"] and seen[-1] == "out:ex3.w"
+    for old, new in (("conv3_3", "out:vgg14.w"), ("conv4_3", "out:vgg21.w"), ("conv5_3", "out:vgg28.w"), ("fc7", "out:vgg33.w"),
+                     ("ex1", "out:ex1.w"), ("ex3", "out:ex3.w")):
+        assert taps[old] is taps[new]
+    assert len(s3fd_ref.contractions()) == 18 and [c[1] for c in s3fd_ref.contractions()][:4] == ["conv1", "pool1", "out:vgg5.w", "pool2"]
+    for i in range(3):
+        assert taps[f"l2norm{i}"].shape == taps[("conv3_3", "conv4_3", "conv5_3")[i]].shape
+    for i in range(6):
+        assert taps[f"head_loc{i}"].shape[-1] == 4 and taps[f"head_conf{i}"].shape[-1] == 2
+    # a hook's return value goes on: zeroing pool5 leaves fc6 with its bias alone
+    z = {}
+    s3fd_ref.s3fd_forward(SD, s3fd_ref.preprocess(_frame("a")), z, hook=lambda name, t: t * 0 if name == "pool5" else t)
+    assert torch.equal(z["conv5_3"], taps["conv5_3"]) and not torch.equal(z["fc7"], taps["fc7"])
+    want = torch.relu(SD["vgg.31.bias"]).view(1, -1, 1, 1).expand_as(z["out:vgg31.w"])
+    assert torch.equal(z["out:vgg31.w"], want)
+
+
+def test_float32_run_is_within_its_rounding_bound_of_the_float64_run_at_every_tap():
+    """One 239 x 431 frame (fc6's map is 7 x 13: its dilated taps read data) through the restatement in float32 and in float64.
+    u = 2^-24.
+      * Each launch by itself, rigorously: a float32 sum of K products and a bias in ANY order is within (K + 2) u (sum |x||w| + |b|)
+        of the exact one, so every contraction of the float32 run is within that of the float64 layer applied to the float32 run's
+        own input; conv1 likewise from the integer pixels (K = 27); a pool of float32 values is exact.
+      * Against the float64 run, where the launches compound: the worst-case propagation of the bound above multiplies by sum |w|
+        per layer (about 80) and says nothing after three layers.  The bound used is the random-walk one: the K_l + 2 roundings of
+        an output are independent and at most u of the partial sums, ReLU and max are 1-Lipschitz, and a layer hands relative
+        errors on with gain at most 1 (it averages K independent ones), so
+            max|err| / max|ref| <= u sqrt(sum over the launches up to this one of (K_l + 2)),
+        1.5e-6 behind vgg.2 and 1.3e-5 behind extras.3.  Measured on this frame: 2.9e-7 (vgg.2) .. 9.6e-7 (vgg.28)."""
+    u = 2.0 ** -24
+    frame = synth.video_frames(239, 1, 239, 431)
+    t64, t32 = {}, {}
+    l64, c64, _ = s3fd_ref.s3fd_forward64(SD, frame, t64)
+    l32, c32, _ = s3fd_ref.s3fd_forward64(SD, frame, t32, dtype=torch.float32)
+    assert all(t32[k].dtype == torch.float32 and t64[k].dtype == torch.float64 for k in s3fd_ref.LAUNCHES)
+    x0 = s3fd_ref.preprocess(frame[0], False, torch.float64)
+    ref, sxw, babs, k0 = s3fd_ref.launch64(SD, s3fd_ref.STEM, x0)
+    assert k0 == 27 and bool(((t32["conv1"].double() - ref).abs() <= (k0 + 2) * u * (sxw + babs)).all())
+    assert torch.equal(ref, t64["conv1"])  # conv1's input is exact, so this rigorous bound IS its bound against the float64 run
+    terms = k0 + 2
+    compound = {"conv1": terms}
+    for spec in s3fd_ref.contractions():
+        name, src = spec[:2]
+        if src.startswith("pool"):
+            assert torch.equal(t32[src], s3fd_ref.pool64(src, t32[s3fd_ref.POOL_INPUT[src]]))
+            compound[src] = terms
+        ref, sxw, babs, k = s3fd_ref.launch64(SD, spec, t32[src])
+        own = ((t32[name].double() - ref).abs() / ((k + 2) * u * (sxw + babs))).max()
+        assert float(own) <= 1.0, (name, float(own))
+        terms += k + 2
+        compound[name] = terms
+    assert set(compound) == set(s3fd_ref.LAUNCHES)
+    for name, n_terms in compound.items():
+        if name == "conv1":
+            continue
+        rel = float((t32[name].double() - t64[name]).abs().max() / t64[name].abs().max())
+        bound = u * n_terms ** 0.5
+        print(f"{name:12s} float32 vs float64 {rel:.2e}  bound {bound:.2e}")
+        assert rel <= bound, (name, rel, bound)
+    assert float((c32.double() - c64).abs().max()) < 1e-5 and float((l32.double() - l64).abs().max() / l64.abs().max()) < 1e-5
+
+
 @pytest.mark.parametrize("which", ["full", "trunc"])
 def test_detect_restatement_reproduces_the_reference(which):
     h, w = (int(v) for v in DET["size"])
