@@ -26,7 +26,7 @@ from . import dist as adist
 from . import io_formats
 from .audio_pipeline import check_window, chunk_spans, replicate_per_frame, resample_out_len, resample_plan
 from .engine import MODE_DEFAULT, MODE_F16X3, MODE_FP32
-from .face_tiles import check_via_jpeg
+from .face_tiles import check_detect_size, check_via_jpeg, scaled_detector
 from .fusion import MODEL_ORDER, covered_frames
 from .video_pipeline import plan_clip
 
@@ -234,7 +234,8 @@ def run_dataset(engine, jobs: Sequence[VideoJob], detector=None, *, mode: int = 
                 step: float = 0.5, padding: str = "mean", weights_prob_model=None, weights_model=(1, 1, 1),
                 ce_weights_type: bool = True, ce_mask: bool = False, max_frames_per_pass: int = 2048,
                 max_windows_per_pass: int = 128, path_save_results: str = "", flag_save_prob: bool = False,
-                skip_failed: bool = False, distributed: bool = False, faces_via_jpeg: bool = False) -> DatasetResults:
+                skip_failed: bool = False, distributed: bool = False, faces_via_jpeg: bool = False, detect_size=None,
+                detect_filter: str = "bilinear") -> DatasetResults:
     """`run_inference` for every job of a set, with the videos sharing the GPU passes (module docstring).  Returns a
     `DatasetResults`: a list with one dict per job, in job order, holding `name` and the keys of `run_inference` -- av / vs / vd
     / a, compound_prob, static_probs, dynamic_logits, audio_rows, audio_frames, records -- with the bits `run_inference` gives for
@@ -245,6 +246,10 @@ def run_dataset(engine, jobs: Sequence[VideoJob], detector=None, *, mode: int = 
     `faces_via_jpeg` (for the call, as the other options): `run_inference`'s option of that name for every job -- the tiles of track
     00 are what reading stage 0's JPEG files back gives; the results are those of `run_inference(..., faces_via_jpeg=True)` for each
     video alone.  Off by default; anything but a bool raises ValueError before any work.
+
+    `detect_size` / `detect_filter` (for the call): `run_inference`'s options of those names -- `detector` runs on a smaller copy of
+    every job's frames (face_tiles.ScaledDetector) and is priced at its network's work on that copy.  None (the default): nothing
+    changes.  A bad value, and a target larger than some job's frames, raise ValueError before any work.
 
     Passes: at most `max_frames_per_pass` tiles per static-CNN call (and LSTM windows per LSTM call), at most
     `max_windows_per_pass` audio windows per audio call; device memory for tiles is one pass plus one video.
@@ -271,6 +276,11 @@ def run_dataset(engine, jobs: Sequence[VideoJob], detector=None, *, mode: int = 
         raise ValueError("run_dataset: pass sizes >= 1")
     check_via_jpeg(faces_via_jpeg)
     check_window(engine, window, sr)
+    check_detect_size(detect_size, detect_filter, detector, [] if detector is None else None)
+    for job in jobs if detect_size is not None else ():
+        if job.detections is None:
+            check_detect_size(detect_size, detect_filter, detector, None, (job.height, job.width))
+    detector = scaled_detector(detector, detect_size, detect_filter)
     errors = {}
 
     def fail(i, e):
@@ -298,9 +308,14 @@ def run_dataset(engine, jobs: Sequence[VideoJob], detector=None, *, mode: int = 
     world = torch.distributed.get_world_size() if distributed and torch.distributed.is_initialized() else 1
     rank = torch.distributed.get_rank() if world > 1 else 0
     # a detector is priced at its own network's work (R50 50.7 GFLOP per 640 x 360 frame, MobileNet-0.25 1.116, S3FD 144.27); one without the
-    # attribute counts as R50, as before
-    det_cost = False if detector is None else (True if getattr(detector, "kind", 1) == 1 else float(detector.gflop_per_frame))
-    shards = adist.shard_videos([adist.video_cost(j, window, det_cost if j.detections is None else False, sr, step) for j in jobs], world)
+    # attribute counts as R50, as before; a face_tiles.ScaledDetector at its inner network's work on the smaller copy of that job's frames
+    def det_cost(j):
+        if detector is None or j.detections is not None:
+            return False
+        if hasattr(detector, "gflop_at"):
+            return float(detector.gflop_at(j.height, j.width))
+        return True if getattr(detector, "kind", 1) == 1 else float(detector.gflop_per_frame)
+    shards = adist.shard_videos([adist.video_cost(j, window, det_cost(j), sr, step) for j in jobs], world)
     side = engine.__dict__.get("_side_stream")
     if side is None:
         side = engine.__dict__["_side_stream"] = torch.cuda.Stream(engine.device)

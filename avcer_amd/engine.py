@@ -111,6 +111,7 @@ class Engine:
         self.audio_classes = 0
         self.x3_fallbacks = 0  # calls `guarded` had to repeat in MODE_FP32 (the x3 range contract was broken)
         self._resample_cache = {}  # (orig_freq, new_freq) -> (plan, taps [span, n] and first [n] on the device): Engine.resample
+        self._resize_cache = {}    # (in, out, filter) -> (plan, its packed table on the host and on the device): Engine.resize_frames
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -399,6 +400,62 @@ class Engine:
         if length:
             self._check(self.lib.avcer_resample(self.ctx, _ptr(x), kind, length, ch, _ptr(taps), _ptr(first), o, n, span, width,
                                                 _ptr(out), n_out, self._stream()))
+        return out
+
+    def _resize_tables(self, in_size: int, out_size: int, filter: str):
+        from .resize import resize_plan
+
+        key = (int(in_size), int(out_size), filter)
+        if key not in self._resize_cache:
+            plan = resize_plan(*key)
+            host = plan.packed()
+            self._resize_cache[key] = (plan, host, torch.from_numpy(host).to(self.device))
+        return self._resize_cache[key]
+
+    def resize_form(self, in_h: int, out_h: int, filter: str = "bilinear") -> int:
+        """The form avcer_resize_frames chooses for a vertical axis in_h -> out_h (resize.FORM_FUSED / FORM_TWO_PASS), from the
+        table alone: nothing is launched."""
+        _, host, _ = self._resize_tables(in_h, out_h, filter)
+        rc = self.lib.avcer_resize_form(host.ctypes.data_as(C.c_void_p), int(out_h))
+        if rc < 0:
+            raise AvcerError(rc, "avcer_resize_form: bad table")
+        return rc
+
+    def resize_frames(self, frames, size, filter: str = "bilinear", form: int = 0, out=None):
+        """frames u8 [n,H,W,3] on the device, contiguous -> u8 [n,h2,w2,3], size = (h2, w2): PIL's Image.resize((w2, h2), filter) of
+        every frame, bit for bit, for "box", "bilinear", "bicubic" and "lanczos" (include/avcer_hip.h avcer_resize_frames; the CPU
+        statement is resize.resize_numpy).  Sides 1..8192.  The tables of an axis are built once per engine and stay on the device.
+        A batch that already has the size is returned as it is, with no launch (unless `out` is given, which is then filled).
+        `form`: resize.FORM_CHOOSE, or FORM_FUSED / FORM_TWO_PASS by name (tests; the bits are the same).  `out`: a contiguous uint8
+        [n,h2,w2,3] on the device to write into.  A wrong dtype, shape, device or layout, a side out of range and an unknown filter
+        raise ValueError before any launch.  No host synchronisation."""
+        from .resize import _check_size, check_filter
+
+        check_filter(filter)
+        h2, w2 = _check_size(size)
+        if not (torch.is_tensor(frames) and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[-1] == 3):
+            raise ValueError("resize_frames: frames must be uint8 [n,H,W,3]")
+        if not frames.is_cuda or frames.device != self.device:
+            raise ValueError(f"resize_frames: frames must be on {self.device}")
+        if not frames.is_contiguous():
+            raise ValueError("resize_frames: frames must be contiguous")
+        n, h, w = (int(v) for v in frames.shape[:3])
+        _check_size((h, w))
+        if form not in (0, 1, 2):
+            raise ValueError(f"resize_frames: form {form!r}")
+        if out is None:
+            if (h, w) == (h2, w2):
+                return frames
+            out = self._new(n, h2, w2, 3, dtype=torch.uint8)
+        elif not (torch.is_tensor(out) and out.dtype == torch.uint8 and tuple(out.shape) == (n, h2, w2, 3) and out.is_contiguous() and
+                  out.device == self.device):
+            raise ValueError("resize_frames: out must be a contiguous uint8 [n,h2,w2,3] on the device")
+        if n == 0:
+            return out
+        xp, xh, xd = self._resize_tables(w, w2, filter)
+        yp, yh, yd = self._resize_tables(h, h2, filter)
+        self._check(self.lib.avcer_resize_frames(self.ctx, _ptr(frames), n, h, w, _ptr(out), h2, w2, xh.ctypes.data_as(C.c_void_p), _ptr(xd),
+                                                 xp.ksize, yh.ctypes.data_as(C.c_void_p), _ptr(yd), yp.ksize, int(form), self._stream()))
         return out
 
     def weight_search_counts(self, preds, labels, weights):

@@ -233,6 +233,114 @@ class S3FDPredictor:
         return [rows[t, :int(cnt[t])] if cnt[t] else np.empty((0, 5), dtype=np.float32) for t in range(len(cnt))]
 
 
+_X_COLS, _Y_COLS = (0, 2, 5, 7, 9, 11, 13), (1, 3, 6, 8, 10, 12, 14)  # box corners, then the five landmarks of a [k,15] row
+
+
+def check_detect_size(detect_size, detect_filter="bilinear", detector=None, detections=None, frame_size=None):
+    """The `detect_size` / `detect_filter` options of run_inference, run_inference_file and run_dataset, checked before any work:
+    None, (height, width) or an int (the longest side) -- anything else is a ValueError, as are a filter other than resize.FILTERS, a
+    `detect_size` beside given `detections` with no detector (nothing would use it), and, once the frame size is known
+    (`frame_size` = (H, W)), a target larger than the frames on either side."""
+    from .resize import check_filter, target_size
+
+    check_filter(detect_filter)
+    if detect_size is None:
+        return
+    target_size(1, 1, detect_size)  # the value's form alone
+    if detector is None and detections is not None:
+        raise ValueError("detect_size is given with detections= and no detector: nothing would use it")
+    if frame_size is not None:
+        ScaledDetector.plan(int(frame_size[0]), int(frame_size[1]), detect_size)
+
+
+def scaled_detector(detector, detect_size, detect_filter="bilinear"):
+    """`detector` as the entry points use it: itself for detect_size=None (no wrapper is constructed) or without a detector."""
+    return detector if detect_size is None or detector is None else ScaledDetector(detector, detect_size, detect_filter)
+
+
+class ScaledDetector:
+    """A detector run on a smaller copy of the frames: `ScaledDetector(detector, size, filter="bilinear")` wraps a
+    RetinaFacePredictor (either network) or an S3FDPredictor and offers what the call sites use -- `batch`, `__call__`, `kind`,
+    `gflop_per_frame`.  The batch is resized on the device (resize.resize_frames: PIL's Image.resize, bit for bit), the inner
+    detector runs on the copy, and every row is mapped back to source pixels, so tracker, crop rectangles and crops work on
+    full-resolution coordinates and the crops come from the full-resolution frames.  This departs from the reference on purpose
+    (data/get_face_images.py:50 detects on whole frames) and is off unless asked for.
+
+    `size`: (height, width), or an int n = the longest side: h2 = max(1, int(H * n / max(H, W) + 0.5)), likewise w2.  A target that
+    shrinks neither side -- the frames' own size, an int >= their longest side -- passes the frames straight to the inner detector:
+    the identical call, the identical arrays.  A target larger than the frames on one side and not equal on the other is refused
+    with ValueError: upscaling for detection is not offered.
+    Mapping: sx = float32(W) / float32(w2), sy = float32(H) / float32(h2); columns 0, 2 (and 5, 7, 9, 11, 13 of a [k,15] row) are
+    multiplied by sx, columns 1, 3 (and 6, 8, 10, 12, 14) by sy, in float32; the score is untouched.
+    `kind` is 0 (a wrapper; `inner.kind` is the network's), so run_dataset prices it by `gflop_per_frame`: the inner detector's
+    figure times (h2 * w2) / (H * W) of the last frame size seen (`gflop_at(H, W)` for any other), which dist.video_cost multiplies
+    by H * W / (640 * 360) again."""
+
+    kind = 0
+
+    def __init__(self, detector, size, filter: str = "bilinear"):
+        from .resize import check_filter, target_size
+
+        target_size(1, 1, size)
+        self.inner, self.size, self.filter = detector, size, check_filter(filter)
+        self.engine = detector.engine
+        self._last = None  # (H, W) of the last frames seen
+
+    @staticmethod
+    def plan(height: int, width: int, size):
+        """(h2, w2) for frames of height x width, or None where the frames pass straight through; ValueError for an upscale."""
+        from .resize import target_size
+
+        h2, w2 = target_size(height, width, size)
+        if h2 >= height and w2 >= width and (isinstance(size, (int, np.integer)) or (h2, w2) == (height, width)):
+            return None
+        if h2 > height or w2 > width:
+            raise ValueError(f"detect size {h2} x {w2} (height x width) is larger than the {height} x {width} frames: upscaling for "
+                             "detection is not offered")
+        return h2, w2
+
+    def gflop_at(self, height: int, width: int) -> float:
+        """The wrapper's price per frame of height x width in dist.video_cost's unit (GFLOP per 640 x 360 frame of the SOURCE)."""
+        t = self.plan(int(height), int(width), self.size)
+        g = float(self.inner.gflop_per_frame)
+        return g if t is None else g * (t[0] * t[1]) / (int(height) * int(width))
+
+    @property
+    def gflop_per_frame(self) -> float:
+        return float(self.inner.gflop_per_frame) if self._last is None else self.gflop_at(*self._last)
+
+    def _map(self, rows: np.ndarray, h: int, w: int, h2: int, w2: int) -> np.ndarray:
+        rows = np.array(rows, dtype=np.float32)  # a copy: the inner arrays may be views of a shared host buffer
+        sx, sy = np.float32(w) / np.float32(w2), np.float32(h) / np.float32(h2)
+        nx = [c for c in _X_COLS if c < rows.shape[1]]
+        ny = [c for c in _Y_COLS if c < rows.shape[1]]
+        rows[:, nx] *= sx
+        rows[:, ny] *= sy
+        return rows
+
+    def batch(self, frames, rgb: bool = False):
+        """frames u8 [T,H,W,3] -> one array per frame, of the inner detector's width, in source pixels."""
+        x = frames if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames))
+        h, w = int(x.shape[1]), int(x.shape[2])
+        t = self.plan(h, w, self.size)
+        self._last = (h, w)
+        if t is None:
+            return self.inner.batch(frames, rgb=rgb)
+        small = self.engine.resize_frames(x.to(self.engine.device).contiguous(), t, self.filter)
+        return [self._map(r, h, w, *t) for r in self.inner.batch(small, rgb=rgb)]
+
+    def __call__(self, image, rgb: bool = True):
+        """image u8 [H,W,3] -> the inner detector's array, in source pixels."""
+        img = image if torch.is_tensor(image) else torch.from_numpy(np.ascontiguousarray(image))
+        h, w = int(img.shape[0]), int(img.shape[1])
+        t = self.plan(h, w, self.size)
+        self._last = (h, w)
+        if t is None:
+            return self.inner(image, rgb=rgb)
+        small = self.engine.resize_frames(img[None].to(self.engine.device).contiguous(), t, self.filter)
+        return self._map(self.inner(small[0], rgb=rgb), h, w, *t)
+
+
 class SimpleFaceTracker:
     """IoU + Hungarian face tracker; ids start at 1, a frame without faces drops every tracklet."""
 

@@ -20,8 +20,8 @@ import torch
 from . import io_formats
 from .audio_pipeline import audio_forward, check_window, replicate_per_frame, resample_plan
 from .engine import MODE_DEFAULT
-from .face_tiles import (VideoTiler, check_tracks, check_via_jpeg, face_crop_paths, pass_rects, roundtrip_face_tiles, select_tracks, track_clip,
-                         write_face_crops)
+from .face_tiles import (VideoTiler, check_detect_size, check_tracks, check_via_jpeg, face_crop_paths, pass_rects, roundtrip_face_tiles,
+                         scaled_detector, select_tracks, track_clip, write_face_crops)
 from .fusion import MODEL_ORDER, fuse, fuse_tracks
 from .video_pipeline import tracks_plan, visual_forward, visual_from_static, visual_from_static_tracks
 
@@ -52,6 +52,9 @@ def run_inference_file(engine, path, detector=None, detections: Optional[Sequenc
     in-memory.
     `tracks=` (run_inference) is refused, where it is refused, before the file is opened, and holds for both paths: streamed, a
     named track that never appeared raises its FileNotFoundError at the end of the sweep, as "no face track 00" does.
+    `detect_size=` / `detect_filter=` (run_inference) hold for both paths too: a bad value is refused before the file is opened, an
+    upscale once the container has named the frame size, before any decode; streamed, every pass is resized on its own (there is no
+    state across frames), so the results are the in-memory call's.
     Returns run_inference's dict; `real_time_factor` includes demux and decode."""
     from . import jpeg
     from .avi import open_avi
@@ -62,8 +65,10 @@ def run_inference_file(engine, path, detector=None, detections: Optional[Sequenc
     if isinstance(audio_windows_per_pass, (bool, np.bool_)) or not isinstance(audio_windows_per_pass, (int, np.integer)) or audio_windows_per_pass < 1:
         raise ValueError(f"audio_windows_per_pass must be an integer >= 1, not {audio_windows_per_pass!r}")
     check_tracks(kw.get("tracks"), kw.get("flag_heatmaps", False))
+    check_detect_size(kw.get("detect_size"), kw.get("detect_filter", "bilinear"), detector, detections)
     start_time = time.time()
     with open_avi(path) as avi:
+        check_detect_size(kw.get("detect_size"), kw.get("detect_filter", "bilinear"), detector, detections, (avi.height, avi.width))
         if "wav" in kw:
             wav, wav_sr = kw.pop("wav"), kw.pop("wav_sr", None)
         elif avi.pcm is None:
@@ -101,7 +106,7 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
                   flag_heatmaps: bool = False, model_heatmaps: str = "static", wav_sr: Optional[int] = None,
                   path_save_faces: Optional[str] = None, jpeg_entropy: str = "host", faces_via_jpeg: bool = False,
                   path_save_video: Optional[str] = None, video_model: str = "av", video_quality: int = 90, video_panel: bool = False,
-                  video_timing: Optional[Sequence[int]] = None, tracks=None):
+                  video_timing: Optional[Sequence[int]] = None, tracks=None, detect_size=None, detect_filter: str = "bilinear"):
     """engine: an `Engine` with the static, dynamic and audio weights loaded.  frames_bgr u8 [T,H,W,3] as cv2 decodes
     them; wav float32 [L] mono at `sr`; fps as `int(cv2.CAP_PROP_FPS)` gives it (get_face_images.py:23).
     `wav_sr`: `wav` is source audio at that rate instead -- int16 [L] / [L, C] as the frames lie in the WAV file ffmpeg writes
@@ -153,9 +158,18 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
     writers as the video `<name_video>__t<kk>`; the result video labels every selected track from its own prediction, the panel
     shows the first.  A named track without a record raises FileNotFoundError naming it before the visual models run, "all" without
     any record the same; anything that is not None, "all" or such a list, and `flag_heatmaps` together with `tracks` (heat maps
-    stay with track 00), raises ValueError before any work."""
+    stay with track 00), raises ValueError before any work.
+    `detect_size`: the detector runs on a smaller copy of the frames -- (height, width), or an int = the longest side -- resized on
+    the device with `detect_filter` ("box", "bilinear", "bicubic" or "lanczos": PIL's Image.resize, bit for bit; resize.py), and
+    its rows are mapped back to source pixels (face_tiles.ScaledDetector wraps `detector`); tracker, rectangles and crops stay at
+    full resolution.  The reference detects on whole frames (get_face_images.py:50): this departs from it on purpose, for HD
+    material, where the detector's cost grows with the pixel count.  None (the default): no wrapper is constructed and nothing
+    changes.  A size that shrinks neither side passes the frames straight through.  A value that is neither, an unknown filter, a
+    target larger than the frames, and `detect_size` beside `detections=` without a detector raise ValueError before any work."""
     tracks = check_tracks(tracks, flag_heatmaps)
     hm = _check_options(engine, video_model, jpeg_entropy, faces_via_jpeg, flag_heatmaps, model_heatmaps, window, sr)
+    check_detect_size(detect_size, detect_filter, detector, detections, None if np.ndim(frames_bgr) != 4 else tuple(frames_bgr.shape[1:3]))
+    detector = scaled_detector(detector, detect_size, detect_filter)
     start_time = time.time()                                                # run.py:200
     frames = frames_bgr if torch.is_tensor(frames_bgr) else torch.from_numpy(np.ascontiguousarray(frames_bgr))
     total_frames = int(frames.shape[0])
@@ -387,6 +401,8 @@ def _run_streamed(engine, avi, wav, wav_sr, fps, detector, detections, stream_fr
     o = _options(**kw)
     tracks = check_tracks(o.tracks, o.flag_heatmaps)
     hm = _check_options(engine, o.video_model, o.jpeg_entropy, o.faces_via_jpeg, o.flag_heatmaps, o.model_heatmaps, o.window, o.sr)
+    check_detect_size(o.detect_size, o.detect_filter, detector, detections, (avi.height, avi.width))
+    detector = scaled_detector(detector, o.detect_size, o.detect_filter)
     total, height, width, per = avi.n_frames, avi.height, avi.width, int(stream_frames)
     duration = total / fps if (fps and fps > 0 and total > 0) else None
     if detections is not None and len(detections) != total:

@@ -96,7 +96,9 @@ enum {
  *      avcer_annotate_frames (the result video's boxes and labels drawn into the frame batch) and its record struct avcer_draw_item
  *      joined under 8 the same way: one more symbol.
  *      avcer_tracker_create, avcer_tracker_push, avcer_tracker_last_error, avcer_tracker_destroy (the face tracker behind a handle:
- *      a video pushed in passes) joined under 8 the same way: four more symbols; avcer_track_faces keeps its argument list. */
+ *      a video pushed in passes) joined under 8 the same way: four more symbols; avcer_track_faces keeps its argument list.
+ *      avcer_resize_frames, avcer_resize_form (PIL's Image.resize of a frame batch on the device, for the detector on a smaller
+ *      copy) joined under 8 the same way: two more symbols, nothing that existed changed. */
 #define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
@@ -428,6 +430,32 @@ typedef struct avcer_draw_item {
 int avcer_annotate_frames(avcer_ctx* ctx, uint8_t* frames, int n, int h, int w, const avcer_draw_item* items, int m, const uint8_t* masks,
                           int64_t masks_bytes, const int32_t* table, int n_masks, const int32_t* work, int n_work, int64_t n_tiles,
                           avcer_stream_t stream);
+
+/* Image.resize of a batch of RGB frames, bit for bit PIL's (Pillow's Resample.c, 8 bits per channel) for its convolution
+ * filters BOX, BILINEAR, BICUBIC and LANCZOS with the default `box` and `reducing_gap=None`; HAMMING and NEAREST are not covered.
+ *   ref: PIL.Image.resize; this departs from the reference on purpose (data/get_face_images.py:50 feeds the detector whole frames).
+ * src u8 [n,h,w,3] -> dst u8 [n,h2,w2,3], both contiguous on the device, dst a buffer of its own.  Two separable passes with a u8
+ * value between them, horizontal first; per axis with `in` source and `out` output pixels, for output o and each channel:
+ *   value = clip(((1 << 21) + sum_{j < count[o]} source[first[o] + j] * kk[o][j]) >> 22, 0, 255)      (int32, arithmetic shift)
+ * The table of an axis is int32 [out * (2 + k)]: first[out], count[out], kk[out][k] back to back, built on the host in double
+ * exactly as Resample.c's precompute_coeffs / normalize_coeffs_8bpc build it (avcer_amd/resize.py resize_plan); an axis that
+ * keeps its size gets the identity table (first = o, count = 1, kk = 1 << 22), which reproduces PIL skipping that pass.
+ * xtab / ytab: the horizontal (in w, out w2, k = xk) and vertical (in h, out h2, k = yk) tables on the DEVICE; xtab_host /
+ * ytab_host: the same tables on the HOST, of which first and count are read -- to refuse a table with first < 0, count > k or
+ * first + count > in (AVCER_EINVAL), and to pick the form.  The kernels clamp their source index as well, so a device table that
+ * differs from the checked one gives wrong numbers, never a read outside the source.
+ * form: AVCER_RESIZE_CHOOSE, or one of the two forms by name (for tests; they give the same bits):
+ *   AVCER_RESIZE_FUSED     one launch: a block resizes the source rows its tile's vertical taps read horizontally into LDS and runs
+ *                          the vertical pass from there; AVCER_EINVAL when a tile's rows do not fit LDS (avcer_resize_form);
+ *   AVCER_RESIZE_TWO_PASS  two launches through a u8 intermediate [n,h,w2,3] in the context's workspace; an unchanged axis is skipped.
+ * Sides 1 .. AVCER_RESIZE_MAX_SIDE on both ends, up- and downscaling.  n = 0: nothing is launched.  No host synchronisation. */
+enum { AVCER_RESIZE_CHOOSE = 0, AVCER_RESIZE_FUSED = 1, AVCER_RESIZE_TWO_PASS = 2 };
+#define AVCER_RESIZE_MAX_SIDE 8192
+int avcer_resize_frames(avcer_ctx* ctx, const uint8_t* src, int n, int h, int w, uint8_t* dst, int h2, int w2, const int32_t* xtab_host,
+                        const int32_t* xtab, int xk, const int32_t* ytab_host, const int32_t* ytab, int yk, int form, avcer_stream_t stream);
+/* The form AVCER_RESIZE_CHOOSE takes for a vertical table (HOST pointer, h2 outputs): AVCER_RESIZE_FUSED or AVCER_RESIZE_TWO_PASS;
+ * AVCER_EINVAL for a null table or h2 outside 1 .. AVCER_RESIZE_MAX_SIDE.  Host code; nothing is launched. */
+int avcer_resize_form(const int32_t* ytab_host, int h2);
 
 /* The face tracker between detector and tiles, for a whole video in ONE call -- HOST code and HOST pointers (the tracker is
  * sequential in time and sees a handful of boxes per frame; the reference runs it on the host too):
