@@ -71,6 +71,9 @@ SIGNATURES = {
     "avcer_resize_frames": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_stream]),
     "avcer_resize_form": (C.c_int, [C.c_void_p, C.c_int]),
+    "avcer_chart_series": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                     C.c_int, C.c_void_p, c_stream]),
+    "avcer_chart_path": (C.c_int, [C.c_int64, C.c_int]),
     "avcer_weight_search_counts": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                              C.c_void_p, C.c_void_p, c_stream]),
     "avcer_audio_frame_mean": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,

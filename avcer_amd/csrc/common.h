@@ -24,7 +24,7 @@ struct DevBuf {
 
 // the context's workspace slots (ws_reserve): one per pipeline, the second lanes of the two ResNets and two utilities
 enum { WS_STATIC = 0, WS_DYNAMIC = 1, WS_AUDIO = 2, WS_FACE = 3, WS_NMS = 4, WS_CEILINGS = 5, WS_STATIC_LANE1 = 6, WS_FACE_LANE1 = 7,
-       WS_GRU = 8, WS_JPEG = 9, WS_RESIZE = 10, WS_COUNT = 11 };
+       WS_GRU = 8, WS_JPEG = 9, WS_RESIZE = 10, WS_CHART = 11, WS_COUNT = 12 };
 
 // how an activation tensor is stored (the `kind` / `act` arguments of the k_* launchers, Net::gemm's akind / okind)
 enum { KIND_F32 = 0, KIND_BF16 = 1, KIND_SP32 = 2 };

@@ -15,6 +15,7 @@ so frames and windows of different videos share passes here and every video stil
 """
 from __future__ import annotations
 
+import os
 import time
 from dataclasses import dataclass
 from typing import Callable, Optional, Sequence
@@ -235,7 +236,7 @@ def run_dataset(engine, jobs: Sequence[VideoJob], detector=None, *, mode: int = 
                 ce_weights_type: bool = True, ce_mask: bool = False, max_frames_per_pass: int = 2048,
                 max_windows_per_pass: int = 128, path_save_results: str = "", flag_save_prob: bool = False,
                 skip_failed: bool = False, distributed: bool = False, faces_via_jpeg: bool = False, detect_size=None,
-                detect_filter: str = "bilinear") -> DatasetResults:
+                detect_filter: str = "bilinear", flag_save_plot_pred: bool = False, plot_size: Sequence[int] = (200, 1200)) -> DatasetResults:
     """`run_inference` for every job of a set, with the videos sharing the GPU passes (module docstring).  Returns a
     `DatasetResults`: a list with one dict per job, in job order, holding `name` and the keys of `run_inference` -- av / vs / vd
     / a, compound_prob, static_probs, dynamic_logits, audio_rows, audio_frames, records -- with the bits `run_inference` gives for
@@ -250,6 +251,12 @@ def run_dataset(engine, jobs: Sequence[VideoJob], detector=None, *, mode: int = 
     `detect_size` / `detect_filter` (for the call): `run_inference`'s options of those names -- `detector` runs on a smaller copy of
     every job's frames (face_tiles.ScaledDetector) and is priced at its network's work on that copy.  None (the default): nothing
     changes.  A bad value, and a target larger than some job's frames, raise ValueError before any work.
+
+    `flag_save_plot_pred` / `plot_size` (for the call): `run_inference`'s option -- the prediction timeline chart of every video that
+    ran, as `<path_save_results>/<name>/pedicted_CEs_Rule N.jpg`, each file byte for byte that of the video's own `run_inference`
+    call (which writes it to its own `path_save_results`); the dict's `plot_pred` is the path.  ONE chart.write_charts call draws
+    the whole set from the fused class table where it lies on the device.  Off by default: nothing changes then.  What
+    run_inference refuses (no `path_save_results`, neither rule, an empty plot rectangle) raises ValueError before any work.
 
     Passes: at most `max_frames_per_pass` tiles per static-CNN call (and LSTM windows per LSTM call), at most
     `max_windows_per_pass` audio windows per audio call; device memory for tiles is one pass plus one video.
@@ -275,6 +282,11 @@ def run_dataset(engine, jobs: Sequence[VideoJob], detector=None, *, mode: int = 
     if max_frames_per_pass < 1 or max_windows_per_pass < 1:
         raise ValueError("run_dataset: pass sizes >= 1")
     check_via_jpeg(faces_via_jpeg)
+    plot = None
+    if flag_save_plot_pred is not False:
+        from . import chart
+
+        plot = chart.check_plot_pred(flag_save_plot_pred, path_save_results, ce_weights_type, ce_mask, plot_size)
     check_window(engine, window, sr)
     check_detect_size(detect_size, detect_filter, detector, [] if detector is None else None)
     for job in jobs if detect_size is not None else ():
@@ -362,6 +374,12 @@ def run_dataset(engine, jobs: Sequence[VideoJob], detector=None, *, mode: int = 
     for i, e in errors.items():
         out[i]["error"] = e
     if tables is not None:
+        if plot is not None:  # one batched call for the whole set, from the class table [4, sum T] on the device
+            plot_files = [chart.plot_paths(os.path.join(path_save_results, jobs[i].name), plot[0])[0] for i in ok]
+            base = chart.chart_plan(int(jobs[ok[0]].n_frames), width=plot[1][1], height=plot[1][0])
+            chart.write_charts(engine, tables[3], plot_files, T=[int(jobs[i].n_frames) for i in ok], plan=base)
+            for i, path in zip(ok, plot_files):
+                out[i]["plot_pred"] = path
         rows, win_logits, prob, am = (t.cpu().numpy() for t in tables)
         f_at = w_at = 0
         for i in ok:

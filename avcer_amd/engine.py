@@ -458,6 +458,50 @@ class Engine:
                                                  xp.ksize, yh.ctypes.data_as(C.c_void_p), _ptr(yd), yp.ksize, int(form), self._stream()))
         return out
 
+    def chart_path(self, T: int, pw: int) -> int:
+        """How avcer_chart_series' envelope treats a chart of T frames on pw columns (chart.PATH_REDUCE / PATH_SEGMENT): nothing is
+        launched."""
+        rc = self.lib.avcer_chart_path(int(T), int(pw))
+        if rc < 0:
+            raise AvcerError(rc, f"avcer_chart_path: {T} frames on {pw} columns")
+        return rc
+
+    def chart_series(self, preds, plans, out, colours=None):
+        """The traces of a batch of prediction charts (include/avcer_hip.h avcer_chart_series; the CPU statement is
+        chart.series_numpy): preds int32 / int64 [S, sum T] on the device, contiguous, S <= 4 -- the class tables of the charts back
+        to back --, plans: one chart.ChartPlan per chart, in that order (their T are the lengths); out uint8 [V, height, width, 3] on
+        the device, contiguous, already holding the background: painted IN PLACE and returned.  colours: S RGB triples
+        (chart.COLOURS).  A wrong dtype, shape, device or layout, and plans that do not fill the table, raise ValueError before any
+        launch; the class values are the caller's to check (chart.render does; the kernel clamps).  No host synchronisation."""
+        from . import chart as ch
+
+        if not (torch.is_tensor(preds) and preds.dim() == 2 and preds.dtype in (torch.int32, torch.int64) and preds.is_contiguous() and
+                preds.device == self.device):
+            raise ValueError(f"chart_series: preds must be a contiguous int32 or int64 [S, sum T] on {self.device}")
+        series, total = (int(v) for v in preds.shape)
+        plans = list(plans)
+        if not 1 <= series <= ch.MAX_SERIES:
+            raise ValueError(f"chart_series: {series} series (1..{ch.MAX_SERIES})")
+        if sum(p.T for p in plans) != total:
+            raise ValueError(f"chart_series: plans of {[p.T for p in plans]} frames over a table of {total} columns")
+        if not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.dim() == 4 and int(out.shape[0]) == len(plans) and
+                out.shape[-1] == 3 and out.is_contiguous() and out.device == self.device):
+            raise ValueError(f"chart_series: out must be a contiguous uint8 [{len(plans)},height,width,3] on {self.device}")
+        h, w = int(out.shape[1]), int(out.shape[2])
+        if any((p.height, p.width) != (h, w) for p in plans):
+            raise ValueError(f"chart_series: a plan of another picture size than out's {w} x {h}")
+        ink = np.ascontiguousarray(ch.COLOURS[:series] if colours is None else colours, dtype=np.uint8).reshape(-1)
+        if ink.size != 3 * series:
+            raise ValueError(f"chart_series: {series} RGB colours are needed")
+        if not plans:
+            return out
+        offsets = np.cumsum([0] + [p.T for p in plans[:-1]])
+        host = np.concatenate([p.record(int(o)) for p, o in zip(plans, offsets)])
+        dev = torch.from_numpy(host.view(np.uint8)).to(self.device, non_blocking=True)
+        self._check(self.lib.avcer_chart_series(self.ctx, _ptr(preds), preds.element_size(), series, total, host.ctypes.data_as(C.c_void_p),
+                                                _ptr(dev), len(plans), _ptr(out), h, w, ink.ctypes.data_as(C.c_void_p), self._stream()))
+        return out
+
     def weight_search_counts(self, preds, labels, weights):
         """Per-candidate argmax counts of the fusion weight search in one launch (include/avcer_hip.h
         avcer_weight_search_counts; data/utils.py:151-154, :176, :200).  preds [M, N, C] probability tables, labels [N],

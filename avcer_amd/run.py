@@ -6,7 +6,8 @@ wav at 16 kHz, CSV tables when `flag_save_prob` -- is replaced by arrays: decode
 waveform at 16 kHz -- or the source audio as it lies in the WAV file, with its rate (`wav_sr`) -- go in; per-frame predictions
 come out.  Grad-CAM heat maps (`flag_heatmaps`) come back as arrays and are written as JPEG files when a results path is given.
 The result video (`path_save_video`) is drawn on the device and written as a Motion-JPEG AVI file (avcer_amd/annotate.py); the
-reference's matplotlib plots are not part of this build.
+prediction timeline chart (`flag_save_plot_pred`) is drawn there too and written as a JPEG file (avcer_amd/chart.py), PIL's
+pixels, not matplotlib's.
 """
 from __future__ import annotations
 
@@ -55,6 +56,8 @@ def run_inference_file(engine, path, detector=None, detections: Optional[Sequenc
     `detect_size=` / `detect_filter=` (run_inference) hold for both paths too: a bad value is refused before the file is opened, an
     upscale once the container has named the frame size, before any decode; streamed, every pass is resized on its own (there is no
     state across frames), so the results are the in-memory call's.
+    `flag_save_plot_pred=` (run_inference) holds for both paths: what it refuses is refused before the file is opened; streamed, the
+    chart is made behind the last pass from the class tables the call keeps anyway, and the file is the in-memory call's.
     Returns run_inference's dict; `real_time_factor` includes demux and decode."""
     from . import jpeg
     from .avi import open_avi
@@ -66,6 +69,8 @@ def run_inference_file(engine, path, detector=None, detections: Optional[Sequenc
         raise ValueError(f"audio_windows_per_pass must be an integer >= 1, not {audio_windows_per_pass!r}")
     check_tracks(kw.get("tracks"), kw.get("flag_heatmaps", False))
     check_detect_size(kw.get("detect_size"), kw.get("detect_filter", "bilinear"), detector, detections)
+    _check_plot(kw.get("flag_save_plot_pred", False), kw.get("path_save_results", ""), kw.get("ce_weights_type", True), kw.get("ce_mask", False),
+                kw.get("plot_size", (200, 1200)))
     start_time = time.time()
     with open_avi(path) as avi:
         check_detect_size(kw.get("detect_size"), kw.get("detect_filter", "bilinear"), detector, detections, (avi.height, avi.width))
@@ -106,7 +111,8 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
                   flag_heatmaps: bool = False, model_heatmaps: str = "static", wav_sr: Optional[int] = None,
                   path_save_faces: Optional[str] = None, jpeg_entropy: str = "host", faces_via_jpeg: bool = False,
                   path_save_video: Optional[str] = None, video_model: str = "av", video_quality: int = 90, video_panel: bool = False,
-                  video_timing: Optional[Sequence[int]] = None, tracks=None, detect_size=None, detect_filter: str = "bilinear"):
+                  video_timing: Optional[Sequence[int]] = None, tracks=None, detect_size=None, detect_filter: str = "bilinear",
+                  flag_save_plot_pred: bool = False, plot_size: Sequence[int] = (200, 1200)):
     """engine: an `Engine` with the static, dynamic and audio weights loaded.  frames_bgr u8 [T,H,W,3] as cv2 decodes
     them; wav float32 [L] mono at `sr`; fps as `int(cv2.CAP_PROP_FPS)` gives it (get_face_images.py:23).
     `wav_sr`: `wav` is source audio at that rate instead -- int16 [L] / [L, C] as the frames lie in the WAV file ffmpeg writes
@@ -165,8 +171,20 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
     full resolution.  The reference detects on whole frames (get_face_images.py:50): this departs from it on purpose, for HD
     material, where the detector's cost grows with the pixel count.  None (the default): no wrapper is constructed and nothing
     changes.  A size that shrinks neither side passes the frames straight through.  A value that is neither, an unknown filter, a
-    target larger than the frames, and `detect_size` beside `detections=` without a detector raise ValueError before any work."""
+    target larger than the frames, and `detect_size` beside `detections=` without a detector raise ValueError before any work.
+    `flag_save_plot_pred` (run.py:272-296, visualize.py:175-215): the prediction timeline chart, the compound class of AV, VS, VD
+    and A against the frame number, written as `<path_save_results>/pedicted_CEs_Rule N.jpg` (the reference's spelling; N = 2 with
+    `ce_weights_type`, else 1 with `ce_mask`, as run.py:281-284 picks it); `out["plot_pred"]` is the path.  `plot_size` = (height,
+    width) of the picture.  Drawn on the device from the class tables where the fusion left them (chart.write_charts: one
+    avcer_chart_series call, one annotate call, the JPEG encoder) -- the tables are not copied to the host for it.  With `tracks`
+    one chart per selected track in that one call: the first under the name above, every other track k as
+    `pedicted_CEs_Rule N__t<kk>.jpg`, and `out["tracks"][k]["plot_pred"]` holds its path.  The pixels are PIL's (ImageDraw.line,
+    ImageDraw.bitmap, Image.save), bit for bit; matplotlib's are not claimed.  The reference switches this on by default; here it
+    is off unless asked for, like every option, and nothing changes then.  Without `path_save_results`, with neither `ce_mask` nor
+    `ce_weights_type` (the reference dies on an unbound `rule`), and with a `plot_size` that leaves no plot rectangle, ValueError
+    before any work."""
     tracks = check_tracks(tracks, flag_heatmaps)
+    plot = _check_plot(flag_save_plot_pred, path_save_results, ce_weights_type, ce_mask, plot_size)
     hm = _check_options(engine, video_model, jpeg_entropy, faces_via_jpeg, flag_heatmaps, model_heatmaps, window, sr)
     check_detect_size(detect_size, detect_filter, detector, detections, None if np.ndim(frames_bgr) != 4 else tuple(frames_bgr.shape[1:3]))
     detector = scaled_detector(detector, detect_size, detect_filter)
@@ -262,7 +280,7 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
     # MODE_F16X3: one read of the range-contract counter behind the last launch; a video during which an activation left fp16's
     # range is run again in MODE_FP32 (engine.guarded)
     out = _results(engine, engine.guarded(mode, gpu_work), host, frames, wav, wav_sr, fps, path_save_results, name_video, flag_save_prob, model_heatmaps, path_save_video, video_model, video_quality,
-                   video_panel, video_timing)
+                   video_panel, video_timing, plot)
     # "Real-time factor for compound expression prediction" as run.py:304-307 prints it: elapsed / video duration (the
     # device -> host copies above have synchronised the stream, so the clock covers all the work); None where the
     # container reported no frame rate
@@ -287,6 +305,16 @@ def _check_options(engine, video_model, jpeg_entropy, faces_via_jpeg, flag_heatm
     return hm
 
 
+def _check_plot(flag_save_plot_pred, path_save_results, ce_weights_type, ce_mask, plot_size):
+    """`flag_save_plot_pred` off (the default): None, and the chart module is not even imported.  On: what chart.check_plot_pred
+    refuses is refused here, before any work; returns (rule, (height, width))."""
+    if flag_save_plot_pred is False:
+        return None
+    from .chart import check_plot_pred
+
+    return check_plot_pred(flag_save_plot_pred, path_save_results, ce_weights_type, ce_mask, plot_size)
+
+
 def _side_stream(engine):
     """The engine's second stream: the audio branch runs on it beside the visual one."""
     side = engine.__dict__.get("_side_stream")
@@ -296,14 +324,23 @@ def _side_stream(engine):
 
 
 def _results(engine, res, host, frames, wav, wav_sr, fps, path_save_results, name_video, flag_save_prob, model_heatmaps, path_save_video,
-             video_model, video_quality, video_panel, video_timing):
+             video_model, video_quality, video_panel, video_timing, plot=None):
     """Everything behind the guarded device work, for the in-memory and the streamed call alike: the tables to the host, the CSV
-    files, the heat-map files, the result video.  `res` is gpu_work's tuple; `frames`: the decoded frames, or -- streamed -- a
+    files, the heat-map files, the result video, the prediction chart (`plot`: _check_plot's pair).  `res` is gpu_work's tuple; `frames`: the decoded frames, or -- streamed -- a
     callable that yields them once more in passes (annotate.write_result_video)."""
     static_probs, dynamic_logits, win_logits, lo, hi, prob, am, maps = res
     records = host["records"]
     rows, aud_frames = replicate_per_frame(win_logits.cpu().numpy(), lo, hi)
     tp = host.get("tracks_plan")
+    plot_files = None
+    if plot is not None:
+        # am int32 [4, T], or [4, K, T] with tracks: K charts back to back in ONE call, read where the fusion left them
+        from . import chart
+
+        n_frames = int(am.shape[-1])
+        plot_files = chart.plot_paths(path_save_results, plot[0], None if tp is None else tp.tracks)
+        chart.write_charts(engine, am.reshape(am.shape[0], -1), plot_files, T=[n_frames] * len(plot_files),
+                           plan=chart.chart_plan(n_frames, width=plot[1][1], height=plot[1][0]))
     am, prob, static_probs, dynamic_logits = am.cpu().numpy(), prob.cpu().numpy(), static_probs.cpu().numpy(), dynamic_logits.cpu().numpy()
     per_track = None
     if tp is not None:
@@ -329,6 +366,10 @@ def _results(engine, res, host, frames, wav, wav_sr, fps, path_save_results, nam
                records=records)
     if per_track is not None:
         out["tracks"] = per_track
+    if plot_files is not None:
+        out["plot_pred"] = plot_files[0]
+        for k, path in zip(tp.tracks if tp is not None else (), plot_files):
+            per_track[k]["plot_pred"] = path
     if "face_files" in host:
         out["face_files"] = host["face_files"]
     if maps is not None:
@@ -402,6 +443,7 @@ def _run_streamed(engine, avi, wav, wav_sr, fps, detector, detections, stream_fr
     tracks = check_tracks(o.tracks, o.flag_heatmaps)
     hm = _check_options(engine, o.video_model, o.jpeg_entropy, o.faces_via_jpeg, o.flag_heatmaps, o.model_heatmaps, o.window, o.sr)
     check_detect_size(o.detect_size, o.detect_filter, detector, detections, (avi.height, avi.width))
+    plot = _check_plot(o.flag_save_plot_pred, o.path_save_results, o.ce_weights_type, o.ce_mask, o.plot_size)
     detector = scaled_detector(detector, o.detect_size, o.detect_filter)
     total, height, width, per = avi.n_frames, avi.height, avi.width, int(stream_frames)
     duration = total / fps if (fps and fps > 0 and total > 0) else None
@@ -519,6 +561,6 @@ def _run_streamed(engine, avi, wav, wav_sr, fps, detector, detections, stream_fr
 
     res = engine.guarded(o.mode, gpu_work)
     out = _results(engine, res, host, lambda: (decode(a) for a in range(0, total, per)), wav, wav_sr, fps, o.path_save_results, o.name_video,
-                   o.flag_save_prob, o.model_heatmaps, o.path_save_video, o.video_model, o.video_quality, o.video_panel, o.video_timing)
+                   o.flag_save_prob, o.model_heatmaps, o.path_save_video, o.video_model, o.video_quality, o.video_panel, o.video_timing, plot)
     out["real_time_factor"] = (time.time() - start_time) / duration if duration else None
     return out

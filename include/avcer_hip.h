@@ -98,7 +98,9 @@ enum {
  *      avcer_tracker_create, avcer_tracker_push, avcer_tracker_last_error, avcer_tracker_destroy (the face tracker behind a handle:
  *      a video pushed in passes) joined under 8 the same way: four more symbols; avcer_track_faces keeps its argument list.
  *      avcer_resize_frames, avcer_resize_form (PIL's Image.resize of a frame batch on the device, for the detector on a smaller
- *      copy) joined under 8 the same way: two more symbols, nothing that existed changed. */
+ *      copy) joined under 8 the same way: two more symbols, nothing that existed changed.
+ *      avcer_chart_series, avcer_chart_path (the traces of the prediction timeline chart) and the record struct avcer_chart_plan
+ *      joined under 8 the same way: two more symbols, nothing that existed changed. */
 #define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
@@ -456,6 +458,42 @@ int avcer_resize_frames(avcer_ctx* ctx, const uint8_t* src, int n, int h, int w,
 /* The form AVCER_RESIZE_CHOOSE takes for a vertical table (HOST pointer, h2 outputs): AVCER_RESIZE_FUSED or AVCER_RESIZE_TWO_PASS;
  * AVCER_EINVAL for a null table or h2 outside 1 .. AVCER_RESIZE_MAX_SIDE.  Host code; nothing is launched. */
 int avcer_resize_form(const int32_t* ytab_host, int h2);
+
+/* The traces of the prediction timeline chart, for a batch of charts in one call: per chart the compound class of up to four
+ * models against the frame number, as dotted lines in four colours.
+ *   ref: run.py:272-296 (flag_save_plot_pred), visualization/visualize.py:175-215 plot_compound_expression_prediction.  matplotlib
+ *   is not reproduced: the claim is identity with PIL's ImageDraw.line(width=1), tolerance zero (avcer_amd/chart.py chart_numpy is
+ *   the CPU statement; frame, ticks, titles and legend are drawn behind this call by avcer_annotate_frames).
+ * table: `series` rows of `stride` classes (0 .. AVCER_CHART_CLASSES - 1), int32 (elem_bytes 4) or int64 (8), on the device; chart v
+ * reads the columns offset .. offset + length - 1 of every row.  Per chart a record: the plot rectangle (x0, y0, pw, ph) inside the
+ * picture, the row centre yc[c] of every class (inside the rectangle), and its offset and length.  Frame i of a chart of T frames
+ * stands in column x0 + ((2i + 1) * pw) / (2T) (64-bit) at row yc[class]; the trace of a series is the union of PIL's lines between
+ * consecutive frames (a lone frame: its point), widened by one row up and down, clipped to the rectangle, and thinned: pixel
+ * (x, y) of series s is painted iff (x + y) % 4 == s, with colours[3s .. 3s + 2].  No two series contend for a pixel.
+ * plans_host / plans: the same n_charts records on the HOST (checked: AVCER_EINVAL for a rectangle that is empty or leaves the
+ * picture, a row centre outside it, a length < 1 or columns behind the stride) and on the DEVICE (read by the kernels, which
+ * bound every address themselves, so a device copy that differs gives wrong pixels, never an access outside table or out).
+ * colours: HOST, 3 * series bytes.  out u8 [n_charts, h, w, 3] on the device, already holding the background; uncovered pixels
+ * are neither read nor written.  Sides 1 .. AVCER_CHART_MAX_SIDE.  A class outside the range is clamped: the caller refuses it.
+ * Two launches -- an envelope of one row interval per (chart, series, column) in the context's workspace, then the paint -- and
+ * none for n_charts = 0.  No host synchronisation. */
+#define AVCER_CHART_CLASSES 7
+#define AVCER_CHART_MAX_SERIES 4
+#define AVCER_CHART_MAX_SIDE 16384
+typedef struct avcer_chart_plan {
+    int32_t x0, y0, pw, ph;
+    int32_t yc[AVCER_CHART_CLASSES];
+    int32_t pad;
+    int64_t offset, length;
+} avcer_chart_plan; /* 64 bytes */
+int avcer_chart_series(avcer_ctx* ctx, const void* table, int elem_bytes, int series, int64_t stride, const avcer_chart_plan* plans_host,
+                       const avcer_chart_plan* plans, int n_charts, uint8_t* out, int h, int w, const uint8_t* colours,
+                       avcer_stream_t stream);
+/* How the envelope treats a chart of `frames` frames on a plot `pw` columns wide: AVCER_CHART_REDUCE (frames >= pw: a column holds
+ * frames / pw frames or more and reduces them over a wave) or AVCER_CHART_SEGMENT (frames < pw: a column evaluates the one segment
+ * that crosses it); AVCER_EINVAL for frames < 1 or pw outside 1 .. AVCER_CHART_MAX_SIDE.  Host code; nothing is launched. */
+enum { AVCER_CHART_REDUCE = 1, AVCER_CHART_SEGMENT = 2 };
+int avcer_chart_path(int64_t frames, int pw);
 
 /* The face tracker between detector and tiles, for a whole video in ONE call -- HOST code and HOST pointers (the tracker is
  * sequential in time and sees a handful of boxes per frame; the reference runs it on the host too):
