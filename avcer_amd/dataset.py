@@ -29,7 +29,7 @@ from .audio_pipeline import check_window, chunk_spans, replicate_per_frame, resa
 from .engine import MODE_DEFAULT, MODE_F16X3, MODE_FP32
 from .face_tiles import check_detect_size, check_via_jpeg, scaled_detector
 from .fusion import MODEL_ORDER, covered_frames
-from .video_pipeline import plan_clip
+from .video_pipeline import _DevicePlan, _tables, clips_plan
 
 
 @dataclass
@@ -86,18 +86,15 @@ class DatasetResults(list):
 
 
 def ragged_plan(presents, fpss):
-    """`plan_clip` over a set of videos with their own frame rates: (static_src [N], dyn_src [N], windows [n_win,10], n_feat),
-    row numbers counted through the set; -1 = the zero row, as in ClipPlan."""
-    s_src, d_src, win, fb, wb = [], [], [], 0, 0
-    for present, fps in zip(presents, fpss):
-        p = plan_clip(present, fps, fb, wb)
-        fb += int(np.asarray(present, dtype=bool).sum())
-        wb += len(p.windows)
-        s_src += p.static_src
-        d_src += p.dyn_src
-        win += p.windows
-    return (np.asarray(s_src, dtype=np.int64), np.asarray(d_src, dtype=np.int64),
-            np.asarray(win, dtype=np.int32).reshape(-1, 10), fb)
+    """`plan_clip` over a set of videos with their own frame rates -- video_pipeline.clips_plan with a mask and a frame rate per
+    video: (static_src [N], dyn_src [N], windows [n_win,10], n_feat), row numbers counted through the set; -1 = the zero row."""
+    s_src, d_src, win, f_off, _ = clips_plan(presents, fpss)
+    return s_src, d_src, win, int(f_off[-1])
+
+
+def _cat(parts):
+    """The passes' outputs as one tensor (None when there was no pass); a single pass is not copied."""
+    return None if not parts else parts[0] if len(parts) == 1 else torch.cat(parts)
 
 
 def _n_audio(job: VideoJob, sr: int) -> int:
@@ -118,10 +115,9 @@ def _track00(engine, job: VideoJob, dets):
     return records, rows[np.argsort(records[rows, 0], kind="stable")]
 
 
-def _local_tables(engine, jobs, idx, plans, detector, m, sr, window, padding, max_frames, max_windows, side, passes, via_jpeg=False):
+def _local_tables(engine, jobs, idx, plans, detector, m, sr, window, padding, max_frames, max_windows, passes, via_jpeg=False):
     """Stages 0 to audio for the videos `idx` (ascending): (stat|dyn rows [sum frames, 14], window logits [sum windows, c])."""
     dev = engine.device
-    main = torch.cuda.current_stream(dev)
     win_a = int(window * sr)
     w_off = np.concatenate([[0], np.cumsum([len(plans[i]["starts"]) for i in idx])]).astype(np.int64)
     s_off = np.concatenate([[0], np.cumsum([plans[i]["n_audio"] for i in idx])]).astype(np.int64)
@@ -129,9 +125,9 @@ def _local_tables(engine, jobs, idx, plans, detector, m, sr, window, padding, ma
         raise ValueError(f"run_dataset: {int(s_off[-1])} audio samples in one set (the chunker takes 2^31 - 1): split the set")
     starts = np.concatenate([plans[i]["starts"] + s_off[k] for k, i in enumerate(idx)] or [np.zeros(0, np.int64)])
     ends = np.concatenate([plans[i]["ends"] + s_off[k] for k, i in enumerate(idx)] or [np.zeros(0, np.int64)])
-    side.wait_stream(main)
-    joined = False
-    try:
+    # a failure in stage 0 or in load() unwinds through the join: no launch of this call outlives it (Engine.side_branch)
+    with engine.side_branch() as branch:
+        side = branch.stream
         with torch.cuda.stream(side):
             wav_all = torch.empty(int(s_off[-1]), dtype=torch.float32, device=dev)
         a_done, a_out = 0, []
@@ -197,38 +193,12 @@ def _local_tables(engine, jobs, idx, plans, detector, m, sr, window, padding, ma
         passes["at"] = None
         static_passes(True)
         audio_passes(int(w_off[-1]), True)
-        # ragged LSTM plan over the whole set, then the per-frame tables by row gathers (video_pipeline.visual_forward)
-        s_src, d_src, win, n_feat = ragged_plan(presents, [jobs[i].fps for i in idx])
-        n = len(s_src)
-        zero = torch.zeros(1, 7, device=dev)
-        if n_feat:
-            assert win.size == 0 or (win.min() >= 0 and win.max() < n_feat)
-            feats_t = feats[0] if len(feats) == 1 else torch.cat(feats)
-            probs_t = probs[0] if len(probs) == 1 else torch.cat(probs)
-            stat = torch.cat([probs_t, zero]).index_select(0, torch.from_numpy(np.where(s_src >= 0, s_src, n_feat)).to(dev))
-            if len(win):
-                win_d = torch.from_numpy(win).to(dev)
-                dl = []
-                for a in range(0, len(win), max_frames):
-                    dl.append(engine.dynamic_forward(engine.gather_windows(feats_t, win_d[a:a + max_frames], validated=True), m))
-                    passes["lstm"].append(int(dl[-1].shape[0]))
-                dyn = torch.cat(dl + [zero]).index_select(0, torch.from_numpy(np.where(d_src >= 0, d_src, len(win))).to(dev))
-            else:
-                dyn = torch.zeros(n, 7, device=dev)
-        else:
-            stat = torch.zeros(n, 7, device=dev)
-            dyn = torch.zeros(n, 7, device=dev)
-        main.wait_stream(side)
-        joined = True
-        c = engine.audio_classes
-        win_logits = (a_out[0] if len(a_out) == 1 else torch.cat(a_out)) if a_out else torch.zeros(0, c, device=dev)
-        win_logits.record_stream(main)
-        return torch.cat([stat, dyn], dim=1), win_logits
-    finally:
-        # a failure in stage 0 or in load() unwinds from here: the audio work already queued on `side` is joined all the same,
-        # so that no launch of this call outlives it (run.run_inference)
-        if not joined:
-            main.wait_stream(side)
+        # ragged LSTM plan over the whole set, then the per-frame tables by row gathers (video_pipeline._tables)
+        plan = _DevicePlan(engine, None, None, clips_plan(presents, [jobs[i].fps for i in idx]))
+        stat, dyn, _ = _tables(engine, plan, _cat(probs), _cat(feats), sum(len(p) for p in presents), m, max_frames, passes["lstm"])
+        branch.results(*a_out)
+    win_logits = _cat(a_out) if a_out else torch.zeros(0, engine.audio_classes, device=dev)
+    return torch.cat([stat, dyn], dim=1), win_logits
 
 
 def run_dataset(engine, jobs: Sequence[VideoJob], detector=None, *, mode: int = MODE_DEFAULT, sr: int = 16000, window: float = 4,
@@ -328,9 +298,6 @@ def run_dataset(engine, jobs: Sequence[VideoJob], detector=None, *, mode: int = 
             return float(detector.gflop_at(j.height, j.width))
         return True if getattr(detector, "kind", 1) == 1 else float(detector.gflop_per_frame)
     shards = adist.shard_videos([adist.video_cost(j, window, det_cost(j), sr, step) for j in jobs], world)
-    side = engine.__dict__.get("_side_stream")
-    if side is None:
-        side = engine.__dict__["_side_stream"] = torch.cuda.Stream(engine.device)
     passes = {}
 
     def local(m):
@@ -342,7 +309,7 @@ def run_dataset(engine, jobs: Sequence[VideoJob], detector=None, *, mode: int = 
                 return (torch.zeros(0, 14, device=engine.device), torch.zeros(0, max(engine.audio_classes, 1), device=engine.device))
             try:
                 return _local_tables(engine, jobs, mine, plans, detector, m, sr, window, padding, int(max_frames_per_pass),
-                                     int(max_windows_per_pass), side, passes, bool(faces_via_jpeg))
+                                     int(max_windows_per_pass), passes, bool(faces_via_jpeg))
             except (ValueError, FileNotFoundError) as e:
                 bad = passes["at"]
                 if bad is None:

@@ -5,6 +5,7 @@ the hot path runs inside libavcer_hip.so.  All methods raise AvcerError on a non
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import weakref
 
@@ -80,6 +81,16 @@ class FaceTracker:
             pass
 
 
+class _SideBranch:
+    """What Engine.side_branch hands out: the side stream, and the tensors named as its results."""
+
+    def __init__(self, stream):
+        self.stream, self.named = stream, []
+
+    def results(self, *tensors):
+        self.named.extend(tensors)
+
+
 _LIVE = {}  # device index -> weak references to the engines created for it, oldest first (Engine.live)
 
 
@@ -111,6 +122,7 @@ class Engine:
         self.audio_classes = 0
         self.x3_fallbacks = 0  # calls `guarded` had to repeat in MODE_FP32 (the x3 range contract was broken)
         self._resample_cache = {}  # (orig_freq, new_freq) -> (plan, taps [span, n] and first [n] on the device): Engine.resample
+        self._side_stream = None   # Engine.side_branch creates it on first use
         self._resize_cache = {}    # (in, out, filter) -> (plan, its packed table on the host and on the device): Engine.resize_frames
 
     def close(self):
@@ -168,6 +180,35 @@ class Engine:
             self.x3_fallbacks += 1
             out = call(MODE_FP32)
         return out
+
+    # ------------------------------------------------------------------ the audio branch beside the visual one
+    @contextlib.contextmanager
+    def side_branch(self, *inputs):
+        """Work beside the current stream, on the engine's ONE side stream (created here, on first use): the audio branch depends on
+        nothing of the visual one and runs there while the caller's stream (and the host: tracker, plans) goes on.
+            with engine.side_branch(wav) as side:
+                with torch.cuda.stream(side.stream):
+                    logits = ...          # queued on the side stream
+                side.results(logits)      # what the caller's stream reads behind the join
+                ...                       # the visual branch, on the caller's stream
+            # joined
+        Entry forks the side stream from the current one; `inputs`, tensors allocated on the current stream, are record_stream'ed on
+        the side stream (the allocator must not hand them out while it still reads them).  EVERY exit, an exception included, joins
+        the side stream back and record_stream's the named results on the caller's stream: no launch queued here outlives the block
+        -- the workspace and the range-contract counter belong to the next call (`guarded` reads the counter behind the join)."""
+        if self._side_stream is None:
+            self._side_stream = torch.cuda.Stream(self.device)
+        main, branch = torch.cuda.current_stream(self.device), _SideBranch(self._side_stream)
+        branch.stream.wait_stream(main)
+        for t in inputs:
+            if torch.is_tensor(t) and t.is_cuda:  # a host input is copied by the kernel wrapper, on the stream that reads it
+                t.record_stream(branch.stream)
+        try:
+            yield branch
+        finally:
+            main.wait_stream(branch.stream)
+            for t in branch.named:
+                t.record_stream(main)
 
     # ------------------------------------------------------------------ weights
     def _load(self, fn, tensors):

@@ -27,7 +27,6 @@ class AVPipeline:
         # default is what bench.py times; its roofline pass switches it off, because co-running kernels make per-launch HIP-event
         # durations meaningless.
         self.overlap_branches = True
-        self._audio_stream = None
 
     def clip_records(self, frames_u8: torch.Tensor, wav: torch.Tensor, fps: float = 25, present=None):
         """frames_u8 [N,T,224,224,3], wav [N,L] (one window per clip).  Returns the per-clip record that is
@@ -44,17 +43,12 @@ class AVPipeline:
             stat, dyn = visual_forward(self.engine, frames_u8, present, fps, mode)
             aud = self.engine.audio_forward(wav, normalize=True, mode=mode)
             return stat, dyn, aud
-        dev = self.engine.device
-        main = torch.cuda.current_stream(dev)
-        if getattr(self, "_audio_stream", None) is None:
-            self._audio_stream = torch.cuda.Stream(dev)
-        side = self._audio_stream
-        side.wait_stream(main)  # the inputs were produced on the caller's stream
-        with torch.cuda.stream(side):
-            aud = self.engine.audio_forward(wav, normalize=True, mode=mode)
-        stat, dyn = visual_forward(self.engine, frames_u8, present, fps, mode)
-        main.wait_stream(side)
-        aud.record_stream(main)
+        # `wav` was produced on the caller's stream; a failure in the visual branch joins the audio launches all the same
+        with self.engine.side_branch(wav) as side:
+            with torch.cuda.stream(side.stream):
+                aud = self.engine.audio_forward(wav, normalize=True, mode=mode)
+            side.results(aud)
+            stat, dyn = visual_forward(self.engine, frames_u8, present, fps, mode)
         return stat, dyn, aud
 
     def fuse_records(self, stat, dyn, aud, weights_1=WEIGHTS_AV_1, weights_2=(1, 1, 1), ce_weights_type=False,

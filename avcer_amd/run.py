@@ -8,23 +8,72 @@ come out.  Grad-CAM heat maps (`flag_heatmaps`) come back as arrays and are writ
 The result video (`path_save_video`) is drawn on the device and written as a Motion-JPEG AVI file (avcer_amd/annotate.py); the
 prediction timeline chart (`flag_save_plot_pred`) is drawn there too and written as a JPEG file (avcer_amd/chart.py), PIL's
 pixels, not matplotlib's.
+
+The pipeline is stated once, as a loop over the passes of a frame source (_run): run_inference gives it the frames as one pass,
+run_inference_file(stream_frames=N) the open recording in passes of N frames.
 """
 from __future__ import annotations
 
 import os
 import time
+from dataclasses import dataclass
 from typing import Optional, Sequence
 
 import numpy as np
 import torch
 
-from . import io_formats
+from . import io_formats, jpeg
 from .audio_pipeline import audio_forward, check_window, replicate_per_frame, resample_plan
 from .engine import MODE_DEFAULT
-from .face_tiles import (VideoTiler, check_detect_size, check_tracks, check_via_jpeg, face_crop_paths, pass_rects, roundtrip_face_tiles,
-                         scaled_detector, select_tracks, track_clip, write_face_crops)
+from .face_tiles import (check_detect_size, check_tracks, check_via_jpeg, pass_rects, roundtrip_face_tiles, scaled_detector, select_tracks,
+                         write_face_crops)
 from .fusion import MODEL_ORDER, fuse, fuse_tracks
-from .video_pipeline import tracks_plan, visual_forward, visual_from_static, visual_from_static_tracks
+from .video_pipeline import lstm_step, tracks_plan, visual_from_static, visual_from_static_tracks
+
+
+@dataclass
+class _Options:
+    """run_inference's keyword options and their defaults, stated once (what each means: run_inference's docstring).  Both calls bind
+    their keyword arguments to it, so an unknown name is Python's own TypeError naming it, and the pass loop reads one object."""
+    path_save_results: str = ""
+    name_video: str = "video"
+    flag_save_prob: bool = False
+    weights_prob_model: object = None
+    weights_model: Sequence = (1, 1, 1)
+    ce_weights_type: bool = True
+    ce_mask: bool = False
+    sr: int = 16000
+    window: float = 4
+    step: float = 0.5
+    padding: str = "mean"
+    mode: int = MODE_DEFAULT
+    flag_heatmaps: bool = False
+    model_heatmaps: str = "static"
+    wav_sr: Optional[int] = None
+    path_save_faces: Optional[str] = None
+    jpeg_entropy: str = "host"
+    faces_via_jpeg: bool = False
+    path_save_video: Optional[str] = None
+    video_model: str = "av"
+    video_quality: int = 90
+    video_panel: bool = False
+    video_timing: Optional[Sequence[int]] = None
+    tracks: object = None
+    detect_size: object = None
+    detect_filter: str = "bilinear"
+    flag_save_plot_pred: bool = False
+    plot_size: Sequence[int] = (200, 1200)
+
+
+class _Source:
+    """A video as the pass loop reads it: `total` frames of `height` x `width` in passes of `per` frames; `decode(a)` returns the pass
+    that starts at frame a, uint8 [<= per, height, width, 3] BGR on the device."""
+
+    def __init__(self, total: int, height: int, width: int, per: int, decode):
+        self.total, self.height, self.width, self.per, self.decode = int(total), int(height), int(width), int(per), decode
+
+    def passes(self):
+        return (self.decode(a) for a in range(0, self.total, self.per))
 
 
 def run_inference_file(engine, path, detector=None, detections: Optional[Sequence[np.ndarray]] = None, fps: Optional[float] = None,
@@ -43,9 +92,9 @@ def run_inference_file(engine, path, detector=None, detections: Optional[Sequenc
     source's timing and sound, sample for sample.
     `stream_frames`: None (the default) decodes the whole file onto the device and calls run_inference, so memory grows with the
     recording (6.2 MB per 1920 x 1080 frame, and the detector's outputs as much again).  An integer N >= 1 runs the file through the
-    same pipeline in passes of N frames instead (_run_streamed): at most N decoded frames -- one pass buffer, decode and compute are
-    not overlapped -- are alive on the device, whatever the length, and the dict, the CSV files, the face folders, the heat maps and
-    the result video are the in-memory call's, bit for bit.  Only the PCM of the whole file stays on the device (30 minutes of
+    same pass loop (_run) in passes of N frames instead of one pass holding all: at most N decoded frames -- one pass buffer, decode
+    and compute are not overlapped -- are alive on the device, whatever the length, and the dict, the CSV files, the face folders, the
+    heat maps and the result video are the in-memory call's, bit for bit (the loop's results do not depend on its pass size).  Only the PCM of the whole file stays on the device (30 minutes of
     44.1 kHz stereo: 318 MB), and the audio windows go through the model `audio_windows_per_pass` at a time (streamed calls only).
     With `path_save_video` the file is decoded a second time behind the fusion, which the labels need.  "No face track 00" is
     known at the end of the sweep and raises the same FileNotFoundError there.  Anything but None or an int >= 1 (0, a negative, a
@@ -59,7 +108,6 @@ def run_inference_file(engine, path, detector=None, detections: Optional[Sequenc
     `flag_save_plot_pred=` (run_inference) holds for both paths: what it refuses is refused before the file is opened; streamed, the
     chart is made behind the last pass from the class tables the call keeps anyway, and the file is the in-memory call's.
     Returns run_inference's dict; `real_time_factor` includes demux and decode."""
-    from . import jpeg
     from .avi import open_avi
 
     if stream_frames is not None and (isinstance(stream_frames, (bool, np.bool_)) or not isinstance(stream_frames, (int, np.integer))
@@ -67,53 +115,49 @@ def run_inference_file(engine, path, detector=None, detections: Optional[Sequenc
         raise ValueError(f"stream_frames must be None or an integer >= 1, not {stream_frames!r}")
     if isinstance(audio_windows_per_pass, (bool, np.bool_)) or not isinstance(audio_windows_per_pass, (int, np.integer)) or audio_windows_per_pass < 1:
         raise ValueError(f"audio_windows_per_pass must be an integer >= 1, not {audio_windows_per_pass!r}")
-    check_tracks(kw.get("tracks"), kw.get("flag_heatmaps", False))
-    check_detect_size(kw.get("detect_size"), kw.get("detect_filter", "bilinear"), detector, detections)
-    _check_plot(kw.get("flag_save_plot_pred", False), kw.get("path_save_results", ""), kw.get("ce_weights_type", True), kw.get("ce_mask", False),
-                kw.get("plot_size", (200, 1200)))
+    given_wav = "wav" in kw
+    wav = kw.pop("wav", None)
+    kw.setdefault("name_video", os.path.splitext(os.path.basename(os.fspath(path)))[0])
+    o = _Options(**kw)
+    check_tracks(o.tracks, o.flag_heatmaps)
+    check_detect_size(o.detect_size, o.detect_filter, detector, detections)
+    _check_plot(o)
     start_time = time.time()
     with open_avi(path) as avi:
-        check_detect_size(kw.get("detect_size"), kw.get("detect_filter", "bilinear"), detector, detections, (avi.height, avi.width))
-        if "wav" in kw:
-            wav, wav_sr = kw.pop("wav"), kw.pop("wav_sr", None)
-        elif avi.pcm is None:
-            raise ValueError(f"{avi.path}: no audio stream (pass wav= and wav_sr= to give the audio some other way)")
-        else:
-            wav, wav_sr = avi.pcm, kw.pop("wav_sr", avi.audio_rate)
-        if wav_sr is not None:
-            resample_plan(wav_sr, kw.get("sr", 16000))
-        check_window(engine, kw.get("window", 4), kw.get("sr", 16000))
+        check_detect_size(o.detect_size, o.detect_filter, detector, detections, (avi.height, avi.width))
+        if not given_wav:
+            if avi.pcm is None:
+                raise ValueError(f"{avi.path}: no audio stream (pass wav= and wav_sr= to give the audio some other way)")
+            wav = avi.pcm
+            if "wav_sr" not in kw:
+                o.wav_sr = avi.audio_rate
+        if o.wav_sr is not None:
+            resample_plan(o.wav_sr, o.sr)
+        check_window(engine, o.window, o.sr)
         if detections is None and detector is None:
             raise ValueError("give a detector or the per-frame detections")
         fps = int(avi.rate / avi.scale) if fps is None else fps
+        if o.path_save_video and "video_timing" not in kw:
+            o.video_timing = (avi.rate, avi.scale)  # the source's own rate / scale pair, not the rounded fps
         if stream_frames is not None:
-            kw.setdefault("name_video", os.path.splitext(os.path.basename(os.fspath(path)))[0])
-            if kw.get("path_save_video"):
-                kw.setdefault("video_timing", (avi.rate, avi.scale))
-            return _run_streamed(engine, avi, wav, wav_sr, fps, detector, detections, int(stream_frames), int(audio_windows_per_pass),
-                                 frames_per_pass, start_time, **kw)
+            per = int(stream_frames)
+            src = _Source(avi.n_frames, avi.height, avi.width, per, lambda a: jpeg.decode_frames(
+                engine, avi.frames[a:a + per], avi.height, avi.width, bgr=True, frames_per_pass=frames_per_pass)[0])
+            return _run(engine, src, wav, fps, detector, detections, o, _check(engine, o, detector, detections, (avi.height, avi.width)),
+                        start_time, int(audio_windows_per_pass))
         frames, _ = jpeg.decode_frames(engine, avi.frames, avi.height, avi.width, bgr=True, frames_per_pass=frames_per_pass)
         n_frames = avi.n_frames
-        timing = (avi.rate, avi.scale)
-    kw.setdefault("name_video", os.path.splitext(os.path.basename(os.fspath(path)))[0])
-    if kw.get("path_save_video"):
-        kw.setdefault("video_timing", timing)  # the source's own rate / scale pair, not the rounded fps
-    out = run_inference(engine, frames, wav, fps, detector=detector, detections=detections, wav_sr=wav_sr, **kw)
+    out = run_inference(engine, frames, wav, fps, detector=detector, detections=detections, **vars(o))
     duration = n_frames / fps if (fps and fps > 0 and n_frames > 0) else None
     out["real_time_factor"] = (time.time() - start_time) / duration if duration else None
     return out
 
 
-def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections: Optional[Sequence[np.ndarray]] = None,
-                  path_save_results: str = "", name_video: str = "video", flag_save_prob: bool = False,
-                  weights_prob_model=None, weights_model=(1, 1, 1), ce_weights_type: bool = True, ce_mask: bool = False,
-                  sr: int = 16000, window: float = 4, step: float = 0.5, padding: str = "mean", mode: int = MODE_DEFAULT,
-                  flag_heatmaps: bool = False, model_heatmaps: str = "static", wav_sr: Optional[int] = None,
-                  path_save_faces: Optional[str] = None, jpeg_entropy: str = "host", faces_via_jpeg: bool = False,
-                  path_save_video: Optional[str] = None, video_model: str = "av", video_quality: int = 90, video_panel: bool = False,
-                  video_timing: Optional[Sequence[int]] = None, tracks=None, detect_size=None, detect_filter: str = "bilinear",
-                  flag_save_plot_pred: bool = False, plot_size: Sequence[int] = (200, 1200)):
-    """engine: an `Engine` with the static, dynamic and audio weights loaded.  frames_bgr u8 [T,H,W,3] as cv2 decodes
+def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections: Optional[Sequence[np.ndarray]] = None, **options):
+    """The frames as ONE pass of the pass loop (_run) that run_inference_file(stream_frames=N) runs in passes of N frames; frames given
+    on the host or as numpy are copied to the device once.  `options`: the keyword options below (_Options states their defaults
+    once); an unknown name raises TypeError.
+    engine: an `Engine` with the static, dynamic and audio weights loaded.  frames_bgr u8 [T,H,W,3] as cv2 decodes
     them; wav float32 [L] mono at `sr`; fps as `int(cv2.CAP_PROP_FPS)` gives it (get_face_images.py:23).
     `wav_sr`: `wav` is source audio at that rate instead -- int16 [L] / [L, C] as the frames lie in the WAV file ffmpeg writes
     (44.1 kHz stereo, data/utils.py:46) or float32 [L] / [C, L] -- and is converted, downmixed and resampled to `sr` on the device,
@@ -155,8 +199,8 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
     ints >= 0: those directories (tid - 1, the folder numbers), in that order.  Every selected track is treated as the reference
     would treat it were its folder named `00` -- its own present mask, hold / zero / reset rule and LSTM windows
     (video_pipeline.tracks_plan); the audio table is the video's -- and its tables are, bit for bit, what
-    `visual_forward(engine, *track_clip(records, tiles, k, T), fps, mode)` and `fusion.fuse` on them give.  Detector, tracker,
-    crops and the audio branch run once; ONE static CNN call takes the selected tracks' tiles, ONE LSTM call all their windows, ONE
+    `visual_forward(engine, *track_clip(records, tiles, k, T), fps, mode)` on VideoTiler's tiles and `fusion.fuse` on them give.  Detector, tracker,
+    crops and the audio branch run once; ONE static CNN call per pass takes the selected tracks' tiles, ONE LSTM call all their windows, ONE
     fusion launch a segment per track (fusion.fuse_tracks); the range contract is read once for all of it.
     `out["tracks"]` = {track: dict of av / vs / vd / a / compound_prob / static_probs / dynamic_logits / present (bool [T])} in the
     order selected; the top-level keys are the FIRST selected track's (`audio_rows`, `audio_frames`, `records`, `face_files` are the
@@ -183,104 +227,162 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
     is off unless asked for, like every option, and nothing changes then.  Without `path_save_results`, with neither `ce_mask` nor
     `ce_weights_type` (the reference dies on an unbound `rule`), and with a `plot_size` that leaves no plot rectangle, ValueError
     before any work."""
-    tracks = check_tracks(tracks, flag_heatmaps)
-    plot = _check_plot(flag_save_plot_pred, path_save_results, ce_weights_type, ce_mask, plot_size)
-    hm = _check_options(engine, video_model, jpeg_entropy, faces_via_jpeg, flag_heatmaps, model_heatmaps, window, sr)
-    check_detect_size(detect_size, detect_filter, detector, detections, None if np.ndim(frames_bgr) != 4 else tuple(frames_bgr.shape[1:3]))
-    detector = scaled_detector(detector, detect_size, detect_filter)
-    start_time = time.time()                                                # run.py:200
+    o = _Options(**options)
     frames = frames_bgr if torch.is_tensor(frames_bgr) else torch.from_numpy(np.ascontiguousarray(frames_bgr))
-    total_frames = int(frames.shape[0])
-    # the duration the real-time factor divides by, settled before any work is queued: `int(cv2.CAP_PROP_FPS)` is 0 on a
-    # broken container, and a finished prediction must not be lost to a ZeroDivisionError in the last statement
-    duration = total_frames / fps if (fps and fps > 0 and total_frames > 0) else None
+    checked = _check(engine, o, detector, detections, None if frames.dim() != 4 else tuple(frames.shape[1:3]))
+    start_time = time.time()                                                # run.py:200
     if detections is None and detector is None:
         raise ValueError("give a detector or the per-frame detections")
-    if wav_sr is None:
-        wav_t = wav if torch.is_tensor(wav) else torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32))
-    else:
-        resample_plan(wav_sr, sr)
-        wav_t = wav if torch.is_tensor(wav) else torch.from_numpy(np.ascontiguousarray(wav))
+    if frames.dim() != 4 or frames.shape[-1] != 3 or frames.dtype != torch.uint8:
+        raise ValueError("frames must be uint8 [T,H,W,3] (BGR, as cv2 decodes them)")
+    if o.wav_sr is not None:
+        resample_plan(o.wav_sr, o.sr)
+    frames = frames.to(engine.device)  # frames given on the host cross once, for the detector, the crops and the result video alike
+    total = int(frames.shape[0])
+    return _run(engine, _Source(total, frames.shape[1], frames.shape[2], max(total, 1), lambda a: frames), wav, fps, detector, detections, o,
+                checked, start_time)
+
+
+def _run(engine, src: _Source, wav, fps, detector, detections, o: _Options, checked, start_time: float, audio_windows_per_pass=None):
+    """The per-video pipeline, once, for run_inference (ONE pass holding all frames) and run_inference_file(stream_frames=N) (passes of
+    N frames, one pass of decoded frames on the device at a time): the results do not depend on the pass size, bit for bit.
+
+    The audio branch is queued first, beside everything else (Engine.side_branch): it depends on nothing of the visual branch and
+    runs while the host walks the tracker.  Per pass: src.decode -> detector (or the pass's slice of `detections`) -> the resumable
+    tracker (Engine.tracker) -> the crop rectangles, their frame index rebased to the pass -> crop_tiles / roundtrip_face_tiles /
+    write_face_crops -> the static CNN on the pass's tiles of track 00, in record order.  Kept between passes: the detections and
+    records (host), and per frame of track 00 the static CNN's 7 probabilities and 512 features (2076 bytes); with `flag_heatmaps`,
+    per heat-map frame (one in lstm_step(fps)) its 7 raw maps [7,7,7] and its base image [224,224,3] -- as large as the overlays
+    that are returned.  Which class a map shows may depend on the LSTM ("dynamic"), which runs behind the sweep, so the overlays of
+    both `model_heatmaps` are rendered there, from what was kept.  With `tracks` the static CNN takes the pass's tiles of the
+    SELECTED tracks and those 2076 bytes are kept per record of a selected track -- with "all" per record, since which tracks there
+    are is known at the end only --, in record order; behind the sweep they are gathered track after track as
+    video_pipeline.tracks_plan lays them out.  "No face track" is known once the tracker has seen the last pass, and raises
+    there, behind that pass's crops and face files and in front of its static CNN call.  Behind the last pass:
+    video_pipeline.visual_from_static / visual_from_static_tracks (plan_clip's windows over all features, one LSTM call), the audio
+    branch joined, fuse (fuse_tracks); nothing has been copied to the host yet.  With `path_save_video` the source is read a SECOND
+    time, pass by pass, for annotate.write_result_video: the labels need the fused predictions.
+    MODE_F16X3: one read of the range-contract counter behind the last launch; a video during which an activation left fp16's range
+    is run again in MODE_FP32 (engine.guarded): records, detections and face files are those of the first sweep, the tiles are cut
+    again.  `checked`: _check's triple."""
+    tracks, plot, hm = checked
+    detector = scaled_detector(detector, o.detect_size, o.detect_filter)
+    total, per, height, width = src.total, src.per, src.height, src.width
+    # the duration the real-time factor divides by, settled before any work is queued: `int(cv2.CAP_PROP_FPS)` is 0 on a
+    # broken container, and a finished prediction must not be lost to a ZeroDivisionError in the last statement
+    duration = total / fps if (fps and fps > 0 and total > 0) else None
+    if detections is not None and len(detections) != total:
+        raise ValueError("one detection array per frame")
     dev = engine.device
-    wav_t = wav_t.to(dev)
-    main, side = torch.cuda.current_stream(dev), _side_stream(engine)
-    host = {}  # detector / tracker / crop results: independent of the arithmetic mode, computed once
+    wav_t = (wav if torch.is_tensor(wav) else torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32 if o.wav_sr is None else None))).to(dev)
+    save = (o.path_save_faces, o.name_video) if o.path_save_faces else (None, None)
+    host = {}  # detections, records and face files of every pass: independent of the arithmetic mode, computed once
 
     def gpu_work(m):
-        # (1) the audio branch depends on nothing of the visual one: it is queued FIRST, on its own stream, and runs while
-        #     the host walks the tracker loop below (750 numpy + linear_sum_assignment iterations for a 30 s video)
-        side.wait_stream(main)
-        wav_t.record_stream(side)  # allocated on `main`: the allocator must not hand it out while `side` still reads it
-        joined = False
-        try:
-            with torch.cuda.stream(side):
-                win_logits, lo, hi = audio_forward(engine, wav_t, sr, fps, window, step, padding, m, wav_sr=wav_sr)  # get_prob_audio_8_cl.py:68-138
-            # (2) faces -> tracks -> tiles (get_face_images.py:38-63), then the visual models on track 00
-            if "clip" not in host:
-                dets = detections if detections is not None else detector.batch(frames, rgb=False)  # get_face_images.py:49
-                if faces_via_jpeg:
-                    records, tiles = VideoTiler(engine).process(frames, dets, path_save_faces or None, name_video if path_save_faces else None,
-                                                                entropy=jpeg_entropy, via_jpeg=True)
-                    if path_save_faces:
-                        host["face_files"] = face_crop_paths(records, path_save_faces, name_video)
-                else:
-                    records, tiles = VideoTiler(engine).process(frames, dets)
-                if path_save_faces and not faces_via_jpeg:
-                    host["face_files"] = write_face_crops(engine, frames, records, path_save_faces, name_video, entropy=jpeg_entropy)
+        # a failure on the way (no face track, a detector error) joins the audio branch all the same (Engine.side_branch)
+        with engine.side_branch(wav_t) as side:
+            with torch.cuda.stream(side.stream):
+                win_logits, lo, hi = audio_forward(engine, wav_t, o.sr, fps, o.window, o.step, o.padding, m, wav_sr=o.wav_sr,
+                                                   windows_per_pass=audio_windows_per_pass)  # get_prob_audio_8_cl.py:68-138
+            side.results(win_logits)
+            first = "records" not in host
+            if first:
+                tracker, passes, files = engine.tracker(0.4, 0.0), [], []  # VideoTiler's tracker settings
+
+            def settle():
+                # every frame has been tracked: which tracks there are is known, in front of the last pass's visual models
+                tracker.close()
+                records = np.concatenate(passes) if passes else np.zeros((0, 6), dtype=np.int64)
+                if save[0]:
+                    host["face_files"] = files
                 if tracks is not None:
-                    # the selected tracks as one ragged set of clips: their tiles alone, track after track (no dense clip per track)
-                    tp = tracks_plan(records, select_tracks(records, tracks), total_frames, fps)
-                    host["records"], host["tracks_plan"] = records, tp
-                    host["clip"] = (tiles if len(tp.rows) == len(tiles) and (np.diff(tp.rows) == 1).all() else
-                                    tiles.index_select(0, torch.from_numpy(tp.rows).to(dev)), tp)
+                    host["tracks_plan"] = tracks_plan(records, select_tracks(records, tracks), total, fps)
+                elif not (records[:, 1] == 0).any():
+                    raise FileNotFoundError("no face track 00 (os.listdir(<faces>/00) fails in the reference, get_prob_video.py:79)")
+                host["passes"], host["records"] = passes, records
+
+            present = np.zeros(total, dtype=bool)
+            every = lstm_step(fps)
+            if every <= 0:
+                raise ZeroDivisionError("integer division or modulo by zero")  # as plan_clip: `curr_idx_frame % step`
+            probs, feats, cams, bases = [], [], [], []
+            kept, n_rec = [], 0  # `tracks`: the records (numbered through the video) whose static outputs are kept
+            for k, a in enumerate(range(0, total, per)):
+                frames = src.decode(a)
+                if first:
+                    dets = detections[a:a + per] if detections is not None else detector.batch(frames, rgb=False)  # get_face_images.py:49
+                    records = tracker.push(dets, width, height)
+                    passes.append(records)
                 else:
-                    if not (len(records) and (records[:, 1] == 0).any()):
-                        raise FileNotFoundError("no face track 00 (os.listdir(<faces>/00) fails in the reference, get_prob_video.py:79)")
-                    host["records"] = records
-                    host["clip"] = track_clip(records, tiles, 0, total_frames)
-            clip, present = host["clip"]
+                    records = host["passes"][k]
+                tiles = None
+                if len(records):
+                    if o.faces_via_jpeg:
+                        tiles, paths = roundtrip_face_tiles(engine, frames, records, *(save if first else (None, None)), entropy=o.jpeg_entropy,
+                                                            frame_base=a)
+                    else:
+                        tiles = engine.crop_tiles(frames, torch.from_numpy(pass_rects(records, a).astype(np.int32)), bgr=True)
+                        paths = write_face_crops(engine, frames, records, *save, entropy=o.jpeg_entropy, frame_base=a) if first and save[0] else None
+                    if first and save[0]:
+                        files.extend(paths)
+                if first and a + per >= total:
+                    settle()
+                if len(records):
+                    if tracks is None:
+                        sel = np.flatnonzero(records[:, 1] == 0)
+                    else:  # "all": which tracks there are is known at the end only, so every record is kept
+                        sel = np.arange(len(records)) if tracks == "all" else np.flatnonzero(np.isin(records[:, 1], tracks))
+                    if len(sel):
+                        r00 = records[sel]
+                        if tracks is None:
+                            present[r00[:, 0]] = True
+                        else:
+                            kept.append(sel + n_rec)
+                        tiles00 = tiles if len(sel) == len(records) else tiles.index_select(0, torch.from_numpy(sel).to(dev))
+                        if hm is not None:
+                            _, p, f, cam = engine.static_forward_cam(tiles00, m)
+                            pick = np.flatnonzero(r00[:, 0] % every == 0)
+                            if len(pick):
+                                cams.append(cam.index_select(0, torch.from_numpy(pick).to(dev)))
+                                rects = torch.from_numpy(pass_rects(r00[pick], a).astype(np.int32))
+                                if o.faces_via_jpeg:  # cv2.resize of the read-back crop (get_prob_video.py:99-100, data/utils.py:105)
+                                    bases.append(engine.crop_resize_linear(*jpeg.roundtrip_canvas(engine, frames, rects, bgr=True), swap_rb=False))
+                                else:
+                                    bases.append(engine.crop_resize_linear(frames, rects, swap_rb=True))
+                        else:
+                            _, p, f = engine.static_forward(tiles00, m)
+                        probs.append(p)
+                        feats.append(f)
+                    del tiles
+                    n_rec += len(records)
+                del frames
+            if "records" not in host:  # a video without a frame
+                settle()
+            probs, feats = (t[0] if len(t) == 1 else torch.cat(t) for t in (probs, feats))
             maps = None
             if tracks is not None:
-                # ONE static CNN sweep over all tracks' tiles, ONE LSTM call over all tracks' windows (video_pipeline.tracks_plan)
-                _, probs, feats = engine.static_forward(clip, m)
-                static_probs, dynamic_logits = visual_from_static_tracks(engine, probs, feats, present, fps, m)
-            elif flag_heatmaps:
-                static_probs, dynamic_logits, cam, fidx, rows, cls = hm.visual_forward_cam(engine, clip, present, fps, m, model_heatmaps)
-                if len(rows):
-                    recs = host["records"]
-                    r00 = recs[recs[:, 1] == 0]
-                    at = {int(f): k for k, f in enumerate(r00[:, 0])}
-                    pick = r00[[at[int(f)] for f in fidx]]
-                    rects = torch.from_numpy(pick[:, [0, 2, 3, 4, 5]].astype(np.int32))
-                    if faces_via_jpeg:  # cv2.resize of the read-back crop (get_prob_video.py:99-100, data/utils.py:105)
-                        from . import jpeg
-
-                        base = engine.crop_resize_linear(*jpeg.roundtrip_canvas(engine, frames, rects, bgr=True), swap_rb=False)
-                    else:
-                        base = engine.crop_resize_linear(frames, rects, swap_rb=True)
-                    maps = (fidx, engine.cam_render(cam, rows, cls, base, hm.JET_BGR, hm.IMAGE_WEIGHT))
-                else:
-                    maps = (fidx, torch.zeros((0, 224, 224, 3), dtype=torch.uint8, device=dev))
+                # what was kept lies in record order; the plan wants it track after track
+                tp = host["tracks_plan"]
+                pos = np.searchsorted(np.concatenate(kept), tp.rows)
+                if len(pos) != len(probs) or (np.diff(pos) != 1).any():
+                    pos = torch.from_numpy(pos).to(dev)
+                    probs, feats = probs.index_select(0, pos), feats.index_select(0, pos)
+                static_probs, dynamic_logits = visual_from_static_tracks(engine, probs, feats, tp, fps, m)
             else:
-                static_probs, dynamic_logits = visual_forward(engine, clip, present, fps, m)         # get_prob_video.py:67-204
-            # (3) fusion last, behind both branches; nothing has been copied to the host yet
-            main.wait_stream(side)
-            joined = True
-            win_logits.record_stream(main)
-            prob, am = (fuse if tracks is None else fuse_tracks)(engine, static_probs, dynamic_logits, win_logits, lo, hi, weights_prob_model,
-                                                                 weights_model, ce_weights_type, ce_mask)  # run.py:25-189
-            return static_probs, dynamic_logits, win_logits, lo, hi, prob, am, maps
-        finally:
-            # the reference's failure paths (no face track, a detector error) unwind from here: the audio branch already queued
-            # on `side` is joined all the same, so that no launch of this video outlives the call (its workspace and the
-            # range-contract counter belong to the next one)
-            if not joined:
-                main.wait_stream(side)
+                static_probs, dynamic_logits, dl = visual_from_static(engine, probs, feats, present, fps, m, with_windows=True)  # get_prob_video.py:67-204
+                if hm is not None:
+                    fidx, rows, win = hm.heatmap_plan(present, fps)
+                    if len(rows):
+                        cls = hm.heatmap_classes(engine, o.model_heatmaps, probs, dl, rows, win)
+                        maps = (fidx, engine.cam_render(torch.cat(cams), np.arange(len(rows)), cls, torch.cat(bases), hm.JET_BGR, hm.IMAGE_WEIGHT))
+                    else:
+                        maps = (fidx, torch.zeros((0, 224, 224, 3), dtype=torch.uint8, device=dev))
+        # fusion last, behind both branches
+        prob, am = (fuse if tracks is None else fuse_tracks)(engine, static_probs, dynamic_logits, win_logits, lo, hi, o.weights_prob_model,
+                                                             o.weights_model, o.ce_weights_type, o.ce_mask)  # run.py:25-189
+        return static_probs, dynamic_logits, win_logits, lo, hi, prob, am, maps
 
-    # MODE_F16X3: one read of the range-contract counter behind the last launch; a video during which an activation left fp16's
-    # range is run again in MODE_FP32 (engine.guarded)
-    out = _results(engine, engine.guarded(mode, gpu_work), host, frames, wav, wav_sr, fps, path_save_results, name_video, flag_save_prob, model_heatmaps, path_save_video, video_model, video_quality,
-                   video_panel, video_timing, plot)
+    out = _results(engine, engine.guarded(o.mode, gpu_work), host, src.passes, wav, fps, o, plot)
     # "Real-time factor for compound expression prediction" as run.py:304-307 prints it: elapsed / video duration (the
     # device -> host copies above have synchronised the stream, so the clock covers all the work); None where the
     # container reported no frame rate
@@ -288,46 +390,42 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
     return out
 
 
-def _check_options(engine, video_model, jpeg_entropy, faces_via_jpeg, flag_heatmaps, model_heatmaps, window, sr):
-    """What run_inference refuses before any work, in its order; returns the heat-map module when `flag_heatmaps`, else None."""
+def _check(engine, o: _Options, detector, detections, frame_size=None):
+    """What both calls refuse before any work, in this order -> (tracks as check_tracks returns them, _check_plot's pair or None,
+    the heat-map module when `flag_heatmaps`, else None)."""
+    tracks = check_tracks(o.tracks, o.flag_heatmaps)
+    plot = _check_plot(o)
     video_models = [m.lower() for m in MODEL_ORDER]
-    if video_model not in video_models:
-        raise ValueError(f"video_model must be one of {' / '.join(video_models)}, not {video_model!r}")
-    if jpeg_entropy not in ("host", "device"):
-        raise ValueError(f'jpeg_entropy must be "host" or "device", not {jpeg_entropy!r}')
-    check_via_jpeg(faces_via_jpeg)
+    if o.video_model not in video_models:
+        raise ValueError(f"video_model must be one of {' / '.join(video_models)}, not {o.video_model!r}")
+    if o.jpeg_entropy not in ("host", "device"):
+        raise ValueError(f'jpeg_entropy must be "host" or "device", not {o.jpeg_entropy!r}')
+    check_via_jpeg(o.faces_via_jpeg)
     hm = None
-    if flag_heatmaps:
+    if o.flag_heatmaps:
         from . import heatmaps as hm
 
-        hm.check_model(model_heatmaps)
-    check_window(engine, window, sr)
-    return hm
+        hm.check_model(o.model_heatmaps)
+    check_window(engine, o.window, o.sr)
+    check_detect_size(o.detect_size, o.detect_filter, detector, detections, frame_size)
+    return tracks, plot, hm
 
 
-def _check_plot(flag_save_plot_pred, path_save_results, ce_weights_type, ce_mask, plot_size):
+def _check_plot(o: _Options):
     """`flag_save_plot_pred` off (the default): None, and the chart module is not even imported.  On: what chart.check_plot_pred
     refuses is refused here, before any work; returns (rule, (height, width))."""
-    if flag_save_plot_pred is False:
+    if o.flag_save_plot_pred is False:
         return None
     from .chart import check_plot_pred
 
-    return check_plot_pred(flag_save_plot_pred, path_save_results, ce_weights_type, ce_mask, plot_size)
+    return check_plot_pred(o.flag_save_plot_pred, o.path_save_results, o.ce_weights_type, o.ce_mask, o.plot_size)
 
 
-def _side_stream(engine):
-    """The engine's second stream: the audio branch runs on it beside the visual one."""
-    side = engine.__dict__.get("_side_stream")
-    if side is None:
-        side = engine.__dict__["_side_stream"] = torch.cuda.Stream(engine.device)
-    return side
-
-
-def _results(engine, res, host, frames, wav, wav_sr, fps, path_save_results, name_video, flag_save_prob, model_heatmaps, path_save_video,
-             video_model, video_quality, video_panel, video_timing, plot=None):
-    """Everything behind the guarded device work, for the in-memory and the streamed call alike: the tables to the host, the CSV
-    files, the heat-map files, the result video, the prediction chart (`plot`: _check_plot's pair).  `res` is gpu_work's tuple; `frames`: the decoded frames, or -- streamed -- a
-    callable that yields them once more in passes (annotate.write_result_video)."""
+def _results(engine, res, host, frames, wav, fps, o: _Options, plot=None):
+    """Everything behind the guarded device work: the tables to the host, the CSV files, the heat-map files, the result video, the
+    prediction chart (`plot`: _check_plot's pair).  `res` is gpu_work's tuple; `frames`: a callable that yields the decoded frames
+    once more in passes (annotate.write_result_video)."""
+    path_save_results, name_video, wav_sr, video_model, video_timing = o.path_save_results, o.name_video, o.wav_sr, o.video_model, o.video_timing
     static_probs, dynamic_logits, win_logits, lo, hi, prob, am, maps = res
     records = host["records"]
     rows, aud_frames = replicate_per_frame(win_logits.cpu().numpy(), lo, hi)
@@ -355,7 +453,7 @@ def _results(engine, res, host, frames, wav, wav_sr, fps, path_save_results, nam
         first = per_track[tp.tracks[0]]
         am, prob = np.stack([first[name.lower()] for name in MODEL_ORDER]), first["compound_prob"].copy()
         static_probs, dynamic_logits = first["static_probs"].copy(), first["dynamic_logits"].copy()
-    if flag_save_prob:
+    if o.flag_save_prob:
         io_formats.write_visual_csvs(static_probs, dynamic_logits, path_save_results, name_video)
         io_formats.write_audio_csv(rows, aud_frames, path_save_results, "audio", name_video)
         for k in (tp.tracks[1:] if tp is not None else ()):  # the other tracks: the same files, as the video `<name_video>__t<kk>`
@@ -377,8 +475,8 @@ def _results(engine, res, host, frames, wav, wav_sr, fps, path_save_results, nam
 
         out["heatmaps"] = (maps[0].astype(np.int32), maps[1].cpu().numpy())
         if path_save_results:
-            hm.write_heatmaps(hm.heatmap_dir(path_save_results, name_video, model_heatmaps), maps[0], maps[1], engine=engine)
-    if path_save_video:
+            hm.write_heatmaps(hm.heatmap_dir(path_save_results, name_video, o.model_heatmaps), maps[0], maps[1], engine=engine)
+    if o.path_save_video:
         from fractions import Fraction
 
         from .annotate import write_result_video
@@ -398,169 +496,7 @@ def _results(engine, res, host, frames, wav, wav_sr, fps, path_save_results, nam
             pred = {k: one[video_model] for k, one in per_track.items()}
             prob_model = {k: one["compound_prob"][j] for k, one in per_track.items()}
             labelled = tp.tracks
-        out["result_video"] = write_result_video(engine, frames, records, pred, prob_model, path_save_video, int(video_timing[0]),
+        out["result_video"] = write_result_video(engine, frames, records, pred, prob_model, o.path_save_video, int(video_timing[0]),
                                                  int(video_timing[1]), pcm=pcm, audio_rate=int(wav_sr) if pcm is not None else 44100,
-                                                 quality=video_quality, entropy="device", panel=video_panel, tracks=labelled)
-    return out
-
-
-def _options(**kw):
-    """run_inference's keyword options with its own defaults (one statement of them), `kw` laid over; an unknown name is the
-    TypeError the call itself would raise."""
-    import inspect
-    from types import SimpleNamespace
-
-    opts = {k: p.default for k, p in inspect.signature(run_inference).parameters.items() if p.default is not inspect.Parameter.empty}
-    unknown = sorted(set(kw) - set(opts))
-    if unknown:
-        raise TypeError(f"run_inference() got an unexpected keyword argument {unknown[0]!r}")
-    opts.update(kw)
-    return SimpleNamespace(**opts)
-
-
-def _run_streamed(engine, avi, wav, wav_sr, fps, detector, detections, stream_frames: int, audio_windows_per_pass: int, frames_per_pass: int,
-                  start_time: float, **kw):
-    """`run_inference` on the open recording `avi` in passes of `stream_frames` frames (run_inference_file's `stream_frames`): the
-    same results, bit for bit, with one pass of decoded frames on the device at a time.
-
-    Per pass: jpeg.decode_frames -> detector (or the pass's slice of `detections`) -> the resumable tracker (Engine.tracker) -> the
-    crop rectangles, their frame index rebased to the pass -> crop_tiles / roundtrip_face_tiles / write_face_crops -> the static CNN
-    on the pass's tiles of track 00.  Kept between passes: the detections and records (host), and per frame of track 00 the static
-    CNN's 7 probabilities and 512 features (2076 bytes); with `flag_heatmaps`, per heat-map frame (one in lstm_step(fps)) its 7
-    raw maps [7,7,7] and its base image [224,224,3] -- as large as the overlays that are returned.  Which class a map shows may
-    depend on the LSTM ("dynamic"), which runs behind the sweep, so the overlays of both `model_heatmaps` are rendered there, from
-    what was kept.  With `tracks` the static CNN takes the pass's tiles of the SELECTED tracks and those 2076 bytes are kept per
-    record of a selected track -- with "all" per record, since which tracks there are is known at the end only --, in record
-    order; behind the sweep they are gathered track after track as video_pipeline.tracks_plan lays them out.  Behind the last
-    pass: video_pipeline.visual_from_static / visual_from_static_tracks (plan_clip's windows over all features, one LSTM call), the
-    audio branch joined, fuse (fuse_tracks).  With `path_save_video` the file is decoded a SECOND time, pass by pass, for
-    annotate.write_result_video: the labels need the fused predictions.  Decode and compute are not overlapped: one pass buffer is
-    alive at a time."""
-    from . import jpeg
-    from .video_pipeline import lstm_step
-
-    o = _options(**kw)
-    tracks = check_tracks(o.tracks, o.flag_heatmaps)
-    hm = _check_options(engine, o.video_model, o.jpeg_entropy, o.faces_via_jpeg, o.flag_heatmaps, o.model_heatmaps, o.window, o.sr)
-    check_detect_size(o.detect_size, o.detect_filter, detector, detections, (avi.height, avi.width))
-    plot = _check_plot(o.flag_save_plot_pred, o.path_save_results, o.ce_weights_type, o.ce_mask, o.plot_size)
-    detector = scaled_detector(detector, o.detect_size, o.detect_filter)
-    total, height, width, per = avi.n_frames, avi.height, avi.width, int(stream_frames)
-    duration = total / fps if (fps and fps > 0 and total > 0) else None
-    if detections is not None and len(detections) != total:
-        raise ValueError("one detection array per frame")
-    dev = engine.device
-    wav_t = (wav if torch.is_tensor(wav) else torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32 if wav_sr is None else None))).to(dev)
-    main, side = torch.cuda.current_stream(dev), _side_stream(engine)
-    save = (o.path_save_faces, o.name_video) if o.path_save_faces else (None, None)
-    host = {}  # detections, records and face files of every pass: independent of the arithmetic mode, computed once
-
-    def decode(a):
-        return jpeg.decode_frames(engine, avi.frames[a:a + per], height, width, bgr=True, frames_per_pass=frames_per_pass)[0]
-
-    def gpu_work(m):
-        side.wait_stream(main)
-        wav_t.record_stream(side)
-        joined = False
-        try:
-            with torch.cuda.stream(side):
-                win_logits, lo, hi = audio_forward(engine, wav_t, o.sr, fps, o.window, o.step, o.padding, m, wav_sr=wav_sr,
-                                                   windows_per_pass=audio_windows_per_pass)
-            first = "records" not in host
-            if first:
-                tracker, passes, files = engine.tracker(0.4, 0.0), [], []  # VideoTiler's tracker
-            present = np.zeros(total, dtype=bool)
-            every = lstm_step(fps)
-            if every <= 0:
-                raise ZeroDivisionError("integer division or modulo by zero")  # as plan_clip: `curr_idx_frame % step`
-            probs, feats, cams, bases = [], [], [], []
-            kept, n_rec = [], 0  # `tracks`: the records (numbered through the video) whose static outputs are kept
-            for k, a in enumerate(range(0, total, per)):
-                frames = decode(a)
-                if first:
-                    dets = detections[a:a + per] if detections is not None else detector.batch(frames, rgb=False)
-                    records = tracker.push(dets, width, height)
-                    passes.append(records)
-                else:
-                    records = host["passes"][k]
-                if len(records):
-                    if o.faces_via_jpeg:
-                        tiles, paths = roundtrip_face_tiles(engine, frames, records, *(save if first else (None, None)), entropy=o.jpeg_entropy,
-                                                            frame_base=a)
-                    else:
-                        tiles = engine.crop_tiles(frames, torch.from_numpy(pass_rects(records, a).astype(np.int32)), bgr=True)
-                        paths = write_face_crops(engine, frames, records, *save, entropy=o.jpeg_entropy, frame_base=a) if first and save[0] else None
-                    if first and save[0]:
-                        files.extend(paths)
-                    if tracks is None:
-                        sel = np.flatnonzero(records[:, 1] == 0)
-                    else:  # "all": which tracks there are is known at the end only, so every record is kept
-                        sel = np.arange(len(records)) if tracks == "all" else np.flatnonzero(np.isin(records[:, 1], tracks))
-                    if len(sel):
-                        r00 = records[sel]
-                        if tracks is None:
-                            present[r00[:, 0]] = True
-                        else:
-                            kept.append(sel + n_rec)
-                        tiles00 = tiles if len(sel) == len(records) else tiles.index_select(0, torch.from_numpy(sel).to(dev))
-                        if o.flag_heatmaps:
-                            _, p, f, cam = engine.static_forward_cam(tiles00, m)
-                            pick = np.flatnonzero(r00[:, 0] % every == 0)
-                            if len(pick):
-                                cams.append(cam.index_select(0, torch.from_numpy(pick).to(dev)))
-                                rects = torch.from_numpy(pass_rects(r00[pick], a).astype(np.int32))
-                                if o.faces_via_jpeg:  # cv2.resize of the read-back crop, as in run_inference
-                                    bases.append(engine.crop_resize_linear(*jpeg.roundtrip_canvas(engine, frames, rects, bgr=True), swap_rb=False))
-                                else:
-                                    bases.append(engine.crop_resize_linear(frames, rects, swap_rb=True))
-                        else:
-                            _, p, f = engine.static_forward(tiles00, m)
-                        probs.append(p)
-                        feats.append(f)
-                    del tiles
-                    n_rec += len(records)
-                del frames
-            if first:
-                tracker.close()
-                records = np.concatenate(passes) if passes else np.zeros((0, 6), dtype=np.int64)
-                if save[0]:
-                    host["face_files"] = files
-                if tracks is not None:
-                    host["tracks_plan"] = tracks_plan(records, select_tracks(records, tracks), total, fps)
-                elif not present.any():
-                    raise FileNotFoundError("no face track 00 (os.listdir(<faces>/00) fails in the reference, get_prob_video.py:79)")
-                host["passes"], host["records"] = passes, records
-            probs, feats = torch.cat(probs), torch.cat(feats)
-            if tracks is not None:
-                # what was kept lies in record order; the plan wants it track after track
-                tp = host["tracks_plan"]
-                pos = np.searchsorted(np.concatenate(kept), tp.rows)
-                if len(pos) != len(probs) or (np.diff(pos) != 1).any():
-                    pos = torch.from_numpy(pos).to(dev)
-                    probs, feats = probs.index_select(0, pos), feats.index_select(0, pos)
-                static_probs, dynamic_logits = visual_from_static_tracks(engine, probs, feats, tp, fps, m)
-            else:
-                static_probs, dynamic_logits, dl = visual_from_static(engine, probs, feats, present, fps, m, with_windows=True)
-            maps = None
-            if o.flag_heatmaps:
-                fidx, rows, win = hm.heatmap_plan(present, fps)
-                if len(rows):
-                    cls = hm.heatmap_classes(engine, o.model_heatmaps, probs, dl, rows, win)
-                    maps = (fidx, engine.cam_render(torch.cat(cams), np.arange(len(rows)), cls, torch.cat(bases), hm.JET_BGR, hm.IMAGE_WEIGHT))
-                else:
-                    maps = (fidx, torch.zeros((0, 224, 224, 3), dtype=torch.uint8, device=dev))
-            main.wait_stream(side)
-            joined = True
-            win_logits.record_stream(main)
-            prob, am = (fuse if tracks is None else fuse_tracks)(engine, static_probs, dynamic_logits, win_logits, lo, hi, o.weights_prob_model,
-                                                                 o.weights_model, o.ce_weights_type, o.ce_mask)
-            return static_probs, dynamic_logits, win_logits, lo, hi, prob, am, maps
-        finally:
-            if not joined:  # as in run_inference: no launch of this video outlives the call
-                main.wait_stream(side)
-
-    res = engine.guarded(o.mode, gpu_work)
-    out = _results(engine, res, host, lambda: (decode(a) for a in range(0, total, per)), wav, wav_sr, fps, o.path_save_results, o.name_video,
-                   o.flag_save_prob, o.model_heatmaps, o.path_save_video, o.video_model, o.video_quality, o.video_panel, o.video_timing, plot)
-    out["real_time_factor"] = (time.time() - start_time) / duration if duration else None
+                                                 quality=o.video_quality, entropy="device", panel=o.video_panel, tracks=labelled)
     return out

@@ -63,14 +63,18 @@ def plan_clip(present, fps: float, feat_base: int = 0, win_base: int = 0) -> Cli
     return plan
 
 
-def clips_plan(present, fps: float):
-    """`plan_clip` over the rows of present bool [n,T], row numbers counted through the set: (static_src int64 [n*T], dyn_src int64
-    [n*T], windows int32 [n_win,10], feat_off int64 [n+1], win_off int64 [n+1]); -1 = the zero row, as in ClipPlan.  Clip c owns the
-    feature rows feat_off[c]..feat_off[c+1] and the LSTM windows win_off[c]..win_off[c+1]."""
-    present = np.asarray(present, dtype=bool)
+def clips_plan(present, fps):
+    """`plan_clip` over the rows of present bool [n,T] -- or over n masks of their own lengths, the videos of a set --, row numbers
+    counted through the set: (static_src int64 [sum T], dyn_src int64 [sum T], windows int32 [n_win,10], feat_off int64 [n+1], win_off
+    int64 [n+1]); -1 = the zero row, as in ClipPlan.  Clip c owns the feature rows feat_off[c]..feat_off[c+1] and the LSTM windows
+    win_off[c]..win_off[c+1].  `fps`: one frame rate for all clips, or one per clip."""
+    present = [np.asarray(row, dtype=bool).reshape(-1) for row in present]
+    fpss = [fps] * len(present) if np.ndim(fps) == 0 else list(fps)
+    if len(fpss) != len(present):
+        raise ValueError(f"clips_plan: {len(fpss)} frame rates for {len(present)} clips")
     s_src, d_src, win, f_off, w_off = [], [], [], [0], [0]
-    for row in present:
-        p = plan_clip(row, fps, f_off[-1], w_off[-1])
+    for row, one_fps in zip(present, fpss):
+        p = plan_clip(row, one_fps, f_off[-1], w_off[-1])
         f_off.append(f_off[-1] + int(row.sum()))
         w_off.append(w_off[-1] + len(p.windows))
         s_src += p.static_src
@@ -112,15 +116,15 @@ def tracks_plan(records, tracks, total_frames: int, fps: float) -> TracksPlan:
 
 class _DevicePlan:
     """Index tensors of one (present mask, fps) combination, resident on the device.  Building them costs Python loops
-    and host->device copies that serialise behind in-flight GPU work, so they are cached per mask."""
+    and host->device copies that serialise behind in-flight GPU work, so they are cached per mask.  `host`: clips_plan's tuple where
+    the caller has it; `present` None beside it: a ragged set (run_dataset), whose tiles never lay in a dense clip to select from."""
 
-    def __init__(self, engine: Engine, present: np.ndarray, fps: float, host=None):
-        n, t = present.shape
+    def __init__(self, engine: Engine, present, fps, host=None):
         s_src, d_src, win, f_off, w_off = clips_plan(present, fps) if host is None else host
         fb, wb = int(f_off[-1]), int(w_off[-1])
         dev = engine.device
         self.n_feat, self.n_win = fb, wb
-        self.sel = None if fb == n * t else torch.from_numpy(np.nonzero(present.reshape(-1))[0]).to(dev)
+        self.sel = None if present is None or fb == present.size else torch.from_numpy(np.nonzero(present.reshape(-1))[0]).to(dev)
         s_src = np.where(s_src >= 0, s_src, fb)
         d_src = np.where(d_src >= 0, d_src, wb)
         assert win.size == 0 or (win.min() >= 0 and win.max() < max(fb, 1))
@@ -164,16 +168,23 @@ def visual_forward(engine: Engine, frames_u8: torch.Tensor, present, fps: float,
     return (stat[0], dyn[0]) if single else (stat, dyn)
 
 
-def _tables(engine: Engine, plan: _DevicePlan, probs, feats, rows: int, mode: int):
+def _tables(engine: Engine, plan: _DevicePlan, probs, feats, rows: int, mode: int, windows_per_pass=None, passes=None):
     """The window logic's one statement: the static CNN's outputs of the present frames (probs [n_feat,7], feats [n_feat,512], in
     frame order; None when there is none) -> (static table [rows,7], dynamic table [rows,7], the LSTM's logits per window or
-    None): the LSTM over the plan's windows, hold-last / zeros rows gathered as the plan says (get_prob_video.py:157-178)."""
+    None): the LSTM over the plan's windows, hold-last / zeros rows gathered as the plan says (get_prob_video.py:157-178).
+    `windows_per_pass`: the LSTM takes that many windows per call (None: all in one; the logits are the same); `passes`: a list
+    that receives the size of every LSTM call."""
     dev = engine.device
     dl = None
     if plan.n_feat:
         stat = torch.cat([probs, plan.zero_row]).index_select(0, plan.s_src)
         if plan.n_win:
-            dl = engine.dynamic_forward(engine.gather_windows(feats, plan.win, validated=True), mode)
+            per = plan.n_win if windows_per_pass is None else int(windows_per_pass)
+            parts = [engine.dynamic_forward(engine.gather_windows(feats, plan.win[a:a + per], validated=True), mode)
+                     for a in range(0, plan.n_win, per)]
+            if passes is not None:
+                passes.extend(int(p.shape[0]) for p in parts)
+            dl = parts[0] if len(parts) == 1 else torch.cat(parts)
             dyn = torch.cat([dl, plan.zero_row]).index_select(0, plan.d_src)
         else:
             dyn = torch.zeros(rows, 7, device=dev)
@@ -295,7 +306,7 @@ def preprocess_video_and_predict(engine: Engine, path_images: str = "", save_pat
     `flag_save_prob` (the reference's files, io_formats.write_visual_csvs).
     `flag_heatmaps`: one Grad-CAM overlay per frame that starts an LSTM evaluation, written as
     `<save_path>/<video>/heatmaps_<model_heatmaps>/NNNNNN.jpg` (avcer_amd/heatmaps.py); the tables are the same as without it.
-    The visual call then runs through `engine.guarded`, maps included.  `model_heatmaps` other than "static" / "dynamic" raises
+    The visual call runs through `engine.guarded`, with or without maps.  `model_heatmaps` other than "static" / "dynamic" raises
     ValueError before any work (the reference dies with UnboundLocalError at its first heat-map frame).
     `decode`: "device" reads the crops through read_face_dir_device / read_face_crops_device (host entropy pass, HIP pixel pass),
     "pil" through read_face_dir / read_face_crops; the tiles are bit-identical, so tables, CSV files and heat maps are the same.
@@ -321,31 +332,30 @@ def preprocess_video_and_predict(engine: Engine, path_images: str = "", save_pat
             canvas, rects = read_face_crops(p, idx)
             return torch.from_numpy(canvas), rects
 
+    hm = None
     if flag_heatmaps:
         from . import heatmaps as hm
 
         hm.check_model(model_heatmaps)
-        frames, present = read_dir(path_images, total_frames)
+    frames, present = read_dir(path_images, total_frames)
+    if hm is not None:
         frame_idx = hm.heatmap_plan(present, fps)[0]
         canvas, rects = read_crops(path_images, frame_idx)
 
-        def call(m):
-            stat, dyn, cam, fidx, rows, cls = hm.visual_forward_cam(engine, frames, present, fps, m, model_heatmaps)
-            imgs = None
-            if len(rows):
-                base = engine.crop_resize_linear(canvas, rects, swap_rb=False)
-                imgs = engine.cam_render(cam, rows, cls, base, hm.JET_BGR, hm.IMAGE_WEIGHT)
-            return stat, dyn, imgs
+    def call(m):
+        if hm is None:
+            return (*visual_forward(engine, frames, present, fps, m), None)
+        stat, dyn, cam, _, rows, cls = hm.visual_forward_cam(engine, frames, present, fps, m, model_heatmaps)
+        imgs = None
+        if len(rows):
+            base = engine.crop_resize_linear(canvas, rects, swap_rb=False)
+            imgs = engine.cam_render(cam, rows, cls, base, hm.JET_BGR, hm.IMAGE_WEIGHT)
+        return stat, dyn, imgs
 
-        stat, dyn, imgs = engine.guarded(mode, call)
-        if imgs is not None:
-            hm.write_heatmaps(hm.heatmap_dir(save_path, os.path.basename(path_images), model_heatmaps), frame_idx, imgs, engine=engine)
-        if flag_save_prob:
-            io_formats.write_visual_csvs(stat, dyn, save_path, os.path.basename(path_images))
-        return dyn.cpu().numpy(), stat.cpu().numpy()
-
-    frames, present = read_dir(path_images, total_frames)
-    stat, dyn = visual_forward(engine, frames, present, fps, mode)
+    # MODE_F16X3: a call during which an activation left fp16's range is repeated in MODE_FP32, maps included (engine.guarded)
+    stat, dyn, imgs = engine.guarded(mode, call)
+    if imgs is not None:
+        hm.write_heatmaps(hm.heatmap_dir(save_path, os.path.basename(path_images), model_heatmaps), frame_idx, imgs, engine=engine)
     if flag_save_prob:
         io_formats.write_visual_csvs(stat, dyn, save_path, os.path.basename(path_images))
     return dyn.cpu().numpy(), stat.cpu().numpy()
