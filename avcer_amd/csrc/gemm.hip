@@ -1195,6 +1195,17 @@ int launch_conv_gemm(avcer_ctx* ctx, const avcer_conv_desc& d, int dtype, const 
         return set_err(ctx, AVCER_EINVAL, "conv_gemm: cin/coff/strides must be multiples of %d", vec);
     if (d.x_stride_w % vec && !(d.kw == 1 && d.pad_w == 0 && (d.stride_w * d.x_stride_w) % vec == 0))
         return set_err(ctx, AVCER_EINVAL, "conv_gemm: x_stride_w=%ld breaks 16-byte alignment", (long)d.x_stride_w);
+    // The straddling gather (cin not a multiple of the K-step: AVCER_ISSUE_TILES, last branch) moves a lane's channel index
+    // kc + a_kc into the NEXT tap once.  kc < cin is a multiple of g = gcd(cin, bk) and reaches cin - g (K is a whole number of
+    // periods lcm(cin, bk)), a_kc reaches bk - vec: the index stays below 2 * cin, one wrap, only while bk - vec - g < cin.
+    // f32 / x3 from f32: cin 16, 24, 28 and any cin > 32; bf16: cin 32, 48, 56 and any cin > 64.
+    if (d.kh * d.kw > 1 && d.cin > 0 && d.cin % bk) {
+        int g = d.cin, r = bk;
+        while (r) { const int t = g % r; g = r; r = t; }
+        if (bk - vec - g >= d.cin)
+            return set_err(ctx, AVCER_EINVAL, "conv_gemm: cin=%d with %d x %d taps: a K-step of %d elements would span more than two "
+                           "taps (needs cin %% %d == 0 or cin > %d - gcd(cin, %d))", d.cin, d.kh, d.kw, bk, bk, bk - vec, bk);
+    }
     const int ovec = o_split ? 32 : 16 / ((dtype == 1) ? 2 : 4);  // 16-byte vectors / whole sp32 groups
     if (d.y_ld % ovec || d.y_coff % ovec || (residual && (d.r_ld % ovec || d.r_coff % ovec)))
         return set_err(ctx, AVCER_EINVAL, "conv_gemm: output/residual leading dims and offsets must be multiples of %d", ovec);

@@ -810,7 +810,11 @@ int avcer_fuse_videos(avcer_ctx* ctx, const float* stat, const float* dyn_logits
 typedef struct avcer_conv_desc {
     int32_t batch, in_h, in_w;       /* input extents used for bounds (zero padding outside) */
     int32_t out_h, out_w;            /* M = batch*out_h*out_w */
-    int32_t cin;                     /* contiguous channels per tap (multiple of 8; of 4 for f32) */
+    int32_t cin;                     /* contiguous channels per tap (multiple of 8; of 4 for f32; of 32 for sp32).  With more than
+                                        one tap and cin not a multiple of the K-step (32 elements; 64 for bf16) a K-step may span
+                                        two taps but not three: f32 input accepts cin 16, 24, 28 and any cin > 32, bf16 accepts
+                                        cin 32, 48, 56 and any cin > 64; the rest (f32 4, 8, 12, 20; bf16 8, 16, 24, 40) is
+                                        AVCER_EINVAL */
     int32_t kh, kw;                  /* taps; K = kh*kw*cin */
     int32_t stride_h, stride_w, pad_h, pad_w, dil_h, dil_w;
     int64_t x_stride_b, x_stride_h, x_stride_w; /* element strides of the input */

@@ -74,13 +74,17 @@ def _linear(m, k, n, **kw):
 
 
 @pytest.mark.parametrize("strided", [False, True], ids=["dense", "strided"])
-@pytest.mark.parametrize("dtype,tile_m", [(t, 0) for t in range(7)] + [(7, 112), (7, 128), (8, 112), (8, 128)])
-def test_conv_gemm_linear(engine, dtype, tile_m, strided):
-    """M = 129: one row past a 128-row tile (dtypes 7 / 8: 17 past a 112-row one).  K = 64, N = 256."""
+@pytest.mark.parametrize("dtype,tile_m,tile_n", [(t, 0, 0) for t in range(7)] + [(7, 112, 0), (7, 128, 0), (8, 112, 0), (8, 128, 0)] +
+                         [(t, 0, 128) for t in range(7)],
+                         ids=[f"{t}-0" for t in range(7)] + ["7-112", "7-128", "8-112", "8-128"] + [f"{t}-0-n128" for t in range(7)])
+def test_conv_gemm_linear(engine, dtype, tile_m, tile_n, strided):
+    """M = 129: one row past a 128-row tile (dtypes 7 / 8: 17 past a 112-row one).  K = 64, N = 256.  tile_n = 0 is the library's
+    choice, 64-wide tiles at this K; n128 forces conv_gemm_kernel<.., 128> of dtypes 0-6 (two column tiles, LDS-staged drain of
+    128 columns in the f32 / bf16 modes)."""
     m, k, n = 129, 64, 256
     g = _gen(m, k, n)
-    _conv_bounds(engine, _linear(m, k, n, tile_m=tile_m), dtype, torch.randn(m, k, generator=g), torch.randn(n, k, generator=g) / k ** 0.5,
-                 strided)
+    _conv_bounds(engine, _linear(m, k, n, tile_m=tile_m, tile_n=tile_n), dtype, torch.randn(m, k, generator=g),
+                 torch.randn(n, k, generator=g) / k ** 0.5, strided)
 
 
 @pytest.mark.parametrize("strided", [False, True], ids=["dense", "strided"])
