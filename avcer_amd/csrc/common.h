@@ -14,6 +14,7 @@
 
 #include "../../include/avcer_hip.h"
 #include "arena.h"
+#include "gemm_forms.h"
 
 typedef uint16_t bf16_t;  // raw bfloat16 bits
 
@@ -26,8 +27,7 @@ struct DevBuf {
 enum { WS_STATIC = 0, WS_DYNAMIC = 1, WS_AUDIO = 2, WS_FACE = 3, WS_NMS = 4, WS_CEILINGS = 5, WS_STATIC_LANE1 = 6, WS_FACE_LANE1 = 7,
        WS_GRU = 8, WS_JPEG = 9, WS_RESIZE = 10, WS_CHART = 11, WS_COUNT = 12 };
 
-// how an activation tensor is stored (the `kind` / `act` arguments of the k_* launchers, Net::gemm's akind / okind)
-enum { KIND_F32 = 0, KIND_BF16 = 1, KIND_SP32 = 2 };
+// storage of an activation tensor: a KIND_* of gemm_forms.h
 struct Storage { int kind; size_t es; };  // es: bytes per element
 // activation storage of a forward pass in `mode`: f32 / bf16 / sp32 pairs
 inline Storage mode_storage(int mode) {
@@ -76,7 +76,7 @@ struct avcer_ctx {
     int lane_min = 32, lane_max = 2048;  // avcer_set_static_lane_range (tools/two_lane_sweep.py: two lanes win from 16 to 2048 frames)
     hipStream_t lane_stream = nullptr;  // the second lane's stream, created on first use, and its fork / join events
     hipEvent_t lane_ev[2] = {nullptr, nullptr};
-    int block_slots = 512;    // 2 x hipDeviceProp_t::multiProcessorCount: what grid_rounds() divides a grid by
+    int block_slots = 512;    // 2 x hipDeviceProp_t::multiProcessorCount: what gemm_forms.h grid_rounds() divides a grid by
     // grow-only workspace arenas (activations), one per WS_* slot
     DevBuf ws[WS_COUNT];
     // device counter of the x3 mode's range contract: += 1 per thread that split a finite |x| >= 65520 into an fp16 pair
@@ -150,19 +150,6 @@ int ws_carve(avcer_ctx* ctx, int slot, const char* what, const Carve& carve) {
 // PIL's NEAREST resize to 224 (data/utils.py:34): the source index of output index `o` along an axis of `len` source pixels.
 // The one statement of the rule: preprocess_kernel, crop_tiles_kernel (kernels.hip) and jpeg_tiles_kernel (jpeg.hip) call it.
 __device__ __forceinline__ int nearest_src(int o, int len) { return min((int)(((double)o + 0.5) * ((double)len / 224.0)), len - 1); }
-
-// Rounds a grid of 256-thread blocks takes on the chip's block slots (two per CU: `slots` = 2 x the CU count the context
-// read from the device at creation, 512 on a whole MI355X), as the form / tile choices model them.
-// Calibrated on tools/ab_layers.py (profiles/r03_ab_layers*.txt, 128- against 112-row tiles of the same layer): a grid of
-// at most one block per CU runs in 0.62 of a round (a block alone on its CU is that much faster); behind whole rounds, a
-// partial round that still fits one block per CU (fraction f <= 0.5) costs 0.25 + 0.7 f -- the whole rounds end ragged and
-// absorb part of it --, a larger one a whole round (some CU runs two blocks from start to end).
-inline double grid_rounds(long tiles, long slots) {
-    const long whole = tiles / slots, rest = tiles % slots;
-    if (whole == 0) return 2 * tiles <= slots ? 0.62 : 1.0;
-    const double f = (double)rest / (double)slots;
-    return (double)whole + (rest == 0 ? 0.0 : (2 * rest <= slots ? 0.25 + 0.7 * f : 1.0));
-}
 
 // ---- gemm.hip
 int launch_conv_gemm(avcer_ctx* ctx, const avcer_conv_desc& d, int dtype, const void* x, const void* w,

@@ -1087,16 +1087,12 @@ void launch_skinny_t(const GemmParams& p, hipStream_t st) {
     else conv_gemm_skinny_kernel<OUT, 3, NFM, D><<<grid, dim3(64), 0, st>>>(p);
 }
 
-// The smallest tile whose grid still fits the chip in one round of one wave per SIMD (bit-identical results either way)
+// positions per wave tile: gemm_forms.h skinny_tile_m (bit-identical results either way)
 template <int OUT>
 void launch_skinny(const GemmParams& p, hipStream_t st) {
-    const long simds = (long)p.slots * 2;  // block slots = 2 per CU, 4 SIMDs per CU
-    // 16-position tiles while they leave half the SIMDs free (a wave is paced by its round trips -- the weights come from beyond
-    // the L2 once per launch -- so the smallest tile wins); past that the round trips lengthen with the load, and the 32-position
-    // tile moves 6 KiB per K-step where two 16s move 8 (tools/ab_layers.py --skinny, profiles/r05_skinny_ab.txt)
-    const long nt = p.N / 16 * (p.groups > 1 ? p.groups : 1);
-    if (p.tile_m == 16 || (p.tile_m == 0 && (long)((p.M + 15) / 16) * nt <= simds / 2)) launch_skinny_t<OUT, 1, 12>(p, st);
-    else if (p.tile_m == 32 || (p.tile_m == 0 && (long)((p.M + 31) / 32) * nt <= simds)) launch_skinny_t<OUT, 2, 8>(p, st);
+    const int tile_m = skinny_tile_m(p.M, p.N, p.groups, p.slots, p.tile_m);
+    if (tile_m == 16) launch_skinny_t<OUT, 1, 12>(p, st);
+    else if (tile_m == 32) launch_skinny_t<OUT, 2, 8>(p, st);
     else launch_skinny_t<OUT, 4, 4>(p, st);
 }
 
@@ -1112,28 +1108,19 @@ void launch_wd_t(GemmParams& p, hipStream_t st) {
     else conv_gemm_wd_kernel<OUT, 3, NFM><<<dim3(p.nwg), dim3(256), 0, st>>>(p);
 }
 
-// 128 or 112 positions per tile: whichever grid costs fewer (rounds x rows per tile); avcer_conv_desc.tile_m overrides.
+// 128 or 112 positions per tile: gemm_forms.h direct_tile_m
 template <int OUT>
 void launch_wd(const GemmParams& p0, hipStream_t st) {
     GemmParams p = p0;
-    const long ntn = p.N / 256;
-    const double c128 = grid_rounds((p.M + 127L) / 128 * ntn, p.slots) * 128, c112 = grid_rounds((p.M + 111L) / 112 * ntn, p.slots) * 112;
-    const bool m112 = p.tile_m == 112 || (p.tile_m == 0 && c112 < 0.97 * c128);
-    if (m112) launch_wd_t<OUT, 7>(p, st);
+    if (direct_tile_m(p.M, p.N, p.slots, p.tile_m) == 112) launch_wd_t<OUT, 7>(p, st);
     else launch_wd_t<OUT, 8>(p, st);
 }
 
-// Tile width by shape.  K <= 128: bandwidth-bound 1x1 convolutions, the 48 KiB BN = 64 tile lets three blocks share a CU.
-inline bool choose_bn128(const GemmParams& p) { return p.K > 128; }
-
+// tile width: gemm_forms.h staged_tile_n
 template <int MODE, int OUT>
 void launch_t(const GemmParams& p0, hipStream_t st) {
     GemmParams p = p0;
-    bool bn128 = p.N % 128 == 0 && choose_bn128(p);
-    // a grid of at most one block per two CUs (the LSTM's recurrent GEMMs, fc1, single-frame calls): twice the blocks at half the width
-    if (bn128 && (long)((p.M + 127) / 128) * (p.N / 128) <= p.slots / 4) bn128 = false;
-    if (p.tile_n == 64) bn128 = false;
-    if (p.tile_n == 128 && p.N % 128 == 0) bn128 = true;
+    const bool bn128 = staged_tile_n(p.M, p.N, p.K, p.slots, p.tile_n) == 128;
     p.ntm = (p.M + 127) / 128;
     p.gm = 8;  // grouped block order: 8 m-tiles x all n-tiles per group (0/4/8/16 measured within +-3 %)
     p.ntn = p.N / (bn128 ? 128 : 64);
@@ -1175,14 +1162,14 @@ int prof_begin(avcer_ctx* ctx, hipStream_t st, hipEvent_t* ev0, hipEvent_t* ev1,
 int launch_conv_gemm(avcer_ctx* ctx, const avcer_conv_desc& d, int dtype, const void* x, const void* w,
                      const float* scale, const float* bias, const void* residual, void* y, hipStream_t st,
                      const void* x2) {
-    if (dtype < 0 || dtype > 10) return set_err(ctx, AVCER_EINVAL, "conv_gemm: dtype %d", dtype);
-    const bool skinny = dtype >= 9;   // 9 / 10: dtype 7 / 8 for a handful of positions (conv_gemm_skinny_kernel)
-    const int es = (dtype == 1 || dtype == 2) ? 2 : 4;
-    const bool wdirect = dtype >= 7;  // 7 / 8 (and 9 / 10): dtype 5 / 6 with the weights in fragment order (conv_gemm_wd_kernel)
-    const bool a_split = dtype == 5 || dtype == 6 || wdirect, o_split = dtype == 4 || dtype == 5 || dtype == 7 || dtype == 9;
+    if (dtype < 0 || dtype >= kGemmForms) return set_err(ctx, AVCER_EINVAL, "conv_gemm: dtype %d", dtype);
+    const int form = kGemmForm[dtype].form;  // what the dtype means: gemm_forms.h
+    const int es = gemm_in_bytes(dtype);
+    const bool a_split = gemm_a_split(dtype);
     const int vec = 16 / es;
-    const int bk = ROWB / es;  // 32 elements (f32, split-fp16) or 64 (bf16) per K-step
-    const long M = (long)d.batch * d.out_h * d.out_w;
+    const int bk = gemm_bk(dtype);  // 32 elements (f32, split-fp16) or 64 (bf16) per K-step
+    static_assert(gemm_bk(0) * 4 == ROWB && gemm_bk(1) * 2 == ROWB, "a K-step is one ROWB-byte row");
+    const long M = gemm_m(d);
     const long K1 = (long)d.kh * d.kw * d.cin;
     const long K = K1 + (x2 ? d.x2_cin : 0);
     if (x2 && (d.kh != 1 || d.kw != 1 || d.pad_h || d.pad_w || d.groups > 1 || d.x2_cin <= 0 || K1 % bk || d.x2_cin % bk ||
@@ -1206,7 +1193,7 @@ int launch_conv_gemm(avcer_ctx* ctx, const avcer_conv_desc& d, int dtype, const 
             return set_err(ctx, AVCER_EINVAL, "conv_gemm: cin=%d with %d x %d taps: a K-step of %d elements would span more than two "
                            "taps (needs cin %% %d == 0 or cin > %d - gcd(cin, %d))", d.cin, d.kh, d.kw, bk, bk, bk - vec, bk);
     }
-    const int ovec = o_split ? 32 : 16 / ((dtype == 1) ? 2 : 4);  // 16-byte vectors / whole sp32 groups
+    const int ovec = gemm_ovec(dtype);  // 16-byte vectors / whole sp32 groups
     if (d.y_ld % ovec || d.y_coff % ovec || (residual && (d.r_ld % ovec || d.r_coff % ovec)))
         return set_err(ctx, AVCER_EINVAL, "conv_gemm: output/residual leading dims and offsets must be multiples of %d", ovec);
     if (a_split && x2 && (d.x2_cin % 32 || d.x2_coff % 32 || d.x2_stride_b % 32 || d.x2_stride_h % 32 || d.x2_stride_w % 32))
@@ -1235,7 +1222,7 @@ int launch_conv_gemm(avcer_ctx* ctx, const avcer_conv_desc& d, int dtype, const 
     if (residual && d.r_sub > 1 && ((long)(d.out_h - 1) * d.r_sub >= d.r_h || (long)(d.out_w - 1) * d.r_sub >= d.r_w))
         return set_err(ctx, AVCER_EINVAL, "conv_gemm: residual grid %d x %d too small for %d x %d outputs at step %d", d.r_h, d.r_w,
                        d.out_h, d.out_w, d.r_sub);
-    const int groups = d.groups > 1 ? d.groups : 1;
+    const int groups = gemm_groups(d);
     const long x_extent = ((long)(d.batch - 1) * d.x_stride_b + (long)(d.in_h - 1) * d.x_stride_h +
                            (long)(d.in_w - 1) * d.x_stride_w + d.x_coff + (long)groups * d.cin) * es;
     const long w_extent = (long)groups * d.n * K * es;
@@ -1255,44 +1242,38 @@ int launch_conv_gemm(avcer_ctx* ctx, const avcer_conv_desc& d, int dtype, const 
     if (d.tile_n != 0 && d.tile_n != 64 && d.tile_n != 128 && d.tile_n != 256)
         return set_err(ctx, AVCER_EINVAL, "conv_gemm: tile_n %d (0, 64, 128 or 256)", d.tile_n);
     p.tile_n = d.tile_n;
-    if (skinny ? (d.tile_m != 0 && d.tile_m != 16 && d.tile_m != 32 && d.tile_m != 64) : (d.tile_m != 0 && d.tile_m != 112 && d.tile_m != 128))
+    if (form == FORM_SKINNY ? (d.tile_m != 0 && d.tile_m != 16 && d.tile_m != 32 && d.tile_m != 64) : (d.tile_m != 0 && d.tile_m != 112 && d.tile_m != 128))
         return set_err(ctx, AVCER_EINVAL, "conv_gemm: tile_m %d (0, 112 or 128; dtype 9 / 10: 0, 16, 32 or 64)", d.tile_m);
     p.tile_m = d.tile_m;
-    p.WF = wdirect ? (const char*)w : nullptr;
-    if (skinny && (x2 || d.cin % 32 || d.n % 32 || M > 4096))
-        return set_err(ctx, AVCER_EINVAL, "conv_gemm: dtype %d (skinny form) needs one source, cin %% 32 == 0, n %% 32 == 0, M <= 4096 (M=%ld)", dtype, M);
-    if (wdirect && !skinny && (d.n % 256 || (K / bk) % 2 || groups != 1 || d.tile_n == 64 || d.tile_n == 128))
-        return set_err(ctx, AVCER_EINVAL, "conv_gemm: dtype %d needs N %% 256 == 0, an even number of K-steps, one group (N=%d, K=%ld)",
-                       dtype, d.n, K);
+    p.WF = kGemmForm[dtype].w_copy == W_FRAGS ? (const char*)w : nullptr;
     p.tapH4 = (int)((long)d.dil_h * d.x_stride_h * 4);
     p.tapW4 = (int)((long)d.dil_w * d.x_stride_w * 4);
-    // Fast gather: Cin a multiple of the K-step, no padding, and the last tap of the last output position inside the
-    // input -- true for every Linear, 1x1 convolution and un-padded Conv1d of both models.
-    p.fast = d.cin % bk == 0 && d.pad_h == 0 && d.pad_w == 0 &&
-             (long)(d.out_h - 1) * d.stride_h + (long)(d.kh - 1) * d.dil_h < d.in_h &&
-             (long)(d.out_w - 1) * d.stride_w + (long)(d.kw - 1) * d.dil_w < d.in_w;
-    if (wdirect && x2 && !p.fast) return set_err(ctx, AVCER_EINVAL, "conv_gemm: dtype %d with a second source needs a pad-free gather", dtype);
+    p.fast = gemm_fast_gather(d, bk);
+    if (const char* why = form == FORM_SKINNY ? skinny_cannot(d, K, x2 != nullptr, p.fast) : form == FORM_DIRECT ? direct_cannot(d, K, x2 != nullptr, p.fast) : nullptr)
+        return set_err(ctx, AVCER_EINVAL, "conv_gemm: dtype %d %s (M=%ld, N=%d, K=%ld)", dtype, why, M, d.n, K);
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     {
         // compulsory traffic: the input once (each position's taps overlap), the weights once, the output (+ residual) once
         const double in_el = (double)d.batch * d.in_h * d.in_w * d.cin * groups + (x2 ? (double)M * d.x2_cin : 0.0);
-        const double bytes = in_el * es + (double)w_extent + (double)M * d.n * groups * (dtype == 1 ? 2 : 4) * (residual ? 2 : 1);
-        TRY(prof_begin(ctx, st, &ev0, &ev1, skinny ? FAM_SKINNY : wdirect ? FAM_GEMM_WD : FAM_GEMM, 2.0 * (double)M * (double)d.n * (double)K * groups, bytes,
+        const double bytes = in_el * es + (double)w_extent + (double)M * d.n * groups * gemm_out_bytes(dtype) * (residual ? 2 : 1);
+        TRY(prof_begin(ctx, st, &ev0, &ev1, gemm_family(dtype), 2.0 * (double)M * (double)d.n * (double)K * groups, bytes,
                        M, (long)d.n * groups, K));
     }
+#define ROW(DTYPE, FORM, MODE, OUT) static_assert(gemm_row_is<DTYPE, FORM, MODE, OUT>, "dispatch differs from the gemm_forms.h table")
     switch (dtype) {
-        case 0: launch_t<0, 0>(p, st); break;  // f32
-        case 1: launch_t<1, 1>(p, st); break;  // bf16 -> bf16
-        case 2: launch_t<1, 0>(p, st); break;  // bf16 -> f32
-        case 3: launch_t<2, 0>(p, st); break;  // f32 (split on the fly) -> f32
-        case 4: launch_t<2, 2>(p, st); break;  // f32 (split on the fly) -> sp32
-        case 5: launch_t<3, 2>(p, st); break;  // sp32 -> sp32
-        case 6: launch_t<3, 0>(p, st); break;  // sp32 -> f32
-        case 7: launch_wd<2>(p, st); break;    // sp32 -> sp32, weights direct
-        case 8: launch_wd<0>(p, st); break;    // sp32 -> f32, weights direct
-        case 9: launch_skinny<2>(p, st); break;   // sp32 -> sp32, a handful of positions
-        default: launch_skinny<0>(p, st); break;  // sp32 -> f32, a handful of positions
+        case 0: ROW(0, FORM_STAGED, 0, 0); launch_t<0, 0>(p, st); break;  // f32
+        case 1: ROW(1, FORM_STAGED, 1, 1); launch_t<1, 1>(p, st); break;  // bf16 -> bf16
+        case 2: ROW(2, FORM_STAGED, 1, 0); launch_t<1, 0>(p, st); break;  // bf16 -> f32
+        case 3: ROW(3, FORM_STAGED, 2, 0); launch_t<2, 0>(p, st); break;  // f32 (split on the fly) -> f32
+        case 4: ROW(4, FORM_STAGED, 2, 2); launch_t<2, 2>(p, st); break;  // f32 (split on the fly) -> sp32
+        case 5: ROW(5, FORM_STAGED, 3, 2); launch_t<3, 2>(p, st); break;  // sp32 -> sp32
+        case 6: ROW(6, FORM_STAGED, 3, 0); launch_t<3, 0>(p, st); break;  // sp32 -> f32
+        case 7: ROW(7, FORM_DIRECT, 3, 2); launch_wd<2>(p, st); break;    // sp32 -> sp32, weights direct
+        case 8: ROW(8, FORM_DIRECT, 3, 0); launch_wd<0>(p, st); break;    // sp32 -> f32, weights direct
+        case 9: ROW(9, FORM_SKINNY, 3, 2); launch_skinny<2>(p, st); break;     // sp32 -> sp32, a handful of positions
+        default: ROW(10, FORM_SKINNY, 3, 0); launch_skinny<0>(p, st); break;   // sp32 -> f32, a handful of positions
     }
+#undef ROW
     if (ev1) (void)hipEventRecord(ev1, st);
     CHECK_LAUNCH(ctx, "conv_gemm");
     ctx->gemm_launches += 1;

@@ -804,7 +804,7 @@ int avcer_fuse_videos(avcer_ctx* ctx, const float* stat, const float* dyn_logits
  * grouped convolutions are supported (one launch, as for 5 / 6); M is not limited by the kernel.  tile_m = 16, 32 or 64 picks
  * the positions per wave tile (0: the smallest tile that leaves half of the chip's SIMDs free); tile_n does not apply.  Anything
  * else is AVCER_EINVAL: use 5 / 6.  The networks choose it while (M / 32) * (n / 16) wave tiles fit the chip's SIMDs in one
- * round and M <= 4096 (api.hip prefer_skinny).
+ * round and M <= 4096 (csrc/gemm_forms.h prefer_skinny).
  * "sp32" storage = per aligned group of 32 channels, 32 fp16 hi values then 32 fp16 lo values (x = hi + lo), i.e. the
  * layout avcer_split_weights produces; 4 bytes per element. */
 typedef struct avcer_conv_desc {

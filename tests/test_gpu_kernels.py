@@ -26,8 +26,10 @@ def _act(v, act):
     return F.relu(v) if act == 1 else (F.gelu(v) if act in (2, 3) else v)
 
 
-A_KIND = {0: "f32", 1: "bf16", 2: "bf16", 3: "f32", 4: "f32", 5: "sp32", 6: "sp32"}
-O_KIND = {0: "f32", 1: "bf16", 2: "f32", 3: "f32", 4: "sp32", 5: "sp32", 6: "f32"}
+# storage of the activations avcer_conv_gemm reads / writes, by dtype: the tests' own statement of the table in
+# avcer_amd/csrc/gemm_forms.h (tests/test_gemm_forms_cpu.py holds the two against each other)
+A_KIND = {0: "f32", 1: "bf16", 2: "bf16", 3: "f32", 4: "f32", 5: "sp32", 6: "sp32", 7: "sp32", 8: "sp32", 9: "sp32", 10: "sp32"}
+O_KIND = {0: "f32", 1: "bf16", 2: "f32", 3: "f32", 4: "sp32", 5: "sp32", 6: "f32", 7: "sp32", 8: "f32", 9: "sp32", 10: "f32"}
 
 
 def _enc(t, kind, dev):

@@ -13,12 +13,10 @@ from avcer_amd._lib import SPLIT_TRAILER
 from avcer_amd.engine import _ptr
 from avcer_amd.sp32 import from_sp32, to_sp32
 from guard_band import Band, check, columns
-from test_gpu_kernels import _desc, _enc
+from test_gpu_kernels import A_KIND, O_KIND, _desc, _enc
 
 pytestmark = pytest.mark.gpu
 
-A_KIND = {0: "f32", 1: "bf16", 2: "bf16", 3: "f32", 4: "f32", 5: "sp32", 6: "sp32", 7: "sp32", 8: "sp32", 9: "sp32", 10: "sp32"}
-O_KIND = {0: "f32", 1: "bf16", 2: "f32", 3: "f32", 4: "sp32", 5: "sp32", 6: "f32", 7: "sp32", 8: "f32", 9: "sp32", 10: "f32"}
 TORCH = {"f32": torch.float32, "bf16": torch.bfloat16, "sp32": torch.int16}
 PAD, COFF = 64, 32          # the strided form: y_ld = n + 64, y_coff = 32 (and the residual likewise)
 
