@@ -76,6 +76,12 @@ SIGNATURES = {
     "avcer_chart_path": (C.c_int, [C.c_int64, C.c_int]),
     "avcer_weight_search_counts": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                              C.c_void_p, C.c_void_p, c_stream]),
+    "avcer_eval_tables_workspace": (C.c_int64, [C.c_int64]),
+    "avcer_eval_tables": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p,
+                                    C.c_void_p, C.c_int64, c_stream]),
+    "avcer_eval_confusion": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_void_p, c_stream]),
     "avcer_audio_frame_mean": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                          C.c_void_p, C.c_void_p, c_stream]),
     "avcer_load_face": (C.c_int, [c_ctx, C.c_void_p, C.c_size_t]),

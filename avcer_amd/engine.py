@@ -27,6 +27,9 @@ PAD_MODES = {"mean": 0, "constant": 1, "repeat": 2}
 _JPEG_DESC_BYTES = _JPEG_DESC.itemsize  # sizeof(struct avcer_jpeg_desc): jpeg.DESC is its one statement on this side
 
 
+EVAL_MAX_ROWS = 1 << 28  # include/avcer_hip.h AVCER_EVAL_MAX_ROWS
+
+
 def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -567,6 +570,102 @@ class Engine:
         self._check(self.lib.avcer_weight_search_counts(self.ctx, _ptr(p), _ptr(lab), n, m, c, _ptr(wt), w, _ptr(tp), _ptr(pred),
                                                         self._stream()))
         return tp, pred
+
+    def eval_tables(self, rows, row_counts, need, need_counts, out_counts, softmax: bool, video_level: bool = False, keys=None,
+                    key_lo=None, key_spans=None, out=None):
+        """One model's tables of a whole file list (include/avcer_hip.h avcer_eval_tables; get_pred_av.py:77-195).  rows [R, c]
+        (7 <= c <= 8): the videos' raw rows one behind the other; keys [R] (optional): each row's `frames` number, with key_lo /
+        key_spans [V]: the first key value and the number of key values of each video's range; row_counts, need_counts,
+        out_counts [V]: HOST integer arrays, the rows, kept positions and output rows per video; need: the videos' ascending
+        kept positions one behind the other.  video_level: one output row per video (out_counts and need are ignored).
+        Returns float64 [sum(out_counts), 7] on the device (`out`: write into this tensor instead).  Limits are the library's:
+        AvcerError with code AVCER_EINVAL.  No host synchronisation."""
+        x = self._dev(rows, torch.float64)
+        if x.dim() != 2:
+            raise ValueError(f"eval_tables: rows [R, c] expected, got {tuple(x.shape)}")
+        counts = [np.asarray(row_counts, dtype=np.int64).reshape(-1)]
+        nv = int(counts[0].shape[0])
+        if video_level:
+            counts += [np.zeros(nv, dtype=np.int64), np.ones(nv, dtype=np.int64)]
+        else:
+            counts += [np.asarray(a, dtype=np.int64).reshape(-1) for a in (need_counts, out_counts)]
+        if any(a.shape[0] != nv for a in counts) or any((a < 0).any() for a in counts):
+            raise ValueError("eval_tables: row_counts, need_counts and out_counts are one non-negative count per video")
+        n_rows, n_need, n_out = (int(a.sum()) for a in counts)
+        if n_rows != int(x.shape[0]):
+            raise ValueError(f"eval_tables: {int(x.shape[0])} rows, row_counts sum to {n_rows}")
+        nd = np.asarray([] if video_level else need, dtype=np.int64).reshape(-1)
+        if nd.shape[0] != n_need:
+            raise ValueError(f"eval_tables: {nd.shape[0]} kept positions, need_counts sum to {n_need}")
+        n_slots = 0
+        spans = np.zeros(nv, dtype=np.int64)
+        if keys is not None:
+            spans = np.asarray(key_spans, dtype=np.int64).reshape(-1)
+            lo = np.asarray(key_lo, dtype=np.int64).reshape(-1)
+            if spans.shape[0] != nv or lo.shape[0] != nv or (spans < 0).any():
+                raise ValueError("eval_tables: key_lo and key_spans are one value per video")
+            n_slots = int(spans.sum())
+        sizes = (n_rows, n_need, n_out, n_slots)
+        fits = max(sizes) <= EVAL_MAX_ROWS  # beyond it the library refuses the sizes themselves: nothing is read or allocated for them
+        if fits:
+            offs = np.zeros((4, nv + 1), dtype=np.int32)
+            for i, a in enumerate(counts + [spans]):
+                offs[i, 1:] = np.cumsum(a)
+            packed = np.concatenate([offs.reshape(-1), (lo if keys is not None else spans).astype(np.int32), nd.astype(np.int32)])
+        else:
+            packed = np.zeros(5 * nv + 4, dtype=np.int32)
+        dev = torch.from_numpy(packed).to(self.device, non_blocking=True)
+        row_off, need_off, out_off, key_off = (dev[i * (nv + 1):(i + 1) * (nv + 1)] for i in range(4))
+        klo, nd_dev = dev[4 * (nv + 1):5 * nv + 4], dev[5 * nv + 4:]
+        k = None
+        ws, ws_bytes = None, 0
+        if keys is not None:
+            k = self._dev(keys, torch.int32)
+            if k.dim() != 1 or int(k.shape[0]) != n_rows:
+                raise ValueError(f"eval_tables: {n_rows} rows, keys {tuple(k.shape)}")
+            ws_bytes = int(self.lib.avcer_eval_tables_workspace(n_slots)) if fits else 0
+            ws = self._new(max(ws_bytes, 8), dtype=torch.uint8)
+        if out is None:
+            out = self._new(n_out if fits else 0, 7, dtype=torch.float64)
+        elif out.dtype != torch.float64 or tuple(out.shape) != (n_out, 7) or not out.is_contiguous():
+            raise ValueError(f"eval_tables: out must be a contiguous float64 [{n_out}, 7]")
+        self._check(self.lib.avcer_eval_tables(self.ctx, _ptr(x), _ptr(k), n_rows, int(x.shape[1]), _ptr(row_off), _ptr(klo), _ptr(key_off),
+                                               n_slots, _ptr(nd_dev), n_need, _ptr(need_off), _ptr(out_off), nv, n_out, int(bool(softmax)),
+                                               int(bool(video_level)), _ptr(out), _ptr(ws), ws_bytes, self._stream()))
+        return out
+
+    def eval_confusion(self, tables, labels=None, weights_1=None, weights_2=None, compound: int = 0, want_pred: bool = True,
+                       want_cm: bool = True, pred=None, cm=None):
+        """The prediction of a model or a fusion and its confusion matrix (include/avcer_hip.h avcer_eval_confusion;
+        get_pred_av.py:35-45).  tables [m, N, 7], labels [N]; weights_1 [m, 7] and weights_2 [m] optional (ones).  compound: 0, or
+        EVAL_COMPOUND with EVAL_CE_WEIGHTS / EVAL_CE_MASK for the compound-expression rule in front of the argmax.  Returns
+        (pred int32 [N] or None, cm int64 [7, 7] or None) on the device.  No host synchronisation."""
+        t = self._dev(tables, torch.float64)
+        if t.dim() != 3 or t.shape[2] != 7:
+            raise ValueError(f"eval_confusion: tables [m, N, 7] expected, got {tuple(t.shape)}")
+        m, n = int(t.shape[0]), int(t.shape[1])
+        lab = None
+        if labels is not None:
+            lab = self._dev(labels, torch.int32)
+            if lab.dim() != 1 or int(lab.shape[0]) != n:
+                raise ValueError(f"eval_confusion: {n} rows, labels {tuple(lab.shape)}")
+        w1 = w2 = None
+        if weights_1 is not None:
+            w1 = np.ascontiguousarray(np.asarray(weights_1, dtype=np.float64))
+            if w1.shape != (m, 7):
+                raise ValueError(f"eval_confusion: weights_1 [{m}, 7] expected, got {w1.shape}")
+        if weights_2 is not None:
+            w2 = np.ascontiguousarray(np.asarray(weights_2, dtype=np.float64))
+            if w2.shape != (m,):
+                raise ValueError(f"eval_confusion: weights_2 [{m}] expected, got {w2.shape}")
+        if pred is None and want_pred:
+            pred = self._new(n, dtype=torch.int32)
+        if cm is None and want_cm and lab is not None:
+            cm = self._new(7, 7, dtype=torch.int64)
+        self._check(self.lib.avcer_eval_confusion(self.ctx, _ptr(t), _ptr(lab), n, m, None if w1 is None else w1.ctypes.data_as(C.c_void_p),
+                                                  None if w2 is None else w2.ctypes.data_as(C.c_void_p), int(compound), _ptr(pred), _ptr(cm),
+                                                  self._stream()))
+        return pred, cm
 
     def audio_frame_mean(self, win_logits, frame_lo, frame_hi, n_frames: int):
         x = self._dev(win_logits, torch.float32)

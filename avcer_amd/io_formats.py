@@ -166,3 +166,43 @@ def dataset_fusion(engine, prediction_file_format: str, root: str, path_preds, n
     txt = os.path.join(save_path, f"C_EXPR_DB_{modality}_sd_{weight_type}_{ce_weights_type}_{ce_mask}.txt")
     save_txt(SUBMISSION_COLUMNS, locations, av_pred, txt)
     return locations, av_pred, txt
+
+
+def dataset_fusion_audio(engine, prediction_file_format: str, path_pred: str, name_videos, name_model: str, modality: str,
+                         ce_weights_type: bool, save_path: str = "src/pred_results/DF_C_EXPR_DB/"):
+    """get_pred_audio.get_c_expr_db_pred (get_pred_audio.py:144-249): the audio model's submission file.  Per video the rows of
+    each frame are averaged, the frames the prediction file lists are kept, the last of them repeated up to the listed count, and
+    the softmax of every row goes through the compound-expression rule -- one Engine.eval_tables and one Engine.eval_confusion
+    launch for all videos, in float64 as pandas and numpy work there.  The reference calls get_compound_expression without its
+    `ce_mask` argument (:221-223, a TypeError as the function stands); the call is read as "no mask", which is what the
+    four-argument version it was written for computed.  Returns (image_locations, audio_pred, txt_path)."""
+    from . import evaluate as ev
+
+    fmt = pd.read_csv(prediction_file_format)
+    by_video = {}
+    for loc in fmt.image_location:
+        by_video.setdefault(loc.split("/")[0], []).append(loc)
+    parts, keys, needs, targets, locations = [], [], [], [], []
+    for video in name_videos:
+        rows, frames = read_audio_csv(os.path.join(path_pred, video) + ".csv")
+        listed = by_video.get(video, [])
+        wanted = set(listed)
+        have = np.unique(frames)  # the groups, in the order `reset_index` numbers them
+        need = np.array([g for g, f in enumerate(have) if f"{video}/{str(int(f) + 1).zfill(5)}.jpg" in wanted], dtype=np.int64)
+        if len(listed) > len(need) and not len(need):
+            raise IndexError("index -1 is out of bounds for axis 0 with size 0")  # curr_pred_audio[-1], get_pred_audio.py:190
+        parts.append(np.asarray(rows, dtype=np.float64))
+        keys.append(frames)
+        needs.append(need)
+        targets.append(max(len(listed), len(need)))
+        locations.extend(listed)
+    table = ev._keyed_table("audio", parts, keys, targets)
+    probs = engine.eval_tables(table.rows, table.row_counts, np.concatenate(needs), [len(n) for n in needs], table.out_counts, True,
+                               False, table.keys, table.key_lo, table.key_spans)
+    flags = ev.EVAL_COMPOUND | (ev.EVAL_CE_WEIGHTS if ce_weights_type else 0)
+    pred, _ = engine.eval_confusion(probs[None], compound=flags, want_cm=False)
+    audio_pred = pred.cpu().numpy()
+    os.makedirs(save_path, exist_ok=True)
+    txt = os.path.join(save_path, f"C_EXPR_DB_{modality}_{name_model}_ce_type_{ce_weights_type}.txt")
+    save_txt(SUBMISSION_COLUMNS, locations, audio_pred, txt)
+    return locations, audio_pred, txt

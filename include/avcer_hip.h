@@ -100,7 +100,10 @@ enum {
  *      avcer_resize_frames, avcer_resize_form (PIL's Image.resize of a frame batch on the device, for the detector on a smaller
  *      copy) joined under 8 the same way: two more symbols, nothing that existed changed.
  *      avcer_chart_series, avcer_chart_path (the traces of the prediction timeline chart) and the record struct avcer_chart_plan
- *      joined under 8 the same way: two more symbols, nothing that existed changed. */
+ *      joined under 8 the same way: two more symbols, nothing that existed changed.
+ *      avcer_eval_tables, avcer_eval_tables_workspace, avcer_eval_confusion (a dataset's per-video CSV tables turned into the
+ *      trues / preds tables of the weight search, and a model or fusion scored on them) joined under 8 the same way: three more
+ *      symbols, nothing that existed changed. */
 #define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
@@ -790,6 +793,62 @@ int avcer_fuse_videos(avcer_ctx* ctx, const float* stat, const float* dyn_logits
                       const int32_t* n_aud, int n_videos, int64_t n_frames, int64_t n_windows, int c, const double* w1_host,
                       const double* w2_host, int ce_weights_type, int ce_mask, float* aud_mean, int32_t* count,
                       double* comp_prob, int32_t* comp_argmax, avcer_stream_t stream);
+
+/* Dataset evaluation, part 1: the per-video loops of get_abaw_pred / get_afew_pred for ONE model's tables of a whole file list.
+ *   ref: get_pred_av.py:77-195, get_pred_video.py (its twins), get_pred_audio.py:64-141, data/utils.py:125-127 (softmax)
+ * rows f64 [n_rows, c], 7 <= c <= 8: the raw rows of all videos one behind the other; only the first 7 columns are used.
+ * keys i32 [n_rows] or NULL: the audio CSV's `frames` number of each row (one row per (window, frame) pair, in no order).
+ * row_off i32 [n_videos+1]: prefix offsets of the videos' rows.  key_lo i32 [n_videos], key_off i32 [n_videos+1] (keys only):
+ * video v's keys lie in [key_lo[v], key_lo[v] + key_off[v+1] - key_off[v]); a row whose key lies outside belongs to no group.
+ * need i32 [n_need], need_off i32 [n_videos+1]: per video the ascending kept positions (`need_index`), need_off[n_videos] = n_need.
+ * out_off i32 [n_videos+1]: prefix offsets of the videos' output rows (their target lengths).  All of these are DEVICE pointers;
+ * n_rows, n_slots = key_off[n_videos], n_need and n_out = out_off[n_videos] are passed by value, because launches and the workspace are
+ * sized from them without reading device memory.  Per video, what the reference's loop does:
+ *   1. with keys: the mean of the rows of each distinct key, the groups numbered 0, 1, .. in ascending key order
+ *      (`groupby("frames").mean().reset_index()`: a kept position indexes this GROUP NUMBER, not the frame value).  A NaN is
+ *      left out of its column's mean as pandas leaves it out (skipna); a column of a group with nothing else is NaN.  The sum is
+ *      exact: every term is rounded once to a fixed-point grid 2^-60 of the column's largest magnitude in the group and added as
+ *      an integer, so it does not depend on the order of the rows (pandas' compensated sum differs from it by < 1 ulp of the
+ *      largest term).  Without keys every row is its own group.
+ *   2. softmax != 0: exp(x - max) / sum over the 7 columns in index order (data/utils.py:125-127); 0: the row as it is.
+ *   3. video_level == 0: output row j of the video is the group need[min(j, k - 1)], where k is the number of kept positions
+ *      below the video's group count: selection, then the last surviving row repeated up to the target length
+ *      (get_pred_av.py:121-129; the caller states the target, and with it that the reference extends the static table by the
+ *      DYNAMIC table's deficit, :124-125).  k == 0 with a target > 0 is where the reference raises IndexError: NaN rows here.
+ *      video_level != 0: ONE output row per video (out_off[v] = v, `need` unused), the mean of step 2 over all its groups
+ *      (np.mean(axis=0)): a fixed tree over 256 partial sums, within n * 2^-53 of numpy's sequential sum; NaN without a group.
+ * out f64 [n_out, 7].  ws: avcer_eval_tables_workspace(n_slots) bytes of device memory (0 without keys; NULL then).
+ * Limits (AVCER_EINVAL beyond them): 1 <= n_videos <= AVCER_EVAL_MAX_VIDEOS, 7 <= c <= 8, 0 <= n_rows, n_slots, n_need, n_out <=
+ * AVCER_EVAL_MAX_ROWS, video_level -> n_out == n_videos, keys -> key_lo, key_off and ws.  No host synchronisation. */
+#define AVCER_EVAL_MAX_VIDEOS 16777216
+#define AVCER_EVAL_MAX_ROWS 268435456LL
+int64_t avcer_eval_tables_workspace(int64_t n_slots);
+int avcer_eval_tables(avcer_ctx* ctx, const double* rows, const int32_t* keys, int64_t n_rows, int c, const int32_t* row_off,
+                      const int32_t* key_lo, const int32_t* key_off, int64_t n_slots, const int32_t* need, int64_t n_need,
+                      const int32_t* need_off, const int32_t* out_off, int n_videos, int64_t n_out, int softmax, int video_level, double* out, void* ws,
+                      int64_t ws_bytes, avcer_stream_t stream);
+
+/* Dataset evaluation, part 2: the prediction of a model or of a fusion and its confusion matrix (get_metrics).
+ *   ref: get_pred_av.py:35-45 and its twin in get_pred_video.py, get_pred_audio.py:30-34; get_compound_expression
+ *        (data/utils.py:222-241) for the audio-only submission file (get_pred_audio.py:202-228)
+ * tables f64 [m][n][7] and labels i32 [n] (or NULL) on the device; w1_host f64 [m][7] and w2_host f64 [m] on the HOST, each
+ * optional (NULL = ones: a product with 1.0 is the value itself).  Per row i, every product and sum rounded on its own:
+ *   f = (tables[0][i] * w1[0]) * w2[0];   f = f + (tables[q][i] * w1[q]) * w2[q]  for q = 1 .. m-1
+ *   compound & AVCER_EVAL_COMPOUND: f is replaced by the 7 compound-expression values of the audio order,
+ *     g[j] = f[p1[j]] * u1[j] + f[p2[j]] * u2[j], u = 1 or, with AVCER_EVAL_CE_WEIGHTS, the pair's class weights over their sum;
+ *     with AVCER_EVAL_CE_MASK values of f not above 1/7 count as 0 first;
+ *   a = the first index of the maximum, a NaN counting as the maximum (np.argmax).
+ * pred i32 [n] (optional) receives a; cm i64 [7][7] (optional, needs labels) receives the counts of (labels[i], a), zeroed by the
+ * call in stream order; a label outside 0..6 is counted nowhere (confusion_matrix(labels=range(7))).  Blocks count in LDS and
+ * add each non-zero cell once, with integer atomics: the result does not depend on their order.
+ * Limits (AVCER_EINVAL beyond them): 1 <= m <= AVCER_EVAL_MAX_MODELS, 1 <= n <= AVCER_EVAL_MAX_ROWS, cm needs labels, one of
+ * pred and cm is given.  No host synchronisation. */
+#define AVCER_EVAL_MAX_MODELS 4
+#define AVCER_EVAL_COMPOUND 1
+#define AVCER_EVAL_CE_WEIGHTS 2
+#define AVCER_EVAL_CE_MASK 4
+int avcer_eval_confusion(avcer_ctx* ctx, const double* tables, const int32_t* labels, int64_t n, int m, const double* w1_host,
+                         const double* w2_host, int compound, int32_t* pred, int64_t* cm, avcer_stream_t stream);
 
 /* The contraction kernel itself (implicit-GEMM convolution with fused epilogue), exported for kernel-level
  * parity tests and micro-benchmarks:  Y[m, n] = act(scale[n] * sum_k A[m,k] * W[n,k] + bias[n] (+ R[m,n]))
