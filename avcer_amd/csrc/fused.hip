@@ -86,119 +86,103 @@ struct StemParams {
 constexpr int ST_TH = 8, ST_TW = 7;                       // pooled tile
 constexpr int ST_RH = 2 * ST_TH + 1, ST_RW = 2 * ST_TW + 1;  // stem region 17 x 15 = 255 positions
 constexpr int ST_TY = 7, ST_TX = 8;                       // tiles per frame (7 x 8 >= 55 / 8 x 55 / 7)
+constexpr int ST_NK = 7;                                  // tap rows: K = 7 x (8 pixels x 4 channels)
+constexpr int ST_PROWS = 2 * (ST_RH - 1) + ST_NK, ST_PCH = (2 * (ST_RW - 1) + 8) / 2;  // 39 patch rows of 18 16-byte chunks (36 pixels)
+constexpr int ST_PLCH = ST_PROWS * ST_PCH;                // 702 chunks, 11 232 B, per patch plane
+constexpr int ST_WT = 64 * ROWB;                          // one tap row's weight tile, 8 KiB
 
-__device__ __forceinline__ int stage64(int row, int chunk) { return row * 256 + ((chunk ^ (row & 7)) << 4); }
-
+// The stem tile, stated once for stem_pool_kernel and the two forms of stem_pool_u8_kernel.
 // One block = one 8 x 7 tile of pooled outputs of one frame: the 17 x 15 stem positions under it are one 256-row
-// implicit-GEMM tile (K = 7 tap rows x 8 pixels x 4 channels, N = 64), the pool runs on the f32 image in LDS.
-// Neighbouring tiles recompute one shared stem row / column (255 positions per 224 useful ones).
-//
-// The A operand is never expanded: the 39 x 36-pixel patch of the (already padded) planar image under the tile is copied
-// to LDS once, as it lies in memory (hi plane, then lo plane; 22 KiB), and a fragment is read straight out of it -- the
-// 8 K-elements of lane group g in tap row ky are the 2 pixels x 4 channels at patch[(2 ry + ky)][2 rx + 2 g], 16
-// contiguous, 16-byte-aligned bytes.  (An im2col tile per tap row moved 224 KiB through the L2 -> LDS path per block.)
-// All seven weight tiles (56 KiB) arrive with the same burst, so the K loop has no barrier and no wait in it; the second
-// block of the CU computes while this one waits for its burst.  Rows of positions outside the 112 x 112 map read whatever
-// follows in memory (or zeros past the planes): each output row depends on its own A row only, and the pool never reads them.
-__global__ void __launch_bounds__(256, 2) stem_pool_kernel(const StemParams p) {
-    constexpr int BN = 64, NK = 7;
-    constexpr int PROWS = 2 * (ST_RH - 1) + NK, PCH = (2 * (ST_RW - 1) + 8) / 2;  // 39 patch rows of 18 16-byte chunks (36 pixels)
-    constexpr int PLANE = PROWS * PCH * 16;                                       // 11 232 B per plane
-    constexpr int NCH = 2 * PROWS * PCH;                                          // 1 404 chunks
-    constexpr int WOFF = ((2 * PLANE + 1023) / 1024) * 1024;                      // weights behind the patch
-    constexpr int WT = BN * ROWB;                                                 // one tap row's weight tile, 8 KiB
-    constexpr int LDS_BYTES = WOFF + NK * WT > 256 * 256 ? WOFF + NK * WT : 256 * 256;
-    __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int blk = xcd_remap(blockIdx.x, gridDim.x);
-    const int b = blk / (ST_TY * ST_TX), t = blk % (ST_TY * ST_TX);
-    const int ty = t / ST_TX, tx = t % ST_TX;
+// implicit-GEMM tile (K = 7 tap rows x 8 pixels x 4 channels, N = 64); BN + ReLU park it as an f32 image in LDS and the
+// 3x3/2 max-pool runs on that image.  Neighbouring tiles recompute one shared stem row / column (255 positions per 224
+// useful ones).
+// The A operand is never expanded: the 39 x 36-pixel patch under the tile lies in LDS as fp16 [39][18 chunks of 2 pixels x 4
+// channels], and a fragment is read straight out of it -- the 8 K-elements of lane group g in tap row ky are the 2 pixels x
+// 4 channels at patch[(2 ry + ky)][2 rx + 2 g], 16 contiguous, 16-byte-aligned bytes.  (An im2col tile per tap row moved
+// 224 KiB through the L2 -> LDS path per block.)
+// Per kernel, because it really differs: how the patch gets into LDS, how the seven weight tiles arrive, and whether the
+// image is parked whole (64 channels) or in two halves of 32.
 
-    const float wmul = split_wmul(p.W, 64 * NK * ROWB);
-    const auto prs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.P), (short)0, (int)p.p_bytes, 0x00020000);
-    const auto wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.W), (short)0, 64 * NK * ROWB, 0x00020000);
-    // patch: chunk c of the LDS image = chunk (c % 702) of plane c / 702; one DMA instruction copies 64 consecutive chunks
-    const unsigned origin = (unsigned)((((long)b * 230 + 4 * ST_TH * ty) * 230 + 4 * ST_TW * tx) * 8);
-#pragma unroll
-    for (int j = 0; j < (NCH + 255) / 256; ++j) {
-        const int piece = wave + 4 * j;
-        const int c = piece * 64 + lane;
-        const int plane = c >= NCH / 2, ci = c - plane * (NCH / 2);
-        const int prow = ci / PCH, pc = ci - prow * PCH;
-        const unsigned off = c < NCH ? origin + (unsigned)(prow * (230 * 8) + pc * 16) + plane * p.plane_bytes : OOB;
-        if (piece * 64 < NCH) dma16(prs, smem + piece * 1024, off);
-    }
-    // weights: tap row ky = rows [64][32 K] of p.W at column block ky, 8 DMA instructions of 8 rows each, swizzled like every tile
-    {
-        const int lrow8 = lane >> 3, slot = lane & 7;
-#pragma unroll
-        for (int j = 0; j < NK * 8 / 4; ++j) {
-            const int piece = wave + 4 * j;  // 0 .. 55
-            const int ky = piece >> 3, row = (piece & 7) * 8 + lrow8;
-            dma16(wrs, smem + WOFF + piece * 1024, (unsigned)(row * (NK * ROWB) + ky * ROWB + ((slot ^ swz_key(row)) << 4)));
-        }
-    }
-
-    f32x4_t acc[4][4];  // [channel tile][position tile]: wave = 64 positions x 64 channels
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[a][c] = f32x4_t{0};
-    const int g = lane >> 4, l15 = lane & 15;
-    int abase[4];  // byte offset of this lane's fragment in tap row 0 of the hi plane
+// Byte offsets of this lane's four A fragments in tap row 0 of a patch plane.  Row 255 of the tile is no position: it reads
+// fragment 0, and nothing reads its output row.
+__device__ __forceinline__ void stem_frag_offsets(int wave, int l15, int g, int (&abase)[4]) {
 #pragma unroll
     for (int fm = 0; fm < 4; ++fm) {
         const int row = wave * 64 + fm * 16 + l15;
         const int ry = row / ST_RW, rx = row - ry * ST_RW;
-        abase[fm] = row < ST_RH * ST_RW ? ((2 * ry) * PCH + rx + g) * 16 : 0;
+        abase[fm] = row < ST_RH * ST_RW ? ((2 * ry) * ST_PCH + rx + g) * 16 : 0;
     }
-    __syncthreads();  // patch and weights have landed
+}
+
+// One tap row: wave = 64 positions x 64 channels, acc[channel tile][position tile].  LO: the activation has a lo plane, three
+// MFMAs per product in mfma3's order (wl.ah, wh.al, wh.ah); !LO: the activation is exact in fp16, wl.ah then wh.ah.  The
+// order of accumulation is the bit-identity contract of these kernels: do not reorder the MFMAs of one accumulator.
+template <bool LO>
+__device__ __forceinline__ void stem_tap_row(f32x4_t (&acc)[4][4], const char* patch_hi, const char* patch_lo, const int (&abase)[4],
+                                             int ky, const char* wt, int l15, int g) {
+    spx8_t ah[4], al[4];
 #pragma unroll
-    for (int ky = 0; ky < NK; ++ky) {
-        const char* sb = smem + WOFF + ky * WT;
-        spx8_t ah[4], al[4];
-#pragma unroll
-        for (int fm = 0; fm < 4; ++fm) {
-            ah[fm] = *reinterpret_cast<const spx8_t*>(smem + abase[fm] + ky * (PCH * 16));
-            al[fm] = *reinterpret_cast<const spx8_t*>(smem + PLANE + abase[fm] + ky * (PCH * 16));
-        }
-#pragma unroll
-        for (int fn = 0; fn < 4; ++fn) {
-            const spx8_t wh = ldfrag(sb, fn * 16 + l15, g), wl = ldfrag(sb, fn * 16 + l15, 4 + g);
-#pragma unroll
-            for (int fm = 0; fm < 4; ++fm) mfma3(acc[fn][fm], wh, wl, ah[fm], al[fm]);
-        }
+    for (int fm = 0; fm < 4; ++fm) {
+        ah[fm] = *reinterpret_cast<const spx8_t*>(patch_hi + abase[fm] + ky * (ST_PCH * 16));
+        if constexpr (LO) al[fm] = *reinterpret_cast<const spx8_t*>(patch_lo + abase[fm] + ky * (ST_PCH * 16));
     }
-    pin(acc);
-    __syncthreads();  // every wave is done with the patch: the f32 image below overwrites it
-    // BN + ReLU, parked as an f32 [256 positions][64 channels] image (64 KiB of the 80 KiB tile buffers)
 #pragma unroll
     for (int fn = 0; fn < 4; ++fn) {
-        const int ch = 32 * (fn >> 1) + 8 * g + 4 * (fn & 1);  // weight rows are stored permuted (split_weight_rows_kernel)
-        float4 sc = *reinterpret_cast<const float4*>(p.scale + ch);
-        const float4 bi = *reinterpret_cast<const float4*>(p.bias + ch);
+        const spx8_t wh = ldfrag(wt, fn * 16 + l15, g), wl = ldfrag(wt, fn * 16 + l15, 4 + g);
+#pragma unroll
+        for (int fm = 0; fm < 4; ++fm) {
+            if constexpr (LO) {
+                mfma3(acc[fn][fm], wh, wl, ah[fm], al[fm]);
+            } else {
+                acc[fn][fm] = mfma_sp(wl, ah[fm], acc[fn][fm]);
+                acc[fn][fm] = mfma_sp(wh, ah[fm], acc[fn][fm]);
+            }
+        }
+    }
+}
+
+// The f32 image [256 positions][CH channels]: byte offset of 16-byte chunk `chunk` of row `row`, swizzled against bank conflicts
+template <int CH>
+__device__ __forceinline__ int stem_img(int row, int chunk) { return row * (CH * 4) + ((chunk ^ (row & 7)) << 4); }
+
+// BN + ReLU of channel tiles fn0 .. fn0 + CH / 16 - 1, parked in the image.  Weight rows are stored permuted
+// (split_weight_rows_kernel): tile fn, lane group g hold channels 32 (fn >> 1) + 8 g + 4 (fn & 1) .. + 3.
+// bias_at(row): the 64 shifts of that position (the BN shift, or the border-class row of the u8 form).
+template <int CH, class BiasAt>
+__device__ __forceinline__ void stem_park(char* img, const f32x4_t (&acc)[4][4], int fn0, const float* scale, float wmul, BiasAt bias_at,
+                                          int wave, int l15, int g) {
+#pragma unroll
+    for (int f = 0; f < CH / 16; ++f) {
+        const int fn = fn0 + f;
+        const int ch = 32 * (fn >> 1) + 8 * g + 4 * (fn & 1);
+        float4 sc = *reinterpret_cast<const float4*>(scale + ch);
         sc = make_float4(sc.x * wmul, sc.y * wmul, sc.z * wmul, sc.w * wmul);  // undoes the power of two of the weight split
 #pragma unroll
         for (int fm = 0; fm < 4; ++fm) {
             const int row = wave * 64 + fm * 16 + l15;
-            *reinterpret_cast<float4*>(smem + stage64(row, ch >> 2)) =
+            const float4 bi = *reinterpret_cast<const float4*>(bias_at(row) + ch);
+            *reinterpret_cast<float4*>(img + stem_img<CH>(row, 8 * ((fn >> 1) % (CH / 32)) + 2 * g + (fn & 1))) =
                 make_float4(relu_nan(acc[fn][fm][0] * sc.x + bi.x), relu_nan(acc[fn][fm][1] * sc.y + bi.y),
                             relu_nan(acc[fn][fm][2] * sc.z + bi.z), relu_nan(acc[fn][fm][3] * sc.w + bi.w));
         }
     }
-    __syncthreads();
-    // 3x3/2 max-pool over the image (no padding: video.py:103), 8 channels per thread, whole-line sp32 stores
-    sp_flags_t ovm = 0;  // range contract of the sp32 output (split_dev.h sp_commit)
+}
+
+// 3x3/2 max-pool over the image, 8 channels per thread, whole-line sp32 stores of output channels ch0 .. ch0 + CH - 1.
+// !FACE: no padding (video.py:103), region row r = stem row 2 py0 + r, 55 x 55 outputs.  FACE: torchvision's padding 1,
+// region row r = stem row 2 py0 - 1 + r; the pool's padding and the map's end are skipped; mh x mw outputs.
+template <int CH, bool FACE>
+__device__ __forceinline__ void stem_pool_store(const char* img, const StemParams& p, int b, int ty, int tx, int ch0, int tid,
+                                                sp_flags_t& ovm) {
+    const int mh = FACE ? p.mh : 55, mw = FACE ? p.mw : 55;
 #pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        const int item = pass * 256 + tid;
-        const int pp = item >> 3, c8 = item & 7;
+    for (int first = 0; first < ST_TH * ST_TW * (CH / 8); first += 256) {
+        const int item = first + tid;
+        const int pp = item / (CH / 8), c8 = item % (CH / 8);  // pooled position of the tile, group of 8 channels
         const int ppy = pp / ST_TW, ppx = pp - ppy * ST_TW;
         const int py = ST_TH * ty + ppy, px = ST_TW * tx + ppx;
-        if (pp >= ST_TH * ST_TW || py >= 55 || px >= 55) continue;
+        if (pp >= ST_TH * ST_TW || py >= mh || px >= mw) continue;
         float m[8];
-        bool nan = false;
 #pragma unroll
         for (int j = 0; j < 8; ++j) m[j] = 0.f;  // post-ReLU values are >= 0
         bool anynan[8] = {false, false, false, false, false, false, false, false};
@@ -207,26 +191,92 @@ __global__ void __launch_bounds__(256, 2) stem_pool_kernel(const StemParams p) {
 #pragma unroll
             for (int dx = 0; dx < 3; ++dx) {
                 const int row = (2 * ppy + dy) * ST_RW + 2 * ppx + dx;
-                const float4 u = *reinterpret_cast<const float4*>(smem + stage64(row, 2 * c8));
-                const float4 v = *reinterpret_cast<const float4*>(smem + stage64(row, 2 * c8 + 1));
+                if constexpr (FACE) {
+                    const int cy = 2 * py - 1 + dy, cx = 2 * px - 1 + dx;
+                    if ((unsigned)cy >= (unsigned)p.oh || (unsigned)cx >= (unsigned)p.ow) continue;
+                }
+                const float4 u = *reinterpret_cast<const float4*>(img + stem_img<CH>(row, 2 * c8));
+                const float4 v = *reinterpret_cast<const float4*>(img + stem_img<CH>(row, 2 * c8 + 1));
                 const float x[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
 #pragma unroll
                 for (int j = 0; j < 8; ++j) { m[j] = fmaxf(m[j], x[j]); anynan[j] |= x[j] != x[j]; }
             }
-        (void)nan;
 #pragma unroll
         for (int j = 0; j < 8; ++j) if (anynan[j]) m[j] = NAN;  // like torch's max-pool
         spx8_t hi, lo;
         sp_split8(m, hi, lo, ovm);
-        const long e = (((long)b * 55 + py) * 55 + px) * 64 + c8 * 8;
+        const long e = (((long)b * mh + py) * mw + px) * 64 + ch0 + c8 * 8;
         char* yp = p.Y + sp32_byte(e);
         *reinterpret_cast<spx8_t*>(yp) = hi;
         *reinterpret_cast<spx8_t*>(yp + 64) = lo;
     }
+}
+
+// From the planar fp16 hi / lo image (already padded): both planes of the patch are copied to LDS as they lie in memory (hi
+// plane, then lo plane; 22 KiB), and all seven weight tiles (56 KiB) arrive with the same burst, so the K loop has no barrier
+// and no wait in it; the second block of the CU computes while this one waits for its burst.  Rows of positions outside the
+// 112 x 112 map read whatever follows in memory (or zeros past the planes): each output row depends on its own A row only,
+// and the pool never reads them.
+__global__ void __launch_bounds__(256, 2) stem_pool_kernel(const StemParams p) {
+    constexpr int PLANE = ST_PLCH * 16;                       // 11 232 B per plane
+    constexpr int NCH = 2 * ST_PLCH;                          // 1 404 chunks
+    constexpr int WOFF = ((2 * PLANE + 1023) / 1024) * 1024;  // weights behind the patch
+    constexpr int IMG = 256 * 256;                            // f32 [256 positions][64 channels]
+    constexpr int LDS_BYTES = WOFF + ST_NK * ST_WT > IMG ? WOFF + ST_NK * ST_WT : IMG;
+    static_assert(LDS_BYTES == 79872, "22 528 B of patch + 7 x 8 192 B of weights: two blocks per CU in 160 KiB of LDS");
+    __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int blk = xcd_remap(blockIdx.x, gridDim.x);
+    const int b = blk / (ST_TY * ST_TX), t = blk % (ST_TY * ST_TX);
+    const int ty = t / ST_TX, tx = t % ST_TX;
+
+    const float wmul = split_wmul(p.W, ST_NK * ST_WT);
+    const auto prs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.P), (short)0, (int)p.p_bytes, 0x00020000);
+    const auto wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.W), (short)0, ST_NK * ST_WT, 0x00020000);
+    // patch: chunk c of the LDS image = chunk (c % 702) of plane c / 702; one DMA instruction copies 64 consecutive chunks
+    const unsigned origin = (unsigned)((((long)b * 230 + 4 * ST_TH * ty) * 230 + 4 * ST_TW * tx) * 8);
+#pragma unroll
+    for (int j = 0; j < (NCH + 255) / 256; ++j) {
+        const int piece = wave + 4 * j;
+        const int c = piece * 64 + lane;
+        const int plane = c >= ST_PLCH, ci = c - plane * ST_PLCH;
+        const int prow = ci / ST_PCH, pc = ci - prow * ST_PCH;
+        const unsigned off = c < NCH ? origin + (unsigned)(prow * (230 * 8) + pc * 16) + plane * p.plane_bytes : OOB;
+        if (piece * 64 < NCH) dma16(prs, smem + piece * 1024, off);
+    }
+    // weights: tap row ky = rows [64][32 K] of p.W at column block ky, 8 DMA instructions of 8 rows each, swizzled like every tile
+    {
+        const int lrow8 = lane >> 3, slot = lane & 7;
+#pragma unroll
+        for (int j = 0; j < ST_NK * 8 / 4; ++j) {
+            const int piece = wave + 4 * j;  // 0 .. 55
+            const int ky = piece >> 3, row = (piece & 7) * 8 + lrow8;
+            dma16(wrs, smem + WOFF + piece * 1024, (unsigned)(row * (ST_NK * ROWB) + ky * ROWB + ((slot ^ swz_key(row)) << 4)));
+        }
+    }
+
+    f32x4_t acc[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[a][c] = f32x4_t{0};
+    const int g = lane >> 4, l15 = lane & 15;
+    int abase[4];
+    stem_frag_offsets(wave, l15, g, abase);
+    __syncthreads();  // patch and weights have landed
+#pragma unroll
+    for (int ky = 0; ky < ST_NK; ++ky) stem_tap_row<true>(acc, smem, smem + PLANE, abase, ky, smem + WOFF + ky * ST_WT, l15, g);
+    pin(acc);
+    __syncthreads();  // every wave is done with the patch: the image (64 KiB of the 78 KiB) overwrites it
+    stem_park<64>(smem, acc, 0, p.scale, wmul, [&](int) { return p.bias; }, wave, l15, g);
+    __syncthreads();
+    sp_flags_t ovm = 0;  // range contract of the sp32 output (split_dev.h sp_commit)
+    stem_pool_store<64, false>(smem, p, b, ty, tx, 0, tid, ovm);
     sp_commit(p.ovf, ovm);
 }
 
-// The stem of the x3 mode when the input is the u8 frames (avcer_static_forward): same tiling, but
+// The stem of the x3 mode when the input is the u8 frames (avcer_static_forward):
 //  * the block builds its patch itself (BGR flip, PIL NEAREST resize when the frame is not 224 x 224, zeros outside the image)
 //    as RAW PIXEL VALUES: integers 0..255 are exact in fp16, so the activation has no lo half -- two MFMAs per product, one
 //    patch plane, no preprocessing launch and no 846 KB-per-frame image in HBM.  The mean subtraction of data/utils.py:36-38
@@ -240,22 +290,19 @@ __global__ void __launch_bounds__(256, 2) stem_pool_kernel(const StemParams p) {
 //    chain -- patch, MFMAs, image, pool, store -- so what hides one block's latencies is the other blocks of its CU.
 //
 // FACE = true (round 6): the stem of the RetinaFace body (torchvision ResNet-50: conv 7x7/2 pad 3, BN, ReLU, max-pool 3x3/2 pad 1;
-// retina_face.py:46-76, retina_face_predictor.py:59-66) on frames of ANY size.  Same tiling -- a block = 8 x 7 pooled outputs, the
-// 17 x 15 stem positions under them, a 39 x 36-pixel patch -- with the window origins of symmetric padding (patch origin
-// (4 py0 - 5, 4 px0 - 5); stem row -1 / column -1 and those past the map are the pool's padding and are skipped).  The net's
+// retina_face.py:46-76, retina_face_predictor.py:59-66) on frames of ANY size, with the window origins of symmetric padding (patch
+// origin (4 py0 - 5, 4 px0 - 5); stem row -1 / column -1 and those past the map are the pool's padding and are skipped).  The net's
 // input is pixel - (104, 117, 123): INTEGER means, so the mean-subtracted value itself is exact in fp16 -- no lo half, two
 // MFMAs per product, zero padding is exactly zero and no border classes are needed (the BN shift is the plain one).
 // Replaces face_pre_kernel + the f32-input stem contraction + the padded 3x3 / 2 max-pool (maxpool_kernel): 0.9 + 7.9 + 3.2 ms per 750 frames of
 // 640 x 360 (profiles/r06_face_trace_before_stem.txt), the stem map [n,180,320,64] written and read once each for nothing.
 template <bool FACE>
 __global__ void __launch_bounds__(256, 3) stem_pool_u8_kernel(const StemParams p) {
-    constexpr int NK = 7, WRING = 3;
-    constexpr int PROWS = 2 * (ST_RH - 1) + NK, PCH = (2 * (ST_RW - 1) + 8) / 2;  // 39 patch rows of 18 16-byte chunks (36 pixels)
-    constexpr int NCH = PROWS * PCH;                                              // 702 chunks, 11 232 B
-    constexpr int WOFF = ((NCH * 16 + 1023) / 1024) * 1024;                       // weight ring behind the patch
-    constexpr int WT = 64 * ROWB;                                                 // one tap row's weight tile, 8 KiB
-    constexpr int IMG = 256 * 128;                                                // f32 [256 positions][32 channels]
+    constexpr int NK = ST_NK, WRING = 3, NCH = ST_PLCH, PCH = ST_PCH, WT = ST_WT;  // one patch plane
+    constexpr int WOFF = ((NCH * 16 + 1023) / 1024) * 1024;                        // weight ring behind the patch
+    constexpr int IMG = 256 * 128;                                                 // f32 [256 positions][32 channels]
     constexpr int LDS_BYTES = WOFF + WRING * WT > IMG ? WOFF + WRING * WT : IMG;
+    static_assert(LDS_BYTES == 35840, "11 264 B of patch + 3 x 8 192 B of weight ring: three blocks per CU in 160 KiB of LDS");
     __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -332,38 +379,21 @@ __global__ void __launch_bounds__(256, 3) stem_pool_u8_kernel(const StemParams p
             if (ci < NCH) *reinterpret_cast<uint4*>(smem + ci * 16) = make_uint4(wds[0], wds[1], wds[2], wds[3]);
         }
     }
-    f32x4_t acc[4][4];  // [channel tile][position tile]: wave = 64 positions x 64 channels
+    f32x4_t acc[4][4];
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
         for (int c = 0; c < 4; ++c) acc[a][c] = f32x4_t{0};
     const int g = lane >> 4, l15 = lane & 15;
-    int abase[4];  // byte offset of this lane's fragment in tap row 0 of the patch
-#pragma unroll
-    for (int fm = 0; fm < 4; ++fm) {
-        const int row = wave * 64 + fm * 16 + l15;
-        const int ry = row / ST_RW, rx = row - ry * ST_RW;
-        abase[fm] = row < ST_RH * ST_RW ? ((2 * ry) * PCH + rx + g) * 16 : 0;
-    }
+    int abase[4];
+    stem_frag_offsets(wave, l15, g, abase);
     __syncthreads();  // the patch is written, tap rows 0 and 1 have landed (this one drains everything)
 #pragma unroll
     for (int ky = 0; ky < NK; ++ky) {
         // slot (ky + 2) % 3 held tap row ky - 1: every wave left it at the barrier that ended the previous step
         if (ky + 2 < NK) AVCER_STEM_W(ky + 2);
         asm volatile("" ::: "memory");
-        const char* sb = smem + WOFF + (ky % WRING) * WT;
-        spx8_t ah[4];
-#pragma unroll
-        for (int fm = 0; fm < 4; ++fm) ah[fm] = *reinterpret_cast<const spx8_t*>(smem + abase[fm] + ky * (PCH * 16));
-#pragma unroll
-        for (int fn = 0; fn < 4; ++fn) {
-            const spx8_t wh = ldfrag(sb, fn * 16 + l15, g), wl = ldfrag(sb, fn * 16 + l15, 4 + g);
-#pragma unroll
-            for (int fm = 0; fm < 4; ++fm) {  // a = ah exactly: a.w = ah.wl + ah.wh (mfma3's order without its al term)
-                acc[fn][fm] = mfma_sp(wl, ah[fm], acc[fn][fm]);
-                acc[fn][fm] = mfma_sp(wh, ah[fm], acc[fn][fm]);
-            }
-        }
+        stem_tap_row<false>(acc, smem, nullptr, abase, ky, smem + WOFF + (ky % WRING) * WT, l15, g);  // a = ah exactly: no al term
         pin(acc);
         // tap row ky + 1 (requested a step ago) must be in; the two pieces just requested may stay in flight
         if (ky + 2 < NK) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
@@ -374,66 +404,25 @@ __global__ void __launch_bounds__(256, 3) stem_pool_u8_kernel(const StemParams p
     }
 #undef AVCER_STEM_W
     // BN + ReLU -> f32 [256 positions][32 channels] image (over the patch and the ring: every wave is past the last barrier),
-    // then the 3x3/2 max-pool (no padding: video.py:103) of those 32 channels; twice
+    // then the max-pool of those 32 channels; twice
     sp_flags_t ovm = 0;  // range contract of the sp32 output (split_dev.h sp_commit)
+    const auto bias_at = [&](int row) {
+        if constexpr (FACE) {
+            return p.bias;
+        } else {
+            // border class of stem position (cy, cx): taps above / left of the image at 0, below / right of it at 110
+            // (111 is computed but never pooled)
+            const int ry = row / ST_RW, rx = row - ry * ST_RW;
+            const int cy = 2 * ST_TH * ty + ry, cx = 2 * ST_TW * tx + rx;
+            const int cls = 3 * (cy == 0 ? 0 : (cy >= 110 ? 2 : 1)) + (cx == 0 ? 0 : (cx >= 110 ? 2 : 1));
+            return p.bias9 + cls * 64;
+        }
+    };
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
-#pragma unroll
-        for (int fh = 0; fh < 2; ++fh) {
-            const int fn = 2 * half + fh;
-            const int ch = 32 * half + 8 * g + 4 * fh;  // weight rows are stored permuted (split_weight_rows_kernel)
-            float4 sc = *reinterpret_cast<const float4*>(p.scale + ch);
-            sc = make_float4(sc.x * wmul, sc.y * wmul, sc.z * wmul, sc.w * wmul);  // undoes the power of two of the weight split
-#pragma unroll
-            for (int fm = 0; fm < 4; ++fm) {
-                const int row = wave * 64 + fm * 16 + l15;
-                // border class of stem position (cy, cx): taps above / left of the image at 0, below / right of it at 110
-                // (111 is computed but never pooled)
-                const int ry = row / ST_RW, rx = row - ry * ST_RW;
-                const int cy = 2 * ST_TH * ty + ry, cx = 2 * ST_TW * tx + rx;
-                const int cls = 3 * (cy == 0 ? 0 : (cy >= 110 ? 2 : 1)) + (cx == 0 ? 0 : (cx >= 110 ? 2 : 1));
-                const float4 bi = *reinterpret_cast<const float4*>(FACE ? p.bias + ch : p.bias9 + cls * 64 + ch);
-                const int chunk = 2 * g + fh;  // 16-byte chunk of the 32-channel row
-                *reinterpret_cast<float4*>(smem + row * 128 + ((chunk ^ (row & 7)) << 4)) =
-                    make_float4(relu_nan(acc[fn][fm][0] * sc.x + bi.x), relu_nan(acc[fn][fm][1] * sc.y + bi.y),
-                                relu_nan(acc[fn][fm][2] * sc.z + bi.z), relu_nan(acc[fn][fm][3] * sc.w + bi.w));
-            }
-        }
+        stem_park<32>(smem, acc, 2 * half, p.scale, wmul, bias_at, wave, l15, g);
         __syncthreads();
-        {
-            const int pp = tid >> 2, c8 = tid & 3;  // pooled position of the tile, group of 8 channels of this half
-            const int ppy = pp / ST_TW, ppx = pp - ppy * ST_TW;
-            const int py = ST_TH * ty + ppy, px = ST_TW * tx + ppx;
-            if (pp < ST_TH * ST_TW && py < (FACE ? p.mh : 55) && px < (FACE ? p.mw : 55)) {
-                float m[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) m[j] = 0.f;  // post-ReLU values are >= 0
-                bool anynan[8] = {false, false, false, false, false, false, false, false};
-#pragma unroll
-                for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                    for (int dx = 0; dx < 3; ++dx) {
-                        const int row = (2 * ppy + dy) * ST_RW + 2 * ppx + dx;
-                        if constexpr (FACE) {  // region row r <-> stem row 2 py0 - 1 + r: the pool's padding and the map's end are skipped
-                            const int cy = 2 * py - 1 + dy, cx = 2 * px - 1 + dx;
-                            if ((unsigned)cy >= (unsigned)p.oh || (unsigned)cx >= (unsigned)p.ow) continue;
-                        }
-                        const float4 u = *reinterpret_cast<const float4*>(smem + row * 128 + (((2 * c8) ^ (row & 7)) << 4));
-                        const float4 v = *reinterpret_cast<const float4*>(smem + row * 128 + (((2 * c8 + 1) ^ (row & 7)) << 4));
-                        const float x[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) { m[j] = fmaxf(m[j], x[j]); anynan[j] |= x[j] != x[j]; }
-                    }
-#pragma unroll
-                for (int j = 0; j < 8; ++j) if (anynan[j]) m[j] = NAN;  // like torch's max-pool
-                spx8_t hi, lo;
-                sp_split8(m, hi, lo, ovm);
-                const long e = (((long)b * (FACE ? p.mh : 55) + py) * (FACE ? p.mw : 55) + px) * 64 + 32 * half + c8 * 8;
-                char* yp = p.Y + sp32_byte(e);
-                *reinterpret_cast<spx8_t*>(yp) = hi;
-                *reinterpret_cast<spx8_t*>(yp + 64) = lo;
-            }
-        }
+        stem_pool_store<32, FACE>(smem, p, b, ty, tx, 32 * half, tid, ovm);
         if (half == 0) __syncthreads();  // the pool of the first half has read the image the second half overwrites
     }
     sp_commit(p.ovf, ovm);
@@ -1213,6 +1202,22 @@ __global__ void copy16_kernel(const uint4* __restrict__ src, uint4* __restrict__
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ launchers
+// The tail every launcher of this file shares: the profile's events around `launch()` (one kernel launch on `st`), the check
+// of that launch (CHECK_LAUNCH's message) and the context's GEMM statistics.  M, N, K: what the per-launch profile records.
+template <class Launch>
+static int launch_counted(avcer_ctx* ctx, hipStream_t st, int family, const char* name, double flops, double bytes, long M, long N,
+                          long K, Launch launch) {
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    TRY(prof_begin(ctx, st, &ev0, &ev1, family, flops, bytes, M, N, K));
+    launch();
+    if (ev1) (void)hipEventRecord(ev1, st);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_err(ctx, AVCER_EHIP, "%s launch: %s", name, hipGetErrorString(e));
+    ctx->gemm_launches += 1;
+    ctx->gemm_flops += flops;
+    return AVCER_OK;
+}
+
 int launch_stem_pool(avcer_ctx* ctx, const void* planes, size_t plane_bytes, const void* w_x3, const float* scale,
                      const float* bias, void* y, int n, hipStream_t st) {
     if (!planes || !w_x3 || !scale || !bias || !y || n <= 0) return set_err(ctx, AVCER_EINVAL, "stem_pool: bad arguments");
@@ -1221,14 +1226,9 @@ int launch_stem_pool(avcer_ctx* ctx, const void* planes, size_t plane_bytes, con
     memset(&p, 0, sizeof(p));
     p.P = (const char*)planes; p.plane_bytes = (unsigned)plane_bytes; p.p_bytes = (unsigned)(2 * plane_bytes);
     p.W = (const char*)w_x3; p.scale = scale; p.bias = bias; p.Y = (char*)y; p.n = n; p.ovf = ctx->ovf;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    TRY(prof_begin(ctx, st, &ev0, &ev1, FAM_STEM, 2.0 * n * 112.0 * 112.0 * 64 * 147, (double)n * (2.0 * 230 * 230 * 4 * 2 + 55.0 * 55 * 64 * 4)));
-    stem_pool_kernel<<<dim3(n * ST_TY * ST_TX), dim3(256), 0, st>>>(p);
-    if (ev1) (void)hipEventRecord(ev1, st);
-    CHECK_LAUNCH(ctx, "stem_pool");
-    ctx->gemm_launches += 1;
-    ctx->gemm_flops += 2.0 * n * 112.0 * 112.0 * 64 * 147;
-    return AVCER_OK;
+    return launch_counted(ctx, st, FAM_STEM, "stem_pool", 2.0 * n * 112.0 * 112.0 * 64 * 147,
+                          (double)n * (2.0 * 230 * 230 * 4 * 2 + 55.0 * 55 * 64 * 4), 0, 0, 0,
+                          [&] { stem_pool_kernel<<<dim3(n * ST_TY * ST_TX), dim3(256), 0, st>>>(p); });
 }
 
 // The same launch from the u8 frames themselves (stem_pool_u8_kernel): no preprocessing pass, two MFMAs per product.
@@ -1240,14 +1240,9 @@ int launch_stem_pool_u8(avcer_ctx* ctx, const uint8_t* frames, int in_h, int in_
     memset(&p, 0, sizeof(p));
     p.F = frames; p.in_h = in_h; p.in_w = in_w; p.bias9 = bias9;
     p.W = (const char*)w_x3; p.scale = scale; p.Y = (char*)y; p.n = n; p.ovf = ctx->ovf;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    TRY(prof_begin(ctx, st, &ev0, &ev1, FAM_STEM, 2.0 * n * 112.0 * 112.0 * 64 * 147, (double)n * ((double)in_h * in_w * 3 + 55.0 * 55 * 64 * 4)));
-    stem_pool_u8_kernel<false><<<dim3(n * ST_TY * ST_TX), dim3(256), 0, st>>>(p);
-    if (ev1) (void)hipEventRecord(ev1, st);
-    CHECK_LAUNCH(ctx, "stem_pool_u8");
-    ctx->gemm_launches += 1;
-    ctx->gemm_flops += 2.0 * n * 112.0 * 112.0 * 64 * 147;
-    return AVCER_OK;
+    return launch_counted(ctx, st, FAM_STEM, "stem_pool_u8", 2.0 * n * 112.0 * 112.0 * 64 * 147,
+                          (double)n * ((double)in_h * in_w * 3 + 55.0 * 55 * 64 * 4), 0, 0, 0,
+                          [&] { stem_pool_u8_kernel<false><<<dim3(n * ST_TY * ST_TX), dim3(256), 0, st>>>(p); });
 }
 
 // The detector's stem (stem_pool_u8_kernel<true>): frames u8 [n][h][w][3] (BGR unless rgb) -> sp32 [n][mh][mw][64], mh = ceil(ceil(h/2)/2).
@@ -1265,15 +1260,9 @@ int launch_stem_pool_face(avcer_ctx* ctx, const uint8_t* frames, int h, int w, i
     p.mean[0] = 104; p.mean[1] = 117; p.mean[2] = 123;  // retina_face_predictor.py:59-65, in the net's (B, G, R) order
     const long grid = (long)n * p.tiles_y * p.tiles_x;
     if (grid >= (1L << 31)) return set_err(ctx, AVCER_EINVAL, "stem_pool_face: %d frames of %d x %d are too many tiles for one launch", n, h, w);
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    const double flops = 2.0 * n * (double)p.oh * p.ow * 64 * 147;
-    TRY(prof_begin(ctx, st, &ev0, &ev1, FAM_STEM, flops, (double)n * ((double)h * w * 3 + (double)p.mh * p.mw * 64 * 4), (long)n * p.oh * p.ow, 64, 147));
-    stem_pool_u8_kernel<true><<<dim3((unsigned)grid), dim3(256), 0, st>>>(p);
-    if (ev1) (void)hipEventRecord(ev1, st);
-    CHECK_LAUNCH(ctx, "stem_pool_face");
-    ctx->gemm_launches += 1;
-    ctx->gemm_flops += flops;
-    return AVCER_OK;
+    return launch_counted(ctx, st, FAM_STEM, "stem_pool_face", 2.0 * n * (double)p.oh * p.ow * 64 * 147,
+                          (double)n * ((double)h * w * 3 + (double)p.mh * p.mw * 64 * 4), (long)n * p.oh * p.ow, 64, 147,
+                          [&] { stem_pool_u8_kernel<true><<<dim3((unsigned)grid), dim3(256), 0, st>>>(p); });
 }
 
 int launch_bneck(avcer_ctx* ctx, int planes, int nb, int h, int w, const void* t1, const void* x, int ds_cin, int out_step,
@@ -1308,44 +1297,37 @@ int launch_bneck(avcer_ctx* ctx, int planes, int nb, int h, int w, const void* t
     const bool t11 = planes == 64 && h == 55 && w == 55 && out_step == 1 && t1n && w2_frags;
     p.nblocks = t11 ? nb * 25 : (int)((M + BM - 1) / BM);
     const int grid = p.nblocks;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    {
-        // per position: T1 in (P), residual or downsample operand in (4P | ds_cin), OUT (4P) and T1' (P) out, 4 bytes per element
-        const double bytes = 4.0 * ((double)M_in * planes + (double)M * (ds_cin ? ds_cin : 4 * planes) + (double)M * 4 * planes +
-                                    (t1n ? (double)M * planes : 0.0));
-        TRY(prof_begin(ctx, st, &ev0, &ev1, FAM_CHAIN, 2.0 * (double)M * planes * (planes * (9.0 + 4.0 + (t1n ? 4.0 : 0.0)) + 4.0 * ds_cin), bytes, M,
-                       4 * planes, planes));
-    }
+    // per position: T1 in (P), residual or downsample operand in (4P | ds_cin), OUT (4P) and T1' (P) out, 4 bytes per element
+    const double bytes = 4.0 * ((double)M_in * planes + (double)M * (ds_cin ? ds_cin : 4 * planes) + (double)M * 4 * planes +
+                                (t1n ? (double)M * planes : 0.0));
+    const double flops = 2.0 * (double)M * planes * (planes * (9.0 + 4.0 + (t1n ? 4.0 : 0.0)) + 4.0 * ds_cin);
     // Resident halo patch for the conv2 phase: planes 128 only (28x28: -5..7 % per launch).  At planes 64 (55x55) the patch
     // costs the third resident block (76 KiB of LDS) and measured +2..4 %, so that form keeps the per-tap gather.
     // Worst case of the patch: the image rows 128 consecutive positions can touch (+ 2 when they cross into the next
     // image) + 2 halo rows, W + 2 slots each, must fit the kernel's LDS image.
     const int rows_worst = (w - 1 + BM + w - 1) / w + 2 + 2;
     const bool patch = planes == 128 && (long)h * w >= BM && rows_worst * (w + 2) <= 304;
-    if (out_step == 2) {
-        if (planes == 64) bneck_kernel<64, BM, false, 0, false, 2><<<dim3(grid), dim3(256), 0, st>>>(p);
-        else bneck_kernel<128, BM, false, 0, false, 2><<<dim3(grid), dim3(256), 0, st>>>(p);
-    } else if (ds_cin) {
-        if (t11) bneck_kernel<64, BM, true, 2, false, 1, true><<<dim3(grid), dim3(256), 0, st>>>(p);
-        else bneck_kernel<64, BM, true, 2, false><<<dim3(grid), dim3(256), 0, st>>>(p);
-    } else if (planes == 64) {
-        if (t11) bneck_kernel<64, BM, true, 0, false, 1, true><<<dim3(grid), dim3(256), 0, st>>>(p);
-        else if (t1n) bneck_kernel<64, BM, true, 0, false><<<dim3(grid), dim3(256), 0, st>>>(p);
-        else bneck_kernel<64, BM, false, 0, false><<<dim3(grid), dim3(256), 0, st>>>(p);
-    } else {
-        if (t1n) {
-            if (patch) bneck_kernel<128, BM, true, 0, true><<<dim3(grid), dim3(256), 0, st>>>(p);
-            else bneck_kernel<128, BM, true, 0, false><<<dim3(grid), dim3(256), 0, st>>>(p);
+    return launch_counted(ctx, st, FAM_CHAIN, "bneck", flops, bytes, M, 4 * planes, planes, [&] {
+        if (out_step == 2) {
+            if (planes == 64) bneck_kernel<64, BM, false, 0, false, 2><<<dim3(grid), dim3(256), 0, st>>>(p);
+            else bneck_kernel<128, BM, false, 0, false, 2><<<dim3(grid), dim3(256), 0, st>>>(p);
+        } else if (ds_cin) {
+            if (t11) bneck_kernel<64, BM, true, 2, false, 1, true><<<dim3(grid), dim3(256), 0, st>>>(p);
+            else bneck_kernel<64, BM, true, 2, false><<<dim3(grid), dim3(256), 0, st>>>(p);
+        } else if (planes == 64) {
+            if (t11) bneck_kernel<64, BM, true, 0, false, 1, true><<<dim3(grid), dim3(256), 0, st>>>(p);
+            else if (t1n) bneck_kernel<64, BM, true, 0, false><<<dim3(grid), dim3(256), 0, st>>>(p);
+            else bneck_kernel<64, BM, false, 0, false><<<dim3(grid), dim3(256), 0, st>>>(p);
         } else {
-            if (patch) bneck_kernel<128, BM, false, 0, true><<<dim3(grid), dim3(256), 0, st>>>(p);
-            else bneck_kernel<128, BM, false, 0, false><<<dim3(grid), dim3(256), 0, st>>>(p);
+            if (t1n) {
+                if (patch) bneck_kernel<128, BM, true, 0, true><<<dim3(grid), dim3(256), 0, st>>>(p);
+                else bneck_kernel<128, BM, true, 0, false><<<dim3(grid), dim3(256), 0, st>>>(p);
+            } else {
+                if (patch) bneck_kernel<128, BM, false, 0, true><<<dim3(grid), dim3(256), 0, st>>>(p);
+                else bneck_kernel<128, BM, false, 0, false><<<dim3(grid), dim3(256), 0, st>>>(p);
+            }
         }
-    }
-    if (ev1) (void)hipEventRecord(ev1, st);
-    CHECK_LAUNCH(ctx, "bneck");
-    ctx->gemm_launches += 1;
-    ctx->gemm_flops += 2.0 * (double)M * planes * (planes * (9.0 + 4.0 + (t1n ? 4.0 : 0.0)) + 4.0 * ds_cin);
-    return AVCER_OK;
+    });
 }
 
 int launch_bneck_tail(avcer_ctx* ctx, int planes, long M, const void* t2, const void* x, void* out, void* t1n, const void* w3,
@@ -1360,16 +1342,10 @@ int launch_bneck_tail(avcer_ctx* ctx, int planes, long M, const void* t2, const 
     p.T1 = (const char*)t2; p.X = (const char*)x; p.OUT = (char*)out; p.T1N = (char*)t1n;
     p.W3 = (const char*)w3; p.W1N = (const char*)w1n; p.b3 = b3; p.b1n = b1n;
     p.M = (int)M; p.ovf = ctx->ovf;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // per position: T2 in (P), residual in (4P), OUT (4P) and T1' (P) out
-    TRY(prof_begin(ctx, st, &ev0, &ev1, FAM_TAIL, 2.0 * (double)M * planes * planes * 8.0, 4.0 * (double)M * planes * 10.0, M, 4 * planes, planes));
     p.t1_bytes = (unsigned)(M * 4096L);
-    bneck_tail2_kernel<256><<<dim3((int)((M + 127) / 128)), dim3(512), 0, st>>>(p);
-    if (ev1) (void)hipEventRecord(ev1, st);
-    CHECK_LAUNCH(ctx, "bneck_tail");
-    ctx->gemm_launches += 1;
-    ctx->gemm_flops += 2.0 * (double)M * planes * planes * 8.0;
-    return AVCER_OK;
+    // per position: T2 in (P), residual in (4P), OUT (4P) and T1' (P) out
+    return launch_counted(ctx, st, FAM_TAIL, "bneck_tail", 2.0 * (double)M * planes * planes * 8.0, 4.0 * (double)M * planes * 10.0, M,
+                          4 * planes, planes, [&] { bneck_tail2_kernel<256><<<dim3((int)((M + 127) / 128)), dim3(512), 0, st>>>(p); });
 }
 
 // Measured ceilings of this GPU: dense 16-bit MFMA issue rate (the f16 form; TFLOP/s) and streaming-copy bandwidth (TB/s, read + write bytes).
