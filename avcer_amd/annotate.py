@@ -371,7 +371,8 @@ def layout(records, pred, prob, height: int, width: int, font=None, panel: bool 
 
 
 def write_result_video(engine, frames, records, pred, prob, path, rate, scale=1, pcm=None, audio_rate=44100, quality=90, subsampling=2,
-                       entropy="device", frames_per_pass=64, bgr=True, font=None, panel=False, tracks=None):
+                       entropy="device", frames_per_pass=64, bgr=True, font=None, panel=False, tracks=None, opendml=False,
+                       segment_bytes=1 << 30):
     """The result video of `frames` (uint8 [T, H, W, 3], on the device or moved there; BGR unless bgr=False) as the Motion-JPEG AVI
     file `path` at `rate` / `scale` frames per second, with `pcm` (int16 [L] / [L, C] at `audio_rate`) as its sound: `layout(records,
     pred, prob, H, W, font, panel)` drawn on every frame.  `frames` may also be a frame SOURCE -- a callable returning an iterator, or
@@ -382,7 +383,8 @@ def write_result_video(engine, frames, records, pred, prob, path, rate, scale=1,
     `save(quality=quality, subsampling=subsampling)` of the drawn frames, byte for byte, under both `entropy` values) and appended
     to the file (avi.AviWriter; the header is patched at the end).  The device holds one pass of copies and coefficients at a time;
     only file bytes cross to the host, and the host keeps the index alone.  What AviWriter refuses (a file past 4 GiB: OSError)
-    propagates, and no partial file is left, whatever the failure.
+    propagates, and no partial file is left, whatever the failure.  `opendml=True`: the OpenDML layout in segments of
+    `segment_bytes` (avi.AviWriter), which may pass 4 GiB; False (the default): the plain file, byte for byte as ever.
     `tracks`: None -- `pred` / `prob` are arrays and label track 00 (or dicts, taken as they are: `layout`) --, "all" or a list of
     track directories (face_tiles.check_tracks): `pred` and `prob` are then dicts keyed by track, and the tracks named ("all": every
     key, ascending) are labelled, each from its own arrays; the panel shows the first.  A named track the dicts do not hold raises
@@ -424,7 +426,8 @@ def write_result_video(engine, frames, records, pred, prob, path, rate, scale=1,
                 # a source's length is not known in front: its items are held to the last frame they name
                 check_items(items, max(int(part.shape[0]), 1) if whole else int(items["frame"].max()) + 1 if len(items) else 1, table, len(flat))
                 state = (items, torch.from_numpy(flat).to(engine.device), table)
-                writer = AviWriter(path, width, height, rate, scale, audio_rate, pcm=pcm)
+                writer = AviWriter(path, width, height, rate, scale, audio_rate, pcm=pcm,
+                                   **(dict(opendml=True, segment_bytes=segment_bytes) if opendml else {}))
             elif (int(part.shape[1]), int(part.shape[2])) != (height, width):
                 raise ValueError(f"a pass of {int(part.shape[2])} x {int(part.shape[1])} frames behind {width} x {height}")
             items, flat_d, table = state

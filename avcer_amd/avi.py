@@ -1,5 +1,5 @@
-"""Motion-JPEG / PCM AVI files read and written on the host: the container in front of `jpeg.decode_frames` (no device, no
-dependency beyond numpy).
+"""Motion-JPEG or uncompressed-BGR / PCM AVI files read and written on the host: the container in front of `jpeg.decode_frames`
+and `dib.unpack_frames` (no device but in AviFile.decode_frames, which picks between the two; no dependency beyond numpy).
 
 What is read is the AVI that `ffmpeg -i clip.mp4 -c:v mjpeg -q:v 2 -c:a pcm_s16le -ar 44100 -ac 2 clip.avi` writes -- exactly as
 `audio_pipeline.convert_mp4_to_mp3` reads "the WAV that ffmpeg writes": a RIFF `AVI ` form with a `hdrl` list (`avih`, one `strl`
@@ -7,13 +7,22 @@ list per stream holding `strh` and `strf`) and a `movi` list whose `NNdc` / `NNd
 interleaved with the `NNwb` chunks of 16-bit PCM.  `open_avi` maps the file (mmap) and hands the frames out as memoryviews of the
 mapping: no frame byte is copied on the way to the native header pass.
 
-Everything else is refused with a ValueError that names the file and the reason, before any frame is touched: another codec,
-another audio format, a second video stream, OpenDML (files past 1 GiB: `AVIX` segments, `indx` / `ix##` indexes), a chunk that
-runs past the end of the file.  H.264 / MP4 is out of reach without a codec library and is not pretended.
+The same container with an uncompressed video stream -- `-c:v rawvideo -pix_fmt bgr24`: biCompression 0 (BI_RGB), 24 or 32 bits,
+handler `DIB `, `RGB `, `RAW ` or none, rows padded to 4 bytes, bottom-up when biHeight > 0 -- is read too (AviFile.codec "DIB"; every
+chunk is one frame of stride * height bytes, dib.py).  `open_avi(path, opendml=True)` reads OpenDML files: any number of RIFF `AVIX`
+forms behind the first, every movi list walked in file order, the indexes (`indx`, `ix##`, LIST odml) skipped -- the walk is the
+source of truth, as it is for idx1 -- and every offset a Python int over the mapping, so files past 4 GiB.
+
+Everything else is refused with a ValueError that names the file and the reason, before any frame is touched: another codec
+(palettised, 16-bit, BI_BITFIELDS, RLE and YUV streams by name), another audio format, a second video stream, OpenDML unless
+`opendml=True` (`AVIX` segments, `indx` / `ix##` indexes), a trailing form that is no `AVIX`, an `AVIX` form cut short or without a
+movi list, a chunk that runs past the end of the file, an uncompressed frame of the wrong length.  H.264 / MP4 is out of reach
+without a codec library and is not pretended.
 
 `write_avi` is the inverse (tests, tools/avi_bench.py, users who want the format); `AviWriter` is the same file written as the frames
 come (the result video of a recording that is never whole in memory): chunks appended, the header sizes and `idx1` patched at
-close.  Plain AVI only, below 4 GiB: OpenDML (`AVIX`) is neither read nor written.
+close.  Plain AVI below 4 GiB by default; `opendml=True` writes the OpenDML 1.02 layout instead (AviWriter's docstring), and
+`write_avi_raw` / `build_avi_raw` write the uncompressed kind.
 """
 from __future__ import annotations
 
@@ -33,8 +42,10 @@ class AviFile:
     """An open Motion-JPEG AVI file (see `open_avi`).  `frames[i]` is a memoryview of the mapping and stays valid until `close()`
     (or the end of the `with` block); `pcm` is an array of its own."""
 
-    def __init__(self, path, mapping, view, width, height, rate, scale, frames, audio_rate, audio_channels, pcm):
+    def __init__(self, path, mapping, view, width, height, rate, scale, frames, audio_rate, audio_channels, pcm, codec="MJPG", bits=24,
+                 bottom_up=False):
         self.path = path
+        self.codec, self.bits, self.bottom_up = codec, int(bits), bool(bottom_up)
         self._map, self._view = mapping, view
         self.width, self.height = int(width), int(height)
         self.rate, self.scale = int(rate), int(scale)
@@ -43,6 +54,18 @@ class AviFile:
         self.n_frames = len(frames)
         self.audio_rate, self.audio_channels = audio_rate, audio_channels
         self.pcm = pcm
+
+    def decode_frames(self, engine, lo: int = 0, hi: Optional[int] = None, bgr: bool = True, frames_per_pass: int = 64):
+        """Frames [lo, hi) on the device, uint8 [hi - lo, height, width, 3] in BGR order (RGB with bgr=False): the ONE place that
+        picks the decoder by `codec` -- jpeg.decode_frames for "MJPG", dib.unpack_frames for "DIB" -- for run_inference_file (in
+        memory, streamed, and the result video's second sweep) and dataset.video_job_from_avi."""
+        from . import dib, jpeg
+
+        whole = lo == 0 and (hi is None or hi >= self.n_frames)
+        part = self.frames if whole else self.frames[lo:hi]
+        if self.codec == "MJPG":
+            return jpeg.decode_frames(engine, part, self.height, self.width, bgr=bgr, frames_per_pass=frames_per_pass)[0]
+        return dib.unpack_frames(engine, part, self.height, self.width, self.bits, self.bottom_up, bgr=bgr, frames_per_pass=frames_per_pass)
 
     def close(self):
         for f in self.frames:
@@ -81,7 +104,15 @@ def _walk(view, at, end, refuse):
         at += 8 + size + (size & 1)
 
 
-def _parse(view, path):
+# what an uncompressed stream's handler may be, and the YUV fourccs that are refused by name (their conversion to BGR is
+# swscale's own arithmetic, which is neither stated nor checked here)
+RAW_HANDLERS = (b"DIB ", b"RGB ", b"RAW ", b"\0\0\0\0")
+YUV_FOURCCS = (b"YUY2", b"YUYV", b"UYVY", b"YVYU", b"I420", b"IYUV", b"YV12", b"NV12", b"NV21", b"Y800", b"Y422", b"YV16", b"Y42B", b"I444",
+               b"Y41P", b"YVU9", b"HDYC", b"V210", b"AYUV", b"P010")
+BI_NAMES = {1: "BI_RLE8", 2: "BI_RLE4", 3: "BI_BITFIELDS"}
+
+
+def _parse(view, path, opendml=False):
     def refuse(reason):
         return ValueError(f"{path}: {reason}")
 
@@ -92,7 +123,7 @@ def _parse(view, path):
     if 8 + riff > n:
         raise refuse(f"the RIFF form ({riff} bytes) runs past the end of the file ({n} bytes)")
     end = 8 + riff
-    if end + (end & 1) + 12 <= n and bytes(view[end + (end & 1):end + (end & 1) + 4]) == b"RIFF":
+    if not opendml and end + (end & 1) + 12 <= n and bytes(view[end + (end & 1):end + (end & 1) + 4]) == b"RIFF":
         raise refuse("OpenDML file (a second RIFF segment, AVIX); only plain AVI up to 1 GiB is read")
     streams = []  # per strl, in file order: dict(type, handler, scale, rate, strf fields)
     movi = None
@@ -110,7 +141,7 @@ def _parse(view, path):
                         s["scale"], s["rate"] = struct.unpack_from("<II", view, at3 + 20)
                     elif cc3 == b"strf":
                         s["strf"] = (at3, size3)
-                    elif cc3 == b"indx":
+                    elif cc3 == b"indx" and not opendml:
                         raise refuse("OpenDML file (an indx chunk); only plain AVI up to 1 GiB is read")
                     # vprp, strn, strd, JUNK, unknown: skipped
                 if "type" not in s or "strf" not in s:
@@ -131,9 +162,23 @@ def _parse(view, path):
         raise refuse("the video stream's strf is no BITMAPINFOHEADER")
     width, height = struct.unpack_from("<ii", view, at + 4)
     comp = bytes(view[at + 16:at + 20])
-    if comp.upper() != b"MJPG":
+    depth = struct.unpack_from("<H", view, at + 14)[0]
+    code = struct.unpack("<I", comp)[0]
+    codec, frame_bytes = "MJPG", None
+    if code == 0:  # BI_RGB: uncompressed
+        if depth not in (24, 32):
+            raise refuse(f"uncompressed video of {depth} bits a pixel ({'palettised' if depth <= 8 else 'a 16-bit format'}): only 24 and 32 bits "
+                         "(BGR) are read")
+        if v["handler"].upper() not in RAW_HANDLERS:
+            raise refuse(f"video handler {v['handler']!r} beside biCompression 0 (BI_RGB): DIB, RGB, RAW or none is read")
+        codec = "DIB"
+    elif code in BI_NAMES:
+        raise refuse(f"video biCompression {code} ({BI_NAMES[code]}): of the uncompressed formats only BI_RGB with 24 or 32 bits is read")
+    elif comp.upper() in YUV_FOURCCS:
+        raise refuse(f"video biCompression {comp!r}: a YUV format; of the uncompressed formats only BI_RGB with 24 or 32 bits (BGR) is read")
+    elif comp.upper() != b"MJPG":
         raise refuse(f"video biCompression {comp!r}: only MJPG (Motion-JPEG) is read")
-    if v["handler"].upper() != b"MJPG":
+    elif v["handler"].upper() != b"MJPG":
         raise refuse(f"video handler {v['handler']!r}: only MJPG (Motion-JPEG) is read")
     if v["scale"] <= 0 or v["rate"] <= 0 or width <= 0 or height == 0:
         raise refuse(f"video stream of {width} x {height} at {v['rate']} / {v['scale']} frames per second")
@@ -150,6 +195,28 @@ def _parse(view, path):
             raise refuse(f"audio stream of {a_ch} channels at {a_rate} Hz")
     if movi is None:
         raise refuse("no movi list")
+    if codec == "DIB":
+        frame_bytes = ((width * (depth // 8) + 3) & ~3) * abs(height)
+    movis = [movi]
+    if opendml:
+        # any number of RIFF AVIX forms behind the first: each holds a movi list, walked in file order like the first.  The indexes
+        # (indx, ix##, the odml list) are skipped: the walk is the source of truth, as it is for idx1
+        at = end + (end & 1)
+        while at + 12 <= n:
+            cc, kind = bytes(view[at:at + 4]), bytes(view[at + 8:at + 12])
+            if cc != b"RIFF" or kind != b"AVIX":
+                raise refuse(f"a trailing {cc!r} {kind!r} form at byte {at}: only RIFF AVIX segments follow the AVI form")
+            size = struct.unpack_from("<I", view, at + 4)[0]
+            if at + 8 + size > n:
+                raise refuse(f"the AVIX form at byte {at} ({size} bytes) runs past the end of the file ({n} bytes)")
+            found = None
+            for cc2, kind2, at2, size2 in _walk(view, at + 12, at + 8 + size, refuse):
+                if cc2 == b"LIST" and kind2 == b"movi" and found is None:
+                    found = (at2 + 4, at2 + size2)
+            if found is None:
+                raise refuse(f"the AVIX form at byte {at} has no movi list")
+            movis.append(found)
+            at += 8 + size + (size & 1)
     # the movi walk is the source of truth: frames and PCM in file order (`rec ` lists hold chunks of their own)
     frames, sound = [], []
 
@@ -160,6 +227,8 @@ def _parse(view, path):
                     walk_movi(at + 4, at + size, False)
                 continue  # LIST INFO, unknown lists
             if cc[:2] == b"ix":
+                if opendml:
+                    continue
                 raise refuse("OpenDML file (an ix## index chunk in movi); only plain AVI up to 1 GiB is read")
             if not cc[:2].isdigit():
                 continue  # JUNK, unknown
@@ -169,22 +238,30 @@ def _parse(view, path):
                     if not frames:
                         raise refuse("the first video chunk is empty (a dropped frame with no predecessor)")
                     frames.append(frames[-1])
+                elif frame_bytes is not None and size != frame_bytes:
+                    raise refuse(f"video frame {len(frames)}: a chunk of {size} bytes, an uncompressed frame of {width} x {abs(height)} at "
+                                 f"{depth} bits is {frame_bytes} bytes")
                 else:
                     frames.append((at, size))
             elif audio and stream == audio[0] and what == b"wb":
                 sound.append((at, size))
 
-    walk_movi(*movi)
+    for span in movis:
+        walk_movi(*span)
     return dict(width=width, height=abs(height), rate=v["rate"], scale=v["scale"], frames=frames, sound=sound, audio_rate=a_rate,
-                audio_channels=a_ch)
+                audio_channels=a_ch, codec=codec, bits=depth if codec == "DIB" else 24, bottom_up=codec == "DIB" and height > 0)
 
 
-def open_avi(path) -> AviFile:
-    """The Motion-JPEG AVI file `path` -> AviFile: width, height, rate, scale (the video stream's dwRate / dwScale), fps = rate /
+def open_avi(path, opendml: bool = False) -> AviFile:
+    """The Motion-JPEG or uncompressed-BGR AVI file `path` -> AviFile: codec ("MJPG": every frame is a JPEG file; "DIB": every frame
+    is an uncompressed bitmap of `bits` = 24 or 32 bits a pixel, `bottom_up` when biHeight > 0; dib.py), width, height, rate, scale (the video stream's dwRate / dwScale), fps = rate /
     scale, n_frames, frames (one zero-copy memoryview per video chunk, in file order; an empty chunk repeats its predecessor),
     audio_rate, audio_channels and pcm (int16 [L, C]: the audio chunks joined, cut to whole sample frames; None, with both fields
     None, when there is no audio stream).  Stream numbers follow the order of the strl lists.  ValueError naming the file and
-    the reason for anything outside that (the module's docstring), raised before a frame is looked at."""
+    the reason for anything outside that (the module's docstring), raised before a frame is looked at.
+    opendml=True reads OpenDML files as well -- any number of RIFF AVIX segments behind the first form, every movi list walked in
+    file order, the indx / ix## / odml indexes skipped, not trusted -- so files past 1 GiB (ffmpeg's switch) and past 4 GiB; False
+    (the default) refuses them as ever."""
     path = os.fspath(path)
     with open(path, "rb") as f:
         if os.fstat(f.fileno()).st_size == 0:
@@ -192,7 +269,7 @@ def open_avi(path) -> AviFile:
         mapping = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
     view = memoryview(mapping)
     try:
-        p = _parse(view, path)
+        p = _parse(view, path, bool(opendml))
         frames = [view[at:at + size] for at, size in p["frames"]]
         pcm = None
         if p["audio_rate"] is not None:
@@ -206,7 +283,8 @@ def open_avi(path) -> AviFile:
         view.release()
         mapping.close()
         raise
-    return AviFile(path, mapping, view, p["width"], p["height"], p["rate"], p["scale"], frames, p["audio_rate"], p["audio_channels"], pcm)
+    return AviFile(path, mapping, view, p["width"], p["height"], p["rate"], p["scale"], frames, p["audio_rate"], p["audio_channels"], pcm,
+                   p["codec"], p["bits"], p["bottom_up"])
 
 
 # ---------------------------------------------------------------------------------------------------- writing
@@ -241,8 +319,10 @@ def _list(kind: bytes, body: bytes, cc: bytes = b"LIST") -> bytes:
 
 
 def build_avi(jpeg_blobs: Sequence, rate: int, scale: int = 1, pcm: Optional[np.ndarray] = None, audio_rate: int = 44100,
-              index: bool = True, audio_first: bool = False, movi_extra: Sequence = (), strl_extra: bytes = b"") -> bytes:
-    """The bytes `write_avi` writes.  Two options beyond it, for tests of the reader: `audio_first` puts the audio stream's strl in
+              index: bool = True, audio_first: bool = False, movi_extra: Sequence = (), strl_extra: bytes = b"", opendml: bool = False,
+              segment_bytes: int = 1 << 30, index_segments: int = 256) -> bytes:
+    """The bytes `write_avi` writes (with `opendml`, `segment_bytes`, `index_segments`: the OpenDML file, AviWriter's docstring; the
+    reader's options below do not combine with it).  Two options beyond it, for tests of the reader: `audio_first` puts the audio stream's strl in
     front of the video's (audio is then stream 00, video 01); `movi_extra` = [(k, raw bytes)], raw chunks or lists placed in movi
     in front of frame k's chunk (k = the frame count: at the end); `strl_extra`: raw chunks behind the video stream's strf (vprp,
     JUNK, ...)."""
@@ -254,6 +334,11 @@ def build_avi(jpeg_blobs: Sequence, rate: int, scale: int = 1, pcm: Optional[np.
     if rate <= 0 or scale <= 0:
         raise ValueError("write_avi: rate and scale positive")
     width, height = jpeg_size(first)
+    if opendml:
+        if audio_first or movi_extra or strl_extra or not index:
+            raise ValueError("build_avi: audio_first, movi_extra, strl_extra and index=False are options of the plain file")
+        return _in_memory(blobs, width, height, rate, scale, pcm, audio_rate, opendml=True, segment_bytes=segment_bytes,
+                          index_segments=index_segments)
     n = len(blobs)
     if pcm is not None:
         pcm = _as_pcm(pcm)
@@ -298,23 +383,37 @@ def build_avi(jpeg_blobs: Sequence, rate: int, scale: int = 1, pcm: Optional[np.
     return _list(b"AVI ", body, b"RIFF")
 
 
+def _super_index(cc: bytes, entries, capacity: int) -> bytes:
+    """An OpenDML `indx` chunk, index of indexes, of fixed capacity: entries = [(file offset of an ix## chunk's header, its size with
+    the header, its duration in stream ticks)]."""
+    body = struct.pack("<HBBI4sIII", 4, 0, 0, len(entries), cc, 0, 0, 0) + b"".join(struct.pack("<QII", *e) for e in entries)
+    return _chunk(b"indx", body + b"\0" * (16 * (capacity - len(entries))))
+
+
 def _hdrl(n: int, biggest: int, width: int, height: int, rate: int, scale: int, sound, audio_rate: int, index: bool,
-          audio_first: bool = False, strl_extra: bytes = b"") -> bytes:
+          audio_first: bool = False, strl_extra: bytes = b"", video=None, odml=None) -> bytes:
     """The `hdrl` list of a file of `n` frames, the largest of `biggest` bytes; `sound` = (sample frames, channels) or None.  Its
-    length does not depend on `n`, `biggest` or the sample count: AviWriter writes it once with zeros and once more at close."""
-    strl_v = _list(b"strl", _chunk(b"strh", struct.pack("<4s4sIHHIIIIIIIIhhhh", b"vids", b"MJPG", 0, 0, 0, 0, scale, rate, 0, n, biggest,
+    length does not depend on `n`, `biggest` or the sample count: AviWriter writes it once with zeros and once more at close.
+    `video` = (handler, biCompression, bits, biHeight, biSizeImage) of another video format than Motion-JPEG.  `odml` = (frames of
+    the first segment, capacity, the video stream's super-index entries, the audio stream's): the OpenDML header -- an `indx`
+    chunk of `capacity` entries in each stream list, avih counts the first segment, LIST odml / dmlh the file."""
+    handler, comp, bits, bi_height, image = video if video is not None else (b"MJPG", b"MJPG", 24, height, width * height * 3)
+    strl_v = _list(b"strl", _chunk(b"strh", struct.pack("<4s4sIHHIIIIIIIIhhhh", b"vids", handler, 0, 0, 0, 0, scale, rate, 0, n, biggest,
                                                         0xFFFFFFFF, 0, 0, 0, width, height)) +
-                   _chunk(b"strf", struct.pack("<IiiHH4sIiiII", 40, width, height, 1, 24, b"MJPG", width * height * 3, 0, 0, 0, 0)) + strl_extra)
+                   _chunk(b"strf", struct.pack("<IiiHH4sIiiII", 40, width, bi_height, 1, bits, comp, image, 0, 0, 0, 0)) + strl_extra +
+                   (b"" if odml is None else _super_index(b"00dc", odml[2], odml[1])))
     lists = [strl_v]
     if sound is not None:
         length, ch = sound
         strl_a = _list(b"strl", _chunk(b"strh", struct.pack("<4s4sIHHIIIIIIIIhhhh", b"auds", b"\1\0\0\0", 0, 0, 0, 0, 1, audio_rate, 0, length,
                                                             0, 0xFFFFFFFF, 2 * ch, 0, 0, 0, 0)) +
-                       _chunk(b"strf", struct.pack("<HHIIHH", WAVE_FORMAT_PCM, ch, audio_rate, audio_rate * 2 * ch, 2 * ch, 16)))
+                       _chunk(b"strf", struct.pack("<HHIIHH", WAVE_FORMAT_PCM, ch, audio_rate, audio_rate * 2 * ch, 2 * ch, 16)) +
+                       (b"" if odml is None else _super_index(b"01wb", odml[3], odml[1])))
         lists = [strl_a, strl_v] if audio_first else [strl_v, strl_a]
-    avih = _chunk(b"avih", struct.pack("<14I", max(1, 1000000 * scale // rate), 0, 0, (AVIF_HASINDEX if index else 0) | AVIF_ISINTERLEAVED, n, 0,
-                                       len(lists), biggest, width, height, 0, 0, 0, 0))
-    return _list(b"hdrl", avih + b"".join(lists))
+    avih = _chunk(b"avih", struct.pack("<14I", max(1, 1000000 * scale // rate), 0, 0, (AVIF_HASINDEX if index else 0) | AVIF_ISINTERLEAVED,
+                                       n if odml is None else odml[0], 0, len(lists), biggest, width, height, 0, 0, 0, 0))
+    tail = b"" if odml is None else _list(b"odml", _chunk(b"dmlh", struct.pack("<I", n)))
+    return _list(b"hdrl", avih + b"".join(lists) + tail)
 
 
 # A plain AVI file is one RIFF form, and a RIFF size is 32 bits: the whole file stays below 4 GiB.  (ffmpeg changes to OpenDML
@@ -342,10 +441,36 @@ class AviWriter:
 
     A plain AVI file cannot pass 4 GiB (AVI_MAX_BYTES): when an append would take the finished file -- the sound still owed and the
     index included -- past it, OSError names the limit and the partial file is removed; so is the file of a writer that is closed
-    without one non-empty frame (ValueError), or left through an exception of its `with` block.  OpenDML is not written."""
+    without one non-empty frame (ValueError), or left through an exception of its `with` block.
+
+    `opendml=True` writes the layout of the OpenDML 1.02 extensions instead (what ffmpeg's muxer writes past 1 GiB; read back with
+    open_avi(opendml=True)), and the file may pass 4 GiB: a first RIFF `AVI ` form whose movi list ends with one `ix##` standard index
+    per stream, followed by an `idx1` over that form alone; then RIFF `AVIX` forms of one movi list each, ended the same way.  A
+    chunk that would take the open form -- closed right behind it, its indexes included -- past `segment_bytes` opens the next
+    form (a form holds at least one chunk, so only a chunk larger than that can make a form larger).  Each stream list carries an
+    `indx` super index of `index_segments` entries, written with zeros and patched at close: {u64 file offset of the ix## chunk, u32
+    its size with the header, u32 its duration in stream ticks}; a standard index entry is {u32 offset of the chunk's DATA from
+    qwBaseOffset -- the file offset of its form's `movi` fourcc --, u32 size, bit 31 set for an empty (repeated) frame}.  avih counts
+    the first form's frames, strh and LIST odml / dmlh the file's.  A file that would need more than `index_segments` forms raises
+    OSError naming the limit and the partial file is removed.  With opendml=False (the default) neither argument is looked at.
+
+    `codec="DIB"`: the chunks are uncompressed frames of `bits` (24 or 32) bits a pixel, bottom-up or top-down, instead of JPEG
+    files (dib.py; write_avi_raw).  `path` may be a writable, seekable binary file object instead of a path; it is then neither
+    closed nor removed."""
 
     def __init__(self, path, width: int, height: int, rate: int, scale: int = 1, audio_rate: int = 44100, channels: Optional[int] = None,
-                 pcm: Optional[np.ndarray] = None, index: bool = True):
+                 pcm: Optional[np.ndarray] = None, index: bool = True, opendml: bool = False, segment_bytes: int = 1 << 30,
+                 index_segments: int = 256, codec: str = "MJPG", bits: int = 24, bottom_up: bool = True):
+        self.opendml, self.segment_bytes, self.index_segments = bool(opendml), int(segment_bytes), int(index_segments)
+        if self.opendml and not (0 < self.segment_bytes < 1 << 32 and self.index_segments >= 1 and index):
+            raise ValueError("AviWriter: opendml takes segment_bytes in 1 .. 2^32 - 1, index_segments >= 1 and index=True")
+        if codec not in ("MJPG", "DIB") or (codec == "DIB" and int(bits) not in (24, 32)):
+            raise ValueError('AviWriter: codec "MJPG", or "DIB" with 24 or 32 bits')
+        self._video = None
+        if codec == "DIB":
+            size = ((int(width) * (int(bits) // 8) + 3) & ~3) * int(height)
+            self._video = (b"DIB ", b"\0\0\0\0", int(bits), int(height) if bottom_up else -int(height), size)
+        self._owned = not hasattr(path, "write")
         self.path = path
         self.width, self.height, self.rate, self.scale = int(width), int(height), int(rate), int(scale)
         if self.rate <= 0 or self.scale <= 0:
@@ -375,22 +500,74 @@ class AviWriter:
     def _sound(self):
         return None if self._pcm is None else (len(self._pcm), self._pcm.shape[1])
 
+    def _header(self, n: int, biggest: int) -> bytes:
+        odml = (self._first[2], self.index_segments, self._super[b"00dc"], self._super[b"01wb"]) if self.opendml else None
+        return _hdrl(n, biggest, self.width, self.height, self.rate, self.scale, self._sound(), self.audio_rate, self.index, video=self._video,
+                     odml=odml)
+
     def _open(self):
-        self._file = open(self.path, "wb")
-        hdrl = _hdrl(0, 0, self.width, self.height, self.rate, self.scale, self._sound(), self.audio_rate, self.index)
+        self._file = open(self.path, "wb") if self._owned else self.path
+        self._base = 0 if self._owned else self._file.tell()
+        # OpenDML: the chunks of the open form per stream, the super-index entries of the closed ones, the first form's sizes
+        self._seg, self._super, self._first = {b"00dc": [], b"01wb": []}, {b"00dc": [], b"01wb": []}, (0, 0, 0)
+        self._seg_start, self._seg_frames, self._seg_ticks = 0, 0, 0
+        hdrl = self._header(0, 0)
         self._file.write(b"RIFF\0\0\0\0AVI " + hdrl + b"LIST\0\0\0\0movi")
         self._movi = 12 + len(hdrl) + 8  # the file offset of the 'movi' fourcc
 
     def _fail(self, error):
         self._closed = True
         if self._file is not None:
-            self._file.close()
+            if self._owned:
+                self._file.close()
+                try:
+                    os.remove(self.path)
+                except OSError:
+                    pass
             self._file = None
-            try:
-                os.remove(self.path)
-            except OSError:
-                pass
         return error
+
+    def _streams(self):
+        return (b"00dc",) if self._pcm is None else (b"00dc", b"01wb")
+
+    def _form_bytes(self, cc: bytes, chunk: int) -> int:
+        """The open form's length, header included, were a chunk of `chunk` bytes of stream `cc` appended and the form closed."""
+        ix = sum(8 + 24 + 8 * (len(self._seg[c]) + (c == cc)) for c in self._streams())
+        idx1 = 8 + 16 * (len(self._entries) + 1) if self._seg_start == 0 else 0
+        return self._movi + self._at + chunk - self._seg_start + ix + idx1
+
+    def _close_form(self):
+        """The open form's ix## chunks (and the first form's idx1) behind its chunks, its two sizes, its super-index entries."""
+        f = self._file
+        for c in self._streams():
+            rows = self._seg[c]
+            body = struct.pack("<HBBI4sQI", 2, 0, 1, len(rows), c, self._base + self._movi, 0) + b"".join(struct.pack("<II", *r) for r in rows)
+            self._super[c].append((self._base + self._movi + self._at, 8 + len(body), self._seg_frames if c == b"00dc" else self._seg_ticks))
+            f.write(b"ix" + c[:2] + struct.pack("<I", len(body)) + body)
+            self._at += 8 + len(body)
+            self._seg[c] = []
+        end = self._movi + self._at
+        if self._seg_start == 0:
+            body = b"".join(self._entries)
+            f.write(b"idx1" + struct.pack("<I", len(body)) + body)
+            end += 8 + len(body)
+            self._first = (end - 8, self._at, self._seg_frames)  # written with the header, at close
+        else:
+            f.seek(self._base + self._seg_start + 4)
+            f.write(struct.pack("<I", end - self._seg_start - 8))
+            f.seek(self._base + self._movi - 4)
+            f.write(struct.pack("<I", self._at))
+            f.seek(self._base + end)
+        return end
+
+    def _next_form(self):
+        if len(self._super[b"00dc"]) + 1 >= self.index_segments:
+            raise self._fail(OSError(f"{self.path}: frame {self.n_frames} would open segment {self.index_segments + 1} of the file; its "
+                                     f"super indexes hold index_segments = {self.index_segments} (of segment_bytes = {self.segment_bytes} bytes each)"))
+        end = self._close_form()
+        self._file.write(b"RIFF\0\0\0\0AVIXLIST\0\0\0\0movi")
+        self._seg_start, self._movi, self._at = end, end + 20, 4
+        self._seg_frames = self._seg_ticks = 0
 
     def _span(self, k: int, last: bool):
         """The samples behind frame k: about its duration's worth; the last frame takes what is left."""
@@ -401,6 +578,21 @@ class AviWriter:
 
     def _put(self, cc: bytes, body, flags: int):
         size = len(body)
+        if self.opendml:
+            if (self._seg[b"00dc"] or self._seg[b"01wb"]) and self._form_bytes(cc, 8 + size + (size & 1)) > self.segment_bytes:
+                self._next_form()
+            self._seg[cc].append((self._at + 8, size | (0 if flags & AVIIF_KEYFRAME else 1 << 31)))
+            if cc == b"00dc":
+                self._seg_frames += 1
+            else:
+                self._seg_ticks += size // (2 * self._pcm.shape[1])
+            if self._seg_start:  # idx1 covers the first form alone
+                self._file.write(cc + struct.pack("<I", size))
+                self._file.write(body)
+                if size & 1:
+                    self._file.write(b"\0")
+                self._at += 8 + size + (size & 1)
+                return
         self._entries.append(cc + struct.pack("<III", flags, self._at, size))
         self._file.write(cc + struct.pack("<I", size))
         self._file.write(body)
@@ -431,9 +623,12 @@ class AviWriter:
         if self._closed:
             raise ValueError("AviWriter: closed")
         for blob in blobs:
+            if self._video is not None and len(blob) not in (0, self._video[4]):
+                raise self._fail(ValueError(f"AviWriter: frame {self.n_frames}: {len(blob)} bytes, an uncompressed frame is {self._video[4]} bytes"))
             if self._file is None:
                 self._open()
-            self._room(len(blob))
+            if not self.opendml:
+                self._room(len(blob))
             if self.n_frames:
                 self._put_sound(self.n_frames - 1, False)
             self._put(b"00dc", blob, AVIIF_KEYFRAME if len(blob) else 0)
@@ -450,16 +645,29 @@ class AviWriter:
             raise self._fail(ValueError("write_avi: no frame"))
         f = self._file
         self._put_sound(self.n_frames - 1, True)
+        if self.opendml:
+            end = self._close_form()
+            f.seek(self._base)
+            f.write(b"RIFF" + struct.pack("<I", self._first[0]) + b"AVI " + self._header(self.n_frames, self._biggest) + b"LIST" +
+                    struct.pack("<I", self._first[1]))
+            f.seek(self._base + end)
+            if self._owned:
+                f.close()
+            self._file, self._closed = None, True
+            return self.path
         if self._at & 1:  # (cannot happen, every chunk is padded; build_avi says the same)
             f.write(b"\0")
         if self.index:
             body = b"".join(self._entries)
             f.write(b"idx1" + struct.pack("<I", len(body)) + body)
         end = f.tell()
-        hdrl = _hdrl(self.n_frames, self._biggest, self.width, self.height, self.rate, self.scale, self._sound(), self.audio_rate, self.index)
-        f.seek(0)
-        f.write(b"RIFF" + struct.pack("<I", end - 8) + b"AVI " + hdrl + b"LIST" + struct.pack("<I", self._at))
-        f.close()
+        hdrl = _hdrl(self.n_frames, self._biggest, self.width, self.height, self.rate, self.scale, self._sound(), self.audio_rate, self.index,
+                     video=self._video)
+        f.seek(self._base)
+        f.write(b"RIFF" + struct.pack("<I", end - self._base - 8) + b"AVI " + hdrl + b"LIST" + struct.pack("<I", self._at))
+        f.seek(end)
+        if self._owned:
+            f.close()
         self._file, self._closed = None, True
         return self.path
 
@@ -473,12 +681,70 @@ class AviWriter:
             self._fail(None)
 
 
+def _in_memory(blobs, width, height, rate, scale, pcm, audio_rate, **kw) -> bytes:
+    """The bytes an AviWriter with these arguments writes from `blobs` in one append."""
+    import io
+
+    f = io.BytesIO()
+    with AviWriter(f, width, height, rate, scale, audio_rate, pcm=pcm, **kw) as w:
+        w.add_frames(blobs)
+    return f.getvalue()
+
+
+def raw_chunks(frames_u8_bgr, bits: int = 24, bottom_up: bool = True):
+    """Frames uint8 [n, H, W, 3] in BGR order (or a sequence of [H, W, 3] frames; None or an empty one: a dropped frame) -> (the
+    chunks of an uncompressed AVI stream of `bits` bits a pixel, one bytes object per frame, width, height): rows padded to 4 bytes
+    with zeros, the last row first when bottom_up, a fourth byte of zero per pixel at 32 bits.  dib.unpack_numpy is the inverse."""
+    if int(bits) not in (24, 32):
+        raise ValueError("write_avi_raw: 24 or 32 bits")
+    shape = next((np.shape(f) for f in frames_u8_bgr if f is not None and np.size(f)), None)
+    if shape is None or len(shape) != 3 or shape[2] != 3:
+        raise ValueError("write_avi_raw: no frame of shape [H, W, 3]")
+    h, w = shape[:2]
+    bpp = int(bits) // 8
+    stride = (w * bpp + 3) & ~3
+    chunks = []
+    for k, f in enumerate(frames_u8_bgr):
+        if f is None or not np.size(f):
+            chunks.append(b"")
+            continue
+        f = np.asarray(f)
+        if f.shape != shape or f.dtype != np.uint8:
+            raise ValueError(f"write_avi_raw: frame {k}: {f.dtype} {list(f.shape)}, the frames are uint8 {list(shape)}")
+        rows = np.zeros((h, stride), dtype=np.uint8)
+        rows[:, :w * bpp].reshape(h, w, bpp)[:, :, :3] = f
+        chunks.append((rows[::-1] if bottom_up else rows).tobytes())
+    return chunks, w, h
+
+
+def build_avi_raw(frames_u8_bgr, rate: int, scale: int = 1, pcm: Optional[np.ndarray] = None, audio_rate: int = 44100, bits: int = 24,
+                  bottom_up: bool = True, opendml: bool = False, segment_bytes: int = 1 << 30, index_segments: int = 256) -> bytes:
+    """The bytes `write_avi_raw` writes."""
+    chunks, w, h = raw_chunks(frames_u8_bgr, bits, bottom_up)
+    return _in_memory(chunks, w, h, rate, scale, pcm, audio_rate, codec="DIB", bits=bits, bottom_up=bottom_up, opendml=opendml,
+                      segment_bytes=segment_bytes, index_segments=index_segments)
+
+
+def write_avi_raw(path, frames_u8_bgr, rate: int, scale: int = 1, pcm: Optional[np.ndarray] = None, audio_rate: int = 44100, bits: int = 24,
+                  bottom_up: bool = True, opendml: bool = False, segment_bytes: int = 1 << 30, index_segments: int = 256):
+    """Writes the uncompressed AVI file `path` -- what `ffmpeg -c:v rawvideo -pix_fmt bgr24 -c:a pcm_s16le` writes: BI_RGB frames of
+    `bits` (24 or 32) bits a pixel from `frames_u8_bgr` (uint8 [n, H, W, 3], BGR; raw_chunks), bottom-up (biHeight > 0) or top-down,
+    sound and timing as write_avi.  A frame is stride * H bytes, so pass opendml=True for more than a few seconds of HD material (a
+    plain file stops at 4 GiB: 690 frames of 1920 x 1080).  Returns `path`."""
+    chunks, w, h = raw_chunks(frames_u8_bgr, bits, bottom_up)
+    with AviWriter(path, w, h, rate, scale, audio_rate, pcm=pcm, codec="DIB", bits=bits, bottom_up=bottom_up, opendml=opendml,
+                   segment_bytes=segment_bytes, index_segments=index_segments) as wr:
+        wr.add_frames(chunks)
+    return path
+
+
 def write_avi(path, jpeg_blobs: Sequence, rate: int, scale: int = 1, pcm: Optional[np.ndarray] = None, audio_rate: int = 44100,
-              index: bool = True):
+              index: bool = True, opendml: bool = False, segment_bytes: int = 1 << 30, index_segments: int = 256):
     """Writes the Motion-JPEG AVI file `path`: one `00dc` chunk per JPEG file of `jpeg_blobs` (an empty one is a dropped frame)
     at `rate` / `scale` frames per second, `pcm` (int16 [L] or [L, C] at `audio_rate`) as stream 01, interleaved in chunks of about
     one video frame's duration, and an `idx1` index when asked.  `open_avi` of the file gives the same bytes and the same samples.
-    One AviWriter fed everything at once: the picture size is the first frame's own, and a file past 4 GiB is its OSError.
+    One AviWriter fed everything at once: the picture size is the first frame's own, and a file past 4 GiB is its OSError --
+    unless `opendml` (with `segment_bytes`, `index_segments`: AviWriter) asks for the OpenDML layout, which has no such end.
     Returns `path`."""
     first = next((b for b in jpeg_blobs if len(b)), None)
     if first is None:
@@ -487,6 +753,7 @@ def write_avi(path, jpeg_blobs: Sequence, rate: int, scale: int = 1, pcm: Option
     if rate <= 0 or scale <= 0:
         raise ValueError("write_avi: rate and scale positive")
     width, height = jpeg_size(first)
-    with AviWriter(path, width, height, rate, scale, audio_rate, pcm=pcm, index=index) as w:
+    with AviWriter(path, width, height, rate, scale, audio_rate, pcm=pcm, index=index, opendml=opendml, segment_bytes=segment_bytes,
+                   index_segments=index_segments) as w:
         w.add_frames(jpeg_blobs)
     return path

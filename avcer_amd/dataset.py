@@ -49,10 +49,12 @@ class VideoJob:
     detections: Optional[Sequence[np.ndarray]] = None
 
 
-def video_job_from_avi(path, detections: Optional[Sequence[np.ndarray]] = None, engine=None, frames_per_pass: int = 64) -> VideoJob:
-    """The job of one Motion-JPEG / PCM AVI file (avcer_amd/avi.py: what is read, what is refused).  The metadata comes from the
+def video_job_from_avi(path, detections: Optional[Sequence[np.ndarray]] = None, engine=None, frames_per_pass: int = 64,
+                       opendml: bool = True) -> VideoJob:
+    """The job of one Motion-JPEG or uncompressed-BGR / PCM AVI file (avcer_amd/avi.py: what is read, what is refused; `opendml`:
+    open_avi's flag, True by default here -- no test pins the refusal through this entry point -- so a file past 1 GiB simply runs).  The metadata comes from the
     container's headers and its chunk walk alone -- no frame is decoded; fps is int(rate / scale), as run.run_inference_file
-    takes it.  `load` opens the file again when the video's turn comes, decodes the frames on the device (jpeg.decode_frames; on
+    takes it.  `load` opens the file again when the video's turn comes, decodes the frames on the device (AviFile.decode_frames; on
     `engine`, default: the engine alive for the current device, which is the one run_dataset was given) and returns them with the
     source audio, int16 [L, C] at the file's rate.  A file without an audio stream raises ValueError here."""
     import os
@@ -60,19 +62,17 @@ def video_job_from_avi(path, detections: Optional[Sequence[np.ndarray]] = None, 
     from .avi import open_avi
 
     path = os.fspath(path)
-    with open_avi(path) as avi:
+    with open_avi(path, opendml=opendml) as avi:
         if avi.pcm is None:
             raise ValueError(f"{path}: no audio stream")
         meta = (avi.n_frames, avi.height, avi.width, int(avi.rate / avi.scale), len(avi.pcm), avi.audio_rate)
 
     def load():
-        from . import jpeg
         from .engine import Engine
 
-        with open_avi(path) as avi:
+        with open_avi(path, opendml=opendml) as avi:
             eng = engine if engine is not None else Engine.live()
-            frames, _ = jpeg.decode_frames(eng, avi.frames, avi.height, avi.width, bgr=True, frames_per_pass=frames_per_pass)
-            return frames, avi.pcm
+            return avi.decode_frames(eng, bgr=True, frames_per_pass=frames_per_pass), avi.pcm
 
     name = os.path.splitext(os.path.basename(path))[0]
     return VideoJob(name, meta[0], meta[1], meta[2], meta[3], meta[4], wav_sr=meta[5], load=load, detections=detections)

@@ -900,6 +900,24 @@ class Engine:
                                                int(height), int(width), 1 if bgr else 0, self._stream()))
         return frames, flags
 
+    def dib_frames(self, span, offsets, n: int, height: int, width: int, bits: int, bottom_up: bool, bgr: bool = True, out=None):
+        """Uncompressed video frames (avcer_dib_frames): span u8 [bytes] and offsets i64 [n] on the device (the first byte of each
+        frame's chunk data in `span`, any alignment) -> frames u8 [n,height,width,3] in BGR order, or RGB with bgr=False.  A frame
+        is `height` rows of (width * bits / 8 + 3) & ~3 bytes, bits 24 or 32, the last row first when bottom_up."""
+        if span.dtype != torch.uint8 or span.dim() != 1 or not span.is_cuda or span.stride(0) != 1:
+            raise ValueError("dib_frames: span must be a uint8 vector on the device")
+        if offsets.dtype != torch.int64 or offsets.numel() < n or not offsets.is_cuda or not offsets.is_contiguous():
+            raise ValueError("dib_frames: offsets int64 [n] on the device")
+        if int(bits) not in (24, 32):
+            raise ValueError(f"dib_frames: {bits} bits a pixel (24 or 32)")
+        frames = self._new(n, int(height), int(width), 3, dtype=torch.uint8) if out is None else out
+        if tuple(frames.shape) != (n, int(height), int(width), 3) or frames.dtype != torch.uint8 or not frames.is_contiguous() or \
+                not frames.is_cuda:
+            raise ValueError("dib_frames: out must be a contiguous uint8 [n,height,width,3] on the device")
+        self._check(self.lib.avcer_dib_frames(self.ctx, _ptr(span), int(span.numel()), _ptr(offsets), int(n), _ptr(frames), int(height),
+                                              int(width), int(bits), 1 if bottom_up else 0, 1 if bgr else 0, self._stream()))
+        return frames
+
     def crop_resize_linear(self, frames_u8, rects, swap_rb: bool = False, out_h: int = 224, out_w: int = 224):
         """frames u8 [T,H,W,3] + rects i32 [n,5] (frame, x0, y0, x1, y1) -> u8 [n,out_h,out_w,3]: cv2.resize of each crop with
         INTER_LINEAR, first and last channel swapped when `swap_rb`."""

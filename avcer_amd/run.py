@@ -58,6 +58,8 @@ class _Options:
     video_quality: int = 90
     video_panel: bool = False
     video_timing: Optional[Sequence[int]] = None
+    video_opendml: bool = False
+    video_segment_bytes: int = 1 << 30
     tracks: object = None
     detect_size: object = None
     detect_filter: str = "bilinear"
@@ -77,11 +79,17 @@ class _Source:
 
 
 def run_inference_file(engine, path, detector=None, detections: Optional[Sequence[np.ndarray]] = None, fps: Optional[float] = None,
-                       frames_per_pass: int = 64, stream_frames: Optional[int] = None, audio_windows_per_pass: int = 128, **kw):
+                       frames_per_pass: int = 64, stream_frames: Optional[int] = None, audio_windows_per_pass: int = 128, opendml: bool = True,
+                       **kw):
     """`run_inference` on a recording: the reference's first line, `VideoPredictor.process` opening a video file
     (data/get_face_images.py:19-24, 44-47), for the one container this project reads without a decoder library -- the Motion-JPEG /
     PCM AVI file that `ffmpeg -i clip.mp4 -c:v mjpeg -q:v 2 -c:a pcm_s16le -ar 44100 -ac 2 clip.avi` writes (avcer_amd/avi.py).
-    open_avi -> jpeg.decode_frames (the frames are decoded on the device and never exist on the host) ->
+    The same container with uncompressed BGR video (`-c:v rawvideo -pix_fmt bgr24`: the decoder's own frames, no lossy transcode; the
+    device unpacks them, dib.unpack_frames) is read as well, and `opendml=True` (the default here; no test pins the refusal through
+    this entry point) reads the OpenDML layout ffmpeg changes to past 1 GiB, so a long file simply runs; opendml=False refuses it as
+    avi.open_avi does by default.
+    open_avi -> AviFile.decode_frames (jpeg.decode_frames or dib.unpack_frames by the file's codec: the frames are decoded on the
+    device and never exist on the host) ->
     run_inference(engine, frames, avi.pcm, fps, wav_sr=avi.audio_rate, name_video=<stem of path>, **kw).
     `fps` defaults to int(rate / scale), what int(cv2.CAP_PROP_FPS) gives the reference (get_face_images.py:23).
     A file without an audio stream raises ValueError unless `wav=` (with `wav_sr=`, or mono at `sr`) is passed; a rate pair the
@@ -123,7 +131,7 @@ def run_inference_file(engine, path, detector=None, detections: Optional[Sequenc
     check_detect_size(o.detect_size, o.detect_filter, detector, detections)
     _check_plot(o)
     start_time = time.time()
-    with open_avi(path) as avi:
+    with open_avi(path, opendml=opendml) as avi:
         check_detect_size(o.detect_size, o.detect_filter, detector, detections, (avi.height, avi.width))
         if not given_wav:
             if avi.pcm is None:
@@ -141,11 +149,11 @@ def run_inference_file(engine, path, detector=None, detections: Optional[Sequenc
             o.video_timing = (avi.rate, avi.scale)  # the source's own rate / scale pair, not the rounded fps
         if stream_frames is not None:
             per = int(stream_frames)
-            src = _Source(avi.n_frames, avi.height, avi.width, per, lambda a: jpeg.decode_frames(
-                engine, avi.frames[a:a + per], avi.height, avi.width, bgr=True, frames_per_pass=frames_per_pass)[0])
+            src = _Source(avi.n_frames, avi.height, avi.width, per,
+                          lambda a: avi.decode_frames(engine, a, a + per, bgr=True, frames_per_pass=frames_per_pass))
             return _run(engine, src, wav, fps, detector, detections, o, _check(engine, o, detector, detections, (avi.height, avi.width)),
                         start_time, int(audio_windows_per_pass))
-        frames, _ = jpeg.decode_frames(engine, avi.frames, avi.height, avi.width, bgr=True, frames_per_pass=frames_per_pass)
+        frames = avi.decode_frames(engine, bgr=True, frames_per_pass=frames_per_pass)
         n_frames = avi.n_frames
     out = run_inference(engine, frames, wav, fps, detector=detector, detections=detections, **vars(o))
     duration = n_frames / fps if (fps and fps > 0 and n_frames > 0) else None
@@ -192,7 +200,9 @@ def run_inference(engine, frames_bgr, wav, fps: float, detector=None, detections
     quality `video_quality`); `out["result_video"]` is the path.  The frame rate is `fps` (or `video_timing` = the container's exact
     (rate, scale) pair); the sound is `wav` when it was given as int16 source audio with `wav_sr`, else there is none.  The
     drawing is PIL's ImageDraw, bit for bit, not cv2's.  `video_model`: "av", "vs", "vd" or "a"; anything else raises ValueError
-    before any work.  Off by default: nothing changes then.
+    before any work.  Off by default: nothing changes then.  `video_opendml=True` writes it in the OpenDML layout (avi.AviWriter:
+    segments of `video_segment_bytes`, read back with open_avi(opendml=True)), which has no 4 GiB end: the result video of a long
+    streamed recording; False (the default) changes nothing.
     `tracks`: which face tracks the visual models and the fusion run on.  None (the default): track directory 00 alone, as the
     reference (get_prob_video.py:79-94 walks `<faces>/00/`; get_face_images.py:73-76 leaves choosing a "target face" among the
     folders to the user) -- today's call, unchanged.  "all": every track directory stage 0 writes, ascending.  A list of distinct
@@ -498,5 +508,6 @@ def _results(engine, res, host, frames, wav, fps, o: _Options, plot=None):
             labelled = tp.tracks
         out["result_video"] = write_result_video(engine, frames, records, pred, prob_model, o.path_save_video, int(video_timing[0]),
                                                  int(video_timing[1]), pcm=pcm, audio_rate=int(wav_sr) if pcm is not None else 44100,
-                                                 quality=o.video_quality, entropy="device", panel=o.video_panel, tracks=labelled)
+                                                 quality=o.video_quality, entropy="device", panel=o.video_panel, tracks=labelled,
+                                                 **(dict(opendml=True, segment_bytes=o.video_segment_bytes) if o.video_opendml else {}))
     return out

@@ -103,7 +103,9 @@ enum {
  *      joined under 8 the same way: two more symbols, nothing that existed changed.
  *      avcer_eval_tables, avcer_eval_tables_workspace, avcer_eval_confusion (a dataset's per-video CSV tables turned into the
  *      trues / preds tables of the weight search, and a model or fusion scored on them) joined under 8 the same way: three more
- *      symbols, nothing that existed changed. */
+ *      symbols, nothing that existed changed.
+ *      avcer_dib_frames (uncompressed BGR video of an AVI file unpacked into the frame batch) joined under 8 the same way: one
+ *      more symbol, nothing that existed changed. */
 #define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
@@ -610,6 +612,22 @@ int avcer_jpeg_entropy_batch_ex(avcer_ctx* ctx, const uint8_t* const* files_host
                                 int64_t cap_blocks, avcer_jpeg_desc* desc_host, int threads, int hflags, int64_t* blocks_needed);
 int avcer_jpeg_frames(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_blocks, const avcer_jpeg_desc* desc, int n, int32_t* flags,
                       uint8_t* frames, int H, int W, int bgr, avcer_stream_t stream);
+
+/* Uncompressed video: the frames of an AVI file whose video stream is BI_RGB device-independent bitmaps of 24 or 32 bits a pixel
+ * (`ffmpeg -c:v rawvideo -pix_fmt bgr24`; avcer_amd/avi.py, avcer_amd/dib.py) unpacked into the same batch,
+ *   ref: data/get_face_images.py:19-24, 44-47 (cv2.VideoCapture: the frames of a recording, BGR)
+ * without a lossy transcode between the decoder's BGR frames and the detector.  There is no arithmetic; the contract is identity
+ * with PIL's BMP reader on the same bytes, tolerance zero.
+ * avcer_dib_frames: `span` = span_bytes file bytes on the device (any alignment), offsets i64 [n] on the device: the first byte of
+ *   frame i's chunk data from `span` (any alignment; two frames may share one: a repeated frame) -> frames u8 [n,H,W,3].  A source
+ *   frame is H rows of stride = (W * bits / 8 + 3) & ~3 bytes, B G R (X) per pixel, bits 24 or 32, the picture's LAST row first
+ *   with bottom_up != 0.  The output rows are top-down, without the padding and the fourth byte, in BGR order with bgr != 0 and in
+ *   RGB order otherwise.  Every byte of `frames` is written, none outside; `frames` needs no alignment (aligned 16-byte stores
+ *   along each row, byte stores at a row's two ends).  No byte outside [span, span + span_bytes) is read (aligned 16-byte loads
+ *   where they lie inside, byte loads at the span's two ends); a frame whose offset is negative or leaves fewer than stride * H
+ *   bytes is written as zeros.  H, W in 1..65535, n H W < 2^36.  One kernel on `stream`, no synchronisation with the host. */
+int avcer_dib_frames(avcer_ctx* ctx, const uint8_t* span, int64_t span_bytes, const int64_t* offsets, int n, uint8_t* frames, int H,
+                     int W, int bits, int bottom_up, int bgr, avcer_stream_t stream);
 
 /* The other direction: the JPEG wire format between stages 0 and 1 is written by this library as well as read.  The face folders
  * of stage 0 and the heat maps,
