@@ -707,8 +707,11 @@ int avcer_jpeg_pack(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_blocks, con
  *   dummy blocks included: one pass then serves the tiles and avcer_jpeg_pack / avcer_jpeg_write_batch.
  * flags i32 [n] (device, written by both calls): as avcer_jpeg_tiles writes them -- an encoder's own coefficients cannot leave the
  *   range, so a 1 there would be a finding about the kernel -- and 1 as well for a descriptor avcer_jpeg_plan did not write or
- *   whose blocks lie outside the n_blocks blocks: such an image's output is zero and nothing is stored or read through its
- *   geometry.  A desc[i] that is NOT_HANDLED yields zeros and flag 0, as in avcer_jpeg_tiles.
+ *   whose blocks lie outside the n_blocks blocks: such an image's tile / canvas slot is zero and no pixel is stored or read
+ *   through its geometry.  `coeffs` is not part of that: it receives what avcer_jpeg_forward stores, and avcer_jpeg_forward does
+ *   not judge a descriptor -- the blocks [coef_block, coef_block + n_blocks) of a flagged image that lie inside the n_blocks
+ *   blocks are written as it writes them.  A desc[i] that is NOT_HANDLED yields zeros and flag 0, as in avcer_jpeg_tiles, and
+ *   none of its blocks is written.
  * Both calls run three kernels on `stream` -- the flags; the forward path of avcer_jpeg_forward per 8 x 8 block, unchanged, with the
  * dequantisation and the inverse DCT of avcer_jpeg_tiles' first kernel behind it in the same lanes, storing u8 component planes
  * into the context's JPEG workspace (64 bytes per block; the coefficients do not leave the chip unless `coeffs` asks for them);

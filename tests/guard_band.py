@@ -14,6 +14,8 @@ byte 0xA5 before the first run and 0x5A before the second -- two patterns that d
   3. they are bit-identical, too, to a third run into a fresh tensor of exactly the output's size, which is the configuration the
      parity tests compare with float64;
   4. every input tensor holds the same bits after the runs as before.
+A band may name a third kind of element besides "must" and "must not": `may`, the elements a contract leaves unspecified (the
+coefficient blocks of a JPEG file that the reader ends up refusing).  They are left out of checks 1 to 3 and of nothing else.
 All comparisons are on bytes, so NaN payloads compare like any other.  The module is device-agnostic: tests/test_guard_band_cpu.py
 applies it to Python functions on CPU tensors, tests/test_gpu_write_bounds.py to the library's kernels."""
 from __future__ import annotations
@@ -30,13 +32,16 @@ GUARD_ROWS = 256
 @dataclass
 class Band:
     """One output tensor of the call: `shape` elements of `dtype`; `written`: None (every element must be written) or a bool
-    tensor that broadcasts to `shape`, True where the call must write, False where it must not (a gap).  `row_bytes`: the bytes
-    of one output row of the case (default: the last dimension), which sizes the guards."""
+    tensor that broadcasts to `shape`, True where the call must write, False where it must not (a gap).  `may`: None or a bool
+    tensor that broadcasts to `shape`, True where the contract leaves the element unspecified (the call may write it or not, with
+    any value); it must not overlap `written`.  `row_bytes`: the bytes of one output row of the case (default: the last dimension),
+    which sizes the guards."""
     name: str
     shape: tuple
     dtype: torch.dtype
     written: torch.Tensor | None = None
     row_bytes: int | None = None
+    may: torch.Tensor | None = None
 
     @property
     def itemsize(self) -> int:
@@ -56,6 +61,19 @@ class Band:
         if self.written is None:
             return torch.ones(self.nbytes, dtype=torch.bool)
         return self.written.cpu().expand(self.shape).reshape(-1).repeat_interleave(self.itemsize)
+
+    def may_mask(self) -> torch.Tensor | None:
+        """bool [nbytes] on the CPU: True where the call may write or not; None without `may`."""
+        if self.may is None:
+            return None
+        if self.written is None:
+            raise ValueError(f"output '{self.name}': a `may` region needs a `written` mask that leaves it out")
+        may = self.may.cpu().expand(self.shape).reshape(-1).repeat_interleave(self.itemsize)
+        both = may & self.byte_mask()
+        if both.any():
+            raise ValueError(f"output '{self.name}': `may` overlaps `written` in {int(both.sum())} bytes, the first at payload "
+                             f"byte {_first(both)}")
+        return may
 
 
 def columns(ld: int, off: int, n: int) -> torch.Tensor:
@@ -85,6 +103,7 @@ def check(run, bands, inputs=(), device="cpu"):
 
     before = [_bytes(t).clone() for t in inputs]   # (on the CPU _bytes is a view)
     masks = [b.byte_mask() for b in bands]
+    mays = [b.may_mask() for b in bands]
     payloads = []
     for run_no, pat in enumerate(PATTERNS):
         bufs, outs = [], []
@@ -96,7 +115,7 @@ def check(run, bands, inputs=(), device="cpu"):
         run(outs)
         sync()
         got = []
-        for b, buf, mask in zip(bands, bufs, masks):
+        for b, buf, mask, may in zip(bands, bufs, masks, mays):
             g = b.guard_bytes
             raw = buf.cpu()
             row = b.row_bytes if b.row_bytes is not None else b.shape[-1] * b.itemsize
@@ -109,6 +128,8 @@ def check(run, bands, inputs=(), device="cpu"):
                                    f"behind the payload (row {b.nbytes // row} + {_first(bad) // row}, byte {_first(bad) % row} of it)")
             pay = raw[g:g + b.nbytes]
             bad = (pay != pat) & ~mask
+            if may is not None:
+                bad &= ~may
             assert not bad.any(), (f"{where}: {int(bad.sum())} bytes of gap elements overwritten, the first at payload byte "
                                    f"{_first(bad)} (row {_first(bad) // row}, byte {_first(bad) % row} of it)")
             got.append(pay.clone())

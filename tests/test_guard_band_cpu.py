@@ -106,6 +106,67 @@ def test_a_modified_input_fails():
         check(run, _bands(), inputs=[x])
 
 
+def _may_bands():
+    """Row M - 1 of the written columns is unspecified: neither "must" nor "must not"."""
+    written = columns(LD, OFF, N).expand(M, LD).clone()
+    written[M - 1] = False
+    may = torch.zeros(M, LD, dtype=torch.bool)
+    may[M - 1, OFF:OFF + N] = True
+    return [Band("y", (M, LD), torch.float32, written=written, may=may)]
+
+
+def _sometimes(x, at):
+    """Writes the "must" rows always and element `at` of the last row in every other call, with another value each time."""
+    calls = []
+
+    def run(outs):
+        outs[0][:M - 1, OFF:OFF + N] = x[:M - 1] * 2 + 1
+        calls.append(0)
+        if len(calls) % 2:
+            outs[0][M - 1, at] = float(len(calls))
+    return run
+
+
+def test_a_may_region_written_in_one_run_and_not_in_the_other_passes():
+    x = torch.arange(M * N, dtype=torch.float32).reshape(M, N)
+    got, = check(_sometimes(x, OFF + N - 1), _may_bands(), inputs=[x])
+    assert torch.equal(got[:M - 1, OFF:OFF + N], x[:M - 1] * 2 + 1)
+    # the same function without `may`: the last row is a gap, and the write into it is seen
+    bands = _may_bands()
+    bands[0].may = None
+    with pytest.raises(AssertionError, match="gap elements overwritten"):
+        check(_sometimes(x, OFF + N - 1), bands, inputs=[x])
+
+
+def test_a_write_one_element_outside_the_may_region_fails():
+    x = torch.ones(M, N)
+    with pytest.raises(AssertionError, match="gap elements overwritten"):
+        check(_sometimes(x, OFF + N), _may_bands(), inputs=[x])
+    with pytest.raises(AssertionError, match="gap elements overwritten"):
+        check(_sometimes(x, OFF - 1), _may_bands(), inputs=[x])
+
+
+def test_a_may_region_does_not_excuse_an_unwritten_must_element():
+    x = torch.ones(M, N)
+
+    def run(outs):
+        outs[0][:M - 1, OFF:OFF + N - 1] = 3.0
+        outs[0][:M - 2, OFF + N - 1] = 3.0           # row M - 2 lacks its last element
+    with pytest.raises(AssertionError, match="differ between the two runs"):
+        check(run, _may_bands(), inputs=[x])
+
+
+def test_a_may_region_that_overlaps_written_is_refused():
+    bands = _may_bands()
+    bands[0].may = bands[0].may.clone()
+    bands[0].may[M - 2, OFF] = True
+    with pytest.raises(ValueError, match="overlaps `written`"):
+        check(_good(torch.ones(M, N)), bands)
+    # written=None is "every element must be written": any `may` overlaps it
+    with pytest.raises(ValueError, match="`may`"):
+        check(_good(torch.ones(M, N)), [Band("y", (M, LD), torch.float32, may=torch.ones(1, dtype=torch.bool))])
+
+
 def test_guards_are_aligned_and_cover_256_rows():
     for band in (Band("t", (300, 2048), torch.int16), Band("s", (17, 33), torch.float32), Band("w", (5,), torch.uint8, row_bytes=3)):
         row = band.row_bytes or band.shape[-1] * band.itemsize
