@@ -233,17 +233,80 @@ def _stacked(engine, predictions):
     return torch.stack([engine._dev(p, torch.float64) for p in predictions])
 
 
-def score(engine, trues, predictions, weights_1=None, weights_2=None) -> dict:
+def score(engine, trues, predictions, weights_1=None, weights_2=None, save_path=None, labels=None, title="") -> dict:
     """get_metrics: {"uar", "acc", "f1", "precision", "mean", "cm"} of the argmax of sum_i predictions[i] * weights_1[i] *
     weights_2[i] (one table without weights: get_pred_audio.get_metrics).  One Engine.eval_confusion launch; the 49 counts are
     the only thing fetched.  Labels outside 0..6 are in no cell of the matrix, and sklearn would average over their classes
-    too: ValueError."""
+    too: ValueError.
+    save_path (a .jpg / .jpeg file; anything else is refused before any launch): the matrix is also drawn as the reference's
+    plot_conf_matrix draws it (figures.write_conf_matrices; `labels`: the tick labels, None: EMO; `title`) and the path is
+    out["plot_conf"].  None, the default: the figures module is not imported and the dict is the one above."""
+    if save_path is not None:
+        from . import figures
+
+        save_path = figures.check_paths([save_path])[0]
     t = _stacked(engine, predictions)
     _, cm = engine.eval_confusion(t, trues, weights_1, weights_2, want_pred=False)
     cm = cm.cpu().numpy()
     if int(cm.sum()) != int(t.shape[1]):
         raise ValueError(f"score: {int(t.shape[1]) - int(cm.sum())} labels outside 0..6")
-    return metrics_from_cm(cm)
+    out = metrics_from_cm(cm)
+    if save_path is not None:
+        out["plot_conf"] = figures.write_conf_matrices(engine, [out["cm"]], EMO if labels is None else labels, [save_path], [title])[0]
+    return out
+
+
+MODEL_STEMS = {"stat": "static", "dyn": "dynamic", "audio": "audio"}  # get_pred_video.py:66,81; "audio": see score_models
+MODEL_TITLES = {"stat": "Static video model", "dyn": "Dynamic video model", "audio": "Audio model ()"}  # :64,79; get_pred_audio.py:40
+
+
+def score_models(engine, trues, models: dict, weights_1=None, weights_2=None, save_dir=None, corpus: str = "ABAW", modality=None,
+                 weight_type: str = "single", name_model: str = "", labels=None, **figure_options) -> dict:
+    """The loop the get_metrics of get_pred_av.py / get_pred_video.py / get_pred_audio.py run: `models` is {"stat" / "dyn" /
+    "audio": table [N, 7]} in the order of `weights_1` [M, 7] / `weights_2` [M].  Scored (`score`) are the fusion of all models --
+    "fusion", left out when there is one model -- and every single model on its own, unweighted, as get_pred_video.py:55-83 does.
+    Returns {"fusion": metrics, "stat": metrics, ...}.
+    save_dir: every confusion matrix is drawn, ALL in one figures.write_conf_matrices call, and each metrics dict gets its
+    "plot_conf".  The file names are the reference's with `.jpg` for its `.pdf` (this project writes no PDF), `modality`
+    defaulting to "AV" / "V" / "A" by the models given:
+      fusion       <corpus>_<modality>_sd_<weight_type>.jpg         "Audio-Video fusion. <corpus>. UAR = xx.xx%" (get_pred_av.py:52-53),
+                                                                    without an audio model "Video fusion. ..." (get_pred_video.py:51-52)
+      stat, dyn    <corpus>_<modality>_static_<weight_type>.jpg, ..._dynamic_...   "Static video model. ...", "Dynamic video model. ..."
+      audio alone  <corpus>_<modality>_<name_model>.jpg             "Audio model (). ..." (get_pred_audio.py:40-42)
+      audio beside visual models: <corpus>_<modality>_audio_<weight_type>.jpg -- get_pred_av.py draws the fusion only; the
+                   single models are scored and drawn here in the video script's manner.
+    `figure_options` (width, height, colorbar, font, quality, subsampling, entropy) go to write_conf_matrices.  A bad option is
+    refused before anything is scored."""
+    unknown = [k for k in models if k not in MODEL_STEMS]
+    if unknown or not models:
+        raise ValueError(f"score_models: models are keyed by {tuple(MODEL_STEMS)}, not {unknown[0]!r}" if unknown else "score_models: no model")
+    names = list(models)
+    if save_dir is not None:
+        from . import figures
+
+        bad = [k for k in figure_options if k not in ("width", "height", "colorbar", "font", "quality", "subsampling", "entropy")]
+        if bad:
+            raise ValueError(f"score_models: unknown figure option {bad[0]!r}")
+    elif figure_options:
+        raise ValueError("score_models: figure options without save_dir")
+    if modality is None:
+        modality = "A" if names == ["audio"] else "AV" if "audio" in names else "V"
+    out, stems, titles = {}, {}, {}
+    if len(names) > 1:
+        out["fusion"] = score(engine, trues, [models[k] for k in names], weights_1, weights_2)
+        stems["fusion"] = f"{corpus}_{modality}_sd_{weight_type}"
+        titles["fusion"] = "Audio-Video fusion" if "audio" in names else "Video fusion"
+    for k in names:
+        out[k] = score(engine, trues, [models[k]])
+        stems[k] = f"{corpus}_{modality}_{name_model}" if len(names) == 1 and k == "audio" else f"{corpus}_{modality}_{MODEL_STEMS[k]}_{weight_type}"
+        titles[k] = MODEL_TITLES[k]
+    if save_dir is not None:
+        paths = [os.path.join(os.fspath(save_dir), stems[k] + ".jpg") for k in out]
+        heads = ["{0}. {1}. UAR = {2:.2f}%".format(titles[k], corpus, out[k]["uar"] * 100) for k in out]
+        figures.write_conf_matrices(engine, [out[k]["cm"] for k in out], EMO if labels is None else labels, paths, heads, **figure_options)
+        for k, path in zip(out, paths):
+            out[k]["plot_conf"] = path
+    return out
 
 
 # --------------------------------------------------------------------------- the kernels, stated in numpy

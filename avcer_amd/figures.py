@@ -2,11 +2,15 @@
 get_pred_video.py / get_pred_av.py / get_pred_audio.py ends in, and `plot_weights_matrix` of get_weights_matrices.py -- a grid of
 coloured cells with their numbers written into them, a colour bar, tick labels, captions and a title.
 
-This module is the CPU STATEMENT of those figures and nothing else: the plan (`matrix_plan`), the numbers as text (`round_scaled`,
-`fixed`), the colours (`lut_index`, `BLUES`), the per-cell records a device kernel would write (`cell_records`) and the picture
-(`paint_numpy`, `matrix_numpy`).  It is what a device path is to be held to, bit for bit, as chart.chart_numpy is for the
-timeline chart; no device path is part of the package yet ("Matrix figures"), so nothing here runs on the
-GPU and nothing in the product calls it.
+The CPU STATEMENT of those figures: the plan (`matrix_plan`), the numbers as text (`round_scaled`, `fixed`), the colours
+(`lut_index`, `BLUES`), the per-cell records (`cell_records`) and the picture (`paint_numpy`, `matrix_numpy`).  It is what the
+device path is held to, bit for bit, as chart.chart_numpy is for the timeline chart.
+
+The DEVICE PATH has no kernel of its own ("Matrix figures").  Everything a figure consists of is an item
+kind of annotate.draw -- a cell and a colour band are FILL items, a glyph is a MASK item -- so a figure is an item list built on
+the host (`matrix_items`: the text is formatted on the host, from counts `evaluate.score` has there anyway) in front of the
+existing avcer_annotate_frames, followed by the existing JPEG encoder: `render` draws a batch, `write_conf_matrices` /
+`write_weights_matrices` write the files, and only file bytes cross to the host.
 
 The reference plots with matplotlib and saves `.pdf`.  Two identities are claimed, both at tolerance zero: with PIL for
 everything drawn (`ImageDraw.rectangle` per cell and colour band, `ImageDraw.bitmap` of the font's masks per glyph and label),
@@ -39,6 +43,7 @@ from the bar's lowest row, e(k) = (k * bh) // 256.
 from __future__ import annotations
 
 import math
+import os
 from dataclasses import dataclass, field
 from fractions import Fraction
 
@@ -368,3 +373,184 @@ def matrix_numpy(values, plan: MatrixPlan) -> np.ndarray:
     pic = np.full((1, plan.height, plan.width, 3), 255, dtype=np.uint8)
     paint_numpy(values, plan, pic[0])
     return an.draw_numpy(pic, plan.items, plan.masks)[0]
+
+
+# ---------------------------------------------------------------------------------------------------- the device path
+_GLYPH_MASKS = {}  # id(font) -> (font, [u8 [h, w]] * 13)
+
+
+def glyph_masks(font) -> list:
+    """The 13 masks of `glyph_atlas` as u8 [h, w] arrays, the same objects at every call, so that a batch stores them once."""
+    hit = _GLYPH_MASKS.get(id(font))
+    if hit is None or hit[0] is not font:
+        flat, table, _ = glyph_atlas(font)
+        hit = _GLYPH_MASKS[id(font)] = (font, [flat[o:o + w * h].reshape(h, w) for o, w, h in table[:, :3].tolist()])
+    return hit[1]
+
+
+def matrix_items(values, plan: MatrixPlan, frame: int = 0):
+    """The whole figure as (items ITEM [m] of frame `frame`, masks): drawn in list order onto a WHITE picture (annotate.draw_numpy,
+    annotate.draw) they give `matrix_numpy(values, plan)`.  In this order: an opaque FILL per cell in its colour; a MASK per glyph
+    of every cell at the position `cell_records` gives, in ink 255 or 0; a FILL per non-empty colour band; `plan.items`.  masks: the
+    13 glyph masks (`glyph_masks`), then `plan.masks`.
+    `paint_numpy` clips a glyph to its cell, a MASK item is not clipped: a glyph that leaves its cell -- only a weight wider than
+    the "0.00" `matrix_plan` sized the cells for can -- raises ValueError naming the cell; nothing else is drawn in its place."""
+    recs = cell_records(values, plan)
+    glyphs = glyph_masks(plan.font)
+    cells, text = [], []
+    for c, (lut, ink, line) in enumerate(recs):
+        i, j = divmod(c, plan.cols)
+        cx0, cy0, cx1, cy1 = plan.cell(i, j)
+        cells.append(an.fill(frame, (cx0, cy0, cx1, cy1), BLUES[lut].tolist()))
+        for g, gx, gy in line:
+            h, w = glyphs[g].shape
+            if gx < cx0 or gy < cy0 or gx + w - 1 > cx1 or gy + h - 1 > cy1:
+                raise ValueError(f"cell ({i}, {j}): its text {''.join(GLYPHS[q] for q, _, _ in line)!r} leaves the cell of "
+                                 f"{cx1 - cx0 + 1} x {cy1 - cy0 + 1} pixels: a larger picture or fewer cells are needed")
+            text.append(an.mask(frame, (gx, gy), (ink, ink, ink), g))
+    bands = [(k, plan.band(k)) for k in range(256)]
+    bands = [an.fill(frame, b, BLUES[k].tolist()) for k, b in bands if b is not None]
+    own = plan.items.copy()
+    own["frame"] = frame
+    own["mask"] = np.where(own["kind"] == an.MASK, own["mask"] + len(glyphs), own["mask"])
+    return np.concatenate([an.as_items(cells + text + bands), own]), glyphs + list(plan.masks)
+
+
+def batch_items(values_list, plans):
+    """The item lists of a batch, figure k as frame k, over ONE mask list in which identical masks (the same array, or the same
+    shape and bytes) stand once -> (items, masks).  Checks everything `render` refuses."""
+    values_list, plans = list(values_list), list(plans)
+    if not plans:
+        raise ValueError("render: no figure")
+    if len(values_list) != len(plans):
+        raise ValueError(f"render: {len(values_list)} matrices for {len(plans)} plans")
+    if any((p.height, p.width) != (plans[0].height, plans[0].width) for p in plans):
+        raise ValueError("render: the figures of one call share one picture size; " +
+                         ", ".join(sorted({f"{p.width} x {p.height}" for p in plans})) + " were given")
+    masks, by_id, by_bytes, parts = [], {}, {}, []
+    for k, (values, plan) in enumerate(zip(values_list, plans)):
+        items, own = matrix_items(values, plan, frame=k)
+        slot = np.zeros(len(own), dtype=np.int32)
+        for q, m in enumerate(own):
+            if id(m) not in by_id:
+                key = (m.shape, m.tobytes())
+                if key not in by_bytes:
+                    by_bytes[key] = len(masks)
+                    masks.append(m)
+                by_id[id(m)] = (by_bytes[key], m)  # the array is kept: its id stays its own
+            slot[q] = by_id[id(m)][0]
+        items["mask"] = np.where(items["kind"] == an.MASK, slot[items["mask"]], items["mask"])
+        parts.append(items)
+    return np.concatenate(parts), masks
+
+
+def render(engine, values_list, plans, max_figures_per_call=None):
+    """`matrix_numpy` on the device for a batch: values_list[k] drawn after plans[k]; kinds and shapes may be mixed, the picture
+    size is one.  Returns uint8 [n, height, width, 3] RGB on the device: one white canvas, the item lists of all figures with
+    frame = k over one shared mask buffer (`batch_items`), drawn by ONE annotate.draw call.  Where annotate.work_table would refuse
+    the tiles of one call (2^31 tiles of 64 x 4 pixels) the batch is split by WHOLE figures into several calls; the pictures are
+    the same (`max_figures_per_call` forces such a split, for the tests).  An empty list, mixed picture sizes and whatever
+    `_check_values` / `matrix_items` refuse of a matrix raise ValueError before any launch."""
+    import torch
+
+    items, masks = batch_items(values_list, plans)
+    n, height, width = len(plans), plans[0].height, plans[0].width
+    flat, table = an.pack_masks(masks)
+    an.check_items(items, n, table, len(flat))
+    per = ((width - 1) // an.TILE_W + 1) * ((height - 1) // an.TILE_H + 1)  # the most tiles work_table counts for one figure
+    step = max(((1 << 31) - 1) // per, 1)
+    if max_figures_per_call is not None:
+        if int(max_figures_per_call) < 1:
+            raise ValueError("render: max_figures_per_call must be at least 1")
+        step = min(step, int(max_figures_per_call))
+    out = torch.full((n, height, width, 3), 255, dtype=torch.uint8, device=engine.device)
+    flat_d = torch.from_numpy(flat).to(engine.device)
+    for lo in range(0, n, step):
+        sel = items if step >= n else items[(items["frame"] >= lo) & (items["frame"] < lo + step)].copy()
+        sel["frame"] -= lo
+        an.draw(engine, out[lo:lo + step], sel, (flat_d, table))
+    return out
+
+
+FILE_TYPES = (".jpg", ".jpeg")
+NOT_WRITTEN = {".png": "PNG", ".pdf": "PDF", ".svg": "SVG"}  # what the reference's savefig would take from the extension
+
+
+def check_paths(paths, n=None) -> list:
+    """The paths of n figures as strings.  The reference takes the format from the extension (visualize.py:85); this project writes
+    JPEG files only: `.jpg` / `.jpeg` pass, `.png`, `.pdf`, `.svg` are refused by name, anything else too (ValueError)."""
+    paths = [os.fspath(p) for p in paths]
+    for p in paths:
+        ext = os.path.splitext(p)[1].lower()
+        if ext in NOT_WRITTEN:
+            raise ValueError(f"{p}: {NOT_WRITTEN[ext]} files are not written by this project: name the figure .jpg or .jpeg")
+        if ext not in FILE_TYPES:
+            raise ValueError(f"{p}: a figure is a JPEG file, named .jpg or .jpeg, not {ext!r}")
+    if n is not None and len(paths) != n:
+        raise ValueError(f"{len(paths)} paths for {n} figures")
+    return paths
+
+
+def _titles(titles, n):
+    if titles is None:
+        return ["Confusion Matrix"] * n  # the default of both functions of the reference (visualize.py:13,91)
+    if isinstance(titles, str):
+        return [titles] * n
+    if len(titles) != n:
+        raise ValueError(f"{len(titles)} titles for {n} figures")
+    return [str(t) for t in titles]
+
+
+def write_figures(engine, values_list, plans, paths, quality: int = 95, subsampling: int = 2, entropy: str = "device"):
+    """`render`, then one file per figure: paths[k] is PIL's Image.save(quality=quality, subsampling=subsampling) of
+    `matrix_numpy(values_list[k], plans[k])`, byte for byte (ONE jpeg.encode_images call over the batch; `entropy` as there).
+    Directories are made.  Every refusal comes before the first launch.  Returns the paths."""
+    from . import jpeg
+
+    jpeg._check_entropy(entropy)
+    plans = list(plans)
+    paths = check_paths(paths, len(plans))
+    pics = render(engine, values_list, plans)
+    n, h, w = (int(v) for v in pics.shape[:3])
+    rects = np.zeros((n, 5), dtype=np.int32)
+    rects[:, 0], rects[:, 3], rects[:, 4] = np.arange(n), w, h
+    files = jpeg.encode_images(engine, pics, rects, bgr=False, quality=quality, subsampling=subsampling, entropy=entropy)
+    for path, data in zip(paths, files):
+        if os.path.dirname(path):
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "wb") as f:
+            f.write(data)
+    return paths
+
+
+def write_conf_matrices(engine, cms, labels, paths, titles=None, width: int = 800, height: int = 600, colorbar: bool = True,
+                        font=None, quality: int = 95, subsampling: int = 2, entropy: str = "device"):
+    """plot_conf_matrix (visualize.py:10-85) for a batch: cms[k] (integer counts [rows, cols]) with the tick labels `labels` (one
+    list for all; None: the indices) and titles[k] (None: the reference's "Confusion Matrix"; a string: that for all) is written
+    to paths[k], all in one `write_figures` call.  Returns the paths."""
+    cms = [np.asarray(cm) for cm in cms]
+    paths = check_paths(paths, len(cms))
+    titles = _titles(titles, len(cms))
+    plans = [matrix_plan(cm.shape[0], cm.shape[1], "conf", width, height, labels, t, font, colorbar) if cm.ndim == 2 else None
+             for cm, t in zip(cms, titles)]
+    if any(p is None for p in plans):
+        raise ValueError("a confusion matrix is a [rows, cols] array")
+    return write_figures(engine, cms, plans, paths, quality, subsampling, entropy)
+
+
+def write_weights_matrices(engine, weights, labels, paths, titles=None, width: int = 800, height: int = 600, colorbar: bool = True,
+                           x_labels=True, font=None, quality: int = 95, subsampling: int = 2, entropy: str = "device"):
+    """plot_weights_matrix (visualize.py:88-172) for a batch: weights[k] (floats [models, classes]) with `labels` = (row labels,
+    column labels) for all (None: the indices), titles[k] as in `write_conf_matrices` and x_labels (a bool for all, or one per
+    figure) is written to paths[k], all in one `write_figures` call.  Returns the paths."""
+    weights = [np.asarray(w) for w in weights]
+    paths = check_paths(paths, len(weights))
+    titles = _titles(titles, len(weights))
+    xl = [x_labels] * len(weights) if isinstance(x_labels, (bool, np.bool_)) else list(x_labels)
+    if len(xl) != len(weights):
+        raise ValueError(f"{len(xl)} x_labels for {len(weights)} figures")
+    if any(w.ndim != 2 for w in weights):
+        raise ValueError("a weight matrix is a [models, classes] array")
+    plans = [matrix_plan(w.shape[0], w.shape[1], "weights", width, height, labels, t, font, colorbar, bool(x))
+             for w, t, x in zip(weights, titles, xl)]
+    return write_figures(engine, weights, plans, paths, quality, subsampling, entropy)

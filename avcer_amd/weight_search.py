@@ -212,3 +212,57 @@ def get_weights_v_model(engine, weights, ground_truth, predictions):
 def get_weights_av_model(engine, weights, ground_truth, predictions):
     """data/utils.py:188-209: [w_static, w_dynamic, w_audio] from the grid weights^3, or [0, 0, 0]."""
     return _grid_model(engine, weights, ground_truth, predictions, 3)
+
+
+# --------------------------------------------------------------------------- the figures of the fitted weights
+WEIGHT_FIGURE_LABELS = (("VS", "VD", "A"), ("Ne", "An", "Di", "Fe", "Ha", "Sa", "Su", "Mo"))  # get_weights_matrices.py:20,43,66
+# models, audio classes -> file stem, title, figsize in inches (100 pixels each), x_labels    (get_weights_matrices.py:18-72)
+WEIGHT_FIGURES = {(2, None): ("weights1_video", "Weights for video modality fusion", (6, 4), False),
+                  (3, 7): ("weights1_av_7", "Weights for audio (7cl) and video modality fusion", (6, 6), False),
+                  (3, 8): ("weights1_av_8", "Weights for audio (8cl) and video modality fusion", (6, 6), True)}
+
+
+def weight_figure_matrix(weights_1, weights_2) -> np.ndarray:
+    """What get_weights_matrices.py plots: weights_1 [M, 7] (a row per model, as the searches return it) with weights_2 [M] as an
+    eighth column "Mo" -- the script's 8 x M table, transposed as it transposes it."""
+    w1, w2 = np.asarray(weights_1, dtype=np.float64), np.asarray(weights_2, dtype=np.float64).reshape(-1)
+    if w1.ndim != 2 or w1.shape[1] != 7 or w2.shape[0] != w1.shape[0] or w1.shape[0] not in (2, 3):
+        raise ValueError(f"weight figures: weights_1 [M, 7] and weights_2 [M] of M = 2 or 3 models, got {w1.shape} and {w2.shape}")
+    return np.concatenate([w1, w2[:, None]], axis=1)
+
+
+def write_weight_figures(engine, weights_1=None, weights_2=None, save_dir=".", audio_classes: int = 8, quality: int = 95,
+                         subsampling: int = 2, entropy: str = "device"):
+    """get_weights_matrices.py:18-70 through figures.write_weights_matrices: the figure of fitted weights -- `weights_1` [M, 7] and
+    `weights_2` [M] as get_weights_prob_model and get_weights_v_model / get_weights_av_model return them -- under the script's
+    labels, title, size and file stem for that model set: M = 2 "weights1_video" (600 x 400, no x labels), M = 3 "weights1_av_7"
+    (600 x 600, no x labels) or, with audio_classes=8, "weights1_av_8" (600 x 600, x labels).  With both weights None: the
+    script itself, its three figures from the tables on record in fusion.py (WEIGHTS_V_*, WEIGHTS_AV7_*, WEIGHTS_AV_*); the two
+    600 x 600 figures share one draw call, the 600 x 400 one has its own.  The reference names its files `.pdf`; this project
+    writes no PDF, so the stems are kept and the files are `.jpg`.  Returns the paths, in the script's order."""
+    import os
+
+    from . import figures, fusion
+
+    if (weights_1 is None) != (weights_2 is None):
+        raise ValueError("weight figures: weights_1 and weights_2 are given together, or neither")
+    if weights_1 is None:
+        sets = [(fusion.WEIGHTS_V_1, fusion.WEIGHTS_V_2, None), (fusion.WEIGHTS_AV7_1, fusion.WEIGHTS_AV7_2, 7),
+                (fusion.WEIGHTS_AV_1, fusion.WEIGHTS_AV_2, 8)]
+    else:
+        sets = [(weights_1, weights_2, None if len(weights_2) == 2 else int(audio_classes))]
+    jobs = []
+    for w1, w2, cls in sets:
+        m = weight_figure_matrix(w1, w2)
+        if (len(m), cls) not in WEIGHT_FIGURES:
+            raise ValueError(f"weight figures: audio_classes is 7 or 8, not {cls!r}")
+        stem, title, (fw, fh), x_labels = WEIGHT_FIGURES[len(m), cls]
+        jobs.append((m, os.path.join(os.fspath(save_dir), stem + ".jpg"), title, x_labels, (100 * fw, 100 * fh)))
+    for size in sorted({j[4] for j in jobs}):
+        group = [j for j in jobs if j[4] == size]
+        labels = (WEIGHT_FIGURE_LABELS[0][:len(group[0][0])], WEIGHT_FIGURE_LABELS[1])
+        if any(len(j[0]) != len(group[0][0]) for j in group):
+            raise ValueError("weight figures: figures of one size share their row labels")
+        figures.write_weights_matrices(engine, [j[0] for j in group], labels, [j[1] for j in group], [j[2] for j in group], size[0], size[1],
+                                       True, [j[3] for j in group], None, quality, subsampling, entropy)
+    return [j[1] for j in jobs]
