@@ -676,6 +676,31 @@ class Engine:
                                                     int(x.shape[1]), int(n_frames), _ptr(out), _ptr(cnt), self._stream()))
         return out, cnt
 
+    def window_votes(self, logits, targets, file_off, out=None):
+        """Softmax, argmax and the per-file majority vote of a corpus's window logits in one launch (include/avcer_hip.h
+        avcer_window_votes; common_utils.py:74-108).  logits [n, c] (2 <= c <= 8), targets [n], file_off [F + 1]: a HOST integer
+        array, the prefix offsets of the files' windows (0 first, ascending, n last).  Returns (probs f32 [n, c], pred i32 [n],
+        file_pred i32 [F], file_target i32 [F], file_onehot i32 [F, c]) on the device (`out`: write into these five tensors instead).
+        Shapes that disagree raise ValueError; limits are the library's (AvcerError).  No host synchronisation."""
+        x = self._dev(logits, torch.float32)
+        t = self._dev(targets, torch.int32)
+        off = np.asarray(file_off, dtype=np.int64).reshape(-1)
+        if x.dim() != 2 or t.dim() != 1 or int(t.shape[0]) != int(x.shape[0]):
+            raise ValueError(f"window_votes: logits [n, c] and targets [n] expected, got {tuple(x.shape)} and {tuple(t.shape)}")
+        n, c, nf = int(x.shape[0]), int(x.shape[1]), int(off.shape[0]) - 1
+        if nf < 1 or off[0] != 0 or off[-1] != n or (np.diff(off) < 0).any():
+            raise ValueError(f"window_votes: file_off must ascend from 0 to {n} over at least one file")
+        shapes = ((n, c), (n,), (nf,), (nf,), (nf, c))
+        dtypes = (torch.float32,) + (torch.int32,) * 4
+        if out is None:
+            out = tuple(self._new(*s, dtype=d) for s, d in zip(shapes, dtypes))
+        elif len(out) != 5 or any(tuple(o.shape) != s or o.dtype != d or not o.is_contiguous() for o, s, d in zip(out, shapes, dtypes)):
+            raise ValueError(f"window_votes: out must be five contiguous tensors of shapes {shapes}")
+        dev_off = torch.from_numpy(off.astype(np.int32)).to(self.device, non_blocking=True)
+        self._check(self.lib.avcer_window_votes(self.ctx, _ptr(x), _ptr(t), _ptr(dev_off), n, c, nf, *(_ptr(o) for o in out),
+                                                self._stream()))
+        return tuple(out)
+
     def face_decode(self, loc, conf, landms, priors, image_size, variance=(0.1, 0.2)):
         """RetinaFace head outputs [P,4], [P,2], [P,10] + priors [P,4] -> dets [P,15] in pixels (before filtering)."""
         loc, conf = self._dev(loc, torch.float32), self._dev(conf, torch.float32)

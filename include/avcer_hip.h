@@ -105,7 +105,9 @@ enum {
  *      trues / preds tables of the weight search, and a model or fusion scored on them) joined under 8 the same way: three more
  *      symbols, nothing that existed changed.
  *      avcer_dib_frames (uncompressed BGR video of an AVI file unpacked into the frame batch) joined under 8 the same way: one
- *      more symbol, nothing that existed changed. */
+ *      more symbol, nothing that existed changed.
+ *      avcer_window_votes (the audio model over a corpus: softmax, argmax and per-file majority vote of the window logits) joined
+ *      under 8 the same way: one more symbol, nothing that existed changed. */
 #define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
@@ -870,6 +872,31 @@ int avcer_eval_tables(avcer_ctx* ctx, const double* rows, const int32_t* keys, i
 #define AVCER_EVAL_CE_MASK 4
 int avcer_eval_confusion(avcer_ctx* ctx, const double* tables, const int32_t* labels, int64_t n, int m, const double* w1_host,
                          const double* w2_host, int compound, int32_t* pred, int64_t* cm, avcer_stream_t stream);
+
+/* The audio model over a labelled corpus, the reduction behind it: window-wise majority voting grouped by file.
+ *   ref: src/audio/utils/common_utils.py:74-108 (majority_voting) behind the softmax of src/audio/test_c_audio.py:48
+ * logits f32 [n, c] (2 <= c <= AVCER_VOTES_MAX_CLASSES): the windows of all files one behind the other; targets i32 [n]; file_off
+ * i32 [n_files + 1]: prefix offsets of the files' windows, file_off[0] = 0, ascending, file_off[n_files] = n.  All DEVICE pointers.
+ * Per window i, in float32, every operation rounded on its own:
+ *   a = the first index of the maximum of logits[i], a NaN counting as the maximum (np.argmax); m = that maximum;
+ *   e[k] = expf(logits[i][k] - m);  s = ((e[0] + e[1]) + ..) + e[c-1];  probs[i][k] = e[k] / s;  pred[i] = a.
+ *   The argmax is taken on the logits: the softmax is monotone, so it is the argmax of the probabilities wherever those differ.
+ * Per file f, over its windows [file_off[f], file_off[f+1]): the counts of pred and of targets; file_pred[f] / file_target[f] =
+ * the most frequent value, the SMALLEST of several equally frequent ones (pd.Series.mode(x)[0]); file_onehot[f][k] = (k ==
+ * file_pred[f]).  Targets are counted in AVCER_VOTES_TARGET_MIN <= t < c (-2: a corpus without labels, -1: an unlabelled frame
+ * run); one outside that range is counted nowhere.  A file without windows (or without a counted target) gets -1, and a zero row.
+ * Outputs: probs f32 [n, c], pred i32 [n], file_pred i32 [n_files], file_target i32 [n_files], file_onehot i32 [n_files, c].
+ * One launch; one wave per file, a lane per window and 64 windows per step, the counts in registers and a shuffle tree behind
+ * them; plain vector stores, no atomics.  Offsets are clamped to [0, n] before they address anything; a window no file covers is
+ * not written.  Limits (AVCER_EINVAL beyond them): 1 <= n_files <= AVCER_VOTES_MAX_FILES, 0 <= n <= AVCER_VOTES_MAX_WINDOWS,
+ * 2 <= c <= AVCER_VOTES_MAX_CLASSES.  No host synchronisation. */
+#define AVCER_VOTES_MAX_CLASSES 8
+#define AVCER_VOTES_TARGET_MIN (-2)
+#define AVCER_VOTES_MAX_FILES 16777216
+#define AVCER_VOTES_MAX_WINDOWS 268435455LL
+int avcer_window_votes(avcer_ctx* ctx, const float* logits, const int32_t* targets, const int32_t* file_off, int64_t n, int c,
+                       int n_files, float* probs, int32_t* pred, int32_t* file_pred, int32_t* file_target, int32_t* file_onehot,
+                       avcer_stream_t stream);
 
 /* The contraction kernel itself (implicit-GEMM convolution with fused epilogue), exported for kernel-level
  * parity tests and micro-benchmarks:  Y[m, n] = act(scale[n] * sum_k A[m,k] * W[n,k] + bias[n] (+ R[m,n]))
