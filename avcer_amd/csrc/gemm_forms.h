@@ -1,5 +1,5 @@
 // What avcer_conv_gemm's `dtype` means, which form of the contraction can take a shape and which form and tile is preferred: one
-// statement for the launcher (gemm.hip) and the networks (api.hip Net::gemm).  Host only, nothing of HIP (tests/gemm_forms_driver.cpp).
+// statement for the launcher (gemm.hip) and the networks (net.h Net::gemm).  Host only, nothing of HIP (tests/gemm_forms_driver.cpp).
 #pragma once
 #include <algorithm>
 

@@ -194,7 +194,7 @@ def test_front_and_back_pass_sizes_do_not_show_in_any_result(engine_static):
 
 @pytest.mark.parametrize("n", [33, 256, 301, 1100])
 def test_two_lane_split_of_mid_sized_calls_is_bit_identical(engine_static, n):
-    """avcer_static_forward runs calls of 32-2048 frames as two half-batches on two HIP streams (api.hip run_two_lanes;
+    """avcer_static_forward runs calls of 32-2048 frames as two half-batches on two HIP streams (net.h run_two_lanes;
     BASELINE config 2 is 256 frames; 1100 frames: each lane runs its own front / back passes).  The split must not show: serial (avcer_set_static_lanes(1)) and two-lane results are
     equal bit for bit, an odd count splits 151 + 150, and the caller's stream sees the second lane's outputs (the join)."""
     eng = engine_static

@@ -235,3 +235,42 @@ def test_run_inference_with_the_mnet_detector(sd_mnet, engine, sd_static, sd_dyn
             np.testing.assert_array_equal(a[key], b[key])
     finally:
         e.close()
+
+
+# ---- 9
+NECK_TAPS = ("body1", "body2", "body3", "fpn1", "fpn2", "fpn3", "ssh1")
+
+
+@pytest.fixture(scope="module")
+def neck_ref(sd_mnet):
+    """Two 75 x 101 frames and the taps of the restatement in float64 and in f32 on the CPU, NHWC like the library's."""
+    frames = synth.video_frames(75, 2, 75, 101)
+    t64, t32 = {}, {}
+    mnet_ref.mnet_forward64(sd_mnet, frames, t64)
+    mnet_ref.mnet_forward(sd_mnet, torch.cat([mnet_ref.preprocess(f) for f in frames]), t32)
+    nhwc = lambda taps: {k: taps[k].permute(0, 2, 3, 1).contiguous().double() for k in NECK_TAPS}
+    return frames, nhwc(t64), nhwc(t32)
+
+
+@pytest.mark.parametrize("mode,mname", MODES)
+def test_neck_taps_against_float64(eng, neck_ref, mode, mname):
+    """The body's three outputs, the pyramid and level 1's SSH output (csrc/detect.hip run_neck), tap by tap against float64,
+    both frames in full.  75 x 101 frames: pyramid extents 10 x 13, 5 x 7 and 3 x 4, odd at every level, and nearest-upsample
+    ratios 5/10 and 3/5 of which one is no whole number.  Activations are NHWC f32 in both modes.  Gate, as in
+    test_dwsep_block_against_float64: max|err| / max|ref| of a tap within 4 x that of the f32 CPU restatement."""
+    frames, t64, t32 = neck_ref
+    assert [tuple(t64[k].shape[1:3]) for k in ("fpn1", "fpn2", "fpn3")] == [(10, 13), (5, 7), (3, 4)]
+    bad = []
+    for name in NECK_TAPS:
+        ref = t64[name]
+        dst = eng.debug_tap("face_" + name, ref.numel())
+        eng.face_forward(frames, mode)
+        assert eng.debug_tap_copied() == ref.numel() * 4, name
+        scale = float(ref.abs().max())
+        e32 = float((t32[name] - ref).abs().max()) / scale
+        err = float((dst.cpu().view(ref.shape).double() - ref).abs().max()) / scale
+        print(f"mnet tap {name} {mname}: library {err:.2e}  f32 cpu {e32:.2e}")
+        if not err <= 4 * e32:
+            bad.append((name, err, e32))
+    assert not bad, bad
+    assert eng.x3_overflow_count() == 0

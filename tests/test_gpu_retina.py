@@ -108,7 +108,7 @@ def test_batch_equals_frame_by_frame(engine_face, sd_retina):
 
 @pytest.mark.parametrize("mode", [MODE_F16X3, MODE_FP32])
 def test_two_lane_detector_batches_are_bit_identical(engine_face, mode):
-    """Batches of at least 16 frames run as two lanes (api.hip run_two_lanes: the halves on two streams, equal passes inside a
+    """Batches of at least 16 frames run as two lanes (net.h run_two_lanes: the halves on two streams, equal passes inside a
     lane); 21 frames of 96 x 128 split 11 + 10.  Same bits as on one lane, and the outputs are complete on the caller's stream."""
     frames = synth.video_frames(21, 21, 96, 128)
     try:

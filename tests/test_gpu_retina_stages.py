@@ -1,5 +1,5 @@
 """RetinaFace-R50 detector stage by stage against the float64 oracle (oracle/retina.py retina_forward64), at 1080p among other
-sizes, and across the pass and lane boundaries of the benchmark's call and of 1080p batches (api.hip face_forward_lane /
+sizes, and across the pass and lane boundaries of the benchmark's call and of 1080p batches (detect.hip face_forward_lane /
 face_forward_impl).  A fresh Engine per module: passes of up to 273 frames grow the detector's workspace slots to tens of GB, which
 the session engine must not keep."""
 import re
@@ -17,8 +17,8 @@ from oracle import retina as orf
 
 pytestmark = pytest.mark.gpu
 
-PASS_LIMIT = 0xF0000000        # api.hip face_forward_lane: every gathered operand of a pass stays below the 4 GiB descriptor range
-TAIL_PAIR_ROWS = 16384         # api.hip kTailPairRows: stage-3 tails of more positions run bneck_tail2_kernel
+PASS_LIMIT = 0xF0000000        # detect.hip face_forward_lane: every gathered operand of a pass stays below the 4 GiB descriptor range
+TAIL_PAIR_ROWS = 16384         # net.h kTailPairRows: stage-3 tails of more positions run bneck_tail2_kernel
 MODES = {MODE_FP32: "fp32", MODE_F16X3: "x3"}
 
 
@@ -84,7 +84,7 @@ def _edges(schedules):
 
 # ------------------------------------------------------------------------------------------------------------ stage taps
 def _tap_list(mode, stage3_rows):
-    """(library tap, oracle tap) pairs the forward of `mode` fills (api.hip run_bneck_stage / face_forward_lane): in x3 mode the
+    """(library tap, oracle tap) pairs the forward of `mode` fills (api.hip run_bneck_stage / detect.hip face_forward_lane): in x3 mode the
     chains of stages 1-2 tap their block output and the next block's conv1 output, the stage-3 tails only when bneck_tail2_kernel
     runs (more than TAIL_PAIR_ROWS positions); conv2 of layer1.0 is a tensor of its own only off the chain."""
     x3 = mode == MODE_F16X3

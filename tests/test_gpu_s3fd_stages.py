@@ -1,4 +1,4 @@
-"""The S3FD detector launch by launch against float64 (api.hip face_s3fd_forward_lane): every one of its 24 launches in front of
+"""The S3FD detector launch by launch against float64 (detect.hip face_s3fd_forward_lane): every one of its 24 launches in front of
 the heads -- the stem, 18 contractions, 5 pools -- is tapped whole for two 239 x 431 frames, in the exact-f32 and the x3 mode, and
 
   (a) compared with the float64 oracle (tests/s3fd_ref.py s3fd_forward64), max|err| / max|ref| per tap.  The bound is 8 x what the
@@ -281,7 +281,7 @@ def test_heads_and_outputs(eng, frames, oracle, dev):
 
 # ---------------------------------------------------------------------------------------------------------------- (e)
 def max_frames(h, w):
-    """api.hip face_s3fd_max_frames: conv1's maps of a pass (64 channels at full resolution, 4 bytes each) stay below 1.5 GiB."""
+    """detect.hip face_s3fd_max_frames: conv1's maps of a pass (64 channels at full resolution, 4 bytes each) stay below 1.5 GiB."""
     return max(1, 0x60000000 // (h * w * 64 * 4))
 
 

@@ -65,7 +65,7 @@ pytestmark = pytest.mark.gpu
 MODES = {MODE_FP32: "fp32", MODE_F16X3: "x3", MODE_BF16: "bf16"}
 F32_GRADE = (MODE_FP32, MODE_F16X3)
 U = 2.0 ** -24                      # unit roundoff of float32
-TAIL_PAIR_ROWS = 16384              # api.hip kTailPairRows
+TAIL_PAIR_ROWS = 16384              # net.h kTailPairRows
 CEILING = 5e-5
 N_B = 85                            # case B: 85 * 14 * 14 = 16660 stage-3 positions
 ALIASES = {"out:stem.w": "stem_conv"}

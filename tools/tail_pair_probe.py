@@ -2,7 +2,7 @@
 """Where does the stage-3 tail (conv3 + residual + next conv1) as TWO contractions beat the fused bneck_tail2_kernel?  (lab)
 Static CNN, x3 mode, frames per call, always fused against always the pair, both timed in one process (one context each).
 The knob it drives (AVCER_LAB_TAIL_PAIR_ROWS, read at context creation) existed in a lab build only: the product has the
-measured threshold as a constant (api.hip kTailPairRows).  Result: profiles/experiments/r05_tail_pair_probe.txt
+measured threshold as a constant (net.h kTailPairRows).  Result: profiles/experiments/r05_tail_pair_probe.txt
 """
 import os
 import sys
