@@ -352,7 +352,7 @@ const FaceKind kFaceKinds[3] = {
     {"S3FD", face_s3fd_forward_lane, face_s3fd_max_frames, [](int H, int W) { return s3fd_geom(H, W).priors; }, false, false},
 };
 
-// Batches of at least 16 frames run as TWO lanes, like the static CNN (api.hip static_forward_impl): the frames' halves on two
+// Batches of at least 16 frames run as TWO lanes, like the static CNN (visual.hip static_forward_impl): the frames' halves on two
 // streams with a workspace each, passes of equal size within a lane.  The detector's late grids are small too -- stage 4 is
 // 12 x 20 positions per 640 x 360 frame, pyramid level 3 the same -- and a pass of 273 frames (the 4 GiB range of layer 1's output)
 // leaves partial rounds that the other lane's launches fill.  Bit-identical (a frame's result does not depend on its batch:

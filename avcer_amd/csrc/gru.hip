@@ -5,7 +5,7 @@
 //     g = W_hh h_{t-1}                        [768] per window
 //     r = sigmoid(xp_r + g_r + b_hr),  z = sigmoid(xp_z + g_z + b_hz),  n = tanh(xp_n + r (g_n + b_hn)),
 //     h_t = (1 - z) n + z h_{t-1},  h_0 = 0   (b_hn sits inside the r product: the two bias vectors cannot be merged)
-// and it depends on the step before: the LSTM's way (one contraction + one cell launch per step, api.hip) would be ~800 dependent
+// and it depends on the step before: the LSTM's way (one contraction + one cell launch per step, visual.hip) would be ~800 dependent
 // launches per call here.
 //
 // Work split.  Windows are independent, so a block owns a tile of 16 windows -- the N of the 16 x 16 MFMA with the weights as

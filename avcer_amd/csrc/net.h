@@ -1,11 +1,34 @@
-// Host-side declarations a network driver needs: a forward pass's Net, the contraction descriptors, the ResNet-50 body driver and
-// the two-lane fork / join.  Included by api.hip (which defines the functions declared here) and detect.hip only: host code, and
-// no translation unit that holds a kernel sees it.
+// Host-side declarations a network driver needs: a forward pass's Net, a tensor's operand pair, the contraction descriptors, the
+// ResNet-50 body driver and the two-lane fork / join.  Included by api.hip (which defines Net's methods, the descriptors and the loaders),
+// visual.hip (which defines run_bneck_stage), audio.hip and detect.hip only: host code, and no translation unit that holds a kernel sees it.
 #pragma once
 
 #include "common.h"
 
 #include <algorithm>
+
+// A tensor as f32 and once more in an operand storage (bf16, or sp32 pairs).  `op` is null where the pass keeps no such copy.
+struct Pair { float* f; void* op; };
+struct Operand { const void* p; int kind; };  // what a contraction reads, and the KIND_* to pass with it
+// The copy of `t` that a reader of storage `kind` takes: the ONE place that chooses between a tensor's two copies
+inline Operand operand(Pair t, int kind) { return {kind == KIND_F32 ? (const void*)t.f : t.op, kind}; }
+// A tensor that exists once, in storage `kind` (a LayerNorm output that only a contraction reads): its other half is null, so it is
+// read back with operand(., kind) of that same kind only
+inline Pair only(void* p, int kind) { return kind == KIND_F32 ? Pair{(float*)p, nullptr} : Pair{nullptr, p}; }
+// `t` from its element `elems` on; `es`: bytes per element of the operand storage
+inline Pair advance(Pair t, size_t elems, size_t es) { return {t.f + elems, t.op ? (char*)t.op + elems * es : nullptr}; }
+// Carves the operand half of a pair, of storage `kind`: the region is taken in every mode, but a kind that reads and writes f32 gets
+// no `op`.  carve_pair: both halves, where they lie side by side; elsewhere `f` is carved on its own, where it always was
+inline void* carve_op(Arena& ar, size_t bytes, int kind) {
+    void* op = ar.get(bytes);
+    return kind == KIND_F32 ? nullptr : op;
+}
+inline Pair carve_pair(Arena& ar, size_t f_bytes, size_t op_bytes, int kind) {
+    float* f = ar.get<float>(f_bytes);
+    return {f, carve_op(ar, op_bytes, kind)};
+}
+// device bytes of one split-fp16 weight copy: the data, its scale trailer (split_dev.h), rounded to 256 (api.hip)
+size_t split_bytes(size_t numel);
 
 // One forward pass of model `m` on stream `st`: looks tensors up by name, issues the contractions, keeps the first error
 struct Net {
@@ -25,6 +48,8 @@ struct Net {
     // shape selects the kernel instantiation (avcer_conv_gemm dtype: gemm_forms.h choose_gemm)
     void gemm(avcer_conv_desc d, const std::string& wname, const float* scale, const float* bias, const void* x,
               const void* res, void* y, int akind, int okind, const void* x2 = nullptr);
+    void gemm(avcer_conv_desc d, const std::string& wname, const float* scale, const float* bias, Operand x, const void* res, void* y,
+              int okind) { gemm(d, wname, scale, bias, x.p, res, y, x.kind, okind); }
     void chk(int r) { if (err == AVCER_OK && r != AVCER_OK) err = r; }
     // debug tap: raw copy of min(requested, available) bytes of an intermediate tensor
     void tap(const char* name, const void* src, size_t bytes);
@@ -50,7 +75,7 @@ int load_blob(avcer_ctx* ctx, Model& m, const void* blob, size_t nbytes);
 // (`bf16_form` = false: a pass that runs the bf16 mode on its f32 kernels and prepares no bf16 copies)
 int begin_forward(avcer_ctx* ctx, const char* who, Model& m, int mode, bool bf16_form, hipStream_t st);
 
-// The recognition CNN (api.hip static_forward_lane) and the RetinaFace detector (detect.hip face_forward_lane) run the same
+// The recognition CNN (visual.hip static_forward_lane) and the RetinaFace detector (detect.hip face_forward_lane) run the same
 // ResNet-50 body on the same kernels.  Trunk is a body between stages: the activation X on an h x w grid of cin channels per
 // frame, the ping-pong pair a block writes into (the one X does not occupy), the buffers of a block's conv1 / conv2 outputs, and
 // the body's three properties (run_bneck_stage): where the stride lives, whether the chain gets the fragment-order conv2
@@ -66,7 +91,7 @@ struct Trunk {
     const char* tap;
 };
 
-// Blocks [b_begin, b_end) of stage li (0-based) on nb frames; the last of them writes to `last_out` when given (api.hip)
+// Blocks [b_begin, b_end) of stage li (0-based) on nb frames; the last of them writes to `last_out` when given (visual.hip)
 void run_bneck_stage(Net& net, Trunk& t, int li, int b_begin, int b_end, int nb, void* last_out, const std::string& end_tap);
 
 // The two lanes of a call (static_forward_impl, face_forward_impl): lane(1, s) on the context's second stream s, forked from `st`

@@ -1,4 +1,4 @@
-"""The audio model (api.hip avcer_audio_forward) launch by launch against the float64 oracle (oracle/audio.py
+"""The audio model (audio.hip avcer_audio_forward) launch by launch against the float64 oracle (oracle/audio.py
 expr_model_v3_forward64): every debug tap of the forward, in the exact-f32 and the x3 mode, at six window lengths from the
 shortest to the longest accepted one; local checks of the small kernels from the library's own tapped inputs; a production-size
 call (130 windows: the weights-direct contraction form and the 128-window pass boundary).
@@ -61,7 +61,7 @@ def sd64(sd_audio):
 
 # ------------------------------------------------------------------------------------------------------------ tap plumbing
 def _is_split(name, mode):
-    """Operand-typed tensors are sp32 pairs in the x3 mode (api.hip: extractor activations, LN outputs, contexts, FFN hidden,
+    """Operand-typed tensors are sp32 pairs in the x3 mode (audio.hip: extractor activations, LN outputs, contexts, FFN hidden,
     pos_in, x + PE); everything else, and every tap of the f32 mode, is f32."""
     return mode == MODE_F16X3 and (name in ("conv0", "extract", "pos_in") or name.startswith(("ln:", "att:", "pe:"))
                                    or name.endswith(".ff1.w"))
@@ -465,7 +465,7 @@ def test_production_size_call_and_the_pass_boundary(sd_audio, sd64):
     conv_gemm_wd_kernel, the form the benchmark runs) and a pass of 2.  A debug tap is one-shot (Net::tap disarms it after its
     first copy), so after such a call it holds the FIRST pass: windows 0 and 127 of it are compared with the float64 oracle under
     the bounds above, as are windows 0, 63 and 127 of a 128-window call.  The second pass is held at the logits: rows 128 and 129
-    against the oracle, rows 126 .. 129 bit for bit against a call of those four windows."""
+    against the oracle, rows 126 .. 129 of logits and features bit for bit against a call of those four windows."""
     t_start = time.time()
     eng = Engine(0)
     try:
@@ -503,9 +503,10 @@ def test_production_size_call_and_the_pass_boundary(sd_audio, sd64):
                 print(f"{MODES[mode]} {n} windows, windows {rows} of the first pass:", {k: f"{v:.1e}" for k, v in rels.items()})
                 bad = {k: v for k, v in rels.items() if v >= TAP_BOUND[mode][_family(k)]}
                 assert not bad, (MODES[mode], n, bad)
-            lg = eng.audio_forward(wav_dev, True, mode)
-            four = eng.audio_forward(wav_dev[126:130], True, mode)
+            lg, feats = eng.audio_forward(wav_dev, True, mode, return_features=True)
+            four, four_feats = eng.audio_forward(wav_dev[126:130], True, mode, return_features=True)
             assert torch.equal(lg[126:130], four), MODES[mode]
+            assert torch.equal(feats[126:130], four_feats), MODES[mode]  # the second pass's features land behind the first's
             want = ref["logits"][[0, 2, 3, 4]]
             d = (lg[[0, 127, 128, 129]].cpu().double() - want).abs().max().item()
             print(f"{MODES[mode]} 130 windows: rows 0, 127, 128, 129 max|dlogit| {d:.2e}")

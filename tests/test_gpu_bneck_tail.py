@@ -65,7 +65,7 @@ def test_bneck_tail_vs_float64(engine, m):
 
 @pytest.mark.parametrize("m", SIZES)
 def test_bneck_tail_is_bit_identical_to_the_pair(engine, m):
-    """Below kTailPairRows positions run_bneck_stage (csrc/api.hip) issues the same two contractions as two avcer_conv_gemm
+    """Below kTailPairRows positions run_bneck_stage (csrc/visual.hip) issues the same two contractions as two avcer_conv_gemm
     launches and states that they are the same arithmetic: conv3 with the residual x and ReLU, then the next block's conv1 on OUT,
     dtype 5, no scale vector.  Both raw int16 outputs must be equal."""
     t2, x, w3, b3, w1n, b1n = args = _device_case(engine, m)

@@ -156,7 +156,7 @@ def oa_softmax(x):
 
 
 def test_static_call_larger_than_one_back_pass(engine, sd_static):
-    """A single static call of more than 2048 frames (api.hip: the outer s0 loop over back passes): 2 back passes, 3 front
+    """A single static call of more than 2048 frames (visual.hip: the outer s0 loop over back passes): 2 back passes, 3 front
     passes.  Rows are compared with the same frames run in separate smaller calls -- bit-identical, since no kernel's
     accumulation order depends on the batch -- and a sample of rows with the CPU oracle."""
     engine.load_static(sd_static)

@@ -63,7 +63,7 @@ def test_batch_and_rgb_against_oracle(engine_face, sd_retina):
 
 @pytest.mark.parametrize("h,w,n", [(150, 214, 3), (70, 33, 2), (75, 101, 2), (360, 640, 2)])
 def test_x3_fused_body_against_oracle_and_fp32_mode(engine_face, sd_retina, h, w, n):
-    """The x3 mode runs the body's stride-1 bottlenecks on the fused chain / tail kernels of the recognition CNN (api.hip
+    """The x3 mode runs the body's stride-1 bottlenecks on the fused chain / tail kernels of the recognition CNN (visual.hip
     run_bneck_stage): odd extents (38 x 54 and 19 x 27 positions per frame in stages 1-2), a frame narrower than one tile row, and
     the bench's 640 x 360 -- against the oracle where it finishes in seconds, against the exact-f32 mode of the library otherwise."""
     frames = synth.video_frames(41, n, h, w)

@@ -84,7 +84,7 @@ def _edges(schedules):
 
 # ------------------------------------------------------------------------------------------------------------ stage taps
 def _tap_list(mode, stage3_rows):
-    """(library tap, oracle tap) pairs the forward of `mode` fills (api.hip run_bneck_stage / detect.hip face_forward_lane): in x3 mode the
+    """(library tap, oracle tap) pairs the forward of `mode` fills (visual.hip run_bneck_stage / detect.hip face_forward_lane): in x3 mode the
     chains of stages 1-2 tap their block output and the next block's conv1 output, the stage-3 tails only when bneck_tail2_kernel
     runs (more than TAIL_PAIR_ROWS positions); conv2 of layer1.0 is a tensor of its own only off the chain."""
     x3 = mode == MODE_F16X3

@@ -1,4 +1,4 @@
-"""The recognition branch launch by launch against float64: the static ResNet-50 (api.hip static_forward_lane) against
+"""The recognition branch launch by launch against float64: the static ResNet-50 (visual.hip static_forward_lane) against
 oracle/video.py resnet50_forward64 and the two-layer LSTM (dynamic_forward_impl) against lstm_forward64, every debug tap of
 both forwards; local checks of avgpool_kernel, fc1, small_linear_kernel (fc2 + softmax) and lstm_cell_kernel from the library's
 OWN tapped inputs.

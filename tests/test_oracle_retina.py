@@ -39,7 +39,7 @@ def test_intermediate_statistics(golden, sd_retina):
 
 
 def _tap_names():
-    """Every tensor the library can tap on the detector (detect.hip face_forward_lane / api.hip run_bneck_stage), "face_" prefix dropped."""
+    """Every tensor the library can tap on the detector (detect.hip face_forward_lane / visual.hip run_bneck_stage), "face_" prefix dropped."""
     names = {"pool", "l1b0_c2", "layer1", "body1", "body2", "body3", "lat1", "lat2", "lat3", "sum2", "fpn2", "fpn1", "ssh1"}
     for li, (_, blocks, _) in enumerate(orf.STAGES, start=1):
         names |= {f"blk{li}_{b}" for b in range(blocks)} | {f"c1:l{li}.{b}." for b in range(blocks)}
