@@ -148,7 +148,7 @@ int ws_carve(avcer_ctx* ctx, int slot, const char* what, const Carve& carve) {
 }
 
 // PIL's NEAREST resize to 224 (data/utils.py:34): the source index of output index `o` along an axis of `len` source pixels.
-// The one statement of the rule: preprocess_kernel, crop_tiles_kernel (kernels.hip) and jpeg_tiles_kernel (jpeg.hip) call it.
+// The one statement of the rule: preprocess_kernel, crop_tiles_kernel (kernels.hip) and jpeg_tiles_kernel (jpeg_decode.hip) call it.
 __device__ __forceinline__ int nearest_src(int o, int len) { return min((int)(((double)o + 0.5) * ((double)len / 224.0)), len - 1); }
 
 // ---- gemm.hip

@@ -1,13 +1,13 @@
-// Self-synchronising Huffman decoding of a JPEG scan (avcer_jpeg_unpack, csrc/jpeg.hip): the pieces that the device kernel and its
+// Self-synchronising Huffman decoding of a JPEG scan (avcer_jpeg_unpack, csrc/jpeg_unpack.hip): the pieces that the device kernel and its
 // host statement avcer_jpeg_unpack_host share, which is every decision of the algorithm -- the byte classes of the marker pass and
 // where a classified byte goes, the derived Huffman table, the bit reader over the unstuffed bytes, the cut of a segment into
 // subsequences, where a subsequence lies and what it enters with, ONE subsequence's decode from an entry state, a round's step, the
 // write step with its marker check, the hand-over between units, the DC prediction's items and range check, the block-ordinal ->
 // storage mapping.  Everything is __host__ __device__, integer and free of barriers.  Written per side is only how the threads of a
-// unit run and combine: jpeg.hip's kernel loads 16 bytes a thread, scans across the workgroup, waits at barriers and takes the
+// unit run and combine: jpeg_unpack.hip's kernel loads 16 bytes a thread, scans across the workgroup, waits at barriers and takes the
 // smallest defect with atomicMin; the host statement loops over the "threads" with running sums and std::min.
 //
-// Semantics are those of Bits / decode_block / decode_scan in jpeg.hip, restated on the UNSTUFFED bytes of one segment (a restart
+// Semantics are those of Bits / decode_block / decode_scan in jpeg_decode.hip, restated on the UNSTUFFED bytes of one segment (a restart
 // interval, or the whole scan): bits behind the segment's end read as zero and cannot be consumed (`bad`).
 #pragma once
 
@@ -48,7 +48,7 @@ JS_HD int byte_class(int prev2, int prev, int cur, bool has_next, int next) {
 }
 
 // ------------------------------------------------------------------------------------------------ tables
-// One Huffman table as Bits::symbol reads it (jpeg.hip derive(), libjpeg's jpeg_make_d_derived_tbl)
+// One Huffman table as Bits::symbol reads it (jpeg_decode.hip derive(), libjpeg's jpeg_make_d_derived_tbl)
 struct DTab {
     uint16_t look[512];   // the next 9 bits -> (length << 8) | symbol, 0: the code is longer
     int32_t maxcode[17];  // largest code of each length, -1 where the length has none

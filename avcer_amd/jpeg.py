@@ -1,4 +1,4 @@
-"""JPEG face crops decoded behind a host entropy pass, and encoded in front of one (csrc/jpeg.hip, include/avcer_hip.h "JPEG
+"""JPEG face crops decoded behind a host entropy pass, and encoded in front of one (csrc/jpeg_*.hip, include/avcer_hip.h "JPEG
 face crops").  Decoding first; `encode_images` and its numpy statement `forward_numpy` are in the second half of this file.
 
 `decode_tiles` / `decode_canvas` take the bytes of n files.  One native host call parses the markers and Huffman-decodes every file
@@ -12,7 +12,7 @@ PIL lines of `video_pipeline.read_face_dir` unchanged; what PIL does with it (de
 Both functions also return, per file, which path served it: "device" or "pil".
 
 With entropy="device" the host parses the headers only (`scan_batch`), the files' entropy-coded bytes cross instead of the
-coefficients, and `Engine.jpeg_unpack` Huffman-decodes them on the device (csrc/jpeg.hip avcer_jpeg_unpack); tiles, canvas and paths
+coefficients, and `Engine.jpeg_unpack` Huffman-decodes them on the device (csrc/jpeg_unpack.hip avcer_jpeg_unpack); tiles, canvas and paths
 are the same.
 
 `decode_frames` is the same path for the frames of a Motion-JPEG video (avcer_amd/avi.py): whole frames of one size in BGR or
@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 OK, NOT_HANDLED = 0, 1
-R_NO_SPACE = 12  # csrc/jpeg.hip: the file's blocks did not fit the coefficient storage given
+R_NO_SPACE = 12  # csrc/jpeg.h: the file's blocks did not fit the coefficient storage given
 
 # struct avcer_jpeg_desc
 DESC = np.dtype([("status", "<i4"), ("reason", "<i4"), ("width", "<i4"), ("height", "<i4"), ("ncomp", "<i4"), ("hs", "<i4"),
@@ -140,7 +140,7 @@ def unpack_host(lib, data: np.ndarray, scan: np.ndarray, tabs: np.ndarray, desc:
 
 # ---------------------------------------------------------------------------------------------------- numpy statement (tests)
 def _idct_1d(v, shift):
-    """csrc/jpeg.hip idct_1d (libjpeg jidctint.c) along axis 0 of an int64 array [8, ...]."""
+    """csrc/jpeg.h idct_1d (libjpeg jidctint.c) along axis 0 of an int64 array [8, ...]."""
     z2, z3 = v[2], v[6]
     z1 = (z2 + z3) * 4433
     tmp2 = z1 + z3 * (-15137)
@@ -160,7 +160,7 @@ def _idct_1d(v, shift):
                      tmp10 - tmp3]) + r >> shift
 
 
-PAIR_MAX = 16383  # csrc/jpeg.hip IDCT_PAIR_MAX
+PAIR_MAX = 16383  # csrc/jpeg.h IDCT_PAIR_MAX
 
 
 def _plane(coeffs, qt, bw, bh):
@@ -197,7 +197,7 @@ def _chroma(p, w, h, hs, vs):
 
 
 def pixels_numpy(coeffs: np.ndarray, desc: np.ndarray):
-    """Kernels A and B of csrc/jpeg.hip stated in numpy (for the tests; not a product path): the coefficient storage and the DESC
+    """Kernels A and B of csrc/jpeg_decode.hip stated in numpy (for the tests; not a product path): the coefficient storage and the DESC
     records of avcer_jpeg_entropy_batch -> per file the RGB image u8 [h, w, 3], or None where the status is not OK or the range guard
     of kernel A fires (the device's flag)."""
     out = []
@@ -502,8 +502,8 @@ def decode_frames(engine, blobs, height: int, width: int, bgr: bool = True, entr
 # files (avcer_jpeg_write_batch: headers, Huffman coding) -- or, with entropy="device", the device does (avcer_jpeg_pack) and only
 # the files cross to the host.  The contract is byte-identity with
 # PIL.Image.fromarray(rgb).save(f, "JPEG", quality=quality, subsampling=subsampling) (libjpeg-turbo, standard Huffman tables).
-HEADER_BYTES = 623  # csrc/jpeg.hip: SOI, APP0, two DQT, SOF0, four DHT, SOS
-R_ENC_SIZE = 18  # csrc/jpeg.hip: an image of zero width or height, or of more than 65535 pixels a side
+HEADER_BYTES = 623  # csrc/jpeg.h: SOI, APP0, two DQT, SOF0, four DHT, SOS
+R_ENC_SIZE = 18  # csrc/jpeg.h: an image of zero width or height, or of more than 65535 pixels a side
 
 # libjpeg's jcparam.c: the two tables of the standard's annex K in natural order
 _STD_LUMA = np.array([16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87,
@@ -678,7 +678,7 @@ def _encode_rects(src, rects) -> np.ndarray:
 
 def _not_written(status, reason):
     i = int(np.nonzero(status != OK)[0][0])
-    return RuntimeError(f"image {i} was not written: reason {int(reason[i])} (csrc/jpeg.hip R_*)")
+    return RuntimeError(f"image {i} was not written: reason {int(reason[i])} (csrc/jpeg.h R_*)")
 
 
 def _pack_to_host(engine, st, coeffs, d_dev, n: int, blocks: int) -> list:

@@ -546,7 +546,7 @@ void avcer_tracker_destroy(avcer_tracker* tracker);
  * lossless / 12-bit files, four components, Adobe transform 0 or 2, other sampling factors, several scans, DNL, 16-bit tables,
  * bytes between segments, a bit stream that ends early, an undefined Huffman code, a coefficient index past 63, a wrong or
  * missing RSTn, a missing EOI, a dequantised coefficient outside int16, and a file whose blocks do not fit the storage given.
- * `reason` says which (csrc/jpeg.hip R_*; 12 = no space).  The caller decodes such a file some other way (avcer_amd/jpeg.py: PIL).
+ * `reason` says which (csrc/jpeg.h R_*; 12 = no space).  The caller decodes such a file some other way (avcer_amd/jpeg.py: PIL).
  *
  * avcer_jpeg_desc: one file.  bw / bh: blocks per component, padded to whole MCUs (a one-component file: ceil(w / 8), ceil(h /
  * 8)); qt: each component's quantisation table in natural order; hs / vs: the first component's sampling factors as the file
@@ -597,7 +597,7 @@ int avcer_jpeg_rgb(avcer_ctx* ctx, const int16_t* coeffs, int64_t n_blocks, cons
  * AVCER_JPEG_STD_TABLES (a bit of `hflags`): many Motion-JPEG producers omit the DHT segments; a Huffman table 0 or 1 that the scan
  *   references and no DHT segment of the file defined is then the table of that class and id of the standard's annex K (K.3 -
  *   K.6) -- the rule of libjpeg-turbo and of ffmpeg's mjpeg2jpeg filter.  A table the file defines is the file's own; ids 2 and 3
- *   have no standard table and stay reason 8.  csrc/jpeg.hip holds ONE statement of the four tables, the writer's.
+ *   have no standard table and stay reason 8.  csrc/jpeg.h holds ONE statement of the four tables, the writer's.
  * avcer_jpeg_entropy_batch_ex / avcer_jpeg_scan_batch_ex (below, beside avcer_jpeg_scan_batch): avcer_jpeg_entropy_batch /
  *   avcer_jpeg_scan_batch with `hflags` (0 or AVCER_JPEG_STD_TABLES; any other bit: AVCER_EINVAL); with hflags 0 they ARE those
  *   calls.  Host code and host pointers, ctx may be NULL.  The calls without the argument do not change: a file without DHT stays

@@ -1,5 +1,5 @@
 """Writes tests/golden/jpeg_encode.npz: small RGB images and the bytes PIL wrote for them (libjpeg-turbo, standard Huffman tables),
-the oracle of the JPEG encoder (csrc/jpeg.hip avcer_jpeg_forward / avcer_jpeg_write_batch, avcer_amd/jpeg.py).  Run on a CPU
+the oracle of the JPEG encoder (csrc/jpeg_encode.hip avcer_jpeg_forward / avcer_jpeg_write_batch, avcer_amd/jpeg.py).  Run on a CPU
 machine: `python tests/golden/make_jpeg_encode_golden.py`.
 
 Keys: `names` [m], `quality` [m], `subsampling` [m] (PIL's numbering: 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0), `rgb_<i>` u8 [h, w, 3] and

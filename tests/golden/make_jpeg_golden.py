@@ -1,5 +1,5 @@
 """Writes tests/golden/jpeg_crops.npz: JPEG byte strings PIL encoded and PIL's own decode of each (libjpeg-turbo), the oracle of
-the JPEG crop decoder (csrc/jpeg.hip, avcer_amd/jpeg.py).  Run on a CPU machine: `python tests/golden/make_jpeg_golden.py`.
+the JPEG crop decoder (csrc/jpeg_decode.hip, avcer_amd/jpeg.py).  Run on a CPU machine: `python tests/golden/make_jpeg_golden.py`.
 
 The GPU tests read this file and never call PIL's JPEG decoder for a supported case -- the libjpeg build of the machine they run
 on is not ours to assume.  Keys: `names` [m] (case labels), `handled` [m] bool (False: the four files that must fall back),

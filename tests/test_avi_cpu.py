@@ -1,5 +1,5 @@
 """Motion-JPEG AVI files on the host (avcer_amd/avi.py) and the annex-K default Huffman tables of the header pass
-(AVCER_JPEG_STD_TABLES, csrc/jpeg.hip): write_avi -> open_avi round trips, every refusal of the reader by name, truncation at
+(AVCER_JPEG_STD_TABLES, csrc/jpeg_decode.hip): write_avi -> open_avi round trips, every refusal of the reader by name, truncation at
 every byte, and frames whose DHT segments were cut out against the untouched files -- through the host entropy pass and through
 the host form of the device decoder, tolerance zero.  No device."""
 import ctypes

@@ -1,4 +1,4 @@
-"""The device half of the JPEG crop decoder (csrc/jpeg.hip avcer_jpeg_tiles / avcer_jpeg_rgb, avcer_amd/jpeg.py) against
+"""The device half of the JPEG crop decoder (csrc/jpeg_decode.hip avcer_jpeg_tiles / avcer_jpeg_rgb, avcer_amd/jpeg.py) against
 tests/golden/jpeg_crops.npz -- PIL's decode of each file, written on the machine that ran tests/golden/make_jpeg_golden.py.  For a
 file the decoder supports no test here calls PIL's JPEG decoder: expected tiles are PIL's NEAREST resize of the golden RGB array."""
 import io

@@ -1,4 +1,4 @@
-"""The JPEG encoder on the device (csrc/jpeg.hip avcer_jpeg_forward, avcer_amd/jpeg.py encode_images) and what is built on it
+"""The JPEG encoder on the device (csrc/jpeg_encode.hip avcer_jpeg_forward, avcer_amd/jpeg.py encode_images) and what is built on it
 (face_tiles.write_face_crops, heatmaps.write_heatmaps with an engine).  The kernel is held to its numpy statement
 (jpeg.forward_numpy, which tests/test_jpeg_encode_host.py holds to PIL's files) coefficient for coefficient, the files to the bytes
 PIL writes: tests/golden/jpeg_encode.npz for the fixtures, PIL's encoder on this machine elsewhere.  No case has a tolerance."""

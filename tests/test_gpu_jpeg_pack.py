@@ -1,4 +1,4 @@
-"""The entropy coder on the device (csrc/jpeg.hip avcer_jpeg_pack, Engine.jpeg_pack, jpeg.encode_images(entropy="device")) against
+"""The entropy coder on the device (csrc/jpeg_pack.hip avcer_jpeg_pack, Engine.jpeg_pack, jpeg.encode_images(entropy="device")) against
 its oracle, the host writer avcer_jpeg_write_batch (which tests/test_jpeg_encode_host.py holds to PIL's files): bytes, offsets and
 statuses are equal for the crafted set and the images of tests/jpeg_pack_cases.py (tests/test_jpeg_pack_host.py shows what these
 hold), and for the three callers that write files.  No case has a tolerance."""

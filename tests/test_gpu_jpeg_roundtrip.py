@@ -1,4 +1,4 @@
-"""The JPEG round trip on the device (csrc/jpeg.hip avcer_jpeg_roundtrip_tiles / _rgb, avcer_amd/jpeg.py roundtrip_tiles /
+"""The JPEG round trip on the device (csrc/jpeg_encode.hip avcer_jpeg_roundtrip_tiles / _rgb, avcer_amd/jpeg.py roundtrip_tiles /
 roundtrip_canvas) and the option built on it (`via_jpeg` of VideoTiler.process, `faces_via_jpeg` of run_inference and run_dataset):
 the visual models see a face crop as the reference's stage 1 does, read back from the JPEG file stage 0 writes of it.  Held to PIL's
 own round trip (Image.save -> Image.open, NEAREST to 224 for the tiles), to the composition of the encoder and the decoder that

@@ -1,4 +1,4 @@
-"""The entropy DECODER on the device (csrc/jpeg.hip avcer_jpeg_unpack, Engine.jpeg_unpack, jpeg.decode_tiles / decode_canvas with
+"""The entropy DECODER on the device (csrc/jpeg_unpack.hip avcer_jpeg_unpack, Engine.jpeg_unpack, jpeg.decode_tiles / decode_canvas with
 entropy="device") against its oracle, the host pass avcer_jpeg_entropy_batch, and against its own host statement
 avcer_jpeg_unpack_host, on the sets of tests/jpeg_unpack_cases.py (tests/test_jpeg_unpack_host.py shows what these hold and that the
 algorithm is right on them): status, reason and coefficients are equal.  Then the callers: tiles, canvas, rects and paths are those

@@ -1,4 +1,4 @@
-"""The host half of the JPEG encoder (csrc/jpeg.hip avcer_jpeg_quant_tables / avcer_jpeg_plan / avcer_jpeg_write_batch, ctx NULL: no
+"""The host half of the JPEG encoder (csrc/jpeg_encode.hip avcer_jpeg_quant_tables / avcer_jpeg_plan / avcer_jpeg_write_batch, ctx NULL: no
 device) and the numpy statement of its device half (avcer_amd/jpeg.py forward_numpy) against the files PIL writes (libjpeg-turbo),
 byte for byte."""
 import ctypes
@@ -69,7 +69,7 @@ def _groups(corpus):
 
 def _write(lib, coeffs, desc, threads=0, room=None, cap=None):
     desc = desc.copy()
-    # by default: the header and the most a block can take (csrc/jpeg.hip BLOCK_ROOM)
+    # by default: the header and the most a block can take (csrc/jpeg_encode.hip BLOCK_ROOM)
     out = np.zeros(room if room is not None else 623 * len(desc) + 420 * (coeffs.size // 64), dtype=np.uint8)
     offsets, need = jpeg.write_batch(lib, np.ascontiguousarray(coeffs.reshape(-1)), desc, out, threads, cap_bytes=cap)
     return out, offsets, need, desc

@@ -1,4 +1,4 @@
-"""The host half of the JPEG crop decoder (csrc/jpeg.hip avcer_jpeg_probe / avcer_jpeg_entropy_batch, ctx NULL: no device) and the
+"""The host half of the JPEG crop decoder (csrc/jpeg_decode.hip avcer_jpeg_probe / avcer_jpeg_entropy_batch, ctx NULL: no device) and the
 numpy statement of its device half (avcer_amd/jpeg.py pixels_numpy) against PIL's decode (libjpeg-turbo), bit for bit."""
 import ctypes
 import io

@@ -1,5 +1,5 @@
 """The device entropy decoder's algorithm on the host: avcer_jpeg_scan_batch + avcer_jpeg_unpack_host (the phases of the kernel as
-loops over its threads, csrc/jpeg.hip) against the host pass avcer_jpeg_entropy_batch on the same files, tolerance zero: the same
+loops over its threads, csrc/jpeg_unpack.hip) against the host pass avcer_jpeg_entropy_batch on the same files, tolerance zero: the same
 status for every file, the same reason on the single-defect files, the same coefficients for every file both call OK -- as one
 batch, file by file and permuted, at the shortest subsequence length and at the default.  Also: what scan_batch does with a short
 buffer, and that it de-duplicates Huffman tables by content."""

@@ -1,5 +1,5 @@
 // Host sanitiser check of the device entropy decoder's host side: a stand-alone program around avcer_jpeg_scan_batch and
-// avcer_jpeg_unpack_host (csrc/jpeg.hip: the phases of the kernel as loops over its threads), built with AddressSanitizer and UBSan on
+// avcer_jpeg_unpack_host (csrc/jpeg_unpack.hip: the phases of the kernel as loops over its threads), built with AddressSanitizer and UBSan on
 // the HOST side only and run on a CPU machine:
 //   python tools/jpeg_unpack_asan.py      (writes the input files, compiles this file, runs it)
 // Input file: i32 n; i64 [n] lengths; the files back to back.  Every buffer given to the library is a heap block of EXACTLY the
@@ -13,7 +13,7 @@
 
 #include "../include/avcer_hip.h"
 
-// what csrc/api.hip gives the library; this program links jpeg.hip alone
+// what csrc/api.hip gives the library; this program links jpeg_decode.hip and jpeg_unpack.hip alone
 struct avcer_ctx;
 int set_err(avcer_ctx*, int code, const char*, ...) { return code; }
 int ws_reserve(avcer_ctx*, int, size_t, void**) { return -1; }

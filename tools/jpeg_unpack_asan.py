@@ -1,4 +1,4 @@
-"""Builds and runs tools/jpeg_unpack_asan.hip: avcer_jpeg_scan_batch and avcer_jpeg_unpack_host (csrc/jpeg.hip: the device entropy
+"""Builds and runs tools/jpeg_unpack_asan.hip: avcer_jpeg_scan_batch and avcer_jpeg_unpack_host (csrc/jpeg_unpack.hip: the device entropy
 decoder's algorithm as host loops) under AddressSanitizer + UBSan, in a stand-alone program, on a CPU machine (never on the GPU,
 never loaded into python).  `python tools/jpeg_unpack_asan.py`."""
 from __future__ import annotations
@@ -29,7 +29,7 @@ def main() -> int:
             f.write(np.int32(len(files)).tobytes() + np.array([len(b) for b in files], dtype=np.int64).tobytes() + b"".join(files))
         san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
         cmd = [build._hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17"] + san + [
-            os.path.join(build.CSRC, "jpeg.hip"), os.path.join(ROOT, "tools", "jpeg_unpack_asan.hip"), "-fsanitize=address,undefined", "-o", exe]
+            os.path.join(build.CSRC, "jpeg_decode.hip"), os.path.join(build.CSRC, "jpeg_unpack.hip"), os.path.join(ROOT, "tools", "jpeg_unpack_asan.hip"), "-fsanitize=address,undefined", "-o", exe]
         subprocess.run(cmd, check=True)
         return subprocess.run([exe, data]).returncode
 

@@ -1,4 +1,4 @@
-// Host sanitiser check of the JPEG writer: a stand-alone program around the host code of csrc/jpeg.hip (avcer_jpeg_plan,
+// Host sanitiser check of the JPEG writer: a stand-alone program around the host code of csrc/jpeg_encode.hip (avcer_jpeg_plan,
 // avcer_jpeg_write_batch), built with AddressSanitizer and UBSan on the HOST side only and run on a CPU machine:
 //   python tools/jpeg_write_asan.py      (writes the input with jpeg.forward_numpy, compiles this file, runs it)
 // Input file: i32 n, quality, subsampling; i32 [n,2] sizes (w, h); i64 count; i16 [count] coefficients; i64 bytes; u8 [bytes] the
@@ -12,7 +12,7 @@
 
 #include "../include/avcer_hip.h"
 
-// what csrc/api.hip gives the library; this program links jpeg.hip alone
+// what csrc/api.hip gives the library; this program links jpeg_encode.hip and, for the launchers it calls, jpeg_decode.hip alone
 struct avcer_ctx;
 int set_err(avcer_ctx*, int code, const char*, ...) { return code; }
 int ws_reserve(avcer_ctx*, int, size_t, void**) { return -1; }

@@ -1,4 +1,4 @@
-"""Builds and runs tools/jpeg_write_asan.hip: the host code of csrc/jpeg.hip under AddressSanitizer + UBSan, in a stand-alone
+"""Builds and runs tools/jpeg_write_asan.hip: the host code of csrc/jpeg_encode.hip under AddressSanitizer + UBSan, in a stand-alone
 program, on a CPU machine (never on the GPU, never loaded into python).  `python tools/jpeg_write_asan.py`."""
 from __future__ import annotations
 
@@ -40,7 +40,7 @@ def main() -> int:
             f.write(np.int64(coeffs.size).tobytes() + coeffs.tobytes() + np.int64(len(blob)).tobytes() + blob)
         san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
         cmd = [build._hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17"] + san + [
-            os.path.join(build.CSRC, "jpeg.hip"), os.path.join(ROOT, "tools", "jpeg_write_asan.hip"), "-fsanitize=address,undefined", "-o", exe]
+            os.path.join(build.CSRC, "jpeg_encode.hip"), os.path.join(build.CSRC, "jpeg_decode.hip"), os.path.join(ROOT, "tools", "jpeg_write_asan.hip"), "-fsanitize=address,undefined", "-o", exe]
         subprocess.run(cmd, check=True)
         return subprocess.run([exe, data]).returncode
 
