@@ -52,6 +52,7 @@ SIGNATURES = {
     "avcer_set_static_back_batch": (C.c_int, [c_ctx, C.c_int]),
     "avcer_set_static_lanes": (C.c_int, [c_ctx, C.c_int]),
     "avcer_set_static_lane_range": (C.c_int, [c_ctx, C.c_int, C.c_int]),
+    "avcer_set_skip_unread_rows": (C.c_int, [c_ctx, C.c_int]),
     "avcer_static_forward_nchw": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                             c_stream]),
     "avcer_gather_windows": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, c_stream]),
@@ -166,6 +167,8 @@ SIGNATURES = {
     "avcer_bneck_chain": (C.c_int, [c_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9 +
                           [c_stream]),
     "avcer_bneck_tail": (C.c_int, [c_ctx, C.c_int, C.c_int64] + [C.c_void_p] * 8 + [c_stream]),
+    "avcer_bneck_chain_keep": (C.c_int, [c_ctx] + [C.c_int] * 4 + [C.c_void_p] * 11 + [C.c_int, c_stream]),
+    "avcer_bneck_tail_keep": (C.c_int, [c_ctx] + [C.c_int] * 4 + [C.c_void_p] * 8 + [C.c_int, c_stream]),
     "avcer_stem_pool": (C.c_int, [c_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, c_stream]),
     "avcer_stem_pool_u8": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      c_stream]),

@@ -73,6 +73,7 @@ struct avcer_ctx {
     int static_batch = 1024;  // frames per internal pass of the static CNN (4 GiB buffer-descriptor limit at f32)
     int static_back = 0;      // frames per back pass of the static CNN (0: two front passes; avcer_set_static_back_batch)
     int static_lanes = 2;     // calls of lane_min .. lane_max frames as two half-batches on two streams (avcer_set_static_lanes)
+    bool skip_unread = true;  // the block in front of a strided last block stores the OUT rows that block reads alone (avcer_set_skip_unread_rows)
     int lane_min = 32, lane_max = 2048;  // avcer_set_static_lane_range (tools/two_lane_sweep.py: two lanes win from 16 to 2048 frames)
     hipStream_t lane_stream = nullptr;  // the second lane's stream, created on first use, and its fork / join events
     hipEvent_t lane_ev[2] = {nullptr, nullptr};
@@ -175,13 +176,16 @@ int launch_stem_pool_face(avcer_ctx* ctx, const uint8_t* frames, int h, int w, i
 // all activations sp32, weights split-fp16 (scaled, row-permuted) with the BN scale folded in (packing.py: *.wf, c3d.w)
 // w2_frags: the conv2 weights once more in MFMA fragment order (k_weight_frags), or null: selects the spatial-tile form
 // where it applies (planes 64, 55 x 55 images, a next conv1)
+// keep = 2 (needs t1n, no downsample, out_step 1): OUT is stored at the even (y, x) of every image alone, at its full-grid
+// addresses -- for the block whose OUT only a strided last block reads; the other rows of `out` are left as they were
 int launch_bneck(avcer_ctx* ctx, int planes, int nb, int h, int w, const void* t1, const void* x, int ds_cin, int out_step,
                  void* out, void* t1n, const void* w2, const float* b2, const void* w3, const float* b3, const void* w1n,
-                 const float* b1n, hipStream_t st, const void* w2_frags = nullptr);
+                 const float* b1n, hipStream_t st, const void* w2_frags = nullptr, int keep = 1);
 
-// conv3 + residual + ReLU of a planes-256 bottleneck and conv1 of the next block in one launch (t2 = conv2 output [M][256])
+// conv3 + residual + ReLU of a planes-256 bottleneck and conv1 of the next block in one launch (t2 = conv2 output [M][256]);
+// keep = 2: as launch_bneck's, on M = whole images of h x w positions
 int launch_bneck_tail(avcer_ctx* ctx, int planes, long M, const void* t2, const void* x, void* out, void* t1n, const void* w3,
-                      const float* b3, const void* w1n, const float* b1n, hipStream_t st);
+                      const float* b3, const void* w1n, const float* b1n, hipStream_t st, int keep = 1, int h = 0, int w = 0);
 
 // ---- gru.hip
 // The recurrence of one GRU layer (hidden size 256) over S steps in one launch: xp [n, S, 768] f32 (input projections + b_ih,

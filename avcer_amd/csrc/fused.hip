@@ -444,6 +444,7 @@ struct BneckParams {
     int OH, OW;         // SUB > 1: the output grid, position (oy, ox) <-> input position (SUB oy, SUB ox)
     unsigned* ovf;      // the context's range-contract counter (split_dev.h sp_commit)
     int nblocks;        // logical blocks (tiles); the grid may be smaller: a block then walks tiles blockIdx.x, + gridDim.x, ...
+    int keep;           // row-keep step of OUT: 1 = every row is stored; 2 = only the rows at even (y, x) (see bneck_kernel, KEEP)
 };
 
 // BM positions per block, 4 waves, each wave owns BM/4 positions and ALL channels (so that a position's whole T2 /
@@ -467,6 +468,13 @@ struct BneckParams {
 // grids (the 3x3 taps of an even position touch odd ones; the residual is picked at the even position).  A quarter of the
 // conv2 / conv3 products, of the residual reads and of the output bytes; every value written is the one the full-
 // resolution evaluation would have put at that position.
+//
+// KEEP (p.keep == 2; the NEXT forms without a downsample): the block IN FRONT of that strided one.  Its OUT is the strided block's
+// residual and nothing else, so only the rows at even (y, x) are ever loaded back; the next conv1 needs OUT at every position,
+// but takes it from registers.  Everything is computed and T1N written as with p.keep == 1; the OUT stores of the other rows
+// (three quarters of them) are not issued.  Kept rows stay at their full-grid addresses and are whole 128-byte lines, so the
+// reader does not change and every value it loads is the one the full store would have left there.  The decision is one lane
+// mask per 16-position tile, made once from the row index (o_ok below, scalar registers): no vector register stays live for it.
 //
 // T11 (round 5; planes 64 on the 55 x 55 images of stage 1): in-kernel stamps (tools/clock_lab.py,
 // profiles/r05_inkernel_clock_shares.txt) put 48 % of a block's residency into the conv2 loop -- 18 K-steps of 24 MFMAs per
@@ -840,6 +848,30 @@ __global__ void __launch_bounds__(256, P == 64 ? 3 : 2) bneck_kernel(const Bneck
             o_row[t] = (unsigned)(m_row[t] * (4L * P * 4) + 16 * g);
         }
     }
+    // rows whose OUT is stored: all of them, or (KEEP) those at even (y, x) of their image; the four lane groups of a row agree,
+    // so a kept row is still written as whole 128-byte lines
+    bool o_ok[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) o_ok[t] = m_ok[t];
+    if constexpr (NEXT && NQX == 0 && SUB == 1) {
+        if (p.keep == 2) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                int y, x;
+                if constexpr (T11) {
+                    const int r = min(wave * (BM / 4) + t * 16 + l15, T11_E * T11_E - 1);
+                    const int ry = r / T11_E;
+                    y = t11_y0 + ry;
+                    x = t11_x0 + r - ry * T11_E;
+                } else {
+                    const int yb = m_row[t] / p.Wd;
+                    x = m_row[t] - yb * p.Wd;
+                    y = yb % p.H;
+                }
+                o_ok[t] = m_ok[t] && ((y | x) & 1) == 0;
+            }
+        }
+    }
     // downsample operand: the NQX K-steps of this lane's positions as B fragments, straight from global memory
     spx8_t xh[NQX > 0 ? NQX : 1][NT], xl[NQX > 0 ? NQX : 1][NT];
     if constexpr (NQX > 0) {
@@ -937,7 +969,7 @@ __global__ void __launch_bounds__(256, P == 64 ? 3 : 2) bneck_kernel(const Bneck
                                 relu_nan(__builtin_fmaf(hi4[0], s3, b1.x) + r[4]), relu_nan(__builtin_fmaf(hi4[1], s3, b1.y) + r[5]),
                                 relu_nan(__builtin_fmaf(hi4[2], s3, b1.z) + r[6]), relu_nan(__builtin_fmaf(hi4[3], s3, b1.w) + r[7])};
             sp_split8(v, oh[t], ol[t], ovm);
-            if (m_ok[t]) {
+            if (o_ok[t]) {
                 char* yp = p.OUT + (size_t)(SUB == 1 ? x_row[t] : o_row[SUB > 1 ? t : 0]) + G * 128;
                 *reinterpret_cast<spx8_t*>(yp) = oh[t];
                 *reinterpret_cast<spx8_t*>(yp + 64) = ol[t];
@@ -1061,7 +1093,14 @@ __global__ void __launch_bounds__(512, 2) bneck_tail2_kernel(const BneckParams p
     const bool m_ok = m < p.M;
     const long mc = m_ok ? m : 0;
     const long x_row = mc * (4L * P * 4) + 16 * g;
-    const unsigned o_row = m_ok ? (unsigned)x_row : OOB;  // rows past M: the buffer store is dropped
+    // p.keep == 2 (bneck_kernel, KEEP): p.M = nb * H * Wd, and the rows off the even (y, x) of their image are not stored either
+    bool o_ok = m_ok;
+    if (p.keep == 2) {
+        const int yb = (int)mc / p.Wd;
+        o_ok = m_ok && ((((int)mc - yb * p.Wd) | (yb % p.H)) & 1) == 0;
+    }
+    // rows past M, and the rows KEEP leaves out: the buffer store is dropped (the offset stays the store's vector address)
+    const unsigned o_row = o_ok ? (unsigned)x_row : OOB;
     spx8_t t2h[NQ], t2l[NQ];
     {
         const char* tp = p.T1 + mc * (P * 4L) + 16 * g;
@@ -1267,8 +1306,11 @@ int launch_stem_pool_face(avcer_ctx* ctx, const uint8_t* frames, int h, int w, i
 
 int launch_bneck(avcer_ctx* ctx, int planes, int nb, int h, int w, const void* t1, const void* x, int ds_cin, int out_step,
                  void* out, void* t1n, const void* w2, const float* b2, const void* w3, const float* b3, const void* w1n,
-                 const float* b1n, hipStream_t st, const void* w2_frags) {
+                 const float* b1n, hipStream_t st, const void* w2_frags, int keep) {
     if (out_step != 1 && out_step != 2) return set_err(ctx, AVCER_EINVAL, "bneck: out_step %d (1 or 2)", out_step);
+    if (keep != 1 && keep != 2) return set_err(ctx, AVCER_EINVAL, "bneck: keep %d (1 or 2)", keep);
+    if (keep == 2 && (!t1n || ds_cin || out_step != 1))
+        return set_err(ctx, AVCER_EINVAL, "bneck: the row-keep step is for a full-resolution block with a next conv1 and no downsample");
     if (out_step == 2 && (t1n || ds_cin)) return set_err(ctx, AVCER_EINVAL, "bneck: the strided form is the last block of a stage (no next conv1, no downsample)");
     const int oh = (h - 1) / out_step + 1, ow = (w - 1) / out_step + 1;
     const long M = (long)nb * oh * ow, M_in = (long)nb * h * w;
@@ -1291,14 +1333,17 @@ int launch_bneck(avcer_ctx* ctx, int planes, int nb, int h, int w, const void* t
     p.b2 = b2; p.b3 = b3; p.b1n = b1n;
     p.t1_bytes = (unsigned)(M_in * planes * 4);
     p.M = (int)M; p.H = h; p.Wd = w; p.OH = oh; p.OW = ow; p.ovf = ctx->ovf;
+    p.keep = keep;
     constexpr int BM = 128;
     // The spatial-tile form (bneck_kernel<..., T11>): planes 64 with a next conv1 on 55 x 55 images (5 x 5 tiles of 11 x 11),
     // when the caller brought the fragment-order copy of the conv2 weights; one block per tile.
     const bool t11 = planes == 64 && h == 55 && w == 55 && out_step == 1 && t1n && w2_frags;
     p.nblocks = t11 ? nb * 25 : (int)((M + BM - 1) / BM);
     const int grid = p.nblocks;
-    // per position: T1 in (P), residual or downsample operand in (4P | ds_cin), OUT (4P) and T1' (P) out, 4 bytes per element
-    const double bytes = 4.0 * ((double)M_in * planes + (double)M * (ds_cin ? ds_cin : 4 * planes) + (double)M * 4 * planes +
+    // per position: T1 in (P), residual or downsample operand in (4P | ds_cin), OUT (4P) and T1' (P) out, 4 bytes per element;
+    // keep == 2: OUT at the even positions of every image alone
+    const long M_out = keep == 2 ? (long)nb * ((h + 1) / 2) * ((w + 1) / 2) : M;
+    const double bytes = 4.0 * ((double)M_in * planes + (double)M * (ds_cin ? ds_cin : 4 * planes) + (double)M_out * 4 * planes +
                                 (t1n ? (double)M * planes : 0.0));
     const double flops = 2.0 * (double)M * planes * (planes * (9.0 + 4.0 + (t1n ? 4.0 : 0.0)) + 4.0 * ds_cin);
     // Resident halo patch for the conv2 phase: planes 128 only (28x28: -5..7 % per launch).  At planes 64 (55x55) the patch
@@ -1331,8 +1376,11 @@ int launch_bneck(avcer_ctx* ctx, int planes, int nb, int h, int w, const void* t
 }
 
 int launch_bneck_tail(avcer_ctx* ctx, int planes, long M, const void* t2, const void* x, void* out, void* t1n, const void* w3,
-                      const float* b3, const void* w1n, const float* b1n, hipStream_t st) {
+                      const float* b3, const void* w1n, const float* b1n, hipStream_t st, int keep, int h, int w) {
     if (!t2 || !x || !out || !t1n || !w3 || !b3 || !w1n || !b1n || M <= 0) return set_err(ctx, AVCER_EINVAL, "bneck_tail: bad arguments");
+    if (keep != 1 && keep != 2) return set_err(ctx, AVCER_EINVAL, "bneck_tail: keep %d (1 or 2)", keep);
+    if (keep == 2 && (h <= 0 || w <= 0 || M % ((long)h * w) != 0))
+        return set_err(ctx, AVCER_EINVAL, "bneck_tail: the row-keep step needs the image grid: M=%ld is not whole images of %d x %d", M, h, w);
     if (planes != 256) return set_err(ctx, AVCER_EINVAL, "bneck_tail: planes %d (256)", planes);
     // OUT is stored through a buffer descriptor (rows past M are dropped by its bounds check): it must stay under 4 GiB,
     // i.e. 5 349 frames of 14 x 14 -- a back pass of the static CNN is at most 2 048
@@ -1343,9 +1391,12 @@ int launch_bneck_tail(avcer_ctx* ctx, int planes, long M, const void* t2, const 
     p.W3 = (const char*)w3; p.W1N = (const char*)w1n; p.b3 = b3; p.b1n = b1n;
     p.M = (int)M; p.ovf = ctx->ovf;
     p.t1_bytes = (unsigned)(M * 4096L);
-    // per position: T2 in (P), residual in (4P), OUT (4P) and T1' (P) out
-    return launch_counted(ctx, st, FAM_TAIL, "bneck_tail", 2.0 * (double)M * planes * planes * 8.0, 4.0 * (double)M * planes * 10.0, M,
-                          4 * planes, planes, [&] { bneck_tail2_kernel<256><<<dim3((int)((M + 127) / 128)), dim3(512), 0, st>>>(p); });
+    p.keep = keep; p.H = h; p.Wd = w;
+    // per position: T2 in (P), residual in (4P), OUT (4P) and T1' (P) out; keep == 2: OUT at the even positions of every image alone
+    const long M_out = keep == 2 ? M / ((long)h * w) * ((h + 1) / 2) * ((w + 1) / 2) : M;
+    return launch_counted(ctx, st, FAM_TAIL, "bneck_tail", 2.0 * (double)M * planes * planes * 8.0,
+                          4.0 * planes * ((double)M * 6.0 + (double)M_out * 4.0), M, 4 * planes, planes,
+                          [&] { bneck_tail2_kernel<256><<<dim3((int)((M + 127) / 128)), dim3(512), 0, st>>>(p); });
 }
 
 // Measured ceilings of this GPU: dense 16-bit MFMA issue rate (the f16 form; TFLOP/s) and streaming-copy bandwidth (TB/s, read + write bytes).

@@ -35,6 +35,9 @@ void run_bneck_stage(Net& net, Trunk& t, int li, int b_begin, int b_end, int nb,
                           pn = "l" + std::to_string(li + 1) + "." + std::to_string(b + 1) + ".";
         void* dst = (b == b_end - 1 && last_out) ? last_out : (t.X == t.pp[0] ? t.pp[1] : t.pp[0]);
         const bool fused = net.x3 && li < 3 && b >= fused_from, chain = fused && li < 2, next = b + 1 < blocks;
+        // Work nobody reads: the block in front of the strided last one hands it OUT as the residual, which that block picks at
+        // (2 oy, 2 ox) alone -- the fused launch stores those rows only (fused.hip KEEP).  A debug tap promises the whole tensor.
+        const int keep = t.stride_last && li < 3 && kStages[li + 1][2] == 2 && b == blocks - 2 && fused && ctx->skip_unread && !ctx->tap_dst ? 2 : 1;
         if (!fused || b == fused_from)
             net.gemm(conv2d_desc(nb, h, w, t.cin, 1, 1, 1, 0, planes, 1), p + "c1.w", net.F(p + "c1.s"), net.F(p + "c1.b"), t.X,
                      nullptr, t.T1, act, act);
@@ -49,7 +52,7 @@ void run_bneck_stage(Net& net, Trunk& t, int li, int b_begin, int b_end, int nb,
             }
             net.chk(launch_bneck(ctx, planes, nb, h, w, t.T1, t.X, first ? t.cin : 0, s, dst, next ? t.T2 : nullptr, w2->x3,
                                  net.F(p + "c2.b"), w3->x3, net.F(first ? p + "c3d.b" : p + "c3.b"), next ? w1n->x3 : nullptr,
-                                 next ? net.F(pn + "c1.b") : nullptr, net.st, t.w2_frags ? w2->x3f : nullptr));
+                                 next ? net.F(pn + "c1.b") : nullptr, net.st, t.w2_frags ? w2->x3f : nullptr, keep));
             if (ctx->tap_dst) {
                 net.tap((tap + "chain_out:" + p).c_str(), dst, (size_t)nb * oh * ow * planes * 4 * es);
                 if (next) net.tap((tap + "chain_t1n:" + p).c_str(), t.T2, (size_t)M * planes * es);
@@ -73,7 +76,7 @@ void run_bneck_stage(Net& net, Trunk& t, int li, int b_begin, int b_end, int nb,
                     return;
                 }
                 net.chk(launch_bneck_tail(ctx, planes, M, t.T2, t.X, dst, t.T1, w3->x3, net.F(p + "c3.b"), w1n->x3,
-                                          net.F(pn + "c1.b"), net.st));
+                                          net.F(pn + "c1.b"), net.st, keep, h, w));
                 if (ctx->tap_dst) {
                     net.tap((tap + "tail_out:" + p).c_str(), dst, (size_t)M * planes * 4 * es);
                     net.tap((tap + "tail_t1n:" + p).c_str(), t.T1, (size_t)M * planes * es);

@@ -284,6 +284,11 @@ class Engine:
         if min_frames is not None or max_frames is not None:
             self._check(self.lib.avcer_set_static_lane_range(self.ctx, int(min_frames or 128), int(max_frames or 512)))
 
+    def set_skip_unread_rows(self, on: bool = True):
+        """True (default): in the x3 mode the block in front of a strided last block of the recognition CNN stores only the output rows
+        that block reads; False: every row.  Results are bit-identical either way."""
+        self._check(self.lib.avcer_set_skip_unread_rows(self.ctx, 1 if on else 0))
+
     # ------------------------------------------------------------------ forward passes
     def static_forward(self, frames_u8, mode: int = MODE_DEFAULT):
         """frames u8 [N,H,W,3] RGB -> (logits [N,7], probs [N,7], feats [N,512] pre-ReLU)."""
@@ -1181,6 +1186,17 @@ class Engine:
         [m,256], x / out sp32 [m,1024], t1n sp32 [m,256]; w3 [1024,256] and w1n [256,1024] from `split_weight_rows`."""
         self._check(self.lib.avcer_bneck_tail(self.ctx, int(planes), int(m), _ptr(t2), _ptr(x), _ptr(out), _ptr(t1n), _ptr(w3),
                                               _ptr(b3), _ptr(w1n), _ptr(b1n), self._stream()))
+
+    def bneck_chain_keep(self, planes: int, nb: int, h: int, w: int, t1, x, out, t1n, w2, b2, w3, b3, w1n, b1n, keep: int, w2_frags=None):
+        """`bneck_chain` (no downsample, out_step 1, with a next conv1) with a row-keep step for `out`: keep = 2 stores only the rows
+        at even (y, x) of every image and leaves the others as they are; keep = 1 is `bneck_chain`."""
+        self._check(self.lib.avcer_bneck_chain_keep(self.ctx, planes, nb, h, w, _ptr(t1), _ptr(x), _ptr(out), _ptr(t1n), _ptr(w2), _ptr(b2),
+                                                    _ptr(w3), _ptr(b3), _ptr(w1n), _ptr(b1n), _ptr(w2_frags), int(keep), self._stream()))
+
+    def bneck_tail_keep(self, planes: int, nb: int, h: int, w: int, t2, x, out, t1n, w3, b3, w1n, b1n, keep: int):
+        """`bneck_tail` on nb images of h x w positions (m = nb * h * w) with the same row-keep step for `out`."""
+        self._check(self.lib.avcer_bneck_tail_keep(self.ctx, int(planes), nb, h, w, _ptr(t2), _ptr(x), _ptr(out), _ptr(t1n), _ptr(w3),
+                                                   _ptr(b3), _ptr(w1n), _ptr(b1n), int(keep), self._stream()))
 
     def dwsep(self, x, dw_w, dw_s, dw_b, pw_w, pw_s, pw_b, stride: int, mode: int = MODE_FP32):
         """Kernel-level entry of one conv_dw block of MobileNet-0.25 (csrc/mnet.hip): x f32 NHWC [nb,h,w,cin], dw_w [9,cin],

@@ -107,7 +107,9 @@ enum {
  *      avcer_dib_frames (uncompressed BGR video of an AVI file unpacked into the frame batch) joined under 8 the same way: one
  *      more symbol, nothing that existed changed.
  *      avcer_window_votes (the audio model over a corpus: softmax, argmax and per-file majority vote of the window logits) joined
- *      under 8 the same way: one more symbol, nothing that existed changed. */
+ *      under 8 the same way: one more symbol, nothing that existed changed.
+ *      avcer_set_skip_unread_rows, avcer_bneck_chain_keep, avcer_bneck_tail_keep (the block in front of a strided last block
+ *      stores only the rows that block reads) joined under 8 the same way: three more symbols, nothing that existed changed. */
 #define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
@@ -166,6 +168,12 @@ int avcer_set_static_lanes(avcer_ctx* ctx, int lanes);
 /* The call sizes that take the two-lane schedule: min_frames <= n <= max_frames, 2 <= min <= max <= 4096 (default 32 .. 2048).
  * A scheduling knob: results do not depend on it. */
 int avcer_set_static_lane_range(avcer_ctx* ctx, int min_frames, int max_frames);
+/* AVCER_MODE_F16X3 only.  The last block of stages 1-3 of the recognition CNN is evaluated at the positions (2 oy, 2 ox) alone, so
+ * of the output of the block in front of it (its residual) only those rows are ever read.  on != 0 (default): that block's fused
+ * launch stores those rows only, at their full-grid addresses (csrc/fused.hip KEEP): 8.4 GB fewer bytes written per 2048 frames.
+ * 0: every row is stored.  Results are bit-identical either way; calls made while a debug tap is armed store every row regardless,
+ * because the blk / chain_out / tail_out taps return the whole tensor. */
+int avcer_set_skip_unread_rows(avcer_ctx* ctx, int on);
 
 /* The same model on an already preprocessed tensor, i.e. the exact argument of the reference's
  * `pth_model_static(x)`:  x f32 [n,3,224,224] (BGR, mean-subtracted).   ref: get_prob_video.py:103-109 */
@@ -997,6 +1005,16 @@ int avcer_bneck_chain(avcer_ctx* ctx, int planes, int nb, int h, int w, const vo
                       const float* b1n, const void* w2_frags, avcer_stream_t stream);
 int avcer_bneck_tail(avcer_ctx* ctx, int planes, int64_t M, const void* t2, const void* x, void* out, void* t1n, const void* w3,
                      const float* b3, const void* w1n, const float* b1n, avcer_stream_t stream);
+/* The same two launches with a row-keep step for `out`, for kernel-level tests of what avcer_set_skip_unread_rows selects.
+ *   keep = 1: every row of out is stored (avcer_bneck_chain with ds_cin 0 and out_step 1; avcer_bneck_tail with M = nb * h * w).
+ *   keep = 2: only the rows at even (y, x) of each of the nb images of h x w positions are stored, at their full-grid addresses;
+ *   the other rows of out keep what the caller put there.  t1n is written at every position either way.  avcer_bneck_chain_keep
+ *   requires t1n / w1n / b1n (the block in front of a strided last block always has a next conv1). */
+int avcer_bneck_chain_keep(avcer_ctx* ctx, int planes, int nb, int h, int w, const void* t1, const void* x, void* out, void* t1n,
+                           const void* w2, const float* b2, const void* w3, const float* b3, const void* w1n, const float* b1n,
+                           const void* w2_frags, int keep, avcer_stream_t stream);
+int avcer_bneck_tail_keep(avcer_ctx* ctx, int planes, int nb, int h, int w, const void* t2, const void* x, void* out, void* t1n,
+                          const void* w3, const float* b3, const void* w1n, const float* b1n, int keep, avcer_stream_t stream);
 /* One conv_dw block of MobileNet-0.25 (retina_face_net.py:29-38) in ONE launch (csrc/mnet.hip dwsep_kernel), for kernel-level tests:
  *     T = leaky(dw3x3(X, stride, pad 1) * dw_s + dw_b);  Y = leaky(conv1x1(T) * pw_s + pw_b),  leaky = LeakyReLU(0.1)
  *   x f32 NHWC [nb,h,w,cin] -> y f32 NHWC [nb,ceil(h/stride),ceil(w/stride),cout]; T never reaches memory.
