@@ -411,7 +411,7 @@ def plan_corpus(engine, files, windows, sr: int = 16000, max_w_len: int = 4, win
 
 
 def run_corpus(engine, files, windows, sr: int = 16000, max_w_len: int = 4, mode: Optional[int] = None, windows_per_pass: int = 128,
-               features: bool = False) -> CorpusResult:
+               features: bool = False, plan=None) -> CorpusResult:
     """The audio model over every window of a corpus.  files: (name, wav) with wav mono float32 [L] at `sr`, or (name, wav,
     wav_sr) with the source audio at `wav_sr` as Engine.resample takes it (int16 [L] / [L, C] or float32 [L] / [C, L]), brought to
     mono at `sr` on the device; windows: one `Windows` table per file (cexpr_windows / abaw_windows / afew_windows).
@@ -421,13 +421,15 @@ def run_corpus(engine, files, windows, sr: int = 16000, max_w_len: int = 4, mode
     file votes.  Everything sits inside one `engine.guarded(mode, ...)`: a corpus in which any activation leaves fp16's range is
     repeated in MODE_FP32 as a whole.  `features`: also the pooled head activations per window.
     Every window's row holds the bits a one-window Engine.audio_forward call on that window gives (tests/test_gpu_audio_corpus.py).
-    What plan_corpus refuses raises ValueError before anything is launched."""
+    What plan_corpus refuses raises ValueError before anything is launched.  `plan`: what plan_corpus returned for these very
+    arguments, for a caller that runs one corpus under several models (validate.validate_checkpoints) and plans it once."""
     import torch
 
     from .engine import MODE_DEFAULT
 
     mode = MODE_DEFAULT if mode is None else mode
-    names, s_off, file_off, starts, ends, targets = plan_corpus(engine, files, windows, sr, max_w_len, windows_per_pass)
+    names, s_off, file_off, starts, ends, targets = plan if plan is not None else plan_corpus(engine, files, windows, sr, max_w_len,
+                                                                                                 windows_per_pass)
     files = [_file_parts(f) for f in files]
     win = int(max_w_len * sr)
     n = int(starts.shape[0])

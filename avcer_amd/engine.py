@@ -706,6 +706,49 @@ class Engine:
                                                 self._stream()))
         return tuple(out)
 
+    def window_losses(self, logits, targets, weights=None, kind: int = 0, label_smoothing: float = 0.2, gamma: float = 0.0,
+                      batch_size: int = 64):
+        """The losses of a corpus's window logits, batched as a DataLoader batches them, in one launch (include/avcer_hip.h
+        avcer_window_losses; net_trainer.py:391-465).  logits [n, c] (2 <= c <= 16), targets [n] in [0, c), weights [c] or None
+        (ones); kind 0: cross entropy with `label_smoothing`, 1: soft focal loss with `gamma`.  Returns (row_loss f64 [n],
+        batch_loss f64 [ceil(n / batch_size)], epoch f64 [2]: the reference's epoch loss and the row-weighted mean) on the device.
+        Shapes that disagree raise ValueError; limits are the library's (AvcerError).  No host synchronisation."""
+        x = self._dev(logits, torch.float32)
+        t = self._dev(targets, torch.int32)
+        if x.dim() != 2 or t.dim() != 1 or int(t.shape[0]) != int(x.shape[0]):
+            raise ValueError(f"window_losses: logits [n, c] and targets [n] expected, got {tuple(x.shape)} and {tuple(t.shape)}")
+        n, c, bsz = int(x.shape[0]), int(x.shape[1]), int(batch_size)
+        w = None
+        if weights is not None:
+            w = self._dev(weights, torch.float32)
+            if tuple(w.shape) != (c,):
+                raise ValueError(f"window_losses: weights [{c}] expected, got {tuple(w.shape)}")
+        n_batches = -(-n // bsz) if n > 0 and bsz > 0 else 0
+        row, batch, epoch = (self._new(k, dtype=torch.float64) for k in (n, n_batches, 2))
+        ticket = self._new(1, dtype=torch.int32)
+        self._check(self.lib.avcer_window_losses(self.ctx, _ptr(x), _ptr(t), _ptr(w), n, c, int(kind), float(label_smoothing), float(gamma),
+                                                 bsz, _ptr(row), _ptr(batch), _ptr(epoch), _ptr(ticket), self._stream()))
+        return row, batch, epoch
+
+    def ccc(self, targets, predicts):
+        """The concordance correlation coefficient of two series (include/avcer_hip.h avcer_ccc; accuracy_utils.ccc_score):
+        tensors or arrays of equal element counts, read as float64; a one-dimensional strided view of a device float64 tensor (a
+        column of an [n, t, 2] table) is read where it lies.  Returns a float64 [1] tensor on the device.  No host synchronisation."""
+        def series(v):
+            if isinstance(v, torch.Tensor) and v.dtype == torch.float64 and v.device == torch.device(self.device) and v.dim() == 1 \
+                    and (v.numel() < 2 or v.stride(0) >= 1):
+                return v, int(v.stride(0)) if v.numel() > 1 else 1
+            return self._dev(v, torch.float64).reshape(-1), 1
+
+        (a, sa), (b, sb) = series(targets), series(predicts)
+        if a.numel() != b.numel():
+            raise ValueError(f"ccc: {a.numel()} targets and {b.numel()} predictions")
+        if sa != sb:
+            a, b, sa = a.contiguous(), b.contiguous(), 1
+        out = self._new(1, dtype=torch.float64)
+        self._check(self.lib.avcer_ccc(self.ctx, _ptr(a), _ptr(b), int(a.numel()), sa, _ptr(out), self._stream()))
+        return out
+
     def face_decode(self, loc, conf, landms, priors, image_size, variance=(0.1, 0.2)):
         """RetinaFace head outputs [P,4], [P,2], [P,10] + priors [P,4] -> dets [P,15] in pixels (before filtering)."""
         loc, conf = self._dev(loc, torch.float32), self._dev(conf, torch.float32)

@@ -109,7 +109,9 @@ enum {
  *      avcer_window_votes (the audio model over a corpus: softmax, argmax and per-file majority vote of the window logits) joined
  *      under 8 the same way: one more symbol, nothing that existed changed.
  *      avcer_set_skip_unread_rows, avcer_bneck_chain_keep, avcer_bneck_tail_keep (the block in front of a strided last block
- *      stores only the rows that block reads) joined under 8 the same way: three more symbols, nothing that existed changed. */
+ *      stores only the rows that block reads) joined under 8 the same way: three more symbols, nothing that existed changed.
+ *      avcer_window_losses, avcer_ccc (validation of audio checkpoints: the epoch loss of a corpus's window logits and the
+ *      concordance coefficient) joined under 8 the same way: two more symbols, nothing that existed changed. */
 #define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
@@ -905,6 +907,48 @@ int avcer_eval_confusion(avcer_ctx* ctx, const double* tables, const int32_t* la
 int avcer_window_votes(avcer_ctx* ctx, const float* logits, const int32_t* targets, const int32_t* file_off, int64_t n, int c,
                        int n_files, float* probs, int32_t* pred, int32_t* file_pred, int32_t* file_target, int32_t* file_onehot,
                        avcer_stream_t stream);
+
+/* Validation of an audio checkpoint: the losses of the window logits of a corpus, batched as the DataLoader batches them.
+ *   ref: src/audio/net_trainer/net_trainer.py:391-465 (iterate_model's loss bookkeeping), torch.nn.CrossEntropyLoss(weight,
+ *        label_smoothing) and SoftFocalLoss behind SoftFocalLossWrapper (src/audio/loss/loss.py:125-137, 165-166)
+ * logits f32 [n, c] (2 <= c <= AVCER_LOSS_MAX_CLASSES), targets i32 [n] in [0, c), weights f32 [c] or NULL (ones): DEVICE pointers.
+ * Batch b owns the rows [b * batch_size, min(n, (b + 1) * batch_size)): n_batches = ceil(n / batch_size), the last may be short.
+ * Per row i, in float64, every operation rounded on its own (y = targets[i], x = logits[i] widened):
+ *   m = max_k x[k];  d[k] = x[k] - m;  e[k] = exp(d[k]);  s = ((e[0] + e[1]) + ..) + e[c-1]
+ *   AVCER_LOSS_CE:          l = log(s);  q[k] = -(d[k] - l)  (the negative log-softmax);  a = w[y] * q[y];
+ *                           g = ((w[0] * q[0] + w[1] * q[1]) + ..) + w[c-1] * q[c-1];  u = w[y]
+ *                           row_loss[i] = (1 - eps) * a + (eps / c) * g          (reduction="none")
+ *   AVCER_LOSS_SOFT_FOCAL:  p = min(max(e[y] / s, 1e-7), 1 - 1e-7);  f = 1 (gamma == 0), (1 - p) * (1 - p) (gamma == 2), else
+ *                           pow(1 - p, gamma);  a = (w[y] * f) * (-log(p));  row_loss[i] = a          (the other classes add +-0)
+ * Per batch, with A, G, U the sums of a, g, u over its n_b rows in the FIXED order below:
+ *   CE: batch_loss[b] = (1 - eps) * (A / U) + (eps / c) * (G / U)  (reduction="mean" with weights);  SOFT_FOCAL: A / n_b.
+ * epoch[0] = sum_b(batch_loss[b] * batch_size) / n_batches -- net_trainer.py:441,460: the short last batch counts with the full
+ * batch size --; epoch[1] = sum_b(batch_loss[b] * n_b) / n, the row-weighted mean.
+ * Order of every sum over rows (and, for epoch, over batches): thread t of 256 adds its items t, t + 256, .. one after the other
+ * from 0.0; the 256 partial sums then fold in halves (s[t] += s[t + 128], then 64, .., 1).  There are no floating-point atomics:
+ * the outputs are a pure function of the inputs.  One launch, one block per batch; the block that finishes last (an integer
+ * ticket in `ticket`, i32 [1] on the device, zeroed by the call in stream order) reduces the batch losses to epoch[0..1].
+ * A target outside [0, c) makes its row, its batch and the epoch NaN; nothing is indexed with it.
+ * Outputs (device): row_loss f64 [n], batch_loss f64 [n_batches], epoch f64 [2].
+ * Limits (AVCER_EINVAL beyond them): 1 <= n <= AVCER_VOTES_MAX_WINDOWS, 2 <= c <= AVCER_LOSS_MAX_CLASSES, batch_size >= 1,
+ * kind one of the two, label_smoothing in [0, 1], gamma >= 0, both finite.  No host synchronisation. */
+#define AVCER_LOSS_CE 0
+#define AVCER_LOSS_SOFT_FOCAL 1
+#define AVCER_LOSS_MAX_CLASSES 16
+int avcer_window_losses(avcer_ctx* ctx, const float* logits, const int32_t* targets, const float* weights, int64_t n, int c, int kind,
+                        double label_smoothing, double gamma, int64_t batch_size, double* row_loss, double* batch_loss, double* epoch,
+                        int32_t* ticket, avcer_stream_t stream);
+
+/* The concordance correlation coefficient of two float64 series (accuracy_utils.ccc_score, src/audio/utils/accuracy_utils.py:124-152).
+ * targets, predicts f64 on the device, n elements each, element i at [i * stride] (stride 2 reads one column of an [n, t, 2]
+ * valence / arousal table: v_score / a_score).  Two passes in float64, sums in the order of avcer_window_losses:
+ *   mt = sum(t) / n, mp = sum(p) / n;  vy = t - mt, vx = p - mp;  sxy = sum(vx * vy), sxx = sum(vx * vx), syy = sum(vy * vy)
+ *   cor = sxy / (sqrt(sxx) * sqrt(syy));  sdt = sqrt(syy / n), sdp = sqrt(sxx / n)
+ *   out[0] = ((2 * cor) * sdt) * sdp / ((sdt * sdt + sdp * sdp) + (mt - mp) * (mt - mp))
+ * A constant series (and n = 1) gives 0 / 0 = NaN, as numpy does.  One launch of one block.  out f64 [1] on the device.
+ * Limits: 1 <= n, 1 <= stride, (n - 1) * stride < 2^40.  No host synchronisation. */
+int avcer_ccc(avcer_ctx* ctx, const double* targets, const double* predicts, int64_t n, int64_t stride, double* out,
+              avcer_stream_t stream);
 
 /* The contraction kernel itself (implicit-GEMM convolution with fused epilogue), exported for kernel-level
  * parity tests and micro-benchmarks:  Y[m, n] = act(scale[n] * sum_k A[m,k] * W[n,k] + bias[n] (+ R[m,n]))
