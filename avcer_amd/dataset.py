@@ -12,6 +12,11 @@ so frames and windows of different videos share passes here and every video stil
   audio, side stream   every waveform (resampled per video where `wav_sr` is set) into ONE device buffer, `chunk_spans` per
                        video shifted by the video's base, chunker + model in passes of <= max_windows_per_pass windows
   fusion               ONE `Engine.fuse_videos` launch for the set
+
+`run_dataset(stream_frames=N)` changes the shape of stage 0 alone: a video's frames arrive in passes of at most N (VideoJob.open), each
+pass goes through the detector, the resumable tracker and the tile cut (face_tiles.track_pass / pass_tiles, the step run._run takes per
+pass of one file) and is dropped before the next one is fetched; its tiles of track 00 join the same static passes, cut at the same
+places.  Device memory for frames is then one frame pass, whatever the length of the recording.
 """
 from __future__ import annotations
 
@@ -27,7 +32,7 @@ from . import dist as adist
 from . import io_formats
 from .audio_pipeline import check_window, chunk_spans, replicate_per_frame, resample_out_len, resample_plan
 from .engine import MODE_DEFAULT, MODE_F16X3, MODE_FP32
-from .face_tiles import check_detect_size, check_via_jpeg, scaled_detector
+from .face_tiles import check_detect_size, check_via_jpeg, pass_tiles, scaled_detector, track_pass
 from .fusion import MODEL_ORDER, covered_frames
 from .video_pipeline import _DevicePlan, _tables, clips_plan
 
@@ -37,7 +42,11 @@ class VideoJob:
     """One video of a set.  The metadata (what a container's header gives) is all that planning and sharding read; `load()` is
     called once, when the video's turn comes, and returns (frames_bgr u8 [n_frames, height, width, 3], wav) as `run_inference`
     takes them: wav float32 [n_samples] mono at the call's `sr`, or, with `wav_sr`, the source audio at that rate with
-    n_samples frames per channel.  `detections`: per-frame detection arrays instead of the call's detector."""
+    n_samples frames per channel.  `detections`: per-frame detection arrays instead of the call's detector.
+    `open(frames_per_pass)`: what `run_dataset(stream_frames=N)` calls instead of `load`, once, when the video's turn comes ->
+    (passes, wav): `passes` an iterable of u8 [k, height, width, 3] BGR batches in frame order (device tensors or host arrays, as
+    `load` may return either), every k <= frames_per_pass, the k's summing to n_frames; `wav` as `load` returns it.  The driver drops
+    a batch before it asks for the next one and calls `passes.close()`, where there is one, on every exit path."""
     name: str
     n_frames: int
     height: int
@@ -47,6 +56,41 @@ class VideoJob:
     wav_sr: Optional[int] = None
     load: Optional[Callable] = None
     detections: Optional[Sequence[np.ndarray]] = None
+    open: Optional[Callable] = None
+
+
+class _AviPasses:
+    """The frames of an open AviFile in passes of `per`, decoded on the device as they are asked for (video_job_from_avi's `open`).  The
+    file is closed behind the last pass, by `close()`, when a decode raises, and when the iterator is dropped."""
+
+    def __init__(self, avi, engine, per: int, frames_per_pass: int):
+        self.avi, self.engine, self.per, self.frames_per_pass, self.at = avi, engine, int(per), frames_per_pass, 0
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self.avi is None or self.at >= self.avi.n_frames:
+            self.close()
+            raise StopIteration
+        lo, hi = self.at, min(self.at + self.per, self.avi.n_frames)
+        try:
+            frames = self.avi.decode_frames(self.engine, lo, hi, bgr=True, frames_per_pass=self.frames_per_pass)
+        except BaseException:
+            self.close()
+            raise
+        self.at = hi
+        if hi >= self.avi.n_frames:
+            self.close()
+        return frames
+
+    def close(self):
+        avi, self.avi = getattr(self, "avi", None), None
+        if avi is not None:
+            avi.close()
+
+    def __del__(self):
+        self.close()
 
 
 def video_job_from_avi(path, detections: Optional[Sequence[np.ndarray]] = None, engine=None, frames_per_pass: int = 64,
@@ -56,7 +100,9 @@ def video_job_from_avi(path, detections: Optional[Sequence[np.ndarray]] = None, 
     container's headers and its chunk walk alone -- no frame is decoded; fps is int(rate / scale), as run.run_inference_file
     takes it.  `load` opens the file again when the video's turn comes, decodes the frames on the device (AviFile.decode_frames; on
     `engine`, default: the engine alive for the current device, which is the one run_dataset was given) and returns them with the
-    source audio, int16 [L, C] at the file's rate.  A file without an audio stream raises ValueError here."""
+    source audio, int16 [L, C] at the file's rate.  A file without an audio stream raises ValueError here.
+    `open(n)` (run_dataset(stream_frames=n)) opens the file again as well and hands out AviFile.decode_frames(engine, lo, lo + n) pass
+    after pass (_AviPasses) with the same audio: no more than n decoded frames of the file are alive, whatever its length and codec."""
     import os
 
     from .avi import open_avi
@@ -74,8 +120,18 @@ def video_job_from_avi(path, detections: Optional[Sequence[np.ndarray]] = None, 
             eng = engine if engine is not None else Engine.live()
             return avi.decode_frames(eng, bgr=True, frames_per_pass=frames_per_pass), avi.pcm
 
+    def open(per):
+        from .engine import Engine
+
+        avi = open_avi(path, opendml=opendml)
+        try:
+            return _AviPasses(avi, engine if engine is not None else Engine.live(), per, frames_per_pass), avi.pcm
+        except BaseException:
+            avi.close()
+            raise
+
     name = os.path.splitext(os.path.basename(path))[0]
-    return VideoJob(name, meta[0], meta[1], meta[2], meta[3], meta[4], wav_sr=meta[5], load=load, detections=detections)
+    return VideoJob(name, meta[0], meta[1], meta[2], meta[3], meta[4], wav_sr=meta[5], load=load, detections=detections, open=open)
 
 
 class DatasetResults(list):
@@ -104,19 +160,57 @@ def _n_audio(job: VideoJob, sr: int) -> int:
     return resample_out_len(int(job.n_samples), plan.o, plan.n)
 
 
+NO_TRACK_00 = "no face track 00 (os.listdir(<faces>/00) fails in the reference, get_prob_video.py:79)"
+
+
 def _track00(engine, job: VideoJob, dets):
     """Tracker + crop rectangles of one video (host code): the records and the rows of track 00 in frame order."""
     if len(dets) != job.n_frames:
         raise ValueError("one detection array per frame")
     records = engine.track_faces(dets, job.width, job.height, 0.4, 0.0)  # VideoTiler's tracker settings
     if not (len(records) and (records[:, 1] == 0).any()):
-        raise FileNotFoundError("no face track 00 (os.listdir(<faces>/00) fails in the reference, get_prob_video.py:79)")
+        raise FileNotFoundError(NO_TRACK_00)
     rows = np.where(records[:, 1] == 0)[0]
     return records, rows[np.argsort(records[rows, 0], kind="stable")]
 
 
-def _local_tables(engine, jobs, idx, plans, detector, m, sr, window, padding, max_frames, max_windows, passes, via_jpeg=False):
-    """Stages 0 to audio for the videos `idx` (ascending): (stat|dyn rows [sum frames, 14], window logits [sum windows, c])."""
+def check_stream_frames(value):
+    """run_dataset's `stream_frames`: None or an int >= 1 (a bool is refused, as run.run_inference_file refuses it), else ValueError."""
+    if value is not None and (isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or value < 1):
+        raise ValueError(f"stream_frames must be None or an integer >= 1, not {value!r}")
+    return None if value is None else int(value)
+
+
+def checked_passes(job: VideoJob, batches, per: int):
+    """The batches `job.open(per)` hands out as (first frame, frames as a tensor) pairs, each held to what the job's metadata says:
+    [k, height, width, 3] with k <= per, and n_frames in all -- the ValueError of the shape check on load() otherwise.  An empty
+    batch is passed over.  No batch is referenced here once the consumer asks for the next one."""
+    at, want = 0, (int(job.n_frames), int(job.height), int(job.width), 3)
+    for batch in batches:
+        frames = batch if torch.is_tensor(batch) else torch.from_numpy(np.ascontiguousarray(batch))
+        del batch
+        shape = tuple(frames.shape)
+        if len(shape) != 4 or shape[1:] != want[1:] or shape[0] > per or at + shape[0] > want[0]:
+            raise ValueError(f"video {job.name}: open({per}) gave frames {shape} at frame {at}, the job says passes of at most {per} "
+                             f"frames and {want} in all")
+        if shape[0]:
+            yield at, frames
+            at += shape[0]
+        del frames
+    if at != want[0]:
+        raise ValueError(f"video {job.name}: open({per}) gave {at} frames, the job says {want}")
+
+
+def pass_rows(frame_of_row: np.ndarray, a: int, b: int):
+    """Rows lo..hi-1 of a table whose frame column `frame_of_row` ascends are those of the frame pass [a, b): how known records (given
+    detections, or the first sweep's when the set is repeated in fp32) are dealt out to the passes."""
+    lo, hi = np.searchsorted(frame_of_row, (a, b), side="left")
+    return int(lo), int(hi)
+
+
+def _local_tables(engine, jobs, idx, plans, detector, m, sr, window, padding, max_frames, max_windows, passes, via_jpeg=False, stream=None):
+    """Stages 0 to audio for the videos `idx` (ascending): (stat|dyn rows [sum frames, 14], window logits [sum windows, c]).
+    `stream`: run_dataset's stream_frames."""
     dev = engine.device
     win_a = int(window * sr)
     w_off = np.concatenate([[0], np.cumsum([len(plans[i]["starts"]) for i in idx])]).astype(np.int64)
@@ -143,25 +237,7 @@ def _local_tables(engine, jobs, idx, plans, detector, m, sr, window, padding, ma
                     passes["audio"].append(b - a_done)
                     a_done = b
 
-        def static_passes(flush):
-            nonlocal pend, n_pend
-            while n_pend >= (1 if flush else max_frames):
-                tiles = pend[0] if len(pend) == 1 else torch.cat(pend)
-                _, p, f = engine.static_forward(tiles[:max_frames], m)
-                probs.append(p)
-                feats.append(f)
-                passes["static"].append(int(p.shape[0]))
-                pend = [tiles[max_frames:]] if tiles.shape[0] > max_frames else []
-                n_pend = int(pend[0].shape[0]) if pend else 0
-
-        for k, i in enumerate(idx):
-            job = jobs[i]
-            passes["at"] = i  # the job a failure in this loop belongs to
-            frames, wav = job.load()
-            frames = frames if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames))
-            if tuple(frames.shape) != (job.n_frames, job.height, job.width, 3):
-                raise ValueError(f"video {job.name}: load() gave frames {tuple(frames.shape)}, the job says "
-                                 f"{(job.n_frames, job.height, job.width, 3)}")
+        def queue_audio(k, i, job, wav):
             # audio first, on its own stream: it depends on nothing of the visual branch
             wav_t = wav if torch.is_tensor(wav) else torch.from_numpy(
                 np.ascontiguousarray(wav, dtype=np.float32) if job.wav_sr is None else np.ascontiguousarray(wav))
@@ -173,6 +249,88 @@ def _local_tables(engine, jobs, idx, plans, detector, m, sr, window, padding, ma
                                      f"n_samples / wav_sr give {plans[i]['n_audio']}")
                 wav_all[int(s_off[k]):int(s_off[k + 1])] = wav_d
             audio_passes(int(w_off[k + 1]), False)
+
+        def static_pass(tiles):
+            _, p, f = engine.static_forward(tiles, m)
+            probs.append(p)
+            feats.append(f)
+            passes["static"].append(int(p.shape[0]))
+
+        def static_passes(flush):
+            nonlocal pend, n_pend
+            while n_pend >= (1 if flush else max_frames):
+                tiles = pend[0] if len(pend) == 1 else torch.cat(pend)
+                static_pass(tiles[:max_frames])
+                pend = [tiles[max_frames:]] if tiles.shape[0] > max_frames else []
+                n_pend = int(pend[0].shape[0]) if pend else 0
+
+        # streamed, the pending tiles lie in ONE buffer of a static pass (or of every tile the videos can give, where that is less)
+        # instead of a list of per-video tensors: a video arrives as many small passes, and joining them as the list is joined would
+        # hold its tiles twice.  The passes are cut at the same places: behind every max_frames tiles of the set, and at its end.
+        if stream is not None:
+            room = sum(len(plans[i]["rows00"]) if "rows00" in plans[i] else int(jobs[i].n_frames) for i in idx)
+            queue = torch.empty((min(max_frames, room), 224, 224, 3), dtype=torch.uint8, device=dev)
+
+        def queue_tiles(tiles):
+            nonlocal n_pend
+            at, n = 0, int(tiles.shape[0])
+            while at < n:
+                take = min(n - at, max_frames - n_pend)
+                queue[n_pend:n_pend + take] = tiles[at:at + take]
+                n_pend, at = n_pend + take, at + take
+                if n_pend == max_frames:
+                    static_pass(queue)
+                    n_pend = 0
+
+        def stream_video(job, plan, batches):
+            """Stage 0 of one video in frame passes -> its present mask; the records are the plan's, or are gathered here."""
+            known = "records" in plan
+            if known:
+                records, rows = plan["records"], plan["rows00"]
+                frame00 = records[rows, 0]
+            else:
+                tracker, parts = engine.tracker(0.4, 0.0), []  # VideoTiler's tracker settings
+            present = np.zeros(job.n_frames, dtype=bool)
+            try:
+                for a, frames in checked_passes(job, batches, stream):
+                    if known:
+                        lo, hi = pass_rows(frame00, a, a + int(frames.shape[0]))
+                        r00 = records[rows[lo:hi]]
+                    else:
+                        parts.append(track_pass(tracker, frames, a, job.width, job.height, detector))
+                        r00 = parts[-1][parts[-1][:, 1] == 0]
+                    if len(r00):
+                        present[r00[:, 0]] = True
+                        queue_tiles(pass_tiles(engine, frames, r00, a, via_jpeg))
+                    del frames  # the pass is dropped before the next one is fetched
+            finally:
+                if not known:
+                    tracker.close()
+            if not known:  # every frame has been tracked: whether there is a track 00 is known now
+                records = np.concatenate(parts) if parts else np.zeros((0, 6), dtype=np.int64)
+                if not (records[:, 1] == 0).any():
+                    raise FileNotFoundError(NO_TRACK_00)
+                rows = np.where(records[:, 1] == 0)[0]
+                plan["records"], plan["rows00"] = records, rows[np.argsort(records[rows, 0], kind="stable")]
+            return present
+
+        for k, i in enumerate(idx):
+            job = jobs[i]
+            passes["at"] = i  # the job a failure in this loop belongs to
+            if stream is not None:
+                batches, wav = job.open(stream)
+                try:
+                    queue_audio(k, i, job, wav)
+                    presents.append(stream_video(job, plans[i], batches))
+                finally:  # an open recording is closed on every path out of its video
+                    getattr(batches, "close", lambda: None)()
+                continue
+            frames, wav = job.load()
+            frames = frames if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames))
+            if tuple(frames.shape) != (job.n_frames, job.height, job.width, 3):
+                raise ValueError(f"video {job.name}: load() gave frames {tuple(frames.shape)}, the job says "
+                                 f"{(job.n_frames, job.height, job.width, 3)}")
+            queue_audio(k, i, job, wav)
             # stage 0: the tiles of track 00, in frame order
             if "records" not in plans[i]:
                 dets = job.detections if job.detections is not None else detector.batch(frames, rgb=False)
@@ -191,7 +349,10 @@ def _local_tables(engine, jobs, idx, plans, detector, m, sr, window, padding, ma
             n_pend += len(rows)
             static_passes(False)
         passes["at"] = None
-        static_passes(True)
+        if stream is None:
+            static_passes(True)
+        elif n_pend:
+            static_pass(queue[:n_pend])
         audio_passes(int(w_off[-1]), True)
         # ragged LSTM plan over the whole set, then the per-frame tables by row gathers (video_pipeline._tables)
         plan = _DevicePlan(engine, None, None, clips_plan(presents, [jobs[i].fps for i in idx]))
@@ -206,13 +367,27 @@ def run_dataset(engine, jobs: Sequence[VideoJob], detector=None, *, mode: int = 
                 ce_weights_type: bool = True, ce_mask: bool = False, max_frames_per_pass: int = 2048,
                 max_windows_per_pass: int = 128, path_save_results: str = "", flag_save_prob: bool = False,
                 skip_failed: bool = False, distributed: bool = False, faces_via_jpeg: bool = False, detect_size=None,
-                detect_filter: str = "bilinear", flag_save_plot_pred: bool = False, plot_size: Sequence[int] = (200, 1200)) -> DatasetResults:
+                detect_filter: str = "bilinear", flag_save_plot_pred: bool = False, plot_size: Sequence[int] = (200, 1200),
+                stream_frames: Optional[int] = None) -> DatasetResults:
     """`run_inference` for every job of a set, with the videos sharing the GPU passes (module docstring).  Returns a
     `DatasetResults`: a list with one dict per job, in job order, holding `name` and the keys of `run_inference` -- av / vs / vd
     / a, compound_prob, static_probs, dynamic_logits, audio_rows, audio_frames, records -- with the bits `run_inference` gives for
     that video alone, in MODE_F16X3 and in MODE_FP32.  The real-time factor is one figure for the call, on the list's
     `real_time_factor` attribute: elapsed time over the summed duration of the videos that ran.  `flag_save_prob` writes each
-    video's CSV files as `run_inference` does (io_formats).  Heat maps are not produced on this path.
+    video's CSV files as `run_inference` does (io_formats).  Heat maps and `tracks=` are not part of this path, streamed or not.
+
+    `stream_frames`: None (the default) is the call as it always was: `job.load()` hands over the whole clip, and device memory
+    grows with the longest video.  An int N >= 1: every job's frames arrive through `job.open(N)` in passes of at most N frames;
+    a pass goes through the detector (or takes its share of the job's `detections`), the resumable tracker and the tile cut, its
+    tiles of track 00 join the pending tiles, and it is dropped before the next pass is fetched -- one frame pass of one video is
+    on the device at a time, whatever the lengths.  The static passes are cut where the in-memory call cuts them (they may end
+    inside a video, inside a frame pass, or span videos), so `passes` and every table are the in-memory call's, bit for bit, for
+    every N; the pending tiles lie in one buffer of min(`max_frames_per_pass`, the tiles the set can give) tiles.  Audio, LSTM,
+    fusion, files, `skip_failed`, the fp32 repeat (every job is opened a second time; the records are the first sweep's) and
+    `distributed` are untouched.  With a detector "no face track 00" is known behind the video's last pass and raises the same
+    FileNotFoundError there.  Anything but None or an int >= 1 (a bool, a float, a string), and a job without `open`, raise
+    ValueError before any work; a batch of the wrong shape or size, and a total other than `n_frames`, raise the ValueError of
+    load()'s shape check when they are met.
 
     `faces_via_jpeg` (for the call, as the other options): `run_inference`'s option of that name for every job -- the tiles of track
     00 are what reading stage 0's JPEG files back gives; the results are those of `run_inference(..., faces_via_jpeg=True)` for each
@@ -229,7 +404,8 @@ def run_dataset(engine, jobs: Sequence[VideoJob], detector=None, *, mode: int = 
     run_inference refuses (no `path_save_results`, neither rule, an empty plot rectangle) raises ValueError before any work.
 
     Passes: at most `max_frames_per_pass` tiles per static-CNN call (and LSTM windows per LSTM call), at most
-    `max_windows_per_pass` audio windows per audio call; device memory for tiles is one pass plus one video.
+    `max_windows_per_pass` audio windows per audio call; device memory for tiles is one pass plus one video, beside that video's
+    decoded frames -- with `stream_frames` one pass plus one frame pass's tiles, beside that frame pass.
 
     Range contract: the packed computation sits inside ONE `engine.guarded(mode, ...)`.  One counter cannot say which video
     overflowed, so a set in which any activation leaves fp16's range is repeated in MODE_FP32 AS A WHOLE (every job is loaded
@@ -247,6 +423,10 @@ def run_dataset(engine, jobs: Sequence[VideoJob], detector=None, *, mode: int = 
     `dist.all_gather_ragged`; fusion runs replicated over the whole set in job order, and every rank returns every video."""
     start_time = time.time()
     jobs = list(jobs)
+    stream_frames = check_stream_frames(stream_frames)
+    for job in jobs if stream_frames is not None else ():
+        if getattr(job, "open", None) is None:
+            raise ValueError(f"video {job.name}: stream_frames={stream_frames} needs a job with `open` (VideoJob.open, video_job_from_avi)")
     if padding not in ("mean", "constant", "repeat"):
         raise ValueError(f"padding={padding!r}")
     if max_frames_per_pass < 1 or max_windows_per_pass < 1:
@@ -309,7 +489,7 @@ def run_dataset(engine, jobs: Sequence[VideoJob], detector=None, *, mode: int = 
                 return (torch.zeros(0, 14, device=engine.device), torch.zeros(0, max(engine.audio_classes, 1), device=engine.device))
             try:
                 return _local_tables(engine, jobs, mine, plans, detector, m, sr, window, padding, int(max_frames_per_pass),
-                                     int(max_windows_per_pass), passes, bool(faces_via_jpeg))
+                                     int(max_windows_per_pass), passes, bool(faces_via_jpeg), stream_frames)
             except (ValueError, FileNotFoundError) as e:
                 bad = passes["at"]
                 if bad is None:

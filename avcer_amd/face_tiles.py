@@ -537,6 +537,22 @@ def pass_rects(records: np.ndarray, frame_base: int = 0) -> np.ndarray:
     return rects
 
 
+def track_pass(tracker, frames, frame_base: int, width: int, height: int, detector=None, detections=None) -> np.ndarray:
+    """Stage 0 of one frame pass, stated once for run._run and for dataset's streamed jobs: the detector on the pass's frames (or the
+    pass's slice of the video's given `detections`) -> the resumable tracker (Engine.tracker) -> the pass's records, their frame
+    index counted over the whole video.  `frame_base`: the video's frame the pass starts at."""
+    dets = detections[frame_base:frame_base + int(frames.shape[0])] if detections is not None else detector.batch(frames, rgb=False)
+    return tracker.push(dets, width, height)
+
+
+def pass_tiles(engine, frames_bgr, records: np.ndarray, frame_base: int = 0, via_jpeg: bool = False):
+    """The tiles of `records` cut from the frames of the pass that starts at frame `frame_base`: u8 [n,224,224,3] RGB on the device, in
+    record order -- the raw crops, or with `via_jpeg` what reading stage 0's files back gives (roundtrip_face_tiles, no file written)."""
+    if via_jpeg:
+        return roundtrip_face_tiles(engine, frames_bgr, records, frame_base=frame_base)[0]
+    return engine.crop_tiles(frames_bgr, torch.from_numpy(pass_rects(records, frame_base).astype(np.int32)), bgr=True)
+
+
 def roundtrip_face_tiles(engine, frames_bgr, records: np.ndarray, save_path: Optional[str] = None, video_name: Optional[str] = None,
                          quality: int = 95, entropy: str = "host", frame_base: int = 0):
     """The tiles of `records` as the reference's stage 1 reads them back from stage 0's files (jpeg.roundtrip_tiles: the rectangles

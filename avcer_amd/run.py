@@ -25,8 +25,8 @@ import torch
 from . import io_formats, jpeg
 from .audio_pipeline import audio_forward, check_window, replicate_per_frame, resample_plan
 from .engine import MODE_DEFAULT
-from .face_tiles import (check_detect_size, check_tracks, check_via_jpeg, pass_rects, roundtrip_face_tiles, scaled_detector, select_tracks,
-                         write_face_crops)
+from .face_tiles import (check_detect_size, check_tracks, check_via_jpeg, pass_rects, pass_tiles, roundtrip_face_tiles, scaled_detector,
+                         select_tracks, track_pass, write_face_crops)
 from .fusion import MODEL_ORDER, fuse, fuse_tracks
 from .video_pipeline import lstm_step, tracks_plan, visual_from_static, visual_from_static_tracks
 
@@ -106,8 +106,8 @@ def run_inference_file(engine, path, detector=None, detections: Optional[Sequenc
     44.1 kHz stereo: 318 MB), and the audio windows go through the model `audio_windows_per_pass` at a time (streamed calls only).
     With `path_save_video` the file is decoded a second time behind the fusion, which the labels need.  "No face track 00" is
     known at the end of the sweep and raises the same FileNotFoundError there.  Anything but None or an int >= 1 (0, a negative, a
-    bool, a float) raises ValueError naming stream_frames before the file is opened.  run_dataset / video_job_from_avi stay
-    in-memory.
+    bool, a float) raises ValueError naming stream_frames before the file is opened.  A set of recordings: run_dataset(stream_frames=N)
+    with video_job_from_avi jobs, the same passes with the videos sharing the GPU passes behind them.
     `tracks=` (run_inference) is refused, where it is refused, before the file is opened, and holds for both paths: streamed, a
     named track that never appeared raises its FileNotFoundError at the end of the sweep, as "no face track 00" does.
     `detect_size=` / `detect_filter=` (run_inference) hold for both paths too: a bad value is refused before the file is opened, an
@@ -320,8 +320,7 @@ def _run(engine, src: _Source, wav, fps, detector, detections, o: _Options, chec
             for k, a in enumerate(range(0, total, per)):
                 frames = src.decode(a)
                 if first:
-                    dets = detections[a:a + per] if detections is not None else detector.batch(frames, rgb=False)  # get_face_images.py:49
-                    records = tracker.push(dets, width, height)
+                    records = track_pass(tracker, frames, a, width, height, detector, detections)  # get_face_images.py:49
                     passes.append(records)
                 else:
                     records = host["passes"][k]
@@ -331,7 +330,7 @@ def _run(engine, src: _Source, wav, fps, detector, detections, o: _Options, chec
                         tiles, paths = roundtrip_face_tiles(engine, frames, records, *(save if first else (None, None)), entropy=o.jpeg_entropy,
                                                             frame_base=a)
                     else:
-                        tiles = engine.crop_tiles(frames, torch.from_numpy(pass_rects(records, a).astype(np.int32)), bgr=True)
+                        tiles = pass_tiles(engine, frames, records, a)
                         paths = write_face_crops(engine, frames, records, *save, entropy=o.jpeg_entropy, frame_base=a) if first and save[0] else None
                     if first and save[0]:
                         files.extend(paths)
