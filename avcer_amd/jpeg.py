@@ -367,14 +367,20 @@ def _check_entropy(entropy):
         raise ValueError(f'entropy must be "host" or "device", not {entropy!r}')
 
 
-def decode_tiles(engine, blobs, threads: int = 0, entropy: str = "host"):
+def decode_tiles(engine, blobs, threads: int = 0, entropy: str = "host", out=None):
     """The files `blobs` -> (tiles u8 [n,224,224,3] RGB on the device, paths): tile i is
     Image.open(file i).convert("RGB").resize((224, 224), NEAREST); paths[i] is "device" or "pil".
     entropy="device": the host parses the headers only and the files' bytes cross, avcer_jpeg_unpack Huffman-decodes them on the
-    device (`threads` then serves the header pass); tiles and paths are the same."""
+    device (`threads` then serves the header pass); tiles and paths are the same.
+    `out`: the tiles are written there and it is returned -- a contiguous u8 [n,224,224,3] on the engine's device, typically the
+    slice buffer[a:a + n] of a larger tile buffer (video_corpus.run_video_corpus' pending tiles); nothing outside it is touched.
+    Anything else raises ValueError before any work."""
     _check_entropy(entropy)
     n = len(blobs)
-    tiles = torch.empty(n, 224, 224, 3, dtype=torch.uint8, device=engine.device)
+    if out is not None and not (torch.is_tensor(out) and tuple(out.shape) == (n, 224, 224, 3) and out.dtype == torch.uint8
+                                and out.device == engine.device and out.is_contiguous()):
+        raise ValueError(f"decode_tiles: out must be a contiguous uint8 [{n},224,224,3] on {engine.device}")
+    tiles = torch.empty(n, 224, 224, 3, dtype=torch.uint8, device=engine.device) if out is None else out
     if n == 0:
         return tiles, []
     if entropy == "device":
