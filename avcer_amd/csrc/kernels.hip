@@ -155,7 +155,8 @@ __global__ void face_rank_kernel(const float* __restrict__ dets, int P, float co
 // sort of the next power of two.  The counting kernel above does P comparisons per candidate -- 90 M per 640 x 360 frame when
 // every prior is a candidate (synthetic detector weights; 14.7 ms per 750 frames, profiles/r06_face_kernel_stats_before.csv) --
 // the sort 105 compare-exchange passes over 16 K keys.  Key = the score's bits made monotone (sign flip), prior index + 1 in the
-// low word: a descending sort visits equal scores HIGHER index first, the rule above; non-candidates are key 0 and sink.
+// low word: a descending sort visits equal scores HIGHER index first, the rule above (-0.0 is keyed as +0.0: they compare equal, in
+// numpy and in the counting kernel); non-candidates are key 0 and sink.
 constexpr int SORT_THREADS = 1024;
 constexpr int SORT_MAX = 16384;  // keys held in LDS (128 KiB); frames with more priors keep the counting kernel
 
@@ -210,6 +211,7 @@ __global__ void __launch_bounds__(SORT_THREADS) face_sort_kernel(const float* __
             const int i = i0 + u * SORT_THREADS + tid;
             if (i < P && sc[u] > conf_thresh) {
                 unsigned v = __float_as_uint(sc[u]);
+                if (v == 0x80000000u) v = 0u;  // -0.0 == +0.0 is a tie for numpy and for the counting kernel: index order, not sign
                 v = (v & 0x80000000u) ? ~v : (v | 0x80000000u);
                 key[atomicAdd(&cnt, 1)] = ((unsigned long long)v << 32) | (unsigned)(i + 1);
             }

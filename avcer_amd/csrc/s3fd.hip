@@ -215,6 +215,7 @@ __global__ void __launch_bounds__(ORDER_THREADS) s3fd_order_kernel(const float* 
         const float s = d[5L * i + 4];
         if (s > conf_thresh) {
             unsigned v = __float_as_uint(s);
+            if (v == 0x80000000u) v = 0u;  // -0.0 == +0.0 is a tie for numpy: index order decides, not the sign bit
             v = (v & 0x80000000u) ? ~v : (v | 0x80000000u);
             gk[atomicAdd(&cnt, 1)] = ((unsigned long long)v << 32) | (unsigned)(i + 1);
         }

@@ -41,14 +41,15 @@ def decode(loc, priors, variance=VARIANCE) -> np.ndarray:
     """box_utils.py:210-228 in float32: centre/size -> corners."""
     v0, v1 = np.float32(variance[0]), np.float32(variance[1])
     out = np.empty((len(loc), 4), dtype=np.float32)
-    for i in range(len(loc)):
-        cx = priors[i, 0] + loc[i, 0] * v0 * priors[i, 2]
-        cy = priors[i, 1] + loc[i, 1] * v0 * priors[i, 3]
-        w = priors[i, 2] * np.exp(loc[i, 2] * v1)
-        h = priors[i, 3] * np.exp(loc[i, 3] * v1)
-        x0 = cx - w / np.float32(2)
-        y0 = cy - h / np.float32(2)
-        out[i] = (x0, y0, w + x0, h + y0)
+    with np.errstate(all="ignore"):   # exp may overflow to inf (then x0 = -inf and x1 = inf - inf = NaN) or underflow to 0
+        for i in range(len(loc)):
+            cx = priors[i, 0] + loc[i, 0] * v0 * priors[i, 2]
+            cy = priors[i, 1] + loc[i, 1] * v0 * priors[i, 3]
+            w = priors[i, 2] * np.exp(loc[i, 2] * v1)
+            h = priors[i, 3] * np.exp(loc[i, 3] * v1)
+            x0 = cx - w / np.float32(2)
+            y0 = cy - h / np.float32(2)
+            out[i] = (x0, y0, w + x0, h + y0)
     return out
 
 
@@ -62,25 +63,29 @@ def decode_landm(pre, priors, variance=VARIANCE) -> np.ndarray:
     return out
 
 
-def nms(dets, thresh, top_k, stable=False):
-    """py_cpu_nms.py:11-39 (areas with the +1 pixel convention, float32).  `stable`: the same expression with
-    `argsort(kind="stable")`, which pins the order of exactly tied scores (higher index first after the reversal);
-    numpy's default sort leaves it unspecified on long arrays."""
+def nms(dets, thresh, top_k, stable=False, ious=None):
+    """py_cpu_nms.py:11-39 (areas with the +1 pixel convention) in the precision of `dets`: float32 is the reference's
+    arithmetic, float64 the yardstick.  `stable`: the same expression with `argsort(kind="stable")`, which pins the order
+    of exactly tied scores (higher index first after the reversal); numpy's default sort leaves it unspecified on long
+    arrays.  `ious` collects the overlaps of every kept box with the boxes still behind it.
+    Maxima and minima are numpy's, which PROPAGATE a NaN operand (Python's max / min return whichever operand the
+    comparison leaves, fmaxf / fminf drop the NaN): a box with a NaN corner has a NaN overlap with every other box."""
+    dt = dets.dtype.type
     x1, y1, x2, y2, scores = (dets[:, c] for c in range(5))
-    areas = (x2 - x1 + 1) * (y2 - y1 + 1)
-    order = list((scores.argsort(kind="stable") if stable else scores.argsort())[: -top_k - 1: -1])
     keep = []
-    while order:
-        i = order.pop(0)
-        keep.append(int(i))
-        rest = []
-        for j in order:
-            w = max(np.float32(0.0), min(x2[i], x2[j]) - max(x1[i], x1[j]) + 1)
-            h = max(np.float32(0.0), min(y2[i], y2[j]) - max(y1[i], y1[j]) + 1)
-            inter = np.float32(w * h)
-            if inter / (areas[i] + areas[j] - inter) <= np.float32(thresh):
-                rest.append(j)
-        order = rest
+    with np.errstate(all="ignore"):   # non-finite and degenerate boxes are inputs like any other (tests/golden/detect_edges.npz)
+        areas = (x2 - x1 + 1) * (y2 - y1 + 1)
+        order = (scores.argsort(kind="stable") if stable else scores.argsort())[: -top_k - 1: -1]
+        while order.size:
+            i, rest = order[0], order[1:]
+            keep.append(int(i))
+            w = np.maximum(dt(0.0), np.minimum(x2[i], x2[rest]) - np.maximum(x1[i], x1[rest]) + 1)
+            h = np.maximum(dt(0.0), np.minimum(y2[i], y2[rest]) - np.maximum(y1[i], y1[rest]) + 1)
+            inter = w * h
+            ovr = inter / (areas[i] + areas[rest] - inter)
+            if ious is not None:
+                ious.append(ovr)
+            order = rest[ovr <= dt(thresh)]
     return keep
 
 

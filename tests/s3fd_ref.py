@@ -169,22 +169,26 @@ def num_priors(h: int, w: int) -> int:
 
 
 # ------------------------------------------------------------------------------------------------ Detect + the predictor's loop
-def decode(loc, priors, variances=VARIANCE):
-    """utils.py:6-24, operation by operation, in float32 torch (so that exp is the reference's)."""
-    loc, priors = torch.as_tensor(np.asarray(loc, np.float32)), torch.as_tensor(np.asarray(priors, np.float32))
+def decode(loc, priors, variances=VARIANCE, dtype=np.float32):
+    """utils.py:6-24, operation by operation, in float32 torch (so that exp is the reference's); dtype=np.float64 is the yardstick."""
+    loc, priors = torch.as_tensor(np.asarray(loc, dtype)), torch.as_tensor(np.asarray(priors, dtype))
     boxes = torch.cat((priors[:, :2] + loc[:, :2] * variances[0] * priors[:, 2:], priors[:, 2:] * torch.exp(loc[:, 2:] * variances[1])), 1)
     boxes[:, :2] -= boxes[:, 2:] / 2
     boxes[:, 2:] += boxes[:, :2]
     return boxes.numpy()
 
 
-def nms_np(boxes, scores, overlap, top_k, ious=None):
-    """utils.py:94-128; `ious` collects every IoU the loop evaluates."""
+@np.errstate(all="ignore")   # non-finite and degenerate boxes are inputs like any other (tests/golden/detect_edges.npz)
+def nms_np(boxes, scores, overlap, top_k, ious=None, stable=False):
+    """utils.py:94-128 in the precision of `boxes`; `ious` collects every IoU the loop evaluates.  numpy's maxima and minima
+    propagate a NaN operand, so a box with a NaN corner has a NaN overlap with every other box and `ovr <= overlap` drops it.
+    `stable`: the same with `argsort(kind="stable")`, the kernels' rule for tied scores (higher index first after the reversal);
+    numpy's default sort leaves their order unspecified."""
     if scores.shape[0] == 0:
         return []
     areas = (boxes[:, 2] - boxes[:, 0]) * (boxes[:, 3] - boxes[:, 1])
     x1, y1, x2, y2 = boxes[:, 0], boxes[:, 1], boxes[:, 2], boxes[:, 3]
-    order = scores.argsort()[: -top_k - 1: -1]
+    order = (scores.argsort(kind="stable") if stable else scores.argsort())[: -top_k - 1: -1]
     keep = []
     while order.size > 0:
         i = order[0]
@@ -199,13 +203,15 @@ def nms_np(boxes, scores, overlap, top_k, ious=None):
     return keep
 
 
-def detect(loc, conf, priors, im_h, im_w, threshold, top_k=750, conf_thresh=0.05, nms_thresh=0.3, nms_top_k=5000, ious=None):
-    """Detect.__call__ for one frame and class 1, then the predictor's loop: [k,5] float32 = x0, y0, x1, y1 (pixels), score."""
-    boxes = decode(loc, priors)
+def detect(loc, conf, priors, im_h, im_w, threshold, top_k=750, conf_thresh=0.05, nms_thresh=0.3, nms_top_k=5000, ious=None,
+           dtype=np.float32, stable=False):
+    """Detect.__call__ for one frame and class 1, then the predictor's loop: [k,5] float32 = x0, y0, x1, y1 (pixels), score.
+    dtype=np.float64: boxes, areas and overlaps in float64 (scores and the thresholds stay the float32 values they are)."""
+    boxes = decode(loc, priors, dtype=dtype)
     scores = np.asarray(conf, np.float32)[:, 1]
     mask = scores > np.float32(conf_thresh)
     boxes, scores = boxes[mask], scores[mask]
-    keep = nms_np(boxes, scores, np.float32(nms_thresh), nms_top_k, ious)[:top_k]
+    keep = nms_np(boxes, scores, np.float32(nms_thresh), nms_top_k, ious, stable)[:top_k]
     rows = []
     for i in keep:
         if not scores[i] >= np.float32(threshold):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from avcer_amd import face_tiles as ft
+import detect_edge_cases as ec
 from oracle import face as of
 
 G = np.load(os.path.join(os.path.dirname(__file__), "golden", "face.npz"))
@@ -54,6 +55,34 @@ def test_oracle_detections_empty():
 def test_nms(fn):
     assert list(fn(G["nms_dets"], 0.4, 5000)) == list(G["nms_keep_04"])
     assert list(fn(G["nms_dets"], 0.2, 50)) == list(G["nms_keep_02_top50"])
+
+
+@pytest.mark.parametrize("name", ec.R_CASES)
+def test_oracle_tail_on_non_finite_degenerate_and_boundary_cases(name):
+    """tests/golden/detect_edges.npz: what py_cpu_nms between the predictor's own statements keeps of NaN / inf scores, NaN / inf boxes,
+    zero-size and inverted boxes, an overlap exactly on nms_thresh and scores exactly on the two thresholds.  The float32 oracle
+    reproduces every case; where nothing ties and nothing sits on a comparison the float64 oracle decides the same."""
+    kind, frames, par, want = ec.retina_case(name)
+    assert kind in ("plain", "boundary", "tie_rule") and par["nms_top_k"] <= 6144 and par["top_k"] <= 1024
+    assert [k.tolist() for k in ec.retina_oracle(name, np.float32)] == [k.tolist() for k in want]
+    if kind == "plain":
+        assert [k.tolist() for k in ec.retina_oracle(name, np.float64)] == [k.tolist() for k in want]
+
+
+@pytest.mark.parametrize("variant", ec.B_VARIANTS)
+def test_oracle_detections_on_overflowing_decodes(variant):
+    """`loc * variance` of 80 (huge, finite), 100 (w = inf, so x0 = -inf and x1 = NaN) and -110 (a zero-size box), NaN in loc and in
+    landms, through RetinaFacePredictor.__call__; the non-finite box scored first, in the middle and last."""
+    E = ec.E
+    size = tuple(int(v) for v in E["b_size"])
+    pri = of.prior_boxes(size)
+    with np.errstate(all="ignore"):
+        boxes = of.decode(E["b_loc"], pri) * np.array([size[1], size[0]] * 2, np.float32)
+        got = of.detections(E["b_loc"], E[f"b_conf_{variant}"], E["b_landms"], size, threshold=float(E["b_threshold"]))
+    ec.assert_decoded(boxes, E["b_boxes"])
+    ref = E[f"b_pred_{variant}"]
+    ec.assert_decoded(got[:, :4], ref[:, :4])
+    assert ec.same_bits(got[:, 4:], ref[:, 4:]) and (~np.isfinite(ref)).any()
 
 
 def test_tracker_and_rects_match_reference_process():

@@ -354,6 +354,32 @@ def test_native_tracker_equals_the_python_tracker_frame_by_frame():
     assert _track_native(lib, outside, w, h)[0] == -1 and _track_python(outside, w, h)[0] == -1
 
 
+def test_native_tracker_on_non_finite_detection_rows():
+    """A detection row whose decode overflowed (tests/test_gpu_detect_edges.py: such rows do leave the detector) in the tracker and the
+    crop: numpy's float32 -> int64 cast turns NaN and +-inf into INT64_MIN, a NaN area is neither below the minimum nor a track.  The
+    native call ends where the Python statements of avcer_amd/face_tiles.py end: no track id for a NaN area, an empty crop for a corner
+    at INT64_MIN on the far side -- and a valid crop from column 0 for x0 = -inf, whose area is inf."""
+    import warnings
+
+    lib = _host_lib()
+    w, h = 640, 360
+    nan, inf = float("nan"), float("inf")
+    cases = {"nan x0": [nan, 10, 60, 50], "nan y1": [10, 10, 60, nan], "all nan": [nan] * 4, "inf x1": [10, 10, inf, 50],
+             "-inf x0": [-inf, 10, 60, 50], "-inf x0, inf x1": [-inf, 10, inf, 50], "inf both": [inf, 10, inf, 50]}
+    seen = set()
+    for name, box in cases.items():
+        dets = [np.array([[20, 20, 80, 90, 0.9] + [0] * 10], np.float32), np.array([[21, 20, 81, 90, 0.9] + [0] * 10, box + [0.8] + [0] * 10], np.float32)]
+        with warnings.catch_warnings(), np.errstate(all="ignore"):
+            warnings.simplefilter("ignore")                                    # "invalid value encountered in cast" is the point
+            rc_p, rec_p = _track_python(dets, w, h)
+        rc_n, rec_n = _track_native(lib, dets, w, h)
+        assert rc_n == rc_p, (name, rc_n, rc_p)
+        if rc_p == 0:
+            np.testing.assert_array_equal(rec_n, rec_p, err_msg=name)
+        seen.add(rc_p)
+    assert seen == {0, -1}
+
+
 def test_native_tracker_reproduces_the_reference_generated_records():
     from test_face_cpu import G, golden_script
 

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import detect_edge_cases as ec
 import s3fd_ref
 from avcer_amd import _lib, build, packing, synth
 from avcer_amd import face_tiles as ft
@@ -135,6 +136,28 @@ def test_detect_restatement_reproduces_the_reference(which):
         np.testing.assert_array_equal(got, DET[f"{which}_dets{t}"])
         assert len(got) == DET[f"{which}_counts"][t]
     assert DET["full_counts"][1] == 0 and int((DET["conf"][3, :, 1] > 0.05).sum()) > 64
+
+
+@pytest.mark.parametrize("name", ec.S_CASES)
+def test_detect_restatement_on_non_finite_degenerate_and_boundary_cases(name):
+    """tests/golden/detect_edges.npz: Detect and the predictor's loop on NaN / inf scores, NaN boxes, a box whose area overflows,
+    zero-size and inverted boxes (S3FD's areas have no "+1": 0 / 0 between two zero-size twins), an overlap exactly on nms_thresh and
+    scores exactly on the two thresholds.  The boxes are dyadic, so the rows are exact: float32 reproduces every case bit for bit, and
+    float64 does where nothing ties and nothing sits on a comparison."""
+    kind, loc, conf, priors, size, par, want = ec.s3fd_case(name)
+    assert kind in ("plain", "boundary", "tie_rule") and par["nms_top_k"] <= 6144 and par["top_k"] <= 1024
+    assert all(ec.same_bits(g, w) for g, w in zip(ec.s3fd_oracle(name, np.float32), want))
+    if kind == "plain":
+        assert all(ec.same_bits(g, w) for g, w in zip(ec.s3fd_oracle(name, np.float64), want))
+
+
+@pytest.mark.parametrize("variant", ec.B_VARIANTS)
+def test_detect_restatement_on_overflowing_decodes(variant):
+    E = ec.E
+    h, w = (int(v) for v in E["sb_size"])
+    want = E[f"sb_rows_{variant}"]
+    got = s3fd_ref.detect(E["sb_loc"], E[f"sb_conf_{variant}"], E["sb_priors"], h, w, float(E["sb_threshold"]))
+    assert ec.same_bits(got, want)   # (float64 is no yardstick here: e^100 is finite in it, and the NaN corner never appears)
 
 
 def test_prior_boxes_equal_the_reference_bit_for_bit():
