@@ -216,7 +216,15 @@ int launch_s3fd_stem(avcer_ctx* ctx, const uint8_t* frames, int n, int h, int w,
 // f * P + row0; inv: scratch for nb * h * w inverse L2 norms (the level is normalised) or null (it is not)
 int launch_s3fd_head(avcer_ctx* ctx, const void* x, int kind, float* inv, const float* wt, const float* b, int nb, int h, int w, int c,
                      int n_out, int row0, int P, float* loc, float* conf, hipStream_t st);
-// Detect + the predictor's loop: decode, order, NMS; ws = s3fd_detect_ws_bytes(T, P, nms_top_k) bytes
+
+// ---- detect_tail.hip (decode, order and NMS of both detectors)
+// RetinaFace: loc / conf / landms [T, P, ..] -> dets [T, P, 15]; dets -> out [T, top_k, 15], out_n [T] (order [T, nms_top_k] and
+// count [T] are scratch)
+int k_face_decode(avcer_ctx*, const float* loc, const float* conf, const float* landms, const float* priors, int T, int P, int im_h,
+                  int im_w, float var0, float var1, float* dets, hipStream_t);
+int k_face_nms(avcer_ctx*, const float* dets, int T, int P, float conf_thresh, float nms_thresh, int nms_top_k, int top_k,
+               float threshold, int32_t* order, int32_t* count, float* out, int32_t* out_n, hipStream_t);
+// S3FD's Detect + the predictor's loop: decode, order, NMS; ws = s3fd_detect_ws_bytes(T, P, nms_top_k) bytes
 size_t s3fd_detect_ws_bytes(int T, int P, int nms_top_k);
 int launch_s3fd_detect(avcer_ctx* ctx, const float* loc, const float* conf, const float* priors, int T, int P, int im_h, int im_w, float var0,
                        float var1, float conf_thresh, float nms_thresh, int nms_top_k, int top_k, float threshold, void* ws, float* out,
@@ -273,10 +281,6 @@ int k_audio_chunks(avcer_ctx*, const float* wav, const int32_t* starts, const in
 int k_split_weights(avcer_ctx*, const float* w, bf16_t* out, size_t n, hipStream_t);
 int k_split_weight_rows(avcer_ctx*, const float* w, bf16_t* out, int n, int k, hipStream_t);
 int k_weight_frags(avcer_ctx*, const bf16_t* rows, bf16_t* out, int n, int k, hipStream_t);
-int k_face_decode(avcer_ctx*, const float* loc, const float* conf, const float* landms, const float* priors, int T, int P, int im_h,
-                  int im_w, float var0, float var1, float* dets, hipStream_t);
-int k_face_nms(avcer_ctx*, const float* dets, int T, int P, float conf_thresh, float nms_thresh, int nms_top_k, int top_k,
-               float threshold, int32_t* order, int32_t* count, float* out, int32_t* out_n, hipStream_t);
 int k_face_pre(avcer_ctx*, const uint8_t* frames, int n, int h, int w, int ph, int pw, int rgb, void* out, int bf16, hipStream_t);
 int k_upsample_add(avcer_ctx*, void* y, const void* coarse, int n, int h, int w, int ch, int cw, int c, int kind, hipStream_t);
 int k_face_head(avcer_ctx*, const float* hd, int ld, int n, int hw, int row0, int P, float* loc, float* conf, float* landms,

@@ -80,242 +80,7 @@ __global__ void pack_nchw_kernel(const float* __restrict__ in, T* __restrict__ o
     else st4<T>(out, idx * 4, v);
 }
 
-// ------------------------------------------------------------------------------------------------ face stage (row f4)
-// retina_face_predictor.py:70-82 with box_utils.py:210-249: every prior's box, score and five landmarks in pixels.
-// The arithmetic follows torch's evaluation order in f32 with contraction off, so only expf may differ (<= 2 ulp).
-__global__ void face_decode_kernel(const float* __restrict__ loc, const float* __restrict__ conf,
-                                   const float* __restrict__ landms, const float* __restrict__ priors, int P, float im_w,
-                                   float im_h, float var0, float var1, float* __restrict__ dets) {
-#pragma clang fp contract(off)
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= P) return;
-    {   // grid.y = frame of a batch: every frame has its own P rows of loc / conf / landms / dets, the priors are shared
-        const long f = blockIdx.y;
-        loc += f * P * 4; conf += f * P * 2; landms += f * P * 10; dets += f * P * 15;
-    }
-    const float4 pr = *reinterpret_cast<const float4*>(priors + 4L * i);
-    const float4 l = *reinterpret_cast<const float4*>(loc + 4L * i);
-    const float cx = pr.x + (l.x * var0) * pr.z;
-    const float cy = pr.y + (l.y * var0) * pr.w;
-    const float w = pr.z * expf(l.z * var1);
-    const float h = pr.w * expf(l.w * var1);
-    const float x0 = cx - w / 2.0f, y0 = cy - h / 2.0f;
-    float* o = dets + 15L * i;
-    o[0] = x0 * im_w;
-    o[1] = y0 * im_h;
-    o[2] = (w + x0) * im_w;
-    o[3] = (h + y0) * im_h;
-    o[4] = conf[2L * i + 1];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        o[5 + 2 * k] = (pr.x + (landms[10L * i + 2 * k] * var0) * pr.z) * im_w;
-        o[6 + 2 * k] = (pr.y + (landms[10L * i + 2 * k + 1] * var0) * pr.w) * im_h;
-    }
-}
-
-// retina_face_predictor.py:86-108 + py_cpu_nms.py:11-39 on the GPU: confidence floor, descending-score order, greedy
-// NMS with the "+1 pixel" areas, top-k, final threshold.  Two kernels per batch of frames:
-//   face_rank_kernel   position of every candidate (score > conf_thresh) in the descending order of py_cpu_nms
-//                      (`scores.argsort()[: -top_k - 1 : -1]`: an ascending sort read backwards, so wherever that sort
-//                      keeps tied scores in index order -- numpy's default does on short arrays, `kind="stable"` always
-//                      -- ties are visited HIGHER prior index first; that is the rule here) by counting, written as
-//                      order[rank] = prior index
-//   face_nms_kernel    one workgroup per frame: the top nms_top_k boxes sit in LDS, boxes are visited in order, a kept
-//                      box clears every later box whose IoU with it exceeds the threshold (one barrier per KEPT box)
-// f32 arithmetic in numpy's evaluation order, contraction off, so the keep decisions are the reference's.
-__global__ void face_rank_kernel(const float* __restrict__ dets, int P, float conf_thresh, int nms_top_k,
-                                 int32_t* __restrict__ order, int32_t* __restrict__ count) {
-    const int f = blockIdx.y;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const float* d = dets + (long)f * P * 15;
-    __shared__ float sc[256];
-    const float si = i < P ? d[15L * i + 4] : 0.f;
-    const bool cand = i < P && si > conf_thresh;
-    int rank = 0;
-    for (int j0 = 0; j0 < P; j0 += 256) {
-        __syncthreads();
-        const int jj = j0 + threadIdx.x;
-        sc[threadIdx.x] = jj < P ? d[15L * jj + 4] : -1.f;
-        __syncthreads();
-        if (cand) {
-            const int lim = min(256, P - j0);
-            for (int k = 0; k < lim; ++k) {
-                const float sj = sc[k];
-                rank += (sj > conf_thresh) && (sj > si || (sj == si && j0 + k > i));
-            }
-        }
-    }
-    if (cand) {
-        atomicAdd(count + f, 1);
-        if (rank < nms_top_k) order[(long)f * nms_top_k + rank] = i;
-    }
-}
-
-// The same order by SORTING (round 6): one workgroup per frame, the (score, prior index) keys of all P priors in LDS, a bitonic
-// sort of the next power of two.  The counting kernel above does P comparisons per candidate -- 90 M per 640 x 360 frame when
-// every prior is a candidate (synthetic detector weights; 14.7 ms per 750 frames, profiles/r06_face_kernel_stats_before.csv) --
-// the sort 105 compare-exchange passes over 16 K keys.  Key = the score's bits made monotone (sign flip), prior index + 1 in the
-// low word: a descending sort visits equal scores HIGHER index first, the rule above (-0.0 is keyed as +0.0: they compare equal, in
-// numpy and in the counting kernel); non-candidates are key 0 and sink.
-constexpr int SORT_THREADS = 1024;
-constexpr int SORT_MAX = 16384;  // keys held in LDS (128 KiB); frames with more priors keep the counting kernel
-
-// NPT compare-exchanges per thread and pass (N = 2048 NPT keys): fully unrolled, branch-free, so that a pass is NPT pairs of
-// LDS reads in flight at once instead of a chain of dependent round trips
-template <int NPT>
-__device__ __forceinline__ void bitonic_desc(unsigned long long* key, int tid) {
-    constexpr int N = 2 * SORT_THREADS * NPT;
-    for (int k = 2; k <= N; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            unsigned long long ka[NPT], kb[NPT];
-            int ia[NPT];
-#pragma unroll
-            for (int u = 0; u < NPT; ++u) {
-                const int t = tid + u * SORT_THREADS;
-                ia[u] = 2 * t - (t & (j - 1));
-                ka[u] = key[ia[u]];
-                kb[u] = key[ia[u] + j];
-            }
-#pragma unroll
-            for (int u = 0; u < NPT; ++u) {
-                // descending runs where bit k of the position is clear: the whole array at k = N
-                const bool sw = ((ia[u] & k) == 0) ? ka[u] < kb[u] : ka[u] > kb[u];
-                key[ia[u]] = sw ? kb[u] : ka[u];
-                key[ia[u] + j] = sw ? ka[u] : kb[u];
-            }
-            __syncthreads();
-        }
-    }
-}
-
-__global__ void __launch_bounds__(SORT_THREADS) face_sort_kernel(const float* __restrict__ dets, int P, float conf_thresh,
-                                                                  int nms_top_k, int32_t* __restrict__ order, int32_t* __restrict__ count) {
-    extern __shared__ __align__(16) unsigned long long sort_keys[];
-    unsigned long long* key = sort_keys;
-    __shared__ int cnt;
-    const int f = blockIdx.x, tid = threadIdx.x;
-    const float* d = dets + (long)f * P * 15;
-    if (tid == 0) cnt = 0;
-    __syncthreads();
-    // candidates only, compacted in arrival order (the sort fixes the order): a real detector leaves a few dozen of 9520 priors
-    // above the confidence floor, and the sort below then runs on 2048 keys instead of 16384
-    for (int i0 = 0; i0 < P; i0 += 4 * SORT_THREADS) {
-        float sc[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int i = i0 + u * SORT_THREADS + tid;
-            sc[u] = i < P ? d[15L * i + 4] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int i = i0 + u * SORT_THREADS + tid;
-            if (i < P && sc[u] > conf_thresh) {
-                unsigned v = __float_as_uint(sc[u]);
-                if (v == 0x80000000u) v = 0u;  // -0.0 == +0.0 is a tie for numpy and for the counting kernel: index order, not sign
-                v = (v & 0x80000000u) ? ~v : (v | 0x80000000u);
-                key[atomicAdd(&cnt, 1)] = ((unsigned long long)v << 32) | (unsigned)(i + 1);
-            }
-        }
-    }
-    __syncthreads();
-    const int c = cnt;
-    int N = 2 * SORT_THREADS;
-    while (N < c) N <<= 1;
-    for (int i = c + tid; i < N; i += SORT_THREADS) key[i] = 0ull;  // padding sinks to the end of a descending sort
-    __syncthreads();
-    switch (N / (2 * SORT_THREADS)) {
-        case 1: bitonic_desc<1>(key, tid); break;
-        case 2: bitonic_desc<2>(key, tid); break;
-        case 4: bitonic_desc<4>(key, tid); break;
-        default: bitonic_desc<8>(key, tid); break;
-    }
-    const int n = min(c, nms_top_k);
-    for (int r = tid; r < n; r += SORT_THREADS) order[(long)f * nms_top_k + r] = (int)(unsigned)(key[r] & 0xffffffffu) - 1;
-    if (tid == 0) count[f] = c;
-}
-
-constexpr int NMS_THREADS = 1024;
-constexpr int NMS_MAX = 6144;  // API bound on nms_top_k (the kernel itself no longer holds all boxes at once)
-
-// Greedy NMS of one frame per workgroup, in CHUNKS of 1024 boxes of the descending-score order (round 6).  The reference keeps
-// every survivor and then takes keep[:top_k] (retina_face_predictor.py:96-100); boxes are visited in score order, so the first top_k
-// kept ones ARE that prefix and nothing behind the chunk that completes them is ever looked at.  Per chunk: every thread owns one
-// box; it is first tested against the boxes kept from earlier chunks (their corners sit in LDS), then the chunk is walked in
-// order with one barrier per kept box and at most ONE IoU per thread and kept box.  The first form of this kernel held all
-// nms_top_k boxes in 126 KiB of LDS (one block per CU) and tested every later box against every kept one: with every prior a
-// candidate (synthetic detector weights) 4.4-6.7 ms per 750 frames, here the walk ends inside the first chunk and three blocks
-// share a CU.  f32 arithmetic in numpy's evaluation order, contraction off: the keep decisions are the reference's.
-__global__ void __launch_bounds__(NMS_THREADS) face_nms_kernel(const float* __restrict__ dets, int P, const int32_t* __restrict__ order,
-                                                                const int32_t* __restrict__ count, int nms_top_k, float nms_thresh,
-                                                                int top_k, float threshold, float* __restrict__ out,
-                                                                int32_t* __restrict__ out_n) {
-#pragma clang fp contract(off)
-    __shared__ float cx1[NMS_THREADS], cy1[NMS_THREADS], cx2[NMS_THREADS], cy2[NMS_THREADS], car[NMS_THREADS];  // the chunk
-    __shared__ float kx1[1024], ky1[1024], kx2[1024], ky2[1024], kar[1024];                                       // kept so far
-    __shared__ unsigned char cdead[NMS_THREADS];
-    __shared__ int kept[1024];  // position in the score order of every kept box (beyond top_k they are never reported)
-    __shared__ int out_rows;
-    const int f = blockIdx.x, tid = threadIdx.x;
-    const int n = min(count[f], nms_top_k);
-    const float* d = dets + (long)f * P * 15;
-    const int32_t* ord = order + (long)f * nms_top_k;
-    const int cap = min(top_k, 1024);
-    int nkept = 0;  // uniform across the block
-    for (int c0 = 0; c0 < n && nkept < cap; c0 += NMS_THREADS) {
-        const int cn = min(NMS_THREADS, n - c0);
-        float x1 = 0.f, y1 = 0.f, x2 = 0.f, y2 = 0.f, ar = 0.f;
-        bool dead = tid >= cn;
-        if (!dead) {
-            const float* r = d + 15L * ord[c0 + tid];
-            x1 = r[0]; y1 = r[1]; x2 = r[2]; y2 = r[3];
-            ar = (x2 - x1 + 1.0f) * (y2 - y1 + 1.0f);
-            for (int k = 0; k < nkept; ++k) {  // boxes kept from earlier chunks all precede this one in the order
-                const float w = fmaxf(0.0f, fminf(kx2[k], x2) - fmaxf(kx1[k], x1) + 1.0f);
-                const float h = fmaxf(0.0f, fminf(ky2[k], y2) - fmaxf(ky1[k], y1) + 1.0f);
-                const float inter = w * h;
-                const float ovr = inter / (kar[k] + ar - inter);
-                if (!(ovr <= nms_thresh)) { dead = true; break; }
-            }
-        }
-        __syncthreads();  // the previous chunk's arrays are free (every thread has left its walk)
-        cx1[tid] = x1; cy1[tid] = y1; cx2[tid] = x2; cy2[tid] = y2; car[tid] = ar;
-        cdead[tid] = dead ? 1 : 0;
-        __syncthreads();
-        for (int a = 0; a < cn; ++a) {
-            if (cdead[a]) continue;  // uniform: every thread reads the same flag behind the previous barrier
-            const float ax1 = cx1[a], ay1 = cy1[a], ax2 = cx2[a], ay2 = cy2[a], aar = car[a];
-            if (tid == 0) {
-                kept[nkept] = c0 + a;
-                kx1[nkept] = ax1; ky1[nkept] = ay1; kx2[nkept] = ax2; ky2[nkept] = ay2; kar[nkept] = aar;
-            }
-            if (++nkept >= cap) break;
-            if (tid > a && !dead) {
-                const float w = fmaxf(0.0f, fminf(ax2, x2) - fmaxf(ax1, x1) + 1.0f);
-                const float h = fmaxf(0.0f, fminf(ay2, y2) - fmaxf(ay1, y1) + 1.0f);
-                const float inter = w * h;
-                const float ovr = inter / (aar + ar - inter);
-                if (!(ovr <= nms_thresh)) { dead = true; cdead[tid] = 1; }
-            }
-            __syncthreads();
-        }
-        __syncthreads();  // tid 0's last kept entry is visible before the next chunk tests against it
-    }
-    // dets[keep][:top_k], then the rows with score >= threshold (retina_face_predictor.py:96-108)
-    __syncthreads();
-    const int nk = min(nkept, cap);
-    if (tid == 0) {
-        int m = 0;
-        for (int k = 0; k < nk; ++k) {
-            const int idx = ord[kept[k]];
-            if (d[15L * idx + 4] >= threshold) kept[m++] = idx;  // compaction in place (m <= k)
-        }
-        out_rows = m;
-        out_n[f] = m;
-    }
-    __syncthreads();
-    for (int e = tid; e < out_rows * 15; e += NMS_THREADS) out[((long)f * top_k + e / 15) * 15 + e % 15] = d[15L * kept[e / 15] + e % 15];
-}
-
+// ------------------------------------------------------------------------------------------------ face tiles (row f4)
 // get_face_images.py:52-56 (crop of the decoded frame) + data/utils.py:34 (PIL NEAREST resize to 224x224) in one pass:
 // tile pixel (y, x) = frame[f][y0 + floor((y + .5) * ch / 224)][x0 + floor((x + .5) * cw / 224)], channels swapped
 // when the frames are BGR (cv2) so that the tile is RGB like the image PIL reads back.  One thread per 4 tile pixels.
@@ -1371,40 +1136,10 @@ int k_fuse_videos(avcer_ctx* ctx, const float* stat, const float* dyn, const flo
     return AVCER_OK;
 }
 
-int k_face_decode(avcer_ctx* ctx, const float* loc, const float* conf, const float* landms, const float* priors, int T, int P,
-                  int im_h, int im_w, float var0, float var1, float* dets, hipStream_t st) {
-    face_decode_kernel<<<dim3(cdiv(P, 256), T), 256, 0, st>>>(loc, conf, landms, priors, P, (float)im_w, (float)im_h, var0, var1, dets);
-    CHECK_LAUNCH(ctx, "face_decode");
-    return AVCER_OK;
-}
-
 int k_crop_tiles(avcer_ctx* ctx, const uint8_t* frames, int T, int H, int W, const int32_t* rects, int n, int swap_rb,
                  uint8_t* tiles, hipStream_t st) {
     crop_tiles_kernel<<<cdiv((long)n * 224 * 56, 256), 256, 0, st>>>(frames, T, H, W, rects, n, swap_rb, tiles);
     CHECK_LAUNCH(ctx, "crop_tiles");
-    return AVCER_OK;
-}
-
-int k_face_nms(avcer_ctx* ctx, const float* dets, int T, int P, float conf_thresh, float nms_thresh, int nms_top_k, int top_k,
-               float threshold, int32_t* order, int32_t* count, float* out, int32_t* out_n, hipStream_t st) {
-    if (nms_top_k > NMS_MAX) return set_err(ctx, AVCER_EINVAL, "face_nms: nms_top_k %d exceeds %d", nms_top_k, NMS_MAX);
-    static uint64_t attr_dev = 0;
-    if (!((attr_dev >> (ctx->device & 63)) & 1)) {
-        HIP_TRY(ctx, hipFuncSetAttribute((const void*)face_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SORT_MAX * 8));
-        attr_dev |= 1ull << (ctx->device & 63);
-    }
-    if (P <= SORT_MAX) {
-        int N = 2 * SORT_THREADS;  // LDS for the worst case (every prior a candidate); the kernel sorts the next power of two of ITS count
-        while (N < P) N <<= 1;
-        face_sort_kernel<<<T, SORT_THREADS, (size_t)N * 8, st>>>(dets, P, conf_thresh, nms_top_k, order, count);
-        CHECK_LAUNCH(ctx, "face_sort");
-    } else {
-        if (hipMemsetAsync(count, 0, (size_t)T * 4, st) != hipSuccess) return set_err(ctx, AVCER_EHIP, "face_nms: memset failed");
-        face_rank_kernel<<<dim3(cdiv(P, 256), T), 256, 0, st>>>(dets, P, conf_thresh, nms_top_k, order, count);
-        CHECK_LAUNCH(ctx, "face_rank");
-    }
-    face_nms_kernel<<<T, NMS_THREADS, 0, st>>>(dets, P, order, count, nms_top_k, nms_thresh, top_k, threshold, out, out_n);
-    CHECK_LAUNCH(ctx, "face_nms");
     return AVCER_OK;
 }
 

@@ -54,13 +54,18 @@ def retina_oracle(name, dtype):
     """oracle/face.py on the case, statement by statement as retina_face_predictor.py:86-108 has them, in float32 or float64 (the
     scores and the thresholds stay the float32 values the kernel sees)."""
     kind, frames, par, _ = retina_case(name)
+    return retina_keep(frames, par, dtype, stable=kind == "tie_rule")
+
+
+def retina_keep(frames, par, dtype=np.float32, stable=True):
+    """The kept row indices per frame of rows [T,P,5]: the statements of retina_oracle on any frames."""
     out = []
     for rows in frames:
         score = rows[:, 4]
         inds = np.where(score > np.float32(par["conf_thresh"]))[0]
         keep = inds
         if len(inds):
-            keep = inds[of.nms(rows[inds].astype(dtype), float(np.float32(par["nms_thresh"])), par["nms_top_k"], stable=kind == "tie_rule")]
+            keep = inds[of.nms(rows[inds].astype(dtype), float(np.float32(par["nms_thresh"])), par["nms_top_k"], stable=stable)]
         keep = keep[:par["top_k"]]
         out.append(keep[score[keep] >= np.float32(par["threshold"])])
     return out

@@ -111,7 +111,7 @@ def _store_data_hazards(asm_text):
     return bad
 
 
-@pytest.mark.parametrize("src", ["fused.hip", "gemm.hip", "kernels.hip"])
+@pytest.mark.parametrize("src", ["fused.hip", "gemm.hip", "kernels.hip", "detect_tail.hip"])
 def test_no_valu_write_right_behind_a_wide_buffer_store(src, tmp_path):
     """gfx950 reads the data registers of a 16-byte buffer store a moment after issue, and hipcc only separates a following VALU
     write of them by a wait state when the store's scalar offset is a constant ("this hazard only exists if the instruction is

@@ -1,4 +1,4 @@
-"""The detector tails (decode, order, NMS of csrc/kernels.hip and csrc/s3fd.hip) where "the keep decisions are the reference's" had no
+"""The detector tails (decode, order, NMS of csrc/detect_tail.hip) where "the keep decisions are the reference's" had no
 test: NaN / inf / -inf / signed-zero scores, a frame that is NaN throughout (what an overflowed x3 pass hands over before the guarded
 caller repeats it in fp32), boxes that leave expf as inf, NaN or with zero size, a NaN or inf box in every role of the chunked walk,
 zero-size and inverted boxes, an overlap exactly on nms_thresh, scores exactly on conf_thresh and threshold, nms_top_k and top_k reached
@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import detect_edge_cases as ec
+import s3fd_ref
 from avcer_amd.engine import _ptr
 from guard_band import Band, check
 from oracle import face as of
@@ -155,3 +156,78 @@ def test_s3fd_decode_then_tail(engine, variant):
     size = tuple(int(v) for v in E["sb_size"])
     par = dict(conf_thresh=0.05, nms_thresh=0.3, nms_top_k=5000, top_k=750, threshold=float(E["sb_threshold"]))
     _s3fd(engine, E["sb_loc"][None], E[f"sb_conf_{variant}"][None], E["sb_priors"], size, par, [E[f"sb_rows_{variant}"]], exact=False)
+
+
+# ------------------------------------------------------------------------------------------------ the shared order kernel's paths
+# One order kernel serves both detectors (csrc/detect_tail.hip order_kernel), so each of them reaches sizes it did not before: S3FD
+# the unrolled sort of 4096 and 8192 keys and compaction into LDS, RetinaFace the sorts below 2048 keys.  Disjoint boxes on a grid
+# (NMS keeps every one, the oracles stay fast), scores drawn from 200 values so that long runs of ties cross every 2048-key boundary:
+# the rows are the oracles' (tests/s3fd_ref.py, oracle/face.py, ties by the kernels' documented rule) bit for bit.
+GRID = 256
+SCORES = (np.float32(0.5) + np.arange(200, dtype=np.float32) / np.float32(512))   # 200 distinct values, all above both floors
+
+
+def _scores(rng, p, n_cand):
+    """[p] scores: n_cand candidates at random places with values of SCORES, the others under every confidence floor."""
+    s = np.full(p, 0.01, np.float32)
+    s[rng.permutation(p)[:n_cand]] = SCORES[rng.integers(0, len(SCORES), n_cand)]
+    return s
+
+
+def _s3fd_grid(cands, p, seed):
+    """loc, conf, priors of len(cands) frames: prior i is a box of half a cell in cell (i % GRID, i // GRID) of a dyadic grid and loc
+    is 0, so decode is exact; on a GRID x GRID image the boxes are half a pixel wide."""
+    rng = np.random.default_rng(seed)
+    i = np.arange(p)
+    priors = np.stack([(i % GRID + 0.5) / GRID, (i // GRID + 0.5) / GRID, np.full(p, 0.5 / GRID), np.full(p, 0.5 / GRID)], 1).astype(np.float32)
+    score = np.stack([_scores(rng, p, c) for c in cands])
+    return np.zeros((len(cands), p, 4), np.float32), np.stack([1 - score, score], -1), priors
+
+
+def _s3fd_grid_case(engine, cands, p, seed, par, rows):
+    loc, conf, priors = _s3fd_grid(cands, p, seed)
+    want = [s3fd_ref.detect(loc[t], conf[t], priors, GRID, GRID, par["threshold"], par["top_k"], par["conf_thresh"], par["nms_thresh"],
+                            par["nms_top_k"], stable=True) for t in range(len(cands))]
+    assert [len(w) for w in want] == rows
+    _s3fd(engine, loc, conf, priors, (GRID, GRID), par, want, exact=True)
+
+
+@pytest.mark.parametrize("top_k,rows", [(1024, [125, 228]), (7, [7, 7])])
+def test_s3fd_through_the_unrolled_sort(engine, top_k, rows):
+    """2049 candidates of 5000 priors (4096 keys, one exchange per thread and pass) and all 5000 (8192 keys, two); the walk stops at
+    the cap top_k, and with top_k = 1024 the threshold, which is one of the scores, cuts the kept rows short."""
+    par = dict(conf_thresh=0.05, nms_thresh=0.3, nms_top_k=6144, top_k=top_k, threshold=float(SCORES[190]))
+    _s3fd_grid_case(engine, [2049, 5000], 5000, 1, par, rows)
+
+
+def test_s3fd_counting_branch_at_its_first_size(engine):
+    """16385 priors, every one a candidate: one key more than LDS holds, ranked by counting.  All top_k = 1024 rows are reported, so
+    the first 1024 ranks, with their runs of some 80 tied scores, are checked one by one."""
+    par = dict(conf_thresh=0.05, nms_thresh=0.3, nms_top_k=2000, top_k=1024, threshold=0.1)
+    _s3fd_grid_case(engine, [16385], 16385, 2, par, [1024])
+
+
+def test_s3fd_few_candidates_compacted_into_lds(engine):
+    """300 priors (the keys are compacted into LDS, not memory) with 0, 1, 63, 64 and 65 candidates: the floor of 64 keys with padding,
+    without, and the first size past it."""
+    par = dict(conf_thresh=0.05, nms_thresh=0.3, nms_top_k=5000, top_k=750, threshold=0.1)
+    _s3fd_grid_case(engine, [0, 1, 63, 64, 65], 300, 3, par, [0, 1, 63, 64, 65])
+
+
+def test_retina_below_2048_candidates(engine):
+    """0, 1, 63, 64, 65 and 2047 candidates among 3000 priors: the looped sort of 64 .. 1024 keys and, at 2047, the first unrolled one.
+    The threshold sits on one of the scores, so the last selection cuts inside the kept rows."""
+    rng = np.random.default_rng(4)
+    cands, p = [0, 1, 63, 64, 65, 2047], 3000
+    i = np.arange(p, dtype=np.float32)
+    x, y = 4 * (i % 64), 4 * (i // 64)   # 2 x 2 pixel boxes ("+1" widths) 4 apart
+    frames = np.stack([np.stack([x, y, x + 1, y + 1, _scores(rng, p, c)], 1) for c in cands]).astype(np.float32)
+    par = dict(conf_thresh=0.02, nms_thresh=0.4, nms_top_k=5000, top_k=750, threshold=float(SCORES[100]))
+    want = ec.retina_keep(frames, par)
+    assert [len(k) for k in want[:5]] == [int((f[:, 4] >= SCORES[100]).sum()) for f in frames[:5]] and len(want[5]) == 750
+    assert 0 < len(want[3]) < 64
+    rows = ec.rows15(frames)
+    got = _retina_nms(engine, rows, par, [rows[f, k] for f, k in enumerate(want)])
+    for f, k in enumerate(want):
+        assert got[f][:, 5].astype(int).tolist() == k.tolist()
+        assert ec.same_bits(got[f], rows[f, k])

@@ -262,15 +262,16 @@ def test_abi_and_symbols():
 
 
 def test_s3fd_kernels_use_no_scratch_and_do_not_spill():
-    """Every kernel of s3fd.hip, and the detector's 2 x 2 pool, which is the shared maxpool_kernel of kernels.hip (all of its instances)."""
+    """Every kernel of s3fd.hip and of detect_tail.hip (Detect, with RetinaFace's tail), and the detector's 2 x 2 pool, which is the
+    shared maxpool_kernel of kernels.hip (all of its instances)."""
     exe = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(exe):
         pytest.skip("hipcc not available")
     flags = [f for f in build.FLAGS if f not in ("-fPIC", "-shared")]
-    # s3fd.hip: stem and inverse norm x two storages, the head x two storages x 8 / 6 outputs, Detect; kernels.hip: the pool, 2 x 2 on
-    # f32 / sp32 and 3 x 3 on f32 / bf16
+    # s3fd.hip: stem and inverse norm x two storages, the head x two storages x 8 / 6 outputs; detect_tail.hip: decode, order and NMS
+    # x two detectors and RetinaFace's counting kernel; kernels.hip: the pool, 2 x 2 on f32 / sp32 and 3 x 3 on f32 / bf16
     bad = []
-    for src, only, count in (("s3fd.hip", "", 2 + 2 + 4 + 3), ("kernels.hip", "maxpool_kernel", 2 + 2)):
+    for src, only, count in (("s3fd.hip", "", 2 + 2 + 4), ("detect_tail.hip", "", 3 * 2 + 1), ("kernels.hip", "maxpool_kernel", 2 + 2)):
         out = os.path.join(tempfile.mkdtemp(prefix="avcer_asm_"), src + ".s")
         r = subprocess.run([exe] + flags + ["-S", "--cuda-device-only", "-o", out, os.path.join(build.CSRC, src)],
                            capture_output=True, text=True, timeout=900)
