@@ -730,6 +730,62 @@ class Engine:
                                                  bsz, _ptr(row), _ptr(batch), _ptr(epoch), _ptr(ticket), self._stream()))
         return row, batch, epoch
 
+    def head_fit(self, feats, targets, hyper, class_w, w0, b0, order, mix_lam=None, mix_index=None, epochs: int = 1,
+                 batch_size: int = 64):
+        """K runs of fitting the classifier head, all epochs, in one launch (include/avcer_hip.h avcer_head_fit;
+        net_trainer.py:357-467, 574-604).  feats f32 [n, F] (a device tensor stays where it is), targets [n] in [0, C); hyper: a
+        HOST float64 [K, 12] table (kind, label_smoothing, gamma, lr, beta1, beta2, eps, t0, eta_min, mixup, first_epoch, 0);
+        class_w [K, C], w0 [K, C, F], b0 [K, C], order int32 [K, epochs, n], mix_lam [K, epochs, n_batches] and mix_index int32
+        [K, epochs, n] or both None.  head_fit.fit_heads builds and validates these tables: this call checks shapes only, and the
+        kernel turns a row number, position or target out of range into NaN.  Returns (w_hist f32 [K, epochs, C, F], b_hist f32
+        [K, epochs, C], batch_loss f32 [K, epochs, n_batches], epoch_loss f64 [K, epochs]) on the device.  Shapes that disagree
+        raise ValueError; limits are the library's (AvcerError).  No host synchronisation behind the upload of the tables."""
+        x = self._dev(feats, torch.float32)
+        t = self._dev(targets, torch.int32)
+        hy = np.ascontiguousarray(np.asarray(hyper, dtype=np.float64))
+        if x.dim() != 2 or t.dim() != 1 or int(t.shape[0]) != int(x.shape[0]) or hy.ndim != 2 or hy.shape[1] != 12:
+            raise ValueError(f"head_fit: feats [n, F], targets [n] and hyper [K, 12] expected, got {tuple(x.shape)}, {tuple(t.shape)}, {hy.shape}")
+        n, f, k, ep, bsz = int(x.shape[0]), int(x.shape[1]), int(hy.shape[0]), int(epochs), int(batch_size)
+        w = self._dev(w0, torch.float32)
+        if w.dim() != 3 or int(w.shape[0]) != k or int(w.shape[2]) != f:
+            raise ValueError(f"head_fit: w0 [{k}, C, {f}] expected, got {tuple(w.shape)}")
+        c = int(w.shape[1])
+        n_batches = -(-n // bsz) if n > 0 and bsz > 0 else 0
+        cw, b, od = self._dev(class_w, torch.float32), self._dev(b0, torch.float32), self._dev(order, torch.int32)
+        if tuple(cw.shape) != (k, c) or tuple(b.shape) != (k, c) or tuple(od.shape) != (k, ep, n):
+            raise ValueError(f"head_fit: class_w and b0 [{k}, {c}] and order [{k}, {ep}, {n}] expected, got {tuple(cw.shape)}, "
+                             f"{tuple(b.shape)}, {tuple(od.shape)}")
+        if (mix_lam is None) != (mix_index is None):
+            raise ValueError("head_fit: mix_lam and mix_index come together")
+        lam = idx = None
+        if mix_lam is not None:
+            lam, idx = self._dev(mix_lam, torch.float32), self._dev(mix_index, torch.int32)
+            if tuple(lam.shape) != (k, ep, n_batches) or tuple(idx.shape) != (k, ep, n):
+                raise ValueError(f"head_fit: mix_lam [{k}, {ep}, {n_batches}] and mix_index [{k}, {ep}, {n}] expected, got "
+                                 f"{tuple(lam.shape)}, {tuple(idx.shape)}")
+        w_hist, b_hist, batch_loss = self._new(k, ep, c, f), self._new(k, ep, c), self._new(k, ep, n_batches)
+        epoch_loss, hy_dev = self._new(k, ep, dtype=torch.float64), self._new(k, 12, dtype=torch.float64)
+        self._check(self.lib.avcer_head_fit(self.ctx, _ptr(x), _ptr(t), n, f, c, k, ep, bsz, hy.ctypes.data_as(C.c_void_p), _ptr(hy_dev),
+                                            _ptr(cw), _ptr(w), _ptr(b), _ptr(od), _ptr(lam), _ptr(idx), _ptr(w_hist), _ptr(b_hist),
+                                            _ptr(batch_loss), _ptr(epoch_loss), self._stream()))
+        return w_hist, b_hist, batch_loss, epoch_loss
+
+    def head_apply(self, feats, w, b, out=None):
+        """The logits of a feature table under many heads in one launch (include/avcer_hip.h avcer_head_apply): feats f32 [m, F],
+        w f32 [H, C, F], b f32 [H, C] -> f32 [H, m, C] on the device (`out`: write into this contiguous tensor).  A head alone
+        gives the bits it gives among many.  Shapes that disagree raise ValueError; limits are the library's (AvcerError)."""
+        x, ww, bb = self._dev(feats, torch.float32), self._dev(w, torch.float32), self._dev(b, torch.float32)
+        if x.dim() != 2 or ww.dim() != 3 or int(ww.shape[2]) != int(x.shape[1]) or tuple(bb.shape) != tuple(ww.shape[:2]):
+            raise ValueError(f"head_apply: feats [m, F], w [H, C, F] and b [H, C] expected, got {tuple(x.shape)}, {tuple(ww.shape)}, "
+                             f"{tuple(bb.shape)}")
+        m, f, h, c = int(x.shape[0]), int(x.shape[1]), int(ww.shape[0]), int(ww.shape[1])
+        if out is None:
+            out = self._new(h, m, c)
+        elif tuple(out.shape) != (h, m, c) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"head_apply: out must be a contiguous float32 tensor of shape {(h, m, c)}")
+        self._check(self.lib.avcer_head_apply(self.ctx, _ptr(x), _ptr(ww), _ptr(bb), m, f, c, h, _ptr(out), self._stream()))
+        return out
+
     def ccc(self, targets, predicts):
         """The concordance correlation coefficient of two series (include/avcer_hip.h avcer_ccc; accuracy_utils.ccc_score):
         tensors or arrays of equal element counts, read as float64; a one-dimensional strided view of a device float64 tensor (a

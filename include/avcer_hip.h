@@ -111,7 +111,9 @@ enum {
  *      avcer_set_skip_unread_rows, avcer_bneck_chain_keep, avcer_bneck_tail_keep (the block in front of a strided last block
  *      stores only the rows that block reads) joined under 8 the same way: three more symbols, nothing that existed changed.
  *      avcer_window_losses, avcer_ccc (validation of audio checkpoints: the epoch loss of a corpus's window logits and the
- *      concordance coefficient) joined under 8 the same way: two more symbols, nothing that existed changed. */
+ *      concordance coefficient) joined under 8 the same way: two more symbols, nothing that existed changed.
+ *      avcer_head_fit, avcer_head_apply (fitting the audio classifier head on extracted features, many runs a launch, and the
+ *      logits of a feature table under many heads) joined under 8 the same way: two more symbols, nothing that existed changed. */
 #define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
@@ -949,6 +951,72 @@ int avcer_window_losses(avcer_ctx* ctx, const float* logits, const int32_t* targ
  * Limits: 1 <= n, 1 <= stride, (n - 1) * stride < 2^40.  No host synchronisation. */
 int avcer_ccc(avcer_ctx* ctx, const double* targets, const double* predicts, int64_t n, int64_t stride, double* out,
               avcer_stream_t stream);
+
+/* Fitting the audio classifier head: the train phase of NetTrainer.run for the last layer, feature_downsample (Linear f -> c), on
+ * features extracted once; k_runs independent runs (seeds, rates, losses, mixup settings) in ONE launch, one workgroup a run.
+ *   ref: src/audio/net_trainer/net_trainer.py:357-467 (iterate_model), 574-604 (mixup_data), src/audio/train_c_audio.py:236-260
+ *        (the losses, torch.optim.Adam, CosineAnnealingWarmRestarts stepped with epoch + idx / iters)
+ * DEVICE: feats f32 [n, f]; targets i32 [n] in [0, c); class_w f32 [k_runs, c] (ones for an unweighted loss); w0 f32 [k_runs, c, f],
+ * b0 f32 [k_runs, c]; order i32 [k_runs, epochs, n], per epoch a permutation of 0 .. n-1; mix_lam f32 [k_runs, epochs, n_batches] and
+ * mix_index i32 [k_runs, epochs, n] (per batch a permutation of the positions 0 .. n_b-1 inside it), both NULL when no run mixes;
+ * hyper_dev f64 [k_runs, AVCER_HEAD_HYPER], scratch the call fills.  HOST: hyper f64 [k_runs, AVCER_HEAD_HYPER] = kind
+ * (AVCER_LOSS_CE / AVCER_LOSS_SOFT_FOCAL), label_smoothing, gamma, lr, beta1, beta2, eps, t0, eta_min, mixup (0 / 1), first_epoch (the trainer's number of
+ * epoch 0 of this call: NetTrainer.run counts from 1), 0; it is checked here and copied in stream order.  n_batches = ceil(n / batch_size); batch i of epoch e holds the rows
+ * order[e, i * batch_size ..], n_b of them, the last batch may be short.
+ * One step (e, i), f32 unless said otherwise, every operation rounded on its own except the two fmaf chains:
+ *   x[b, :] = feats[row_b, :], or with mixup lam * feats[row_b, :] + (1 - lam) * feats[row_{index[b]}, :], the label being
+ *     y_b = (lam > 1 - lam) ? y : (lam < 1 - lam) ? y' : min(y, y')  (argmax of the mixed one-hot rows, first maximum);
+ *   logits[b, k] = S + bias[k], S summed in this FIXED order: thread t of 256 owns the columns t, t + 256, .. and chains
+ *     fmaf(x[b, col], W[k, col], .) over them upwards from 0; eight adders take 32 consecutive threads' partials each, one after
+ *     the other from the first; the eight sums fold in halves ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7));
+ *   the loss of row b exactly as avcer_window_losses states it, in f32; its sums A, G, U over the batch in that entry's order
+ *     (thread b holds row b; 256 partials fold in halves); batch_loss as there;
+ *   G[b, k] = d batch_loss / d logits[b, k], with p = softmax(logits[b]), W_ = ((w[0] + w[1]) + ..):
+ *     CE          ((1 - eps) * (w[y] * (p[k] - [k == y])) + (eps / c) * (W_ * p[k] - w[k])) / U
+ *     SOFT_FOCAL  ((D * p[y]) * ([k == y] - p[k])) / n_b,  D = w[y] * (g' * log(pc) - fo / pc) while 1e-7 <= p[y] <= 1 - 1e-7, else
+ *                 0 (the clip), pc the clipped p[y], fo = (1 - pc)^gamma, g' = gamma * (1 - pc)^(gamma - 1) (0 for gamma == 0);
+ *   dW[k, col] = fmaf(G[b, k], x[b, col], .) over b = 0, 1, .. from 0, by the thread that owns col;  db[k] = ((G[0, k] + G[1, k]) + ..);
+ *   Adam (no weight decay, no amsgrad), step s = 1, 2, ..: m += (1 - beta1) * (g - m);  v = v * beta2 + ((1 - beta2) * g) * g;
+ *     W -= step_size * (m / (sqrt(v) / bc2 + eps)), step_size = f32(lr_s / (1 - beta1^s)), bc2 = f32(sqrt(1 - beta2^s)), the two
+ *     computed in double, beta^s as a running product;
+ *   lr for the next step, in double: eta_min + (lr - eta_min) * (1 + cos(pi * T / t0)) / 2, T = (first_epoch + e) + i / n_batches, taken mod t0 once
+ *     it reaches t0 (T_mult = 1).  The first step runs at lr.
+ * There are no atomics, no tickets and no waits but workgroup barriers: a run's outputs are a pure function of its inputs, the
+ * same bits alone as among k_runs.  W, b, m and v of a run stay in its workgroup's registers from the first step to the last:
+ * 3 * c * f floats over 256 threads, so c * f <= AVCER_HEAD_MAX_STATE (every c <= 16 at every f <= 1024).
+ * A row number outside [0, n), a mixup position outside [0, n_b) or a target outside [0, c) is checked where it is read and
+ * turns the step's loss (and the weights behind it) into NaN; nothing is indexed with it.  Callers validate them beforehand.
+ * Outputs (device): w_hist f32 [k_runs, epochs, c, f] and b_hist f32 [k_runs, epochs, c], the state at the end of every epoch;
+ * batch_loss f32 [k_runs, epochs, n_batches]; epoch_loss f64 [k_runs, epochs] = sum_i(f64(batch_loss) * batch_size) / n_batches,
+ * the short batch counting with the full size (net_trainer.py:441,460), added in double in step order.
+ * Limits (AVCER_EINVAL beyond them, before any launch): 1 <= n <= AVCER_HEAD_MAX_ROWS; f a multiple of 64, 64 .. AVCER_HEAD_MAX_FEATURES;
+ * 2 <= c <= AVCER_LOSS_MAX_CLASSES; c * f <= AVCER_HEAD_MAX_STATE; 1 <= batch_size <= AVCER_HEAD_MAX_BATCH; 1 <= epochs <=
+ * AVCER_HEAD_MAX_EPOCHS; 1 <= k_runs <= AVCER_HEAD_MAX_RUNS; epochs * n_batches <= AVCER_HEAD_MAX_STEPS; per run a known kind,
+ * label_smoothing in [0, 1], gamma >= 0, betas in [0, 1), eps >= 0, t0 an integer >= 1, first_epoch an integer >= 0, all of them, lr and eta_min finite.
+ * One host-to-device copy of `hyper` in stream order; no host synchronisation beyond it. */
+#define AVCER_HEAD_HYPER 12
+#define AVCER_HEAD_MAX_BATCH 256
+#define AVCER_HEAD_MAX_FEATURES 1024
+#define AVCER_HEAD_MAX_STATE 16384
+#define AVCER_HEAD_MAX_ROWS 268435455LL
+#define AVCER_HEAD_MAX_EPOCHS 1048576
+#define AVCER_HEAD_MAX_RUNS 1048576
+#define AVCER_HEAD_MAX_STEPS 1073741824LL
+#define AVCER_HEAD_MAX_HEADS 65535
+int avcer_head_fit(avcer_ctx* ctx, const float* feats, const int32_t* targets, int64_t n, int f, int c, int k_runs, int epochs,
+                   int batch_size, const double* hyper, double* hyper_dev, const float* class_w, const float* w0, const float* b0,
+                   const int32_t* order, const float* mix_lam, const int32_t* mix_index, float* w_hist, float* b_hist,
+                   float* batch_loss, double* epoch_loss, avcer_stream_t stream);
+
+/* The logits of a feature table under many heads: logits[h, i, k] = S + b[h, k], S = sum_col feats[i, col] * w[h, k, col].
+ * DEVICE: feats f32 [m, f], w f32 [heads, c, f], b f32 [heads, c] -> logits f32 [heads, m, c] (heads = runs x epochs of
+ * avcer_head_fit's w_hist / b_hist).  S in a FIXED order that depends on f alone: lane l of a wave chains fmaf(x, w, .) over the
+ * columns l, l + 64, .. upwards from 0; the 64 partials fold by lane exchange at distances 32, 16, 8, 4, 2, 1.  One head alone
+ * gives the bits it gives among many.  One launch; one wave per four rows and head.
+ * Limits: 1 <= m <= AVCER_HEAD_MAX_ROWS, f a multiple of 64 up to AVCER_HEAD_MAX_FEATURES, 2 <= c <= AVCER_LOSS_MAX_CLASSES,
+ * 1 <= heads <= AVCER_HEAD_MAX_HEADS.  No host synchronisation. */
+int avcer_head_apply(avcer_ctx* ctx, const float* feats, const float* w, const float* b, int64_t m, int f, int c, int heads,
+                     float* logits, avcer_stream_t stream);
 
 /* The contraction kernel itself (implicit-GEMM convolution with fused epilogue), exported for kernel-level
  * parity tests and micro-benchmarks:  Y[m, n] = act(scale[n] * sum_k A[m,k] * W[n,k] + bias[n] (+ R[m,n]))
