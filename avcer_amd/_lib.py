@@ -88,6 +88,10 @@ SIGNATURES = {
                                       C.c_int64] + [C.c_void_p] * 4 + [c_stream]),
     "avcer_ccc": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, c_stream]),
     "avcer_head_fit": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_int] * 5 + [C.c_void_p] * 12 + [c_stream]),
+    "avcer_head_fit_views": (C.c_int, [c_ctx, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_int] * 5 + [C.c_void_p] * 12 +
+                             [c_stream]),
+    "avcer_wave_augment": (C.c_int, [c_ctx, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, c_stream]),
     "avcer_head_apply": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, c_stream]),
     "avcer_audio_frame_mean": (C.c_int, [c_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                          C.c_void_p, C.c_void_p, c_stream]),

@@ -3,7 +3,9 @@
     cexpr_windows / abaw_windows / afew_windows   `parse_features` / `prepare_data` of src/audio/data/c_expr_dataset.py:111-179,
                                                   abaw_fe_dataset.py:103-202 and afew_fe_dataset.py:113-156: label files, mouth-open
                                                   tables and durations become the window tables the datasets hold as `meta`
-    window_samples                                the cut of their `__getitem__` (c_expr_dataset.py:283-285, abaw_fe_dataset.py:312-318)
+    meld_windows                                  `prepare_data` of meld_dataset.py:93-180, the second training corpus of
+                                                  train_c_audio.py, on one utterance's VAD segments
+    window_samples                               the cut of their `__getitem__` (c_expr_dataset.py:283-285, abaw_fe_dataset.py:312-318)
     run_corpus                                    test_c_audio.iterate_model / NetTrainer.extract_features (net_trainer.py:469-535):
                                                   the model over every window of every file
     majority_voting                               utils/common_utils.py:74-108: one prediction per file
@@ -43,7 +45,11 @@ AFEW_TO_ABAW = {"Neutral": 0, "Angry": 1, "Disgust": 2, "Fear": 3, "Happy": 4, "
 NEW_FPS = 5              # abaw_fe_dataset.py:75: mouth_open is reported at 5 values per second
 VOTES_MAX_CLASSES = 8    # include/avcer_hip.h AVCER_VOTES_MAX_CLASSES
 VOTES_TARGET_MIN = -2    # include/avcer_hip.h AVCER_VOTES_TARGET_MIN
+MELD_TO_ABAW = {"neutral": 0, "anger": 1, "disgust": 2, "fear": 3, "joy": 4, "sadness": 5, "surprise": 6}   # meld_dataset.py:81-89
 KINDS = ("cexpr", "abaw", "afew")
+# the kinds of a Windows table and the window_samples rule each is cut by: MELD's __getitem__ (meld_dataset.py:202-204) cuts
+# round(sr * start_t) : round(sr * end_t), which is the C-EXPR rule (c_expr_dataset.py:283-285)
+TABLE_CUTS = {"cexpr": "cexpr", "abaw": "abaw", "afew": "afew", "meld": "cexpr"}
 
 
 def round_math(val: float) -> int:
@@ -213,10 +219,49 @@ def afew_windows(duration: int, label, sr: int = 16000, shift: float = 2, min_w_
     return _table("afew", sorted(rows, key=lambda r: (r[0], r[3])), vad_info=vad_info)
 
 
+def meld_label(label) -> int:
+    """meld_dataset.py:72-91: the MELD emotion name as the ABAW class number; an int passes through."""
+    if isinstance(label, (int, np.integer)) and not isinstance(label, bool):
+        return int(label)
+    if label not in MELD_TO_ABAW:
+        raise ValueError(f"MELD label {label!r}: one of {sorted(MELD_TO_ABAW)}")
+    return MELD_TO_ABAW[label]
+
+
+def meld_windows(segments, emotion, sr: int = 16000, shift: float = 2, min_w_len: float = 2, max_w_len: float = 4,
+                 num_classes: int = 8) -> Windows:
+    """The window loop of MeldDataset.prepare_data (meld_dataset.py:115-170) for one utterance: `segments` are its entries of the
+    VAD pickle, {"start": sample, "end": sample} each, `emotion` its label (meld_label).  Per segment of at least min_w_len
+    seconds: windows in SAMPLES every `shift` seconds from the segment's start, max_w_len seconds long and ending with the segment
+    at the latest; one shorter than min_w_len becomes the segment's last max_w_len seconds (from its start at the earliest), which
+    is often a window that exists already: duplicates leave.  An utterance whose class is above num_classes - 1 has no windows.
+    The reference de-duplicates through a set and leaves the order to it: here the windows are SORTED by (start_f, end_f).
+    ValueError: an unknown emotion, sr, shift or a window length that round to less than one sample, a segment that is no pair of
+    integers with start <= end."""
+    shift_s, max_s, min_s = round(shift * sr), round(max_w_len * sr), round(min_w_len * sr)
+    if sr <= 0 or shift_s < 1 or max_s < 1:
+        raise ValueError(f"sr={sr!r}, shift={shift!r}, max_w_len={max_w_len!r}: the shift and the window must be at least one sample")
+    expr = meld_label(emotion)
+    rows = set()
+    for s in segments:
+        a, b = s["start"], s["end"]
+        if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in (a, b)) or a < 0 or b < a:
+            raise ValueError(f"a VAD segment is {{'start': sample, 'end': sample}} with 0 <= start <= end, got {s!r}")
+        a, b = int(a), int(b)
+        if b - a < min_s or expr > num_classes - 1:
+            continue
+        for seg in range(0, b - a, shift_s):
+            start, end = a + seg, min(b, a + seg + max_s)
+            if end - start < min_s:
+                start, end = max(a, b - max_s), b
+            rows.add((start / sr, end / sr, start, end, expr))
+    return _table("meld", sorted(rows, key=lambda r: (r[2], r[3])), vad_info=list(segments))
+
+
 def window_samples(start_t: float, end_t: float, sr: int, max_w_len: int = 4, kind: str = "cexpr"):
     """The sample range `__getitem__` cuts: (round(sr * start_t), round(sr * end_t)) with Python's round (halves to even), and for
     the ABAW dataset min(round(sr * end_t), sr * (end_t + max_w_len)) as its end (abaw_fe_dataset.py:312-318).  The range is what
-    the slice is asked for: it ends with the file where the file is shorter."""
+    the slice is asked for: it ends with the file where the file is shorter.  A MELD table is cut by the "cexpr" rule (TABLE_CUTS)."""
     if kind not in KINDS:
         raise ValueError(f"kind={kind!r}: one of {KINDS}")
     a, b = round(sr * start_t), round(sr * end_t)
@@ -258,6 +303,22 @@ def read_vad(path: str) -> dict:
     """The VAD pickle of afew_fe_dataset.py:117-119: {wav file name: speech timestamps}."""
     with open(path, "rb") as f:
         return pickle.load(f)
+
+
+def read_meld_labels(path: str, vad: dict) -> list:
+    """A MELD label file (`*_sent_emo.csv`: a header naming Dialogue_ID, Utterance_ID and Emotion among its columns) ->
+    [(wav file name, emotion)] in the file's order, "dia{Dialogue_ID}_utt{Utterance_ID}.wav" as meld_dataset.py:128 names it, with
+    the reference's two filters (:129-133): the broken dia125_utt3 and every name the VAD pickle `vad` (read_vad) does not list."""
+    import csv
+
+    out = []
+    with open(path, newline="") as f:
+        for row in csv.DictReader(f):
+            fn = "dia{0}_utt{1}.wav".format(int(row["Dialogue_ID"]), int(row["Utterance_ID"]))
+            if "dia125_utt3" in fn or fn not in vad:
+                continue
+            out.append((fn, row["Emotion"]))
+    return out
 
 
 def avi_fps_frames(path: str):
@@ -392,10 +453,10 @@ def plan_corpus(engine, files, windows, sr: int = 16000, max_w_len: int = 4, win
         raise ValueError(f"run_corpus: {int(s_off[-1])} audio samples in one call (the chunker takes 2^31 - 1): split the corpus")
     starts, ends, targets = [], [], []
     for (name, _, _), length, tab in zip(files, lengths, windows):
-        if tab.kind not in KINDS:
+        if tab.kind not in TABLE_CUTS:
             raise ValueError(f"file {name}: window kind {tab.kind!r}")
         for i in range(len(tab)):
-            a, b = window_samples(float(tab.start_t[i]), float(tab.end_t[i]), sr, max_w_len, tab.kind)
+            a, b = window_samples(float(tab.start_t[i]), float(tab.end_t[i]), sr, max_w_len, TABLE_CUTS[tab.kind])
             a, b = min(max(a, 0), length), min(max(b, 0), length)   # a slice ends with the file
             b = max(a, b)
             if b - a > max_w_len * sr:
@@ -411,7 +472,7 @@ def plan_corpus(engine, files, windows, sr: int = 16000, max_w_len: int = 4, win
 
 
 def run_corpus(engine, files, windows, sr: int = 16000, max_w_len: int = 4, mode: Optional[int] = None, windows_per_pass: int = 128,
-               features: bool = False, plan=None) -> CorpusResult:
+               features: bool = False, plan=None, transform=None) -> CorpusResult:
     """The audio model over every window of a corpus.  files: (name, wav) with wav mono float32 [L] at `sr`, or (name, wav,
     wav_sr) with the source audio at `wav_sr` as Engine.resample takes it (int16 [L] / [L, C] or float32 [L] / [C, L]), brought to
     mono at `sr` on the device; windows: one `Windows` table per file (cexpr_windows / abaw_windows / afew_windows).
@@ -422,14 +483,24 @@ def run_corpus(engine, files, windows, sr: int = 16000, max_w_len: int = 4, mode
     repeated in MODE_FP32 as a whole.  `features`: also the pooled head activations per window.
     Every window's row holds the bits a one-window Engine.audio_forward call on that window gives (tests/test_gpu_audio_corpus.py).
     What plan_corpus refuses raises ValueError before anything is launched.  `plan`: what plan_corpus returned for these very
-    arguments, for a caller that runs one corpus under several models (validate.validate_checkpoints) and plans it once."""
+    arguments, for a caller that runs one corpus under several models (validate.validate_checkpoints) and plans it once.
+    `transform`: an augment.AugmentSpec -- the training windows of train_c_audio.py:112-119 -- puts ONE Engine.wave_augment call
+    between the chunker and the forward of every pass; the records of all windows are drawn once, in front of the first pass, from
+    (the spec's seed, the window's row in the corpus), so a window's bits do not depend on `windows_per_pass`.  None: nothing of it
+    is imported, constructed or launched."""
     import torch
 
     from .engine import MODE_DEFAULT
 
+    if transform is not None:
+        from . import augment
+
+        if not isinstance(transform, augment.AugmentSpec):
+            raise ValueError(f"run_corpus: transform is an augment.AugmentSpec or None, got {type(transform).__name__}")
     mode = MODE_DEFAULT if mode is None else mode
     names, s_off, file_off, starts, ends, targets = plan if plan is not None else plan_corpus(engine, files, windows, sr, max_w_len,
                                                                                                  windows_per_pass)
+    aug_plan = None if transform is None else augment.draw_plan(transform, int(starts.shape[0]))
     files = [_file_parts(f) for f in files]
     win = int(max_w_len * sr)
     n = int(starts.shape[0])
@@ -453,6 +524,8 @@ def run_corpus(engine, files, windows, sr: int = 16000, max_w_len: int = 4, mode
         for a in range(0, n, int(windows_per_pass)):
             b = min(a + int(windows_per_pass), n)
             chunks = engine.audio_chunks(wav_all, g_starts[a:b], g_ends[a:b], win, "constant")
+            if aug_plan is not None:
+                augment.augment(engine, chunks, aug_plan.rows(a, b))
             out = engine.audio_forward(chunks, normalize=True, mode=m, return_features=features)
             lg.append(out[0] if features else out)
             if features:
@@ -472,13 +545,14 @@ def run_corpus(engine, files, windows, sr: int = 16000, max_w_len: int = 4, mode
 
 # ------------------------------------------------------------------------------------------------ per-file regrouping
 def extract_features(engine, files, windows, sr: int = 16000, max_w_len: int = 4, mode: Optional[int] = None,
-                     windows_per_pass: int = 128) -> dict:
+                     windows_per_pass: int = 128, transform=None) -> dict:
     """run_extract_features.py:223-260: run_corpus with features, regrouped per file.  {file name: {"targets": [np.int64],
     "predicts": [float32 [C] softmax rows], "features": [float32 [1024 or 256] rows], "frame_start" / "frame_end": [int],
     "timestep_start" / "timestep_end": [float]}}, one list entry per window in the table's order, and with them, as the
     datasets' sample_info has them: "fps": [float] and "mouth_open": [int64 [groups]] for ABAW tables, "vad_info": [str, the entry
-    as JSON] for AFEW tables.  A file without windows never reaches the reference's loop: it has no entry."""
-    res = run_corpus(engine, files, windows, sr, max_w_len, mode, windows_per_pass, features=True)
+    as JSON] for AFEW tables.  A file without windows never reaches the reference's loop: it has no entry.  `transform`: as
+    run_corpus takes it."""
+    res = run_corpus(engine, files, windows, sr, max_w_len, mode, windows_per_pass, features=True, transform=transform)
     probs, feats = res.probs.cpu().numpy(), res.features.cpu().numpy()
     out = {}
     for f, (name, tab) in enumerate(zip(res.names, windows)):

@@ -1,7 +1,8 @@
 // Fitting the audio classifier head (feature_downsample, Linear F -> C) on extracted features: the train phase of
 // NetTrainer.run (src/audio/net_trainer/net_trainer.py:357-467, 574-604; src/audio/train_c_audio.py:236-260) for the last layer
 // alone, and the logits of a feature table under many fitted heads.  Definitions: include/avcer_hip.h avcer_head_fit,
-// avcer_head_apply; stated in numpy float64 by avcer_amd/head_fit.py (head_fit_numpy), which referees tests/test_gpu_head_fit.py.
+// avcer_head_fit_views (an epoch's rows from one of several tables; one body, avcer_head_fit is its views = 1), avcer_head_apply;
+// stated in numpy float64 by avcer_amd/head_fit.py (head_fit_numpy), which referees tests/test_gpu_head_fit.py.
 //
 // avcer_head_fit: ONE launch, one workgroup of 256 threads per run, nothing shared between workgroups.  A step is half a
 // megaflop and waits for the step before it, so a run is launch-bound in any framework; here the whole run -- every epoch, every
@@ -39,6 +40,7 @@ constexpr int HF_HYPER = AVCER_HEAD_HYPER;
 
 struct HeadFitArgs {
     const float* feats;
+    const int32_t* view;  // [k_runs, epochs]: the table of feats [views, n, f] an epoch reads, or null: table 0
     const int32_t* targets;
     const double* hyper;
     const float* class_w;
@@ -51,7 +53,7 @@ struct HeadFitArgs {
     float* b_hist;
     float* batch_loss;
     double* epoch_loss;
-    int n, f, c, epochs, bsz, n_batches;
+    int n, f, c, epochs, bsz, n_batches, views;
 };
 
 // three columns of 256 partial sums folded in halves: v[k] of EVERY thread becomes the column's sum (block_fold of losses.hip in f32)
@@ -71,9 +73,10 @@ __device__ __forceinline__ void fold3(float (&v)[3], float* sh) {
     __syncthreads();
 }
 
-// the J feature values of batch row b this thread owns: the row itself, or its mixup with the row at the drawn position
+// the J feature values of batch row b this thread owns, from the epoch's table `feats`: the row itself, or its mixup with the row
+// at the drawn position
 template <int J>
-__device__ __forceinline__ void load_row(const HeadFitArgs& a, const int* row_sh, const int* mix_sh, int b, bool mix, float lam, float onem,
+__device__ __forceinline__ void load_row(const HeadFitArgs& a, const float* feats, const int* row_sh, const int* mix_sh, int b, bool mix, float lam, float onem,
                                          float (&x)[J]) {
     const int t = threadIdx.x;
     const int r = row_sh[b];
@@ -83,9 +86,9 @@ __device__ __forceinline__ void load_row(const HeadFitArgs& a, const int* row_sh
         const int f = t + HF_THREADS * j;
         float v = 0.0f;
         if (f < a.f) {
-            v = r >= 0 ? a.feats[(long)r * a.f + f] : NAN;
+            v = r >= 0 ? feats[(long)r * a.f + f] : NAN;
             if (mix) {
-                const float v2 = r2 >= 0 ? a.feats[(long)r2 * a.f + f] : NAN;
+                const float v2 = r2 >= 0 ? feats[(long)r2 * a.f + f] : NAN;
                 v = lam * v + onem * v2;  // net_trainer.py:602 in f32
             }
         }
@@ -140,6 +143,10 @@ __global__ void __launch_bounds__(HF_THREADS) head_fit_kernel(HeadFitArgs a) {
 
     for (int e = 0; e < a.epochs; ++e) {
         double running = 0.0;
+        // the epoch's table of feature rows; a view out of range makes every row of the epoch invalid
+        const int view = a.view ? a.view[run * a.epochs + e] : 0;
+        const bool view_ok = view >= 0 && view < a.views;
+        const float* feats = a.feats + (view_ok ? (long)view * n * F : 0L);
         for (int i = 0; i < a.n_batches; ++i) {
             const int r0 = i * a.bsz;
             const int nb = n - r0 < a.bsz ? n - r0 : a.bsz;
@@ -150,7 +157,7 @@ __global__ void __launch_bounds__(HF_THREADS) head_fit_kernel(HeadFitArgs a) {
             if (t < nb) {
                 const long at = (run * a.epochs + e) * (long)n + r0 + t;
                 const int r = a.order[at];
-                const bool ok = r >= 0 && r < n;
+                const bool ok = view_ok && r >= 0 && r < n;
                 row_sh[t] = ok ? r : -1;
                 tgt_sh[t] = ok ? a.targets[r] : -1;
                 if (mix) {
@@ -177,7 +184,7 @@ __global__ void __launch_bounds__(HF_THREADS) head_fit_kernel(HeadFitArgs a) {
                 for (int rr = 0; rr < RP; ++rr) {
                     const int b = p0 + rr;
                     float x[J];
-                    if (b < nb) load_row<J>(a, row_sh, mix_sh, b, mix, lam, onem, x);
+                    if (b < nb) load_row<J>(a, feats, row_sh, mix_sh, b, mix, lam, onem, x);
 #pragma unroll
                     for (int k = 0; k < CP; ++k) {
                         float s = 0.0f;
@@ -289,7 +296,7 @@ __global__ void __launch_bounds__(HF_THREADS) head_fit_kernel(HeadFitArgs a) {
                 for (int j = 0; j < J; ++j) dW[k][j] = 0.0f;
             for (int b = 0; b < nb; ++b) {
                 float x[J];
-                load_row<J>(a, row_sh, mix_sh, b, mix, lam, onem, x);
+                load_row<J>(a, feats, row_sh, mix_sh, b, mix, lam, onem, x);
                 const float4* g4 = reinterpret_cast<const float4*>(lg + b * CP);
 #pragma unroll
                 for (int k4 = 0; k4 < CP / 4; ++k4) {
@@ -408,10 +415,11 @@ bool hf_finite(double v) { return v == v && v < 1.0e300 && v > -1.0e300; }
 
 }  // namespace
 
-extern "C" int avcer_head_fit(avcer_ctx* ctx, const float* feats, const int32_t* targets, int64_t n, int f, int c, int k_runs, int epochs,
-                              int batch_size, const double* hyper, double* hyper_dev, const float* class_w, const float* w0,
-                              const float* b0, const int32_t* order, const float* mix_lam, const int32_t* mix_index, float* w_hist,
-                              float* b_hist, float* batch_loss, double* epoch_loss, avcer_stream_t stream) {
+extern "C" int avcer_head_fit_views(avcer_ctx* ctx, const float* feats, int views, const int32_t* view, const int32_t* targets, int64_t n,
+                                    int f, int c, int k_runs, int epochs, int batch_size, const double* hyper, double* hyper_dev,
+                                    const float* class_w, const float* w0, const float* b0, const int32_t* order, const float* mix_lam,
+                                    const int32_t* mix_index, float* w_hist, float* b_hist, float* batch_loss, double* epoch_loss,
+                                    avcer_stream_t stream) {
     if (!ctx) return AVCER_EINVAL;
     if (n < 1 || n > AVCER_HEAD_MAX_ROWS || c < 2 || c > AVCER_LOSS_MAX_CLASSES || f < 64 || f > AVCER_HEAD_MAX_FEATURES || f % 64 != 0 ||
         (long)c * f > AVCER_HEAD_MAX_STATE || batch_size < 1 || batch_size > AVCER_HEAD_MAX_BATCH || epochs < 1 ||
@@ -421,6 +429,9 @@ extern "C" int avcer_head_fit(avcer_ctx* ctx, const float* feats, const int32_t*
                        "%d (1..%d), %d epochs (1..%d), %d runs (1..%d)",
                        (long long)n, (long long)AVCER_HEAD_MAX_ROWS, f, AVCER_HEAD_MAX_FEATURES, c, AVCER_LOSS_MAX_CLASSES,
                        AVCER_HEAD_MAX_STATE, batch_size, AVCER_HEAD_MAX_BATCH, epochs, AVCER_HEAD_MAX_EPOCHS, k_runs, AVCER_HEAD_MAX_RUNS);
+    if (views < 1 || views > AVCER_HEAD_MAX_ROWS / n)
+        return set_err(ctx, AVCER_EINVAL, "head fit: %d views of %lld rows (views >= 1, views * rows <= %lld)", views, (long long)n,
+                       (long long)AVCER_HEAD_MAX_ROWS);
     if (!feats || !targets || !hyper || !hyper_dev || !class_w || !w0 || !b0 || !order || !w_hist || !b_hist || !batch_loss || !epoch_loss)
         return set_err(ctx, AVCER_EINVAL, "head fit: null buffer");
     const long n_batches = ((long)n + batch_size - 1) / batch_size;
@@ -443,14 +454,22 @@ extern "C" int avcer_head_fit(avcer_ctx* ctx, const float* feats, const int32_t*
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(ctx, hipMemcpyAsync(hyper_dev, hyper, sizeof(double) * HF_HYPER * (size_t)k_runs, hipMemcpyHostToDevice, st));
-    HeadFitArgs a{feats,   targets, hyper_dev,  class_w,    w0,     b0, order, mix_lam, mix_index, w_hist,
-                  b_hist,  batch_loss, epoch_loss, (int)n,  f,      c,  epochs, batch_size, (int)n_batches};
+    HeadFitArgs a{feats,  view,       targets,    hyper_dev, class_w, w0, b0,     order,      mix_lam,        mix_index, w_hist,
+                  b_hist, batch_loss, epoch_loss, (int)n,    f,       c,  epochs, batch_size, (int)n_batches, views};
     if (c <= 8)
         launch_fit<8>(a, k_runs, st);
     else
         launch_fit<16>(a, k_runs, st);
     CHECK_LAUNCH(ctx, "head fit");
     return AVCER_OK;
+}
+
+extern "C" int avcer_head_fit(avcer_ctx* ctx, const float* feats, const int32_t* targets, int64_t n, int f, int c, int k_runs, int epochs,
+                              int batch_size, const double* hyper, double* hyper_dev, const float* class_w, const float* w0,
+                              const float* b0, const int32_t* order, const float* mix_lam, const int32_t* mix_index, float* w_hist,
+                              float* b_hist, float* batch_loss, double* epoch_loss, avcer_stream_t stream) {
+    return avcer_head_fit_views(ctx, feats, 1, nullptr, targets, n, f, c, k_runs, epochs, batch_size, hyper, hyper_dev, class_w, w0, b0,
+                                order, mix_lam, mix_index, w_hist, b_hist, batch_loss, epoch_loss, stream);
 }
 
 extern "C" int avcer_head_apply(avcer_ctx* ctx, const float* feats, const float* w, const float* b, int64_t m, int f, int c, int heads,

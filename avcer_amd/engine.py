@@ -730,8 +730,39 @@ class Engine:
                                                  bsz, _ptr(row), _ptr(batch), _ptr(epoch), _ptr(ticket), self._stream()))
         return row, batch, epoch
 
+    def wave_augment(self, chunks, recs, min_snr: float = 1e-4, max_snr: float = 5e-3, noise=None, return_std: bool = False):
+        """The reference's waveform augmentations on padded windows, IN PLACE (include/avcer_hip.h avcer_wave_augment;
+        wave_augmentation.py:8-108): chunks f32 [n, win], a contiguous device tensor as Engine.audio_chunks(padding="constant")
+        returns it; recs: a HOST array of augment.REC records [n] (kind, ratio, u, key; augment.draw_plan makes them); noise f32
+        [n, win] or None: added to the windows of kind 2 in place of the generated noise.  Returns chunks, and with `return_std` also
+        the f32 [n] standard deviations the kernel took for its kind-2 windows (NaN elsewhere).  Shapes that disagree raise
+        ValueError; limits are the library's (AvcerError).  No host synchronisation behind the upload of the records."""
+        from .augment import REC
+
+        if not (isinstance(chunks, torch.Tensor) and chunks.is_cuda and chunks.dtype == torch.float32 and chunks.dim() == 2
+                and chunks.is_contiguous()):
+            raise ValueError("wave_augment: chunks must be a contiguous float32 device tensor [n, win] (it is changed in place)")
+        n, win = int(chunks.shape[0]), int(chunks.shape[1])
+        rc = np.ascontiguousarray(recs)
+        if rc.dtype != REC or rc.shape != (n,):
+            raise ValueError(f"wave_augment: {n} records of augment.REC expected, got {rc.dtype} {rc.shape}")
+        nz = None
+        if noise is not None:
+            nz = self._dev(noise, torch.float32)
+            if tuple(nz.shape) != (n, win):
+                raise ValueError(f"wave_augment: noise [{n}, {win}] expected, got {tuple(nz.shape)}")
+        std = torch.full((n,), float("nan"), device=self.device) if return_std else None
+        if n:
+            recs_dev = self._new(n * REC.itemsize, dtype=torch.uint8)
+            part_len = 4096 * -(-win // (1 << 20))             # include/avcer_hip.h: CH and P of avcer_wave_augment
+            used = nz is None and bool((rc["kind"] == 2).any())  # only kind 2 with the generated noise takes a std
+            parts = self._new(n * -(-win // part_len) * 2 if used else 1, dtype=torch.float64)
+            self._check(self.lib.avcer_wave_augment(self.ctx, _ptr(chunks), n, win, rc.ctypes.data_as(C.c_void_p), _ptr(recs_dev),
+                                                    float(min_snr), float(max_snr), _ptr(nz), _ptr(parts), _ptr(std), self._stream()))
+        return (chunks, std) if return_std else chunks
+
     def head_fit(self, feats, targets, hyper, class_w, w0, b0, order, mix_lam=None, mix_index=None, epochs: int = 1,
-                 batch_size: int = 64):
+                 batch_size: int = 64, view=None):
         """K runs of fitting the classifier head, all epochs, in one launch (include/avcer_hip.h avcer_head_fit;
         net_trainer.py:357-467, 574-604).  feats f32 [n, F] (a device tensor stays where it is), targets [n] in [0, C); hyper: a
         HOST float64 [K, 12] table (kind, label_smoothing, gamma, lr, beta1, beta2, eps, t0, eta_min, mixup, first_epoch, 0);
@@ -739,13 +770,26 @@ class Engine:
         [K, epochs, n] or both None.  head_fit.fit_heads builds and validates these tables: this call checks shapes only, and the
         kernel turns a row number, position or target out of range into NaN.  Returns (w_hist f32 [K, epochs, C, F], b_hist f32
         [K, epochs, C], batch_loss f32 [K, epochs, n_batches], epoch_loss f64 [K, epochs]) on the device.  Shapes that disagree
-        raise ValueError; limits are the library's (AvcerError).  No host synchronisation behind the upload of the tables."""
+        raise ValueError; limits are the library's (AvcerError).  No host synchronisation behind the upload of the tables.
+        feats f32 [V, n, F] with view int32 [K, epochs]: epoch e of run r takes its rows from feats[view[r, e]] (avcer_head_fit_views;
+        a view out of range turns its epoch into NaN)."""
         x = self._dev(feats, torch.float32)
         t = self._dev(targets, torch.int32)
         hy = np.ascontiguousarray(np.asarray(hyper, dtype=np.float64))
-        if x.dim() != 2 or t.dim() != 1 or int(t.shape[0]) != int(x.shape[0]) or hy.ndim != 2 or hy.shape[1] != 12:
-            raise ValueError(f"head_fit: feats [n, F], targets [n] and hyper [K, 12] expected, got {tuple(x.shape)}, {tuple(t.shape)}, {hy.shape}")
-        n, f, k, ep, bsz = int(x.shape[0]), int(x.shape[1]), int(hy.shape[0]), int(epochs), int(batch_size)
+        views = None
+        if x.dim() == 3 and x.shape[0] >= 1:
+            views, x = int(x.shape[0]), x.reshape(-1, x.shape[2])
+        elif view is not None:
+            raise ValueError("head_fit: view comes with feats [V, n, F]")
+        if x.dim() != 2 or t.dim() != 1 or int(t.shape[0]) * (views or 1) != int(x.shape[0]) or hy.ndim != 2 or hy.shape[1] != 12:
+            raise ValueError(f"head_fit: feats [n, F] or [V, n, F], targets [n] and hyper [K, 12] expected, got {tuple(np.shape(feats))}, "
+                             f"{tuple(t.shape)}, {hy.shape}")
+        n, f, k, ep, bsz = int(t.shape[0]), int(x.shape[1]), int(hy.shape[0]), int(epochs), int(batch_size)
+        vw = None
+        if views is not None:
+            vw = self._dev(np.zeros((k, ep), np.int32) if view is None else view, torch.int32)
+            if tuple(vw.shape) != (k, ep):
+                raise ValueError(f"head_fit: view [{k}, {ep}] expected, got {tuple(vw.shape)}")
         w = self._dev(w0, torch.float32)
         if w.dim() != 3 or int(w.shape[0]) != k or int(w.shape[2]) != f:
             raise ValueError(f"head_fit: w0 [{k}, C, {f}] expected, got {tuple(w.shape)}")
@@ -765,9 +809,12 @@ class Engine:
                                  f"{tuple(lam.shape)}, {tuple(idx.shape)}")
         w_hist, b_hist, batch_loss = self._new(k, ep, c, f), self._new(k, ep, c), self._new(k, ep, n_batches)
         epoch_loss, hy_dev = self._new(k, ep, dtype=torch.float64), self._new(k, 12, dtype=torch.float64)
-        self._check(self.lib.avcer_head_fit(self.ctx, _ptr(x), _ptr(t), n, f, c, k, ep, bsz, hy.ctypes.data_as(C.c_void_p), _ptr(hy_dev),
-                                            _ptr(cw), _ptr(w), _ptr(b), _ptr(od), _ptr(lam), _ptr(idx), _ptr(w_hist), _ptr(b_hist),
-                                            _ptr(batch_loss), _ptr(epoch_loss), self._stream()))
+        tail = (n, f, c, k, ep, bsz, hy.ctypes.data_as(C.c_void_p), _ptr(hy_dev), _ptr(cw), _ptr(w), _ptr(b), _ptr(od), _ptr(lam), _ptr(idx),
+                _ptr(w_hist), _ptr(b_hist), _ptr(batch_loss), _ptr(epoch_loss), self._stream())
+        if views is None:
+            self._check(self.lib.avcer_head_fit(self.ctx, _ptr(x), _ptr(t), *tail))
+        else:
+            self._check(self.lib.avcer_head_fit_views(self.ctx, _ptr(x), views, _ptr(vw), _ptr(t), *tail))
         return w_hist, b_hist, batch_loss, epoch_loss
 
     def head_apply(self, feats, w, b, out=None):

@@ -3,6 +3,8 @@
     head_fit_numpy      the statement: NetTrainer.iterate_model (net_trainer.py:357-467) with mixup_data (574-604) and the losses,
                         torch.optim.Adam and CosineAnnealingWarmRestarts of train_c_audio.py:236-260, for `feature_downsample`
                         (Linear F -> C) alone, in numpy float64
+    augmented_views     the features of a corpus under V draws of the reference's waveform augmentation (avcer_amd/augment.py),
+                        f32 [V, n, F]; head_fit_numpy and fit_heads take them, HeadRun.view says which view an epoch reads
     fit_heads           the same on the device: K runs -- seeds, rates, losses, mixup settings -- in ONE avcer_head_fit launch,
                         one workgroup a run (csrc/head_fit.hip)
     make_order / make_mixup   the random draws of a run, made on the host
@@ -10,12 +12,13 @@
                         validate.best_epoch
     write_checkpoint    the trainer's epoch_N.pth with the fitted head in a base checkpoint's place
 
-The chain is audio_corpus.extract_features -> fit_heads -> select -> write_checkpoint -> validate.validate_checkpoints.
+The chain is audio_corpus.extract_features (or augmented_views) -> fit_heads -> select -> write_checkpoint ->
+validate.validate_checkpoints.
 
 Where this departs from the reference, on purpose: the reference trains the conv tail, tl1 / tl2 and the last 2-4 wav2vec2 blocks
 too, in train mode with dropout, and mixes WAVEFORMS.  Here everything below `feature_downsample` is frozen and in eval mode -- its
-output is extracted once --, and mixup mixes FEATURE rows.  This is linear probing of the reference's model with the reference's
-recipe; nothing in the inference routes calls it.
+output is extracted once (per augmented view, where the windows are augmented) --, and mixup mixes FEATURE rows.  This is linear
+probing of the reference's model with the reference's recipe; nothing in the inference routes calls it.
 
 The random numbers are not torch's: `make_order` and `make_mixup` draw from numpy's Generator, so a run here does not repeat the
 batches DataLoader(shuffle=True) and np.random.beta / torch.randperm would deal under the same seed.  The tables are arguments:
@@ -60,6 +63,7 @@ class HeadRun:
     eta_min: float = 1e-4
     mix_lam: object = None
     mix_index: object = None
+    view: object = None    # int [epochs]: which table of feats [V, n, F] epoch e takes its rows from; None: e % V
 
 
 class HeadFitRun(NamedTuple):
@@ -96,6 +100,8 @@ class _Packed(NamedTuple):
     order: np.ndarray        # int32 [K, epochs, n]
     mix_lam: Optional[np.ndarray]     # f32 [K, epochs, n_batches]
     mix_index: Optional[np.ndarray]   # int32 [K, epochs, n]
+    views: Optional[int] = None       # V of feats [V, n, F]; None: feats [n, F]
+    view: Optional[np.ndarray] = None  # int32 [K, epochs], with `views`
 
 
 def _is_int(v, lo: int) -> bool:
@@ -104,9 +110,10 @@ def _is_int(v, lo: int) -> bool:
 
 def _pack(feats_shape, targets, runs: Sequence[HeadRun], epochs, batch_size, first_epoch) -> _Packed:
     """Every argument check of head_fit_numpy and fit_heads, before any work, and the runs as the tables avcer_head_fit takes."""
-    if len(feats_shape) != 2 or feats_shape[0] < 1:
-        raise ValueError(f"features [n, F] with n >= 1 expected, got {tuple(feats_shape)}")
-    n, f = int(feats_shape[0]), int(feats_shape[1])
+    if len(feats_shape) not in (2, 3) or min(feats_shape[:-1]) < 1:
+        raise ValueError(f"features [n, F] or [V, n, F] with n >= 1 (and V >= 1) expected, got {tuple(feats_shape)}")
+    views = int(feats_shape[0]) if len(feats_shape) == 3 else None
+    n, f = int(feats_shape[-2]), int(feats_shape[-1])
     if not _is_int(epochs, 1):
         raise ValueError(f"epochs must be an integer >= 1, got {epochs!r}")
     if not _is_int(batch_size, 1) or batch_size > MAX_BATCH:
@@ -133,7 +140,16 @@ def _pack(feats_shape, targets, runs: Sequence[HeadRun], epochs, batch_size, fir
     mix_lam = np.ones((len(runs), epochs, n_batches), np.float32) if any_mix else None
     mix_index = np.zeros((len(runs), epochs, n), np.int32) if any_mix else None
     identity = np.arange(n, dtype=np.int64)
+    view = None if views is None else np.tile(np.arange(epochs, dtype=np.int32) % views, (len(runs), 1))
     for k, r in enumerate(runs):
+        if r.view is not None:
+            vw = np.asarray(r.view)
+            if views is None:
+                raise ValueError(f"run {k}: view comes with features [V, n, F]")
+            if vw.shape != (epochs,) or not np.issubdtype(vw.dtype, np.integer) or vw.min() < 0 or vw.max() >= views:
+                raise ValueError(f"run {k}: view, integers [{epochs}] in 0 .. {views - 1}, expected, got {vw.dtype} {vw.shape}"
+                                 + (f" in [{vw.min()}, {vw.max()}]" if vw.size and np.issubdtype(vw.dtype, np.integer) else ""))
+            view[k] = vw
         kind, t, w = validate._check_loss(c, targets, r.kind, r.weights, r.label_smoothing, r.gamma, bsz)
         if t.shape[0] != n:
             raise ValueError(f"{n} feature rows and {t.shape[0]} targets")
@@ -181,7 +197,7 @@ def _pack(feats_shape, targets, runs: Sequence[HeadRun], epochs, batch_size, fir
             mix_lam[k], mix_index[k] = lam, idx
         hyper[k, :11] = (kind, float(r.label_smoothing), float(r.gamma), float(r.lr), float(r.betas[0]), float(r.betas[1]),
                          float(r.eps), float(r.t0), float(r.eta_min), 0.0 if r.mix_lam is None else 1.0, float(first_epoch))
-    return _Packed(n, f, c, epochs, bsz, n_batches, t, hyper, class_w, w0, b0, order, mix_lam, mix_index)
+    return _Packed(n, f, c, epochs, bsz, n_batches, t, hyper, class_w, w0, b0, order, mix_lam, mix_index, views, view)
 
 
 # ------------------------------------------------------------------------------------------------ the statement
@@ -243,9 +259,13 @@ def head_fit_numpy(feats, targets, runs: Sequence[HeadRun], epochs: int, batch_s
     be short), mixup if the run has it, logits = x W^T + b, the loss and its gradient (loss_and_grad), one Adam step with torch's
     formula, and the scheduler's rate for the next iteration (cosine_lr at first_epoch + e + i / iters).  ValueError before any
     work: shapes, targets outside [0, C), an order[e] that is no permutation of 0 .. n-1, a mix_index that is no permutation
-    inside a batch, a mix_lam outside [0, 1], non-finite hyper-parameters."""
+    inside a batch, a mix_lam outside [0, 1], non-finite hyper-parameters.
+    feats [V, n, F]: V views of the same n windows (augmented_views); epoch e of a run takes its rows, mixup partners included,
+    from feats[run.view[e]] (default e % V) -- targets, order and the mixup tables do not change with the view.  A view outside
+    0 .. V-1 raises ValueError.  [1, n, F] is [n, F]."""
     x_all = np.asarray(feats, dtype=np.float32)
     pk = _pack(x_all.shape, targets, runs, epochs, batch_size, first_epoch)
+    x_views = x_all if pk.views is not None else x_all[None]
     y_all = pk.targets.astype(np.int64)
     out = []
     for k, r in enumerate(runs):
@@ -258,6 +278,7 @@ def head_fit_numpy(feats, targets, runs: Sequence[HeadRun], epochs: int, batch_s
         lr, step = lr0, 0
         for e in range(pk.epochs):
             running = 0.0
+            x_all = x_views[0 if pk.view is None else pk.view[k, e]]
             for i in range(pk.n_batches):
                 rows = pk.order[k, e, i * pk.bsz:(i + 1) * pk.bsz].astype(np.int64)
                 x32, y = x_all[rows], y_all[rows]
@@ -315,14 +336,37 @@ def make_mixup(n: int, epochs: int, batch_size: int, alpha: float, seed: int):
 
 
 # ------------------------------------------------------------------------------------------------ device calls
+def augmented_views(engine, files, windows, views: int, spec, sr: int = 16000, max_w_len: int = 4, mode: Optional[int] = None,
+                    windows_per_pass: int = 128):
+    """The features of a training corpus under `views` draws of the waveform augmentation: f32 [views, n, F] on the device.  View
+    v is audio_corpus.run_corpus(features=True, transform=spec with seed + v): the reference augments a window afresh every time
+    it is dealt (train_c_audio.py:112-119); here an epoch picks one of V extracted views (HeadRun.view).  ValueError before any
+    work: views < 1, a spec that is no augment.AugmentSpec, what run_corpus refuses."""
+    import dataclasses
+
+    import torch
+
+    from . import audio_corpus, augment
+
+    if isinstance(views, bool) or not isinstance(views, (int, np.integer)) or views < 1:
+        raise ValueError(f"views must be an integer >= 1, got {views!r}")
+    if not isinstance(spec, augment.AugmentSpec):
+        raise ValueError(f"augmented_views: spec is an augment.AugmentSpec, got {type(spec).__name__}")
+    plan = audio_corpus.plan_corpus(engine, files, windows, sr, max_w_len, windows_per_pass)
+    return torch.stack([audio_corpus.run_corpus(engine, files, windows, sr, max_w_len, mode, windows_per_pass, features=True, plan=plan,
+                                                transform=dataclasses.replace(spec, seed=int(spec.seed) + v)).features
+                        for v in range(int(views))])
+
+
 def fit_heads(engine, feats, targets, runs: Sequence[HeadRun], epochs: int, batch_size: int = 64, first_epoch: int = 1) -> HeadFit:
     """head_fit_numpy on the device, all runs in one launch (Engine.head_fit): feats [n, F] -- a device tensor, the `features` of
     audio_corpus.run_corpus, stays where it is --, targets [n] host integers.  The tables of the runs are checked on the host
     (ValueError as head_fit_numpy raises them, before anything is launched) and uploaded once.  Returns a HeadFit of device
-    tensors; nothing synchronises with the host."""
+    tensors; nothing synchronises with the host.  feats [V, n, F] and HeadRun.view: as head_fit_numpy takes them
+    (avcer_head_fit_views; [n, F] goes through avcer_head_fit as before)."""
     pk = _pack(tuple(feats.shape), targets, runs, epochs, batch_size, first_epoch)
     w_hist, b_hist, batch_loss, epoch_loss = engine.head_fit(feats, pk.targets, pk.hyper, pk.class_w, pk.w0, pk.b0, pk.order,
-                                                             pk.mix_lam, pk.mix_index, pk.epochs, pk.bsz)
+                                                             pk.mix_lam, pk.mix_index, pk.epochs, pk.bsz, view=pk.view)
     return HeadFit(w_hist, b_hist, batch_loss, epoch_loss, int(first_epoch))
 
 

@@ -113,7 +113,10 @@ enum {
  *      avcer_window_losses, avcer_ccc (validation of audio checkpoints: the epoch loss of a corpus's window logits and the
  *      concordance coefficient) joined under 8 the same way: two more symbols, nothing that existed changed.
  *      avcer_head_fit, avcer_head_apply (fitting the audio classifier head on extracted features, many runs a launch, and the
- *      logits of a feature table under many heads) joined under 8 the same way: two more symbols, nothing that existed changed. */
+ *      logits of a feature table under many heads) joined under 8 the same way: two more symbols, nothing that existed changed.
+ *      avcer_wave_augment (the waveform augmentations of the training windows) and its record struct avcer_augment_rec, and
+ *      avcer_head_fit_views (avcer_head_fit with a table of feature rows per augmented view) joined under 8 the same way: two more
+ *      symbols, nothing that existed changed. */
 #define AVCER_ABI_VERSION 8
 int avcer_abi_version(void);
 /* Hash (16 hex digits) of the sources and headers this binary was compiled from, embedded at build time by
@@ -1017,6 +1020,65 @@ int avcer_head_fit(avcer_ctx* ctx, const float* feats, const int32_t* targets, i
  * 1 <= heads <= AVCER_HEAD_MAX_HEADS.  No host synchronisation. */
 int avcer_head_apply(avcer_ctx* ctx, const float* feats, const float* w, const float* b, int64_t m, int f, int c, int heads,
                      float* logits, avcer_stream_t stream);
+
+/* avcer_head_fit with the feature rows of every epoch taken from one of `views` tables: feats f32 [views, n, f] (the same windows
+ * under `views` draws of the waveform augmentation, avcer_wave_augment), view i32 [k_runs, epochs] (device): epoch e of run r reads
+ * row_b at feats[view[r, e], row_b, :], the mixup partner from the same table.  Targets, order and the mixup tables are per window
+ * and do not change with the view.  A view outside [0, views) turns every step of its epoch into NaN, as an invalid row does;
+ * callers validate beforehand.  Everything else is avcer_head_fit's, which is this call with views = 1 and view = NULL (all 0):
+ * one kernel body serves both.  Limits: those of avcer_head_fit and 1 <= views, views * n <= AVCER_HEAD_MAX_ROWS. */
+int avcer_head_fit_views(avcer_ctx* ctx, const float* feats, int views, const int32_t* view, const int32_t* targets, int64_t n, int f,
+                         int c, int k_runs, int epochs, int batch_size, const double* hyper, double* hyper_dev, const float* class_w,
+                         const float* w0, const float* b0, const int32_t* order, const float* mix_lam, const int32_t* mix_index,
+                         float* w_hist, float* b_hist, float* batch_loss, double* epoch_loss, avcer_stream_t stream);
+
+/* The waveform augmentations of the reference's training windows, in place on the padded windows avcer_audio_chunks(mode 1) wrote
+ * and in front of the forward's normalisation: one of PolarityInversion, WhiteNoise, Gain per window, chosen on the host.
+ *   ref: src/audio/train_c_audio.py:112-119 (RandomChoice([PolarityInversion(), WhiteNoise(), Gain()]) on every training window),
+ *        src/audio/augmentation/wave_augmentation.py:8-108
+ *        torchaudio==2.1.2 transforms/_transforms.py Vol.forward, functional/functional.py gain (third party, BSD-2): `waveform *
+ *        10 ** (gain_db / 20)`, the Python float as a float32 scalar, then torch.clamp(waveform, -1, 1)
+ * DEVICE: chunks f32 [n, win], changed in place; recs_dev [n] and parts f64 [n, P, 2] (P below; at least one element), scratch the call fills;
+ * noise f32 [n, win] or NULL; std_out f32 [n] or NULL.  HOST: recs [n], one avcer_augment_rec per window, checked here and copied
+ * in stream order.  Per window, by rec.kind:
+ *   AVCER_AUGMENT_NONE      nothing: the window's bytes are neither read nor written;
+ *   AVCER_AUGMENT_POLARITY  x = -x (torch.neg);
+ *   AVCER_AUGMENT_NOISE     std = torch.std(window): sqrt(sum((x - mean)^2) / (win - 1)) over all win samples, the padding zeros
+ *       among them, accumulated in f64 in an order that depends on win alone (below) and rounded to f32 (std_out[w], if given);
+ *       noise_std = lo + (hi - lo) * rec.u in f64, lo = min_snr * (double)std, hi = max_snr * (double)std (random.uniform);
+ *       x[i] = x[i] + (float)(noise_std * (double)z[i]), the sum in f32.  z[i] is lane i % 4 of Philox4x32-10 (Salmon et al.,
+ *       SC'11; multipliers 0xD2511F53, 0xCD9E8D57, key steps 0x9E3779B9, 0xBB67AE85) at counter (i / 4, 0) -- low word, high word,
+ *       0, 0 -- under key (rec.key & 0xffffffff, rec.key >> 32); lanes (0, 1) and (2, 3) are Box-Muller pairs: with words a, b
+ *       u1 = ((a >> 8) + 1) * 2^-24, u2 = (b >> 8) * 2^-24, r = sqrtf(-2 * logf(u1)), z = r * cospif(2 * u2), r * sinpif(2 * u2)
+ *       with the accurate f32 functions: |z| <= 5.77.  win == 1 gives std = 0 / 0 = NaN and a NaN window, as the reference does; a
+ *       window of zeros stays zeros; a NaN sample makes the window NaN.
+ *       With `noise`: x[i] = x[i] + noise[w, i] instead (the reference's own draw fed through); std is not computed.
+ *   AVCER_AUGMENT_GAIN      g = x * rec.ratio; x = g < -1 ? -1 : g > 1 ? 1 : g (torch.clamp: NaN stays).
+ * The order of std: the window is cut into P = ceil(win / CH) parts of CH = 4096 * ceil(win / 2^20) samples (P <= AVCER_AUGMENT_PARTS);
+ * a part's sum S_p: thread t of 256 adds the samples of its quads (four consecutive samples) t, t + 256, .. of the part upwards,
+ * the 256 partials fold in halves; M_p = sum((x - S_p / len_p)^2) the same way; then mean = fold(S_p) / win and
+ * sum((x - mean)^2) = fold(M_p + len_p * (S_p / len_p - mean)^2), both folds over 256 slots (those at and behind P hold 0) in halves.
+ * No atomics; two launches give the same bits; a window alone gives the bits it gives among n, whatever its place and however the
+ * windows are split into calls.  Two launches of n * P workgroups (one when no window is of kind 2 or `noise` is given, none when
+ * all are of kind 0).  n == 0 returns at once.
+ * Limits (AVCER_EINVAL beyond them, before any launch): 1 <= win <= AVCER_AUGMENT_MAX_WIN (what avcer_audio_chunks takes),
+ * n * win <= AVCER_AUGMENT_MAX_ELEMS, n * P < 2^31; min_snr <= max_snr, both finite; per window a known kind, u in [0, 1), a ratio
+ * that is a number.  One host-to-device copy of `recs` in stream order; no host synchronisation beyond it. */
+#define AVCER_AUGMENT_NONE 0
+#define AVCER_AUGMENT_POLARITY 1
+#define AVCER_AUGMENT_NOISE 2
+#define AVCER_AUGMENT_GAIN 3
+#define AVCER_AUGMENT_PARTS 256
+#define AVCER_AUGMENT_MAX_WIN 2147483647LL
+#define AVCER_AUGMENT_MAX_ELEMS 1099511627776LL
+typedef struct avcer_augment_rec {
+    int32_t kind;   /* AVCER_AUGMENT_* */
+    float ratio;    /* kind 3: 10 ** (gain_db / 20) rounded to float32 */
+    double u;       /* kind 2: the window's uniform draw in [0, 1) */
+    uint64_t key;   /* kind 2: the Philox key of the window's noise */
+} avcer_augment_rec;
+int avcer_wave_augment(avcer_ctx* ctx, float* chunks, int64_t n, int64_t win, const avcer_augment_rec* recs, avcer_augment_rec* recs_dev,
+                       double min_snr, double max_snr, const float* noise, double* parts, float* std_out, avcer_stream_t stream);
 
 /* The contraction kernel itself (implicit-GEMM convolution with fused epilogue), exported for kernel-level
  * parity tests and micro-benchmarks:  Y[m, n] = act(scale[n] * sum_k A[m,k] * W[n,k] + bias[n] (+ R[m,n]))
